@@ -7,7 +7,12 @@ Workload at N=1 is BASELINE.json configs[1]: [64,400,601] -> [64,400,86] (f0 1 +
 + 2D-conv critic, fp32, errtype WLSWGAN (run.py's default), lambda = 10.  With N ranks each rank works on its own
 64-sample shard (weak scaling, global batch 64*N) and the flat gradients are all-reduced over RCCL.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps (`value`, `ms_per_step`, `cycle_ms`) and prints the
+line; --dump-outputs DIR writes what the last timed step computes (losses, both networks' weights and moving averages) as DIR/<name>.npy,
+from the seeded state the timed region started from (see dump_outputs).
+With --full the side legs and checks run behind the headline loop as well, and add these objects:
+  variant_fp32_mfma_gemms, all_exact_work_reductions_off, critic_step_ms, generator_step_ms, lstm_graph, pcie_inclusive,
+  reference_shape, config2_bf16, config4_gated_dilated_causal_T2000 (each switched off by its --no-* option)
   roofline       SURVEY.md 8(d)'s quantity (round 4): the critic's whole 2D-conv stack, (149 C + 3) B T F s algorithmic bytes per critic
                  step over the summed HIP-event time of every conv2d launch of the step, against the 8 TB/s HBM roofline; the stack's
                  dominant kernel per launch is the sub-field `dominant_kernel` (the 4 -> 4 Conv2D layer kernel; --dtype bf16: the
@@ -17,7 +22,7 @@ Prints ONE JSON line (rank 0).  Extra objects:
                  gemm_bf16x6_kernel / gemm_bf16x1_kernel)
   roofline_lstm  the BLSTM recurrence (2 x T step launches per generator step: by time in the loop the top kernel), fp32 MFMA peak
   cpu_baseline   the CPU oracle (PyTorch-CPU fp32 restatement of the reference path) on a bounded sample
-With more than one rank: `allreduce_ms` (both buckets, backend, the exposed -- not overlapped -- update time per critic step).
+With more than one rank and --full: `allreduce_ms` (both buckets, backend, the exposed -- not overlapped -- update time per critic step).
 --graph-critic / --graph-generator {on,off} pin the form of each step kind instead of the 'tune' timing comparison.
 """
 from __future__ import print_function
@@ -72,7 +77,9 @@ def parse():
     ap.add_argument('--no-variants', action='store_true', help='skip the extra timed loop of the fp32-MFMA context-Conv1D variant')
     ap.add_argument('--no-host-leg', action='store_true', help='skip the PCIe-inclusive leg (host batches through the prefetcher)')
     ap.add_argument('--cpu-batch', type=int, default=32)
-    ap.add_argument('--side-legs', action='store_true', help='with --gpus N > 1: also run the side legs (variants, reference shape, bf16, gated, host-fed); by default a multi-GPU run prints the headline loop, the two step times and the all-reduce times only')
+    ap.add_argument('--side-legs', action='store_true', help='with --full and --gpus N > 1: also run the side legs (variants, reference shape, bf16, gated, host-fed); by default a multi-GPU --full run prints the headline loop, the two step times and the all-reduce times only')
+    ap.add_argument('--full', action='store_true', help='after the headline loop also run the side legs and checks (variants, step times, roofline, host-fed, reference shape, bf16, gated, CPU baseline, all-reduce times); off by default: a plain run times the headline loop only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="after the timed steps write what the last one computes, from the seeded state in front of the timed region, as DIR/<name>.npy (float32): the losses device_step returns, both networks' weights and BatchNorm moving averages")
     return ap.parse_args()
 
 
@@ -435,6 +442,44 @@ def timed_loop(opt, batches, nsteps, warmup, dev, cycle=5):
     return dt, percentiles(cyc)
 
 
+def dump_outputs(opt, snap, batches, nsteps, outdir, write):
+    """--dump-outputs: what the timed path computes in its last step -- the two losses device_step returns (generator_loss only when
+    that step trains the generator) and the state it leaves: both networks' weights and their BatchNorm moving averages -- as float32
+    DIR/<name>.npy, so that two builds can be compared output for output (about 32 MB at the default geometry).
+    The default path's fp32 atomics (deterministic mode) give every step a rounding-level run-to-run spread, which Adam and
+    the GAN's training steps amplify: two runs are 1e-3 apart after 10 steps, percents after hundreds.  So the state the last timed
+    step started from is not the same in two runs, and the step is computed again after the timed region, from the state `snap` taken
+    in front of it (seeded weights, Adam moments, moving averages, the device's random stream: the same in every run) -- the last timed
+    step's batch id and batch, the generator-update count it ran with (it picks the schedule), the same device_step and eager / hipGraph
+    forms.  Every rank runs it (the data-parallel update is a collective); `write` on rank 0."""
+    import numpy as np
+    import torch
+    bid = nsteps - 1
+    # the generator-update count the last timed step started from (10 critic steps per generator step below 25 and at every 500th,
+    # optimizertts_wgan.device_step): one less than the count the timed loop ended with if that step trained the generator
+    runs = lambda u: 10 if (u < 25) or (u % 500 == 0) else 5
+    gu = opt.generator_updates
+    if bid % runs(gu - 1) == 0:
+        gu -= 1
+    opt._state_restore(snap)
+    opt.generator_updates = gu
+    X, Y = batches[bid % len(batches)]
+    lc, lg = opt.device_step(bid, X, Y)
+    opt.wait_updates()
+    torch.cuda.synchronize()
+    if not write:
+        return
+    arrays = [('critic_loss', lc), ('generator_loss', lg),
+              ('critic_weights', opt.critic_opti.flat.flat), ('generator_weights', opt.gen_opti.flat.flat)]
+    for name, net in (('critic', opt.critic_net), ('generator', opt._model.kerasmodel)):
+        bufs = [b.detach().reshape(-1) for b in net.buffers() if b.numel() > 0 and b.is_floating_point()]
+        arrays.append((name + '_moving_averages', torch.cat(bufs) if bufs else None))
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays:
+        if t is not None:
+            np.save(os.path.join(outdir, name + '.npy'), t.detach().to(torch.float32).reshape(-1).cpu().numpy())
+
+
 def main():
     args = parse()
     world_env = int(os.environ.get('WORLD_SIZE', '0'))
@@ -453,6 +498,12 @@ def main():
         # the first real multi-GPU run should print its line quickly: no side legs (each builds optimisers of its own with their
         # own broadcasts / all-reduces) -- `--side-legs` brings them back
         args.no_variants = args.no_unreduced = args.no_host_leg = args.no_reference_shape = args.no_bf16_leg = args.no_gated_leg = True
+    if not args.full:
+        # a plain run: the headline loop and nothing else (every side leg, timing and check below is --full's)
+        args.no_variants = args.no_unreduced = args.no_host_leg = args.no_reference_shape = args.no_bf16_leg = args.no_gated_leg = True
+        args.no_roofline = args.no_cpu_baseline = True
+    # the networks' initial weights (numpy) and the device's random stream (the gradient penalty's interpolation): the same from run to run
+    backend_hip.set_random_seed(123)
     spec, nm = 65, 20
     cfg, voc, mod, crit, opt = build_optimizer(args, args.ctx, spec, nm, args.batch, args.errtype)
     par_streams = bool(cfg.train_wgan_parallel_streams)
@@ -469,7 +520,12 @@ def main():
                        'mode': cfg.train_wgan_hipgraph, 'pinned': {'critic': cfg.train_wgan_graph_critic, 'generator': cfg.train_wgan_graph_generator},
                        'form_with_more_than_one_rank': 'split graph (forward + backward captured; all-reduce + Adam eager behind it)' if world > 1 else None,
                        'tuning_ms': {k[0]: {kk: (round(vv, 3) if isinstance(vv, float) else vv) for kk, vv in v.items()} for k, v in opt._graph_tuning.items()}}
+    # --dump-outputs: the training state in front of the priming, warm-up and timed steps (the seeded one), for dump_outputs
+    snap = opt._state_snapshot() if args.dump_outputs else None
     dt, cyc = timed_loop(opt, batches, args.steps, args.warmup, dev)
+    if snap is not None:
+        dump_outputs(opt, snap, batches, args.steps, args.dump_outputs, rank == 0)
+        del snap
     # (a batch that trains both networks may run as ONE graph: decided on the first such batch, inside the warm-up)
     hipgraph_choice['batch_that_trains_both_as_one_graph'] = bool(opt._graph_choice.get(('batch', tuple(batches[0][0].shape), tuple(batches[0][1].shape)), False))
     hipgraph_choice['tuning_ms'] = {k[0]: {kk: (round(vv, 3) if isinstance(vv, float) else vv) for kk, vv in v.items()} for k, v in opt._graph_tuning.items()}
@@ -512,58 +568,59 @@ def main():
                     'critic(fake) as two passes, the generator step recomputes its context Conv1D and waits for the BLSTM before the critic',
             'value': short * B * T * world / dtu, 'unit': 'frames/s', 'ms_per_step': dtu / short * 1e3, 'steps': short}
 
-    # separate timings of the two step kinds (eager or graph as configured) and the roofline leg.  Every rank runs them
+    # (--full) separate timings of the two step kinds (eager or graph as configured) and the roofline leg.  Every rank runs them
     # (the steps contain the gradient all-reduce: a collective only rank 0 entered would hang the job); rank 0 reports.
     X, Y = batches[0]
-    def timeit(fn, n):
-        fn(); torch.cuda.synchronize()
-        t = time.time()
-        for _ in range(n): fn()
-        torch.cuda.synchronize()
-        return (time.time() - t) / n * 1e3
-    graph_c, graph_g = bool(opt._use_graph(X, 'critic', Y)), bool(opt._use_graph(X, 'generator', Y))
-    extra['critic_step_ms'] = timeit((lambda: opt._graphed('critic', X, Y)) if graph_c else (lambda: opt.critic_step(X, Y)), 10)
-    extra['generator_step_ms'] = timeit((lambda: opt._graphed('generator', X, Y)) if graph_g else (lambda: opt.generator_step(X, Y)), 5)
-    import ctypes
-    from percivaltts_amd import _hip
-    st3 = [ctypes.c_ulonglong(0) for _ in range(3)]
-    _hip.lib().ptts_lstm_graph_stats(*[ctypes.byref(v) for v in st3])
-    extra['lstm_graph'] = {'replays': st3[0].value, 'captures': st3[1].value, 'plain_launch_fallbacks': st3[2].value,
-                           'what': "the BLSTM's 400-step recurrences (forward, backward) replayed as one hipGraph launch each"}
-    if world > 1:
-        # the two exchanges of a cycle, timed on their own (HIP events on the launch stream, max over ranks): all-reduce (sum) of
-        # the flat fp32 gradient bucket of each network
-        import torch.distributed as dist
-        def ar_ms(t, n=10):
-            parallel.allreduce_sum_(t); torch.cuda.synchronize(); parallel.barrier()
-            s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s_.record()
-            for _ in range(n): parallel.allreduce_sum_(t)
-            e_.record(); torch.cuda.synchronize()
-            return parallel.max_over_ranks(s_.elapsed_time(e_) / n, dev)
-        gc, gg = torch.zeros_like(opt.critic_opti.flat.grad), torch.zeros_like(opt.gen_opti.flat.grad)
-        extra['allreduce_ms'] = {'critic_grads': ar_ms(gc), 'generator_grads': ar_ms(gg), 'critic_bytes': gc.numel() * 4, 'generator_bytes': gg.numel() * 4,
-                                 'backend': dist.get_backend(), 'what': 'all-reduce(sum) of one flat fp32 gradient bucket per network, max over ranks'}
-        # what of the exchange + Adam is NOT hidden behind the next step: back-to-back steps with the update (on the communication
-        # stream, overlapped) against the same steps without it (gradients only)
-        def loop_ms(fn, n=10):
-            fn(); opt.wait_updates(); torch.cuda.synchronize(); parallel.barrier()
+    if args.full:
+        def timeit(fn, n):
+            fn(); torch.cuda.synchronize()
             t = time.time()
             for _ in range(n): fn()
-            opt.wait_updates(); torch.cuda.synchronize()
-            return parallel.max_over_ranks((time.time() - t) / n * 1e3, dev)
-        with_c = loop_ms((lambda: opt._graphed('critic', X, Y)) if graph_c else (lambda: opt.critic_step(X, Y)))
-        saved_update = opt._update
-        opt._update = lambda kind: None
-        try:
-            only_c = loop_ms((lambda: opt._graphed('critic', X, Y)) if graph_c else (lambda: opt._critic_grads(X, Y)))
-        finally:
-            opt._update = saved_update
-        extra['allreduce_ms']['critic_update_exposed_ms_per_step'] = with_c - only_c
-        extra['allreduce_ms']['critic_step_ms_with_update'] = with_c
-        extra['allreduce_ms']['critic_step_ms_gradients_only'] = only_c
-        extra['allreduce_ms']['update_form'] = 'asynchronous (communication stream: event -> all_reduce(async_op) -> work.wait() -> Adam)' if opt._async() else 'synchronous'
-        extra['allreduce_ms']['critic_step_form'] = 'split hipGraph replay + eager update' if graph_c else 'eager launches'
+            torch.cuda.synchronize()
+            return (time.time() - t) / n * 1e3
+        graph_c, graph_g = bool(opt._use_graph(X, 'critic', Y)), bool(opt._use_graph(X, 'generator', Y))
+        extra['critic_step_ms'] = timeit((lambda: opt._graphed('critic', X, Y)) if graph_c else (lambda: opt.critic_step(X, Y)), 10)
+        extra['generator_step_ms'] = timeit((lambda: opt._graphed('generator', X, Y)) if graph_g else (lambda: opt.generator_step(X, Y)), 5)
+        import ctypes
+        from percivaltts_amd import _hip
+        st3 = [ctypes.c_ulonglong(0) for _ in range(3)]
+        _hip.lib().ptts_lstm_graph_stats(*[ctypes.byref(v) for v in st3])
+        extra['lstm_graph'] = {'replays': st3[0].value, 'captures': st3[1].value, 'plain_launch_fallbacks': st3[2].value,
+                               'what': "the BLSTM's 400-step recurrences (forward, backward) replayed as one hipGraph launch each"}
+        if world > 1:
+            # the two exchanges of a cycle, timed on their own (HIP events on the launch stream, max over ranks): all-reduce (sum) of
+            # the flat fp32 gradient bucket of each network
+            import torch.distributed as dist
+            def ar_ms(t, n=10):
+                parallel.allreduce_sum_(t); torch.cuda.synchronize(); parallel.barrier()
+                s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s_.record()
+                for _ in range(n): parallel.allreduce_sum_(t)
+                e_.record(); torch.cuda.synchronize()
+                return parallel.max_over_ranks(s_.elapsed_time(e_) / n, dev)
+            gc, gg = torch.zeros_like(opt.critic_opti.flat.grad), torch.zeros_like(opt.gen_opti.flat.grad)
+            extra['allreduce_ms'] = {'critic_grads': ar_ms(gc), 'generator_grads': ar_ms(gg), 'critic_bytes': gc.numel() * 4, 'generator_bytes': gg.numel() * 4,
+                                     'backend': dist.get_backend(), 'what': 'all-reduce(sum) of one flat fp32 gradient bucket per network, max over ranks'}
+            # what of the exchange + Adam is NOT hidden behind the next step: back-to-back steps with the update (on the communication
+            # stream, overlapped) against the same steps without it (gradients only)
+            def loop_ms(fn, n=10):
+                fn(); opt.wait_updates(); torch.cuda.synchronize(); parallel.barrier()
+                t = time.time()
+                for _ in range(n): fn()
+                opt.wait_updates(); torch.cuda.synchronize()
+                return parallel.max_over_ranks((time.time() - t) / n * 1e3, dev)
+            with_c = loop_ms((lambda: opt._graphed('critic', X, Y)) if graph_c else (lambda: opt.critic_step(X, Y)))
+            saved_update = opt._update
+            opt._update = lambda kind: None
+            try:
+                only_c = loop_ms((lambda: opt._graphed('critic', X, Y)) if graph_c else (lambda: opt._critic_grads(X, Y)))
+            finally:
+                opt._update = saved_update
+            extra['allreduce_ms']['critic_update_exposed_ms_per_step'] = with_c - only_c
+            extra['allreduce_ms']['critic_step_ms_with_update'] = with_c
+            extra['allreduce_ms']['critic_step_ms_gradients_only'] = only_c
+            extra['allreduce_ms']['update_form'] = 'asynchronous (communication stream: event -> all_reduce(async_op) -> work.wait() -> Adam)' if opt._async() else 'synchronous'
+            extra['allreduce_ms']['critic_step_form'] = 'split hipGraph replay + eager update' if graph_c else 'eager launches'
 
     if not args.no_roofline:
         extra.update(roofline_leg(opt, X, Y, args))

@@ -155,7 +155,7 @@ def test_bench_two_ranks_prints_one_line():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PTTS_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
+           '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full',
            '--batch', '4', '--frames', '40', '--no-cpu-baseline', '--no-gated-leg', '--no-reference-shape', '--no-bf16-leg']
     out = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
@@ -164,7 +164,7 @@ def test_bench_two_ranks_prints_one_line():
     res = json.loads(lines[0])
     assert res['n_gpus'] == 2 and res['config']['global_batch'] == 8 and res['scaling'] == 'weak'
     assert res['value'] > 0 and 'roofline' in res
-    # a multi-GPU run prints the headline loop, the two step times and the two all-reduce times -- no side legs unless --side-legs
+    # a multi-GPU --full run prints the headline loop, the two step times and the two all-reduce times -- no side legs unless --side-legs
     assert res['allreduce_ms']['backend'] == 'gloo' and res['allreduce_ms']['critic_grads'] > 0 and res['allreduce_ms']['generator_grads'] > 0
     assert 'critic_step_ms' in res and 'generator_step_ms' in res and 'variant_fp32_mfma_gemms' not in res and 'pcie_inclusive' not in res
     assert 'per rank' in res['config']['batchnorm_statistics'] and res['config']['collective_backend'] == 'gloo'

@@ -1,4 +1,4 @@
-LEGS="--no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline"
+LEGS="--full --no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline"
 for i in 1 2 3; do
 python3 bench.py $LEGS --steps 60 --warmup 15 2>/dev/null | python3 -c "
 import json,sys

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B on one box: the critic's context branch on a side stream beside the spectral stacks (cfg.train_wgan_ctx_stream)
 cd "$GRAFT_REPO_ROOT"
-LEGS="--no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline --no-roofline"
+LEGS="--full --no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline --no-roofline"
 for i in 1 2; do
 for v in 0 1; do
 PTTS_CTX_STREAM=$v python3 bench.py $LEGS --steps 60 --warmup 15 2>/dev/null | python3 -c "

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B on the GPU box: generator step with the BLSTM recurrences as hipGraph replays (PTTS_LSTM_GRAPH) and with the side branch's
 # nodes created last (PTTS_SIDE_DEFER: its backward chain is then enqueued first).  Prints value / critic / generator ms per setting.
-LEGS="--no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline"
+LEGS="--full --no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline"
 for dt in f32 bf16; do
 for g in 0 1; do for d in 0 1; do
   PTTS_LSTM_GRAPH=$g PTTS_SIDE_DEFER=$d python3 bench.py --dtype $dt $LEGS --steps 36 --warmup 12 2>/dev/null | python3 -c "

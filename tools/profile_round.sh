@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 # the same for BASELINE configs[2] (--dtype bf16)
 # the step forms are PINNED to what 'tune' picks outside the profiler (critic step replayed, generator step launched eagerly with its
 # forward one batch ahead): under rocprofv3 the timing comparison comes out differently, and the trace and the bench line must time ONE program
-LEGS="--no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline --graph-critic on --graph-generator off"
+LEGS="--full --no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline --graph-critic on --graph-generator off"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py $LEGS --steps 100 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
 echo "trace done" > $OUT/progress.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bf16 -- python3 bench.py --dtype bf16 $LEGS --steps 100 --warmup 20 > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err

@@ -21,7 +21,7 @@ def short(name):
 
 rows = list(csv.DictReader(open(max(glob.glob(src + '/trace/runc/*_kernel_stats.csv'), key=os.path.getmtime))))
 total = sum(float(r['TotalDurationNs']) for r in rows)
-lines = ['# rocprofv3 --kernel-trace --stats -- python bench.py (headline loop only: --no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline)   (round %s)' % tag,
+lines = ['# rocprofv3 --kernel-trace --stats -- python bench.py --full (headline loop only: --no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline)   (round %s)' % tag,
          '# total kernel time %.1f ms' % (total / 1e6),
          '%8s %12s %11s %11s %11s %6s  %s' % ('calls', 'total_us', 'avg_us', 'min_us', 'max_us', '%', 'kernel')]
 for r in rows[:40]:
@@ -35,7 +35,7 @@ bf = glob.glob(src + '/trace_bf16/runc/*_kernel_stats.csv')
 if bf:
     rows16 = list(csv.DictReader(open(max(bf, key=os.path.getmtime))))
     total16 = sum(float(r['TotalDurationNs']) for r in rows16)
-    l16 = ['# rocprofv3 --kernel-trace --stats -- python bench.py --dtype bf16 (headline loop only)   (round %s)' % tag,
+    l16 = ['# rocprofv3 --kernel-trace --stats -- python bench.py --full --dtype bf16 (headline loop only)   (round %s)' % tag,
            '# total kernel time %.1f ms' % (total16 / 1e6),
            '%8s %12s %11s %11s %11s %6s  %s' % ('calls', 'total_us', 'avg_us', 'min_us', 'max_us', '%', 'kernel')]
     for r in rows16[:40]:
