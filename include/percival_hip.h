@@ -546,6 +546,28 @@ int ptts_set_lstm_graph(int on);
 int ptts_lstm_graph_stats(unsigned long long* hits, unsigned long long* captures, unsigned long long* direct);
 int ptts_lstm_graph_clear(void);
 
+/* ---------------------------------------------------------------------------------------
+ * Keras GRU, reset_after = False (gates z, r, h; activation tanh, recurrent_activation
+ * hard_sigmoid hs(a) = clip(0.2a + 0.5, 0, 1), the TF 1.x default; networktts.py:101-114).
+ * ndir = 1: one direction, forwards; ndir = 2: kl.Bidirectional(concat), direction 0 forwards and
+ * direction 1 backwards in the SAME launches.  Any H >= 1 (padded tail tiles).
+ *   xproj [B,T,ndir*3H] = x.W_d + b_d per direction (ptts_gemm products);  U [ndir,H,3H]
+ *   h_out [B,T,ndir*H] (the Bidirectional concat layout), gates (post-nonlinearity z, r, hh)
+ *   [B,T,ndir*3H] and rh = r * h_{t-1} [B,T,ndir*H] are kept for the backward (rh is the
+ *   operand of the candidate's recurrent-weight gradient).
+ * Two launches per time step (r completes before (r*h).U_h starts); exact fp32 MFMA products
+ * against the recurrent kernel packed into the workspace; no device memory is allocated.
+ * ------------------------------------------------------------------------------------- */
+size_t ptts_gru_fwd_workspace_bytes(int B, int T, int H, int ndir);    /* packed recurrent kernel */
+int ptts_gru_fwd(const float* xproj, const float* U, float* h_out, float* gates, float* rh,
+                 void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, void* stream);
+/* dgates [B,T,ndir*3H] out: gradients w.r.t. the gate PRE-activations (hs' = 0.2 inside (0,1), 0
+ * where clipped, taken from the stored gate); dx, dW, dU and db follow from them as ptts_gemm
+ * products.  workspace: ptts_gru_bwd_workspace_bytes (packed U^T + the [ndir,B,H] carries) */
+size_t ptts_gru_bwd_workspace_bytes(int B, int T, int H, int ndir);
+int ptts_gru_bwd(const float* dh_out /*[B,T,ndir*H]*/, const float* U, const float* h_out, const float* gates,
+                 float* dgates, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

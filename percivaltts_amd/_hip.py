@@ -143,6 +143,10 @@ SIGNATURES = {
     'ptts_set_lstm_graph': (c_i, [c_i]),
     'ptts_lstm_graph_stats': (c_i, [c_p] * 3),
     'ptts_lstm_graph_clear': (c_i, []),
+    'ptts_gru_fwd_workspace_bytes': (c_sz, [c_i] * 4),
+    'ptts_gru_fwd': (c_i, [c_p] * 5 + [c_p, c_sz] + [c_i] * 4 + [c_p]),
+    'ptts_gru_bwd_workspace_bytes': (c_sz, [c_i] * 4),
+    'ptts_gru_bwd': (c_i, [c_p] * 5 + [c_p, c_sz] + [c_i] * 4 + [c_p]),
 }
 
 _lib = None

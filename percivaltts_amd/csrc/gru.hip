@@ -1,0 +1,308 @@
+// Keras GRU recurrence (reset_after = False; gates z, r, h; activation tanh, recurrent_activation hard_sigmoid, the TF 1.x
+// default that pGRU does not override), both directions of a Bidirectional wrapper advanced by the same launches.
+// Reference: networktts.py:101-114 (pGRU / pBGRU).
+//
+// The input projection x.W+b and every weight gradient are big products done outside (ops.gru); what is left here is the
+// T-sequential part.  The candidate's recurrent product (r * h_{t-1}).U_h needs the complete r, so a step is TWO launches:
+//   forward  A: z, r = hs(xp_zr + h_{t-1}.U_zr), rh = r * h_{t-1}         tiles of 16 samples x 16 of the 2H z|r columns
+//            B: hh = tanh(xp_h + rh.U_h), h_t = z h_{t-1} + (1 - z) hh     tiles of 16 samples x 16 units
+//   backward A': da_h = dh (1 - z)(1 - hh^2), d(rh) = da_h.U_h^T; dz, dr, da_zr and the elementwise part of dh_{t-1}
+//            B': dh_{t-1} += da_zr.U_zr^T  (K = 2H)
+// Every product is exact fp32 on v_mfma_f32_16x16x4_f32 against the recurrent kernel packed once per call (the layout of
+// lstm_pack_u_fwd_kernel: each lane's B operands of all k-steps contiguous), K split over the 4 waves of a workgroup and the
+// partial tiles summed through LDS in a fixed order.  Any H: K is padded to a multiple of 16 with zero weights, and the A
+// operands, columns and samples beyond H / 2H / B are predicated off.
+#include "common.h"
+
+namespace ptts {
+
+typedef float f32x4g __attribute__((ext_vector_type(4)));
+constexpr int GCH = 16;    // k-steps per register chunk: all loads of a chunk are issued before its first MFMA
+
+__host__ __device__ static inline int round16(int n) { return (n + 15) & ~15; }
+__host__ __device__ static inline int tiles16(int n) { return (n + 15) / 16; }
+
+__device__ __forceinline__ float hard_sigmoid(float a) { return fminf(fmaxf(0.2f * a + 0.5f, 0.f), 1.f); }
+// Derivative taken from the stored gate value: 0.2 strictly inside (0, 1), 0 where clipped.  At the ties a = +-2.5 (gate
+// exactly 0 or 1) TF's clip_by_value passes the gradient and this does not: a set of measure zero.
+__device__ __forceinline__ float hard_sigmoid_grad(float g) { return (g > 0.f && g < 1.f) ? 0.2f : 0.f; }
+
+// Upk[d][jt][w][lane][st] = U[d][k][c0 + col]  (trans = 0)   or   U[d][col][c0 + k]  (trans = 1),
+//   col = jt*16 + (lane & 15),  k = w*KP/4 + (lane >> 4)*KS + st,  KP = round16(K), KS = KP/16;  0 where k >= K or col >= N.
+// U [ndir][H][3H].
+__global__ void gru_pack_kernel(const float* __restrict__ U, float* __restrict__ Upk, int H, int ndir, int K, int N, int c0,
+                                int trans) {
+    const int KS = round16(K) / 16, NT = tiles16(N);
+    const long long G3 = 3LL * H;
+    const long long total = (long long)ndir * NT * 256 * KS;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        long long r = i;
+        const int st = (int)(r % KS); r /= KS;
+        const int lane = (int)(r % 64); r /= 64;
+        const int w = (int)(r % 4); r /= 4;
+        const int jt = (int)(r % NT);
+        const int d = (int)(r / NT);
+        const int k = w * 4 * KS + (lane >> 4) * KS + st, col = jt * 16 + (lane & 15);
+        float v = 0.f;
+        if (k < K && col < N)
+            v = trans ? U[((long long)d * H + col) * G3 + c0 + k] : U[((long long)d * H + k) * G3 + c0 + col];
+        Upk[i] = v;
+    }
+}
+
+// One wave's share of a 16 x 16 tile  D[sample r16][col] = sum_k A(k) . Bpk(k, col)  over k = kbase + st, st < KS, where
+// loadA(k) is this lane's A operand (sample b0 + (lane & 15)) and bp this lane's packed B operands.  Even and odd k-steps go
+// to two accumulators (half the dependent MFMA chain), added at the end: a fixed order, so the result is reproducible.
+// The wave's partial tile is left in red[sample * 16 + col].
+template <class LoadA>
+__device__ __forceinline__ void gru_wave_tile(const float* __restrict__ bp, int KS, int kbase, LoadA loadA, float* red) {
+    const int lane = threadIdx.x & 63, r16 = lane & 15, q = lane >> 4;
+    f32x4g acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    for (int s0 = 0; s0 < KS; s0 += GCH) {
+        float a[GCH], bv[GCH];
+#pragma unroll
+        for (int i = 0; i < GCH; ++i) {
+            const bool in = s0 + i < KS;
+            a[i] = in ? loadA(kbase + s0 + i) : 0.f;
+            bv[i] = in ? bp[s0 + i] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < GCH; i += 2) {
+            if (s0 + i < KS) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], bv[i], acc0, 0, 0, 0);
+            if (s0 + i + 1 < KS) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i + 1], bv[i + 1], acc1, 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[(q * 4 + r) * 16 + r16] = acc0[r] + acc1[r];
+}
+
+// Forward launch A of step s: grid (tiles16(2H), ceil(B/16), ndir), 256 threads.
+__global__ __launch_bounds__(256) void gru_fwd_zr_kernel(
+    const float* __restrict__ xproj, const float* __restrict__ Upk, const float* __restrict__ h_out, float* __restrict__ gates,
+    float* __restrict__ rh, int B, int T, int H, int ndir, int s) {
+    __shared__ float red[4][256];
+    // a latency chain that shares its CUs with the wide kernels of other streams: its waves go first at the issue arbiter
+    __builtin_amdgcn_s_setprio(3);
+    const int d = blockIdx.z;
+    const int t = d == 1 ? T - 1 - s : s, tp = d == 1 ? t + 1 : t - 1;
+    const int jt = blockIdx.x, b0 = blockIdx.y * 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
+    const int KS = round16(H) / 16, NT = tiles16(2 * H);
+    const long long G3 = 3LL * H, GG = ndir * G3, HH = (long long)ndir * H;
+    // epilogue inputs first: sample eb, column c of the z|r block
+    const int eb = b0 + (tid >> 4), c = jt * 16 + (tid & 15);
+    const bool epi = eb < B && c < 2 * H;
+    float xv = 0.f, hp = 0.f;
+    if (epi) {
+        xv = xproj[((long long)eb * T + t) * GG + d * G3 + c];
+        if (s > 0 && c >= H) hp = h_out[((long long)eb * T + tp) * HH + (long long)d * H + c - H];
+    }
+    if (s > 0) {
+        const int b = b0 + r16;
+        const bool bok = b < B;
+        const float* hrow = h_out + ((long long)(bok ? b : 0) * T + tp) * HH + (long long)d * H;
+        const float* bp = Upk + ((((long long)d * NT + jt) * 4 + wave) * 64 + lane) * KS;
+        gru_wave_tile(bp, KS, wave * 4 * KS + q * KS, [&](int k) { return bok && k < H ? hrow[k] : 0.f; }, red[wave]);
+        __syncthreads();
+    }
+    if (!epi) return;
+    float a = xv;
+    if (s > 0) a += red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    const float g = hard_sigmoid(a);
+    const long long row = (long long)eb * T + t;
+    gates[row * GG + d * G3 + c] = g;
+    if (c >= H) rh[row * HH + (long long)d * H + c - H] = g * hp;
+}
+
+// Forward launch B of step s: grid (tiles16(H), ceil(B/16), ndir), 256 threads.
+__global__ __launch_bounds__(256) void gru_fwd_h_kernel(
+    const float* __restrict__ xproj, const float* __restrict__ Upk, float* __restrict__ h_out, float* __restrict__ gates,
+    const float* __restrict__ rh, int B, int T, int H, int ndir, int s) {
+    __shared__ float red[4][256];
+    __builtin_amdgcn_s_setprio(3);
+    const int d = blockIdx.z;
+    const int t = d == 1 ? T - 1 - s : s, tp = d == 1 ? t + 1 : t - 1;
+    const int jt = blockIdx.x, b0 = blockIdx.y * 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
+    const int KS = round16(H) / 16, NT = tiles16(H);
+    const long long G3 = 3LL * H, GG = ndir * G3, HH = (long long)ndir * H;
+    const int eb = b0 + (tid >> 4), j = jt * 16 + (tid & 15);
+    const bool epi = eb < B && j < H;
+    const long long row = (long long)eb * T + t;
+    float xv = 0.f, z = 0.f, hp = 0.f;
+    if (epi) {
+        xv = xproj[row * GG + d * G3 + 2 * H + j];
+        z = gates[row * GG + d * G3 + j];
+        if (s > 0) hp = h_out[((long long)eb * T + tp) * HH + (long long)d * H + j];
+    }
+    if (s > 0) {      // at s = 0, rh = r * h_{-1} = 0
+        const int b = b0 + r16;
+        const bool bok = b < B;
+        const float* rrow = rh + ((long long)(bok ? b : 0) * T + t) * HH + (long long)d * H;
+        const float* bp = Upk + ((((long long)d * NT + jt) * 4 + wave) * 64 + lane) * KS;
+        gru_wave_tile(bp, KS, wave * 4 * KS + q * KS, [&](int k) { return bok && k < H ? rrow[k] : 0.f; }, red[wave]);
+        __syncthreads();
+    }
+    if (!epi) return;
+    float a = xv;
+    if (s > 0) a += red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    const float hh = tanhf(a);
+    gates[row * GG + d * G3 + 2 * H + j] = hh;
+    h_out[row * HH + (long long)d * H + j] = z * hp + (1.f - z) * hh;
+}
+
+// Backward launch A' of forward step s (launched for s = T-1 .. 0): grid (tiles16(H), ceil(B/16), ndir), 256 threads.
+// dh = dh_out[t] + carry (dh_{t} through the recurrence, left by B' of step s+1).  Each workgroup recomputes da_h over its
+// K range as the MFMA's A operand; for its own 16 units it writes dgates (z, r, h) and carry2 = dh z + d(rh) r.
+__global__ __launch_bounds__(256) void gru_bwd_h_kernel(
+    const float* __restrict__ dh_out, const float* __restrict__ Upk, const float* __restrict__ h_out,
+    const float* __restrict__ gates, float* __restrict__ dgates, const float* __restrict__ carry, float* __restrict__ carry2,
+    int B, int T, int H, int ndir, int s) {
+    __shared__ float red[4][256];
+    __builtin_amdgcn_s_setprio(3);
+    const int d = blockIdx.z;
+    const int t = d == 1 ? T - 1 - s : s, tp = d == 1 ? t + 1 : t - 1;
+    const int jt = blockIdx.x, b0 = blockIdx.y * 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
+    const int KS = round16(H) / 16, NT = tiles16(H);
+    const long long G3 = 3LL * H, GG = ndir * G3, HH = (long long)ndir * H;
+    const bool has_next = s < T - 1;
+    const int eb = b0 + (tid >> 4), j = jt * 16 + (tid & 15);
+    const bool epi = eb < B && j < H;
+    const long long row = (long long)eb * T + t;
+    float dh = 0.f, z = 0.f, r = 0.f, hh = 0.f, hp = 0.f;
+    if (epi) {
+        dh = dh_out[row * HH + (long long)d * H + j];
+        if (has_next) dh += carry[((long long)d * B + eb) * H + j];
+        const float* gp = gates + row * GG + d * G3;
+        z = gp[j]; r = gp[H + j]; hh = gp[2 * H + j];
+        if (s > 0) hp = h_out[((long long)eb * T + tp) * HH + (long long)d * H + j];
+    }
+    if (s > 0) {      // at s = 0, d(rh) only meets h_{-1} = 0 and no earlier step takes carry2
+        const int b = b0 + r16;
+        const bool bok = b < B;
+        const long long bs = bok ? b : 0;
+        const float* dhrow = dh_out + (bs * T + t) * HH + (long long)d * H;
+        const float* crow = carry + ((long long)d * B + bs) * H;
+        const float* grow = gates + (bs * T + t) * GG + d * G3;
+        const float* bp = Upk + ((((long long)d * NT + jt) * 4 + wave) * 64 + lane) * KS;
+        gru_wave_tile(bp, KS, wave * 4 * KS + q * KS, [&](int n) {
+            if (!(bok && n < H)) return 0.f;
+            float g = dhrow[n];
+            if (has_next) g += crow[n];
+            const float zn = grow[n], hn = grow[2 * H + n];
+            return g * (1.f - zn) * (1.f - hn * hn);
+        }, red[wave]);
+        __syncthreads();
+    }
+    if (!epi) return;
+    const float drh = s > 0 ? red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid] : 0.f;
+    const float da_h = dh * (1.f - z) * (1.f - hh * hh);      // the expression of the operand above: the same rounding
+    float* dg = dgates + row * GG + d * G3;
+    dg[j] = dh * (hp - hh) * hard_sigmoid_grad(z);
+    dg[H + j] = drh * hp * hard_sigmoid_grad(r);
+    dg[2 * H + j] = da_h;
+    carry2[((long long)d * B + eb) * H + j] = dh * z + drh * r;
+}
+
+// Backward launch B' of forward step s (s >= 1): carry = carry2 + da_zr.U_zr^T; grid (tiles16(H), ceil(B/16), ndir).
+__global__ __launch_bounds__(256) void gru_bwd_zr_kernel(
+    const float* __restrict__ Upk, const float* __restrict__ dgates, const float* __restrict__ carry2, float* __restrict__ carry,
+    int B, int T, int H, int ndir, int s) {
+    __shared__ float red[4][256];
+    __builtin_amdgcn_s_setprio(3);
+    const int d = blockIdx.z;
+    const int t = d == 1 ? T - 1 - s : s;
+    const int jt = blockIdx.x, b0 = blockIdx.y * 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
+    const int KS = round16(2 * H) / 16, NT = tiles16(H);
+    const long long G3 = 3LL * H, GG = ndir * G3;
+    const int eb = b0 + (tid >> 4), j = jt * 16 + (tid & 15);
+    const bool epi = eb < B && j < H;
+    const long long si = ((long long)d * B + eb) * H + j;
+    const float base = epi ? carry2[si] : 0.f;
+    const int b = b0 + r16;
+    const bool bok = b < B;
+    const float* grow = dgates + ((long long)(bok ? b : 0) * T + t) * GG + d * G3;
+    const float* bp = Upk + ((((long long)d * NT + jt) * 4 + wave) * 64 + lane) * KS;
+    gru_wave_tile(bp, KS, wave * 4 * KS + q * KS, [&](int n) { return bok && n < 2 * H ? grow[n] : 0.f; }, red[wave]);
+    __syncthreads();
+    if (!epi) return;
+    carry[si] = base + (red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
+}
+
+// floats of one packed operand: ndir x tiles16(N) x 256 lanes x KS
+static inline size_t packed_floats(int ndir, int K, int N) { return (size_t)ndir * tiles16(N) * 256 * (round16(K) / 16); }
+
+static void launch_pack(const float* U, float* Upk, int H, int ndir, int K, int N, int c0, int trans, hipStream_t st) {
+    const size_t total = packed_floats(ndir, K, N);
+    const int blocks = (int)(total / 256 + 1 < 1024 ? total / 256 + 1 : 1024);
+    hipLaunchKernelGGL(gru_pack_kernel, dim3(blocks), dim3(256), 0, st, U, Upk, H, ndir, K, N, c0, trans);
+}
+
+}  // namespace ptts
+
+using namespace ptts;
+
+extern "C" size_t ptts_gru_fwd_workspace_bytes(int B, int T, int H, int ndir) {
+    (void)B; (void)T;
+    if (H < 1 || ndir < 1) return 16;
+    return (packed_floats(ndir, H, 2 * H) + packed_floats(ndir, H, H)) * sizeof(float);
+}
+
+extern "C" int ptts_gru_fwd(const float* xproj, const float* U, float* h_out, float* gates, float* rh, void* workspace,
+                            size_t workspace_bytes, int B, int T, int H, int ndir, void* stream) {
+    PTTS_REQUIRE(xproj && U && h_out && gates && rh, "gru_fwd: null tensor");
+    PTTS_REQUIRE(B > 0 && T > 0 && H > 0 && (ndir == 1 || ndir == 2), "gru_fwd: bad dims B=%d T=%d H=%d ndir=%d", B, T, H, ndir);
+    const size_t need = ptts_gru_fwd_workspace_bytes(B, T, H, ndir);
+    if (!workspace || workspace_bytes < need) {
+        set_error("gru_fwd: workspace %zu < %zu", workspace_bytes, need);
+        return PTTS_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float* Uzr = (float*)workspace;                        // U[:, 0:2H]: K = H, N = 2H
+    float* Uh = Uzr + packed_floats(ndir, H, 2 * H);       // U[:, 2H:3H]: K = H, N = H
+    launch_pack(U, Uzr, H, ndir, H, 2 * H, 0, 0, st);
+    launch_pack(U, Uh, H, ndir, H, H, 2 * H, 0, st);
+    const dim3 gzr(tiles16(2 * H), tiles16(B), ndir), gh(tiles16(H), tiles16(B), ndir);
+    for (int s = 0; s < T; ++s) {
+        hipLaunchKernelGGL(gru_fwd_zr_kernel, gzr, dim3(256), 0, st, xproj, (const float*)Uzr, (const float*)h_out, gates, rh,
+                           B, T, H, ndir, s);
+        hipLaunchKernelGGL(gru_fwd_h_kernel, gh, dim3(256), 0, st, xproj, (const float*)Uh, h_out, gates, (const float*)rh,
+                           B, T, H, ndir, s);
+    }
+    return check_launch("gru_fwd");
+}
+
+extern "C" size_t ptts_gru_bwd_workspace_bytes(int B, int T, int H, int ndir) {
+    (void)T;
+    if (B < 1 || H < 1 || ndir < 1) return 16;
+    return (packed_floats(ndir, H, H) + packed_floats(ndir, 2 * H, H) + (size_t)2 * ndir * B * H) * sizeof(float);
+}
+
+extern "C" int ptts_gru_bwd(const float* dh_out, const float* U, const float* h_out, const float* gates, float* dgates,
+                            void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, void* stream) {
+    PTTS_REQUIRE(dh_out && U && h_out && gates && dgates, "gru_bwd: null tensor");
+    PTTS_REQUIRE(B > 0 && T > 0 && H > 0 && (ndir == 1 || ndir == 2), "gru_bwd: bad dims B=%d T=%d H=%d ndir=%d", B, T, H, ndir);
+    const size_t need = ptts_gru_bwd_workspace_bytes(B, T, H, ndir);
+    if (!workspace || workspace_bytes < need) {
+        set_error("gru_bwd: workspace %zu < %zu", workspace_bytes, need);
+        return PTTS_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float* UhT = (float*)workspace;                        // U_h^T: K = H (gate units n), N = H (rows j of U)
+    float* UzrT = UhT + packed_floats(ndir, H, H);         // U_zr^T: K = 2H, N = H
+    float* carry = UzrT + packed_floats(ndir, 2 * H, H);   // [ndir][B][H]: dh_t through the recurrence
+    float* carry2 = carry + (size_t)ndir * B * H;          // [ndir][B][H]: its elementwise part
+    launch_pack(U, UhT, H, ndir, H, H, 2 * H, 1, st);
+    launch_pack(U, UzrT, H, ndir, 2 * H, H, 0, 1, st);
+    const dim3 grid(tiles16(H), tiles16(B), ndir);
+    for (int s = T - 1; s >= 0; --s) {
+        hipLaunchKernelGGL(gru_bwd_h_kernel, grid, dim3(256), 0, st, dh_out, (const float*)UhT, h_out, gates, dgates,
+                           (const float*)carry, carry2, B, T, H, ndir, s);
+        if (s > 0)
+            hipLaunchKernelGGL(gru_bwd_zr_kernel, grid, dim3(256), 0, st, (const float*)UzrT, (const float*)dgates,
+                               (const float*)carry2, carry, B, T, H, ndir, s);
+    }
+    return check_launch("gru_bwd");
+}

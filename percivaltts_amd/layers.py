@@ -416,8 +416,11 @@ class LSTM(Layer):
 
 
 class GRU(Layer):
-    """kl.GRU(reset_after=False) / Bidirectional: not on the WGAN hot path -> stock torch ops.
-    Parameter layout follows Keras (kernel [In,3H], recurrent [H,3H], bias [3H]; gates z,r,h)."""
+    """kl.GRU(units, tanh, recurrent hard_sigmoid, reset_after=False, return_sequences=True), optionally kl.Bidirectional(concat).
+    pGRU passes no recurrent_activation (networktts.py:101-114), so the gates z, r take TF 1.x's default hard_sigmoid
+    clip(0.2a + 0.5, 0, 1).  The recurrence runs on the HIP step kernels of csrc/gru.hip (ops.gru); the input projection, dx and the
+    weight gradients are ptts_gemm / bf16x6 products (gemm_raw picks the kernel).  Parameter layout follows Keras per direction: kernel [nd,In,3H],
+    recurrent_kernel [nd,H,3H], bias [nd,3H]; gates z,r,h."""
     def __init__(self, units, bidirectional=False, name=None):
         super(GRU, self).__init__(name)
         self.units, self.ndir = int(units), 2 if bidirectional else 1
@@ -432,23 +435,8 @@ class GRU(Layer):
         return (self.units * self.ndir,)
 
     def compute(self, vals, training, memo):
-        x = to_tensor(vals[0])
-        H = self.units
-        outs = []
-        for d in range(self.ndir):
-            W, U, b = self.kernel[d], self.recurrent_kernel[d], self.bias[d]
-            xp = x @ W + b
-            h = x.new_zeros((x.shape[0], H))
-            seq = [None] * x.shape[1]
-            order = range(x.shape[1] - 1, -1, -1) if d == 1 else range(x.shape[1])
-            for t in order:
-                zr = torch.sigmoid(xp[:, t, :2 * H] + h @ U[:, :2 * H])
-                z, r = zr[:, :H], zr[:, H:]
-                hh = torch.tanh(xp[:, t, 2 * H:] + (r * h) @ U[:, 2 * H:])
-                h = z * h + (1 - z) * hh
-                seq[t] = h
-            outs.append(torch.stack(seq, dim=1))
-        return outs[0] if self.ndir == 1 else torch.cat(outs, dim=-1)
+        x = to_tensor(vals[0] if not isinstance(vals[0], LazyConcat) else vals[0].tensor()).contiguous()
+        return ops.gru(x, self.kernel, self.recurrent_kernel, self.bias)
 
 
 class Reshape(Layer):

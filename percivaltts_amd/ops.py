@@ -2230,6 +2230,22 @@ def lstm_launch(x, W, U, b, reverse=False):
     return h, c, gates
 
 
+def _h_prev(h, ndir, H, reverse=False):
+    """h_{t-1} of every step in each direction's walking order (zero at its first step): h shifted by one step.  Direction 1 of a
+    Bidirectional pair walks backwards; a single direction does when `reverse`."""
+    T = h.shape[1]
+    hprev = torch.zeros_like(h)
+    if T > 1:
+        for d in range(ndir):
+            rev = (d == 1) if ndir == 2 else bool(reverse)
+            sl = slice(d * H, (d + 1) * H)
+            if rev:
+                hprev[:, :-1, sl].copy_(h[:, 1:, sl])
+            else:
+                hprev[:, 1:, sl].copy_(h[:, :-1, sl])
+    return hprev
+
+
 lstm_dx_ready = None      # (data_ptr of the last LSTM backward's dx, event recorded right behind its product)
 
 
@@ -2286,15 +2302,7 @@ class LSTMFn(torch.autograd.Function):
             db = _colsum_f32(dgates.view(M, ndir * G4))
         if ctx.needs_input_grad[2]:
             # dU[d] = sum_t h_prev[d]^T . dgates[d]; h_prev is h shifted by one step in the walking direction
-            hprev = torch.zeros_like(h)
-            for d in range(ndir):
-                rev = (d == 1) if ndir == 2 else bool(ctx.reverse)
-                sl = slice(d * H, (d + 1) * H)
-                if T > 1:
-                    if rev:
-                        hprev[:, :-1, sl].copy_(h[:, 1:, sl])
-                    else:
-                        hprev[:, 1:, sl].copy_(h[:, :-1, sl])
+            hprev = _h_prev(h, ndir, H, ctx.reverse)
             dU = torch.empty_like(U)
             for d in range(ndir):
                 gemm_raw(hprev.view(M, ndir * H)[:, d * H:], dgates.view(M, ndir * G4)[:, d * G4:], dU[d],
@@ -2314,6 +2322,74 @@ class LSTMFn(torch.autograd.Function):
 
 def lstm(v, W, U, b, reverse=False, pre=None):
     return LSTMFn.apply(as_tensor(v).contiguous(), W, U, b, reverse, pre)
+
+
+# ----------------------------------------------------------------------------------------------
+# GRU / Bidirectional GRU, reset_after=False, hard-sigmoid gates (networktts.py:101-114)
+# ----------------------------------------------------------------------------------------------
+class GRUFn(torch.autograd.Function):
+    """x [B,T,In]; W [ndir,In,3H]; U [ndir,H,3H]; b [ndir,3H] -> h [B,T,ndir*H] (Keras gate order z,r,h; direction 1 walks time
+    backwards and keeps its outputs at the time index they were computed for)."""
+    @staticmethod
+    def forward(ctx, x, W, U, b):
+        f32c(x, 'gru.x'); f32c(W); f32c(U); f32c(b)
+        B, T, In = x.shape
+        ndir, H, G3 = U.shape
+        assert G3 == 3 * H and W.shape == (ndir, In, G3) and b.shape == (ndir, G3)
+        dev, M = x.device, B * T
+        xproj = torch.empty((B, T, ndir * G3), dtype=torch.float32, device=dev)
+        h = torch.empty((B, T, ndir * H), dtype=torch.float32, device=dev)
+        gates = torch.empty((B, T, ndir * G3), dtype=torch.float32, device=dev)
+        rh = torch.empty((B, T, ndir * H), dtype=torch.float32, device=dev)
+        xp2 = xproj.view(M, ndir * G3)
+        for d in range(ndir):
+            gemm_raw(x, W[d], xp2[:, d * G3:], M, G3, In, ldc=ndir * G3, bias=b[d])
+        ws = _workspace(_hip.lib().ptts_gru_fwd_workspace_bytes(B, T, H, ndir), dev)
+        call('ptts_gru_fwd', ptr(xproj), ptr(U), ptr(h), ptr(gates), ptr(rh), ptr(ws), ws.numel(), B, T, H, ndir, stream(),
+             tag=(B, T, H, ndir))
+        ctx.save_for_backward(x, W, U, h, gates, rh)
+        return h
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh):
+        x, W, U, h, gates, rh = ctx.saved_tensors
+        B, T, In = x.shape
+        ndir, H, G3 = U.shape
+        dev, M = x.device, B * T
+        dh = dh.contiguous()
+        dgates = torch.empty_like(gates)
+        ws = _workspace(_hip.lib().ptts_gru_bwd_workspace_bytes(B, T, H, ndir), dev)
+        call('ptts_gru_bwd', ptr(dh), ptr(U), ptr(h), ptr(gates), ptr(dgates), ptr(ws), ws.numel(), B, T, H, ndir, stream(),
+             tag=(B, T, H, ndir))
+        dg2 = dgates.view(M, ndir * G3)
+        dx = dW = dU = db = None
+        if ctx.needs_input_grad[0]:
+            # dx = sum_d dgates_d . W_d^T, the second direction added onto the first
+            dx = torch.empty_like(x)
+            for d in range(ndir):
+                gemm_raw(dg2[:, d * G3:], W[d], dx, M, In, G3, lda=ndir * G3, transB=1, ldb=G3, accumulate=int(d > 0))
+        if ctx.needs_input_grad[1]:
+            dW = torch.empty_like(W)
+            for d in range(ndir):
+                gemm_raw(x, dg2[:, d * G3:], dW[d], In, G3, M, transA=1, lda=In, rows_per_seg=M, ldb=ndir * G3)
+        if ctx.needs_input_grad[3]:
+            db = _colsum_f32(dg2).view(ndir, G3)
+        if ctx.needs_input_grad[2]:
+            # dU_zr[d] = sum_t h_{t-1}^T . da_zr,  dU_h[d] = sum_t (r * h_{t-1})^T . da_h
+            hprev = _h_prev(h, ndir, H).view(M, ndir * H)
+            rh2 = rh.view(M, ndir * H)
+            dU = torch.empty_like(U)
+            for d in range(ndir):
+                gemm_raw(hprev[:, d * H:], dg2[:, d * G3:], dU[d][:, :2 * H], H, 2 * H, M, transA=1, lda=ndir * H,
+                         rows_per_seg=M, ldb=ndir * G3, ldc=G3)
+                gemm_raw(rh2[:, d * H:], dg2[:, d * G3 + 2 * H:], dU[d][:, 2 * H:], H, H, M, transA=1, lda=ndir * H,
+                         rows_per_seg=M, ldb=ndir * G3, ldc=G3)
+        return dx, dW, dU, db
+
+
+def gru(v, W, U, b):
+    return GRUFn.apply(as_tensor(v).contiguous(), W, U, b)
 
 
 # ----------------------------------------------------------------------------------------------
