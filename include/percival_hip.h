@@ -568,6 +568,43 @@ size_t ptts_gru_bwd_workspace_bytes(int B, int T, int H, int ndir);
 int ptts_gru_bwd(const float* dh_out /*[B,T,ndir*H]*/, const float* U, const float* h_out, const float* gates,
                  float* dgates, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Random numbers: Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), counter-based.
+ * Every number is a pure function of (seed, call counter, index); nothing is stored per thread
+ * and no mask is kept.  Philox counter = (index lo, index hi, call lo, call hi), key = (seed
+ * lo, seed hi).
+ * state: a caller-owned DEVICE block of two 64-bit words {seed, call counter}, one per device.
+ * A forward entry point reads it in its main kernel, which leaves the call counter it used in the
+ * caller's 8-byte device word `used`, then enqueues a one-thread kernel on the same stream that
+ * adds one to the counter: replays of a captured graph draw fresh numbers, and the backward pass
+ * of a replay (which reads `used`, not the live counter) sees its own forward's mask.  Calls that
+ * share a block are ordered by the stream they are launched on.
+ * ------------------------------------------------------------------------------------- */
+int ptts_rng_seed(unsigned long long* state, unsigned long long seed, unsigned long long counter, void* stream);
+/* out_host[0] = seed, out_host[1] = call counter; synchronises the stream */
+int ptts_rng_state_get(const unsigned long long* state, unsigned long long* out_host, void* stream);
+/* Dropout with Keras noise_shape = (batch, 1, None) (networktts.py:65-70): one mask per sample and
+ * column, shared along time.   y[b,t,d] = a[b,t,d] * m[b0+b,d] / (1 - rate),
+ *   a = x (PTTS_IN_NONE) or lrelu(scale[d]*x + shift[d]) (PTTS_IN_LRELU; scale/shift both or NULL),
+ *   m = 1 where float(w >> 8) * 2^-24 < 1 - rate (fp32), w = word d & 3 of the Philox block of
+ *   index (b0 + b) * ceil(D/4) + (d >> 2).
+ * b0: global index of the first sample (a batch sharded over ranks draws the masks of the whole
+ * batch).  One pass: 16-byte accesses where D % 4 == 0 and x, y are 16-byte aligned, scalar ones
+ * otherwise; the masks of a workgroup's column groups are drawn once and reused down the rows. */
+int ptts_dropout_fwd(const float* x /*[B,T,D]*/, const float* scale, const float* shift, float* y,
+                     unsigned long long* state, unsigned long long* used, float rate /*[0,1)*/, float alpha,
+                     int mode, int B, int T, int D, long long b0, void* stream);
+/* da = dy * m / (1 - rate), the mask regenerated from `used` (and the block's seed); in place
+ * allowed.  The gradient through a fused input activation is ptts_affine_act_bwd on da. */
+int ptts_dropout_bwd(const float* dy, float* da, const unsigned long long* used, const unsigned long long* state,
+                     float rate, int B, int T, int D, long long b0, void* stream);
+/* out[i] = element i0 + i of the call's N(0, stddev^2) sequence, i < n (i0: a rank's offset into
+ * the whole batch's noise).  Box-Muller, four values per Philox block e >> 2 of element e: for the
+ * word pairs (0,1) and (2,3), r = stddev * sqrt(-2 ln u1), u1 = ((w >> 8) + 1) * 2^-24 in (0, 1],
+ * values r cos(2 pi u2), r sin(2 pi u2), u2 = (w' >> 8) * 2^-24. */
+int ptts_normal_fill(float* out, unsigned long long* state, unsigned long long* used, float stddev /*>= 0*/,
+                     long long i0, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ c_i = ctypes.c_int
 c_ll = ctypes.c_longlong
 c_p = ctypes.c_void_p
 c_sz = ctypes.c_size_t
+c_ull = ctypes.c_ulonglong
 
 class WGradDesc(ctypes.Structure):
     """struct ptts_wgrad_desc of include/percival_hip.h (one weight-gradient product of a grouped launch)."""
@@ -147,6 +148,11 @@ SIGNATURES = {
     'ptts_gru_fwd': (c_i, [c_p] * 5 + [c_p, c_sz] + [c_i] * 4 + [c_p]),
     'ptts_gru_bwd_workspace_bytes': (c_sz, [c_i] * 4),
     'ptts_gru_bwd': (c_i, [c_p] * 5 + [c_p, c_sz] + [c_i] * 4 + [c_p]),
+    'ptts_rng_seed': (c_i, [c_p, c_ull, c_ull, c_p]),
+    'ptts_rng_state_get': (c_i, [c_p, c_p, c_p]),
+    'ptts_dropout_fwd': (c_i, [c_p] * 6 + [c_f, c_f] + [c_i] * 4 + [c_ll, c_p]),
+    'ptts_dropout_bwd': (c_i, [c_p] * 4 + [c_f] + [c_i] * 3 + [c_ll, c_p]),
+    'ptts_normal_fill': (c_i, [c_p] * 3 + [c_f, c_ll, c_ll, c_p]),
 }
 
 _lib = None

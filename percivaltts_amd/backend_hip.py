@@ -21,8 +21,11 @@ def device():
 
 
 def set_random_seed(seed=123):
+    """numpy, torch and the library's own generator (ops.rng_seed: its call counter goes back to 0)."""
     np.random.seed(seed)
     torch.manual_seed(seed)
+    from . import ops
+    ops.rng_seed(seed)
 
 
 def gpu_memused():

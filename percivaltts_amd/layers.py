@@ -514,12 +514,12 @@ class Dropout(Layer):
         self.rate = float(rate)
 
     def compute(self, vals, training, memo):
-        x = to_tensor(vals[0])
+        v = vals[0]
         if not training or self.rate <= 0:
-            return x
-        keep = 1.0 - self.rate
-        mask = (torch.rand(x.shape[0], 1, x.shape[2], device=x.device) < keep).to(x.dtype) / keep
-        return x * mask
+            return v
+        if isinstance(v, LazyConcat):
+            v = v.tensor()
+        return ops.dropout(v, self.rate)
 
 
 class GaussianNoiseInput(Layer):
@@ -532,9 +532,12 @@ class GaussianNoiseInput(Layer):
         return (in_shapes[0][-1] + self.width,)
 
     def compute(self, vals, training, memo):
-        x = to_tensor(vals[0])
-        noise = torch.randn(x.shape[0], x.shape[1], self.width, device=x.device) * self.stddev
-        return torch.cat([x, noise], dim=-1)
+        v = vals[0]
+        parts = list(v.parts) if isinstance(v, LazyConcat) else [v]
+        B, T = parts[0].shape[0], parts[0].shape[1]
+        z = parts[0].z if isinstance(parts[0], Lazy) else parts[0]
+        # (drawn in inference too, as the reference does); a Dense consumer never builds the concatenation
+        return LazyConcat(parts + [ops.normal((B, T, self.width), self.stddev, z.device)])
 
 
 # --------------------------------------------------------------------------------------------

@@ -2098,6 +2098,131 @@ def affine_act(x, scale=None, shift=None, act=None, alpha=0.3):
 
 
 # ----------------------------------------------------------------------------------------------
+# random layers on the library's counter-based generator (csrc/random.hip): Dropout (networktts.py:65-70) and the noise
+# channels of GaussianNoiseInput (networktts.py:36-56)
+# ----------------------------------------------------------------------------------------------
+class _RNG(object):
+    """The generator's state: one device block {seed, call counter} (two 64-bit words) per device, created at first use and
+    seeded from `seed` (backend_hip.set_random_seed) or, without one, from torch.initial_seed()."""
+    seed = None
+    blocks = {}      # device index -> int64[2] device tensor
+    scratch = {}     # device index -> the `used` word of calls whose backward needs none (ops.normal)
+    MASK = (1 << 64) - 1
+
+    @classmethod
+    def state(cls, device):
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise _hip.HipLibraryError('the random generator lives on the device (got {}); there is no CPU path'.format(device))
+        idx = torch.cuda.current_device() if device.index is None else device.index
+        st = cls.blocks.get(idx)
+        if st is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise _hip.HipLibraryError('the random state block of cuda:{} must exist before a graph is captured: '
+                                           'run the model once (or call ops.rng_state()) first'.format(idx))
+            st = torch.zeros(2, dtype=torch.int64, device=torch.device('cuda', idx))
+            seed = torch.initial_seed() if cls.seed is None else cls.seed
+            with torch.cuda.device(idx):
+                call('ptts_rng_seed', ptr(st), seed & cls.MASK, 0, stream())
+            cls.blocks[idx] = st
+            cls.scratch[idx] = torch.zeros(1, dtype=torch.int64, device=st.device)
+        return st
+
+
+def rng_seed(seed, counter=0, device=None):
+    """Seed the library's generator (every device's block, or the one of `device`) and set its call counter."""
+    seed = int(seed) & _RNG.MASK
+    if device is None:
+        _RNG.seed = seed
+        targets = list(_RNG.blocks.items())
+    else:
+        st = _RNG.state(device)
+        targets = [(st.device.index, st)]
+    for idx, st in targets:
+        with torch.cuda.device(idx):
+            call('ptts_rng_seed', ptr(st), seed, int(counter) & _RNG.MASK, stream())
+
+
+def rng_state(device=None):
+    """(seed, call counter) of the device's generator; synchronises the current stream."""
+    st = _RNG.state(torch.device('cuda', torch.cuda.current_device()) if device is None else device)
+    out = (ctypes.c_ulonglong * 2)()
+    with torch.cuda.device(st.device.index):
+        call('ptts_rng_state_get', ptr(st), ctypes.cast(out, ctypes.c_void_p), stream())
+    return int(out[0]), int(out[1])
+
+
+def _rank():
+    from . import parallel
+    return parallel.rank()
+
+
+class DropoutFn(torch.autograd.Function):
+    """y = act(z) * mask / (1 - rate), one mask per (sample, column) shared along time; nothing but y is written: the backward
+    pass regenerates the mask from the call counter the forward launch left in `used`."""
+    @staticmethod
+    def forward(ctx, z, scale, shift, mode, alpha, rate, b0):
+        f32c(z, 'dropout.x')
+        if z.dim() != 3:
+            raise _hip.HipLibraryError('dropout: expected a [batch, time, features] tensor, got {}'.format(tuple(z.shape)))
+        B, T, D = z.shape
+        st = _RNG.state(z.device)
+        y = torch.empty_like(z)
+        used = torch.empty(1, dtype=torch.int64, device=z.device)
+        call('ptts_dropout_fwd', ptr(z), ptr(scale), ptr(shift), ptr(y), ptr(st), ptr(used), rate, alpha, mode, B, T, D, b0,
+             stream(), tag=(B, T, D, mode))
+        ctx.save_for_backward(z, scale, shift, used)
+        ctx.cfg = (mode, alpha, rate, b0)
+        ctx.mark_non_differentiable(used)
+        return y, used
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, _dused):
+        z, scale, shift, used = ctx.saved_tensors
+        mode, alpha, rate, b0 = ctx.cfg
+        B, T, D = z.shape
+        dy = dy.contiguous()
+        da = torch.empty_like(dy)
+        call('ptts_dropout_bwd', ptr(dy), ptr(da), ptr(used), ptr(_RNG.state(z.device)), rate, B, T, D, b0, stream(), tag=(B, T, D))
+        if mode != IN_LRELU:
+            return da, None, None, None, None, None, None
+        dz, dscale, dshift = _affine_act_bwd_raw(da, z, None, scale, shift, ACT_LRELU, alpha, want_dx=ctx.needs_input_grad[0])
+        if scale is None:
+            dscale = dshift = None
+        return dz, dscale, dshift, None, None, None, None
+
+
+def dropout(v, rate, b0=None):
+    """Dropout of a [B, T, D] tensor or Lazy with one mask per (sample, column).  A Lazy with LeakyReLU is applied while the kernel
+    loads its input (nothing is materialised in front of it).  b0: global index of the first sample, rank * B by default."""
+    lz = as_lazy(v)
+    f = _fusable(lz)
+    if f is None:
+        z, mode, scale, shift = lz.tensor(), IN_NONE, None, None
+    else:
+        z, (mode, scale, shift) = lz.z, f
+    z = z.contiguous()
+    if b0 is None:
+        b0 = _rank() * z.shape[0]
+    return DropoutFn.apply(z, scale, shift, mode, lz.alpha, float(rate), int(b0))[0]
+
+
+def normal(shape, stddev=1.0, device=None, i0=None):
+    """N(0, stddev^2) noise from the library's generator.  i0: index of the first element in the whole batch's sequence,
+    rank * numel by default (the ranks of a sharded batch draw disjoint parts of one sequence)."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    st = _RNG.state(device)
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=st.device)
+    n = out.numel()
+    if i0 is None:
+        i0 = _rank() * n
+    call('ptts_normal_fill', ptr(out), ptr(st), ptr(_RNG.scratch[st.device.index]), float(stddev), int(i0), n, stream(),
+         tag=(n,))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # gated product of a gated convolution (networktts.py:128-134: Conv2D(...) * Conv2D(..., activation=sigmoid))
 # ----------------------------------------------------------------------------------------------
 class GatedMulFn(torch.autograd.Function):

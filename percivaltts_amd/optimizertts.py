@@ -93,6 +93,8 @@ class OptimizerTTS:
         extras['torch_rng_cpu'] = torch.get_rng_state().numpy()
         if torch.cuda.is_available():
             extras['torch_rng_cuda'] = torch.cuda.get_rng_state().cpu().numpy()
+            # the library's own generator (Dropout masks, GaussianNoiseInput): {seed, call counter} of this device's block
+            extras['ptts_rng'] = ops.rng_state()
         with open(fstate + '.model.cfgextras.pkl', 'wb') as f:
             pickle.dump([self.cfg, extras, np.random.get_state()], f)
         print(' done')
@@ -168,6 +170,8 @@ class OptimizerTTS:
                 torch.set_rng_state(torch.as_tensor(extras['torch_rng_cpu'], dtype=torch.uint8))
             if 'torch_rng_cuda' in extras and torch.cuda.is_available():
                 torch.cuda.set_rng_state(torch.as_tensor(extras['torch_rng_cuda'], dtype=torch.uint8))
+            if 'ptts_rng' in extras and torch.cuda.is_available():      # (absent in state files written before the generator existed)
+                ops.rng_seed(extras['ptts_rng'][0], extras['ptts_rng'][1], device=torch.device('cuda', torch.cuda.current_device()))
             costs = extras['costs']
             epochs_modelssaved = extras['epochs_modelssaved']
             epochs_durs = extras['epochs_durs']
