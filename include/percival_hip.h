@@ -569,6 +569,30 @@ int ptts_gru_bwd(const float* dh_out /*[B,T,ndir*H]*/, const float* U, const flo
                  float* dgates, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Maximum-likelihood parameter generation (MLPG; external/merlin/mlpg_fast.py:95-135 as
+ * modeltts.py:163-179 calls it): [B,T,K*D] statics + deltas -> the [B,T,D] trajectory.
+ * K = 1 + number of windows (2 or 3); stream k of feature d is column k*D + d.  Per utterance
+ * b and feature d one symmetric positive-definite pentadiagonal system of L = lengths[b] unknowns
+ *   P = sum_k W_k^T diag(1/var_k) W_k,  b = sum_k W_k^T (mu_k / var_k),  out = P^-1 b,
+ * W_0 = I, W_k[t,t+j] = wins[k-1][j+1] (taps outside the utterance dropped), and the variance
+ * of the delta streams set to 1e11 at the utterance's first and last frame.  All B*D systems are
+ * solved by one launch, one lane each, by an LDL^T sweep in fp64 (operands and result are fp32
+ * in memory); a system's result does not depend on the rest of the batch.
+ *   y       [B,T,K*D] the means, or the normalised network output when mean/std are given:
+ *           mu = y*std + mean in fp64 (mean, std [K*D], both or neither)
+ *   var     [K*D] (var_per_frame = 0: the same for every frame) or [B,T,K*D] (var_per_frame = 1)
+ *   wins    [K-1][3] HOST memory, read before the call returns
+ *   lengths [B] device int32 or NULL (every utterance has T frames).  A length is CLAMPED to
+ *           [0, T]: nothing is read or written out of bounds and nothing is reported.
+ *   out     [B,T,D]; frames t >= lengths[b] are written as 0
+ * workspace: ptts_mlpg_workspace_bytes = 24 bytes per frame and system; no device allocation.
+ * ------------------------------------------------------------------------------------- */
+size_t ptts_mlpg_workspace_bytes(int B, int T, int D);
+int ptts_mlpg(const float* y, const float* mean, const float* std, const float* var, int var_per_frame,
+              const float* wins, const int* lengths, float* out, void* workspace, size_t workspace_bytes,
+              int B, int T, int D, int K, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Random numbers: Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), counter-based.
  * Every number is a pure function of (seed, call counter, index); nothing is stored per thread
  * and no mask is kept.  Philox counter = (index lo, index hi, call lo, call hi), key = (seed

@@ -148,6 +148,8 @@ SIGNATURES = {
     'ptts_gru_fwd': (c_i, [c_p] * 5 + [c_p, c_sz] + [c_i] * 4 + [c_p]),
     'ptts_gru_bwd_workspace_bytes': (c_sz, [c_i] * 4),
     'ptts_gru_bwd': (c_i, [c_p] * 5 + [c_p, c_sz] + [c_i] * 4 + [c_p]),
+    'ptts_mlpg_workspace_bytes': (c_sz, [c_i] * 3),
+    'ptts_mlpg': (c_i, [c_p] * 4 + [c_i] + [c_p] * 4 + [c_sz] + [c_i] * 4 + [c_p]),
     'ptts_rng_seed': (c_i, [c_p, c_ull, c_ull, c_p]),
     'ptts_rng_state_get': (c_i, [c_p, c_p, c_p]),
     'ptts_dropout_fwd': (c_i, [c_p] * 6 + [c_f, c_f] + [c_i] * 4 + [c_ll, c_p]),

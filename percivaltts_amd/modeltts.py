@@ -3,8 +3,9 @@
 Holds `.ctxsize .vocoder .kerasmodel`; `kerasmodel` keeps its name for drop-in compatibility but is a
 percivaltts_amd.layers.Model running on HIP kernels.  predict / count_params / save / load follow
 modeltts.py:68-130; the model file trio keeps its stems (`.arch.json`, `.weights.npz` in place of `.weights.h5`
-because h5py is not part of this image, `.cfgextras.pkl`).  generate_wav needs the vocoder DSP and stays
-out of scope.
+because h5py is not part of this image, `.cfgextras.pkl`).  generate_params is generate_wav (modeltts.py:144-205) up to
+the vocoder call: de-normalisation, MLPG on the device (csrc/mlpg.hip), parameter files and objective measures.  Only the
+waveform synthesis itself needs the vocoder DSP and stays out of scope.
 """
 from __future__ import print_function
 
@@ -18,6 +19,7 @@ import torch
 from . import backend_hip
 from . import data
 from . import networktts
+from . import ops
 
 
 class ModelTTS:
@@ -41,13 +43,16 @@ class ModelTTS:
             self.kerasmodel.to(dev)
         return dev
 
-    def predict(self, x):
-        """Inference forward (BatchNorm uses its moving statistics): numpy [B,T,ctx] -> numpy [B,T,out]."""
+    def predict_device(self, x):
+        """predict() without the copy back: numpy [B,T,ctx] -> float32 device tensor [B,T,out]."""
         dev = self.to_device()
         with torch.no_grad():
             xt = torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).to(dev)
-            y = self.kerasmodel(xt, training=False)
-        return y.cpu().numpy()
+            return ops.as_tensor(self.kerasmodel(xt, training=False))
+
+    def predict(self, x):
+        """Inference forward (BatchNorm uses its moving statistics): numpy [B,T,ctx] -> numpy [B,T,out]."""
+        return self.predict_device(x).cpu().numpy()
 
     def count_params(self):
         return self.kerasmodel.count_params()
@@ -88,5 +93,97 @@ class ModelTTS:
             CMP = self.predict(np.reshape(X[vi], [1] + [s for s in X[vi].shape]))[0,]
             CMP.astype('float32').tofile(outpath.replace('*', fid_lst[vi]))
 
+    def _nb_mlpg_wins(self):
+        wins = self.vocoder.mlpg_wins
+        return len(wins) if wins is not None else 0
+
+    def denormalise(self, CMP, Ymean, Ystd, mlpg_ignore=False):
+        """The nested denormalise() of the reference's generate_wav (modeltts.py:163-179): numpy [T, featuressize()] ->
+        numpy float32 [T, featuressizeraw()].  CMP*Ystd + Ymean, then, for a vocoder with `mlpg_wins`, either the static columns
+        (`mlpg_ignore`: pure numpy) or MLPG with var = Ystd**2 at every frame, solved on the device (ops.mlpg; the
+        de-normalisation is then done in fp64 inside the kernel).  Without windows the width is unchanged and no device is
+        needed."""
+        CMP = np.asarray(CMP, dtype=np.float32)
+        Ymean, Ystd = np.asarray(Ymean, dtype=np.float32), np.asarray(Ystd, dtype=np.float32)
+        if CMP.ndim != 2 or CMP.shape[1] != self.vocoder.featuressize() or Ymean.shape != (CMP.shape[1],) or Ystd.shape != Ymean.shape:
+            raise ValueError('denormalise: CMP {} / mean {} / std {} do not match the vocoder\'s {} features'.format(
+                CMP.shape, Ymean.shape, Ystd.shape, self.vocoder.featuressize()))
+        if self._nb_mlpg_wins() == 0:
+            return CMP * Ystd + Ymean
+        ops.mlpg_windows(self.vocoder.mlpg_wins)        # ValueError for windows MLPG cannot use, whichever branch follows
+        if mlpg_ignore:
+            return (CMP * Ystd + Ymean)[:, :self.vocoder.featuressizeraw()]
+        dev = backend_hip.device()
+        mean, std = torch.from_numpy(Ymean).to(dev), torch.from_numpy(Ystd).to(dev)
+        out = ops.mlpg(torch.from_numpy(np.ascontiguousarray(CMP)).to(dev), self.vocoder.mlpg_wins, std * std, mean=mean, std=std)
+        return out.cpu().numpy()
+
+    def generate_params(self, inpath, outpath, fid_lst, gendir, do_objmeas=True, batch_size=8):
+        """The reference's generate_wav (modeltts.py:144-205) up to the vocoder call: read mean4norm.dat / std4norm.dat beside
+        `outpath`, predict each file of `fid_lst`, de-normalise (with MLPG when the vocoder has `mlpg_wins`), write
+        `gendir/<fid>.cmp` as headerless float32 [T, featuressizeraw()], and, with `do_objmeas`, feed the vocoder's objective
+        measures with (generated, de-normalised target statics), print their statistics and return them (None otherwise).
+
+        With MLPG the network's output tensor stays on the device: it goes into ptts_mlpg with mean / std given, so the
+        de-normalisation is fused into the solve's loads, and up to `batch_size` utterances share one launch (zero-padded to
+        the longest, each solved over its own length).  The network itself still sees ONE utterance per predict, as in the
+        reference: padding would change what a context Conv1D or a BLSTM computes for an utterance's real frames wherever it
+        looks across the pad, and the files must not depend on how they were batched.  Only the MLPG launch is batched; its
+        systems are independent, so the files are bit-identical for every `batch_size`."""
+        Ymean = np.fromfile(os.path.join(os.path.dirname(outpath), 'mean4norm.dat'), dtype='float32')
+        Ystd = np.fromfile(os.path.join(os.path.dirname(outpath), 'std4norm.dat'), dtype='float32')
+        nout, nraw = self.vocoder.featuressize(), self.vocoder.featuressizeraw()
+        if Ymean.shape != (nout,) or Ystd.shape != (nout,):
+            raise ValueError('mean4norm.dat / std4norm.dat hold {} / {} values, the vocoder has {} features'.format(
+                Ymean.size, Ystd.size, nout))
+        use_mlpg = self._nb_mlpg_wins() > 0
+        if use_mlpg: ops.mlpg_windows(self.vocoder.mlpg_wins)
+        if batch_size < 1: raise ValueError('batch_size has to be at least 1')
+
+        X_test = data.load(inpath, fid_lst, verbose=1, label='Context labels: ')
+        if do_objmeas:
+            y_test = data.load(outpath, fid_lst, verbose=1, label='Output features: ')
+            X_test, y_test = data.croplen((X_test, y_test))
+            self.vocoder.objmeasures_clear()
+        if not os.path.isdir(gendir): os.makedirs(gendir)
+
+        if use_mlpg:
+            dev = self.to_device()
+            mean, std = torch.from_numpy(Ymean).to(dev), torch.from_numpy(Ystd).to(dev)
+            var = std * std                 # "Simplification!" (modeltts.py:176): the global variance at every frame
+        for v0 in range(0, len(fid_lst), batch_size):
+            vis = list(range(v0, min(v0 + batch_size, len(fid_lst))))
+            ys = []
+            for vi in vis:
+                print('Generating {}/{} fid={} ...'.format(1 + vi, len(fid_lst), fid_lst[vi]))
+                y = self.predict_device(np.reshape(X_test[vi], [1] + [s for s in X_test[vi].shape]))[0]
+                if y.shape[-1] != nout:
+                    raise ValueError('the model predicts {} features, the vocoder expects {}'.format(y.shape[-1], nout))
+                ys.append(y)
+            if use_mlpg:
+                lens = [int(y.shape[0]) for y in ys]
+                if len(ys) == 1:
+                    gen = ops.mlpg(ys[0].contiguous(), self.vocoder.mlpg_wins, var, mean=mean, std=std).unsqueeze(0)
+                else:
+                    ypad = torch.zeros((len(ys), max(lens), nout), dtype=torch.float32, device=dev)
+                    for i, y in enumerate(ys): ypad[i, :lens[i]] = y
+                    gen = ops.mlpg(ypad, self.vocoder.mlpg_wins, var, mean=mean, std=std,
+                                   lengths=torch.tensor(lens, dtype=torch.int32, device=dev))
+                gen = gen.cpu().numpy()
+                CMPs = [gen[i, :lens[i]] for i in range(len(ys))]
+            else:
+                CMPs = [self.denormalise(y.cpu().numpy(), Ymean, Ystd) for y in ys]
+            for vi, CMP in zip(vis, CMPs):
+                CMP = np.ascontiguousarray(CMP, dtype=np.float32)
+                assert CMP.shape[1] == nraw
+                CMP.tofile(os.path.join(gendir, fid_lst[vi] + '.cmp'))
+                if do_objmeas:
+                    self.vocoder.objmeasures_add(CMP, self.denormalise(y_test[vi], Ymean, Ystd, mlpg_ignore=True))
+        stats = self.vocoder.objmeasures_stats() if do_objmeas else None
+        print('Generation finished')
+        sys.stdout.flush()
+        return stats
+
     def generate_wav(self, *args, **kwargs):
-        raise NotImplementedError('waveform synthesis needs the vocoder DSP (pulsemodel/pyworld), outside this build')
+        raise NotImplementedError('waveform synthesis needs the vocoder DSP (pulsemodel/pyworld), outside this build; '
+                                  'generate_params writes the de-normalised (MLPG) parameters a vocoder would read')

@@ -63,7 +63,15 @@ class DCNNF0SpecNoiseFeatures(modeltts.ModelTTS):
             l_nm = networktts.pFC(l_nm, cfgarch.arch_hiddenwidth)
         l_nm = kl.Dense(vocoder.noisesize(), activation='sigmoid')(l_nm)
 
-        l_out = kl.Concatenate()([l_f0, l_spec, l_nm])
+        heads = [l_f0, l_spec, l_nm]
+        # Build extension: the reference's DCNN has no delta heads, so with a vocoder built with `mlpg_wins` its output would be
+        # narrower than the composed features.  Here the delta (and delta-delta) streams get the heads network_final gives the
+        # Generic model (networktts.py:201-208), fed by the context: linear f0+spec, tanh resp. 2*tanh noise mask.
+        nwins = len(vocoder.mlpg_wins) if vocoder.mlpg_wins is not None else 0
+        for wi, (prefix, nm_act) in enumerate((('lo_delta', 'tanh'), ('lo_deltadelta', ('tanh_saturated', 2.0)))[:nwins]):
+            heads.append(kl.Dense(1 + vocoder.specsize(), activation=None, name=prefix + '_f0spec')(l_ctx))
+            heads.append(kl.Dense(vocoder.noisesize(), activation=nm_act, name=prefix + '_nm')(l_ctx))
+        l_out = kl.Concatenate()(heads)
 
         # handles for the critic step, which only needs the spectral branch (the critic slices it, networks_critic.py:58)
         self.node_spec, self.node_f0, self.node_nm = l_spec, l_f0, l_nm

@@ -2518,6 +2518,71 @@ def gru(v, W, U, b):
 
 
 # ----------------------------------------------------------------------------------------------
+# parameter generation (modeltts.py:163-179 -> external/merlin/mlpg_fast.py:95-135)
+# ----------------------------------------------------------------------------------------------
+MLPG_WORKSPACE_CAP = 256 << 20      # bytes of workspace one ptts_mlpg launch may use; larger batches are split along B
+
+
+def mlpg_windows(wins):
+    """Validate delta windows (one or two, three taps each) -> flat list of 3*len(wins) floats."""
+    if wins is None or not 1 <= len(wins) <= 2:
+        raise ValueError('MLPG needs one or two delta windows, got {}'.format(0 if wins is None else len(wins)))
+    flat = []
+    for w in wins:
+        if len(w) != 3:
+            raise ValueError('an MLPG window has three taps, got {}'.format(list(w)))
+        flat.extend(float(c) for c in w)
+    return flat
+
+
+def mlpg(y, wins, var, mean=None, std=None, lengths=None):
+    """Maximum-likelihood parameter generation on the device (csrc/mlpg.hip): y [B,T,K*D] (or [T,K*D], treated as B = 1) means,
+    or the normalised network output when mean / std [K*D] are given (mu = y*std + mean in fp64); var [K*D] (every frame the
+    same) or the shape of y; wins: K-1 three-tap windows; lengths [B] int32 (frames behind an utterance's end come back as 0,
+    a length is clamped to [0, T]).  Returns [B,T,D] ([T,D] for a 2-D y).  No autograd node."""
+    flat = mlpg_windows(wins)
+    K = 1 + len(flat) // 3
+    for t in (y, var, mean, std):
+        if t is not None and t.requires_grad:
+            raise ValueError('ops.mlpg has no backward pass: detach its inputs')
+    if (mean is None) != (std is None):
+        raise ValueError('ops.mlpg: mean and std go together (both or neither)')
+    f32c(y, 'mlpg.y'); f32c(var, 'mlpg.var'); f32c(mean, 'mlpg.mean'); f32c(std, 'mlpg.std')
+    squeeze = y.dim() == 2
+    y3 = y.unsqueeze(0) if squeeze else y
+    if y3.dim() != 3 or y3.shape[-1] % K != 0 or min(y3.shape) < 1:
+        raise ValueError('ops.mlpg: y {} is not [B,T,{}*D]'.format(tuple(y.shape), K))
+    B, T, KD = y3.shape
+    D = KD // K
+    per_frame = var.dim() > 1
+    if per_frame:
+        if squeeze and var.dim() == 2: var = var.unsqueeze(0)
+        if var.shape != y3.shape:
+            raise ValueError('ops.mlpg: per-frame var {} does not match y {}'.format(tuple(var.shape), tuple(y3.shape)))
+    elif var.shape != (KD,):
+        raise ValueError('ops.mlpg: var {} is neither [{}] nor the shape of y'.format(tuple(var.shape), KD))
+    for t, name in ((mean, 'mean'), (std, 'std')):
+        if t is not None and t.shape != (KD,):
+            raise ValueError('ops.mlpg: {} {} is not [{}]'.format(name, tuple(t.shape), KD))
+    if lengths is not None:
+        if not (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.shape == (B,)):
+            raise _hip.HipLibraryError('mlpg.lengths: expected a contiguous int32 device tensor of shape [{}]'.format(B))
+    wbuf = (ctypes.c_float * len(flat))(*flat)
+    out = torch.empty((B, T, D), dtype=torch.float32, device=y.device)
+    l = _hip.lib()
+    nb = B
+    while nb > 1 and l.ptts_mlpg_workspace_bytes(nb, T, D) > MLPG_WORKSPACE_CAP:
+        nb = (nb + 1) // 2
+    for b0 in range(0, B, nb):
+        n = min(nb, B - b0)
+        ws = _workspace(l.ptts_mlpg_workspace_bytes(n, T, D), y.device)
+        call('ptts_mlpg', ptr(y3[b0:b0 + n]), ptr(mean), ptr(std), ptr(var[b0:b0 + n] if per_frame else var), int(per_frame),
+             wbuf, ptr(lengths[b0:b0 + n]) if lengths is not None else None, ptr(out[b0:b0 + n]), ptr(ws), ws.numel(),
+             n, T, D, K, stream(), tag=(n, T, D, K))
+    return out[0] if squeeze else out
+
+
+# ----------------------------------------------------------------------------------------------
 # WGAN-GP pieces (optimizertts_wgan.py:44-79)
 # ----------------------------------------------------------------------------------------------
 def gp_interpolate(real, fake, alpha_b, out=None):

@@ -78,6 +78,9 @@ def synthesize_corpus(nfiles=48, minlen=450, maxlen=700, seed=123):
         w = np.ones((n, 1), dtype=np.float32)
         w[:20] = 0.0; w[-20:] = 0.0
         w.tofile(cfg.wpath.split(':')[0].replace('*', fid))
+    # the synthetic features count as already normalised: identity statistics beside them (compose.py writes the real ones)
+    np.zeros(out_size, dtype=np.float32).tofile(os.path.join(os.path.dirname(cfg.outpath), 'mean4norm.dat'))
+    np.ones(out_size, dtype=np.float32).tofile(os.path.join(os.path.dirname(cfg.outpath), 'std4norm.dat'))
     return fids
 
 
@@ -103,6 +106,10 @@ def generate(fparams=None):
     mod.load(fparams)
     fid_lst_test = fids[cfg.id_valid_start + cfg.id_valid_nb:cfg.id_valid_start + cfg.id_valid_nb + cfg.id_test_nb]
     mod.generate_cmp(cfg.inpath, os.path.splitext(fparams)[0] + '-gen/*.cmp', fid_lst_test)
+    # where the reference calls generate_wav (run.py:218): everything of it up to the vocoder's synthesis
+    demostart = cfg.id_test_demostart if hasattr(cfg, 'id_test_demostart') else 0
+    mod.generate_params(cfg.inpath, cfg.outpath, fid_lst_test[demostart:demostart + 10], os.path.splitext(fparams)[0] + '-demo-params',
+                        do_objmeas=True)
 
 
 if __name__ == "__main__":

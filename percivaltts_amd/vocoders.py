@@ -4,13 +4,23 @@ The reference's vocoders.py:33-352 also does signal analysis/synthesis through t
 submodule (absent from the reference checkout) and pyworld; that DSP is out of scope here (SURVEY.md
 section 2, row 9).  The networks, the critic and the WGAN losses only need the feature-size accessors
 (vocoders.py:95-109,130-131,176-179,228-232), `fs`, `shift`, `mlpg_wins`, and the class identity that
-network_final switches on (networktts.py:195,212).
+network_final switches on (networktts.py:195,212).  The objective measures of vocoders.py:112-117,209-218,333-342
+(`objmeasures_clear / objmeasures_add / objmeasures_stats`) are plain numpy on a few hundred kilobytes per utterance.
 """
+from __future__ import print_function
+
+import numpy as np
+
+
+def log2db(x):
+    """Natural-log amplitude -> decibels (the reference's sigproc.log2db)."""
+    return (20.0 / np.log(10.0)) * x
 
 
 class Vocoder(object):
     def __init__(self, name, fs, shift, mlpg_wins=None):
         self._name, self.fs, self.shift, self.mlpg_wins = name, fs, shift, mlpg_wins
+        self.features_err = dict()      # per instance (a class-level dict in the reference, shared between vocoders by accident)
 
     def __str__(self):
         return '{} (fs={}, shift={})'.format(self.name(), self.fs, self.shift)
@@ -30,6 +40,18 @@ class Vocoder(object):
     def noisesize(self): return -1
     def vuvsize(self): return -1
 
+    # Objective measures (vocoders.py:112-117): lists of per-utterance errors, keyed by feature
+    def objmeasures_clear(self):
+        self.features_err = dict()
+
+    def objmeasures_stats(self):
+        """Print `key: mean` per feature as the reference does, and return them as a dict."""
+        stats = dict()
+        for key in self.features_err:
+            stats[key] = float(np.mean(np.vstack(self.features_err[key])))
+            print('{}: {}'.format(key, stats[key]))
+        return stats
+
     def _out_of_scope(self, *a, **k):
         raise NotImplementedError('waveform analysis/synthesis is outside the MI355X hot-path build '
                                   '(needs the pulsemodel/pyworld DSP of the reference)')
@@ -44,6 +66,17 @@ class VocoderF0Spec(Vocoder):
     def f0size(self): return 1
     def specsize(self): return self.spec_size
 
+    def _objmeasures_add_f0spec(self, CMP, REF):
+        """F0[Hz]: RMS of the exp(f0) differences; SPEC[dB]: per-band RMS of the log2db differences."""
+        self.features_err.setdefault('F0[Hz]', []).append(np.sqrt(np.mean((np.exp(REF[:, 0]) - np.exp(CMP[:, 0]))**2)))
+        spectrg = log2db(REF[:, 1:1 + self.spec_size])
+        specgen = log2db(CMP[:, 1:1 + self.spec_size])
+        self.features_err.setdefault('SPEC[dB]', []).append(np.sqrt(np.mean((spectrg - specgen)**2, 0)))
+
+    def _objmeasures_add_band(self, key, CMP, REF, size):
+        lo = 1 + self.spec_size
+        self.features_err.setdefault(key, []).append(np.sqrt(np.mean((REF[:, lo:lo + size] - CMP[:, lo:lo + size])**2, 0)))
+
 
 class VocoderPML(VocoderF0Spec):
     """f0 | spec | noise mask"""
@@ -55,6 +88,11 @@ class VocoderPML(VocoderF0Spec):
     def noisesize(self): return self.nm_size
     def vuvsize(self): return 0
 
+    def objmeasures_add(self, CMP, REF):
+        """Generated and target [T, >= raw] de-normalised features of one utterance (vocoders.py:209-218)."""
+        self._objmeasures_add_f0spec(CMP, REF)
+        self._objmeasures_add_band('NM', CMP, REF, self.nm_size)
+
 
 class VocoderWORLD(VocoderF0Spec):
     """f0 | spec | aperiodicity | vuv"""
@@ -65,3 +103,8 @@ class VocoderWORLD(VocoderF0Spec):
     def featuressizeraw(self): return 1 + self.spec_size + self.aper_size + 1
     def noisesize(self): return self.aper_size
     def vuvsize(self): return 1
+
+    def objmeasures_add(self, CMP, REF):
+        """As VocoderPML's, the aperiodicity bands in place of the noise mask (vocoders.py:333-342; no VUV measure there)."""
+        self._objmeasures_add_f0spec(CMP, REF)
+        self._objmeasures_add_band('APER[dB]', CMP, REF, self.aper_size)
