@@ -593,6 +593,53 @@ int ptts_mlpg(const float* y, const float* mean, const float* std, const float* 
               int B, int T, int D, int K, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Feature composition (compose.py:34-183, 239-298): delta windows, per-column corpus statistics,
+ * normalisers.  A chunk of N utterances is packed row-wise, [R, D] fp32, no padding; offsets [N+1]
+ * device int32, utterance u owns rows offsets[u] .. offsets[u+1]-1 (clamped into [0, R]: nothing
+ * is read or written out of bounds whatever offsets holds).
+ *
+ * ptts_compose_windows: out [R, K*D], K = 1 + number of windows (1 .. 8).  Columns 0..D-1 are y
+ * bit for bit; window k (taps w = wins[k], fp64) fills columns (k+1)*D ..: for an utterance of T
+ * frames and t in 1..T-2
+ *   mlpg_order = 0:  -(w[2]*y[t-1] + w[1]*y[t] + w[0]*y[t+1])      (-scipy.signal.convolve(y, w))
+ *   mlpg_order = 1:    w[0]*y[t-1] + w[1]*y[t] + w[2]*y[t+1]       (W_k y of ptts_mlpg)
+ * in fp64, added left to right as written (oldest frame first), rounded once; frame 0 repeats frame 1, frame T-1 repeats frame T-2 (an
+ * utterance shorter than 3 frames gets neighbours clamped into it: defined, not the reference's).
+ * Fused statistics over utterances u < n_stat_utts (of this chunk): min and max of the fp32
+ * results, sum of the fp64 values before rounding.  Two stages, no atomics: one partial per
+ * utterance and column in the workspace (a function of that utterance's rows only), then the
+ * partials are added in utterance order ONTO run_min / run_max [K*D] fp32 and run_sum [K*D] fp64,
+ * which the caller initialises (+inf, -inf, 0) and carries from chunk to chunk: the result does
+ * not depend on how a corpus is cut into chunks.  n_stat_utts = 0: no statistics, the running
+ * buffers and the workspace may be NULL.
+ *   wins  [K-1][3] doubles in HOST memory, read before the call returns (NULL for K = 1)
+ * workspace: ptts_compose_windows_workspace_bytes(min(n_stat_utts, N), D, K); no device allocation.
+ *
+ * ptts_compose_sqdev: run_sq[c] += sum over the rows of utterances u < n_stat_utts of
+ * (double(y[r,c]) - mean[c])^2, y [R, W] fp32 (composed rows), mean [W] DEVICE fp64; the centred
+ * second pass of the standard deviation, same two stages and the same chunk invariance.
+ * workspace: ptts_compose_sqdev_workspace_bytes(min(n_stat_utts, N), W).
+ *
+ * ptts_compose_normalise: out[r,j] = f(y[r, keepidx[j]]), y [R, Win], out [R, Wout], keepidx [Wout]
+ * device int32 or NULL (then Wout = Win and out may be y).  fp32, numpy's operation order, IEEE
+ * division, no contraction:
+ *   PTTS_NORM_MEANSTD  (y - a[j]) / b[j]
+ *   PTTS_NORM_MINMAX   ((((y - a[j]) / b[j]) - 0.5f) * 2.0f) * scale + offset
+ * a, b [Wout] (already gathered).  Needs no workspace.
+ * ------------------------------------------------------------------------------------- */
+#define PTTS_NORM_MEANSTD 0
+#define PTTS_NORM_MINMAX  1
+size_t ptts_compose_windows_workspace_bytes(int N, int D, int K);
+int ptts_compose_windows(const float* y, const int* offsets, const double* wins, int mlpg_order, float* out,
+                         float* run_min, float* run_max, double* run_sum, int n_stat_utts, void* workspace,
+                         size_t workspace_bytes, int N, int R, int D, int K, void* stream);
+size_t ptts_compose_sqdev_workspace_bytes(int N, int W);
+int ptts_compose_sqdev(const float* y, const int* offsets, const double* mean, double* run_sq, int n_stat_utts,
+                       void* workspace, size_t workspace_bytes, int N, int R, int W, void* stream);
+int ptts_compose_normalise(const float* y, const int* keepidx, const float* a, const float* b, int mode, float scale,
+                           float offset, float* out, long long R, int Win, int Wout, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Random numbers: Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), counter-based.
  * Every number is a pure function of (seed, call counter, index); nothing is stored per thread
  * and no mask is kept.  Philox counter = (index lo, index hi, call lo, call hi), key = (seed

@@ -2583,6 +2583,138 @@ def mlpg(y, wins, var, mean=None, std=None, lengths=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# feature composition (compose.py:34-183, 239-298): csrc/compose.hip
+# ----------------------------------------------------------------------------------------------
+NORM_MEANSTD, NORM_MINMAX = 0, 1
+COMPOSE_MAX_WINS = 7
+
+
+def compose_window_taps(wins):
+    """Validate composition windows (none .. seven, three taps each) -> flat list of 3*len(wins) floats (fp64 taps)."""
+    wins = [] if wins is None else list(wins)
+    if len(wins) > COMPOSE_MAX_WINS:
+        raise ValueError('compose takes at most {} windows, got {}'.format(COMPOSE_MAX_WINS, len(wins)))
+    flat = []
+    for w in wins:
+        if len(w) != 3:
+            raise ValueError('a composition window has three taps, got {}'.format(list(w)))
+        flat.extend(float(c) for c in w)
+    return flat
+
+
+def _dev_tensor(t, dtype, name, shape=None):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise _hip.HipLibraryError('{}: expected a contiguous {} device tensor'.format(name, dtype))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError('{}: shape {} is not {}'.format(name, tuple(t.shape), tuple(shape)))
+    return t
+
+
+def compose_stats_buffers(W, device):
+    """Running (min, max, sum) [W] for compose_windows, initialised to (+inf, -inf, 0)."""
+    return (torch.full((W,), float('inf'), dtype=torch.float32, device=device),
+            torch.full((W,), float('-inf'), dtype=torch.float32, device=device),
+            torch.zeros(W, dtype=torch.float64, device=device))
+
+
+def compose_windows(y, offsets, wins, stats=None, n_stat_utts=0, mlpg_order=False, out=None):
+    """y [R,D] fp32 rows of N packed utterances, offsets [N+1] int32 (device) -> [R,K*D]: the statics and one stream per window
+    (csrc/compose.hip; `mlpg_order` picks W_k y instead of the reference's -convolve).  stats = (run_min, run_max, run_sum) from
+    compose_stats_buffers is updated in place with the rows of the first `n_stat_utts` utterances.  No autograd node."""
+    flat = compose_window_taps(wins)
+    K = 1 + len(flat) // 3
+    f32c(y, 'compose_windows.y')
+    if y.dim() != 2 or min(y.shape) < 1:
+        raise ValueError('ops.compose_windows: y {} is not [R,D]'.format(tuple(y.shape)))
+    if y.requires_grad:
+        raise ValueError('ops.compose_windows has no backward pass: detach its input')
+    R, D = y.shape
+    if R >= 1 << 31:
+        raise ValueError('ops.compose_windows: {} rows exceed the int32 offsets'.format(R))
+    _dev_tensor(offsets, torch.int32, 'compose_windows.offsets')
+    if offsets.dim() != 1 or offsets.numel() < 2:
+        raise ValueError('ops.compose_windows: offsets {} is not [N+1]'.format(tuple(offsets.shape)))
+    N = offsets.numel() - 1
+    n_stat = min(int(n_stat_utts), N)
+    if n_stat < 0 or (n_stat > 0 and stats is None):
+        raise ValueError('ops.compose_windows: n_stat_utts={} with stats={}'.format(n_stat_utts, 'None' if stats is None else 'given'))
+    W = K * D
+    if out is None:
+        out = torch.empty((R, W), dtype=torch.float32, device=y.device)
+    else:
+        f32c(out, 'compose_windows.out')
+        if out.shape != (R, W):
+            raise ValueError('ops.compose_windows: out {} is not [{},{}]'.format(tuple(out.shape), R, W))
+    rmin = rmax = rsum = ws = None
+    nws = 0
+    if n_stat > 0:
+        rmin = _dev_tensor(stats[0], torch.float32, 'compose_windows.run_min', (W,))
+        rmax = _dev_tensor(stats[1], torch.float32, 'compose_windows.run_max', (W,))
+        rsum = _dev_tensor(stats[2], torch.float64, 'compose_windows.run_sum', (W,))
+        nws = _hip.lib().ptts_compose_windows_workspace_bytes(n_stat, D, K)
+        ws = _workspace(nws, y.device)
+    wbuf = (ctypes.c_double * max(len(flat), 1))(*flat)
+    call('ptts_compose_windows', ptr(y), ptr(offsets), wbuf if flat else None, int(bool(mlpg_order)), ptr(out), ptr(rmin), ptr(rmax),
+         ptr(rsum), n_stat, ptr(ws), nws, N, R, D, K, stream(), tag=(N, R, D, K))
+    return out
+
+
+def compose_sqdev(y, offsets, mean, run_sq, n_stat_utts):
+    """run_sq [W] fp64 += sum over the rows of the first `n_stat_utts` utterances of (double(y) - mean)^2; y [R,W] fp32,
+    mean [W] fp64 (device).  The centred second pass of the standard deviation (compose.py:289-296)."""
+    f32c(y, 'compose_sqdev.y')
+    if y.dim() != 2 or min(y.shape) < 1:
+        raise ValueError('ops.compose_sqdev: y {} is not [R,W]'.format(tuple(y.shape)))
+    R, W = y.shape
+    _dev_tensor(offsets, torch.int32, 'compose_sqdev.offsets')
+    if offsets.dim() != 1 or offsets.numel() < 2:
+        raise ValueError('ops.compose_sqdev: offsets {} is not [N+1]'.format(tuple(offsets.shape)))
+    N = offsets.numel() - 1
+    _dev_tensor(mean, torch.float64, 'compose_sqdev.mean', (W,))
+    _dev_tensor(run_sq, torch.float64, 'compose_sqdev.run_sq', (W,))
+    n_stat = min(int(n_stat_utts), N)
+    if n_stat < 0:
+        raise ValueError('ops.compose_sqdev: n_stat_utts={}'.format(n_stat_utts))
+    if n_stat == 0:
+        return run_sq
+    nws = _hip.lib().ptts_compose_sqdev_workspace_bytes(n_stat, W)
+    ws = _workspace(nws, y.device)
+    call('ptts_compose_sqdev', ptr(y), ptr(offsets), ptr(mean), ptr(run_sq), n_stat, ptr(ws), nws, N, R, W, stream(), tag=(N, R, W))
+    return run_sq
+
+
+def compose_normalise(y, a, b, mode=NORM_MEANSTD, scale=1.0, offset=0.0, keepidx=None, out=None):
+    """out[r,j] = f(y[r, keepidx[j]]) in fp32 and numpy's operation order: (y - a)/b (NORM_MEANSTD) or
+    ((((y - a)/b) - 0.5)*2)*scale + offset (NORM_MINMAX); a, b [Wout] fp32, keepidx [Wout] int32 or None.  out=y runs in place
+    (without keepidx)."""
+    f32c(y, 'compose_normalise.y')
+    if y.dim() != 2 or min(y.shape) < 1:
+        raise ValueError('ops.compose_normalise: y {} is not [R,W]'.format(tuple(y.shape)))
+    if mode not in (NORM_MEANSTD, NORM_MINMAX):
+        raise ValueError('ops.compose_normalise: unknown mode {}'.format(mode))
+    R, Win = y.shape
+    Wout = Win
+    if keepidx is not None:
+        _dev_tensor(keepidx, torch.int32, 'compose_normalise.keepidx')
+        if keepidx.dim() != 1 or keepidx.numel() < 1:
+            raise ValueError('ops.compose_normalise: keepidx {} is not [Wout]'.format(tuple(keepidx.shape)))
+        Wout = keepidx.numel()
+    _dev_tensor(a, torch.float32, 'compose_normalise.a', (Wout,))
+    _dev_tensor(b, torch.float32, 'compose_normalise.b', (Wout,))
+    if out is None:
+        out = torch.empty((R, Wout), dtype=torch.float32, device=y.device)
+    else:
+        f32c(out, 'compose_normalise.out')
+        if out.shape != (R, Wout):
+            raise ValueError('ops.compose_normalise: out {} is not [{},{}]'.format(tuple(out.shape), R, Wout))
+        if keepidx is not None and out.data_ptr() == y.data_ptr():
+            raise ValueError('ops.compose_normalise: a column gather cannot run in place')
+    call('ptts_compose_normalise', ptr(y), ptr(keepidx), ptr(a), ptr(b), int(mode), float(scale), float(offset), ptr(out), R, Win,
+         Wout, stream(), tag=(R, Win, Wout, mode))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # WGAN-GP pieces (optimizertts_wgan.py:44-79)
 # ----------------------------------------------------------------------------------------------
 def gp_interpolate(real, fake, alpha_b, out=None):

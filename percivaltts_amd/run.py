@@ -3,7 +3,9 @@
 (features_extraction / contexts_extraction: vocoder analysis and HTS label normalisation, run.py:147-180) need
 the pulsemodel/merlin front ends and are outside this build; `synthesize_corpus()` writes a synthetic corpus of
 the same on-disk format (headerless float32 `path:(-1,D)` files + file_id_list.scp) so that the training stages run
-unchanged.  Point `cfg.inpath / cfg.outpath / cfg.wpath / cfg.fileids` at real composed features to train on them.
+unchanged.  `features_compose()` is the composition half of the reference's features_extraction (run.py:155-165): from raw
+per-stream feature files it writes the time weights and the composed, normalised outputs `cfg.outpath` points at
+(percivaltts_amd.compose, on the device).
 """
 from __future__ import print_function
 
@@ -13,7 +15,7 @@ import sys
 import numpy as np
 
 from percivaltts_amd import *  # noqa: F401,F403  (configuration, readids, print_log, ...)
-from percivaltts_amd import modeltts_common, networks_critic, optimizertts, optimizertts_wgan, vocoders
+from percivaltts_amd import compose, modeltts_common, networks_critic, optimizertts, optimizertts_wgan, vocoders
 
 print_log('Global configurations')
 cfg = configuration()
@@ -78,10 +80,25 @@ def synthesize_corpus(nfiles=48, minlen=450, maxlen=700, seed=123):
         w = np.ones((n, 1), dtype=np.float32)
         w[:20] = 0.0; w[-20:] = 0.0
         w.tofile(cfg.wpath.split(':')[0].replace('*', fid))
-    # the synthetic features count as already normalised: identity statistics beside them (compose.py writes the real ones)
+    # the synthetic features count as already normalised: identity statistics beside them (features_compose -> compose.compose writes the real ones)
     np.zeros(out_size, dtype=np.float32).tofile(os.path.join(os.path.dirname(cfg.outpath), 'mean4norm.dat'))
     np.ones(out_size, dtype=np.float32).tofile(os.path.join(os.path.dirname(cfg.outpath), 'std4norm.dat'))
     return fids
+
+
+def features_compose(rawpaths, fids=None, win_convention='mlpg'):
+    """The composition stage of the reference's features_extraction (run.py:155-165).  rawpaths: the raw feature streams in
+    the vocoder's order, [f0_path, spec_path, noise_path] without shape selectors (VocoderWORLD: + vuv_path).  Writes the time
+    weights from the spectral energy to cfg.wpath and the composed outputs, with `vocoder.mlpg_wins` and the statistics of the
+    first cfg.id_valid_start files, to cfg.outpath.  `win_convention`: 'mlpg' by default here, because generate() inverts the
+    windows with MLPG (see compose.compose); 'reference' reproduces the reference's files."""
+    fids = readids(cfg.fileids) if fids is None else fids
+    spec_path = rawpaths[1] + ':(-1,' + str(vocoder.specsize()) + ')'
+    compose.create_weights_spec(spec_path, fids, cfg.wpath)
+    outpaths = [rawpaths[0], spec_path, rawpaths[2] + ':(-1,' + str(vocoder.noisesize()) + ')'] + list(rawpaths[3:])
+    normfn = compose.normalise_meanstd_nmnoscale if isinstance(vocoder, vocoders.VocoderPML) else compose.normalise_meanstd
+    return compose.compose(outpaths, fids, cfg.outpath, id_valid_start=cfg.id_valid_start, normfn=normfn, wins=vocoder.mlpg_wins,
+                           win_convention=win_convention)
 
 
 def build_model():
