@@ -640,6 +640,63 @@ int ptts_compose_normalise(const float* y, const int* keepidx, const float* a, c
                            float offset, float* out, long long R, int Win, int Wout, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Label front end (external/merlin/label_normalisation.py: pattern_matching_binary,
+ * pattern_matching_continous_position, load_labels_with_state_alignment :661-710,
+ * load_labels_with_phone_alignment :546-568): HTS full-context labels -> frame-level context rows.
+ *
+ * ptts_labels_match: V [P, nQS + nCQS] fp32 and status [P] int32 from P labels (one per phone).
+ *   labels     packed bytes [label_bytes], label_off [P+1] device int32 (clamped into the buffer);
+ *              max_label_len is the longest label as the host measured it: above
+ *              PTTS_LABELS_MAX_LABEL the call fails with PTTS_EINVAL before anything is launched.
+ *   patterns   pat_bytes [n_pat_bytes]; per pattern pat_off and pat_meta = length (low 16 bits)
+ *              | PTTS_LABELS_ANCHOR_START | PTTS_LABELS_ANCHOR_END | PTTS_LABELS_WILD (the pattern
+ *              holds '*' = any run of characters or '?' = one character).  A pattern is an HTK
+ *              question with its outer '*' stripped; without an anchor it may match anywhere.
+ *   QS         qs_first [nQS+1]: question q owns patterns qs_first[q] .. qs_first[q+1]-1; its
+ *              column is 1.0 when one of them matches, else 0.0.
+ *   CQS        cqs [nCQS][3] = {prefix pattern, suffix pattern, PTTS_LABELS_CAPTURE_*} (neither
+ *              pattern may hold '*'): leftmost prefix match, longest run of digits (and '.' for
+ *              _DECIMAL) behind it after which the suffix matches; the column is the captured
+ *              decimal -- integer mantissa / power of ten in fp64, rounded to fp32 -- or -1.0.
+ *   status[p]  0, or ((CQS index + 1) << 2) | PTTS_LABELS_ERR_* of the first CQS of label p whose
+ *              capture is not a number of at most 15 digits with at most one '.'.
+ * All tables are device memory; every index read from them is clamped.  No atomics, no workspace.
+ *
+ * ptts_labels_expand: X [T, Q + F] fp32 from V [P, Q] and seg [S][8] device int32 (16-byte
+ * aligned, as X): {phone row, first output row, frame_number, state_index, state_index_backward,
+ * phone_duration, state_duration_base, 0} per HMM state or phone, first rows ascending, T the end
+ * of the last.  Row r of segment s copies V[phone] and appends, with i = r - first row (ratios
+ * divided in fp64, rounded once to fp32):
+ *   PTTS_LABELS_FULL (F = 9)   (i+1)/fn, (fn-i)/fn, fn, state_index, state_index_backward, pd,
+ *                              fn/pd, (pd-i-base)/pd, (base+i+1)/pd
+ *   _MINIMAL_FRAME (2)         (i+1)/fn, state_index        _STATE_ONLY (1)  state_index
+ *   _MINIMAL_PHONEME (3)       (i+1)/fn, (fn-i)/fn, fn      _NONE (0)
+ *   _COARSE_CODING (4)         cc[0][300+k], cc[1][200+k], cc[2][100+k], pd with
+ *                              k = int((200/pd)*(base+i)); cc_table [3][PTTS_LABELS_CC_POINTS] fp32
+ * ------------------------------------------------------------------------------------- */
+#define PTTS_LABELS_MAX_LABEL       1024
+#define PTTS_LABELS_CC_POINTS       600
+#define PTTS_LABELS_ANCHOR_START    0x10000
+#define PTTS_LABELS_ANCHOR_END      0x20000
+#define PTTS_LABELS_WILD            0x40000
+#define PTTS_LABELS_CAPTURE_DIGITS  0
+#define PTTS_LABELS_CAPTURE_DECIMAL 1
+#define PTTS_LABELS_ERR_DIGITS      1
+#define PTTS_LABELS_ERR_FORMAT      2
+#define PTTS_LABELS_FULL            0
+#define PTTS_LABELS_MINIMAL_FRAME   1
+#define PTTS_LABELS_STATE_ONLY      2
+#define PTTS_LABELS_NONE            3
+#define PTTS_LABELS_MINIMAL_PHONEME 4
+#define PTTS_LABELS_COARSE_CODING   5
+int ptts_labels_feature_count(int mode);
+int ptts_labels_match(const unsigned char* labels, const int* label_off, int P, int label_bytes, int max_label_len,
+                      const unsigned char* pat_bytes, int n_pat_bytes, const int* pat_off, const int* pat_meta, int NP,
+                      const int* qs_first, int nQS, const int* cqs, int nCQS, float* V, int* status, void* stream);
+int ptts_labels_expand(const float* V, const int* seg, const float* cc_table, float* X, int P, int Q, int S, int T,
+                       int mode, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Random numbers: Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), counter-based.
  * Every number is a pure function of (seed, call counter, index); nothing is stored per thread
  * and no mask is kept.  Philox counter = (index lo, index hi, call lo, call hi), key = (seed

@@ -155,7 +155,10 @@ SIGNATURES = {
     'ptts_compose_sqdev_workspace_bytes': (c_sz, [c_i] * 2),
     'ptts_compose_sqdev': (c_i, [c_p] * 4 + [c_i, c_p, c_sz] + [c_i] * 3 + [c_p]),
     'ptts_compose_normalise': (c_i, [c_p] * 4 + [c_i, c_f, c_f, c_p, c_ll, c_i, c_i, c_p]),
-    'ptts_rng_seed': (c_i, [c_p, c_ull, c_ull, c_p]),
+    'ptts_labels_feature_count': (c_i, [c_i]),
+    'ptts_labels_match': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
+    'ptts_labels_expand': (c_i, [c_p] * 4 + [c_i] * 5 + [c_p]),
+    'ptts_rng_seed':(c_i, [c_p, c_ull, c_ull, c_p]),
     'ptts_rng_state_get': (c_i, [c_p, c_p, c_p]),
     'ptts_dropout_fwd': (c_i, [c_p] * 6 + [c_f, c_f] + [c_i] * 4 + [c_ll, c_p]),
     'ptts_dropout_bwd': (c_i, [c_p] * 4 + [c_f] + [c_i] * 3 + [c_ll, c_p]),

@@ -487,11 +487,11 @@ def create_weights_spec(specfeaturepath, fids, outfilepath, thresh=-32, dftlen=4
 def create_weights_lab(labpath, fids, outfilepath, lineheadregexp=r'([^\^]+)\^([^-]+)-([^\+]+)\+([^=]+)=([^@]+)@(.+)',
                        silencesymbol='sil', shift=0.005):
     """One weight per frame from an HTS label file: 0 over the segments whose centre phone is `silencesymbol`, 1 elsewhere.
-    `fids` is the path of the file-id list.  Some label formats use r'([^\\~]+)\\~([^-]+)-([^\\+]+)\\+([^=]+)=([^:]+):(.+)'."""
+    `fids` is the path of the file-id list (or the list of ids itself).  Some label formats use r'([^\\~]+)\\~([^-]+)-([^\\+]+)\\+([^=]+)=([^:]+):(.+)'."""
     makedirs(os.path.dirname(outfilepath))
     outfilepath, _ = data.getpathandshape(outfilepath)
     segment = re.compile(r'([0-9]+)\s+([0-9]+)\s+(.+)')
-    for fid in readids(fids):
+    for fid in (readids(fids) if isinstance(fids, str) else fids):
         print_tty('\r    Processing feature file {}                '.format(fid))
         with open(labpath.replace('*', fid)) as f:
             lines = f.readlines()

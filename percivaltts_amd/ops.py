@@ -2715,6 +2715,75 @@ def compose_normalise(y, a, b, mode=NORM_MEANSTD, scale=1.0, offset=0.0, keepidx
 
 
 # ----------------------------------------------------------------------------------------------
+# label front end (external/merlin/label_normalisation.py): csrc/labels.hip
+# ----------------------------------------------------------------------------------------------
+LABELS_MAX_LABEL = 1024                     # PTTS_LABELS_MAX_LABEL: bytes of a label the match kernel stages
+LABELS_CC_POINTS = 600
+LABELS_ANCHOR_START, LABELS_ANCHOR_END, LABELS_WILD = 0x10000, 0x20000, 0x40000
+LABELS_CAPTURE_DIGITS, LABELS_CAPTURE_DECIMAL = 0, 1
+LABELS_ERR_DIGITS, LABELS_ERR_FORMAT = 1, 2
+LABELS_MODES = {'full': 0, 'minimal_frame': 1, 'state_only': 2, 'none': 3, 'minimal_phoneme': 4, 'coarse_coding': 5}
+LABELS_FEATURES = {'full': 9, 'minimal_frame': 2, 'state_only': 1, 'none': 0, 'minimal_phoneme': 3, 'coarse_coding': 4}
+
+
+def labels_match(labels, label_off, max_label_len, table):
+    """labels: packed uint8 bytes of P labels, label_off [P+1] int32 (both device), max_label_len: the longest of them as the host
+    measured it; table: dict of device tensors pat_bytes (uint8), pat_off, pat_meta [NP], qs_first [nQS+1], cqs [nCQS,3] (int32;
+    None for an absent kind) as label_normalisation.QuestionSet.device_table builds it.  Returns V [P, nQS+nCQS] fp32 and
+    status [P] int32 (0, or the failed capture: see include/percival_hip.h)."""
+    if max_label_len > LABELS_MAX_LABEL:
+        raise ValueError('a label of {} bytes exceeds the {} the match kernel stages'.format(max_label_len, LABELS_MAX_LABEL))
+    _dev_tensor(labels, torch.uint8, 'labels_match.labels')
+    _dev_tensor(label_off, torch.int32, 'labels_match.label_off')
+    if label_off.dim() != 1 or label_off.numel() < 2:
+        raise ValueError('ops.labels_match: label_off {} is not [P+1]'.format(tuple(label_off.shape)))
+    P = label_off.numel() - 1
+    NP = table['pat_off'].numel()
+    _dev_tensor(table['pat_bytes'], torch.uint8, 'labels_match.pat_bytes')
+    _dev_tensor(table['pat_off'], torch.int32, 'labels_match.pat_off', (NP,))
+    _dev_tensor(table['pat_meta'], torch.int32, 'labels_match.pat_meta', (NP,))
+    nQS = nCQS = 0
+    if table.get('qs_first') is not None:
+        nQS = _dev_tensor(table['qs_first'], torch.int32, 'labels_match.qs_first').numel() - 1
+    if table.get('cqs') is not None:
+        nCQS = _dev_tensor(table['cqs'], torch.int32, 'labels_match.cqs').shape[0]
+    if nQS + nCQS < 1:
+        raise ValueError('ops.labels_match: the question table has no question')
+    V = torch.empty((P, nQS + nCQS), dtype=torch.float32, device=labels.device)
+    status = torch.empty(P, dtype=torch.int32, device=labels.device)
+    call('ptts_labels_match', ptr(labels), ptr(label_off), P, labels.numel(), int(max_label_len), ptr(table['pat_bytes']),
+         table['pat_bytes'].numel(), ptr(table['pat_off']), ptr(table['pat_meta']), NP, ptr(table.get('qs_first')), nQS,
+         ptr(table.get('cqs')), nCQS, ptr(V), ptr(status), stream(), tag=(P, nQS, nCQS))
+    return V, status
+
+
+def labels_expand(V, seg, T, subphone_feats, cc_table=None):
+    """V [P,Q] fp32, seg [S,8] int32 (phone row, first output row, frame_number, state_index, state_index_backward,
+    phone_duration, state_duration_base, 0; first rows ascending, T the end of the last) -> X [T, Q+F] fp32, F frame features of
+    `subphone_feats` (LABELS_MODES); cc_table [3,600] fp32 for 'coarse_coding'."""
+    if subphone_feats not in LABELS_MODES:
+        raise ValueError('ops.labels_expand: unknown subphone_feats {!r}'.format(subphone_feats))
+    f32c(V, 'labels_expand.V')
+    if V.dim() != 2 or min(V.shape) < 1:
+        raise ValueError('ops.labels_expand: V {} is not [P,Q]'.format(tuple(V.shape)))
+    _dev_tensor(seg, torch.int32, 'labels_expand.seg')
+    if seg.dim() != 2 or seg.shape[1] != 8 or seg.shape[0] < 1:
+        raise ValueError('ops.labels_expand: seg {} is not [S,8]'.format(tuple(seg.shape)))
+    if subphone_feats == 'coarse_coding':
+        _dev_tensor(cc_table, torch.float32, 'labels_expand.cc_table', (3, LABELS_CC_POINTS))
+    else:
+        cc_table = None
+    T = int(T)
+    if not 0 < T < 1 << 31:
+        raise ValueError('ops.labels_expand: T={} rows'.format(T))
+    P, Q = V.shape
+    X = torch.empty((T, Q + LABELS_FEATURES[subphone_feats]), dtype=torch.float32, device=V.device)
+    call('ptts_labels_expand', ptr(V), ptr(seg), ptr(cc_table), ptr(X), P, Q, seg.shape[0], T, LABELS_MODES[subphone_feats], stream(),
+         tag=(P, Q, seg.shape[0], T))
+    return X
+
+
+# ----------------------------------------------------------------------------------------------
 # WGAN-GP pieces (optimizertts_wgan.py:44-79)
 # ----------------------------------------------------------------------------------------------
 def gp_interpolate(real, fake, alpha_b, out=None):

@@ -1,10 +1,11 @@
 """Experiment script with the shape of the reference's percivaltts/run.py:57-230: a module-level `cfg`,
 `build_model()`, `training(cont)`, `generate()`.  The corpus-preparation stages of the reference
-(features_extraction / contexts_extraction: vocoder analysis and HTS label normalisation, run.py:147-180) need
-the pulsemodel/merlin front ends and are outside this build; `synthesize_corpus()` writes a synthetic corpus of
-the same on-disk format (headerless float32 `path:(-1,D)` files + file_id_list.scp) so that the training stages run
-unchanged.  `features_compose()` is the composition half of the reference's features_extraction (run.py:155-165): from raw
-per-stream feature files it writes the time weights and the composed, normalised outputs `cfg.outpath` points at
+split in two.  The vocoder analysis of features_extraction (run.py:147-154) needs the pulsemodel front end and is outside
+this build; `synthesize_corpus()` writes a synthetic corpus of the same on-disk format (headerless float32 `path:(-1,D)`
+files + file_id_list.scp) so that the training stages run unchanged.  `contexts_extraction()` is the reference's stage of
+that name (run.py:168-180): HTS labels through the label normaliser (percivaltts_amd.external.merlin, on the device), the
+time weights from the labels, and the min-max normalised inputs `cfg.inpath` points at.  `features_compose()` is the
+composition half of the reference's features_extraction (run.py:155-165): from raw per-stream feature files it writes the time weights and the composed, normalised outputs `cfg.outpath` points at
 (percivaltts_amd.compose, on the device).
 """
 from __future__ import print_function
@@ -99,6 +100,28 @@ def features_compose(rawpaths, fids=None, win_convention='mlpg'):
     normfn = compose.normalise_meanstd_nmnoscale if isinstance(vocoder, vocoders.VocoderPML) else compose.normalise_meanstd
     return compose.compose(outpaths, fids, cfg.outpath, id_valid_start=cfg.id_valid_start, normfn=normfn, wins=vocoder.mlpg_wins,
                            win_convention=win_convention)
+
+
+def contexts_extraction(lab_path, fids, lab_questions, labbin_path, labs_wpath, inpath, lab_type='state', id_valid_start=-1,
+                        shift=0.005):
+    """The reference's contexts_extraction (run.py:168-180).  lab_path: the HTS label files ('dir/*.lab'), state-aligned for
+    lab_type 'state' (sub-phone features 'full'), phone-aligned for any false value or 'phone' ('coarse_coding'); fids: the file
+    ids (a list, or the path of the id list); lab_questions: the HTK question file (the package ships none).  Writes the
+    un-normalised context matrices to labbin_path, one weight per frame (0 over 'sil') to labs_wpath, and the inputs, min-max
+    normalised to [-1, 1] from the statistics of the first `id_valid_start` files, to inpath (a ':(-1,D)' suffix on labbin_path /
+    inpath is ignored).  All files go through the normaliser in one call: a chunk of utterances is two kernel launches."""
+    from percivaltts_amd.external.merlin.label_normalisation import HTSLabelNormalisation
+    fids = readids(fids) if isinstance(fids, str) else list(fids)
+    state = bool(lab_type) and lab_type != 'phone'
+    normaliser = HTSLabelNormalisation(question_file_name=lab_questions, add_frame_features=True,
+                                       subphone_feats='full' if state else 'coarse_coding')
+    labbin_path = labbin_path.split(':')[0]
+    makedirs(os.path.dirname(labbin_path))
+    normaliser.perform_normalisation([lab_path.replace('*', fid) for fid in fids], [labbin_path.replace('*', fid) for fid in fids],
+                                     label_type='state_align' if state else 'phone_align')
+    compose.create_weights_lab(lab_path, fids, labs_wpath, silencesymbol='sil', shift=shift)
+    return compose.compose([labbin_path + ':(-1,' + str(normaliser.dimension) + ')'], fids, inpath, id_valid_start=id_valid_start,
+                           normfn=compose.normalise_minmax, wins=[], do_finalcheck=False)
 
 
 def build_model():

@@ -1,0 +1,102 @@
+"""Timing of the label front end (csrc/labels.hip, external/merlin/label_normalisation.py) on the fixtures of tests/golden/labels:
+host wall time and HIP-event time of the two launches at a corpus-sized batch, and files per second end to end.
+
+    python tools/labels_probe.py [--copies 70] [--files 100] [--reps 5]
+
+Prints one JSON line.  `match`: the fixtures' 144 phone labels replicated `copies` times (10 080 phones at 70, about 40 000 at 280) against the
+shipped question set; `expand`: their segment tables replicated the same way, GB/s against the T x 425 floats it has to write;
+`end_to_end`: `files` label files (the five fixtures, cycled) through perform_normalisation into a temporary directory, with the
+share of the wall time spent parsing text, on the device path (upload, two launches, download) and writing files.
+"""
+from __future__ import print_function
+
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+G = os.path.join(ROOT, 'tests', 'golden', 'labels')
+FIDS = ['arctic_a0002', 'arctic_a0004', 'arctic_a0005', 'arctic_a0006', 'arctic_a0008']
+
+
+def timed(fn, reps):
+    """(best wall ms including the stream synchronisation, best HIP-event ms of the launch) over `reps` calls after one warm-up."""
+    import torch
+    from percivaltts_amd import _hip
+    fn()
+    torch.cuda.synchronize()
+    wall, dev = [], []
+    for _ in range(reps):
+        with _hip.KernelTimer() as kt:
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            wall.append(1e3 * (time.perf_counter() - t0))
+        dev.append(sum(ms for _, _, ms in kt.durations_ms()))
+    return min(wall), min(dev)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--copies', type=int, default=70)
+    ap.add_argument('--files', type=int, default=100)
+    ap.add_argument('--reps', type=int, default=5)
+    args = ap.parse_args()
+    import torch
+    from percivaltts_amd import compose, ops
+    from percivaltts_amd.external.merlin import label_normalisation as ln
+    dev = compose._device()
+    norm = ln.HTSLabelNormalisation(os.path.join(G, 'questions-radio_dnn_416.hed'))
+    parsed = [norm._parse(os.path.join(G, 'label_state_align', fid + '.lab'), 'state_align') for fid in FIDS] * args.copies
+
+    phones, segs, p0, row = [], [], 0, 0
+    for ph, sg in parsed:
+        sg = np.concatenate([sg, np.zeros((len(sg), 1), np.int32)], axis=1)
+        sg[:, 0] += p0; sg[:, 1] += row
+        segs.append(sg); phones.extend(ph)
+        p0 += len(ph); row += int(sg[:, 2].sum())
+    off = np.zeros(len(phones) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(p) for p in phones])
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    labels_d, off_d, seg_d = to(np.frombuffer(b''.join(phones), dtype=np.uint8).copy()), to(off), to(np.concatenate(segs))
+    table = norm.questions.device_table(dev)
+    maxlen = max(len(p) for p in phones)
+    V, _ = ops.labels_match(labels_d, off_d, maxlen, table)
+    mw, md = timed(lambda: ops.labels_match(labels_d, off_d, maxlen, table), args.reps)
+    ew, ed = timed(lambda: ops.labels_expand(V, seg_d, row, 'full'), args.reps)
+    out_bytes = row * norm.dimension * 4
+    result = dict(device=torch.cuda.get_device_name(dev),
+                  match=dict(phones=len(phones), questions=norm.dict_size, patterns=len(norm.questions.patterns), label_bytes=int(off[-1]),
+                             wall_ms=round(mw, 3), event_ms=round(md, 3), us_per_phone=round(1e3 * md / len(phones), 4)),
+                  expand=dict(rows=row, width=norm.dimension, segments=int(seg_d.shape[0]), bytes_written=out_bytes, wall_ms=round(ew, 3),
+                              event_ms=round(ed, 3), write_GBps=round(out_bytes / (ed * 1e-3) / 1e9, 1)))
+
+    with tempfile.TemporaryDirectory() as d:
+        ins = [os.path.join(G, 'label_state_align', FIDS[i % len(FIDS)] + '.lab') for i in range(args.files)]
+        outs = [os.path.join(d, '{:05d}.lab'.format(i)) for i in range(args.files)]
+        norm.perform_normalisation(ins[:5], outs[:5])
+        t0 = time.perf_counter()
+        norm.perform_normalisation(ins, outs)
+        total = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        chunk = [norm._parse(f, 'state_align') for f in ins]
+        t_parse = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        X, offs = norm._run_chunk(chunk, dev)
+        t_device = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        for i, o in enumerate(outs): X[offs[i]:offs[i + 1]].tofile(o)
+        t_write = time.perf_counter() - t0
+    result['end_to_end'] = dict(files=args.files, frames=int(offs[-1]), seconds=round(total, 4), files_per_s=round(args.files / total, 1),
+                                parse_s=round(t_parse, 4), device_path_s=round(t_device, 4), write_s=round(t_write, 4))
+    print(json.dumps(result))
+
+
+if __name__ == '__main__':
+    main()
