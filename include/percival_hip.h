@@ -640,6 +640,47 @@ int ptts_compose_normalise(const float* y, const int* keepidx, const float* a, c
                            float offset, float* out, long long R, int Win, int Wout, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Spectral envelope decompression and the mel-cepstral post-filter (vocoders.py:147-166
+ * decompress_spectrum; external/merlin/generate_pp.py mcep_postproc_sptk).  L = dftlen (even,
+ * 8 .. 2^20), K = L/2 + 1 bins, w_k = 2 pi k / L, wt_k = w_k + 2 atan2(alpha sin w_k,
+ * 1 - alpha cos w_k), |alpha| < 1.  Rows are contiguous; fp32 in memory, fp64 arithmetic, one
+ * rounding of each result.  A frame's result depends on that frame only (no atomics).
+ *
+ *   logA_k(c) = sum_m c_m cos(m wt_k);   r0(x) = (1/L) (E_0 + E_{K-1} + 2 sum_{0<k<K-1} E_k),
+ *   E_k = exp(2 x_k)
+ *
+ * ptts_mcep_postfilter: out [T, M1] from mcep [T, M1], M1 = 2 .. 512.  With c' = c * [1, 1, pf,
+ *   pf, ...]:  out_0 = c_0 + ln(r0(logA(c)) / r0(logA(c'))) / 2,  out_m = c'_m (m >= 1).  One
+ *   pass, nothing of size [T, K] is stored.
+ * ptts_mcep2spec: spec [T, K] = exp(logA(c)) (log_out != 0: logA(c)); postfilter != 0: of the
+ *   post-filtered cepstrum, which is not stored.
+ * ptts_fwbnd2spec: fw [T, nb] log-amplitudes of nb = 2 .. 1024 bands with centres
+ *   f_b = 700 (exp(b mel(fs/2) / ((nb-1) 1127)) - 1), mel(f) = 1127 ln(1 + f/700);
+ *   logA_k = their linear interpolation (in Hz) at k fs / L.  postfilter != 0: with q_k the
+ *   trapezoid weights of the nodes wt_k on [0, pi], c_0 = (1/pi) sum q_k logA_k,
+ *   c_1 = (2/pi) sum q_k logA_k cos wt_k,  logA'_k = pf logA_k - (pf - 1) (c_0 + c_1 cos wt_k),
+ *   spec_k = exp(logA'_k + ln(r0(logA) / r0(logA')) / 2).
+ * T = 0 succeeds without a launch.
+ *
+ * Tables (device memory the CALLER keeps, one per parameter set; no device allocation here):
+ *   ptts_mcep_table   [M1][Kp] fp32, Kp = K rounded up to 4: cos(m wt_k), for (M1, alpha, dftlen)
+ *   ptts_fwbnd_table  [4][Kp] fp64: lower band, fraction, cos wt_k, q_k, for (nb, fs, alpha, dftlen)
+ * built by one small launch on `stream`; 32-byte aligned.  The entry points above take the table
+ * that was built with THEIR parameters: alpha (and fs, nb) are checked, the table's contents
+ * are not (band indices read from it are clamped).
+ * ------------------------------------------------------------------------------------- */
+size_t ptts_mcep_table_bytes(int M1, int dftlen);
+int ptts_mcep_table(float* table, size_t table_bytes, int M1, double alpha, int dftlen, void* stream);
+size_t ptts_fwbnd_table_bytes(int dftlen);
+int ptts_fwbnd_table(double* table, size_t table_bytes, int nb, double fs, double alpha, int dftlen, void* stream);
+int ptts_mcep_postfilter(const float* mcep, float* out, int T, int M1, double alpha, int dftlen, double pf_coef,
+                         const float* table, size_t table_bytes, void* stream);
+int ptts_mcep2spec(const float* mcep, float* spec, int T, int M1, double alpha, int dftlen, int log_out, int postfilter,
+                   double pf_coef, const float* table, size_t table_bytes, void* stream);
+int ptts_fwbnd2spec(const float* fw, float* spec, int T, int nb, double fs, double alpha, int dftlen, int log_out,
+                    int postfilter, double pf_coef, const double* table, size_t table_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Label front end (external/merlin/label_normalisation.py: pattern_matching_binary,
  * pattern_matching_continous_position, load_labels_with_state_alignment :661-710,
  * load_labels_with_phone_alignment :546-568): HTS full-context labels -> frame-level context rows.

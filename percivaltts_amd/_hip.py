@@ -12,6 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PTTS_LIB_PATH') or os.path.join(_HERE, 'lib', 'libpercival_hip.so')      # (PTTS_LIB_PATH: an A/B build of the library, tools/ab_define.sh)
 
+c_d = ctypes.c_double
 c_f = ctypes.c_float
 c_i = ctypes.c_int
 c_ll = ctypes.c_longlong
@@ -155,6 +156,13 @@ SIGNATURES = {
     'ptts_compose_sqdev_workspace_bytes': (c_sz, [c_i] * 2),
     'ptts_compose_sqdev': (c_i, [c_p] * 4 + [c_i, c_p, c_sz] + [c_i] * 3 + [c_p]),
     'ptts_compose_normalise': (c_i, [c_p] * 4 + [c_i, c_f, c_f, c_p, c_ll, c_i, c_i, c_p]),
+    'ptts_mcep_table_bytes': (c_sz, [c_i, c_i]),
+    'ptts_mcep_table': (c_i, [c_p, c_sz, c_i, c_d, c_i, c_p]),
+    'ptts_fwbnd_table_bytes': (c_sz, [c_i]),
+    'ptts_fwbnd_table': (c_i, [c_p, c_sz, c_i, c_d, c_d, c_i, c_p]),
+    'ptts_mcep_postfilter': (c_i, [c_p, c_p, c_i, c_i, c_d, c_i, c_d, c_p, c_sz, c_p]),
+    'ptts_mcep2spec': (c_i, [c_p, c_p, c_i, c_i, c_d, c_i, c_i, c_i, c_d, c_p, c_sz, c_p]),
+    'ptts_fwbnd2spec': (c_i, [c_p, c_p, c_i, c_i, c_d, c_d, c_i, c_i, c_i, c_d, c_p, c_sz, c_p]),
     'ptts_labels_feature_count': (c_i, [c_i]),
     'ptts_labels_match': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
     'ptts_labels_expand': (c_i, [c_p] * 4 + [c_i] * 5 + [c_p]),

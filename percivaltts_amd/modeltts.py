@@ -118,7 +118,7 @@ class ModelTTS:
         out = ops.mlpg(torch.from_numpy(np.ascontiguousarray(CMP)).to(dev), self.vocoder.mlpg_wins, std * std, mean=mean, std=std)
         return out.cpu().numpy()
 
-    def generate_params(self, inpath, outpath, fid_lst, gendir, do_objmeas=True, batch_size=8):
+    def generate_params(self, inpath, outpath, fid_lst, gendir, do_objmeas=True, batch_size=8, pp_mcep=False, specdir=None):
         """The reference's generate_wav (modeltts.py:144-205) up to the vocoder call: read mean4norm.dat / std4norm.dat beside
         `outpath`, predict each file of `fid_lst`, de-normalise (with MLPG when the vocoder has `mlpg_wins`), write
         `gendir/<fid>.cmp` as headerless float32 [T, featuressizeraw()], and, with `do_objmeas`, feed the vocoder's objective
@@ -129,7 +129,12 @@ class ModelTTS:
         the longest, each solved over its own length).  The network itself still sees ONE utterance per predict, as in the
         reference: padding would change what a context Conv1D or a BLSTM computes for an utterance's real frames wherever it
         looks across the pad, and the files must not depend on how they were batched.  Only the MLPG launch is batched; its
-        systems are independent, so the files are bit-identical for every `batch_size`."""
+        systems are independent, so the files are bit-identical for every `batch_size`.
+
+        With `specdir` each utterance's spectral columns also go through the vocoder's decompress_spectrum(pp_mcep=pp_mcep) while
+        they are on the device (csrc/spectrum.hip) and `specdir/<fid>.spec` is written as headerless float32 [T, dftlen/2+1]:
+        the envelope a waveform generator reads.  The .cmp files and the measures are what they are without it (the reference,
+        too, measures before the post-filter); without `specdir` no spectrum kernel is launched."""
         Ymean = np.fromfile(os.path.join(os.path.dirname(outpath), 'mean4norm.dat'), dtype='float32')
         Ystd = np.fromfile(os.path.join(os.path.dirname(outpath), 'std4norm.dat'), dtype='float32')
         nout, nraw = self.vocoder.featuressize(), self.vocoder.featuressizeraw()
@@ -146,6 +151,11 @@ class ModelTTS:
             X_test, y_test = data.croplen((X_test, y_test))
             self.vocoder.objmeasures_clear()
         if not os.path.isdir(gendir): os.makedirs(gendir)
+        if specdir is not None:
+            if not hasattr(self.vocoder, 'decompress_spectrum'):
+                raise ValueError('specdir given, but the vocoder {} has no spectral envelope to decompress'.format(self.vocoder.name()))
+            if not os.path.isdir(specdir): os.makedirs(specdir)
+            s0, s1 = 1, 1 + self.vocoder.specsize()
 
         if use_mlpg:
             dev = self.to_device()
@@ -169,10 +179,18 @@ class ModelTTS:
                     for i, y in enumerate(ys): ypad[i, :lens[i]] = y
                     gen = ops.mlpg(ypad, self.vocoder.mlpg_wins, var, mean=mean, std=std,
                                    lengths=torch.tensor(lens, dtype=torch.int32, device=dev))
+                if specdir is not None:
+                    specs = [self.vocoder.decompress_spectrum(gen[i, :lens[i], s0:s1], pp_mcep=pp_mcep) for i in range(len(ys))]
                 gen = gen.cpu().numpy()
                 CMPs = [gen[i, :lens[i]] for i in range(len(ys))]
             else:
                 CMPs = [self.denormalise(y.cpu().numpy(), Ymean, Ystd) for y in ys]
+                if specdir is not None:     # the .cmp values themselves, back on the device
+                    specs = [self.vocoder.decompress_spectrum(torch.from_numpy(np.ascontiguousarray(c[:, s0:s1])).to(self.to_device()),
+                                                              pp_mcep=pp_mcep) for c in CMPs]
+            if specdir is not None:
+                for vi, spec in zip(vis, specs):
+                    spec.cpu().numpy().tofile(os.path.join(specdir, fid_lst[vi] + '.spec'))
             for vi, CMP in zip(vis, CMPs):
                 CMP = np.ascontiguousarray(CMP, dtype=np.float32)
                 assert CMP.shape[1] == nraw

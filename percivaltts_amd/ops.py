@@ -2715,6 +2715,117 @@ def compose_normalise(y, a, b, mode=NORM_MEANSTD, scale=1.0, offset=0.0, keepidx
 
 
 # ----------------------------------------------------------------------------------------------
+# spectral envelope decompression and the mel-cepstral post-filter (vocoders.py:147-166,
+# external/merlin/generate_pp.py): csrc/spectrum.hip
+# ----------------------------------------------------------------------------------------------
+SPECTRUM_MAX_M1, SPECTRUM_MAX_NB, SPECTRUM_MAX_DFTLEN = 512, 1024, 1 << 20
+_spectrum_tables = {}       # (kind, device, parameters) -> device table; a function of its key only, so never stale
+
+
+def spectrum_check(dftlen, alpha, pf_coef):
+    """ValueError for a dftlen / alpha / pf_coef the spectrum kernels do not take.  Touches no device."""
+    if int(dftlen) != dftlen or dftlen < 8 or dftlen % 2 != 0 or dftlen > SPECTRUM_MAX_DFTLEN:
+        raise ValueError('dftlen={} has to be even, at least 8 and at most {}'.format(dftlen, SPECTRUM_MAX_DFTLEN))
+    if not -1.0 < float(alpha) < 1.0:
+        raise ValueError('|alpha|={} has to be below 1'.format(alpha))
+    if not 0.0 < float(pf_coef) < 1e6:
+        raise ValueError('pf_coef={} has to be positive'.format(pf_coef))
+
+
+def _spectrum_rows(x, name, lo, hi, what):
+    """[T,W] or [B,T,W] fp32 device rows -> (x, T_total, W); ValueError for a shape or width that cannot be, before f32c looks at
+    the device."""
+    if not torch.is_tensor(x) or x.dim() not in (2, 3):
+        raise ValueError('ops.{}: expected a [T,{w}] or [B,T,{w}] tensor'.format(name, w=what))
+    W = x.shape[-1]
+    if not lo <= W <= hi:
+        raise ValueError('ops.{}: {}={} outside [{}, {}]'.format(name, what, W, lo, hi))
+    if x.requires_grad:
+        raise ValueError('ops.{} has no backward pass: detach its input'.format(name))
+    rows = x.numel() // W
+    if rows >= 1 << 31:
+        raise ValueError('ops.{}: {} frames exceed the int32 frame count'.format(name, rows))
+    f32c(x, name)
+    return x, rows, W
+
+
+def _mcep_table(device, M1, alpha, dftlen):
+    key = ('mcep', device, M1, float(alpha), dftlen)
+    tab = _spectrum_tables.get(key)
+    if tab is None:
+        l = _hip.lib()
+        n = l.ptts_mcep_table_bytes(M1, dftlen)
+        tab = torch.empty(n // 4, dtype=torch.float32, device=device)
+        call('ptts_mcep_table', ptr(tab), n, M1, float(alpha), dftlen, stream(), tag=(M1, dftlen))
+        _spectrum_tables[key] = tab
+    return tab, tab.numel() * 4
+
+
+def _fwbnd_table(device, nb, fs, alpha, dftlen):
+    key = ('fwbnd', device, nb, float(fs), float(alpha), dftlen)
+    tab = _spectrum_tables.get(key)
+    if tab is None:
+        l = _hip.lib()
+        n = l.ptts_fwbnd_table_bytes(dftlen)
+        tab = torch.empty(n // 8, dtype=torch.float64, device=device)
+        call('ptts_fwbnd_table', ptr(tab), n, nb, float(fs), float(alpha), dftlen, stream(), tag=(nb, dftlen))
+        _spectrum_tables[key] = tab
+    return tab, tab.numel() * 8
+
+
+def bark_alpha(fs):
+    """The all-pass coefficient that approximates the Bark scale at sampling frequency fs (the reference's sp.bark_alpha)."""
+    import math
+    return 0.8517 * math.sqrt(math.atan(0.06583 * fs / 1000.0)) - 0.1916
+
+
+def mcep_postfilter(mcep, alpha, dftlen=4096, pf_coef=1.4):
+    """Merlin's formant-enhancing post-filter on mel-cepstra (csrc/spectrum.hip): mcep [T,M1] or [B,T,M1] fp32 device ->
+    same shape.  Coefficients 2.. are scaled by pf_coef; c_0 is corrected so that the frame's energy r0 is kept."""
+    spectrum_check(dftlen, alpha, pf_coef)
+    mcep, T, M1 = _spectrum_rows(mcep, 'mcep_postfilter', 2, SPECTRUM_MAX_M1, 'M1')
+    out = torch.empty_like(mcep)
+    if T == 0:
+        return out
+    tab, nb = _mcep_table(mcep.device, M1, alpha, dftlen)
+    call('ptts_mcep_postfilter', ptr(mcep), ptr(out), T, M1, float(alpha), int(dftlen), float(pf_coef), ptr(tab), nb, stream(),
+         tag=(T, M1, dftlen))
+    return out
+
+
+def mcep2spec(mcep, alpha, dftlen=4096, log=False, pp=False, pf_coef=1.4):
+    """Mel-cepstra [T,M1] or [B,T,M1] fp32 device -> amplitude envelope [.., dftlen/2+1] (`log`: its logarithm); `pp`: of the
+    post-filtered cepstrum, which is never stored (csrc/spectrum.hip)."""
+    spectrum_check(dftlen, alpha, pf_coef)
+    mcep, T, M1 = _spectrum_rows(mcep, 'mcep2spec', 2, SPECTRUM_MAX_M1, 'M1')
+    out = torch.empty(tuple(mcep.shape[:-1]) + (dftlen // 2 + 1,), dtype=torch.float32, device=mcep.device)
+    if T == 0:
+        return out
+    tab, nb = _mcep_table(mcep.device, M1, alpha, dftlen)
+    call('ptts_mcep2spec', ptr(mcep), ptr(out), T, M1, float(alpha), int(dftlen), int(bool(log)), int(bool(pp)), float(pf_coef),
+         ptr(tab), nb, stream(), tag=(T, M1, dftlen))
+    return out
+
+
+def fwbnd2spec(fw, fs, dftlen=4096, log=False, pp=False, pf_coef=1.4):
+    """Log-amplitudes of nb frequency-warped bands [T,nb] or [B,T,nb] fp32 device -> amplitude envelope [.., dftlen/2+1] (`log`:
+    its logarithm) by linear interpolation between the band centres; `pp`: with the spectral-domain post-filter
+    (csrc/spectrum.hip)."""
+    if not 0.0 < float(fs) < 1e9:
+        raise ValueError('fs={} has to be positive'.format(fs))
+    alpha = bark_alpha(fs)
+    spectrum_check(dftlen, alpha, pf_coef)
+    fw, T, nbands = _spectrum_rows(fw, 'fwbnd2spec', 2, SPECTRUM_MAX_NB, 'nb')
+    out = torch.empty(tuple(fw.shape[:-1]) + (dftlen // 2 + 1,), dtype=torch.float32, device=fw.device)
+    if T == 0:
+        return out
+    tab, nbytes = _fwbnd_table(fw.device, nbands, fs, alpha, dftlen)
+    call('ptts_fwbnd2spec', ptr(fw), ptr(out), T, nbands, float(fs), float(alpha), int(dftlen), int(bool(log)), int(bool(pp)),
+         float(pf_coef), ptr(tab), nbytes, stream(), tag=(T, nbands, dftlen))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # label front end (external/merlin/label_normalisation.py): csrc/labels.hip
 # ----------------------------------------------------------------------------------------------
 LABELS_MAX_LABEL = 1024                     # PTTS_LABELS_MAX_LABEL: bytes of a label the match kernel stages

@@ -148,8 +148,9 @@ def generate(fparams=None):
     mod.generate_cmp(cfg.inpath, os.path.splitext(fparams)[0] + '-gen/*.cmp', fid_lst_test)
     # where the reference calls generate_wav (run.py:218): everything of it up to the vocoder's synthesis
     demostart = cfg.id_test_demostart if hasattr(cfg, 'id_test_demostart') else 0
+    # cfg.specdir / cfg.pp_mcep, if present: also write the decompressed (post-filtered) spectral envelopes
     mod.generate_params(cfg.inpath, cfg.outpath, fid_lst_test[demostart:demostart + 10], os.path.splitext(fparams)[0] + '-demo-params',
-                        do_objmeas=True)
+                        do_objmeas=True, pp_mcep=getattr(cfg, 'pp_mcep', False), specdir=getattr(cfg, 'specdir', None))
 
 
 if __name__ == "__main__":

@@ -6,10 +6,18 @@ section 2, row 9).  The networks, the critic and the WGAN losses only need the f
 (vocoders.py:95-109,130-131,176-179,228-232), `fs`, `shift`, `mlpg_wins`, and the class identity that
 network_final switches on (networktts.py:195,212).  The objective measures of vocoders.py:112-117,209-218,333-342
 (`objmeasures_clear / objmeasures_add / objmeasures_stats`) are plain numpy on a few hundred kilobytes per utterance.
+`decompress_spectrum` (vocoders.py:147-166), the frame-wise step in front of the waveform generator, runs on the device
+(csrc/spectrum.hip).
 """
 from __future__ import print_function
 
 import numpy as np
+
+
+def bark_alpha(fs):
+    """All-pass coefficient of the Bark-like warping at sampling frequency fs (the reference's sigproc.bark_alpha)."""
+    from . import ops
+    return ops.bark_alpha(fs)
 
 
 def log2db(x):
@@ -66,6 +74,25 @@ class VocoderF0Spec(Vocoder):
     def f0size(self): return 1
     def specsize(self): return self.spec_size
 
+    def decompress_spectrum(self, COMPSPEC, spec_type=None, pp_mcep=False):
+        """Compressed spectral columns [T, spec_size] -> amplitude envelope [T, dftlen/2+1] (vocoders.py:147-166), on the device:
+        'fwbnd' log-bands by interpolation (ops.fwbnd2spec), 'mcep' mel-cepstra by ops.mcep2spec with alpha = bark_alpha(fs);
+        `pp_mcep` applies the formant-enhancing post-filter.  As in the reference the dispatch is on self.spec_type and the
+        `spec_type` argument is not looked at.  numpy in -> numpy out, device tensor in -> device tensor out."""
+        import torch
+        from . import backend_hip, ops
+        if self.spec_type not in ('fwbnd', 'mcep'):
+            raise ValueError("spec_type is 'fwbnd' or 'mcep', got {!r}".format(self.spec_type))
+        as_numpy = not torch.is_tensor(COMPSPEC)
+        x = COMPSPEC
+        if as_numpy:
+            x = torch.from_numpy(np.ascontiguousarray(COMPSPEC, dtype=np.float32)).to(backend_hip.device())
+        if self.spec_type == 'fwbnd':
+            SPEC = ops.fwbnd2spec(x.contiguous(), self.fs, dftlen=self.dftlen, pp=pp_mcep)
+        else:
+            SPEC = ops.mcep2spec(x.contiguous(), bark_alpha(self.fs), dftlen=self.dftlen, pp=pp_mcep)
+        return SPEC.cpu().numpy() if as_numpy else SPEC
+
     def _objmeasures_add_f0spec(self, CMP, REF):
         """F0[Hz]: RMS of the exp(f0) differences; SPEC[dB]: per-band RMS of the log2db differences."""
         self.features_err.setdefault('F0[Hz]', []).append(np.sqrt(np.mean((np.exp(REF[:, 0]) - np.exp(CMP[:, 0]))**2)))
@@ -80,8 +107,9 @@ class VocoderF0Spec(Vocoder):
 
 class VocoderPML(VocoderF0Spec):
     """f0 | spec | noise mask"""
-    def __init__(self, fs, shift, spec_size, nm_size, dftlen=4096, mlpg_wins=None):
-        VocoderF0Spec.__init__(self, 'PML', fs, shift, spec_size, 'fwbnd', dftlen, mlpg_wins=mlpg_wins)
+    def __init__(self, fs, shift, spec_size, nm_size, dftlen=4096, mlpg_wins=None, spec_type='fwbnd'):
+        # spec_type: a build extension (the reference hard-codes 'fwbnd' although its base class handles 'mcep')
+        VocoderF0Spec.__init__(self, 'PML', fs, shift, spec_size, spec_type, dftlen, mlpg_wins=mlpg_wins)
         self.nm_size = nm_size
 
     def featuressizeraw(self): return 1 + self.spec_size + self.nm_size
@@ -96,8 +124,8 @@ class VocoderPML(VocoderF0Spec):
 
 class VocoderWORLD(VocoderF0Spec):
     """f0 | spec | aperiodicity | vuv"""
-    def __init__(self, fs, shift, spec_size, aper_size, dftlen=4096, mlpg_wins=None):
-        VocoderF0Spec.__init__(self, 'WORLD', fs, shift, spec_size, 'fwbnd', dftlen, mlpg_wins=mlpg_wins)
+    def __init__(self, fs, shift, spec_size, aper_size, dftlen=4096, mlpg_wins=None, spec_type='fwbnd'):
+        VocoderF0Spec.__init__(self, 'WORLD', fs, shift, spec_size, spec_type, dftlen, mlpg_wins=mlpg_wins)
         self.aper_size = aper_size
 
     def featuressizeraw(self): return 1 + self.spec_size + self.aper_size + 1
