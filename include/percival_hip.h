@@ -681,6 +681,29 @@ int ptts_fwbnd2spec(const float* fw, float* spec, int T, int nb, double fs, doub
                     int postfilter, double pf_coef, const double* table, size_t table_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Pulse-and-noise waveform synthesis of the PML vocoder (csrc/pulsesynth.hip; the definition
+ * is this build's own).  L = dftlen, a power of two in 256 .. 8192 (anything
+ * else: PTTS_EINVAL without a launch), K = L/2 + 1.  fp32 in memory, fp64 arithmetic.
+ *
+ * ptts_noise_mask: nmb [T, nb] band values, f0 [T] Hz -> out [T, K]: the bands interpolated at
+ *   k fs / L with the band / fraction rows of ptts_fwbnd_table(nb, fs, ., dftlen), bins below
+ *   int(2 f0 L / fs) zeroed, thresholded (> 0.5 -> 1), smoothed along k by the 17 taps w * w,
+ *   w = hanning(9) / 4, over the odd extension of the row, clipped to [0, 1].
+ * ptts_pulse_segments: one workgroup per pulse; seg [P][W] gets the first winlen samples of
+ *   irfft(E ((1 - m) D + m N)) (the rest of a row is neither written nor read).  spec, mask
+ *   [T, K]; noise [wavlen] N(0,1) samples; itab [5][P] int32 rows start, winlen, lb, rb, fr
+ *   (winlen <= W <= L, 0 <= lb <= rb <= wavlen, 0 <= fr < T; a pulse whose row breaks this is
+ *   skipped); dtab [2][P] fp64 rows delay, f0.  P = 0 or T = 0 succeeds without a launch.
+ * ptts_pulse_overlap_add: wav[j] = sum over the pulses with start <= j < start + winlen of
+ *   seg[n][j - start], in pulse order, one lane per sample, no atomics; start is ascending.
+ * ------------------------------------------------------------------------------------- */
+int ptts_noise_mask(const float* nmb, const float* f0, float* out, int T, int nb, double fs, int dftlen, const double* table,
+                    size_t table_bytes, void* stream);
+int ptts_pulse_segments(const float* spec, const float* mask, const float* noise, const int* itab, const double* dtab, int P, int T,
+                        int dftlen, double fs, long long wavlen, float* seg, int W, void* stream);
+int ptts_pulse_overlap_add(const float* seg, const int* itab, int P, int W, float* wav, long long wavlen, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Label front end (external/merlin/label_normalisation.py: pattern_matching_binary,
  * pattern_matching_continous_position, load_labels_with_state_alignment :661-710,
  * load_labels_with_phone_alignment :546-568): HTS full-context labels -> frame-level context rows.

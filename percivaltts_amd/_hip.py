@@ -163,6 +163,9 @@ SIGNATURES = {
     'ptts_mcep_postfilter': (c_i, [c_p, c_p, c_i, c_i, c_d, c_i, c_d, c_p, c_sz, c_p]),
     'ptts_mcep2spec': (c_i, [c_p, c_p, c_i, c_i, c_d, c_i, c_i, c_i, c_d, c_p, c_sz, c_p]),
     'ptts_fwbnd2spec': (c_i, [c_p, c_p, c_i, c_i, c_d, c_d, c_i, c_i, c_i, c_d, c_p, c_sz, c_p]),
+    'ptts_noise_mask': (c_i, [c_p, c_p, c_p, c_i, c_i, c_d, c_i, c_p, c_sz, c_p]),
+    'ptts_pulse_segments': (c_i, [c_p] * 5 + [c_i, c_i, c_i, c_d, c_ll, c_p, c_i, c_p]),
+    'ptts_pulse_overlap_add': (c_i, [c_p, c_p, c_i, c_i, c_p, c_ll, c_p]),
     'ptts_labels_feature_count': (c_i, [c_i]),
     'ptts_labels_match': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
     'ptts_labels_expand': (c_i, [c_p] * 4 + [c_i] * 5 + [c_p]),

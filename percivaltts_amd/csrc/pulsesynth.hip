@@ -1,0 +1,411 @@
+// Pulse-and-noise waveform synthesis of the PML vocoder (the step behind the reference's vocoders.py:194-206, whose
+// pulsemodel submodule is absent from the reference checkout: the definition is this build's own).
+// Notation: L = dftlen, M = L/2, K = M + 1 bins, P pulses, one table row {start, winlen, lb, rb, fr | delay, f0} per pulse.
+//
+// noise mask       [T,nb] -> [T,K]: band values interpolated at k fs / L (band / fraction rows of ptts_fwbnd_table), bins below
+//                  int(2 f0 L / fs) zeroed, thresholded at 0.5, smoothed along k by the 17 taps h = w * w, w = hanning(9) / 4,
+//                  over the odd extension of the row (what a forward-backward pass of w does), clipped to [0, 1].
+// segment of pulse n, row fr of the envelope and of the mask:
+//                  la_k = ln(max(SPEC_k hp_k, 1e-10)),  hp_k = (1 + (tan(pi fcut / fs) / tan(pi k / L))^8)^(-1/2), fcut = f0_n / 2
+//                  c = irfft(la); c[1..M-1] *= 2, c[M+1..] = 0;  E = exp(rfft(c))              (minimum phase)
+//                  x = the normals g[lb..rb) at lb - start, tapered over 1 ms at both ends; N = rfft(x), scaled to the mean
+//                  spectral energy of a Dirac;  D_k = exp(-2 pi i delay k / L)
+//                  seg = irfft(E ((1 - m) D + m N))[0 .. winlen)
+// overlap-add      wav[j] = sum_n seg_n[j - start_n], in pulse order.
+//
+// A real transform of length L is a complex transform of length M on the packed sequence z[n] = x[2n] + i x[2n+1] plus one pass
+// over the bin pairs (k, M - k); the complex transform is radix-2 in LDS, decimation in frequency forwards (natural in, bit-reversed
+// out) and decimation in time backwards (bit-reversed in, natural out), so a spectrum lives at bit-reversed addresses and no
+// reordering pass exists.  X_0 and X_M of a real sequence are real and share slot 0.  One workgroup per pulse holds two such
+// buffers (E and the noise / the product) and a quarter circle of twiddles: 2.25 M complex fp64 = 72 KiB at L = 4096, 144 KiB at 8192.
+// Arithmetic is fp64 throughout, the segment is rounded to fp32 once.  The noise energy is summed inside the workgroup in a fixed
+// order (wave butterflies, then wave order through LDS); the overlap-add gathers, so nothing here uses an atomic and a result does
+// not depend on the grid.
+#include "common.h"
+
+namespace ptts {
+
+constexpr int PS_THREADS = 256;
+constexpr int PS_MIN_DFTLEN = 256, PS_MAX_DFTLEN = 8192;
+constexpr int PS_ITAB_ROWS = 5, PS_DTAB_ROWS = 2;      // {start, winlen, lb, rb, fr} int32 [5][P]; {delay, f0} fp64 [2][P]
+constexpr int NM_TAPS = 17, NM_HALF = 8;
+constexpr int NM_MAX_NB = 1024;
+
+struct NmTaps { double h[NM_TAPS]; };
+
+__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ double2 cconj(double2 a) { return make_double2(a.x, -a.y); }
+
+// exp(-2 pi i t / M), 0 <= t < M/2, from the quarter circle wq[0 .. M/4)
+__device__ __forceinline__ double2 twiddle(const double2* wq, int t, int Mq) {
+    if (t < Mq) return wq[t];
+    const double2 w = wq[t - Mq];
+    return make_double2(w.y, -w.x);
+}
+
+// exp(-2 pi i k / L)
+__device__ __forceinline__ double2 pair_twiddle(int k, int L) {
+    double s, c;
+    sincospi(2.0 * (double)k / (double)L, &s, &c);
+    return make_double2(c, -s);
+}
+
+__device__ __forceinline__ int bitrev(int k, int logM) { return (int)(__brev((unsigned)k) >> (32 - logM)); }
+
+// a[0..M) natural -> its transform at bit-reversed addresses
+__device__ void fft_forward(double2* a, const double2* wq, int logM) {
+    const int M = 1 << logM, Mq = M >> 2;
+    __syncthreads();
+    for (int s = logM - 1; s >= 0; --s) {
+        const int half = 1 << s;
+        for (int b = threadIdx.x; b < (M >> 1); b += blockDim.x) {
+            const int j = b & (half - 1), i = ((b >> s) << (s + 1)) | j;
+            const double2 u = a[i], v = a[i + half];
+            a[i] = cadd(u, v);
+            a[i + half] = cmul(csub(u, v), twiddle(wq, j << (logM - 1 - s), Mq));
+        }
+        __syncthreads();
+    }
+}
+
+// a spectrum at bit-reversed addresses -> M times its inverse transform, natural order
+__device__ void fft_inverse(double2* a, const double2* wq, int logM) {
+    const int M = 1 << logM, Mq = M >> 2;
+    __syncthreads();
+    for (int s = 0; s < logM; ++s) {
+        const int half = 1 << s;
+        for (int b = threadIdx.x; b < (M >> 1); b += blockDim.x) {
+            const int j = b & (half - 1), i = ((b >> s) << (s + 1)) | j;
+            const double2 u = a[i], v = cmul(a[i + half], cconj(twiddle(wq, j << (logM - 1 - s), Mq)));
+            a[i] = cadd(u, v);
+            a[i + half] = csub(u, v);
+        }
+        __syncthreads();
+    }
+}
+
+// Bins k and M - k (0 < k <= M/2) of the real sequence whose packed transform gave zk = Z[k], zm = Z[M-k].
+__device__ __forceinline__ void unpack_pair(double2 zk, double2 zm, double2 t, double2& xk, double2& xm) {
+    const double2 e = make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));
+    const double2 p = cmul(t, make_double2(0.5 * (zk.x - zm.x), 0.5 * (zk.y + zm.y)));
+    xk = make_double2(e.x + p.y, e.y - p.x);
+    xm = make_double2(e.x - p.y, -e.y - p.x);
+}
+
+// The inverse: Z[k] and Z[M-k] of the packed sequence from bins xk = X[k], xm = X[M-k]; t = exp(-2 pi i k / L).
+__device__ __forceinline__ void pack_pair(double2 xk, double2 xm, double2 t, double2& zk, double2& zm) {
+    const double2 a = make_double2(0.5 * (xk.x + xm.x), 0.5 * (xk.y - xm.y));
+    const double2 q = cmul(cconj(t), make_double2(0.5 * (xk.x - xm.x), 0.5 * (xk.y + xm.y)));
+    zk = make_double2(a.x - q.y, a.y + q.x);
+    zm = make_double2(a.x + q.y, -a.y + q.x);
+}
+
+// In place: the packed transform Z (bit-reversed addresses) -> bins X_k of the real sequence, X_0 and X_M in slot 0.
+__device__ void unpack_real(double2* a, int logM) {
+    const int M = 1 << logM, L = M << 1;
+    for (int k = threadIdx.x; k <= (M >> 1); k += blockDim.x) {
+        if (k == 0) {
+            const double2 z = a[0];
+            a[0] = make_double2(z.x + z.y, z.x - z.y);
+        } else if (k == (M >> 1)) {
+            const int r = bitrev(k, logM);
+            a[r] = cconj(a[r]);
+        } else {
+            const int rk = bitrev(k, logM), rm = bitrev(M - k, logM);
+            double2 xk, xm;
+            unpack_pair(a[rk], a[rm], pair_twiddle(k, L), xk, xm);
+            a[rk] = xk;
+            a[rm] = xm;
+        }
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ double block_sum(double v, double* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const double s = wave_sum(v);
+    __syncthreads();
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    double tot = red[0];
+    for (int w = 1; w < nwaves; ++w) tot += red[w];
+    return tot;
+}
+
+// ln(max(SPEC_k hp_k, 1e-10)); tc = tan(pi fcut / fs)
+__device__ __forceinline__ double log_amplitude(const float* __restrict__ row, int k, int L, double tc) {
+    double hp = 0.0;
+    if (k > 0) {
+        double s, c;
+        sincospi((double)k / (double)L, &s, &c);
+        const double r = tc * c / s, r2 = r * r, r4 = r2 * r2;
+        hp = 1.0 / sqrt(1.0 + r4 * r4);
+    }
+    const double v = (double)row[k] * hp;
+    return log(v > 1e-10 ? v : 1e-10);
+}
+
+// One workgroup per pulse.  dynamic LDS: (2 M + M/4) double2.
+__global__ __launch_bounds__(PS_THREADS) void pulse_segments_kernel(const float* __restrict__ spec, const float* __restrict__ mask,
+                                                                    const float* __restrict__ noise, const int* __restrict__ itab,
+                                                                    const double* __restrict__ dtab, const int P, const int T,
+                                                                    const int logM, const double fs, const int taper,
+                                                                    const long long wavlen, float* __restrict__ seg, const int W) {
+    extern __shared__ double2 lds[];
+    __shared__ double red[PS_THREADS / 64];
+    const int M = 1 << logM, L = M << 1, K = M + 1, Mq = M >> 2;
+    double2* bufe = lds;            // the minimum-phase chain, E at the end
+    double2* bufn = lds + M;        // the noise, then the product
+    double2* wq = lds + 2 * M;
+    const int n = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int start = itab[n], winlen = itab[P + n], lb = itab[2 * P + n], rb = itab[3 * P + n], fr = itab[4 * P + n];
+    const double delay = dtab[n], f0 = dtab[P + n];
+    // a row the host checks would have refused: nothing of it is read or written
+    if (winlen < 1 || winlen > W || winlen > L || fr < 0 || fr >= T || lb < 0 || rb > wavlen || rb < lb || !(f0 > 0.0)) return;
+    const float* srow = spec + (size_t)fr * K;
+    const float* mrow = mask + (size_t)fr * K;
+
+    for (int j = tid; j < Mq; j += nthr) {
+        double s, c;
+        sincospi(2.0 * (double)j / (double)M, &s, &c);
+        wq[j] = make_double2(c, -s);
+    }
+
+    // the noise segment, packed; position p of the frame holds g[start + p] for lb <= start + p < rb
+    const long long p0 = (long long)lb - start, p1 = (long long)rb - start;
+    const int len = rb - lb;
+    const bool tapered = taper > 0 && len >= 2 * (taper + 1);
+    for (int i = tid; i < M; i += nthr) {
+        double v[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const long long p = 2 * (long long)i + h;
+            v[h] = 0.0;
+            if (p >= p0 && p < p1) {
+                const int q = (int)(p - p0);
+                double g = (double)noise[(long long)lb + q];
+                if (tapered) {
+                    if (q <= taper) g *= 0.5 - 0.5 * cospi((double)q / (double)taper);
+                    if (len - 1 - q <= taper) g *= 0.5 - 0.5 * cospi((double)(len - 1 - q) / (double)taper);
+                }
+                v[h] = g;
+            }
+        }
+        bufn[i] = make_double2(v[0], v[1]);
+    }
+
+    // la is real: the packed spectrum of c = irfft(la)
+    double s0, c0;
+    sincospi(0.5 * f0 / fs, &s0, &c0);
+    const double tc = s0 / c0;
+    for (int k = tid; k <= (M >> 1); k += nthr) {
+        const double lk = log_amplitude(srow, k, L, tc), lm = log_amplitude(srow, M - k, L, tc);
+        double2 zk, zm;
+        pack_pair(make_double2(lk, 0.0), make_double2(lm, 0.0), pair_twiddle(k, L), zk, zm);
+        if (k == 0) {
+            bufe[0] = make_double2(0.5 * (lk + lm), 0.5 * (lk - lm));
+        } else {
+            bufe[bitrev(k, logM)] = zk;
+            if (k != (M >> 1)) bufe[bitrev(M - k, logM)] = zm;
+        }
+    }
+    fft_inverse(bufe, wq, logM);
+    // c[2i] + i c[2i+1] = bufe[i] / M; fold the cepstrum onto its causal half
+    const double inv_m = 1.0 / (double)M;
+    for (int i = tid; i < M; i += nthr) {
+        const double2 z = bufe[i];
+        double2 o = make_double2(0.0, 0.0);
+        if (i == 0) o = make_double2(z.x * inv_m, 2.0 * z.y * inv_m);
+        else if (i < (M >> 1)) o = make_double2(2.0 * z.x * inv_m, 2.0 * z.y * inv_m);
+        else if (i == (M >> 1)) o = make_double2(z.x * inv_m, 0.0);
+        bufe[i] = o;
+    }
+    fft_forward(bufe, wq, logM);
+    unpack_real(bufe, logM);
+    for (int k = tid; k < M; k += nthr) {
+        const int r = bitrev(k, logM);
+        const double2 c = bufe[r];
+        if (k == 0) {
+            bufe[0] = make_double2(exp(c.x), exp(c.y));       // E_0 and E_M, both real
+        } else {
+            double s, cs;
+            sincos(c.y, &s, &cs);
+            const double m = exp(c.x);
+            bufe[r] = make_double2(m * cs, m * s);
+        }
+    }
+
+    fft_forward(bufn, wq, logM);
+    unpack_real(bufn, logM);
+    double e = 0.0;
+    for (int k = tid; k < M; k += nthr) {
+        const double2 z = bufn[bitrev(k, logM)];
+        e += k == 0 ? z.x * z.x + z.y * z.y : 2.0 * (z.x * z.x + z.y * z.y);
+    }
+    e = block_sum(e, red) / (double)L;
+    const double gain = e > 0.0 ? 1.0 / sqrt(e) : 0.0;
+
+    // S = E ((1 - m) D + m N), packed for the inverse transform in the same pass
+    for (int k = tid; k <= (M >> 1); k += nthr) {
+        const int km = M - k, rk = bitrev(k, logM), rm = k == 0 ? 0 : bitrev(km, logM);
+        const double mk = (double)mrow[k], mm = (double)mrow[km];
+        double sk, ck, sm, cm;
+        sincospi(2.0 * delay * (double)k / (double)L, &sk, &ck);
+        sincospi(2.0 * delay * (double)km / (double)L, &sm, &cm);
+        if (k == 0) {
+            const double2 ev = bufe[0], nv = bufn[0];
+            const double x0 = ev.x * ((1.0 - mk) + mk * gain * nv.x);
+            const double xm = ev.y * ((1.0 - mm) * cm + mm * gain * nv.y);      // the real part: what irfft reads of bin M
+            bufn[0] = make_double2(0.5 * (x0 + xm), 0.5 * (x0 - xm));
+        } else {
+            const double2 nk = bufn[rk], nm = bufn[rm];
+            const double2 xk = cmul(bufe[rk], make_double2((1.0 - mk) * ck + mk * gain * nk.x, -(1.0 - mk) * sk + mk * gain * nk.y));
+            const double2 xm = cmul(bufe[rm], make_double2((1.0 - mm) * cm + mm * gain * nm.x, -(1.0 - mm) * sm + mm * gain * nm.y));
+            double2 zk, zm;
+            pack_pair(xk, xm, pair_twiddle(k, L), zk, zm);
+            bufn[rk] = zk;
+            if (k != (M >> 1)) bufn[rm] = zm;
+        }
+    }
+    fft_inverse(bufn, wq, logM);
+    float* out = seg + (size_t)n * W;
+    for (int p = tid; p < winlen; p += nthr) {
+        const double2 z = bufn[p >> 1];
+        out[p] = (float)(((p & 1) ? z.y : z.x) * inv_m);
+    }
+}
+
+// One lane per sample: the pulses whose window covers it lie between two binary searches over the ascending starts.
+__global__ __launch_bounds__(256) void pulse_overlap_add_kernel(const float* __restrict__ seg, const int* __restrict__ itab, const int P,
+                                                                const int W, float* __restrict__ wav, const long long wavlen) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= wavlen) return;
+    const int* start = itab;
+    const int* winlen = itab + P;
+    int lo = 0, hi = P;                                 // first pulse with start > j - W
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)start[mid] > j - W) hi = mid; else lo = mid + 1;
+    }
+    const int first = lo;
+    hi = P;                                             // first pulse with start > j
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)start[mid] > j) hi = mid; else lo = mid + 1;
+    }
+    double acc = 0.0;
+    for (int n = first; n < lo; ++n) {
+        const long long off = j - start[n];
+        const int wl = winlen[n];
+        if (off >= 0 && off < wl && wl <= W) acc += (double)seg[(size_t)n * W + off];
+    }
+    wav[j] = (float)acc;
+}
+
+// One workgroup per frame.  dynamic LDS: (K + 2 NM_HALF) floats (the thresholded row and its extension) + nb floats.
+__global__ __launch_bounds__(256) void noise_mask_kernel(const float* __restrict__ nmb, const float* __restrict__ f0,
+                                                         const double* __restrict__ tab, float* __restrict__ out, const int nb,
+                                                         const int K, const int Kp, const int L, const double fs, const NmTaps taps) {
+    extern __shared__ float nm_lds[];
+    float* x = nm_lds + NM_HALF;                        // x[-8 .. K + 8)
+    float* sb = nm_lds + K + 2 * NM_HALF;               // the frame's bands
+    const int t = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    for (int i = tid; i < nb; i += nthr) sb[i] = nmb[(size_t)t * nb + i];
+    __syncthreads();
+    const int kcut = (int)(2.0 * (double)f0[t] * (double)L / fs);
+    for (int k = tid; k < K; k += nthr) {
+        int b = (int)tab[k];
+        b = b < 0 ? 0 : (b > nb - 2 ? nb - 2 : b);      // whatever the table holds
+        const double lo = (double)sb[b], hi = (double)sb[b + 1];
+        const double v = fma(tab[(size_t)Kp + k], hi - lo, lo);
+        x[k] = (k >= kcut && v > 0.5) ? 1.f : 0.f;
+    }
+    __syncthreads();
+    if (tid < NM_HALF) {
+        const int j = tid + 1;
+        x[-j] = 2.f * x[0] - x[j];
+        x[K - 1 + j] = 2.f * x[K - 1] - x[K - 1 - j];
+    }
+    __syncthreads();
+    for (int k = tid; k < K; k += nthr) {
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < NM_TAPS; ++i) acc += taps.h[i] * (double)x[k + i - NM_HALF];
+        out[(size_t)t * K + k] = (float)(acc < 0.0 ? 0.0 : (acc > 1.0 ? 1.0 : acc));
+    }
+}
+
+static int ps_log2(int dftlen) {
+    for (int l = 8; l <= 13; ++l)
+        if (dftlen == (1 << l)) return l;
+    return -1;
+}
+
+}  // namespace ptts
+
+using namespace ptts;
+
+extern "C" int ptts_noise_mask(const float* nmb, const float* f0, float* out, int T, int nb, double fs, int dftlen,
+                               const double* table, size_t table_bytes, void* stream) {
+    PTTS_REQUIRE(T >= 0, "noise_mask: T=%d", T);
+    PTTS_REQUIRE(nb >= 2 && nb <= NM_MAX_NB, "noise_mask: nb=%d outside [2, %d]", nb, NM_MAX_NB);
+    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "noise_mask: fs=%g", fs);
+    PTTS_REQUIRE(ps_log2(dftlen) > 0, "noise_mask: dftlen=%d is not a power of two in [%d, %d]", dftlen, PS_MIN_DFTLEN, PS_MAX_DFTLEN);
+    if (T == 0) return PTTS_OK;
+    PTTS_REQUIRE(nmb && f0 && out && table, "noise_mask: null tensor");
+    const int K = dftlen / 2 + 1, Kp = (K + 3) / 4 * 4;
+    PTTS_REQUIRE(((size_t)table & 31) == 0 && table_bytes >= ptts_fwbnd_table_bytes(dftlen),
+                 "noise_mask: the table of ptts_fwbnd_table(dftlen=%d) needs %zu aligned bytes, got %zu", dftlen,
+                 ptts_fwbnd_table_bytes(dftlen), table_bytes);
+    // h = w * w, w = hanning(9) / 4
+    NmTaps taps;
+    double w[9];
+    for (int i = 0; i < 9; ++i) w[i] = (0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * i / 8.0)) / 4.0;
+    for (int i = 0; i < NM_TAPS; ++i) {
+        double s = 0.0;
+        for (int j = 0; j < 9; ++j)
+            if (i - j >= 0 && i - j < 9) s += w[j] * w[i - j];
+        taps.h[i] = s;
+    }
+    const size_t lds = (size_t)(K + 2 * NM_HALF + nb) * sizeof(float);
+    hipLaunchKernelGGL(noise_mask_kernel, dim3(T), dim3(256), lds, (hipStream_t)stream, nmb, f0, table, out, nb, K, Kp, dftlen, fs,
+                       taps);
+    return check_launch("noise_mask");
+}
+
+extern "C" int ptts_pulse_segments(const float* spec, const float* mask, const float* noise, const int* itab, const double* dtab,
+                                   int P, int T, int dftlen, double fs, long long wavlen, float* seg, int W, void* stream) {
+    PTTS_REQUIRE(P >= 0 && T >= 0 && wavlen >= 0, "pulse_segments: P=%d T=%d wavlen=%lld", P, T, wavlen);
+    const int logL = ps_log2(dftlen);
+    PTTS_REQUIRE(logL > 0, "pulse_segments: dftlen=%d is not a power of two in [%d, %d]", dftlen, PS_MIN_DFTLEN, PS_MAX_DFTLEN);
+    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "pulse_segments: fs=%g", fs);
+    PTTS_REQUIRE(W >= 1 && W <= dftlen, "pulse_segments: W=%d outside [1, dftlen]", W);
+    if (P == 0 || T == 0) return PTTS_OK;
+    PTTS_REQUIRE(spec && mask && itab && dtab && seg && (noise || wavlen == 0), "pulse_segments: null tensor");
+    const int M = dftlen / 2;
+    const int lds = (2 * M + M / 4) * (int)sizeof(double2);
+    static int lds_reserved = 0;
+    if (lds > lds_reserved) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pulse_segments_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) { set_error("pulse_segments: cannot reserve %d B of LDS: %s", lds, hipGetErrorString(e)); return PTTS_ELAUNCH; }
+        lds_reserved = lds;
+    }
+    const int threads = M / 4 < 64 ? 64 : (M / 4 > PS_THREADS ? PS_THREADS : M / 4);
+    const int taper = (int)floor(0.001 * fs + 0.5);
+    hipLaunchKernelGGL(pulse_segments_kernel, dim3(P), dim3(threads), (size_t)lds, (hipStream_t)stream, spec, mask, noise, itab, dtab,
+                       P, T, logL - 1, fs, taper, wavlen, seg, W);
+    return check_launch("pulse_segments");
+}
+
+extern "C" int ptts_pulse_overlap_add(const float* seg, const int* itab, int P, int W, float* wav, long long wavlen, void* stream) {
+    PTTS_REQUIRE(P >= 0 && W >= 1 && wavlen >= 0, "pulse_overlap_add: P=%d W=%d wavlen=%lld", P, W, wavlen);
+    if (wavlen == 0) return PTTS_OK;
+    PTTS_REQUIRE(wav && (P == 0 || (seg && itab)), "pulse_overlap_add: null tensor");
+    PTTS_REQUIRE((wavlen + 255) / 256 < (1LL << 31), "pulse_overlap_add: wavlen=%lld", wavlen);
+    hipLaunchKernelGGL(pulse_overlap_add_kernel, dim3((unsigned)((wavlen + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seg, itab,
+                       P, W, wav, wavlen);
+    return check_launch("pulse_overlap_add");
+}

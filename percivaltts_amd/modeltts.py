@@ -4,8 +4,9 @@ Holds `.ctxsize .vocoder .kerasmodel`; `kerasmodel` keeps its name for drop-in c
 percivaltts_amd.layers.Model running on HIP kernels.  predict / count_params / save / load follow
 modeltts.py:68-130; the model file trio keeps its stems (`.arch.json`, `.weights.npz` in place of `.weights.h5`
 because h5py is not part of this image, `.cfgextras.pkl`).  generate_params is generate_wav (modeltts.py:144-205) up to
-the vocoder call: de-normalisation, MLPG on the device (csrc/mlpg.hip), parameter files and objective measures.  Only the
-waveform synthesis itself needs the vocoder DSP and stays out of scope.
+the vocoder call: de-normalisation, MLPG on the device (csrc/mlpg.hip), parameter files and objective measures.  The
+reference's own waveform needs the vocoder DSP it delegates to and stays out of scope; with `wavdir`
+generate_params writes the waveform of the build's pulse-and-noise synthesiser (csrc/pulsesynth.hip) instead.
 """
 from __future__ import print_function
 
@@ -118,7 +119,8 @@ class ModelTTS:
         out = ops.mlpg(torch.from_numpy(np.ascontiguousarray(CMP)).to(dev), self.vocoder.mlpg_wins, std * std, mean=mean, std=std)
         return out.cpu().numpy()
 
-    def generate_params(self, inpath, outpath, fid_lst, gendir, do_objmeas=True, batch_size=8, pp_mcep=False, specdir=None):
+    def generate_params(self, inpath, outpath, fid_lst, gendir, do_objmeas=True, batch_size=8, pp_mcep=False, specdir=None,
+                        wavdir=None):
         """The reference's generate_wav (modeltts.py:144-205) up to the vocoder call: read mean4norm.dat / std4norm.dat beside
         `outpath`, predict each file of `fid_lst`, de-normalise (with MLPG when the vocoder has `mlpg_wins`), write
         `gendir/<fid>.cmp` as headerless float32 [T, featuressizeraw()], and, with `do_objmeas`, feed the vocoder's objective
@@ -134,7 +136,12 @@ class ModelTTS:
         With `specdir` each utterance's spectral columns also go through the vocoder's decompress_spectrum(pp_mcep=pp_mcep) while
         they are on the device (csrc/spectrum.hip) and `specdir/<fid>.spec` is written as headerless float32 [T, dftlen/2+1]:
         the envelope a waveform generator reads.  The .cmp files and the measures are what they are without it (the reference,
-        too, measures before the post-filter); without `specdir` no spectrum kernel is launched."""
+        too, measures before the post-filter); without `specdir` no spectrum kernel is launched.
+
+        With `wavdir` each utterance's generated parameters also go through the vocoder's synthesis_device(pp_mcep=pp_mcep) while
+        they are on the device (csrc/pulsesynth.hip) and `wavdir/<fid>.wav` is written as 16-bit PCM at the vocoder's fs; the noise
+        comes from the library's generator (ops.rng_seed).  The .cmp and .spec files are what they are without it.  A vocoder
+        without synthesis_device is a ValueError."""
         Ymean = np.fromfile(os.path.join(os.path.dirname(outpath), 'mean4norm.dat'), dtype='float32')
         Ystd = np.fromfile(os.path.join(os.path.dirname(outpath), 'std4norm.dat'), dtype='float32')
         nout, nraw = self.vocoder.featuressize(), self.vocoder.featuressizeraw()
@@ -156,6 +163,11 @@ class ModelTTS:
                 raise ValueError('specdir given, but the vocoder {} has no spectral envelope to decompress'.format(self.vocoder.name()))
             if not os.path.isdir(specdir): os.makedirs(specdir)
             s0, s1 = 1, 1 + self.vocoder.specsize()
+        if wavdir is not None:
+            if not hasattr(self.vocoder, 'synthesis_device'):
+                raise ValueError('wavdir given, but the vocoder {} has no waveform synthesis in this build'.format(self.vocoder.name()))
+            from . import vocoders
+            if not os.path.isdir(wavdir): os.makedirs(wavdir)
 
         if use_mlpg:
             dev = self.to_device()
@@ -181,6 +193,8 @@ class ModelTTS:
                                    lengths=torch.tensor(lens, dtype=torch.int32, device=dev))
                 if specdir is not None:
                     specs = [self.vocoder.decompress_spectrum(gen[i, :lens[i], s0:s1], pp_mcep=pp_mcep) for i in range(len(ys))]
+                if wavdir is not None:
+                    wavs = [self.vocoder.synthesis_device(gen[i, :lens[i]], pp_mcep=pp_mcep) for i in range(len(ys))]
                 gen = gen.cpu().numpy()
                 CMPs = [gen[i, :lens[i]] for i in range(len(ys))]
             else:
@@ -188,9 +202,15 @@ class ModelTTS:
                 if specdir is not None:     # the .cmp values themselves, back on the device
                     specs = [self.vocoder.decompress_spectrum(torch.from_numpy(np.ascontiguousarray(c[:, s0:s1])).to(self.to_device()),
                                                               pp_mcep=pp_mcep) for c in CMPs]
+                if wavdir is not None:
+                    wavs = [self.vocoder.synthesis_device(torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)).to(self.to_device()),
+                                                          pp_mcep=pp_mcep) for c in CMPs]
             if specdir is not None:
                 for vi, spec in zip(vis, specs):
                     spec.cpu().numpy().tofile(os.path.join(specdir, fid_lst[vi] + '.spec'))
+            if wavdir is not None:
+                for vi, wav in zip(vis, wavs):
+                    vocoders.wavwrite(os.path.join(wavdir, fid_lst[vi] + '.wav'), wav, self.vocoder.fs)
             for vi, CMP in zip(vis, CMPs):
                 CMP = np.ascontiguousarray(CMP, dtype=np.float32)
                 assert CMP.shape[1] == nraw
@@ -203,5 +223,7 @@ class ModelTTS:
         return stats
 
     def generate_wav(self, *args, **kwargs):
+        """The reference's name promises pulsemodel's (or pyworld's) waveform, which this build does not have.  The build's own
+        synthesiser is reached through generate_params(..., wavdir=...)."""
         raise NotImplementedError('waveform synthesis needs the vocoder DSP (pulsemodel/pyworld), outside this build; '
                                   'generate_params writes the de-normalised (MLPG) parameters a vocoder would read')

@@ -2826,6 +2826,158 @@ def fwbnd2spec(fw, fs, dftlen=4096, log=False, pp=False, pf_coef=1.4):
 
 
 # ----------------------------------------------------------------------------------------------
+# pulse-and-noise waveform synthesis of the PML vocoder (the step behind vocoders.py:194-206): csrc/pulsesynth.hip
+# ----------------------------------------------------------------------------------------------
+PULSE_MIN_DFTLEN, PULSE_MAX_DFTLEN = 256, 8192
+PULSE_F0_FLOOR = 50.0
+PULSE_INT_ROWS = ('start', 'winlen', 'lb', 'rb', 'fr')
+
+
+def pulse_check(dftlen, fs):
+    """ValueError for a dftlen / fs the synthesis kernels do not take.  Touches no device."""
+    if int(dftlen) != dftlen or not PULSE_MIN_DFTLEN <= dftlen <= PULSE_MAX_DFTLEN or dftlen & (dftlen - 1):
+        raise ValueError('dftlen={} has to be a power of two in [{}, {}]'.format(dftlen, PULSE_MIN_DFTLEN, PULSE_MAX_DFTLEN))
+    if not 0.0 < float(fs) < 1e9:
+        raise ValueError('fs={} has to be positive'.format(fs))
+
+
+def _rnd(x):
+    import math
+    return int(math.floor(x + 0.5))
+
+
+def pulse_table(f0, shift, fs, wavlen, dftlen):
+    """The pulse positions of one utterance and everything the kernels need per pulse, on the host in fp64:
+    f0 [T] in Hz at the frame times shift * i (values below 50 Hz are synthesised at 50 Hz), wavlen = round(shift (T-1) fs).
+    Returns a dict of numpy arrays, one entry per pulse: 't' fp64 (t_0 = 0, t_{n+1} = t_n + 1 / f0(t_n), the last one at or beyond
+    the end), the int32 rows 'start', 'winlen', 'lb', 'rb', 'fr' and the fp64 rows 'delay', 'f0'.  The noise segments [lb, rb) tile
+    [0, wavlen).  ValueError when a window does not fit dftlen."""
+    import numpy as np
+    pulse_check(dftlen, fs)
+    f0 = np.ascontiguousarray(f0, dtype=np.float64)
+    if f0.ndim != 1 or f0.size < 1 or not (np.isfinite(f0).all() and (f0 > 0).all()):
+        raise ValueError('ops.pulse_table: f0 has to be [T] positive finite Hz values')
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('ops.pulse_table: shift={}'.format(shift))
+    T, fs, shift = f0.size, float(fs), float(shift)
+    if int(wavlen) != int(round(shift * (T - 1) * fs)) or wavlen >= 1 << 31:
+        raise ValueError('ops.pulse_table: wavlen={} is not round(shift (T-1) fs) = {}'.format(wavlen, int(round(shift * (T - 1) * fs))))
+    wavlen = int(wavlen)
+    times = shift * np.arange(T)
+    f0_at = lambda x: max(float(np.interp(x, times, f0)), PULSE_F0_FLOOR)
+    t = [0.0]
+    while t[-1] < wavlen / fs:
+        t.append(t[-1] + 1.0 / f0_at(t[-1]))
+    P = len(t)
+    tab = {'t': np.array(t, dtype=np.float64), 'delay': np.zeros(P, dtype=np.float64), 'f0': np.zeros(P, dtype=np.float64)}
+    for key in PULSE_INT_ROWS:
+        tab[key] = np.zeros(P, dtype=np.int32)
+    for n in range(P):
+        f0n = f0_at(t[n])
+        winlen = 2 * int(max(0.050 * fs, 4.0 * fs / f0n) / 2) + 1
+        if winlen > dftlen:
+            raise ValueError('ops.pulse_table: the window of pulse {} ({} samples at f0 = {:.1f} Hz) does not fit dftlen={}'.format(
+                n, winlen, f0n, dftlen))
+        pos = int(winlen / 4)
+        c = _rnd(fs * t[n])
+        lb = _rnd(fs * (t[n - 1] + t[n]) / 2) if n > 0 else _rnd(fs * (t[n] - 0.5 / f0n))
+        rb = _rnd(fs * (t[n] + t[n + 1]) / 2) if n < P - 1 else _rnd(fs * (t[n] + 0.5 / f0n))
+        tab['start'][n], tab['winlen'][n] = c - pos, winlen
+        tab['lb'][n], tab['rb'][n] = min(max(lb, 0), wavlen), min(max(rb, 0), wavlen)
+        tab['fr'][n] = min(max(_rnd(t[n] / shift), 0), T - 1)
+        tab['delay'][n], tab['f0'][n] = pos + (fs * t[n] - c), f0n
+    return tab
+
+
+def _pulse_table_rows(table, T, dftlen, wavlen):
+    """(itab [5,P] int32, dtab [2,P] fp64, W) of a pulse table after the checks that keep the kernels inside their buffers."""
+    import numpy as np
+    try:
+        rows = [np.asarray(table[k]) for k in PULSE_INT_ROWS + ('delay', 'f0')]
+    except (KeyError, TypeError, IndexError):
+        raise ValueError('ops.pulse_synthesis: table is what ops.pulse_table returns')
+    P = rows[0].shape[0] if rows[0].ndim == 1 else -1
+    if any(r.shape != (P,) for r in rows):
+        raise ValueError('ops.pulse_synthesis: the rows of the table are not all [P]')
+    itab = np.ascontiguousarray(np.stack(rows[:5]) if P else np.zeros((5, 0)), dtype=np.int64)
+    dtab = np.ascontiguousarray(np.stack(rows[5:]) if P else np.zeros((2, 0)), dtype=np.float64)
+    if P == 0:
+        return itab.astype(np.int32), dtab, 1
+    start, winlen, lb, rb, fr = itab
+    if winlen.min() < 1 or winlen.max() > dftlen:
+        raise ValueError('ops.pulse_synthesis: a window of {} samples does not fit dftlen={}'.format(winlen.max(), dftlen))
+    if (np.diff(start) < 0).any():
+        raise ValueError('ops.pulse_synthesis: the pulses\' start samples have to ascend (f0 falls too fast between two pulses)')
+    filled = rb > lb
+    if lb.min() < 0 or rb.max() > wavlen or (rb < lb).any() or (filled & ((lb < start) | (rb - start > dftlen))).any():
+        raise ValueError('ops.pulse_synthesis: a noise segment lies outside the waveform or its pulse\'s frame')
+    if fr.min() < 0 or fr.max() >= T:
+        raise ValueError('ops.pulse_synthesis: frame {} of the table is outside the {} frames given'.format(fr.max(), T))
+    if not (np.isfinite(dtab).all() and (dtab[1] > 0).all()):
+        raise ValueError('ops.pulse_synthesis: delay / f0 of the table are not finite and positive')
+    if np.abs(start).max() >= 1 << 30:
+        raise ValueError('ops.pulse_synthesis: a start sample exceeds the int32 table')
+    return itab.astype(np.int32), dtab, int(winlen.max())
+
+
+def noise_mask(nmb, f0, fs, dftlen=4096):
+    """Noise-mask bands [T,nb] in [0,1] and f0 [T] in Hz (fp32 device) -> the binary mask smoothed along frequency, [T, dftlen/2+1]
+    (csrc/pulsesynth.hip): interpolation at k fs / dftlen on the band axis of fwbnd2spec, zero below the second harmonic, threshold at
+    0.5, a forward-backward pass of hanning(9), clip."""
+    pulse_check(dftlen, fs)
+    if not torch.is_tensor(nmb) or nmb.dim() != 2 or not 2 <= nmb.shape[1] <= SPECTRUM_MAX_NB:
+        raise ValueError('ops.noise_mask: expected a [T,nb] tensor with nb in [2, {}]'.format(SPECTRUM_MAX_NB))
+    T, nbands = nmb.shape
+    if not torch.is_tensor(f0) or tuple(f0.shape) != (T,):
+        raise ValueError('ops.noise_mask: f0 is not [{}]'.format(T))
+    if nmb.requires_grad or f0.requires_grad:
+        raise ValueError('ops.noise_mask has no backward pass: detach its input')
+    f32c(nmb, 'noise_mask.nmb'); f32c(f0, 'noise_mask.f0')
+    out = torch.empty((T, dftlen // 2 + 1), dtype=torch.float32, device=nmb.device)
+    if T == 0:
+        return out
+    tab, nbytes = _fwbnd_table(nmb.device, nbands, fs, bark_alpha(fs), dftlen)
+    call('ptts_noise_mask', ptr(nmb), ptr(f0), ptr(out), T, nbands, float(fs), int(dftlen), ptr(tab), nbytes, stream(),
+         tag=(T, nbands, dftlen))
+    return out
+
+
+def pulse_synthesis(spec, mask, table, noise, fs, dftlen, wavlen):
+    """The waveform [wavlen] (fp32 device) of one utterance: spec and mask [T, dftlen/2+1] fp32 device, table from
+    ops.pulse_table (host), noise [wavlen] N(0,1) fp32 device.  One workgroup per pulse builds its segment (minimum-phase envelope
+    times the mix of a delayed pulse and the pulse's stretch of the noise), then one lane per sample adds the segments that cover
+    it, in pulse order (csrc/pulsesynth.hip).  Same input, same bytes."""
+    import numpy as np
+    pulse_check(dftlen, fs)
+    K = dftlen // 2 + 1
+    if not torch.is_tensor(spec) or spec.dim() != 2 or spec.shape[1] != K:
+        raise ValueError('ops.pulse_synthesis: spec is not [T,{}]'.format(K))
+    T = spec.shape[0]
+    if not torch.is_tensor(mask) or tuple(mask.shape) != (T, K):
+        raise ValueError('ops.pulse_synthesis: mask is not [{},{}]'.format(T, K))
+    wavlen = int(wavlen)
+    if wavlen < 0 or not torch.is_tensor(noise) or tuple(noise.shape) != (wavlen,):
+        raise ValueError('ops.pulse_synthesis: noise is not [wavlen={}]'.format(wavlen))
+    if spec.requires_grad or mask.requires_grad or noise.requires_grad:
+        raise ValueError('ops.pulse_synthesis has no backward pass: detach its input')
+    f32c(spec, 'pulse_synthesis.spec'); f32c(mask, 'pulse_synthesis.mask'); f32c(noise, 'pulse_synthesis.noise')
+    itab, dtab, W = _pulse_table_rows(table, T, dftlen, wavlen)
+    P = itab.shape[1]
+    wav = torch.empty(wavlen, dtype=torch.float32, device=spec.device)
+    if wavlen == 0:
+        return wav
+    if P == 0 or T == 0:
+        return wav.zero_()
+    it = torch.from_numpy(itab).to(spec.device)
+    dt = torch.from_numpy(dtab).to(spec.device)
+    seg = torch.empty((P, W), dtype=torch.float32, device=spec.device)
+    call('ptts_pulse_segments', ptr(spec), ptr(mask), ptr(noise), ptr(it), ptr(dt), P, T, int(dftlen), float(fs), wavlen, ptr(seg), W,
+         stream(), tag=(P, dftlen, W))
+    call('ptts_pulse_overlap_add', ptr(seg), ptr(it), P, W, ptr(wav), wavlen, stream(), tag=(P, W, wavlen))
+    return wav
+
+
+# ----------------------------------------------------------------------------------------------
 # label front end (external/merlin/label_normalisation.py): csrc/labels.hip
 # ----------------------------------------------------------------------------------------------
 LABELS_MAX_LABEL = 1024                     # PTTS_LABELS_MAX_LABEL: bytes of a label the match kernel stages

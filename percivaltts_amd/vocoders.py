@@ -7,7 +7,8 @@ section 2, row 9).  The networks, the critic and the WGAN losses only need the f
 network_final switches on (networktts.py:195,212).  The objective measures of vocoders.py:112-117,209-218,333-342
 (`objmeasures_clear / objmeasures_add / objmeasures_stats`) are plain numpy on a few hundred kilobytes per utterance.
 `decompress_spectrum` (vocoders.py:147-166), the frame-wise step in front of the waveform generator, runs on the device
-(csrc/spectrum.hip).
+(csrc/spectrum.hip).  `VocoderPML.synthesis_device` is the build's own pulse-and-noise synthesiser (csrc/pulsesynth.hip, DESIGN.md
+section 3); `synthesis` keeps its name for pulsemodel's waveform and keeps raising.
 """
 from __future__ import print_function
 
@@ -23,6 +24,26 @@ def bark_alpha(fs):
 def log2db(x):
     """Natural-log amplitude -> decibels (the reference's sigproc.log2db)."""
     return (20.0 / np.log(10.0)) * x
+
+
+def wavwrite(path, wav, fs):
+    """Write a mono waveform as 16-bit PCM (the standard library's `wave`).  A waveform whose peak exceeds 1 is divided by its peak
+    first, and a line says so."""
+    import wave
+    wav = np.asarray(wav, dtype=np.float64).reshape(-1)
+    peak = float(np.abs(wav).max()) if wav.size else 0.0
+    if peak > 1.0:
+        print('    wavwrite: peak {:.3f} above full scale, {} divided by its peak'.format(peak, path))
+        wav = wav / peak
+    pcm = np.round(wav * 32767.0).astype('<i2')
+    f = wave.open(path, 'wb')
+    try:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(int(round(fs)))
+        f.writeframes(pcm.tobytes())
+    finally:
+        f.close()
 
 
 class Vocoder(object):
@@ -61,6 +82,8 @@ class Vocoder(object):
         return stats
 
     def _out_of_scope(self, *a, **k):
+        """analysisf / analysisfid / synthesis promise pulsemodel's or pyworld's signal processing, which this build does not have.
+        The build's own synthesiser is VocoderPML.synthesis_device."""
         raise NotImplementedError('waveform analysis/synthesis is outside the MI355X hot-path build '
                                   '(needs the pulsemodel/pyworld DSP of the reference)')
     analysisf = analysisfid = synthesis = _out_of_scope
@@ -120,6 +143,36 @@ class VocoderPML(VocoderF0Spec):
         """Generated and target [T, >= raw] de-normalised features of one utterance (vocoders.py:209-218)."""
         self._objmeasures_add_f0spec(CMP, REF)
         self._objmeasures_add_band('NM', CMP, REF, self.nm_size)
+
+    def synthesis_device(self, CMP, pp_mcep=False, pp_f0_smooth=None, noise=None):
+        """De-normalised parameters [T, featuressizeraw()] (numpy or a device tensor) -> the waveform, numpy float32
+        [round(shift (T-1) fs)], by the build's pulse-and-noise synthesiser: exp(lf0), decompress_spectrum
+        (`pp_mcep` passed through), the noise mask, the pulse table on the host, one segment per pulse and their overlap-add
+        (csrc/pulsesynth.hip).  `noise`: a [wavlen] fp32 device tensor of N(0,1) samples, used as it is; None draws them from the
+        library's generator, so ops.rng_seed makes a waveform reproducible.  Not built: f0 smoothing (`pp_f0_smooth` other than
+        None is a ValueError), ener_multT0, nm_cont, pp_atten1stharminsilences."""
+        import torch
+        from . import backend_hip, ops
+        if pp_f0_smooth is not None:
+            raise ValueError('pp_f0_smooth={!r}: f0 smoothing is not part of this synthesiser'.format(pp_f0_smooth))
+        if not hasattr(CMP, 'shape') or len(CMP.shape) != 2 or CMP.shape[1] != self.featuressizeraw() or CMP.shape[0] < 1:
+            raise ValueError('synthesis_device: CMP is not [T, {}] with T >= 1'.format(self.featuressizeraw()))
+        ops.pulse_check(self.dftlen, self.fs)
+        x = CMP
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.ascontiguousarray(CMP, dtype=np.float32)).to(backend_hip.device())
+        if x.requires_grad:
+            raise ValueError('synthesis_device has no backward pass: detach its input')
+        T = x.shape[0]
+        s1 = 1 + self.spec_size
+        wavlen = int(round(self.shift * (T - 1) * self.fs))
+        f0 = torch.exp(x[:, 0]).contiguous()
+        table = ops.pulse_table(f0.cpu().numpy(), self.shift, self.fs, wavlen, self.dftlen)
+        SPEC = self.decompress_spectrum(x[:, 1:s1].contiguous(), pp_mcep=pp_mcep)
+        mask = ops.noise_mask(x[:, s1:s1 + self.nm_size].contiguous(), f0, self.fs, self.dftlen)
+        if noise is None:
+            noise = ops.normal((wavlen,), device=x.device, i0=0)
+        return ops.pulse_synthesis(SPEC, mask, table, noise, self.fs, self.dftlen, wavlen).cpu().numpy()
 
 
 class VocoderWORLD(VocoderF0Spec):
