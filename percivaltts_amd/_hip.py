@@ -1,186 +1,102 @@
 """ctypes binding of libpercival_hip.so (the C ABI declared in include/percival_hip.h).
 
+The header is the single source of the binding: SIGNATURES and the descriptor structures below are parsed from it once, at
+import.  A new entry point or struct field is declared in the header only; a declaration the parser cannot read, or a type
+it does not know, raises at import.
+
 There is NO fallback: if the library is missing or a kernel reports an error the call raises.
 The reference reaches its arithmetic through tf.keras (percivaltts/backend_tensorflow.py:38-39
 opens the TF session); this module is the counterpart for the MI355X build.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PTTS_LIB_PATH') or os.path.join(_HERE, 'lib', 'libpercival_hip.so')      # (PTTS_LIB_PATH: an A/B build of the library, tools/ab_define.sh)
-
-c_d = ctypes.c_double
-c_f = ctypes.c_float
-c_i = ctypes.c_int
-c_ll = ctypes.c_longlong
-c_p = ctypes.c_void_p
-c_sz = ctypes.c_size_t
-c_ull = ctypes.c_ulonglong
-
-class WGradDesc(ctypes.Structure):
-    """struct ptts_wgrad_desc of include/percival_hip.h (one weight-gradient product of a grouped launch)."""
-    _fields_ = [('A', c_p), ('B', c_p), ('C', c_p), ('colsum_b', c_p), ('in_scale', c_p), ('in_shift', c_p), ('mask_src', c_p),
-                ('M', c_i), ('N', c_i), ('K', c_i), ('lda', c_ll), ('ldb', c_ll), ('ldc', c_ll), ('in_mode', c_i), ('alpha', c_f)]
-
-
-class DenseWgradReduceDesc(ctypes.Structure):
-    """struct ptts_dense_wgrad_reduce_desc of include/percival_hip.h (the partial rows of one weight-gradient product)."""
-    _fields_ = [('partials', c_p), ('split', c_i), ('Kin', c_i), ('N', c_i), ('ldc', c_ll), ('C', c_p), ('colsum_b', c_p)]
-
-
-class DenseSplitDesc(ctypes.Structure):
-    """struct ptts_dense_split_desc of include/percival_hip.h (one weight of a grouped plane split)."""
-    _fields_ = [('w', c_p), ('planes', c_p), ('ldw', c_ll), ('K', c_i), ('N', c_i), ('transposed', c_i), ('reserved', c_i)]
-
-
-class Conv2dReduceDesc(ctypes.Structure):
-    """struct ptts_conv2d_reduce_desc of include/percival_hip.h (one queued conv2d backward pass)."""
-    _fields_ = [('partials', c_p), ('nblocks', c_i), ('npart', c_i), ('nw', c_i), ('cout', c_i), ('dw', c_p), ('dbias', c_p)]
-
-
-# name -> (restype, argtypes); must mirror include/percival_hip.h exactly
-SIGNATURES = {
-    'ptts_version': (ctypes.c_char_p, []),
-    'ptts_device_arch': (ctypes.c_char_p, []),
-    'ptts_last_error': (ctypes.c_char_p, []),
-    'ptts_device_status': (c_i, [c_p]),
-    'ptts_device_status_clear': (c_i, []),
-    'ptts_device_status_word': (c_p, []),
-    'ptts_device_status_message': (c_i, [ctypes.c_uint, ctypes.c_char_p, c_sz]),
-    'ptts_set_deterministic': (c_i, [c_i]),
-    'ptts_get_deterministic': (c_i, []),
-    'ptts_set_bf16_products': (c_i, [c_i]),
-    'ptts_get_bf16_products': (c_i, []),
-    'ptts_conv2d_fwd': (c_i, [c_p] * 7 + [c_i] * 10 + [c_f, c_p]),
-    'ptts_conv2d_bwd_workspace_bytes': (c_sz, [c_i] * 8),
-    'ptts_conv2d_bwd': (c_i, [c_p] * 11 + [c_p, c_sz] + [c_i] * 10 + [c_f, c_p]),
-    'ptts_gemm': (c_i, [c_p] * 4 + [c_i] * 3 + [c_i, c_ll, c_ll, c_ll, c_i, c_ll, c_ll, c_i, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p]),
-    'ptts_gemm_wgrad_grouped': (c_i, [c_p, c_i, c_p]),
-    'ptts_split3_frames': (c_i, [c_p] * 4 + [c_i] * 6 + [c_p]),
-    'ptts_split3_weight_t': (c_i, [c_p] * 4 + [c_i] * 4 + [c_p]),
-    'ptts_conv1d_bf16x6': (c_i, [c_p] * 8 + [c_i] * 5 + [c_p]),
-    'ptts_split3_frames_t': (c_i, [c_p] * 4 + [c_i] * 6 + [c_ll, c_p]),
-    'ptts_conv1d_wgrad_bf16x6': (c_i, [c_p] * 7 + [c_i] * 6 + [c_ll, c_p]),
-    'ptts_transpose_frames': (c_i, [c_p] * 2 + [c_i] * 6 + [c_ll, c_p]),
-    'ptts_conv1d_wgrad_t': (c_i, [c_p] * 4 + [c_i] * 6 + [c_ll, c_p]),
-    'ptts_conv2d_bwd_partials': (c_i, [c_p] * 5 + [c_p, c_sz, c_p] + [c_i] * 10 + [c_f, c_p]),
-    'ptts_conv2d_reduce_grouped': (c_i, [c_p, c_i, c_p]),
-    'ptts_conv2d_mfma_debug': (c_i, [c_i, c_p]),
-    'ptts_conv2d_mfma_table_bytes': (c_sz, [c_i]),
-    'ptts_conv2d_mfma_tables': (c_i, [c_p, c_p, c_p] + [c_i] * 5 + [c_p]),
-    'ptts_conv2d_mfma_tables_grouped': (c_i, [c_p, c_p, c_p, c_i, c_i, c_p]),
-    'ptts_conv2d_mfma_supported': (c_i, [c_i] * 6),
-    'ptts_conv2d_mfma_fwd': (c_i, [c_p] * 8 + [c_i] * 7 + [c_f] + [c_i] * 3 + [c_p]),
-    'ptts_conv2d_mfma_fwd_stats_supported': (c_i, [c_i, c_i, c_i]),
-    'ptts_conv2d_mfma_fwd_stats': (c_i, [c_p] * 6 + [c_i] * 6 + [c_f] + [c_p, c_i, c_p, c_p]),
-    'ptts_conv2d_mfma_wgrad_workspace_bytes': (c_sz, [c_i, c_i]),
-    'ptts_conv2d_mfma_wgrad_partials': (c_i, [c_p] * 4 + [c_sz, c_p, c_p] + [c_i] * 7 + [c_f] + [c_i] * 3 + [c_p]),
-    'ptts_conv2d_mfma_bwd_fused_workspace_bytes': (c_sz, [c_i, c_i]),
-    'ptts_conv2d_mfma_bwd_fused_supported': (c_i, [c_i, c_i, c_i]),
-    'ptts_conv2d_mfma_bwd_fused_affine': (c_i, [c_p] * 5 + [c_sz, c_p, c_p] + [c_i] * 5 + [c_f, c_p, c_p, c_p]),
-    'ptts_conv2d_mfma_bwd_fused': (c_i, [c_p] * 6 + [c_sz, c_p, c_p] + [c_i] * 6 + [c_f, c_p]),
-    'ptts_conv2d_chain_supported': (c_i, [c_i] * 6),
-    'ptts_conv2d_chain_debug': (c_i, [c_p]),
-    'ptts_conv2d_chain_tables_bytes': (c_sz, []),
-    'ptts_conv2d_chain_partials_bytes': (c_sz, [c_i]),
-    'ptts_conv2d_chain_map_elems': (c_ll, [c_i] * 3),
-    'ptts_conv2d_chain_tables': (c_i, [c_p, c_p, c_p, c_i, c_i, c_p]),
-    'ptts_conv2d_chain_fwd': (c_i, [c_p, c_ll, c_p, c_p, c_p] + [c_i] * 4 + [c_f, c_p]),
-    'ptts_conv2d_chain_bwd': (c_i, [c_p, c_i, c_p, c_ll, c_p, c_p, c_p, c_p, c_sz, c_p, c_p] + [c_i] * 5 + [c_f, c_p]),
-    'ptts_conv2d_chain_bwd_data': (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_p] + [c_i] * 4 + [c_f, c_p]),
-    'ptts_conv2d_chain_second': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p, c_p] + [c_i] * 5 + [c_f, c_p]),
-    'ptts_dense_planes_bytes': (c_sz, [c_i, c_i]),
-    'ptts_split3_dense_weight': (c_i, [c_p, c_ll, c_i, c_i, c_i, c_p, c_p]),
-    'ptts_split3_dense_weight_grouped': (c_i, [c_p, c_i, c_p]),
-    'ptts_split3_frame_windows': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_ll, c_p]),
-    'ptts_split3_dense_weight_strided': (c_i, [c_p, c_ll, c_p, c_ll, c_i, c_ll, c_i, c_i, c_i, c_p]),
-    'ptts_dense_bf16x6_supported': (c_i, [c_i, c_i, c_i, c_ll, c_ll]),
-    'ptts_dense_bf16x6': (c_i, [c_p] * 4 + [c_i] * 3 + [c_ll, c_ll, c_i, c_p, c_p, c_p, c_f, c_i, c_p, c_p]),
-    'ptts_dense_bf16x6_stats_rows': (c_i, [c_i, c_i]),
-    'ptts_dense_bf16x6_stats': (c_i, [c_p] * 4 + [c_i] * 3 + [c_ll, c_ll, c_i, c_p, c_p, c_f, c_p, c_i, c_p, c_p]),
-    'ptts_dense_bf16x6_bwd_affine': (c_i, [c_p] * 3 + [c_i] * 3 + [c_ll, c_ll, c_p, c_p, c_p, c_f, c_p, c_i, c_p, c_p]),
-    'ptts_partial_rows_sum': (c_i, [c_p, c_i, c_i, c_p, c_p]),
-    'ptts_dense_bf16x6_res': (c_i, [c_p] * 4 + [c_i] * 3 + [c_ll, c_ll, c_i, c_p, c_p, c_p, c_f, c_p, c_i, c_ll, c_p, c_p]),
-    'ptts_conv1d_freq_kernel_planes': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
-    'ptts_transpose_batched': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p]),
-    'ptts_conv1d_freq_wgrad_combine': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
-    'ptts_conv1d_freq_wgrad_inverse_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
-    'ptts_conv1d_freq_wgrad_inverse': (c_i, [c_p, c_p, c_p, c_p, c_sz, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    'ptts_dft_mirror': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p]),
-    'ptts_dense_bf16x6_batched': (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_p, c_ll, c_i, c_i, c_i, c_i, c_ll, c_ll, c_i, c_p]),
-    'ptts_dense_wgrad_bf16x6_supported': (c_i, [c_i, c_i, c_i, c_ll, c_ll]),
-    'ptts_dense_wgrad_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
-    'ptts_dense_wgrad_bf16x6_partials': (c_i, [c_p] * 6 + [c_sz, c_p] + [c_i] * 3 + [c_ll] * 2 + [c_i, c_f, c_p]),
-    'ptts_dense_wgrad_reduce_grouped': (c_i, [c_p, c_i, c_p]),
-    'ptts_dense_wgrad_bf16x6': (c_i, [c_p] * 8 + [c_sz] + [c_i] * 3 + [c_ll] * 3 + [c_i, c_f, c_p]),
-    'ptts_colstats_workspace_bytes': (c_sz, [c_ll, c_i]),
-    'ptts_colstats': (c_i, [c_p, c_ll, c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_sz, c_p]),
-    'ptts_bn_finalize': (c_i, [c_p, c_ll, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
-    'ptts_bn_batch_stats_supported': (c_i, [c_ll, c_i]),
-    'ptts_bn_finalize_partials': (c_i, [c_p, c_i, c_ll, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
-    'ptts_bn_batch_stats': (c_i, [c_p, c_ll, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p]),
-    'ptts_bn_bwd_coefs': (c_i, [c_p] * 5 + [c_ll, c_i] + [c_p] * 4 + [c_p]),
-    'ptts_bn_bwd_coefs_acc': (c_i, [c_p] * 5 + [c_ll, c_i] + [c_p] * 4 + [c_p]),
-    'ptts_affine_act': (c_i, [c_p, c_p, c_p, c_p, c_ll, c_i, c_i, c_f, c_p]),
-    'ptts_affine_act_bwd': (c_i, [c_p] * 7 + [c_p, c_sz, c_ll, c_i, c_i, c_f, c_p]),
-    'ptts_gated_mul_fwd': (c_i, [c_p] * 3 + [c_ll, c_p]),
-    'ptts_gated_mul_bwd': (c_i, [c_p] * 5 + [c_ll, c_p]),
-    'ptts_axpby_cols': (c_i, [c_p] * 6 + [c_ll, c_i, c_p]),
-    'ptts_gp_interpolate': (c_i, [c_p] * 4 + [c_i, c_ll, c_p]),
-    'ptts_gp_sqnorm': (c_i, [c_p, c_p, c_i, c_ll, c_p]),
-    'ptts_gp_penalty': (c_i, [c_p, c_p, c_p, c_i, c_p]),
-    'ptts_gp_scale_rows': (c_i, [c_p] * 4 + [c_i, c_ll, c_p]),
-    'ptts_mean_scaled': (c_i, [c_p, c_ll, c_f, c_p, c_p]),
-    'ptts_wlse_fwd': (c_i, [c_p] * 4 + [c_ll, c_i, c_p]),
-    'ptts_wlse_bwd': (c_i, [c_p] * 5 + [c_ll, c_i, c_p]),
-    'ptts_weight_clip': (c_i, [c_p, c_ll, c_f, c_f, c_p]),
-    'ptts_adam_keras_step': (c_i, [c_p] * 4 + [c_ll] + [c_f] * 5 + [c_p, c_p]),
-    'ptts_lstm_fwd_workspace_bytes': (c_sz, [c_i] * 4),
-    'ptts_lstm_fwd': (c_i, [c_p] * 5 + [c_p, c_sz] + [c_i] * 5 + [c_p]),
-    'ptts_lstm_bwd_workspace_bytes': (c_sz, [c_i] * 4),
-    'ptts_lstm_bwd': (c_i, [c_p] * 5 + [c_p, c_sz] + [c_i] * 5 + [c_p]),
-    'ptts_set_lstm_graph': (c_i, [c_i]),
-    'ptts_lstm_graph_stats': (c_i, [c_p] * 3),
-    'ptts_lstm_graph_clear': (c_i, []),
-    'ptts_gru_fwd_workspace_bytes': (c_sz, [c_i] * 4),
-    'ptts_gru_fwd': (c_i, [c_p] * 5 + [c_p, c_sz] + [c_i] * 4 + [c_p]),
-    'ptts_gru_bwd_workspace_bytes': (c_sz, [c_i] * 4),
-    'ptts_gru_bwd': (c_i, [c_p] * 5 + [c_p, c_sz] + [c_i] * 4 + [c_p]),
-    'ptts_mlpg_workspace_bytes': (c_sz, [c_i] * 3),
-    'ptts_mlpg': (c_i, [c_p] * 4 + [c_i] + [c_p] * 4 + [c_sz] + [c_i] * 4 + [c_p]),
-    'ptts_compose_windows_workspace_bytes': (c_sz, [c_i] * 3),
-    'ptts_compose_windows': (c_i, [c_p] * 3 + [c_i] + [c_p] * 4 + [c_i, c_p, c_sz] + [c_i] * 4 + [c_p]),
-    'ptts_compose_sqdev_workspace_bytes': (c_sz, [c_i] * 2),
-    'ptts_compose_sqdev': (c_i, [c_p] * 4 + [c_i, c_p, c_sz] + [c_i] * 3 + [c_p]),
-    'ptts_compose_normalise': (c_i, [c_p] * 4 + [c_i, c_f, c_f, c_p, c_ll, c_i, c_i, c_p]),
-    'ptts_mcep_table_bytes': (c_sz, [c_i, c_i]),
-    'ptts_mcep_table': (c_i, [c_p, c_sz, c_i, c_d, c_i, c_p]),
-    'ptts_fwbnd_table_bytes': (c_sz, [c_i]),
-    'ptts_fwbnd_table': (c_i, [c_p, c_sz, c_i, c_d, c_d, c_i, c_p]),
-    'ptts_mcep_postfilter': (c_i, [c_p, c_p, c_i, c_i, c_d, c_i, c_d, c_p, c_sz, c_p]),
-    'ptts_mcep2spec': (c_i, [c_p, c_p, c_i, c_i, c_d, c_i, c_i, c_i, c_d, c_p, c_sz, c_p]),
-    'ptts_fwbnd2spec': (c_i, [c_p, c_p, c_i, c_i, c_d, c_d, c_i, c_i, c_i, c_d, c_p, c_sz, c_p]),
-    'ptts_noise_mask': (c_i, [c_p, c_p, c_p, c_i, c_i, c_d, c_i, c_p, c_sz, c_p]),
-    'ptts_pulse_segments': (c_i, [c_p] * 5 + [c_i, c_i, c_i, c_d, c_ll, c_p, c_i, c_p]),
-    'ptts_pulse_overlap_add': (c_i, [c_p, c_p, c_i, c_i, c_p, c_ll, c_p]),
-    'ptts_labels_feature_count': (c_i, [c_i]),
-    'ptts_labels_match': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
-    'ptts_labels_expand': (c_i, [c_p] * 4 + [c_i] * 5 + [c_p]),
-    'ptts_rng_seed':(c_i, [c_p, c_ull, c_ull, c_p]),
-    'ptts_rng_state_get': (c_i, [c_p, c_p, c_p]),
-    'ptts_dropout_fwd': (c_i, [c_p] * 6 + [c_f, c_f] + [c_i] * 4 + [c_ll, c_p]),
-    'ptts_dropout_bwd': (c_i, [c_p] * 4 + [c_f] + [c_i] * 3 + [c_ll, c_p]),
-    'ptts_normal_fill': (c_i, [c_p] * 3 + [c_f, c_ll, c_ll, c_p]),
-}
-
-_lib = None
+HEADER_PATH = os.environ.get('PTTS_HEADER_PATH') or os.path.join(_HERE, '..', 'include', 'percival_hip.h')   # as csrc/Makefile finds it
 
 
 class HipLibraryError(RuntimeError):
     pass
+
+
+_SCALARS = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'float': ctypes.c_float, 'double': ctypes.c_double,
+            'size_t': ctypes.c_size_t, 'long long': ctypes.c_longlong, 'unsigned long long': ctypes.c_ulonglong}
+_DECLARATOR = re.compile(r'(.*[\s*])(\w+)\s*(\[\s*\])?', re.S)      # type, name, [] of `const float* bias` / `int n` / `T name[]`
+
+
+def _ctype(spelling, where):
+    """The ctypes class of a C type as the header spells it: char* is c_char_p, any other pointer c_void_p."""
+    t = ' '.join(w for w in spelling.replace('*', ' * ').split() if w != 'const')
+    if t.endswith('*'):
+        return ctypes.c_char_p if t == 'char *' else ctypes.c_void_p
+    if t not in _SCALARS:
+        raise HipLibraryError('percival_hip.h: unknown type {!r} in {!r}'.format(spelling.strip(), ' '.join(where.split())))
+    return _SCALARS[t]
+
+
+def _declaration(text, where):
+    """`TYPE name` or `TYPE name[]` -> (name, ctypes class)."""
+    m = _DECLARATOR.fullmatch(text.strip())
+    if m is None:
+        raise HipLibraryError('percival_hip.h: cannot read {!r} in {!r}'.format(text.strip(), ' '.join(where.split())))
+    return m.group(2), _ctype(m.group(1) + ('*' if m.group(3) else ''), where)
+
+
+def parse_header(text):
+    """The declarations of a C header in the style of include/percival_hip.h -> (structs, functions): struct name ->
+    [(field, ctypes class)] for every `typedef struct NAME { ... } NAME;`, function name -> (restype, [argtypes]) for every
+    `RET ptts_xxx(ARGS);`.  Anything else left after comments and preprocessor lines raises HipLibraryError."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    text = re.sub(r'#ifdef __cplusplus.*?#endif', '', text, flags=re.S)          # the extern "C" braces
+    text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+    structs, functions = {}, {}
+
+    def struct(m):
+        fields = structs[m.group(1)] = []
+        for line in filter(str.strip, m.group(2).split(';')):                   # `int a, b` declares several fields of one type
+            first, *more = line.split(',')
+            name, ctype = _declaration(first, line)
+            if not all(n.strip().isidentifier() for n in more):
+                raise HipLibraryError('percival_hip.h: cannot read {!r}'.format(' '.join(line.split())))
+            fields.extend((n.strip(), ctype) for n in [name] + more)
+        return ''
+
+    text = re.sub(r'typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;', struct, text, flags=re.S)
+    for decl in filter(str.strip, text.split(';')):
+        m = re.fullmatch(r'\s*(.+?)\b(ptts_\w+)\s*\((.*)\)\s*', decl, flags=re.S)
+        if m is None:
+            raise HipLibraryError('percival_hip.h: cannot read {!r}'.format(' '.join(decl.split())))
+        args = [] if m.group(3).strip() == 'void' else [_declaration(a, decl)[1] for a in m.group(3).split(',')]
+        functions[m.group(2)] = (_ctype(m.group(1), decl), args)
+    return structs, functions
+
+
+def read_header(path):
+    """parse_header of the file at `path`; like the library, a missing header is an error that names the path."""
+    if not os.path.exists(path):
+        raise HipLibraryError('percival_hip.h not found at {}: it lies in include/ beside the package (or set PTTS_HEADER_PATH). '
+                              'The binding is read from it.'.format(path))
+    with open(path) as f:
+        return parse_header(f.read())
+
+
+_STRUCTS, SIGNATURES = read_header(HEADER_PATH)          # SIGNATURES: name -> (restype, argtypes)
+
+
+def _structure(name, cname):
+    return type(name, (ctypes.Structure,), {'_fields_': _STRUCTS[cname], '__doc__': 'struct {} of include/percival_hip.h.'.format(cname)})
+
+
+WGradDesc = _structure('WGradDesc', 'ptts_wgrad_desc')                                   # one weight-gradient product of a grouped launch
+DenseWgradReduceDesc = _structure('DenseWgradReduceDesc', 'ptts_dense_wgrad_reduce_desc')   # the partial rows of one weight-gradient product
+DenseSplitDesc = _structure('DenseSplitDesc', 'ptts_dense_split_desc')                   # one weight of a grouped plane split
+Conv2dReduceDesc = _structure('Conv2dReduceDesc', 'ptts_conv2d_reduce_desc')             # one queued conv2d backward pass
+
+_lib = None
 
 
 def lib():
@@ -282,3 +198,16 @@ def f32c(t, name='tensor'):
         raise HipLibraryError('{}: expected a contiguous float32 device tensor, got {} {} contiguous={}'.format(
             name, t.device, t.dtype, t.is_contiguous()))
     return t
+
+
+_ws_cache = {}
+
+
+def _workspace(nbytes, device):
+    """One growing scratch buffer per device and stream (kernels on one stream are ordered)."""
+    key = (device.index, stream_id(), torch.cuda.is_current_stream_capturing())
+    buf = _ws_cache.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+        _ws_cache[key] = buf
+    return buf

@@ -130,7 +130,7 @@ def _as_keepidx(keepidx, n):
 
 
 def _plan_minmax(mins, maxs, outdir, nrange, keepidx, zerovarstozeros):
-    from . import ops
+    from . import ops_offline as ops
     if nrange is None: nrange = [-1, 1]
     orisize = len(maxs)
     kidx = np.arange(len(mins)) if keepidx is None else np.asarray(keepidx)
@@ -148,7 +148,7 @@ def _plan_minmax(mins, maxs, outdir, nrange, keepidx, zerovarstozeros):
 
 
 def _plan_meanstd(means, stds, outdir, noise_slices=()):
-    from . import ops
+    from . import ops_offline as ops
     means = means.astype('float32')
     stds = stds.astype('float32')
     for sl in noise_slices:             # _nmnoscale: the noise columns pass through untouched
@@ -182,7 +182,7 @@ def _plan_device(plan, dev):
 
 def _normalise_files(plan, filepath, fids, outfilepath):
     """The files of `fids` through ptts_compose_normalise, a chunk at a time."""
-    from . import ops
+    from . import ops_offline as ops
     dev = _device()
     a, b, kidx = _plan_device(plan, dev)
     width = plan['width']
@@ -291,7 +291,7 @@ def _device_stats(chunks_of, nbframes, W, dev):
     """Statistics of packed device chunks [(rows, device offsets, utterances that count)] through the composition kernels:
     min, max (fp32), mean and sum of squared deviations (fp64)."""
     import torch
-    from . import ops
+    from . import ops_offline as ops
     stats = ops.compose_stats_buffers(W, dev)
     for rows, offs_d, ns in chunks_of():
         if ns > 0: ops.compose_windows(rows, offs_d, None, stats=stats, n_stat_utts=ns)
@@ -330,7 +330,7 @@ def compose(featurepaths, fids, outfilepath, wins=None, id_valid_start=-1, normf
     'keepidx', 'size', 'resident' and, with `do_finalcheck`, 'finalcheck': the statistics of what was written for the first
     `id_valid_start` files, recomputed with the same kernels ('verif_min', 'verif_max', 'verif_means', and 'verif_stds', which
     as in the reference is the unbiased VARIANCE)."""
-    from . import ops
+    from . import ops_offline as ops
     print('Compose data (id_valid_start={})'.format(id_valid_start))
     if id_valid_start <= 0:
         raise ValueError('id_valid_start has to be greater than zero, i.e. training set has to contain at least one sample, '

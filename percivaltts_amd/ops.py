@@ -1,7 +1,9 @@
-"""torch.autograd.Functions over the HIP kernels of libpercival_hip.so.
+"""torch.autograd.Functions over the HIP kernels of libpercival_hip.so: the training path.
 
 Every numeric op of the WGAN-GP hot path goes through the C ABI (include/percival_hip.h); torch
 supplies device memory, the autograd tape and streams only.  There is no CPU path.
+The wrappers of the offline pipeline (MLPG, compose, spectrum, pulse synthesis, labels: no autograd
+nodes) live in ops_offline.py; their public names are re-exported here.
 
 The layers of the reference are Linear -> (BatchNorm) -> LeakyReLU (networktts.py:59-63,116-126,
 networks_critic.py:66-68).  Here a layer's output is kept as its PRE-activation `z`; the pending
@@ -21,7 +23,8 @@ import os
 import torch
 
 from . import _hip
-from ._hip import call, ptr, stream, f32c
+from ._hip import call, ptr, stream, f32c, _workspace
+from .ops_offline import *     # noqa: F401,F403 -- the names of ops_offline.__all__
 
 IN_NONE, IN_LRELU, IN_MASKMUL = 0, 1, 2
 PAD_SAME, PAD_CAUSAL = 0, 1
@@ -275,7 +278,6 @@ def flush_weight_grads():
     _Deferred.streams = []
 
 
-_ws_cache = {}
 _counter_cache = {}
 
 
@@ -286,16 +288,6 @@ def _stream_counter(device):
     if c is None:
         c = _counter_cache[key] = torch.zeros(1, dtype=torch.int32, device=device)
     return c
-
-
-def _workspace(nbytes, device):
-    """One growing scratch buffer per device and stream (kernels on one stream are ordered)."""
-    key = (device.index, _hip.stream_id(), torch.cuda.is_current_stream_capturing())
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
-        _ws_cache[key] = buf
-    return buf
 
 
 # ----------------------------------------------------------------------------------------------
@@ -2515,535 +2507,6 @@ class GRUFn(torch.autograd.Function):
 
 def gru(v, W, U, b):
     return GRUFn.apply(as_tensor(v).contiguous(), W, U, b)
-
-
-# ----------------------------------------------------------------------------------------------
-# parameter generation (modeltts.py:163-179 -> external/merlin/mlpg_fast.py:95-135)
-# ----------------------------------------------------------------------------------------------
-MLPG_WORKSPACE_CAP = 256 << 20      # bytes of workspace one ptts_mlpg launch may use; larger batches are split along B
-
-
-def mlpg_windows(wins):
-    """Validate delta windows (one or two, three taps each) -> flat list of 3*len(wins) floats."""
-    if wins is None or not 1 <= len(wins) <= 2:
-        raise ValueError('MLPG needs one or two delta windows, got {}'.format(0 if wins is None else len(wins)))
-    flat = []
-    for w in wins:
-        if len(w) != 3:
-            raise ValueError('an MLPG window has three taps, got {}'.format(list(w)))
-        flat.extend(float(c) for c in w)
-    return flat
-
-
-def mlpg(y, wins, var, mean=None, std=None, lengths=None):
-    """Maximum-likelihood parameter generation on the device (csrc/mlpg.hip): y [B,T,K*D] (or [T,K*D], treated as B = 1) means,
-    or the normalised network output when mean / std [K*D] are given (mu = y*std + mean in fp64); var [K*D] (every frame the
-    same) or the shape of y; wins: K-1 three-tap windows; lengths [B] int32 (frames behind an utterance's end come back as 0,
-    a length is clamped to [0, T]).  Returns [B,T,D] ([T,D] for a 2-D y).  No autograd node."""
-    flat = mlpg_windows(wins)
-    K = 1 + len(flat) // 3
-    for t in (y, var, mean, std):
-        if t is not None and t.requires_grad:
-            raise ValueError('ops.mlpg has no backward pass: detach its inputs')
-    if (mean is None) != (std is None):
-        raise ValueError('ops.mlpg: mean and std go together (both or neither)')
-    f32c(y, 'mlpg.y'); f32c(var, 'mlpg.var'); f32c(mean, 'mlpg.mean'); f32c(std, 'mlpg.std')
-    squeeze = y.dim() == 2
-    y3 = y.unsqueeze(0) if squeeze else y
-    if y3.dim() != 3 or y3.shape[-1] % K != 0 or min(y3.shape) < 1:
-        raise ValueError('ops.mlpg: y {} is not [B,T,{}*D]'.format(tuple(y.shape), K))
-    B, T, KD = y3.shape
-    D = KD // K
-    per_frame = var.dim() > 1
-    if per_frame:
-        if squeeze and var.dim() == 2: var = var.unsqueeze(0)
-        if var.shape != y3.shape:
-            raise ValueError('ops.mlpg: per-frame var {} does not match y {}'.format(tuple(var.shape), tuple(y3.shape)))
-    elif var.shape != (KD,):
-        raise ValueError('ops.mlpg: var {} is neither [{}] nor the shape of y'.format(tuple(var.shape), KD))
-    for t, name in ((mean, 'mean'), (std, 'std')):
-        if t is not None and t.shape != (KD,):
-            raise ValueError('ops.mlpg: {} {} is not [{}]'.format(name, tuple(t.shape), KD))
-    if lengths is not None:
-        if not (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.shape == (B,)):
-            raise _hip.HipLibraryError('mlpg.lengths: expected a contiguous int32 device tensor of shape [{}]'.format(B))
-    wbuf = (ctypes.c_float * len(flat))(*flat)
-    out = torch.empty((B, T, D), dtype=torch.float32, device=y.device)
-    l = _hip.lib()
-    nb = B
-    while nb > 1 and l.ptts_mlpg_workspace_bytes(nb, T, D) > MLPG_WORKSPACE_CAP:
-        nb = (nb + 1) // 2
-    for b0 in range(0, B, nb):
-        n = min(nb, B - b0)
-        ws = _workspace(l.ptts_mlpg_workspace_bytes(n, T, D), y.device)
-        call('ptts_mlpg', ptr(y3[b0:b0 + n]), ptr(mean), ptr(std), ptr(var[b0:b0 + n] if per_frame else var), int(per_frame),
-             wbuf, ptr(lengths[b0:b0 + n]) if lengths is not None else None, ptr(out[b0:b0 + n]), ptr(ws), ws.numel(),
-             n, T, D, K, stream(), tag=(n, T, D, K))
-    return out[0] if squeeze else out
-
-
-# ----------------------------------------------------------------------------------------------
-# feature composition (compose.py:34-183, 239-298): csrc/compose.hip
-# ----------------------------------------------------------------------------------------------
-NORM_MEANSTD, NORM_MINMAX = 0, 1
-COMPOSE_MAX_WINS = 7
-
-
-def compose_window_taps(wins):
-    """Validate composition windows (none .. seven, three taps each) -> flat list of 3*len(wins) floats (fp64 taps)."""
-    wins = [] if wins is None else list(wins)
-    if len(wins) > COMPOSE_MAX_WINS:
-        raise ValueError('compose takes at most {} windows, got {}'.format(COMPOSE_MAX_WINS, len(wins)))
-    flat = []
-    for w in wins:
-        if len(w) != 3:
-            raise ValueError('a composition window has three taps, got {}'.format(list(w)))
-        flat.extend(float(c) for c in w)
-    return flat
-
-
-def _dev_tensor(t, dtype, name, shape=None):
-    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
-        raise _hip.HipLibraryError('{}: expected a contiguous {} device tensor'.format(name, dtype))
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError('{}: shape {} is not {}'.format(name, tuple(t.shape), tuple(shape)))
-    return t
-
-
-def compose_stats_buffers(W, device):
-    """Running (min, max, sum) [W] for compose_windows, initialised to (+inf, -inf, 0)."""
-    return (torch.full((W,), float('inf'), dtype=torch.float32, device=device),
-            torch.full((W,), float('-inf'), dtype=torch.float32, device=device),
-            torch.zeros(W, dtype=torch.float64, device=device))
-
-
-def compose_windows(y, offsets, wins, stats=None, n_stat_utts=0, mlpg_order=False, out=None):
-    """y [R,D] fp32 rows of N packed utterances, offsets [N+1] int32 (device) -> [R,K*D]: the statics and one stream per window
-    (csrc/compose.hip; `mlpg_order` picks W_k y instead of the reference's -convolve).  stats = (run_min, run_max, run_sum) from
-    compose_stats_buffers is updated in place with the rows of the first `n_stat_utts` utterances.  No autograd node."""
-    flat = compose_window_taps(wins)
-    K = 1 + len(flat) // 3
-    f32c(y, 'compose_windows.y')
-    if y.dim() != 2 or min(y.shape) < 1:
-        raise ValueError('ops.compose_windows: y {} is not [R,D]'.format(tuple(y.shape)))
-    if y.requires_grad:
-        raise ValueError('ops.compose_windows has no backward pass: detach its input')
-    R, D = y.shape
-    if R >= 1 << 31:
-        raise ValueError('ops.compose_windows: {} rows exceed the int32 offsets'.format(R))
-    _dev_tensor(offsets, torch.int32, 'compose_windows.offsets')
-    if offsets.dim() != 1 or offsets.numel() < 2:
-        raise ValueError('ops.compose_windows: offsets {} is not [N+1]'.format(tuple(offsets.shape)))
-    N = offsets.numel() - 1
-    n_stat = min(int(n_stat_utts), N)
-    if n_stat < 0 or (n_stat > 0 and stats is None):
-        raise ValueError('ops.compose_windows: n_stat_utts={} with stats={}'.format(n_stat_utts, 'None' if stats is None else 'given'))
-    W = K * D
-    if out is None:
-        out = torch.empty((R, W), dtype=torch.float32, device=y.device)
-    else:
-        f32c(out, 'compose_windows.out')
-        if out.shape != (R, W):
-            raise ValueError('ops.compose_windows: out {} is not [{},{}]'.format(tuple(out.shape), R, W))
-    rmin = rmax = rsum = ws = None
-    nws = 0
-    if n_stat > 0:
-        rmin = _dev_tensor(stats[0], torch.float32, 'compose_windows.run_min', (W,))
-        rmax = _dev_tensor(stats[1], torch.float32, 'compose_windows.run_max', (W,))
-        rsum = _dev_tensor(stats[2], torch.float64, 'compose_windows.run_sum', (W,))
-        nws = _hip.lib().ptts_compose_windows_workspace_bytes(n_stat, D, K)
-        ws = _workspace(nws, y.device)
-    wbuf = (ctypes.c_double * max(len(flat), 1))(*flat)
-    call('ptts_compose_windows', ptr(y), ptr(offsets), wbuf if flat else None, int(bool(mlpg_order)), ptr(out), ptr(rmin), ptr(rmax),
-         ptr(rsum), n_stat, ptr(ws), nws, N, R, D, K, stream(), tag=(N, R, D, K))
-    return out
-
-
-def compose_sqdev(y, offsets, mean, run_sq, n_stat_utts):
-    """run_sq [W] fp64 += sum over the rows of the first `n_stat_utts` utterances of (double(y) - mean)^2; y [R,W] fp32,
-    mean [W] fp64 (device).  The centred second pass of the standard deviation (compose.py:289-296)."""
-    f32c(y, 'compose_sqdev.y')
-    if y.dim() != 2 or min(y.shape) < 1:
-        raise ValueError('ops.compose_sqdev: y {} is not [R,W]'.format(tuple(y.shape)))
-    R, W = y.shape
-    _dev_tensor(offsets, torch.int32, 'compose_sqdev.offsets')
-    if offsets.dim() != 1 or offsets.numel() < 2:
-        raise ValueError('ops.compose_sqdev: offsets {} is not [N+1]'.format(tuple(offsets.shape)))
-    N = offsets.numel() - 1
-    _dev_tensor(mean, torch.float64, 'compose_sqdev.mean', (W,))
-    _dev_tensor(run_sq, torch.float64, 'compose_sqdev.run_sq', (W,))
-    n_stat = min(int(n_stat_utts), N)
-    if n_stat < 0:
-        raise ValueError('ops.compose_sqdev: n_stat_utts={}'.format(n_stat_utts))
-    if n_stat == 0:
-        return run_sq
-    nws = _hip.lib().ptts_compose_sqdev_workspace_bytes(n_stat, W)
-    ws = _workspace(nws, y.device)
-    call('ptts_compose_sqdev', ptr(y), ptr(offsets), ptr(mean), ptr(run_sq), n_stat, ptr(ws), nws, N, R, W, stream(), tag=(N, R, W))
-    return run_sq
-
-
-def compose_normalise(y, a, b, mode=NORM_MEANSTD, scale=1.0, offset=0.0, keepidx=None, out=None):
-    """out[r,j] = f(y[r, keepidx[j]]) in fp32 and numpy's operation order: (y - a)/b (NORM_MEANSTD) or
-    ((((y - a)/b) - 0.5)*2)*scale + offset (NORM_MINMAX); a, b [Wout] fp32, keepidx [Wout] int32 or None.  out=y runs in place
-    (without keepidx)."""
-    f32c(y, 'compose_normalise.y')
-    if y.dim() != 2 or min(y.shape) < 1:
-        raise ValueError('ops.compose_normalise: y {} is not [R,W]'.format(tuple(y.shape)))
-    if mode not in (NORM_MEANSTD, NORM_MINMAX):
-        raise ValueError('ops.compose_normalise: unknown mode {}'.format(mode))
-    R, Win = y.shape
-    Wout = Win
-    if keepidx is not None:
-        _dev_tensor(keepidx, torch.int32, 'compose_normalise.keepidx')
-        if keepidx.dim() != 1 or keepidx.numel() < 1:
-            raise ValueError('ops.compose_normalise: keepidx {} is not [Wout]'.format(tuple(keepidx.shape)))
-        Wout = keepidx.numel()
-    _dev_tensor(a, torch.float32, 'compose_normalise.a', (Wout,))
-    _dev_tensor(b, torch.float32, 'compose_normalise.b', (Wout,))
-    if out is None:
-        out = torch.empty((R, Wout), dtype=torch.float32, device=y.device)
-    else:
-        f32c(out, 'compose_normalise.out')
-        if out.shape != (R, Wout):
-            raise ValueError('ops.compose_normalise: out {} is not [{},{}]'.format(tuple(out.shape), R, Wout))
-        if keepidx is not None and out.data_ptr() == y.data_ptr():
-            raise ValueError('ops.compose_normalise: a column gather cannot run in place')
-    call('ptts_compose_normalise', ptr(y), ptr(keepidx), ptr(a), ptr(b), int(mode), float(scale), float(offset), ptr(out), R, Win,
-         Wout, stream(), tag=(R, Win, Wout, mode))
-    return out
-
-
-# ----------------------------------------------------------------------------------------------
-# spectral envelope decompression and the mel-cepstral post-filter (vocoders.py:147-166,
-# external/merlin/generate_pp.py): csrc/spectrum.hip
-# ----------------------------------------------------------------------------------------------
-SPECTRUM_MAX_M1, SPECTRUM_MAX_NB, SPECTRUM_MAX_DFTLEN = 512, 1024, 1 << 20
-_spectrum_tables = {}       # (kind, device, parameters) -> device table; a function of its key only, so never stale
-
-
-def spectrum_check(dftlen, alpha, pf_coef):
-    """ValueError for a dftlen / alpha / pf_coef the spectrum kernels do not take.  Touches no device."""
-    if int(dftlen) != dftlen or dftlen < 8 or dftlen % 2 != 0 or dftlen > SPECTRUM_MAX_DFTLEN:
-        raise ValueError('dftlen={} has to be even, at least 8 and at most {}'.format(dftlen, SPECTRUM_MAX_DFTLEN))
-    if not -1.0 < float(alpha) < 1.0:
-        raise ValueError('|alpha|={} has to be below 1'.format(alpha))
-    if not 0.0 < float(pf_coef) < 1e6:
-        raise ValueError('pf_coef={} has to be positive'.format(pf_coef))
-
-
-def _spectrum_rows(x, name, lo, hi, what):
-    """[T,W] or [B,T,W] fp32 device rows -> (x, T_total, W); ValueError for a shape or width that cannot be, before f32c looks at
-    the device."""
-    if not torch.is_tensor(x) or x.dim() not in (2, 3):
-        raise ValueError('ops.{}: expected a [T,{w}] or [B,T,{w}] tensor'.format(name, w=what))
-    W = x.shape[-1]
-    if not lo <= W <= hi:
-        raise ValueError('ops.{}: {}={} outside [{}, {}]'.format(name, what, W, lo, hi))
-    if x.requires_grad:
-        raise ValueError('ops.{} has no backward pass: detach its input'.format(name))
-    rows = x.numel() // W
-    if rows >= 1 << 31:
-        raise ValueError('ops.{}: {} frames exceed the int32 frame count'.format(name, rows))
-    f32c(x, name)
-    return x, rows, W
-
-
-def _mcep_table(device, M1, alpha, dftlen):
-    key = ('mcep', device, M1, float(alpha), dftlen)
-    tab = _spectrum_tables.get(key)
-    if tab is None:
-        l = _hip.lib()
-        n = l.ptts_mcep_table_bytes(M1, dftlen)
-        tab = torch.empty(n // 4, dtype=torch.float32, device=device)
-        call('ptts_mcep_table', ptr(tab), n, M1, float(alpha), dftlen, stream(), tag=(M1, dftlen))
-        _spectrum_tables[key] = tab
-    return tab, tab.numel() * 4
-
-
-def _fwbnd_table(device, nb, fs, alpha, dftlen):
-    key = ('fwbnd', device, nb, float(fs), float(alpha), dftlen)
-    tab = _spectrum_tables.get(key)
-    if tab is None:
-        l = _hip.lib()
-        n = l.ptts_fwbnd_table_bytes(dftlen)
-        tab = torch.empty(n // 8, dtype=torch.float64, device=device)
-        call('ptts_fwbnd_table', ptr(tab), n, nb, float(fs), float(alpha), dftlen, stream(), tag=(nb, dftlen))
-        _spectrum_tables[key] = tab
-    return tab, tab.numel() * 8
-
-
-def bark_alpha(fs):
-    """The all-pass coefficient that approximates the Bark scale at sampling frequency fs (the reference's sp.bark_alpha)."""
-    import math
-    return 0.8517 * math.sqrt(math.atan(0.06583 * fs / 1000.0)) - 0.1916
-
-
-def mcep_postfilter(mcep, alpha, dftlen=4096, pf_coef=1.4):
-    """Merlin's formant-enhancing post-filter on mel-cepstra (csrc/spectrum.hip): mcep [T,M1] or [B,T,M1] fp32 device ->
-    same shape.  Coefficients 2.. are scaled by pf_coef; c_0 is corrected so that the frame's energy r0 is kept."""
-    spectrum_check(dftlen, alpha, pf_coef)
-    mcep, T, M1 = _spectrum_rows(mcep, 'mcep_postfilter', 2, SPECTRUM_MAX_M1, 'M1')
-    out = torch.empty_like(mcep)
-    if T == 0:
-        return out
-    tab, nb = _mcep_table(mcep.device, M1, alpha, dftlen)
-    call('ptts_mcep_postfilter', ptr(mcep), ptr(out), T, M1, float(alpha), int(dftlen), float(pf_coef), ptr(tab), nb, stream(),
-         tag=(T, M1, dftlen))
-    return out
-
-
-def mcep2spec(mcep, alpha, dftlen=4096, log=False, pp=False, pf_coef=1.4):
-    """Mel-cepstra [T,M1] or [B,T,M1] fp32 device -> amplitude envelope [.., dftlen/2+1] (`log`: its logarithm); `pp`: of the
-    post-filtered cepstrum, which is never stored (csrc/spectrum.hip)."""
-    spectrum_check(dftlen, alpha, pf_coef)
-    mcep, T, M1 = _spectrum_rows(mcep, 'mcep2spec', 2, SPECTRUM_MAX_M1, 'M1')
-    out = torch.empty(tuple(mcep.shape[:-1]) + (dftlen // 2 + 1,), dtype=torch.float32, device=mcep.device)
-    if T == 0:
-        return out
-    tab, nb = _mcep_table(mcep.device, M1, alpha, dftlen)
-    call('ptts_mcep2spec', ptr(mcep), ptr(out), T, M1, float(alpha), int(dftlen), int(bool(log)), int(bool(pp)), float(pf_coef),
-         ptr(tab), nb, stream(), tag=(T, M1, dftlen))
-    return out
-
-
-def fwbnd2spec(fw, fs, dftlen=4096, log=False, pp=False, pf_coef=1.4):
-    """Log-amplitudes of nb frequency-warped bands [T,nb] or [B,T,nb] fp32 device -> amplitude envelope [.., dftlen/2+1] (`log`:
-    its logarithm) by linear interpolation between the band centres; `pp`: with the spectral-domain post-filter
-    (csrc/spectrum.hip)."""
-    if not 0.0 < float(fs) < 1e9:
-        raise ValueError('fs={} has to be positive'.format(fs))
-    alpha = bark_alpha(fs)
-    spectrum_check(dftlen, alpha, pf_coef)
-    fw, T, nbands = _spectrum_rows(fw, 'fwbnd2spec', 2, SPECTRUM_MAX_NB, 'nb')
-    out = torch.empty(tuple(fw.shape[:-1]) + (dftlen // 2 + 1,), dtype=torch.float32, device=fw.device)
-    if T == 0:
-        return out
-    tab, nbytes = _fwbnd_table(fw.device, nbands, fs, alpha, dftlen)
-    call('ptts_fwbnd2spec', ptr(fw), ptr(out), T, nbands, float(fs), float(alpha), int(dftlen), int(bool(log)), int(bool(pp)),
-         float(pf_coef), ptr(tab), nbytes, stream(), tag=(T, nbands, dftlen))
-    return out
-
-
-# ----------------------------------------------------------------------------------------------
-# pulse-and-noise waveform synthesis of the PML vocoder (the step behind vocoders.py:194-206): csrc/pulsesynth.hip
-# ----------------------------------------------------------------------------------------------
-PULSE_MIN_DFTLEN, PULSE_MAX_DFTLEN = 256, 8192
-PULSE_F0_FLOOR = 50.0
-PULSE_INT_ROWS = ('start', 'winlen', 'lb', 'rb', 'fr')
-
-
-def pulse_check(dftlen, fs):
-    """ValueError for a dftlen / fs the synthesis kernels do not take.  Touches no device."""
-    if int(dftlen) != dftlen or not PULSE_MIN_DFTLEN <= dftlen <= PULSE_MAX_DFTLEN or dftlen & (dftlen - 1):
-        raise ValueError('dftlen={} has to be a power of two in [{}, {}]'.format(dftlen, PULSE_MIN_DFTLEN, PULSE_MAX_DFTLEN))
-    if not 0.0 < float(fs) < 1e9:
-        raise ValueError('fs={} has to be positive'.format(fs))
-
-
-def _rnd(x):
-    import math
-    return int(math.floor(x + 0.5))
-
-
-def pulse_table(f0, shift, fs, wavlen, dftlen):
-    """The pulse positions of one utterance and everything the kernels need per pulse, on the host in fp64:
-    f0 [T] in Hz at the frame times shift * i (values below 50 Hz are synthesised at 50 Hz), wavlen = round(shift (T-1) fs).
-    Returns a dict of numpy arrays, one entry per pulse: 't' fp64 (t_0 = 0, t_{n+1} = t_n + 1 / f0(t_n), the last one at or beyond
-    the end), the int32 rows 'start', 'winlen', 'lb', 'rb', 'fr' and the fp64 rows 'delay', 'f0'.  The noise segments [lb, rb) tile
-    [0, wavlen).  ValueError when a window does not fit dftlen."""
-    import numpy as np
-    pulse_check(dftlen, fs)
-    f0 = np.ascontiguousarray(f0, dtype=np.float64)
-    if f0.ndim != 1 or f0.size < 1 or not (np.isfinite(f0).all() and (f0 > 0).all()):
-        raise ValueError('ops.pulse_table: f0 has to be [T] positive finite Hz values')
-    if not 0.0 < float(shift) < 1e3:
-        raise ValueError('ops.pulse_table: shift={}'.format(shift))
-    T, fs, shift = f0.size, float(fs), float(shift)
-    if int(wavlen) != int(round(shift * (T - 1) * fs)) or wavlen >= 1 << 31:
-        raise ValueError('ops.pulse_table: wavlen={} is not round(shift (T-1) fs) = {}'.format(wavlen, int(round(shift * (T - 1) * fs))))
-    wavlen = int(wavlen)
-    times = shift * np.arange(T)
-    f0_at = lambda x: max(float(np.interp(x, times, f0)), PULSE_F0_FLOOR)
-    t = [0.0]
-    while t[-1] < wavlen / fs:
-        t.append(t[-1] + 1.0 / f0_at(t[-1]))
-    P = len(t)
-    tab = {'t': np.array(t, dtype=np.float64), 'delay': np.zeros(P, dtype=np.float64), 'f0': np.zeros(P, dtype=np.float64)}
-    for key in PULSE_INT_ROWS:
-        tab[key] = np.zeros(P, dtype=np.int32)
-    for n in range(P):
-        f0n = f0_at(t[n])
-        winlen = 2 * int(max(0.050 * fs, 4.0 * fs / f0n) / 2) + 1
-        if winlen > dftlen:
-            raise ValueError('ops.pulse_table: the window of pulse {} ({} samples at f0 = {:.1f} Hz) does not fit dftlen={}'.format(
-                n, winlen, f0n, dftlen))
-        pos = int(winlen / 4)
-        c = _rnd(fs * t[n])
-        lb = _rnd(fs * (t[n - 1] + t[n]) / 2) if n > 0 else _rnd(fs * (t[n] - 0.5 / f0n))
-        rb = _rnd(fs * (t[n] + t[n + 1]) / 2) if n < P - 1 else _rnd(fs * (t[n] + 0.5 / f0n))
-        tab['start'][n], tab['winlen'][n] = c - pos, winlen
-        tab['lb'][n], tab['rb'][n] = min(max(lb, 0), wavlen), min(max(rb, 0), wavlen)
-        tab['fr'][n] = min(max(_rnd(t[n] / shift), 0), T - 1)
-        tab['delay'][n], tab['f0'][n] = pos + (fs * t[n] - c), f0n
-    return tab
-
-
-def _pulse_table_rows(table, T, dftlen, wavlen):
-    """(itab [5,P] int32, dtab [2,P] fp64, W) of a pulse table after the checks that keep the kernels inside their buffers."""
-    import numpy as np
-    try:
-        rows = [np.asarray(table[k]) for k in PULSE_INT_ROWS + ('delay', 'f0')]
-    except (KeyError, TypeError, IndexError):
-        raise ValueError('ops.pulse_synthesis: table is what ops.pulse_table returns')
-    P = rows[0].shape[0] if rows[0].ndim == 1 else -1
-    if any(r.shape != (P,) for r in rows):
-        raise ValueError('ops.pulse_synthesis: the rows of the table are not all [P]')
-    itab = np.ascontiguousarray(np.stack(rows[:5]) if P else np.zeros((5, 0)), dtype=np.int64)
-    dtab = np.ascontiguousarray(np.stack(rows[5:]) if P else np.zeros((2, 0)), dtype=np.float64)
-    if P == 0:
-        return itab.astype(np.int32), dtab, 1
-    start, winlen, lb, rb, fr = itab
-    if winlen.min() < 1 or winlen.max() > dftlen:
-        raise ValueError('ops.pulse_synthesis: a window of {} samples does not fit dftlen={}'.format(winlen.max(), dftlen))
-    if (np.diff(start) < 0).any():
-        raise ValueError('ops.pulse_synthesis: the pulses\' start samples have to ascend (f0 falls too fast between two pulses)')
-    filled = rb > lb
-    if lb.min() < 0 or rb.max() > wavlen or (rb < lb).any() or (filled & ((lb < start) | (rb - start > dftlen))).any():
-        raise ValueError('ops.pulse_synthesis: a noise segment lies outside the waveform or its pulse\'s frame')
-    if fr.min() < 0 or fr.max() >= T:
-        raise ValueError('ops.pulse_synthesis: frame {} of the table is outside the {} frames given'.format(fr.max(), T))
-    if not (np.isfinite(dtab).all() and (dtab[1] > 0).all()):
-        raise ValueError('ops.pulse_synthesis: delay / f0 of the table are not finite and positive')
-    if np.abs(start).max() >= 1 << 30:
-        raise ValueError('ops.pulse_synthesis: a start sample exceeds the int32 table')
-    return itab.astype(np.int32), dtab, int(winlen.max())
-
-
-def noise_mask(nmb, f0, fs, dftlen=4096):
-    """Noise-mask bands [T,nb] in [0,1] and f0 [T] in Hz (fp32 device) -> the binary mask smoothed along frequency, [T, dftlen/2+1]
-    (csrc/pulsesynth.hip): interpolation at k fs / dftlen on the band axis of fwbnd2spec, zero below the second harmonic, threshold at
-    0.5, a forward-backward pass of hanning(9), clip."""
-    pulse_check(dftlen, fs)
-    if not torch.is_tensor(nmb) or nmb.dim() != 2 or not 2 <= nmb.shape[1] <= SPECTRUM_MAX_NB:
-        raise ValueError('ops.noise_mask: expected a [T,nb] tensor with nb in [2, {}]'.format(SPECTRUM_MAX_NB))
-    T, nbands = nmb.shape
-    if not torch.is_tensor(f0) or tuple(f0.shape) != (T,):
-        raise ValueError('ops.noise_mask: f0 is not [{}]'.format(T))
-    if nmb.requires_grad or f0.requires_grad:
-        raise ValueError('ops.noise_mask has no backward pass: detach its input')
-    f32c(nmb, 'noise_mask.nmb'); f32c(f0, 'noise_mask.f0')
-    out = torch.empty((T, dftlen // 2 + 1), dtype=torch.float32, device=nmb.device)
-    if T == 0:
-        return out
-    tab, nbytes = _fwbnd_table(nmb.device, nbands, fs, bark_alpha(fs), dftlen)
-    call('ptts_noise_mask', ptr(nmb), ptr(f0), ptr(out), T, nbands, float(fs), int(dftlen), ptr(tab), nbytes, stream(),
-         tag=(T, nbands, dftlen))
-    return out
-
-
-def pulse_synthesis(spec, mask, table, noise, fs, dftlen, wavlen):
-    """The waveform [wavlen] (fp32 device) of one utterance: spec and mask [T, dftlen/2+1] fp32 device, table from
-    ops.pulse_table (host), noise [wavlen] N(0,1) fp32 device.  One workgroup per pulse builds its segment (minimum-phase envelope
-    times the mix of a delayed pulse and the pulse's stretch of the noise), then one lane per sample adds the segments that cover
-    it, in pulse order (csrc/pulsesynth.hip).  Same input, same bytes."""
-    import numpy as np
-    pulse_check(dftlen, fs)
-    K = dftlen // 2 + 1
-    if not torch.is_tensor(spec) or spec.dim() != 2 or spec.shape[1] != K:
-        raise ValueError('ops.pulse_synthesis: spec is not [T,{}]'.format(K))
-    T = spec.shape[0]
-    if not torch.is_tensor(mask) or tuple(mask.shape) != (T, K):
-        raise ValueError('ops.pulse_synthesis: mask is not [{},{}]'.format(T, K))
-    wavlen = int(wavlen)
-    if wavlen < 0 or not torch.is_tensor(noise) or tuple(noise.shape) != (wavlen,):
-        raise ValueError('ops.pulse_synthesis: noise is not [wavlen={}]'.format(wavlen))
-    if spec.requires_grad or mask.requires_grad or noise.requires_grad:
-        raise ValueError('ops.pulse_synthesis has no backward pass: detach its input')
-    f32c(spec, 'pulse_synthesis.spec'); f32c(mask, 'pulse_synthesis.mask'); f32c(noise, 'pulse_synthesis.noise')
-    itab, dtab, W = _pulse_table_rows(table, T, dftlen, wavlen)
-    P = itab.shape[1]
-    wav = torch.empty(wavlen, dtype=torch.float32, device=spec.device)
-    if wavlen == 0:
-        return wav
-    if P == 0 or T == 0:
-        return wav.zero_()
-    it = torch.from_numpy(itab).to(spec.device)
-    dt = torch.from_numpy(dtab).to(spec.device)
-    seg = torch.empty((P, W), dtype=torch.float32, device=spec.device)
-    call('ptts_pulse_segments', ptr(spec), ptr(mask), ptr(noise), ptr(it), ptr(dt), P, T, int(dftlen), float(fs), wavlen, ptr(seg), W,
-         stream(), tag=(P, dftlen, W))
-    call('ptts_pulse_overlap_add', ptr(seg), ptr(it), P, W, ptr(wav), wavlen, stream(), tag=(P, W, wavlen))
-    return wav
-
-
-# ----------------------------------------------------------------------------------------------
-# label front end (external/merlin/label_normalisation.py): csrc/labels.hip
-# ----------------------------------------------------------------------------------------------
-LABELS_MAX_LABEL = 1024                     # PTTS_LABELS_MAX_LABEL: bytes of a label the match kernel stages
-LABELS_CC_POINTS = 600
-LABELS_ANCHOR_START, LABELS_ANCHOR_END, LABELS_WILD = 0x10000, 0x20000, 0x40000
-LABELS_CAPTURE_DIGITS, LABELS_CAPTURE_DECIMAL = 0, 1
-LABELS_ERR_DIGITS, LABELS_ERR_FORMAT = 1, 2
-LABELS_MODES = {'full': 0, 'minimal_frame': 1, 'state_only': 2, 'none': 3, 'minimal_phoneme': 4, 'coarse_coding': 5}
-LABELS_FEATURES = {'full': 9, 'minimal_frame': 2, 'state_only': 1, 'none': 0, 'minimal_phoneme': 3, 'coarse_coding': 4}
-
-
-def labels_match(labels, label_off, max_label_len, table):
-    """labels: packed uint8 bytes of P labels, label_off [P+1] int32 (both device), max_label_len: the longest of them as the host
-    measured it; table: dict of device tensors pat_bytes (uint8), pat_off, pat_meta [NP], qs_first [nQS+1], cqs [nCQS,3] (int32;
-    None for an absent kind) as label_normalisation.QuestionSet.device_table builds it.  Returns V [P, nQS+nCQS] fp32 and
-    status [P] int32 (0, or the failed capture: see include/percival_hip.h)."""
-    if max_label_len > LABELS_MAX_LABEL:
-        raise ValueError('a label of {} bytes exceeds the {} the match kernel stages'.format(max_label_len, LABELS_MAX_LABEL))
-    _dev_tensor(labels, torch.uint8, 'labels_match.labels')
-    _dev_tensor(label_off, torch.int32, 'labels_match.label_off')
-    if label_off.dim() != 1 or label_off.numel() < 2:
-        raise ValueError('ops.labels_match: label_off {} is not [P+1]'.format(tuple(label_off.shape)))
-    P = label_off.numel() - 1
-    NP = table['pat_off'].numel()
-    _dev_tensor(table['pat_bytes'], torch.uint8, 'labels_match.pat_bytes')
-    _dev_tensor(table['pat_off'], torch.int32, 'labels_match.pat_off', (NP,))
-    _dev_tensor(table['pat_meta'], torch.int32, 'labels_match.pat_meta', (NP,))
-    nQS = nCQS = 0
-    if table.get('qs_first') is not None:
-        nQS = _dev_tensor(table['qs_first'], torch.int32, 'labels_match.qs_first').numel() - 1
-    if table.get('cqs') is not None:
-        nCQS = _dev_tensor(table['cqs'], torch.int32, 'labels_match.cqs').shape[0]
-    if nQS + nCQS < 1:
-        raise ValueError('ops.labels_match: the question table has no question')
-    V = torch.empty((P, nQS + nCQS), dtype=torch.float32, device=labels.device)
-    status = torch.empty(P, dtype=torch.int32, device=labels.device)
-    call('ptts_labels_match', ptr(labels), ptr(label_off), P, labels.numel(), int(max_label_len), ptr(table['pat_bytes']),
-         table['pat_bytes'].numel(), ptr(table['pat_off']), ptr(table['pat_meta']), NP, ptr(table.get('qs_first')), nQS,
-         ptr(table.get('cqs')), nCQS, ptr(V), ptr(status), stream(), tag=(P, nQS, nCQS))
-    return V, status
-
-
-def labels_expand(V, seg, T, subphone_feats, cc_table=None):
-    """V [P,Q] fp32, seg [S,8] int32 (phone row, first output row, frame_number, state_index, state_index_backward,
-    phone_duration, state_duration_base, 0; first rows ascending, T the end of the last) -> X [T, Q+F] fp32, F frame features of
-    `subphone_feats` (LABELS_MODES); cc_table [3,600] fp32 for 'coarse_coding'."""
-    if subphone_feats not in LABELS_MODES:
-        raise ValueError('ops.labels_expand: unknown subphone_feats {!r}'.format(subphone_feats))
-    f32c(V, 'labels_expand.V')
-    if V.dim() != 2 or min(V.shape) < 1:
-        raise ValueError('ops.labels_expand: V {} is not [P,Q]'.format(tuple(V.shape)))
-    _dev_tensor(seg, torch.int32, 'labels_expand.seg')
-    if seg.dim() != 2 or seg.shape[1] != 8 or seg.shape[0] < 1:
-        raise ValueError('ops.labels_expand: seg {} is not [S,8]'.format(tuple(seg.shape)))
-    if subphone_feats == 'coarse_coding':
-        _dev_tensor(cc_table, torch.float32, 'labels_expand.cc_table', (3, LABELS_CC_POINTS))
-    else:
-        cc_table = None
-    T = int(T)
-    if not 0 < T < 1 << 31:
-        raise ValueError('ops.labels_expand: T={} rows'.format(T))
-    P, Q = V.shape
-    X = torch.empty((T, Q + LABELS_FEATURES[subphone_feats]), dtype=torch.float32, device=V.device)
-    call('ptts_labels_expand', ptr(V), ptr(seg), ptr(cc_table), ptr(X), P, Q, seg.shape[0], T, LABELS_MODES[subphone_feats], stream(),
-         tag=(P, Q, seg.shape[0], T))
-    return X
 
 
 # ----------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@ import numpy as np
 
 def bark_alpha(fs):
     """All-pass coefficient of the Bark-like warping at sampling frequency fs (the reference's sigproc.bark_alpha)."""
-    from . import ops
+    from . import ops_offline as ops
     return ops.bark_alpha(fs)
 
 
@@ -103,7 +103,7 @@ class VocoderF0Spec(Vocoder):
         `pp_mcep` applies the formant-enhancing post-filter.  As in the reference the dispatch is on self.spec_type and the
         `spec_type` argument is not looked at.  numpy in -> numpy out, device tensor in -> device tensor out."""
         import torch
-        from . import backend_hip, ops
+        from . import backend_hip, ops_offline as ops
         if self.spec_type not in ('fwbnd', 'mcep'):
             raise ValueError("spec_type is 'fwbnd' or 'mcep', got {!r}".format(self.spec_type))
         as_numpy = not torch.is_tensor(COMPSPEC)

@@ -1,5 +1,5 @@
 """CPU tests: the C-ABI library loads (no compute) and exports every symbol include/percival_hip.h declares,
-and the ctypes signature table of percivaltts_amd/_hip.py covers exactly that set."""
+and the ctypes signature table that percivaltts_amd/_hip.py parses from that header covers exactly that set."""
 import ctypes
 import os
 import re
@@ -34,6 +34,90 @@ def test_library_exports_every_declared_symbol():
     assert set(_hip.SIGNATURES) == set(declared_symbols())
     lib.ptts_device_arch.restype = ctypes.c_char_p
     assert lib.ptts_device_arch() == b'gfx950'
+
+
+SNIPPET = """
+/* every shape of declaration the real header has */
+#ifndef SNIPPET_H
+#define SNIPPET_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define PTTS_X 1   /* a constant */
+const char* ptts_name(void);      // a line comment; with (punctuation)
+unsigned* ptts_word(void);
+int ptts_message(unsigned word, char* buf, size_t n);
+typedef struct ptts_desc {
+    const float* partials;      /* a pointer */
+    int a, b;
+    long long ld;
+    float* dw; float* dbias;
+    float alpha;
+} ptts_desc;
+int ptts_grouped(const ptts_desc* descs, int n, void* stream);
+size_t ptts_bytes(int B, long long rows);
+long long ptts_elems(int B);
+int ptts_fwd(const float* x, const float* bias /*[Cout] or NULL*/,
+             const unsigned char* labels, unsigned* word_out, const float* const* w,
+             double fs, unsigned long long seed, unsigned long long* state,
+             const int offs[], float alpha, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif /* SNIPPET_H */
+"""
+
+
+def test_parser_reads_every_shape_of_declaration():
+    from percivaltts_amd._hip import parse_header
+    c = ctypes
+    P, I = c.c_void_p, c.c_int
+    structs, functions = parse_header(SNIPPET)
+    assert structs == {'ptts_desc': [('partials', P), ('a', I), ('b', I), ('ld', c.c_longlong), ('dw', P), ('dbias', P),
+                                     ('alpha', c.c_float)]}
+    assert functions == {
+        'ptts_name': (c.c_char_p, []),
+        'ptts_word': (P, []),
+        'ptts_message': (I, [c.c_uint, c.c_char_p, c.c_size_t]),
+        'ptts_grouped': (I, [P, I, P]),
+        'ptts_bytes': (c.c_size_t, [I, c.c_longlong]),
+        'ptts_elems': (c.c_longlong, [I]),
+        'ptts_fwd': (I, [P, P, P, P, P, c.c_double, c.c_ulonglong, P, P, c.c_float, P]),
+    }
+    for res, args in functions.values():            # the classes themselves, not look-alikes: c_char_p == c_void_p is False anyway
+        assert all(isinstance(t, type) and issubclass(t, c._SimpleCData) for t in [res] + args)
+
+
+@pytest.mark.parametrize('text', ['int ptts_x(foo_t v);',                    # unknown type
+                                  'foo_t ptts_x(int v);',                    # unknown return type
+                                  'int ptts_x(int);',                        # a parameter without a name
+                                  'int other_x(int v);',                     # not an entry point of this library
+                                  'typedef struct s { foo_t a; } s; int ptts_x(void);',
+                                  'typedef struct s { int a, *b; } s;',
+                                  'struct s { int a; };'])
+def test_parser_raises_on_what_it_cannot_read(text):
+    from percivaltts_amd._hip import HipLibraryError, parse_header
+    with pytest.raises(HipLibraryError, match='percival_hip.h: '):
+        parse_header(text)
+
+
+def test_descriptor_structures_follow_the_header():
+    from percivaltts_amd import _hip
+    for cls, fields, size in (
+            (_hip.WGradDesc, 'A B C colsum_b in_scale in_shift mask_src M N K lda ldb ldc in_mode alpha', 104),
+            (_hip.DenseWgradReduceDesc, 'partials split Kin N ldc C colsum_b', 48),
+            (_hip.DenseSplitDesc, 'w planes ldw K N transposed reserved', 40),
+            (_hip.Conv2dReduceDesc, 'partials nblocks npart nw cout dw dbias', 40)):
+        assert issubclass(cls, ctypes.Structure)
+        assert [f[0] for f in cls._fields_] == fields.split() and ctypes.sizeof(cls) == size, cls
+
+
+def test_missing_header_fails_loudly(tmp_path):
+    from percivaltts_amd import _hip
+    with pytest.raises(_hip.HipLibraryError, match='absent.h'):
+        _hip.read_header(str(tmp_path / 'absent.h'))
+    assert _hip.read_header(HEADER)[1] == _hip.SIGNATURES
 
 
 def test_device_status_word_is_sticky_and_decoded():

@@ -490,7 +490,7 @@ def test_batch_invariance_and_repeatability():
 
 @pytest.mark.gpu
 def test_ops_mlpg_splits_a_batch_over_the_workspace_cap(monkeypatch):
-    from percivaltts_amd import _hip, ops
+    from percivaltts_amd import _hip, ops_offline
     B, T, D = 7, 60, 40
     y, mean, std = make_inputs(61, B, T, D, REF_WINS)
     var = std * std
@@ -498,7 +498,7 @@ def test_ops_mlpg_splits_a_batch_over_the_workspace_cap(monkeypatch):
     with _hip.KernelTimer() as kt:
         whole = _run(y, mean, std, var, REF_WINS, lengths)
     assert [r[0] for r in kt.records] == ['ptts_mlpg']
-    monkeypatch.setattr(ops, 'MLPG_WORKSPACE_CAP', 2 * T * D * 24 + 256)            # room for two utterances
+    monkeypatch.setattr(ops_offline, 'MLPG_WORKSPACE_CAP', 2 * T * D * 24 + 256)            # room for two utterances
     with _hip.KernelTimer() as kt:
         split = _run(y, mean, std, var, REF_WINS, lengths)
     assert [r[1][0] for r in kt.records] == [2, 2, 2, 1]
@@ -506,7 +506,7 @@ def test_ops_mlpg_splits_a_batch_over_the_workspace_cap(monkeypatch):
     rng = np.random.RandomState(3)
     varf = (var[None, None, :] * rng.uniform(0.5, 2.0, size=y.shape)).astype(np.float32)
     split_f = _run(y, mean, std, varf, REF_WINS, lengths)
-    monkeypatch.setattr(ops, 'MLPG_WORKSPACE_CAP', 256 << 20)
+    monkeypatch.setattr(ops_offline, 'MLPG_WORKSPACE_CAP', 256 << 20)
     np.testing.assert_array_equal(split_f, _run(y, mean, std, varf, REF_WINS, lengths))
 
 
