@@ -59,10 +59,10 @@ const char* ptts_version(void);
 const char* ptts_device_arch(void);     /* "gfx950" : the only code object in the library */
 const char* ptts_last_error(void);      /* thread-local message of the last failure */
 /* Device status.  Kernels whose waves wait for each other with bounded polls (the wave-specialised Conv2D forward's LDS-counter
- * hand-off, the persistent LSTM's granule hand-off) do not hang when a count never arrives -- and do not stay silent either: the
+ * hand-off) do not hang when a count never arrives -- and do not stay silent either: the
  * wave that gave up stores a code into a block of pinned, device-mapped host memory.  The word is STICKY: ptts_device_status()
- * returns PTTS_EDEVICE (message in ptts_last_error(), bit mask in *word_out: 1 = Conv2D hand-off, 2 = LSTM hand-off) from then on,
- * and so does every later ptts_conv2d_mfma_fwd / ptts_lstm_fwd call, until ptts_device_status_clear().  Reading it is a host
+ * returns PTTS_EDEVICE (message in ptts_last_error(), bit mask in *word_out: 1 = Conv2D hand-off, 2 = reserved, formerly the
+ * persistent LSTM's hand-off) from then on, and so does every later ptts_conv2d_mfma_fwd call, until ptts_device_status_clear().  Reading it is a host
  * memory load (no synchronisation): call it at step boundaries.  The reference has no counterpart (TF raises from Session.run,
  * optimizertts.py:254 turns a NaN cost into a ValueError); this is how a corrupted launch becomes an error instead of a bad step.
  * ptts_device_status_word() returns the HOST address of the first word (tests poke it to exercise the host logic without a GPU);
@@ -537,14 +537,9 @@ size_t ptts_lstm_bwd_workspace_bytes(int B, int T, int H, int ndir);
 int ptts_lstm_bwd(const float* dh_out /*[B,T,ndir*H]*/, const float* U, const float* gates, const float* c_out,
                   float* dgates, void* workspace, size_t workspace_bytes,
                   int B, int T, int H, int ndir, int reverse, void* stream);
-/* Optionally the T step launches of a recurrence go out as ONE hipGraph launch: the chain of a (pointers, shape) tuple is captured once and
- * replayed while the same addresses come back (a training loop's allocation pattern repeats); misses capture anew (16 entries,
- * least recently used dropped), repeated misses fall back to plain launches, a call inside a stream capture joins that capture.
- * Off by default; PTTS_LSTM_GRAPH=1 or ptts_set_lstm_graph(1) switch it on.  Counters since load: replays, captures,
- * plain-launch fallbacks. */
-int ptts_set_lstm_graph(int on);
+/* Kept for bench.py, which reports these counters.  The replay of a recurrence's step launches as one hipGraph was removed
+ * (HISTORY.md), so it writes 0 to each non-null output and returns PTTS_OK. */
 int ptts_lstm_graph_stats(unsigned long long* hits, unsigned long long* captures, unsigned long long* direct);
-int ptts_lstm_graph_clear(void);
 
 /* ---------------------------------------------------------------------------------------
  * Keras GRU, reset_after = False (gates z, r, h; activation tanh, recurrent_activation

@@ -9,9 +9,6 @@
 // read coalesced along the unit index (it stays L2-resident: 1 MiB per direction at H = 256).
 // Round-1 form: generic in (B, H); an MFMA 16x16x4 tile version is the planned replacement.
 #include "common.h"
-#include <cstdlib>
-#include <mutex>
-#include <vector>
 
 namespace ptts {
 
@@ -465,267 +462,21 @@ __global__ __launch_bounds__(64 * NW) void lstm_bwd_step_pk_kernel(
 
 static inline bool lstm_pk_ok(int H) { return H % 64 == 0 && ((H / 16) <= 16 ? true : (H / 16) % 16 == 0); }
 
-
-// ------------------------------------------------------------------------------------------------
-// Persistent forward recurrence (H = 256): ONE launch for all T steps.
-//
-// The recurrence of one (direction, 16-sample slice) -- a "group" -- involves 32 workgroups of 8 hidden units each (the
-// tiling of lstm_fwd_step_pk_kernel); nothing couples different groups.  A workgroup keeps its slice of U (32 registers per
-// lane) and its cell state c in registers for the whole sequence; what crosses workgroups per step is h_t: 512 bytes
-// written, the group's 16 KB read.  It travels as DATA-TAGGED GRANULES (MI355X_MICROARCH.md, hand-off rows): every value is
-// one naturally aligned 8-byte {h, step tag} written by ONE sc1 store and read by sc1 loads until the tag is the expected
-// one -- no flag, no counter, no drain, no ordering to get wrong.  (A first version with sc1 payload + drained stores + a
-// barrier + one agent-scope counter add per workgroup + a polled counter measured 7.0 us per step, slower than the 6.3 us of
-// the per-step launches it replaces.)  Two granule buffers by step parity: a workgroup can be one step ahead of the slowest
-// member of its group, never two (it needs that member's h first).  Group = blockIdx % groups, so with groups = 8 (B = 64,
-// both directions) the 32 members of a group sit on one XCD (workgroups go to XCDs round-robin); any other placement is
-// slower, not wrong.  A poll that does not match within ~2^21 rounds (seconds: a workgroup of the group never became
-// resident) gives up for good: no hang, NaNs in the outputs from that step on AND STATUS_LSTM_HANDOFF in the device status word
-// (common.h), so that ptts_lstm_fwd / ptts_device_status return PTTS_EDEVICE from the next call on instead of a silent bad step.
-// ------------------------------------------------------------------------------------------------
-struct LstmPersistArgs {
-    const float* xproj; const float* Upk; float* h_out; float* gates; float* c_out; unsigned long long* xbuf;
-    int B, T, ndir, reverse, groups;
-    unsigned* status;
-};
-
-__global__ __launch_bounds__(256) void lstm_fwd_persistent_kernel(LstmPersistArgs a) {
-    constexpr int H = 256, KS = 16;
-    __shared__ float red[2][4][2][256];
-    __shared__ volatile int give_up;
-    const int g = blockIdx.x % a.groups, jt = blockIdx.x / a.groups;        // 32 members per group
-    const int nslices = a.groups / a.ndir;
-    const int d = g / nslices, b0 = (g - d * nslices) * 16, j0 = jt * 8;
-    const bool rev = a.ndir == 2 ? d == 1 : a.reverse != 0;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r16 = lane & 15, q = lane >> 4;
-    const int B = a.B, T = a.T, ndir = a.ndir;
-    const long long G4 = 4LL * H, HH = (long long)ndir * H;
-    if (tid == 0) give_up = 0;
-    // this lane's slice of U: k = wave * 64 + q * 16 + st, columns (gate pair, unit) = r16
-    f32x4a uv[KS / 2];
-    {
-        const float* up = a.Upk + ((((long long)d * (H / 8) + jt) * 4 + wave) * 64 + lane) * KS * 2;
-#pragma unroll
-        for (int i = 0; i < KS / 2; ++i) uv[i] = *reinterpret_cast<const f32x4a*>(up + 4 * i);
-    }
-    const int bb = tid >> 3, jj = tid & 7;
-    const int eb = b0 + bb, ej = j0 + jj;
-    const bool epi = tid < 128 && eb < B;
-    const bool feeds = b0 + r16 < B;                                         // the sample whose h this lane feeds to the MFMA exists
-    // granules of the group: [parity][16 samples][256 units]
-    unsigned long long* const xg = a.xbuf + (size_t)g * 16 * H;
-    const size_t xpar = (size_t)a.groups * 16 * H;
-    const unsigned long long* const xin = xg + (size_t)r16 * H + wave * (H / 4) + q * KS;
-    unsigned long long* const xout = xg + (size_t)bb * H + ej;
-    float c = 0.f;
-    bool gave_up = false;
-    __syncthreads();
-    for (int s = 0; s < T; ++s) {
-        const int t = rev ? T - 1 - s : s;
-        float xv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (epi) {
-            const float* xp = a.xproj + (((long long)eb * T + t) * ndir + d) * G4;
-#pragma unroll
-            for (int gt = 0; gt < 4; ++gt) xv[gt] = xp[gt * H + ej];
-        }
-        float (*rd)[2][256] = red[s & 1];
-        if (s > 0) {
-            // h of the previous step: 16 granules of this lane's sample, tag = s
-            const unsigned long long* xp = xin + ((s - 1) & 1) * xpar;
-            unsigned long long gr[KS];
-            int rounds = 0;
-            gave_up = gave_up || give_up != 0;
-            for (;;) {
-#pragma unroll
-                for (int i = 0; i < KS; ++i) gr[i] = __hip_atomic_load(xp + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                bool ok = true;
-#pragma unroll
-                for (int i = 0; i < KS; ++i) ok = ok && (unsigned)(gr[i] >> 32) == (unsigned)s;
-                if (__all(ok || !feeds) || gave_up) break;
-                __builtin_amdgcn_s_sleep(1);
-                if (++rounds > (1 << 21)) {
-                    gave_up = true; give_up = 1;
-                    if (lane == 0) raise_status(a.status, STATUS_SLOT_LSTM, STATUS_LSTM_HANDOFF);
-                }
-            }
-            f32x4v acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < KS; ++i) {
-                float av = feeds ? __builtin_bit_cast(float, (unsigned)gr[i]) : 0.f;
-                if (gave_up) av = __builtin_nanf("");
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, uv[i / 2][(i % 2) * 2], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, uv[i / 2][(i % 2) * 2 + 1], acc1, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                rd[wave][0][(q * 4 + r) * 16 + r16] = acc0[r];
-                rd[wave][1][(q * 4 + r) * 16 + r16] = acc1[r];
-            }
-            __syncthreads();
-        }
-        if (epi) {
-            float a4[4];
-#pragma unroll
-            for (int gt = 0; gt < 4; ++gt) {
-                float v = xv[gt];
-                if (s > 0) {
-                    const int idx = bb * 16 + (gt & 1) * 8 + jj;
-                    v += rd[0][gt >> 1][idx] + rd[1][gt >> 1][idx] + rd[2][gt >> 1][idx] + rd[3][gt >> 1][idx];
-                }
-                a4[gt] = v;
-            }
-            const float gi = sigmoidf_(a4[0]), gf = sigmoidf_(a4[1]), gc = tanhf(a4[2]), go = sigmoidf_(a4[3]);
-            const long long so = ((long long)eb * T + t) * HH + (long long)d * H + ej;
-            c = gf * c + gi * gc;
-            const float h = go * tanhf(c);
-            // the hand-off first: {h, tag s + 1} in one 8-byte sc1 store
-            __hip_atomic_store(xout + (s & 1) * xpar, ((unsigned long long)(unsigned)(s + 1) << 32) | __builtin_bit_cast(unsigned, h),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a.c_out[so] = c;
-            a.h_out[so] = h;
-            float* gp = a.gates + (((long long)eb * T + t) * ndir + d) * G4;
-            gp[ej] = gi; gp[H + ej] = gf; gp[2 * H + ej] = gc; gp[3 * H + ej] = go;
-        }
-    }
-}
-
 }  // namespace ptts
 
 using namespace ptts;
 
-// the persistent forward kernel: H = 256, at least two steps, all workgroups resident at once (<= 4 per CU).  OFF by
-// default (PTTS_LSTM_PERSISTENT=1 selects it, read at every call): at [64,400] it measured 10.6 us per step with the
-// data-tagged granules below and 7.0 us with a drained-store + counter hand-off, against 6.3 us for the per-step launches --
-// every sc1 round trip of the hand-off costs about what a kernel boundary does.
-static bool lstm_persistent_ok(int B, int T, int H, int ndir) {
-    const char* e = getenv("PTTS_LSTM_PERSISTENT");
-    const int groups = ((B + 15) / 16) * ndir;
-    if (!(e && atoi(e) != 0 && H == 256 && T >= 2 && groups * 32 <= 1024)) return false;
-    // every workgroup of the grid must be resident at once (the members of a group wait for each other): refuse the path --
-    // the per-step launches run instead -- unless the occupancy of an EMPTY chip covers the grid.  (Kernels of other streams
-    // can still hold CUs; the kernel's poll then gives up after ~2^21 rounds and the step shows NaNs: opt-in, experimental.)
-    static int per_cu = -1, ncu = 0;
-    if (per_cu < 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&lstm_fwd_persistent_kernel), 256, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            per_cu = 0;
-        } else {
-            ncu = prop.multiProcessorCount;
-        }
-    }
-    return (long long)per_cu * ncu >= (long long)groups * 32;
-}
-
-// ---- the T launches of a recurrence replayed as ONE hipGraph launch ---------------------------------------------------------------
-// A generator step spends 2 x 400 launches on the BLSTM; enqueued one by one they hold the host for about a millisecond each way
-// (the wide kernels of the other branches wait behind them in the host's launch order), so the chain of a (pointers, shape) tuple is
-// captured once, instantiated and replayed: the training loop's allocation pattern repeats, so the same addresses come back step after
-// step.  A miss captures anew (least recently used entry dropped); when misses keep coming (addresses that do not repeat) the
-// launches go out directly again and instantiation is retried only now and then.  Inside somebody else's capture (the optimiser's
-// whole-step graph) the launches simply join that graph.  Off by default (PTTS_LSTM_GRAPH=1 / ptts_set_lstm_graph(1) switch it on):
-// measured -0.1 ... -0.4 ms per generator step when the addresses repeat, but a capture costs more than it saves when they do not.
-struct LstmGraphKey {
-    int kind, B, T, H, ndir, reverse;
-    const void* p[6];
-    int device = -1;        // filled in by lstm_graph_run: an executable graph belongs to the device it was instantiated on
-    bool operator==(const LstmGraphKey& o) const {
-        if (kind != o.kind || B != o.B || T != o.T || H != o.H || ndir != o.ndir || reverse != o.reverse || device != o.device) return false;
-        for (int i = 0; i < 6; ++i) if (p[i] != o.p[i]) return false;
-        return true;
-    }
-};
-struct LstmGraphEntry { LstmGraphKey k; hipGraphExec_t exec; unsigned long long stamp; };
-static std::mutex g_lg_mu;
-static std::vector<LstmGraphEntry> g_lg;
-static unsigned long long g_lg_clock = 0, g_lg_hits = 0, g_lg_misses = 0, g_lg_direct = 0;
-static int g_lg_consecutive_misses = 0;
-constexpr size_t LSTM_GRAPH_CACHE = 16;
-
-static int g_lstm_graph = -1;      // -1: from the environment (PTTS_LSTM_GRAPH, default off); 0 / 1: ptts_set_lstm_graph
-static bool lstm_graph_on() {
-    if (g_lstm_graph < 0) { const char* e = getenv("PTTS_LSTM_GRAPH"); g_lstm_graph = e ? (atoi(e) != 0) : 0; }
-    return g_lstm_graph != 0;
-}
-extern "C" int ptts_set_lstm_graph(int on) { g_lstm_graph = on ? 1 : 0; return PTTS_OK; }
-
-template <class F>
-static int lstm_graph_run(const LstmGraphKey& key_in, hipStream_t st, const char* what, F&& launch_all) {
-    LstmGraphKey key = key_in;
-    if (hipGetDevice(&key.device) != hipSuccess) { (void)hipGetLastError(); key.device = -1; }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (!lstm_graph_on() || key.T < 8 || hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-        launch_all();
-        return check_launch(what);
-    }
-    std::lock_guard<std::mutex> lock(g_lg_mu);
-    ++g_lg_clock;
-    for (auto& e : g_lg)
-        if (e.k == key) {
-            e.stamp = g_lg_clock; ++g_lg_hits; g_lg_consecutive_misses = 0;
-            if (hipGraphLaunch(e.exec, st) != hipSuccess) { set_error("%s: hipGraphLaunch failed", what); return PTTS_ELAUNCH; }
-            return PTTS_OK;
-        }
-    ++g_lg_misses;
-    if (g_lg_consecutive_misses >= 8 && (g_lg_misses & 63) != 0) {      // addresses do not repeat: plain launches
-        ++g_lg_direct;
-        launch_all();
-        return check_launch(what);
-    }
-    ++g_lg_consecutive_misses;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); launch_all(); return check_launch(what); }
-    launch_all();
-    // The launches above went into the capture, not to the device: if the capture cannot be ended or instantiated the recurrence has
-    // NOT run yet -- clear the error, launch it directly, and stay on direct launches from now on (retried only now and then).
-    auto direct_after_failure = [&]() {
-        (void)hipGetLastError();
-        g_lg_consecutive_misses = 1 << 20;
-        ++g_lg_direct;
-        launch_all();
-        return check_launch(what);
-    };
-    if (hipStreamEndCapture(st, &graph) != hipSuccess || !graph) return direct_after_failure();
-    const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ie != hipSuccess || !exec) return direct_after_failure();
-    if (g_lg.size() >= LSTM_GRAPH_CACHE) {
-        size_t lru = 0;
-        for (size_t i = 1; i < g_lg.size(); ++i) if (g_lg[i].stamp < g_lg[lru].stamp) lru = i;
-        (void)hipGraphExecDestroy(g_lg[lru].exec);
-        g_lg.erase(g_lg.begin() + lru);
-    }
-    g_lg.push_back({key, exec, g_lg_clock});
-    if (hipGraphLaunch(exec, st) != hipSuccess) { set_error("%s: hipGraphLaunch failed", what); return PTTS_ELAUNCH; }
-    return PTTS_OK;
-}
-
-// hits / captures / direct-launch fallbacks of the recurrence graphs so far (bench.py reports them)
+// kept for bench.py, which reports these counters: the recurrence graphs were removed, so they are always zero
 extern "C" int ptts_lstm_graph_stats(unsigned long long* hits, unsigned long long* captures, unsigned long long* direct) {
-    std::lock_guard<std::mutex> lock(g_lg_mu);
-    if (hits) *hits = g_lg_hits;
-    if (captures) *captures = g_lg_misses - g_lg_direct;
-    if (direct) *direct = g_lg_direct;
-    return PTTS_OK;
-}
-
-// drop every cached recurrence graph (buffers about to be freed for good, tests)
-extern "C" int ptts_lstm_graph_clear(void) {
-    std::lock_guard<std::mutex> lock(g_lg_mu);
-    for (auto& e : g_lg) (void)hipGraphExecDestroy(e.exec);
-    g_lg.clear();
-    g_lg_consecutive_misses = 0;
+    if (hits) *hits = 0;
+    if (captures) *captures = 0;
+    if (direct) *direct = 0;
     return PTTS_OK;
 }
 
 extern "C" size_t ptts_lstm_fwd_workspace_bytes(int B, int T, int H, int ndir) {
-    (void)T;
-    const size_t granules = (size_t)2 * ((B + 15) / 16) * ndir * 16 * H * 8;     // the persistent kernel's {h, tag} buffers, behind the packed U
-    return lstm_pk_ok(H) ? (size_t)ndir * 4 * H * H * sizeof(float) + granules : 16;
+    (void)B; (void)T;
+    return lstm_pk_ok(H) ? (size_t)ndir * 4 * H * H * sizeof(float) : 16;
 }
 
 extern "C" int ptts_lstm_fwd(const float* xproj, const float* U, float* h_out, float* gates, float* c_out,
@@ -739,30 +490,15 @@ extern "C" int ptts_lstm_fwd(const float* xproj, const float* U, float* h_out, f
     const size_t lds = (size_t)LY * H * sizeof(float);
     if (lstm_pk_ok(H) && workspace && workspace_bytes >= ptts_lstm_fwd_workspace_bytes(B, T, H, ndir)) {
         float* Upk = (float*)workspace;
-        if (lstm_persistent_ok(B, T, H, ndir)) {
-            if (int rc0 = check_status("lstm_fwd")) return rc0;       // an earlier persistent launch gave up: sticky
-            hipLaunchKernelGGL(lstm_pack_u_fwd_kernel, dim3(1024), dim3(256), 0, st, U, Upk, H, ndir);
-            LstmPersistArgs pa;
-            pa.xproj = xproj; pa.Upk = Upk; pa.h_out = h_out; pa.gates = gates; pa.c_out = c_out;
-            pa.xbuf = reinterpret_cast<unsigned long long*>(Upk + (size_t)ndir * 4 * H * H);
-            pa.B = B; pa.T = T; pa.ndir = ndir; pa.reverse = reverse; pa.groups = ((B + 15) / 16) * ndir;
-            pa.status = status_words();
-            int rc = zero_f32(reinterpret_cast<float*>(pa.xbuf), (size_t)2 * pa.groups * 16 * H * 2, st);      // tags 0
-            if (rc) return rc;
-            hipLaunchKernelGGL(lstm_fwd_persistent_kernel, dim3(pa.groups * 32), dim3(256), 0, st, pa);
-            return check_launch("lstm_fwd_persistent");
-        }
         dim3 mgrid(H / 8, (B + 15) / 16, ndir);
         const int KS = H / 16;
-        const LstmGraphKey key{0, B, T, H, ndir, reverse, {xproj, U, h_out, gates, c_out, workspace}};
-        return lstm_graph_run(key, st, "lstm_fwd_pk", [&]() {
-            hipLaunchKernelGGL(lstm_pack_u_fwd_kernel, dim3(1024), dim3(256), 0, st, U, Upk, H, ndir);
-            for (int s = 0; s < T; ++s) {
-                if (KS == 4) hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<4>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
-                else if (KS == 8) hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<8>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
-                else hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<16>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
-            }
-        });
+        hipLaunchKernelGGL(lstm_pack_u_fwd_kernel, dim3(1024), dim3(256), 0, st, U, Upk, H, ndir);
+        for (int s = 0; s < T; ++s) {
+            if (KS == 4) hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<4>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
+            else if (KS == 8) hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<8>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
+            else hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<16>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
+        }
+        return check_launch("lstm_fwd_pk");
     }
     if (H % 16 == 0) {
         dim3 mgrid(H / 8, (B + 15) / 16, ndir);
@@ -776,12 +512,6 @@ extern "C" int ptts_lstm_fwd(const float* xproj, const float* U, float* h_out, f
                            reverse, s);
     }
     return check_launch("lstm_fwd");
-}
-
-static int lstm_bwd_waves() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("PTTS_LSTM_BWD_WAVES"); v = e ? atoi(e) : 8; }
-    return v;
 }
 
 extern "C" size_t ptts_lstm_bwd_workspace_bytes(int B, int T, int H, int ndir) {
@@ -806,18 +536,16 @@ extern "C" int ptts_lstm_bwd(const float* dh_out, const float* U, const float* g
     float* dc_state = UTpk + (size_t)ndir * 4 * H * H;
     if (lstm_pk_ok(H)) {
         dim3 pgrid(H / 16, (B + 15) / 16, ndir);
-        const bool w8 = H == 256 && lstm_bwd_waves() == 8;
-        const LstmGraphKey key{1, B, T, H, ndir, reverse, {dh_out, U, gates, c_out, dgates, workspace}};
-        return lstm_graph_run(key, st, "lstm_bwd_pk", [&]() {
-            hipLaunchKernelGGL(lstm_pack_u_bwd_kernel, dim3(1024), dim3(256), 0, st, U, UTpk, H, ndir);
-            for (int s = T - 1; s >= 0; --s)
-                if (w8)
-                    hipLaunchKernelGGL(lstm_bwd_step_pk_kernel<8>, pgrid, dim3(512), 0, st, dh_out,
-                                       (const float*)UTpk, gates, c_out, dgates, dc_state, B, T, H, ndir, reverse, s);
-                else
-                    hipLaunchKernelGGL(lstm_bwd_step_pk_kernel<4>, pgrid, dim3(256), 0, st, dh_out,
-                                       (const float*)UTpk, gates, c_out, dgates, dc_state, B, T, H, ndir, reverse, s);
-        });
+        const bool w8 = H == 256;
+        hipLaunchKernelGGL(lstm_pack_u_bwd_kernel, dim3(1024), dim3(256), 0, st, U, UTpk, H, ndir);
+        for (int s = T - 1; s >= 0; --s)
+            if (w8)
+                hipLaunchKernelGGL(lstm_bwd_step_pk_kernel<8>, pgrid, dim3(512), 0, st, dh_out,
+                                   (const float*)UTpk, gates, c_out, dgates, dc_state, B, T, H, ndir, reverse, s);
+            else
+                hipLaunchKernelGGL(lstm_bwd_step_pk_kernel<4>, pgrid, dim3(256), 0, st, dh_out,
+                                   (const float*)UTpk, gates, c_out, dgates, dc_state, B, T, H, ndir, reverse, s);
+        return check_launch("lstm_bwd_pk");
     }
     const long long tot = (long long)ndir * 4 * H * H;
     int tb = (int)((tot + 255) / 256);

@@ -984,7 +984,8 @@ def test_affine_act_bwd_wide(ops, act):
     close(shd.grad, shr.grad, rtol=2e-4, atol=2e-3, what='dshift')
 
 
-@pytest.mark.parametrize('case', [(3, 7, 5, 4), (16, 20, 24, 64), (5, 33, 10, 70), (20, 9, 12, 32), (64, 6, 40, 256)])
+@pytest.mark.parametrize('case', [(3, 7, 5, 4), (16, 20, 24, 64), (5, 33, 10, 70), (20, 9, 12, 32), (64, 6, 40, 256),
+                                  (20, 33, 8, 256), (64, 9, 12, 256)])
 def test_blstm(ops, case):
     B, T, In, H = case
     g = gen(10)
@@ -1209,35 +1210,10 @@ def test_dense_weight_gradient_bf16x6(ops, case):
         close(db_s, dY64.sum(0), rtol=2e-4, atol=2e-3, what='db ' + name)
 
 
-def test_persistent_lstm_forward_equals_the_per_step_launches(ops, monkeypatch):
-    """csrc/lstm.hip, lstm_fwd_persistent_kernel (one launch for all T steps, h handed from workgroup to workgroup as
-    data-tagged sc1 granules; off by default because it measured slower than the per-step launches): same arithmetic in
-    the same order, so h, c and the gates must be BIT-identical to the per-step kernels -- both directions, a batch that is no
-    multiple of the 16-sample slice, and against the fp64 oracle."""
-    g = gen(13)
-    for (B, T, In, H) in ((64, 9, 12, 256), (20, 33, 8, 256)):
-        x = torch.randn(B, T, In, generator=g, dtype=torch.float64)
-        W = torch.randn(In, 8 * H, generator=g, dtype=torch.float64) / math.sqrt(In)
-        U = torch.randn(2, H, 4 * H, generator=g, dtype=torch.float64) / math.sqrt(H)
-        b = torch.randn(8 * H, generator=g, dtype=torch.float64) * 0.2
-        monkeypatch.delenv('PTTS_LSTM_PERSISTENT', raising=False)
-        with ops._hip.KernelTimer() as kt:
-            h_steps = ops.lstm(dev(x), dev(W), dev(U), dev(b))
-        monkeypatch.setenv('PTTS_LSTM_PERSISTENT', '1')
-        h_pers = ops.lstm(dev(x), dev(W), dev(U), dev(b))
-        monkeypatch.delenv('PTTS_LSTM_PERSISTENT', raising=False)
-        torch.cuda.synchronize()
-        assert torch.equal(h_pers, h_steps), float((h_pers - h_steps).abs().max())
-        close(h_pers, O.blstm(x, W, U, b), rtol=2e-4, atol=2e-5, what='h')
-
-
-def test_lstm_recurrence_graph_replay_equals_the_plain_launches(ops):
-    """csrc/lstm.hip, lstm_graph_run (ptts_set_lstm_graph(1)): the T step launches of the forward and of the backward recurrence
-    captured once per (pointers, shape) tuple and replayed as one hipGraph launch.  Same kernels in the same order: h and every
-    gradient BIT-identical to the plain launches; a second call on the same buffers is a replay (counters), a call on other
-    buffers captures anew; ptts_lstm_graph_clear drops the cache."""
-    import ctypes
-    lib = ops._hip.lib()
+def test_lstm_is_deterministic_in_deterministic_mode(ops):
+    """csrc/lstm.hip, the per-step launches of the forward and of the backward recurrence at H = 256 with a batch that is no
+    multiple of the 16-sample slice: under ops.deterministic(True) (the products around the recurrence -- dx, dW, dU -- without
+    order-dependent atomics) two runs on fresh tensors give h and every gradient BIT-identical."""
     g = gen(31)
     B, T, In, H = 20, 24, 8, 256
     x = torch.randn(B, T, In, generator=g, dtype=torch.float64)
@@ -1253,30 +1229,15 @@ def test_lstm_recurrence_graph_replay_equals_the_plain_launches(ops):
         torch.cuda.synchronize()
         return [h.detach().clone()] + [t.grad.detach().clone() for t in xs]
 
-    def stats():
-        v = [ctypes.c_ulonglong(0) for _ in range(3)]
-        lib.ptts_lstm_graph_stats(*[ctypes.byref(q) for q in v])
-        return [q.value for q in v]
-
-    lib.ptts_set_lstm_graph(0)
-    ops.deterministic(True)          # the products around the recurrence (dx, dW, dU) without order-dependent atomics
-    plain = run()
+    was = ops.deterministic()
+    ops.deterministic(True)
     try:
-        lib.ptts_lstm_graph_clear()
-        lib.ptts_set_lstm_graph(1)
-        s0 = stats()
         first = run()
-        s1 = stats()
-        again = run()           # the allocator hands the same blocks back: replays, or new captures -- identical results either way
-        s2 = stats()
+        again = run()
     finally:
-        lib.ptts_set_lstm_graph(0)
-        lib.ptts_lstm_graph_clear()
-        ops.deterministic(False)
-    assert s1[1] - s0[1] == 2 and s1[2] == s0[2], (s0, s1)              # forward + backward chains captured
-    assert (s2[0] - s1[0]) + (s2[1] - s1[1]) == 2, (s1, s2)
-    for name, a, c, p in zip(('h', 'dx', 'dW', 'dU', 'db'), first, again, plain):
-        assert torch.equal(a, p) and torch.equal(c, p), name
+        ops.deterministic(was)
+    for name, a, c in zip(('h', 'dx', 'dW', 'dU', 'db'), first, again):
+        assert torch.equal(a, c), name
 
 
 def test_bn_batch_stats_one_launch_equals_the_three_launch_path(ops):
