@@ -16,7 +16,7 @@ static inline int ew_blocks(long long n, int per_thread = 4) {
 // ---------------------------------------------------------------------------------------------
 // two-quantity column reduction over [rows, C]: deterministic two-stage, fp64 accumulation
 // ---------------------------------------------------------------------------------------------
-constexpr int MAXC_SLOTS = 8;   // C <= 2048
+constexpr int MAXC_SLOTS = 8;   // C <= 2048 in colreduce2_kernel; wider inputs take colreduce2_wide_kernel
 
 template <class Op>
 __global__ __launch_bounds__(EW_THREADS) void colreduce2_kernel(Op op, long long rows, int C,
@@ -68,6 +68,25 @@ __global__ __launch_bounds__(EW_THREADS) void colreduce2_kernel(Op op, long long
             if (c < C) { out[c] = q1[s]; out[C + c] = q2[s]; }
         }
     }
+}
+
+// C > MAXC_SLOTS * EW_THREADS (the gate gradients of a recurrence at H >= 512: ndir * 4H columns): one lane per column,
+// grid (row blocks, ceil(C / EW_THREADS)); the same partials layout and the same fixed order as above.
+template <class Op>
+__global__ __launch_bounds__(EW_THREADS) void colreduce2_wide_kernel(Op op, long long rows, int C,
+                                                                     double* __restrict__ partials) {
+    const int c = blockIdx.y * EW_THREADS + threadIdx.x;
+    if (c >= C) return;
+    double q1 = 0.0, q2 = 0.0;
+    for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
+        float a, b;
+        op(row * C + c, c, a, b);
+        q1 += (double)a;
+        q2 += (double)b;
+    }
+    double* out = partials + (size_t)blockIdx.x * 2 * C;
+    out[c] = q1;
+    out[C + c] = q2;
 }
 
 // Vectorised form of the two-quantity column reduction for C % 4 == 0, C <= 1024 and 16-byte aligned operands: every
@@ -765,7 +784,7 @@ extern "C" size_t ptts_colstats_workspace_bytes(long long rows, int C) {
 template <class Op>
 static int run_colreduce(const Op& op, long long rows, int C, double* out, void* workspace,
                          size_t workspace_bytes, hipStream_t st, const char* what) {
-    PTTS_REQUIRE(C > 0 && C <= MAXC_SLOTS * EW_THREADS, "%s: C=%d unsupported", what, C);
+    PTTS_REQUIRE(C > 0, "%s: C=%d unsupported", what, C);
     PTTS_REQUIRE(rows > 0, "%s: rows=%lld", what, rows);
     const int nb = colreduce_blocks(rows, C);
     const size_t need = (size_t)nb * 2 * C * sizeof(double);
@@ -773,7 +792,11 @@ static int run_colreduce(const Op& op, long long rows, int C, double* out, void*
         set_error("%s: workspace %zu < %zu", what, workspace_bytes, need);
         return PTTS_EWORKSPACE;
     }
-    hipLaunchKernelGGL((colreduce2_kernel<Op>), dim3(nb), dim3(EW_THREADS), 0, st, op, rows, C, (double*)workspace);
+    if (C > MAXC_SLOTS * EW_THREADS)
+        hipLaunchKernelGGL((colreduce2_wide_kernel<Op>), dim3(nb, (C + EW_THREADS - 1) / EW_THREADS), dim3(EW_THREADS), 0, st, op, rows,
+                           C, (double*)workspace);
+    else
+        hipLaunchKernelGGL((colreduce2_kernel<Op>), dim3(nb), dim3(EW_THREADS), 0, st, op, rows, C, (double*)workspace);
     int rc = check_launch(what);
     if (rc) return rc;
     hipLaunchKernelGGL(colreduce_final_kernel, dim3((2 * C + 7) / 8), dim3(256), 0, st,

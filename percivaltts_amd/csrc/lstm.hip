@@ -4,10 +4,12 @@
 //
 // The input projection x.W+b and every weight gradient are large GEMMs done by ptts_gemm; what
 // is left here is the T-sequential part: one small launch per time step that adds h_{t-1}.U,
-// applies the gate non-linearities and advances (c, h).  Each lane owns one (sample, unit)
-// pair and all four of its gates, h_{t-1} of the workgroup's samples is staged in LDS, U is
-// read coalesced along the unit index (it stays L2-resident: 1 MiB per direction at H = 256).
-// Round-1 form: generic in (B, H); an MFMA 16x16x4 tile version is the planned replacement.
+// applies the gate non-linearities and advances (c, h).  Three per-step paths, chosen by H alone:
+//   packed MFMA : lstm_pk_ok(H), i.e. H % 64 == 0 and (H <= 256 or H % 256 == 0): 64, 128, 192, 256, 512, 768, 1024, ...
+//                 (forward only with a workspace of ptts_lstm_fwd_workspace_bytes; without one it takes the MFMA path)
+//   MFMA        : every other H % 16 == 0 (16, 32, 48, 80, ..., 320, 384, ...)
+//   scalar      : any other H; one lane per (sample, unit), h_{t-1} staged in LDS
+// Limits: H <= 4096 forward, H <= 1024 backward (the scalar kernels' LDS rows bound every path).
 #include "common.h"
 
 namespace ptts {
@@ -494,9 +496,10 @@ extern "C" int ptts_lstm_fwd(const float* xproj, const float* U, float* h_out, f
         const int KS = H / 16;
         hipLaunchKernelGGL(lstm_pack_u_fwd_kernel, dim3(1024), dim3(256), 0, st, U, Upk, H, ndir);
         for (int s = 0; s < T; ++s) {
-            if (KS == 4) hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<4>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
-            else if (KS == 8) hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<8>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
-            else hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<16>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
+            // the chunk must divide KS (a lane owns exactly KS k-steps of Upk and of its h row segment); H % 64 == 0 gives KS % 4 == 0
+            if (KS % 16 == 0) hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<16>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
+            else if (KS % 8 == 0) hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<8>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
+            else hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<4>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s);
         }
         return check_launch("lstm_fwd_pk");
     }
