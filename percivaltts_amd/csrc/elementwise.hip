@@ -18,6 +18,15 @@ static inline int ew_blocks(long long n, int per_thread = 4) {
 // ---------------------------------------------------------------------------------------------
 constexpr int MAXC_SLOTS = 8;   // C <= 2048 in colreduce2_kernel; wider inputs take colreduce2_wide_kernel
 
+// The second quantity of an Op.  Op::SQUARE (the statistics): the square of the first, formed in fp64, where the product of two
+// floats is exact.  Rounded to float32 first, the squares of a constant column all carry the same error and var = E[x^2] - mean^2
+// came out as that error instead of 0: against eps = 1e-3 up to 3e-4 of scale at |x| = 3.
+template <class Op>
+__device__ __forceinline__ double second_quantity(float a, float b) {
+    if constexpr (Op::SQUARE) return (double)a * (double)a;
+    else return (double)b;
+}
+
 template <class Op>
 __global__ __launch_bounds__(EW_THREADS) void colreduce2_kernel(Op op, long long rows, int C,
                                                                 double* __restrict__ partials) {
@@ -34,7 +43,7 @@ __global__ __launch_bounds__(EW_THREADS) void colreduce2_kernel(Op op, long long
                 float a, b;
                 op(row * C + c, c, a, b);
                 q1 += (double)a;
-                q2 += (double)b;
+                q2 += second_quantity<Op>(a, b);
             }
         }
         sh[0][tid] = q1;
@@ -58,7 +67,7 @@ __global__ __launch_bounds__(EW_THREADS) void colreduce2_kernel(Op op, long long
                     float a, b;
                     op(row * C + c, c, a, b);
                     q1[s] += (double)a;
-                    q2[s] += (double)b;
+                    q2[s] += second_quantity<Op>(a, b);
                 }
             }
         }
@@ -82,7 +91,7 @@ __global__ __launch_bounds__(EW_THREADS) void colreduce2_wide_kernel(Op op, long
         float a, b;
         op(row * C + c, c, a, b);
         q1 += (double)a;
-        q2 += (double)b;
+        q2 += second_quantity<Op>(a, b);
     }
     double* out = partials + (size_t)blockIdx.x * 2 * C;
     out[c] = q1;
@@ -91,8 +100,9 @@ __global__ __launch_bounds__(EW_THREADS) void colreduce2_wide_kernel(Op op, long
 
 // Vectorised form of the two-quantity column reduction for C % 4 == 0, C <= 1024 and 16-byte aligned operands: every
 // lane owns four adjacent channels and streams float4.  The loads of VU row sweeps are issued before any of them is
-// consumed (a lone 16-byte load per lane per iteration leaves the kernel latency-bound at ~1 TB/s); fp32 partials over
-// 16 rows are folded into fp64.  Op4 provides  load(off, regs)  and  apply(off, c, regs, a[4], b[4]).
+// consumed (a lone 16-byte load per lane per iteration leaves the kernel latency-bound at ~1 TB/s).  The gradient sums (ActBwdOp4)
+// fold fp32 partials over 16 rows into fp64; the statistics (Op4::SQUARE) add every value and its exact square in fp64.
+// Op4 provides  load(off, regs)  and  apply(off, c, regs, a[4], b[4]).
 constexpr int VU = 4;
 
 template <class Op4>
@@ -121,18 +131,27 @@ __global__ __launch_bounds__(EW_THREADS) void colreduce2_vec4_kernel(Op4 op, lon
                 if (row < rows) {
                     float a[4], b[4];
                     op.apply(row * C + c4 * 4, c4 * 4, regs[u], a, b);
+                    if constexpr (Op4::SQUARE) {
+                        // the statistics: sums and exact squares straight into fp64 (float32 partial sums put 2^-24 of noise on
+                        // mean and E[x^2], which var = E[x^2] - mean^2 of a constant or far-off-centre column does not forgive)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { fs[e] += a[e]; fq[e] += b[e]; }
+                        for (int e = 0; e < 4; ++e) { const double d = (double)a[e]; s[e] += d; q[e] = fma(d, d, q[e]); }
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { fs[e] += a[e]; fq[e] += b[e]; }
+                    }
                 }
             }
-            if (++n == 16 / VU) {
+            if (!Op4::SQUARE && ++n == 16 / VU) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { s[e] += fs[e]; q[e] += fq[e]; fs[e] = 0.f; fq[e] = 0.f; }
                 n = 0;
             }
         }
+        if constexpr (!Op4::SQUARE) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { s[e] += fs[e]; q[e] += fq[e]; }
+            for (int e = 0; e < 4; ++e) { s[e] += fs[e]; q[e] += fq[e]; }
+        }
     }
     double* out = partials + (size_t)blockIdx.x * 2 * C;
     if (C4 <= 32 && (C4 & (C4 - 1)) == 0 && R * C4 == EW_THREADS) {
@@ -207,6 +226,7 @@ static int colreduce_blocks(long long rows, int C) {
 }
 
 struct StatsOp {
+    static constexpr bool SQUARE = true;
     const float* x; int in_mode; const float* in_scale; const float* in_shift; const float* mask_src; float alpha;
     __device__ __forceinline__ void operator()(long long i, int c, float& a, float& b) const {
         float v = x[i];
@@ -231,6 +251,7 @@ __device__ __forceinline__ float act_fwd(float p, int act, float alpha) {
 }
 
 struct ActBwdOp {
+    static constexpr bool SQUARE = false;
     const float* dy; const float* x; const float* y; const float* scale; const float* shift; float* dx;
     int act; float alpha;
     __device__ __forceinline__ void operator()(long long i, int c, float& a, float& b) const {
@@ -259,6 +280,7 @@ struct ActBwdOp {
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 struct StatsOp4 {
+    static constexpr bool SQUARE = true;
     const float* x; int in_mode; const float* in_scale; const float* in_shift; const float* mask_src; float alpha;
     struct Regs { float4 v, m; };
     __device__ __forceinline__ void load(long long off, Regs& r) const {
@@ -283,6 +305,7 @@ struct StatsOp4 {
 };
 
 struct ActBwdOp4 {
+    static constexpr bool SQUARE = false;
     const float* dy; const float* x; const float* y; const float* scale; const float* shift; float* dx;
     int act; float alpha;
     struct Regs { float4 d, x, y; };
@@ -375,8 +398,6 @@ __global__ __launch_bounds__(EW_THREADS) void bn_stats_fused_kernel(const float*
     const int r = tid / C4, c4 = tid - r * C4;
     double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
     {
-        float fs[4] = {0, 0, 0, 0}, fq[4] = {0, 0, 0, 0};
-        int n = 0;
         const long long step = (long long)gridDim.x * R * VU;
         for (long long base = (long long)blockIdx.x * R * VU + r; base < rows; base += step) {
             float4 v[VU];
@@ -385,19 +406,14 @@ __global__ __launch_bounds__(EW_THREADS) void bn_stats_fused_kernel(const float*
                 const long long row = base + (long long)u * R;
                 v[u] = row < rows ? ld4(x + row * C + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
+            // sums and exact squares in fp64, in the order of colreduce2_vec4_kernel<StatsOp4> (a row past the end adds zeros)
 #pragma unroll
             for (int u = 0; u < VU; ++u) {
-                fs[0] += v[u].x; fs[1] += v[u].y; fs[2] += v[u].z; fs[3] += v[u].w;
-                fq[0] += v[u].x * v[u].x; fq[1] += v[u].y * v[u].y; fq[2] += v[u].z * v[u].z; fq[3] += v[u].w * v[u].w;
-            }
-            if (++n == 16 / VU) {
+                const double d[4] = {(double)v[u].x, (double)v[u].y, (double)v[u].z, (double)v[u].w};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { s[e] += fs[e]; q[e] += fq[e]; fs[e] = 0.f; fq[e] = 0.f; }
-                n = 0;
+                for (int e = 0; e < 4; ++e) { s[e] += d[e]; q[e] = fma(d[e], d[e], q[e]); }
             }
         }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { s[e] += fs[e]; q[e] += fq[e]; }
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -775,9 +791,18 @@ __global__ void adam_keras_kernel(float* __restrict__ p, const float* __restrict
 
 using namespace ptts;
 
+// Room for either reduction of [rows, C], and never less for more rows: a caller may size one buffer for its largest map.  The
+// vectorised kernel's own count drops where another pass begins (1024 workgroups for 1024 chunks, 513 for 1025), so its share is
+// the count of a single pass.
 extern "C" size_t ptts_colstats_workspace_bytes(long long rows, int C) {
-    int nb = colreduce_blocks(rows, C);
-    if (C % 4 == 0 && C <= 4 * EW_THREADS) { const int v = colreduce_vec4_blocks(rows, C); if (v > nb) nb = v; }
+    if (C <= 0) return 0;
+    long long nb = colreduce_blocks(rows, C);
+    if (C % 4 == 0 && C <= 4 * EW_THREADS) {
+        const long long per = (long long)(EW_THREADS / (C / 4)) * VU;
+        long long v = (rows + per - 1) / per;
+        if (v > 1024) v = 1024;
+        if (v > nb) nb = v;
+    }
     return (size_t)nb * 2 * (size_t)C * sizeof(double);
 }
 
@@ -826,6 +851,7 @@ extern "C" int ptts_colstats(const float* x, long long rows, int C, int in_mode,
                              const float* in_shift, const float* mask_src, float alpha, double* sums,
                              void* workspace, size_t workspace_bytes, void* stream) {
     PTTS_REQUIRE(x && sums, "colstats: null tensor");
+    PTTS_REQUIRE(C > 0, "colstats: C=%d unsupported", C);
     PTTS_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "colstats: scale/shift must come together");
     if (C % 4 == 0 && C <= 4 * EW_THREADS && al16(x) && al16(mask_src)) {
         StatsOp4 op4{x, in_mode, in_scale, in_shift, mask_src, alpha};
