@@ -121,18 +121,59 @@ def input_grad_only():
 
 
 # ----------------------------------------------------------------------------------------------
-# Deferred weight gradients: inside `deferred_weight_grads()` the Dense layers do not launch their
-# dW = a^T.dy product (4 tiles of 128x128 over K = 25 600: launch, zero-fill and a 128-way split for
-# 3.4 GFLOP) one by one; they queue it, and flush_weight_grads() runs every queued product of the
-# backward pass in ONE grouped launch that accumulates straight into the parameters' .grad buffers
-# (ptts_gemm_wgrad_grouped).  Only parameters whose .grad exists beforehand (FlatParams views) take
-# part; everything else keeps the immediate path.
+# Deferred weight gradients: inside `deferred_weight_grads()` a backward pass does not hand the gradients of parameters whose
+# .grad exists beforehand (FlatParams views: grad_target) to autograd; they reach the .grad buffers by one of three routes, all
+# kept by _Deferred:
+#   * queued Dense products (`items`, _defer_wgrad): dW = a^T.dy (4 tiles of 128x128 over K = 25 600: launch, zero-fill and a
+#     128-way split for 3.4 GFLOP) is not launched per layer; every PTTS_WG_FLUSH products of a stream, and the rest at flush
+#     time, run as ONE grouped launch that accumulates straight into the buffers (_launch_wgrads);
+#   * queued Conv2D partial rows (`conv_items`, _Deferred.queue_conv): the backward kernels leave per-workgroup partial sums of
+#     dW / dbias in a buffer of their own; flush time reduces the rows of every pass in ONE launch (_conv2d_reduce);
+#   * direct adds (BatchNorm, LSTM): the kernel or an add_ on the backward's own stream writes the buffer at once and only
+#     notes that stream (_Deferred.note_stream).
+# Every producer notes the stream it ran on.  flush_weight_grads() -- the context's exit -- makes the current stream wait for
+# every noted stream, whether or not anything is queued, then launches what is queued: work that follows it on the current
+# stream (the optimiser) sees every gradient of the context.  Everything else keeps the immediate path.
 # ----------------------------------------------------------------------------------------------
 class _Deferred(object):
     active = False
-    items = []          # (x2, dy2, mask, scale, shift, gw, gb, M_out, N, K_rows, mode, alpha)
+    items = []          # (stream handle, x2, dy2, mask, scale, shift, gw, gb, K_in, N, M_rows, mode, alpha)
     conv_items = []     # (partials buffer, byte offset of the rows, nblocks, npart, nw, cout, gw, gb): conv2d backward passes awaiting their reduction
-    streams = []
+    streams = []        # the streams the context's producers ran on
+
+    @classmethod
+    def live(cls):
+        """May a backward pass use the queue NOW?  Asked at backward time: the targets were noted at FORWARD time, and a backward
+        run after the forward's context closed would append to a list nobody flushes -- the gradients would be lost.
+        Deterministic mode keeps the immediate, fixed-order paths."""
+        return cls.active and not _Flags.deterministic
+
+    @classmethod
+    def targets(cls, *params):
+        """Forward time: the gradient buffer (grad_target) of each parameter if the queue is live, else None for each."""
+        return tuple([grad_target(p) for p in params] if cls.live() else [None] * len(params))
+
+    @classmethod
+    def note_stream(cls, s=None):
+        """Note the current stream (or `s`) for flush_weight_grads() to join; returns its raw handle.  A Stream object is built
+        only for a handle not seen in this context."""
+        sid = _hip.stream_id() if s is None else s.cuda_stream
+        if all(sid != q.cuda_stream for q in cls.streams):
+            cls.streams.append(torch.cuda.current_stream() if s is None else s)
+        return sid
+
+    @classmethod
+    def queue_conv(cls, *passes):
+        """Queue Conv2D passes (buffer, byte offset, nblocks, npart, nw, cout, gw, gb) launched on the current stream."""
+        cls.note_stream()
+        cls.conv_items.extend(passes)
+
+    @classmethod
+    def reset(cls):
+        """Empty the queue; returns what it held."""
+        st = (cls.items, cls.conv_items, cls.streams)
+        cls.items, cls.conv_items, cls.streams = [], [], []
+        return st
 
 
 @contextlib.contextmanager
@@ -144,18 +185,14 @@ def deferred_weight_grads():
         flush_weight_grads()
     finally:
         _Deferred.active = old
-        _Deferred.items = []
-        _Deferred.conv_items = []
-        _Deferred.streams = []
+        _Deferred.reset()
 
 
 def deferred_detach():
     """Take the queued weight-gradient products and the list of streams to join out of the current deferred_weight_grads() context
     (they are handed to a later context with deferred_attach): the early backward pass of a side branch must not make the main stream
     wait for that branch when its context closes."""
-    st = (_Deferred.items, _Deferred.conv_items, _Deferred.streams)
-    _Deferred.items, _Deferred.conv_items, _Deferred.streams = [], [], []
-    return st
+    return _Deferred.reset()
 
 
 def deferred_attach(st):
@@ -165,8 +202,7 @@ def deferred_attach(st):
     _Deferred.items = list(items) + _Deferred.items
     _Deferred.conv_items = list(conv_items) + _Deferred.conv_items
     for q in streams:
-        if all(q.cuda_stream != r.cuda_stream for r in _Deferred.streams):
-            _Deferred.streams.append(q)
+        _Deferred.note_stream(q)
 
 
 def grad_target(p):
@@ -190,14 +226,12 @@ _WG_FLUSH_AT = int(__import__('os').environ.get('PTTS_WG_FLUSH', '3'))     # > 0
 
 
 def _defer_wgrad(x2, dy2, gw, gb, K_in, N, M_rows, mode, scale, shift, mask_src, alpha):
-    cur = torch.cuda.current_stream()
-    if all(cur.cuda_stream != s.cuda_stream for s in _Deferred.streams):
-        _Deferred.streams.append(cur)
-    _Deferred.items.append((cur.cuda_stream, x2, dy2, mask_src, scale, shift, gw, gb, K_in, N, M_rows, mode, alpha))
+    sid = _Deferred.note_stream()
+    _Deferred.items.append((sid, x2, dy2, mask_src, scale, shift, gw, gb, K_in, N, M_rows, mode, alpha))
     if _WG_FLUSH_AT > 0:
-        mine = [it for it in _Deferred.items if it[0] == cur.cuda_stream]
+        mine = [it for it in _Deferred.items if it[0] == sid]
         if len(mine) >= _WG_FLUSH_AT:
-            _Deferred.items = [it for it in _Deferred.items if it[0] != cur.cuda_stream]
+            _Deferred.items = [it for it in _Deferred.items if it[0] != sid]
             _launch_wgrads(mine)
 
 
@@ -255,27 +289,32 @@ def _launch_wgrads(items):
 
 
 def flush_weight_grads():
-    items, conv_items = _Deferred.items, _Deferred.conv_items
-    if not items and not conv_items:
+    items, conv_items, streams = _Deferred.reset()
+    if not (items or conv_items or streams):
         return
     cur = torch.cuda.current_stream()
-    for s in _Deferred.streams:           # operands produced on the side streams of the backward pass
+    for s in streams:                     # operands and direct adds on the side streams of the backward pass
         if s.cuda_stream != cur.cuda_stream:
             cur.wait_stream(s)
     if items:
         _launch_wgrads(items)
     if conv_items:
-        descs = (_hip.Conv2dReduceDesc * len(conv_items))()
-        for d, (buf, off, nblocks, npart, nw, cout, gw, gb) in zip(descs, conv_items):
-            buf.record_stream(cur)
-            d.partials = buf.data_ptr() + off
-            d.nblocks, d.npart, d.nw, d.cout = nblocks, npart, nw, cout
-            d.dw = gw.data_ptr() if gw is not None else None
-            d.dbias = gb.data_ptr() if gb is not None else None
-        call('ptts_conv2d_reduce_grouped', ctypes.cast(descs, ctypes.c_void_p), len(conv_items), stream(), tag=(len(conv_items),))
-    _Deferred.items = []
-    _Deferred.conv_items = []
-    _Deferred.streams = []
+        _conv2d_reduce(conv_items, cur)
+
+
+def _conv2d_reduce(passes, record=None):
+    """ONE ptts_conv2d_reduce_grouped launch: the partial rows of every pass (buffer, byte offset, nblocks, npart, nw, cout, dw,
+    dbias) are added into its tensors dw [nw] / dbias [cout] (either may be None).  record: the stream that reads the buffers
+    when it is not the one that allocated them."""
+    descs = (_hip.Conv2dReduceDesc * len(passes))()
+    for d, (buf, off, nblocks, npart, nw, cout, dw, db) in zip(descs, passes):
+        if record is not None:
+            buf.record_stream(record)
+        d.partials = buf.data_ptr() + off
+        d.nblocks, d.npart, d.nw, d.cout = nblocks, npart, nw, cout
+        d.dw = dw.data_ptr() if dw is not None else None
+        d.dbias = db.data_ptr() if db is not None else None
+    call('ptts_conv2d_reduce_grouped', ctypes.cast(descs, ctypes.c_void_p), len(passes), stream(), tag=(len(passes),))
 
 
 _counter_cache = {}
@@ -496,6 +535,26 @@ def _conv2d_fwd_raw(x, w, b, scale, shift, mask_src, mode, alpha, dil_t, pad_mod
     return y
 
 
+def _conv2d_mfma_bwd(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_rows, planes):
+    """The matrix-core backward of a 4 -> 4 layer: backward data = forward through the transposed table with the layer input's
+    LeakyReLU mask in the store; weight gradient = per-workgroup partial sums -- ONE fused launch where both are wanted and the
+    shape allows.  Returns (dx, pass): the pass is (buffer, byte offset, nblocks, npart, nw, cout), its rows still to be
+    reduced (_conv2d_reduce) or queued (_Deferred.queue_conv); None where not wanted.  The gradient of a map is stored like the
+    map (bf16 storage: dx has x's type)."""
+    pad_t = _C2M.pad_t(dil_t, pad_mode)
+    dx = None
+    if want_dx and want_rows and mode == IN_LRELU and _C2MFused.ok(x, dil_t, pad_mode, planes):
+        dx, buf, nblocks, npart = _conv2d_mfma_bwd_fused(1, dy, x, None, w, alpha)      # dx + dW + dbias: one launch
+    else:
+        if want_dx:
+            assert mode != IN_MASKMUL, 'conv2d_bwd: dx is not defined for MASKMUL (weight-only sweep)'
+            dx = _conv2d_mfma_fwd(dy, w, _C2M.table(w, True, planes), None, None, None, None, x if mode == IN_LRELU else None,
+                                  IN_NONE, alpha, dil_t, 4 * dil_t - pad_t, planes, _is16(x))
+        if want_rows:
+            buf, nblocks, npart = _conv2d_mfma_wgrad(dy, x, mask_src, mode, alpha, dil_t, pad_t, planes)
+    return dx, ((buf, 4096, nblocks, npart, w.numel(), w.shape[3]) if want_rows else None)
+
+
 def _conv2d_bwd_raw(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode,
                     want_dx, want_dw, want_db, want_affine, planes=3):
     if planes == 1:
@@ -509,29 +568,13 @@ def _conv2d_bwd_raw(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mo
     assert mask_src is None or mask_src.shape == x.shape
     dev = x.device
     if (planes == 1 or _C2M.enabled) and _C2M.eligible(x, w, dil_t) and scale is None and not want_affine and 0.0 <= alpha <= 1.0:
-        # matrix-core kernels: backward data = forward through the transposed table with the layer input's LeakyReLU mask
-        # in the store; weight gradient = per-workgroup partial sums + the grouped reduction.  The gradient of a map is
-        # stored like the map (bf16 storage: dx has x's type)
-        pad_t = _C2M.pad_t(dil_t, pad_mode)
-        dx = dw = db = None
-        fused = want_dx and (want_dw or want_db) and mode == IN_LRELU and _C2MFused.ok(x, dil_t, pad_mode, planes)
-        if fused:
-            dx, buf, nblocks, npart = _conv2d_mfma_bwd_fused(1, dy, x, None, w, alpha)
-        elif want_dx:
-            assert mode != IN_MASKMUL, 'conv2d_bwd: dx is not defined for MASKMUL (weight-only sweep)'
-            dx = _conv2d_mfma_fwd(dy, w, _C2M.table(w, True, planes), None, None, None, None, x if mode == IN_LRELU else None,
-                                  IN_NONE, alpha, dil_t, 4 * dil_t - pad_t, planes, _is16(x))
-        if want_dw or want_db:
-            if not fused:
-                buf, nblocks, npart = _conv2d_mfma_wgrad(dy, x, mask_src, mode, alpha, dil_t, pad_t, planes)
+        # matrix-core kernels; the partial rows are reduced at once into fresh tensors
+        dw = db = None
+        dx, rows = _conv2d_mfma_bwd(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_dw or want_db, planes)
+        if rows is not None:
             dw = torch.zeros_like(w) if want_dw else None
             db = torch.zeros(Cout, dtype=torch.float32, device=dev) if want_db else None
-            desc = (_hip.Conv2dReduceDesc * 1)()
-            desc[0].partials = buf.data_ptr() + 4096
-            desc[0].nblocks, desc[0].npart, desc[0].nw, desc[0].cout = nblocks, npart, KT * KF * Cin * Cout, Cout
-            desc[0].dw = dw.data_ptr() if dw is not None else None
-            desc[0].dbias = db.data_ptr() if db is not None else None
-            call('ptts_conv2d_reduce_grouped', ctypes.cast(desc, ctypes.c_void_p), 1, stream(), tag=(1,))
+            _conv2d_reduce([rows + (dw, db)])
         return dx, dw, db, None, None
     if planes == 3 and scale is not None and mode == IN_LRELU and want_dx and mask_src is None and _C2M.enabled and _BNStats.enabled and \
             _C2M.eligible(x, w, dil_t) and 0.0 <= alpha <= 1.0 and _C2MFused.ok(x, dil_t, pad_mode, planes) and \
@@ -543,22 +586,13 @@ def _conv2d_bwd_raw(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mo
         dw = torch.zeros_like(w) if want_dw else None
         db = torch.zeros(Cout, dtype=torch.float32, device=dev) if want_db else None
         daff = torch.zeros(2 * Cin, dtype=torch.float32, device=dev) if want_affine else None
-        nd = int(want_dw or want_db) + int(want_affine)
-        if nd:
-            desc = (_hip.Conv2dReduceDesc * nd)()
-            i = 0
-            if want_dw or want_db:
-                desc[i].partials = buf.data_ptr() + 4096
-                desc[i].nblocks, desc[i].npart, desc[i].nw, desc[i].cout = nblocks, npart, nw, Cout
-                desc[i].dw = dw.data_ptr() if dw is not None else None
-                desc[i].dbias = db.data_ptr() if db is not None else None
-                i += 1
-            if want_affine:
-                desc[i].partials = buf.data_ptr() + 4096 + 4 * (nw + Cout)        # (the eight sums behind dW and dbias in every row)
-                desc[i].nblocks, desc[i].npart, desc[i].nw, desc[i].cout = nblocks, npart, Cin, Cin
-                desc[i].dw = daff.data_ptr()
-                desc[i].dbias = daff.data_ptr() + 4 * Cin
-            call('ptts_conv2d_reduce_grouped', ctypes.cast(desc, ctypes.c_void_p), nd, stream(), tag=(nd,))
+        passes = []
+        if want_dw or want_db:
+            passes.append((buf, 4096, nblocks, npart, nw, Cout, dw, db))
+        if want_affine:                 # (the eight sums behind dW and dbias in every row)
+            passes.append((buf, 4096 + 4 * (nw + Cout), nblocks, npart, Cin, Cin, daff[:Cin], daff[Cin:]))
+        if passes:
+            _conv2d_reduce(passes)
         return dx, dw, db, (daff[:Cin] if want_affine else None), (daff[Cin:] if want_affine else None)
     dx = torch.empty_like(x) if want_dx else None
     dw = torch.empty_like(w) if (want_dw or want_db) else None
@@ -581,19 +615,8 @@ def _conv2d_bwd_deferred(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_
     B, T, F, Cin = x.shape
     KT, KF, _, Cout = w.shape
     if (planes == 1 or _C2M.enabled) and _C2M.eligible(x, w, dil_t) and 0.0 <= alpha <= 1.0:
-        pad_t = _C2M.pad_t(dil_t, pad_mode)
-        dx = None
-        if want_dx and mode == IN_LRELU and _C2MFused.ok(x, dil_t, pad_mode, planes):
-            dx, buf, nblocks, npart = _conv2d_mfma_bwd_fused(1, dy, x, None, w, alpha)      # dx + dW + dbias: one launch
-        else:
-            if want_dx:
-                dx = _conv2d_mfma_fwd(dy, w, _C2M.table(w, True, planes), None, None, None, None, x if mode == IN_LRELU else None,
-                                      IN_NONE, alpha, dil_t, 4 * dil_t - pad_t, planes, _is16(x))
-            buf, nblocks, npart = _conv2d_mfma_wgrad(dy, x, mask_src, mode, alpha, dil_t, pad_t, planes)
-        cur = torch.cuda.current_stream()
-        if all(cur.cuda_stream != st.cuda_stream for st in _Deferred.streams):
-            _Deferred.streams.append(cur)
-        _Deferred.conv_items.append((buf, 4096, nblocks, npart, KT * KF * Cin * Cout, Cout, gw, gb))
+        dx, rows = _conv2d_mfma_bwd(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_dx, True, planes)
+        _Deferred.queue_conv(rows + (gw, gb))
         return dx
     nws = _hip.lib().ptts_conv2d_bwd_workspace_bytes(B, T, F, Cin, Cout, KT, KF, dil_t)
     if nws <= 16:
@@ -605,11 +628,8 @@ def _conv2d_bwd_deferred(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_
     call('ptts_conv2d_bwd_partials', ptr(dy), ptr(x), ptr(w), ptr(mask_src), ptr(dx), ptr(buf), buf.numel(),
          ctypes.byref(nblocks), B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha, stream(),
          tag=(B, T, F, Cin, Cout, mode, int(want_dx), 1, 0))
-    cur = torch.cuda.current_stream()
-    if all(cur.cuda_stream != s.cuda_stream for s in _Deferred.streams):
-        _Deferred.streams.append(cur)
     nw = KT * KF * Cin * Cout
-    _Deferred.conv_items.append((buf, 4096, nblocks.value, nw + Cout + 2 * Cin, nw, Cout, gw, gb))
+    _Deferred.queue_conv((buf, 4096, nblocks.value, nw + Cout + 2 * Cin, nw, Cout, gw, gb))
     return dx
 
 
@@ -800,8 +820,7 @@ class Conv2dFn(torch.autograd.Function):
         ctx.cfg = (mode, alpha, dil_t, pad_mode)
         ctx.planes = 1 if bf16 else 3
         # persistent gradient buffers of kernel / bias (deferred, grouped reduction of the backward's partial sums)
-        ctx.gw = grad_target(w) if _Deferred.active else None
-        ctx.gb = grad_target(b) if (_Deferred.active and b is not None) else None
+        ctx.gw, ctx.gb = _Deferred.targets(w, b)
         ctx.set_materialize_grads(False)
         return _conv2d_fwd_raw(x, w, b, scale, shift, None, mode, alpha, dil_t, pad_mode, ctx.planes, bf16 == 'out16')
 
@@ -846,7 +865,7 @@ class Conv2dFn(torch.autograd.Function):
 
 
 def _conv2d_can_defer(ctx, need_w, need_b):
-    return _Deferred.active and not _Flags.deterministic and (not need_w or ctx.gw is not None) and (not need_b or ctx.gb is not None)
+    return _Deferred.live() and (not need_w or ctx.gw is not None) and (not need_b or ctx.gb is not None)
 
 
 class Conv2dBwdDataFn(torch.autograd.Function):
@@ -876,26 +895,18 @@ class Conv2dBwdDataFn(torch.autograd.Function):
         if ctx.needs_input_grad[0] and ctx.needs_input_grad[2] and m2 == IN_MASKMUL and _C2M.enabled and _C2M.eligible(u, w, dil_t) and \
                 0.0 <= alpha <= 1.0 and _C2MFused.ok(u, dil_t, pad_mode, planes):
             # the masked forward and the weight gradient of the sweep read the same staged tile u . lrelu'(x): one launch
-            defer = _Deferred.active and not _Flags.deterministic and ctx.gw is not None
             cot_dy, buf, nblocks, npart = _conv2d_mfma_bwd_fused(2, u, dy, msk, w, alpha)
-            if defer:
-                cur = torch.cuda.current_stream()
-                if all(cur.cuda_stream != st.cuda_stream for st in _Deferred.streams):
-                    _Deferred.streams.append(cur)
-                _Deferred.conv_items.append((buf, 4096, nblocks, npart, w.numel(), w.shape[3], ctx.gw, None))
-                return cot_dy, None, None, None, None, None, None, None, None
-            cot_w = torch.zeros_like(w)
-            desc = (_hip.Conv2dReduceDesc * 1)()
-            desc[0].partials = buf.data_ptr() + 4096
-            desc[0].nblocks, desc[0].npart, desc[0].nw, desc[0].cout = nblocks, npart, w.numel(), w.shape[3]
-            desc[0].dw = cot_w.data_ptr()
-            desc[0].dbias = None
-            call('ptts_conv2d_reduce_grouped', ctypes.cast(desc, ctypes.c_void_p), 1, stream(), tag=(1,))
+            rows = (buf, 4096, nblocks, npart, w.numel(), w.shape[3])
+            if _Deferred.live() and ctx.gw is not None:
+                _Deferred.queue_conv(rows + (ctx.gw, None))
+            else:
+                cot_w = torch.zeros_like(w)
+                _conv2d_reduce([rows + (cot_w, None)])
             return cot_dy, None, cot_w, None, None, None, None, None, None
         if ctx.needs_input_grad[0]:
             cot_dy = _conv2d_fwd_raw(u, w, None, None, None, msk, m2, alpha, dil_t, pad_mode, planes, _is16(dy))
         if ctx.needs_input_grad[2]:
-            if _Deferred.active and not _Flags.deterministic and ctx.gw is not None and \
+            if _Deferred.live() and ctx.gw is not None and \
                     _conv2d_bwd_deferred(dy, u, w, msk, m2, alpha, dil_t, pad_mode, False, ctx.gw, None, planes) is not False:
                 return cot_dy, None, None, None, None, None, None, None, None
             _, cot_w, _, _, _ = _conv2d_bwd_raw(dy, u, w, None, None, msk, m2, alpha, dil_t, pad_mode,
@@ -955,8 +966,7 @@ class Conv2dPairFn(torch.autograd.Function):
         ctx.save_for_backward(x0, x1, w)
         ctx.has_b = b is not None
         ctx.cfg = (mode, alpha, dil_t, pad_mode)
-        ctx.gw = grad_target(w) if _Deferred.active else None
-        ctx.gb = grad_target(b) if (_Deferred.active and b is not None) else None
+        ctx.gw, ctx.gb = _Deferred.targets(w, b)
         ctx.set_materialize_grads(False)
         return y[:x0.shape[0]], y[x0.shape[0]:]
 
@@ -1036,33 +1046,18 @@ def _chain_x0(x0):
 
 
 def _chain_reduce(parts, nblocks, npart, ws, gws, gbs, want_b):
-    """Partial rows [L][nblocks][npart] -> the gradient buffers: queued for the grouped launch inside deferred_weight_grads()
-    (gws / gbs: the parameters' .grad views), else reduced now into fresh tensors, which are returned."""
+    """Partial rows [L][nblocks][npart] -> the gradient buffers: queued for the grouped launch while deferred_weight_grads()
+    is live (gws / gbs: the parameters' .grad views, as noted at forward time), else reduced now into fresh tensors, which
+    are returned."""
     L = len(ws)
-    deferred = gws is not None and all(g is not None for g in gws) and (not want_b or all(g is not None for g in gbs))
-    if deferred:
-        cur = torch.cuda.current_stream()
-        if all(cur.cuda_stream != st.cuda_stream for st in _Deferred.streams):
-            _Deferred.streams.append(cur)
-        for l, w in enumerate(ws):
-            _Deferred.conv_items.append((parts, l * nblocks * npart * 4, nblocks, npart, w.numel(), w.shape[3], gws[l], gbs[l] if want_b else None))
+    rows = [(parts, l * nblocks * npart * 4, nblocks, npart, w.numel(), w.shape[3]) for l, w in enumerate(ws)]
+    if _Deferred.live() and all(g is not None for g in gws) and (not want_b or all(g is not None for g in gbs)):
+        _Deferred.queue_conv(*[r + (gw, gb if want_b else None) for r, gw, gb in zip(rows, gws, gbs)])
         return None, None
     dws = [torch.zeros_like(w) for w in ws]
     dbs = [torch.zeros(w.shape[3], dtype=torch.float32, device=w.device) for w in ws] if want_b else [None] * L
-    descs = (_hip.Conv2dReduceDesc * L)()
-    for l, (d, w) in enumerate(zip(descs, ws)):
-        d.partials = parts.data_ptr() + l * nblocks * npart * 4
-        d.nblocks, d.npart, d.nw, d.cout = nblocks, npart, w.numel(), w.shape[3]
-        d.dw = dws[l].data_ptr()
-        d.dbias = dbs[l].data_ptr() if want_b else None
-    call('ptts_conv2d_reduce_grouped', ctypes.cast(descs, ctypes.c_void_p), L, stream(), tag=(L,))
+    _conv2d_reduce([r + (dw, db) for r, dw, db in zip(rows, dws, dbs)])
     return dws, dbs
-
-
-def _chain_defer_targets(ws, bs):
-    if not (_Deferred.active and not _Flags.deterministic):
-        return None, None
-    return [grad_target(w) for w in ws], [None if b is None else grad_target(b) for b in bs]
 
 
 class Conv2dChainFn(torch.autograd.Function):
@@ -1080,7 +1075,7 @@ class Conv2dChainFn(torch.autograd.Function):
         call('ptts_conv2d_chain_fwd', ptr(x0), x0.stride(1), ptr(tab), ptr(maps), ptr(a_last), B, T, F, L, alpha, stream(), tag=(B, T, F, L))
         ctx.save_for_backward(x0, maps, a_last, tab, *ws)
         ctx.alpha, ctx.L, ctx.has_b = alpha, L, [b is not None for b in bs]
-        ctx.gws, ctx.gbs = _chain_defer_targets(ws, bs)
+        ctx.gws, ctx.gbs = _Deferred.targets(*ws), _Deferred.targets(*bs)
         ctx.set_materialize_grads(False)
         return a_last
 
@@ -1116,10 +1111,7 @@ class Conv2dChainFn(torch.autograd.Function):
                      ptr(parts), parts.numel(), ctypes.byref(nblocks), ctypes.byref(npart), B, T, F, L, int(ws[0].shape[2]), alpha, stream(),
                      tag=(B, T, F, L))
                 want_b = any(ctx.has_b)
-                # the targets were noted at FORWARD time; queue only if a deferred_weight_grads() context is open NOW (a backward run
-                # after the forward's context closed would append to a list nobody flushes, and the gradients would be lost)
-                live = _Deferred.active and not _Flags.deterministic
-                dws, dbs = _chain_reduce(parts, nblocks.value, npart.value, ws, ctx.gws if live else None, ctx.gbs if live else None, want_b)
+                dws, dbs = _chain_reduce(parts, nblocks.value, npart.value, ws, ctx.gws, ctx.gbs, want_b)
                 if dws is not None:
                     for l in range(L):
                         grads[2 * l] = dws[l]
@@ -1164,8 +1156,7 @@ class Conv2dChainBwdDataFn(torch.autograd.Function):
         need_w = any(ctx.needs_input_grad[6 + l] for l in range(L))
         grads = [None] * L
         if need_w:
-            gws = ctx.gws if (_Deferred.active and not _Flags.deterministic) else None
-            dws, _ = _chain_reduce(parts, nblocks.value, npart.value, ws, gws, [None] * L, False)
+            dws, _ = _chain_reduce(parts, nblocks.value, npart.value, ws, ctx.gws, [None] * L, False)
             if dws is not None:
                 grads = dws
         return (out if ctx.needs_input_grad[0] else None, None, None, None, None, None) + tuple(grads)
@@ -1232,8 +1223,7 @@ class DenseFn(torch.autograd.Function):
         ctx.has_b = b is not None
         ctx.cfg = (mode, alpha)
         # persistent gradient buffers of the kernel / bias (for the deferred, grouped weight-gradient launch)
-        ctx.gw = grad_target(w) if _Deferred.active else None
-        ctx.gb = grad_target(b) if (_Deferred.active and b is not None) else None
+        ctx.gw, ctx.gb = _Deferred.targets(w, b)
         ctx.set_materialize_grads(False)
         return y
 
@@ -1270,7 +1260,7 @@ class DenseFn(torch.autograd.Function):
                 dx = dx2.view(x.shape)
             elif need_aff:
                 _, dscale, dshift = _dense_bwd_data(dy2, x2, w, mode, scale, shift, alpha, True)
-            if need_w and _Deferred.active and not _Flags.deterministic and ctx.gw is not None and N > 4 and (not need_b or ctx.gb is not None) \
+            if need_w and _Deferred.live() and ctx.gw is not None and N > 4 and (not need_b or ctx.gb is not None) \
                     and M >= 2048 and (scale is None or mode == IN_LRELU):
                 # queued for the grouped launch, which adds into the .grad buffers itself (no dw / db for autograd)
                 _defer_wgrad(x2, dy2, ctx.gw, ctx.gb if need_b else None, K, N, M, mode, scale, shift, None, alpha)
@@ -1317,7 +1307,7 @@ class DenseBwdDataFn(torch.autograd.Function):
             gemm_raw(u2, w, cot_dy, M, N, K, mode=m2, mask_src=msk, alpha=alpha)
             cot_dy = cot_dy.view(dy.shape)
         if ctx.needs_input_grad[2]:
-            if _Deferred.active and not _Flags.deterministic and ctx.gw is not None and N > 4 and M >= 2048:
+            if _Deferred.live() and ctx.gw is not None and N > 4 and M >= 2048:
                 _defer_wgrad(u2, dy.view(M, N), ctx.gw, None, K, N, M, m2, None, None, msk, alpha)
             else:
                 cot_w = torch.empty_like(w)
@@ -1339,8 +1329,7 @@ class DensePairFn(torch.autograd.Function):
         ctx.has_b = b is not None
         ctx.cfg = (mode, alpha)
         ctx.res_shape = None if res is None else tuple(res.shape)
-        ctx.gw = grad_target(w) if _Deferred.active else None
-        ctx.gb = grad_target(b) if (_Deferred.active and b is not None) else None
+        ctx.gw, ctx.gb = _Deferred.targets(w, b)
         ctx.set_materialize_grads(False)
         return y[:x0.shape[0]], y[x0.shape[0]:]
 
@@ -1976,7 +1965,7 @@ class BatchNormTrainFn(torch.autograd.Function):
         ctx.sync = _SyncBN.world
         # inside deferred_weight_grads(): dgamma / dbeta are added straight into the parameters' gradient buffers by the kernel that
         # computes them (two AccumulateGrad add launches per BatchNorm layer less: 30 per generator step)
-        ctx.gt = (grad_target(gamma), grad_target(beta)) if _Deferred.active else None
+        ctx.gt = _Deferred.targets(gamma, beta)
         part = getattr(z, '_ptts_bn_partials', None)
         if part is not None and ctx.sync <= 1 and part[2] == rows and part[0].shape[1] == 2 * C:
             # the convolution that produced z summed what it stored (_BNStats): only the finish is left
@@ -2015,14 +2004,12 @@ class BatchNormTrainFn(torch.autograd.Function):
         c0 = torch.empty(C, dtype=torch.float32, device=dev)
         c2 = torch.empty(C, dtype=torch.float32, device=dev)
         gt = ctx.gt
-        direct = gt is not None and gt[0] is not None and gt[1] is not None and _Deferred.active and not _Flags.deterministic and \
+        direct = gt[0] is not None and gt[1] is not None and _Deferred.live() and \
             ctx.needs_input_grad[1] and ctx.needs_input_grad[2]
         if direct:
             call('ptts_bn_bwd_coefs_acc', ptr(dscale), ptr(dshift), ptr(mean), ptr(rstd), ptr(gamma), rows, C,
                  ptr(gt[0]), ptr(gt[1]), ptr(c0), ptr(c2), stream())
-            cur = torch.cuda.current_stream()
-            if all(cur.cuda_stream != q.cuda_stream for q in _Deferred.streams):
-                _Deferred.streams.append(cur)             # flush_weight_grads() joins this stream before the optimiser reads the buffer
+            _Deferred.note_stream()             # flush_weight_grads() joins this stream before the optimiser reads the buffer
             dgamma = dbeta = None
         else:
             dgamma = torch.empty(C, dtype=torch.float32, device=dev)
@@ -2347,7 +2334,7 @@ class LSTMFn(torch.autograd.Function):
         # backward chain.  Handed to autograd instead, their AccumulateGrad nodes (made on the main stream) make the MAIN stream wait
         # for this side stream at the moment the engine reaches them -- with the chain enqueued first (Model.side_backward_first) that
         # is before the critic's backward pass, which then runs after the recurrence instead of under it.
-        ctx.gt = (grad_target(W), grad_target(U), grad_target(b)) if _Deferred.active else None
+        ctx.gt = _Deferred.targets(W, U, b)
         return h
 
     @staticmethod
@@ -2388,14 +2375,12 @@ class LSTMFn(torch.autograd.Function):
                 gemm_raw(hprev.view(M, ndir * H)[:, d * H:], dgates.view(M, ndir * G4)[:, d * G4:], dU[d],
                          H, G4, M, transA=1, lda=ndir * H, rows_per_seg=M, ldb=ndir * G4)
         gt = ctx.gt
-        if gt is not None and _Deferred.active and not _Flags.deterministic and \
+        if _Deferred.live() and \
                 all(t is not None or g is None for t, g in zip(gt, (dW, dU, db))):
             for t, g in zip(gt, (dW, dU, db)):
                 if g is not None:
                     t.add_(g.view(t.shape))
-            cur = torch.cuda.current_stream()
-            if all(cur.cuda_stream != q.cuda_stream for q in _Deferred.streams):
-                _Deferred.streams.append(cur)             # flush_weight_grads() joins this stream before the optimiser reads the buffer
+            _Deferred.note_stream()             # flush_weight_grads() joins this stream before the optimiser reads the buffer
             dW = dU = db = None
         return dx, dW, dU, db, None, None
 
