@@ -261,6 +261,9 @@ __global__ __launch_bounds__(256) void split3_dense_weight_strided_lds_kernel(Sp
 #define DNS_DEPTH 2        // register stages of the A operand in dense_bf16x6_kernel (1 = the single stage of rounds 2-3; measured 1 / 2 / 3 / 4 / 6:
                            // 25.6 / 25.0 / 25.6 / 26.5 / 29.8 us at 25 600 rows, 82.4 / 75.3 / 80.3 / 83.0 / 86.0 at 76 800: the loads are not what bounds it)
 #endif
+#ifndef DNS_SKIP_DEAD
+#define DNS_SKIP_DEAD 1    // a wave whose columns lie beyond N runs the staging-only loop (0: the MFMAs of the first tile as well, as before)
+#endif
 struct DenseArgs {
     const float* A; const float* mask_src; const float* in_scale; const float* in_shift;
     const u16* planes; const float* bias; const float* out_mask; float* C;
@@ -274,7 +277,11 @@ struct DenseArgs {
     const float* om_scale; const float* om_shift;     // (ptts_dense_bf16x6_bwd_affine) out_mask holds z of a BatchNorm-affine + LeakyReLU input: see the store
 };
 
-template <int MODE, bool AFFINE, int MT, int NPL>
+// XT: the launch has floor(N / 256) column blocks and the LAST one also owns the 1..16 columns beyond them, as a 17th column tile
+// (nt = 16 of the block: the planes are laid out for 256 more columns anyway).  Its MT row tiles are dealt over the waves -- wave w
+// multiplies row tile w -- so a wave's k-step grows by one accumulator, three weight-fragment loads, three ds_read_b128 and six
+// MFMAs (12 MT + 6: + 6 % at MT = 8) instead of a second column block of full price or a second pass over A by a thin kernel.
+template <int MODE, bool AFFINE, int MT, int NPL, bool XT = false>
 __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
     if (gridDim.z > 1) {
         g.A += (long long)blockIdx.z * g.bsA;
@@ -293,6 +300,7 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
     const int m0 = blockIdx.x * TBM, n0 = blockIdx.y * NBLK;
     const int KS = g.KS;
     const bool wave_live = n0 + 32 * wave < g.N;              // a wave whose columns lie beyond N only stages
+    const bool xt_wave = XT && blockIdx.y == gridDim.y - 1 && wave < MT;      // this wave multiplies row tile `wave` of the extra tile
 
     // ---- this lane's staging slots: quad q = tid + 512 j -> row q >> 3, k-quad q & 7 (the same for every j).  No branches
     // in the k-loop: rows beyond the tile or M read row 0 and are zeroed by a select, and so are the quads beyond K.
@@ -364,6 +372,12 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
 #pragma unroll
             for (int p = 0; p < NPL; ++p) wf[j][p] = *reinterpret_cast<const bf16x8*>(wp[j] + p * ps + (size_t)s * 512);
     };
+    // ... and of the extra tile.  No branch in the k-loop: a wave without a share of it loads the block's first tile and drops it.
+    const u16* wpx = g.planes + (((size_t)((n0 >> 4) + (xt_wave ? NBLK / 16 : 0)) * KS) * 64 + lane) * 8;
+    auto load_wx = [&](int s, bf16x8 (&wf)[NPL]) {
+#pragma unroll
+        for (int p = 0; p < NPL; ++p) wf[p] = *reinterpret_cast<const bf16x8*>(wpx + p * ps + (size_t)s * 512);
+    };
 
     f32x4 acc[MT][2];
 #pragma unroll
@@ -384,15 +398,31 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
         }
     };
 
+    // extra tile: activation fragments of row tile `wave` (read once more, in the k-step's main block: reusing those of mfma_rows would
+    // put a wave-dependent branch into every row tile of it); the six products in the order of the main tiles
+    f32x4 accx = {0.f, 0.f, 0.f, 0.f};
+    const int xoff = boff + (wave < MT ? wave : MT - 1) * 16 * BK;
+    auto read_x = [&](const u16* as, bf16x8 (&bf)[NPL]) {
+#pragma unroll
+        for (int p = 0; p < NPL; ++p) bf[p] = *reinterpret_cast<const bf16x8*>(as + p * PL + xoff);
+    };
+    auto mfma_x = [&](const bf16x8 (&wf)[NPL], const bf16x8 (&bf)[NPL]) {
+#define DNS_MM(PA, PW) accx = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[PW < NPL ? PW : 0], bf[PA < NPL ? PA : 0], accx, 0, 0, 0);
+        DNS_PRODUCTS_NPL(NPL, DNS_MM);
+#undef DNS_MM
+    };
+
     // One basic block per k-step: the staging of step s+1 (transform, split, LDS stores into the other buffer) and the loads
-    // of step s+2 sit between the MFMAs of step s.  (A wave whose columns lie beyond N runs the same code on the first
-    // tile's planes: the MFMAs are cheap next to a divergent barrier structure, and nothing of it is stored.)
+    // of step s+2 sit between the MFMAs of step s.  (A wave whose columns lie beyond N stages its share and meets the same
+    // barriers in a loop of its own, run_dead, without weight loads and MFMAs: the SIMD's matrix time is the sum of what its two waves
+    // issue, so those MFMAs were paid for by the live wave beside it.)
     // DEPTH register stages of A: the loads of k-step s + DEPTH are issued while step s is multiplied.  The kernel's time is linear in M
     // from 25 600 rows up (tools/dense_ramp_probe.py: 1.0 us per 1000 rows, 130 TF) and hardly moves with DEPTH: what bounds a k-step is
     // the matrix pipe -- TWO waves per SIMD x 84 six-product MFMAs x 16 cycles = 2 700 cycles at the ~1.8 GHz it holds under that load.
     constexpr int DEPTH = DNS_DEPTH;
     Stage sg[DEPTH];
     bf16x8 wc[2][NPL], wn[2][NPL];
+    bf16x8 wx[XT ? NPL : 1];                                  // (no second stage: loaded at the head of its k-step, used at its end)
 #pragma unroll
     for (int j = 0; j < DEPTH; ++j) load_a(j, sg[j]);
     load_w(0, wc);
@@ -405,14 +435,25 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
     auto step = [&](int s, int cut, Stage& nx) {             // nx: the stage that holds step s + 1 (slot (s + 1) % DEPTH), refilled with step s + 1 + DEPTH
         const u16* as = As[s & 1];
         load_w(s + 1 < KS ? s + 1 : s, wn);
+        if constexpr (XT) load_wx(s, wx);
         mfma_rows(as, wc, 0, cut);
         commit(nx, As[(s + 1) & 1]);                          // the other buffer: every wave left it at the last barrier
         load_a(s + 1 + DEPTH, nx);
+        bf16x8 bx[XT ? NPL : 1];
+        if constexpr (XT) read_x(as, bx);
         mfma_rows(as, wc, cut, MT);
+        if constexpr (XT) {
+            if (xt_wave) mfma_x(wx, bx);                      // (wave-uniform, in front of the barrier and not around it)
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int p = 0; p < NPL; ++p) wc[j][p] = wn[j][p];
+        __syncthreads();
+    };
+    auto step_dead = [&](int s, Stage& nx) {                  // the staging and the barrier of `step`, nothing else
+        commit(nx, As[(s + 1) & 1]);
+        load_a(s + 1 + DEPTH, nx);
         __syncthreads();
     };
     auto run = [&](int cut) {
@@ -425,7 +466,46 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
         for (int j = 0; j < DEPTH; ++j)
             if (s + j < KS) step(s + j, cut, sg[(j + 1) % DEPTH]);
     };
-    if (wave < 4) run(2); else run(MT - 2);
+    auto run_dead = [&]() {
+        int s = 0;
+        for (; s + DEPTH <= KS; s += DEPTH) {
+#pragma unroll
+            for (int j = 0; j < DEPTH; ++j) step_dead(s + j, sg[(j + 1) % DEPTH]);
+        }
+#pragma unroll
+        for (int j = 0; j < DEPTH; ++j)
+            if (s + j < KS) step_dead(s + j, sg[(j + 1) % DEPTH]);
+    };
+    if (DNS_SKIP_DEAD && !XT && !wave_live) run_dead();       // (XT: every column block is full)
+    else if (wave < 4) run(2); else run(MT - 2);
+    if constexpr (XT) {
+        // ---- store of the extra tile: lane (li, lg) of accx holds row m0 + 16 wave + li, columns n0 + 256 + 4 lg .. + 3
+        const int m = m0 + 16 * wave + li, n = n0 + NBLK + 4 * lg;
+        if (xt_wave && m < g.M && n < g.N) {
+            const long long off = (long long)m * g.ldc + n;
+            int mr = m; while (g.res && mr >= g.res_rows) mr -= g.res_rows;
+            if (g.vec_out) {                                  // N % 4 == 0: the four columns are inside or outside together
+                f32x4 v = accx;
+                if (g.bias) v += *reinterpret_cast<const f32x4*>(g.bias + n);
+                if (g.out_mask) {
+                    const f32x4 mk = *reinterpret_cast<const f32x4*>(g.out_mask + off);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = v[e] * (mk[e] > 0.f ? 1.f : g.out_alpha);
+                }
+                if (g.res) v += *reinterpret_cast<const f32x4*>(g.res + (long long)mr * g.ldr + n);
+                *reinterpret_cast<f32x4*>(g.C + off) = v;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (n + e >= g.N) continue;
+                    float v = accx[e] + (g.bias ? g.bias[n + e] : 0.f);
+                    if (g.out_mask) v *= g.out_mask[off + e] > 0.f ? 1.f : g.out_alpha;
+                    if (g.res) v += g.res[(long long)mr * g.ldr + n + e];
+                    g.C[off + e] = v;
+                }
+            }
+        }
+    }
     if (!wave_live) return;
     // ---- store: lane (li, lg) of acc[i][j] holds row m0 + 16 i + li, columns n0 + 32 wave + 16 j + 4 lg .. + 3
     const bool interior = m0 + TBM <= g.M;                    // no row guards: the mask / old-value loads go out together
@@ -532,6 +612,16 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
     }
 }
 
+// The extra-tile form exists for MT <= 7: at MT = 8 and three planes its registers no longer fit (the compiler answers with a kernel
+// that keeps its stages in scratch memory).
+template <int MODE, bool AFFINE, int MT, int NPL>
+static void dense_launch_kernel(bool xt, dim3 grid, hipStream_t st, const DenseArgs& g) {
+    if constexpr (MT < 8) {
+        if (xt) { hipLaunchKernelGGL((dense_bf16x6_kernel<MODE, AFFINE, MT, NPL, true>), grid, dim3(THREADS), 0, st, g); return; }
+    }
+    hipLaunchKernelGGL((dense_bf16x6_kernel<MODE, AFFINE, MT, NPL>), grid, dim3(THREADS), 0, st, g);
+}
+
 // rows per workgroup (multiple of 16, 64..128) that best fills 256 CUs in whole rounds
 static int pick_mt(int M, int col_blocks) {
     static int forced = -1;
@@ -569,27 +659,38 @@ __device__ __forceinline__ bf16x8 cat8(bf16x4 a, bf16x4 b) { return __builtin_sh
 
 struct WgradArgs {
     const float* A; const float* dY; const float* mask_src; const float* in_scale; const float* in_shift;
-    float* partials;                         // [tile][split][WPART]: the workgroups' partial tiles (+ 128 bias sums)
+    float* partials;                         // [tile][split][part]: the workgroups' partial tiles (+ 128 bias sums, + the remainder tile)
     int Kin, N, M;
     long long lda, ldb;
     float alpha;
     int tiles_n, steps_total, split;         // 128-column tiles along N; 32-row steps of M; workgroups per tile
+    int tiles_k, part;                       // 128-row tiles along Kin (wgrad_tiles_k); floats of a partial row (wgrad_part)
 };
 
 constexpr int WT = 128;                       // tile edge (columns of A x columns of dY)
 constexpr int WROW = WT;                      // elements per staged row of a plane
 constexpr int WPL = 32 * WROW;                // elements of one plane of one operand
 constexpr int WPART = WT * WT + WT;           // floats of a workgroup's partial row: the tile and the bias sums
+// Remainder tile: 1..16 rows of dW beyond a multiple of 128 (the critic's 260-wide layer) are no tile row of their own -- 4 live rows
+// of 128 at the price of a whole tile, and half as many frames' worth of workgroups for every tile -- but a 16-row tile more for the
+// workgroups of the LAST full tile row: rows 128 tiles_k .. + 15 against their 128 dY columns, eight MFMA tiles, one per wave.
+constexpr int WXR = 16;                       // rows of the remainder tile
+constexpr int WXPL = 32 * WXR + 4 * 64;       // elements of a plane of its staged A columns: 32 rows of 16, 64 more per 8 rows (banks)
+constexpr int WPARTX = WXR * WT;              // floats it adds to every partial row of the product
+__host__ __device__ inline bool wgrad_has_rem(int Kin) { return Kin > WT && Kin % WT >= 1 && Kin % WT <= WXR; }
+__host__ __device__ inline int wgrad_tiles_k(int Kin) { return wgrad_has_rem(Kin) ? Kin / WT : (Kin + WT - 1) / WT; }
+__host__ __device__ inline int wgrad_part(int Kin) { return WPART + (wgrad_has_rem(Kin) ? WPARTX : 0); }
 
-template <int MODE, bool AFFINE, int NPL>
+template <int MODE, bool AFFINE, int NPL, bool XR = false>
 __global__ __launch_bounds__(THREADS) void dense_wgrad_bf16x6_kernel(WgradArgs g) {
     constexpr bool MASK = MODE == PTTS_IN_MASKMUL;
-    extern __shared__ __attribute__((aligned(16))) u16 lds_w[];          // [buffer][A planes 0..2 | dY planes 0..2]: 96 KB
+    extern __shared__ __attribute__((aligned(16))) u16 lds_w[];          // [buffer][A planes 0..2 | dY planes 0..2]: 96 KB; XR: + [buffer][3 WXPL]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
     const int tile = blockIdx.y, tk = tile / g.tiles_n, tn = tile - tk * g.tiles_n;
     const int k0 = tk * WT, n0 = tn * WT;
+    const bool xr_wg = XR && tk == g.tiles_k - 1;                        // this workgroup also owns the remainder tile
     // this workgroup's share of the 32-row steps
     const int per = (g.steps_total + g.split - 1) / g.split;
     const int s_begin = blockIdx.x * per, s_end = min(g.steps_total, s_begin + per);
@@ -609,8 +710,25 @@ __global__ __launch_bounds__(THREADS) void dense_wgrad_bf16x6_kernel(WgradArgs g
     }
     f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
     if (AFFINE && a_ok) { sc = *reinterpret_cast<const f32x4*>(g.in_scale + k0 + 4 * c4); sh = *reinterpret_cast<const f32x4*>(g.in_shift + k0 + 4 * c4); }
-    struct Stage { f32x4 va[2], vm[MASK ? 2 : 1], vd[2]; bool ok[2]; };
+    // remainder tile: the 16 columns of A behind the last full tile, 32 rows x 4 quads = the lanes of waves 0 and 1, one quad each
+    const bool xr_stage = xr_wg && wave < 2;
+    const int xrow = tid >> 2, xkq = g.tiles_k * WT + 4 * (tid & 3);
+    const bool x_ok = xr_stage && xkq < g.Kin;
+    const float* pax = g.A + (x_ok ? xkq : 0);
+    const float* pmx = MASK ? g.mask_src + (x_ok ? xkq : 0) : nullptr;
+    auto xrow_off = [](int row) { return row * WXR + 64 * (row >> 3); };
+    const int xdst = xrow_off(xrow & 31) + 4 * (tid & 3);
+    f32x4 scx = {1.f, 1.f, 1.f, 1.f}, shx = {0.f, 0.f, 0.f, 0.f};
+    if (AFFINE && x_ok) { scx = *reinterpret_cast<const f32x4*>(g.in_scale + xkq); shx = *reinterpret_cast<const f32x4*>(g.in_shift + xkq); }
+    struct Stage { f32x4 va[2], vm[MASK ? 2 : 1], vd[2]; bool ok[2]; f32x4 vx, vmx; bool okx; };
     auto load = [&](int s, Stage& sg) {
+        if (XR && xr_stage) {                                            // (wave-uniform)
+            const int m = (s_begin + s) * 32 + xrow;
+            sg.okx = s < nsteps && m < g.M && x_ok;
+            const long long r = sg.okx ? m : 0;
+            sg.vx = *reinterpret_cast<const f32x4*>(pax + r * g.lda);
+            if (MASK) sg.vmx = *reinterpret_cast<const f32x4*>(pmx + r * g.lda);
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int m = (s_begin + s) * 32 + ((tid + j * THREADS) >> 5);
@@ -622,8 +740,34 @@ __global__ __launch_bounds__(THREADS) void dense_wgrad_bf16x6_kernel(WgradArgs g
         }
     };
     f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
-    auto commit = [&](const Stage& sg, u16* ls) {
+    auto commit = [&](const Stage& sg, u16* ls, u16* lsx) {
         const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+        if (XR && xr_stage) {                                            // the transform and the split of the main tile's columns
+            f32x4 a = sg.vx;
+            if (MODE == PTTS_IN_LRELU) {
+                if (AFFINE) a = a * scx + shx;
+                if (!sg.okx) a = z4;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a[e] = max_fast(a[e], g.alpha * a[e]);
+            } else if (MASK) {
+                if (!sg.okx) a = z4;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a[e] = a[e] * (sg.vmx[e] > 0.f ? 1.f : g.alpha);
+            } else {
+                if (!sg.okx) a = z4;
+            }
+            u16* q = lsx + xdst;
+            if (NPL == 3) {
+                unsigned a1, a2, a3, b1, b2, b3;
+                split3_pair(a[0], a[1], a1, a2, a3);
+                split3_pair(a[2], a[3], b1, b2, b3);
+                *reinterpret_cast<u32x2*>(q) = (u32x2){a1, b1};
+                *reinterpret_cast<u32x2*>(q + WXPL) = (u32x2){a2, b2};
+                *reinterpret_cast<u32x2*>(q + 2 * WXPL) = (u32x2){a3, b3};
+            } else {
+                *reinterpret_cast<u32x2*>(q) = (u32x2){pk_bf16(a[0], a[1]), pk_bf16(a[2], a[3])};
+            }
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             f32x4 a = sg.va[j], d = sg.vd[j];
@@ -681,6 +825,26 @@ __global__ __launch_bounds__(THREADS) void dense_wgrad_bf16x6_kernel(WgradArgs g
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // remainder tile of this wave: its 16 rows x dY-column tile `wave` (one of the four above, read once more: no wave-dependent
+    // index into the fragment registers); the same six products in the same order
+    f32x4 accx = {0.f, 0.f, 0.f, 0.f};
+    int axo[2], bxo[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        axo[h] = xrow_off(8 * lg + (li >> 2) + 4 * h) + (li & 3) * 4;
+        bxo[h] = 3 * WPL + tr_off(wave, h);
+    }
+    auto mfma_rem = [&](const u16* ls, const u16* lsx) {
+        bf16x8 af[NPL], bf[NPL];
+#pragma unroll
+        for (int p = 0; p < NPL; ++p) {
+            af[p] = cat8(tr_read(lsx + p * WXPL + axo[0]), tr_read(lsx + p * WXPL + axo[1]));
+            bf[p] = cat8(tr_read(ls + p * WPL + bxo[0]), tr_read(ls + p * WPL + bxo[1]));
+        }
+#define DNS_MM(PA, PW) accx = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[PA < NPL ? PA : 0], bf[PW < NPL ? PW : 0], accx, 0, 0, 0);
+        DNS_PRODUCTS_NPL(NPL, DNS_MM);
+#undef DNS_MM
+    };
     // one k-step of MFMAs on buffer BUF (a compile-time index: every LDS address is a lane base + an immediate); the dY
     // fragments are read once and serve both A-column tiles; `stage` (the next step's transform / split / LDS stores and the
     // loads of the step after) runs between the two tile rows in waves 0-3 and in front of them in waves 4-7
@@ -701,20 +865,23 @@ __global__ __launch_bounds__(THREADS) void dense_wgrad_bf16x6_kernel(WgradArgs g
             for (int p = 0; p < NPL; ++p) bf[j][p] = cat8(tr_read(ls + p * WPL + bo[j][0]), tr_read(ls + p * WPL + bo[j][1]));
     };
 
-    Stage sg;
-    load(0, sg);
-    commit(sg, lds_w);
-    load(1, sg);
-    __syncthreads();
     u16* const buf0 = lds_w;
     u16* const buf1 = lds_w + 6 * WPL;
-    auto step = [&](int s, const u16* cur, u16* nxt, bool stage_first) {
+    u16* const xbuf0 = lds_w + 12 * WPL;
+    u16* const xbuf1 = xbuf0 + 3 * WXPL;
+    Stage sg;
+    load(0, sg);
+    commit(sg, buf0, xbuf0);
+    load(1, sg);
+    __syncthreads();
+    auto step = [&](int s, const u16* cur, u16* nxt, const u16* curx, u16* nxtx, bool stage_first) {
         bf16x8 bf[4][NPL];
-        if (stage_first) { commit(sg, nxt); load(s + 2, sg); }       // (rows of a step beyond the share are staged as zeros)
+        if (stage_first) { commit(sg, nxt, nxtx); load(s + 2, sg); }       // (rows of a step beyond the share are staged as zeros)
         read_bf(cur, bf);
         mfma_tile_row(cur, 0, bf);
-        if (!stage_first) { commit(sg, nxt); load(s + 2, sg); }
+        if (!stage_first) { commit(sg, nxt, nxtx); load(s + 2, sg); }
         mfma_tile_row(cur, 1, bf);
+        if (XR && xr_wg) mfma_rem(cur, curx);                        // (workgroup-uniform, in front of the barrier)
         __syncthreads();
     };
     // The two waves of a SIMD leave every barrier together: waves 0-3 run half of their MFMAs before the staging of the next
@@ -722,17 +889,23 @@ __global__ __launch_bounds__(THREADS) void dense_wgrad_bf16x6_kernel(WgradArgs g
     // buffers are compile-time.
     if (wave < 4) {
         int s = 0;
-        for (; s + 1 < nsteps; s += 2) { step(s, buf0, buf1, false); step(s + 1, buf1, buf0, false); }
-        if (s < nsteps) step(s, buf0, buf1, false);
+        for (; s + 1 < nsteps; s += 2) { step(s, buf0, buf1, xbuf0, xbuf1, false); step(s + 1, buf1, buf0, xbuf1, xbuf0, false); }
+        if (s < nsteps) step(s, buf0, buf1, xbuf0, xbuf1, false);
     } else {
         int s = 0;
-        for (; s + 1 < nsteps; s += 2) { step(s, buf0, buf1, true); step(s + 1, buf1, buf0, true); }
-        if (s < nsteps) step(s, buf0, buf1, true);
+        for (; s + 1 < nsteps; s += 2) { step(s, buf0, buf1, xbuf0, xbuf1, true); step(s + 1, buf1, buf0, xbuf1, xbuf0, true); }
+        if (s < nsteps) step(s, buf0, buf1, xbuf0, xbuf1, true);
     }
 
-    // ---- the workgroup's partial tile, row (tile, split index) of the partials: [128 k][128 n] | 128 column sums of dY.
+    // ---- the workgroup's partial tile, row (tile, split index) of the partials: [128 k][128 n] | 128 column sums of dY | with a
+    // remainder in the product, [16 k][128 n] of it (written by the last tile row's workgroups, never read of the others).
     // lane (li, lg) of acc[i][j] holds rows k = 32 (wave & 3) + 16 i + 4 lg + r, column 64 (wave >> 2) + 16 j + li
-    float* out = g.partials + ((size_t)tile * g.split + blockIdx.x) * WPART;
+    float* out = g.partials + ((size_t)tile * g.split + blockIdx.x) * g.part;
+    if (XR && xr_wg) {
+        // lane (li, lg) of accx holds rows 128 tiles_k + 4 lg + r, column 16 wave + li of the tile
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[WPART + (4 * lg + r) * WT + 16 * wave + li] = accx[r];
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -771,33 +944,40 @@ struct DwReduceArgs {
     int split[DR_MAX], tiles_n[DR_MAX], Kin[DR_MAX], N[DR_MAX];
     long long ldc[DR_MAX];
 };
-constexpr int DR_BPT = (WPART + 255) / 256;       // blocks per tile (the last one holds the bias sums)
+// blocks per tile: a block per 256 floats of a partial row (the tile, the bias sums, with a remainder in the product its 16 rows)
+__host__ __device__ inline int dr_bpt(int Kin) { return (wgrad_part(Kin) + 255) / 256; }
 __global__ __launch_bounds__(256) void dense_wgrad_reduce_kernel(DwReduceArgs a) {
     int gi = 0;
     while ((int)blockIdx.x >= a.blk_begin[gi + 1]) ++gi;
     const int b = blockIdx.x - a.blk_begin[gi];
-    const int tile = b / DR_BPT, e = (b - tile * DR_BPT) * 256 + threadIdx.x;
-    if (e >= WPART) return;
+    const int PART = wgrad_part(a.Kin[gi]), BPT = dr_bpt(a.Kin[gi]);
+    const int tile = b / BPT, e = (b - tile * BPT) * 256 + threadIdx.x;
+    if (e >= PART) return;
+    const int tk = tile / a.tiles_n[gi], tn = tile - tk * a.tiles_n[gi];
+    const int tiles_k = wgrad_tiles_k(a.Kin[gi]);
+    if (e >= WPART && tk != tiles_k - 1) return;             // the remainder tile belongs to the last tile row
     const int S = a.split[gi];
-    const float* p = a.partials[gi] + (size_t)tile * S * WPART + e;
+    const float* p = a.partials[gi] + (size_t)tile * S * PART + e;
     // eight rows in flight per thread (a fixed order still: the same sums in every run): the plain loop waited for every load in turn
     float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f, v4 = 0.f, v5 = 0.f, v6 = 0.f, v7 = 0.f;
     int s = 0;
     for (; s + 8 <= S; s += 8) {
-        const float* q = p + (size_t)s * WPART;
-        const float t0 = q[0], t1 = q[(size_t)WPART], t2 = q[(size_t)2 * WPART], t3 = q[(size_t)3 * WPART];
-        const float t4 = q[(size_t)4 * WPART], t5 = q[(size_t)5 * WPART], t6 = q[(size_t)6 * WPART], t7 = q[(size_t)7 * WPART];
+        const float* q = p + (size_t)s * PART;
+        const float t0 = q[0], t1 = q[(size_t)PART], t2 = q[(size_t)2 * PART], t3 = q[(size_t)3 * PART];
+        const float t4 = q[(size_t)4 * PART], t5 = q[(size_t)5 * PART], t6 = q[(size_t)6 * PART], t7 = q[(size_t)7 * PART];
         v0 += t0; v1 += t1; v2 += t2; v3 += t3; v4 += t4; v5 += t5; v6 += t6; v7 += t7;
     }
-    for (; s < S; ++s) v0 += p[(size_t)s * WPART];
+    for (; s < S; ++s) v0 += p[(size_t)s * PART];
     const float v = ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7));
-    const int tk = tile / a.tiles_n[gi], tn = tile - tk * a.tiles_n[gi];
     if (e < WT * WT) {
         const int k = tk * WT + (e >> 7), n = tn * WT + (e & (WT - 1));
         if (k < a.Kin[gi] && n < a.N[gi]) atomicAdd(a.C[gi] + (long long)k * a.ldc[gi] + n, v);
-    } else if (tk == 0 && a.colsum[gi]) {
+    } else if (e < WPART) {
         const int n = tn * WT + (e - WT * WT);
-        if (n < a.N[gi]) atomicAdd(a.colsum[gi] + n, v);
+        if (tk == 0 && a.colsum[gi] && n < a.N[gi]) atomicAdd(a.colsum[gi] + n, v);
+    } else {
+        const int k = tiles_k * WT + ((e - WPART) >> 7), n = tn * WT + ((e - WPART) & (WT - 1));
+        if (k < a.Kin[gi] && n < a.N[gi]) atomicAdd(a.C[gi] + (long long)k * a.ldc[gi] + n, v);
     }
 }
 
@@ -896,24 +1076,23 @@ extern "C" int ptts_dense_bf16x6_supported(int M, int N, int K, long long lda, l
 
 // C[M,N] (+)= T(A)[M,K] . B (+ bias), then C *= (out_mask > 0 ? 1 : alpha) -- the contract of ptts_gemm with transA = 0 and
 // B given as the planes of ptts_split3_dense_weight.  in_mode / in_scale / in_shift / mask_src / alpha as in ptts_gemm.
-extern "C" int ptts_dense_bf16x6_res(const float* A, const void* planes, const float* bias, float* C, int M, int N, int K,
-                                     long long lda, long long ldc, int in_mode, const float* in_scale, const float* in_shift,
-                                     const float* mask_src, float alpha, const float* res, int res_rows, long long ldr,
-                                     const float* out_mask, void* stream);
+// extra_tile: 1..16 columns beyond a multiple of 256 run as a 17th column tile of the last column block (dense_bf16x6_kernel<.., XT>).
+// Only the plain entry point asks for it; the others keep their whole column blocks.
+static int dense_launch(const float* A, const void* planes, const float* bias, float* C, int M, int N, int K,
+                        long long lda, long long ldc, int in_mode, const float* in_scale, const float* in_shift,
+                        const float* mask_src, float alpha, const float* res, int res_rows, long long ldr,
+                        const float* out_mask, double* stats, int stats_capacity_rows, int* stats_rows_out, void* stream,
+                        bool extra_tile = false);
 extern "C" int ptts_dense_bf16x6(const float* A, const void* planes, const float* bias, float* C, int M, int N, int K,
                                  long long lda, long long ldc, int in_mode, const float* in_scale, const float* in_shift,
                                  const float* mask_src, float alpha, int accumulate, const float* out_mask, void* stream) {
-    return ptts_dense_bf16x6_res(A, planes, bias, C, M, N, K, lda, ldc, in_mode, in_scale, in_shift, mask_src, alpha,
-                                 accumulate ? C : nullptr, M, ldc, out_mask, stream);
+    return dense_launch(A, planes, bias, C, M, N, K, lda, ldc, in_mode, in_scale, in_shift, mask_src, alpha,
+                        accumulate ? C : nullptr, M, ldc, out_mask, nullptr, 0, nullptr, stream, true);
 }
 
 // ... + res[m % res_rows][n] (row stride ldr) in the store: the product of a concat part that several stacked evaluations share (the
 // critic's context branch, computed once at B rows) joins each of the k B-row blocks of the stacked product without an add pass of its
 // own.  res == C, res_rows >= M is the plain accumulate of ptts_dense_bf16x6.
-static int dense_launch(const float* A, const void* planes, const float* bias, float* C, int M, int N, int K,
-                        long long lda, long long ldc, int in_mode, const float* in_scale, const float* in_shift,
-                        const float* mask_src, float alpha, const float* res, int res_rows, long long ldr,
-                        const float* out_mask, double* stats, int stats_capacity_rows, int* stats_rows_out, void* stream);
 static thread_local const float* g_om_scale = nullptr;        // (set around dense_launch by ptts_dense_bf16x6_bwd_affine)
 static thread_local const float* g_om_shift = nullptr;
 
@@ -960,7 +1139,8 @@ extern "C" int ptts_dense_bf16x6_stats_rows(int M, int N) {
 static int dense_launch(const float* A, const void* planes, const float* bias, float* C, int M, int N, int K,
                         long long lda, long long ldc, int in_mode, const float* in_scale, const float* in_shift,
                         const float* mask_src, float alpha, const float* res, int res_rows, long long ldr,
-                        const float* out_mask, double* stats, int stats_capacity_rows, int* stats_rows_out, void* stream) {
+                        const float* out_mask, double* stats, int stats_capacity_rows, int* stats_rows_out, void* stream,
+                        bool extra_tile) {
     const int accumulate = res != nullptr;
     PTTS_REQUIRE(!res || (res_rows > 0 && ldr >= N && M <= 8LL * res_rows), "dense_bf16x6: bad residual (rows %d, ldr %lld)", res_rows, ldr);
     PTTS_REQUIRE(A && planes && C, "dense_bf16x6: null matrix");
@@ -983,8 +1163,10 @@ static int dense_launch(const float* A, const void* planes, const float* bias, f
     g.lda = lda; g.ldc = ldc; g.alpha = alpha; g.out_alpha = alpha; g.accumulate = accumulate; g.has_affine = in_scale != nullptr; g.vec_out = vec_out;
     g.res = res; g.res_rows = res ? res_rows : 1; g.ldr = ldr;
     g.bsA = g.bsP = g.bsC = 0;
-    const int cb = (N + NBLK - 1) / NBLK;
-    const int mt = pick_mt(M, cb);
+    const bool xt = extra_tile && !stats && !g_om_scale && N > NBLK && N % NBLK >= 1 && N % NBLK <= 16;
+    const int cb = xt ? N / NBLK : (N + NBLK - 1) / NBLK;
+    int mt = pick_mt(M, cb);
+    if (xt && mt == 8) mt = 7;                                // (dense_launch_kernel)
     const dim3 grid((unsigned)((M + 16 * mt - 1) / (16 * mt)), (unsigned)cb);
     g.stats = stats;
     g.om_scale = g_om_scale; g.om_shift = g_om_shift;
@@ -995,8 +1177,8 @@ static int dense_launch(const float* A, const void* planes, const float* bias, f
     }
     hipStream_t st = (hipStream_t)stream;
     const bool one = ptts::bf16_products();
-#define DNS_L(MODE, AFF, MT) do { if (one) hipLaunchKernelGGL((dense_bf16x6_kernel<MODE, AFF, MT, 1>), grid, dim3(THREADS), 0, st, g); \
-                                  else hipLaunchKernelGGL((dense_bf16x6_kernel<MODE, AFF, MT, 3>), grid, dim3(THREADS), 0, st, g); } while (0)
+#define DNS_L(MODE, AFF, MT) do { if (one) dense_launch_kernel<MODE, AFF, MT, 1>(xt, grid, st, g); \
+                                  else dense_launch_kernel<MODE, AFF, MT, 3>(xt, grid, st, g); } while (0)
 #define DNS_M(MT)                                                                \
     do {                                                                         \
         if (in_mode == PTTS_IN_LRELU) { if (in_scale) DNS_L(PTTS_IN_LRELU, true, MT); else DNS_L(PTTS_IN_LRELU, false, MT); } \
@@ -1092,12 +1274,12 @@ extern "C" int ptts_dense_bf16x6_batched(const float* A, long long strideA, cons
 // 1 when ptts_dense_wgrad_bf16x6 takes the shape
 extern "C" int ptts_dense_wgrad_bf16x6_supported(int Kin, int N, int M, long long lda, long long ldb) {
     return (Kin > 0 && N > 0 && M > 0 && Kin % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 &&
-            (long long)((Kin + WT - 1) / WT) * ((N + WT - 1) / WT) <= 65535) ? 1 : 0;
+            (long long)wgrad_tiles_k(Kin) * ((N + WT - 1) / WT) <= 65535) ? 1 : 0;
 }
 
 namespace {
 int wgrad_split(int Kin, int N, int M) {
-    const int tiles = ((Kin + WT - 1) / WT) * ((N + WT - 1) / WT), steps = (M + 31) / 32;
+    const int tiles = wgrad_tiles_k(Kin) * ((N + WT - 1) / WT), steps = (M + 31) / 32;
     int split = (256 + tiles - 1) / tiles;                 // about one workgroup per CU
     static int env_split = -1;                              // measurement hook (tools/dense_split_probe.py)
     if (env_split < 0) { const char* e = getenv("PTTS_DENSE_WGRAD_SPLIT"); env_split = e ? atoi(e) : 0; }
@@ -1109,12 +1291,12 @@ int wgrad_split(int Kin, int N, int M) {
 
 extern "C" size_t ptts_dense_wgrad_workspace_bytes(int Kin, int N, int M) {
     if (Kin <= 0 || N <= 0 || M <= 0) return 0;
-    const size_t tiles = (size_t)((Kin + WT - 1) / WT) * ((N + WT - 1) / WT);
-    return tiles * wgrad_split(Kin, N, M) * WPART * sizeof(float);
+    const size_t tiles = (size_t)wgrad_tiles_k(Kin) * ((N + WT - 1) / WT);
+    return tiles * wgrad_split(Kin, N, M) * wgrad_part(Kin) * sizeof(float);
 }
 
 // Stage 1 of a weight-gradient product dW[Kin,N] = T(A)[M,Kin]^T . dY[M,N] (+ column sums of dY): every workgroup's partial
-// tile as a row of `workspace` ([tile][split][128*128 + 128] floats; *split_out = workgroups per tile).  Stage 2,
+// tile as a row of `workspace` ([tile][split][128*128 + 128 (+ 16*128: Kin % 128 in 1..16)] floats; *split_out = workgroups per tile).  Stage 2,
 // ptts_dense_wgrad_reduce_grouped, adds the rows of several products into their gradient buffers in one launch.
 extern "C" int ptts_dense_wgrad_bf16x6_partials(const float* A, const float* dY, const float* mask_src, const float* in_scale,
                                                 const float* in_shift, void* workspace, size_t workspace_bytes, int* split_out,
@@ -1135,7 +1317,9 @@ extern "C" int ptts_dense_wgrad_bf16x6_partials(const float* A, const float* dY,
     WgradArgs g;
     g.A = A; g.dY = dY; g.mask_src = mask_src; g.in_scale = in_scale; g.in_shift = in_shift; g.partials = (float*)workspace;
     g.Kin = Kin; g.N = N; g.M = M; g.lda = lda; g.ldb = ldb; g.alpha = alpha;
-    const int tiles_k = (Kin + WT - 1) / WT;
+    const int tiles_k = wgrad_tiles_k(Kin);
+    const bool xr = wgrad_has_rem(Kin);
+    g.tiles_k = tiles_k; g.part = wgrad_part(Kin);
     g.tiles_n = (N + WT - 1) / WT;
     g.steps_total = (M + 31) / 32;
     const int tiles = tiles_k * g.tiles_n;
@@ -1144,13 +1328,19 @@ extern "C" int ptts_dense_wgrad_bf16x6_partials(const float* A, const float* dY,
     const dim3 grid((unsigned)g.split, (unsigned)tiles);
     hipStream_t st = (hipStream_t)stream;
     constexpr size_t lds = (size_t)2 * 6 * WPL * sizeof(u16);
+    constexpr size_t ldsx = lds + (size_t)2 * 3 * WXPL * sizeof(u16);   // 105 KB
     const bool one = ptts::bf16_products();
 #define DNS_W(MODE, AFF)                                                                                                  \
     do {                                                                                                                  \
         static bool attr = false;                                                                                         \
         if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_wgrad_bf16x6_kernel<MODE, AFF, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_wgrad_bf16x6_kernel<MODE, AFF, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; } \
-        if (one) hipLaunchKernelGGL((dense_wgrad_bf16x6_kernel<MODE, AFF, 1>), grid, dim3(THREADS), lds, st, g);          \
+                     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_wgrad_bf16x6_kernel<MODE, AFF, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+                     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_wgrad_bf16x6_kernel<MODE, AFF, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsx); \
+                     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_wgrad_bf16x6_kernel<MODE, AFF, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsx); attr = true; } \
+        if (xr) {                                                                                                         \
+            if (one) hipLaunchKernelGGL((dense_wgrad_bf16x6_kernel<MODE, AFF, 1, true>), grid, dim3(THREADS), ldsx, st, g); \
+            else hipLaunchKernelGGL((dense_wgrad_bf16x6_kernel<MODE, AFF, 3, true>), grid, dim3(THREADS), ldsx, st, g);   \
+        } else if (one) hipLaunchKernelGGL((dense_wgrad_bf16x6_kernel<MODE, AFF, 1>), grid, dim3(THREADS), lds, st, g);   \
         else hipLaunchKernelGGL((dense_wgrad_bf16x6_kernel<MODE, AFF, 3>), grid, dim3(THREADS), lds, st, g);              \
     } while (0)
     if (in_mode == PTTS_IN_LRELU) { if (in_scale) DNS_W(PTTS_IN_LRELU, true); else DNS_W(PTTS_IN_LRELU, false); }
@@ -1171,7 +1361,7 @@ extern "C" int ptts_dense_wgrad_reduce_grouped(const ptts_dense_wgrad_reduce_des
             PTTS_REQUIRE(d.partials && d.C && d.split > 0 && d.Kin > 0 && d.N > 0 && d.ldc >= d.N, "dense_wgrad_reduce_grouped: bad product %d", base + i);
             a.blk_begin[i] = blocks;
             a.tiles_n[i] = (d.N + WT - 1) / WT;
-            blocks += ((d.Kin + WT - 1) / WT) * a.tiles_n[i] * DR_BPT;
+            blocks += wgrad_tiles_k(d.Kin) * a.tiles_n[i] * dr_bpt(d.Kin);
             a.partials[i] = d.partials; a.C[i] = d.C; a.colsum[i] = d.colsum_b; a.split[i] = d.split; a.Kin[i] = d.Kin; a.N[i] = d.N; a.ldc[i] = d.ldc;
         }
         a.blk_begin[a.n] = blocks;

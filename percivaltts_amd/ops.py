@@ -747,9 +747,9 @@ def gemm_raw(A, Bm, C, M, N, K, transA=0, lda=None, rows_per_seg=None, seg_strid
              ptr(ws), ws.numel(), M, N, K, lda, ldb, ldc, mode, alpha, stream(), tag=(M, N, K))
         return C
     if transA == 0 and seg_stride == 0 and rows_per_seg == M and colsum_b is None:
-        # M >> N products against a weight: the bf16x6 split kernel; a few columns beyond a multiple of 256 (the 260-wide
-        # spectral part) go to the thin fp32 kernel
-        N1 = N if (N <= 256 or N % 256 == 0 or N % 256 > 32) else N - N % 256
+        # M >> N products against a weight: the bf16x6 split kernel; up to 16 columns beyond a multiple of 256 (the 260-wide
+        # spectral part) are an extra tile of its last column block, 17..32 go to the thin fp32 kernel
+        N1 = N if (N <= 256 or N % 256 == 0 or N % 256 > 32 or N % 256 <= 16) else N - N % 256
         if _DenseSplit.eligible(A, C, M, N1, K, lda, ldc, (scale, shift, mask_src)):
             planes = _DenseSplit.get(Bm, K, N1, ldb, transB)
             if planes is not None and _BNStats.want and _BNStats.enabled and N1 == N and N % 4 == 0 and ldc % 4 == 0 and mask_src is None and \
