@@ -14,7 +14,6 @@ orthogonal recurrent kernels, unit forget bias, BN gamma/beta/moving_mean/moving
 import math
 
 import numpy as np
-import os
 
 import torch
 import torch.nn as nn
@@ -393,26 +392,9 @@ class LSTM(Layer):
     def out_shape(self, in_shapes):
         return (self.units * self.ndir,)
 
-    def _input(self, vals):
-        return to_tensor(vals[0] if not isinstance(vals[0], LazyConcat) else vals[0].tensor()).contiguous()
-
-    def precompute(self, vals, training, memo):
-        """The forward launches now, the autograd node later (`compute(..., pre=...)`): Model._run creates the node of a side-stream
-        recurrence last, so that its backward chain -- the critical path of the generator step -- is the first thing the backward
-        pass enqueues."""
-        x = self._input(vals)
-        with torch.no_grad():
-            res = ops.lstm_launch(x.detach(), self.kernel.detach(), self.recurrent_kernel.detach(), self.bias.detach())
-        # the input passes through an identity node created NOW, on this (side) stream: the late node's dx lands in that node's input
-        # buffer -- a side-stream consumer -- and reaches the producer of x when the engine gets to this early, low-priority node.
-        # Delivered directly, the engine would make the main stream wait for the whole backward chain at the moment the chain's node
-        # finishes on the host, i.e. before the critic's backward is even enqueued.
-        return {'x': ops.grad_gate(x) if x.requires_grad else x, 'res': res}
-
-    def compute(self, vals, training, memo, pre=None):
-        if pre is not None:
-            return ops.lstm(pre['x'], self.kernel, self.recurrent_kernel, self.bias, pre=pre['res'])
-        return ops.lstm(self._input(vals), self.kernel, self.recurrent_kernel, self.bias)
+    def compute(self, vals, training, memo):
+        x = to_tensor(vals[0] if not isinstance(vals[0], LazyConcat) else vals[0].tensor()).contiguous()
+        return ops.lstm(x, self.kernel, self.recurrent_kernel, self.bias)
 
 
 class GRU(Layer):
@@ -553,7 +535,7 @@ def side_streams(n, kind='side'):
     ss = _SIDE_STREAMS.setdefault(key, [])
     while len(ss) < n:
         # high priority: a latency-bound chain of small kernels (the BLSTM branch) must not queue behind the wide ones
-        ss.append(torch.cuda.Stream(priority=int(os.environ.get('PTTS_SIDE_PRIO', '-1'))))
+        ss.append(torch.cuda.Stream(priority=-1))
     return ss[:n]
 
 
@@ -612,22 +594,10 @@ class Model(nn.Module):
         on_side = set()
         if '__side__' in values:
             on_side, pending, side, cur = values.pop('__side__')
-        pre = values.pop('__pre__', {})       # node id -> launched-ahead results of a side-stream layer (Layer.precompute)
-        late = bool(getattr(self, 'side_backward_first', False))
         held = set()
-        order = self.order
-        if use_side and os.environ.get('PTTS_SIDE_DEFER', '0') != '0':
-            # (experiment, off: enqueue the main-stream nodes that do not need a side-stream result first.  Measured
-            # 1.5 ms slower per generator step: the side branch's small kernels then queue behind the wide ones)
-            side_nodes = set(id(n) for n in self.order if getattr(n, 'stream', 0))
-            needs_side = set()
-            for n in self.order:
-                if id(n) in side_nodes or any(id(p) in needs_side or id(p) in side_nodes for p in n.parents):
-                    needs_side.add(id(n))
-            order = [n for n in self.order if id(n) not in needs_side] + [n for n in self.order if id(n) in needs_side]
         given = set(values.keys())                  # ready before this call (model inputs, shared values)
         start_ev = torch.cuda.current_stream().record_event() if use_side else None
-        for n in order:
+        for n in self.order:
             if id(n) in values:
                 continue
             if not n.parents:
@@ -647,13 +617,6 @@ class Model(nn.Module):
                     # (bench.py's all_exact_work_reductions_off: 17.8 against 10.9 ms).
                     side = side_streams(2)[1]
                     cur = torch.cuda.current_stream()
-                if id(n) in pre:
-                    # launched in the earlier call; this one only creates the autograd node (no kernel reads the parents now)
-                    with torch.cuda.stream(side):
-                        values[id(n)] = n.layer.compute(vals, training, memo, pre=pre.pop(id(n)))
-                    on_side.add(id(n))
-                    pending = True
-                    continue
                 if not any(id(p) in on_side for p in n.parents):
                     # inputs come from the main stream: if they all existed before this call, wait only for the point
                     # where the call started, not for the main-stream work enqueued since
@@ -677,14 +640,6 @@ class Model(nn.Module):
                             t = leaf
                         cvals.append(t)
                     vals = cvals
-                if late and hold and not cut_side and torch.is_grad_enabled() and hasattr(n.layer, 'precompute'):
-                    # a later call finishes the graph (`hold`): launch now, create the node then -- after everything the caller
-                    # evaluates in between (the critic), i.e. with the highest priority of the backward pass
-                    with torch.cuda.stream(side):
-                        pre[id(n)] = n.layer.precompute(vals, training, memo)
-                    held.add(id(n))
-                    pending = True
-                    continue
                 with torch.cuda.stream(side):
                     values[id(n)] = n.layer.compute(vals, training, memo)
                 on_side.add(id(n))
@@ -706,7 +661,6 @@ class Model(nn.Module):
             values[id(n)] = n.layer.compute(vals, training, memo)
         if held:
             values['__side__'] = (on_side, pending, side, cur)      # the join happens in the call that finishes the graph
-            values['__pre__'] = pre
             if cut_side and pending and side is not None:
                 values['__side_ev__'] = side.record_event()
         elif pending:
@@ -749,30 +703,9 @@ class Model(nn.Module):
                 for i, pn in enumerate(n.parents[0].parents):
                     if i > 0 and id(pn) in shared:
                         n.layer.prime_part(i, [pp.shape[-1] for pp in n.parents[0].parents], shared[id(pn)], memo)
-        results = []
-        streams = self._variant_streams(len(variants)) if parallel_streams else None
-        cur = torch.cuda.current_stream() if parallel_streams else None
-        for vi, x in enumerate(variants):
-            values = dict(shared)
-            values[id(vin)] = x
-            if streams is not None and vi > 0:
-                st = streams[vi - 1]
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    values = self._run({}, training, memo, values)
-                    outs = [to_tensor(values[id(o)]) for o in self.outputs]
-            else:
-                values = self._run({}, training, memo, values)
-                outs = [to_tensor(values[id(o)]) for o in self.outputs]
-            results.append(outs[0] if self.single_output else outs)
-        if streams is not None:
-            for vi in range(1, len(variants)):
-                cur.wait_stream(streams[vi - 1])
-                for o in (results[vi] if isinstance(results[vi], list) else [results[vi]]):
-                    o.record_stream(cur)
-        return results
+        return self._fan_out(shared, id(vin), variants, training, memo, parallel_streams)
 
-    def forward_multi_at(self, node, variants, feed, training=False, memo=None, parallel_streams=False, shared_stream=False, pair=False):
+    def forward_multi_at(self, node, variants, feed, training=False, memo=None, parallel_streams=False, pair=False):
         """forward_multi with the varying value at an INTERNAL node (`variants` are values of `node`, e.g. the critic's spectral slice:
         the stacked real / fake spectra and the interpolated sample, built by the optimiser without materialising the 86-column
         inputs they would be sliced from).  `feed` = {input node: tensor} for the inputs the rest of the graph needs; nodes that only
@@ -790,59 +723,24 @@ class Model(nn.Module):
         up(node)
         feed = {id(k): v for k, v in feed.items()}
         shared = {}
-        # shared_stream: the part of the graph that does not depend on `node` (the critic's context branch: Conv1D + two Dense layers and
-        # its product with the first post-concat kernel) runs on a side stream BESIDE the variants' own part up to the first node that
-        # needs it (the concatenation); autograd replays the fork in the backward pass.  One fork and one join per pass.
-        side_sh = cur_sh = ev_sh = None
-        join_nodes = None
-        if shared_stream and torch.cuda.is_available() and not parallel_streams:
-            join_nodes = set(id(n) for n in self.order if id(n) in desc and any(id(p) not in desc and id(p) not in anc for p in n.parents))
-            if join_nodes:
-                side_sh = side_streams(1, 'shared')[0]
-                cur_sh = torch.cuda.current_stream()
-                side_sh.wait_stream(cur_sh)
-        import contextlib as _ctx
-        with (torch.cuda.stream(side_sh) if side_sh is not None else _ctx.nullcontext()):
-            for n in self.order:
-                if id(n) in desc:
-                    continue
-                if not n.parents:
-                    if id(n) in feed:
-                        shared[id(n)] = feed[id(n)]
-                    else:
-                        assert id(n) in anc, 'forward_multi_at: input {} is needed but was not fed'.format(n.name)
-                        shared[id(n)] = None
-                elif id(n) in anc and any(shared.get(id(p)) is None for p in n.parents):
-                    shared[id(n)] = None                  # feeds only `node`: its value is given
+        for n in self.order:
+            if id(n) in desc:
+                continue
+            if not n.parents:
+                if id(n) in feed:
+                    shared[id(n)] = feed[id(n)]
                 else:
-                    shared[id(n)] = n.layer.compute([shared[id(p)] for p in n.parents], training, memo)
-            for n in self.order:
-                if isinstance(n.layer, Dense) and id(n) in desc and isinstance(n.parents[0].layer, Concatenate):
-                    for i, pn in enumerate(n.parents[0].parents):
-                        if i > 0 and id(pn) in shared and shared[id(pn)] is not None:
-                            n.layer.prime_part(i, [pp.shape[-1] for pp in n.parents[0].parents], shared[id(pn)], memo)
-            if side_sh is not None:
-                ev_sh = side_sh.record_event()
-        if side_sh is not None:
-            # the variants' own part first, all of them, then the join, then the rest
-            results, partial = [], []
-            for x in variants:
-                values = dict(shared)
-                values[id(node)] = x
-                partial.append(self._run({}, training, memo, values, hold=join_nodes))
-            cur_sh.wait_event(ev_sh)
-            for v in shared.values():
-                t = v.z if isinstance(v, Lazy) else v
-                if torch.is_tensor(t):
-                    t.record_stream(cur_sh)
-            for k, t in memo.items():
-                if isinstance(k, tuple) and k and k[0] == 'dense_part' and torch.is_tensor(t):
-                    t.record_stream(cur_sh)
-            for values in partial:
-                values = self._run({}, training, memo, values)
-                outs = [to_tensor(values[id(o)]) for o in self.outputs]
-                results.append(outs[0] if self.single_output else outs)
-            return results
+                    assert id(n) in anc, 'forward_multi_at: input {} is needed but was not fed'.format(n.name)
+                    shared[id(n)] = None
+            elif id(n) in anc and any(shared.get(id(p)) is None for p in n.parents):
+                shared[id(n)] = None                  # feeds only `node`: its value is given
+            else:
+                shared[id(n)] = n.layer.compute([shared[id(p)] for p in n.parents], training, memo)
+        for n in self.order:
+            if isinstance(n.layer, Dense) and id(n) in desc and isinstance(n.parents[0].layer, Concatenate):
+                for i, pn in enumerate(n.parents[0].parents):
+                    if i > 0 and id(pn) in shared and shared[id(pn)] is not None:
+                        n.layer.prime_part(i, [pp.shape[-1] for pp in n.parents[0].parents], shared[id(pn)], memo)
         results = []
         if pair and len(variants) == 2 and not parallel_streams and ops._PairFlags.enabled and \
                 not any(getattr(n, 'stream', 0) for n in self.order if id(n) in desc):
@@ -864,11 +762,17 @@ class Model(nn.Module):
                 outs = [to_tensor(vals[v][id(o)]) for o in self.outputs]
                 results.append(outs[0] if self.single_output else outs)
             return results
-        streams = self._variant_streams(len(variants)) if parallel_streams else None
+        return self._fan_out(shared, id(node), variants, training, memo, parallel_streams)
+
+    def _fan_out(self, shared, node_id, variants, training, memo, parallel_streams):
+        """The rest of the graph once per variant (a value of node `node_id`) over the `shared` values; with `parallel_streams` every
+        variant but the first runs on a side stream of its own, joined before the results are returned."""
+        results = []
+        streams = side_streams(len(variants) - 1) if parallel_streams else None
         cur = torch.cuda.current_stream() if parallel_streams else None
         for vi, x in enumerate(variants):
             values = dict(shared)
-            values[id(node)] = x
+            values[node_id] = x
             if streams is not None and vi > 0:
                 st = streams[vi - 1]
                 st.wait_stream(cur)
@@ -885,9 +789,6 @@ class Model(nn.Module):
                 for o in (results[vi] if isinstance(results[vi], list) else [results[vi]]):
                     o.record_stream(cur)
         return results
-
-    def _variant_streams(self, n):
-        return side_streams(n - 1)
 
     # ---- Keras-like accessors ----------------------------------------------------------------
     def weights(self):

@@ -2242,22 +2242,6 @@ def _lstm_mark(tag):
         lstm_trace.append((tag, ev))
 
 
-class _GradGateFn(torch.autograd.Function):
-    """Identity whose only purpose is its place in the autograd tape (creation order = priority of the backward pass, stream of
-    creation = stream its input buffer accumulates on)."""
-    @staticmethod
-    def forward(ctx, x):
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return g
-
-
-def grad_gate(x):
-    return _GradGateFn.apply(x)
-
-
 class _GradInjectFn(torch.autograd.Function):
     """Identity in the forward pass; in the backward pass the gradient that another, EARLIER backward pass left in `holder`
     (holder['grad'], made on another stream: holder['event']) is added to the incoming one.  The wait for that stream happens here,
@@ -2324,16 +2308,14 @@ lstm_dx_ready = None      # (data_ptr of the last LSTM backward's dx, event reco
 class LSTMFn(torch.autograd.Function):
     """x [B,T,In]; W [In, ndir*4H]; U [ndir,H,4H]; b [ndir*4H] -> h [B,T,ndir*H] (Keras gate order i,f,c,o)."""
     @staticmethod
-    def forward(ctx, x, W, U, b, reverse, pre=None):
-        # `pre`: (h, c, gates) of lstm_launch() on the same operands -- the launches went out earlier, this call only ties the result
-        # into the autograd tape (layers.Model._run: a node created late has its backward chain enqueued early)
-        h, c, gates = lstm_launch(x, W, U, b, reverse) if pre is None else pre
+    def forward(ctx, x, W, U, b, reverse):
+        h, c, gates = lstm_launch(x, W, U, b, reverse)
         ctx.save_for_backward(x, W, U, h, c, gates)
         ctx.reverse = int(reverse)
         # inside deferred_weight_grads(): the weight gradients are added straight into the flat gradient buffer on the stream of the
         # backward chain.  Handed to autograd instead, their AccumulateGrad nodes (made on the main stream) make the MAIN stream wait
-        # for this side stream at the moment the engine reaches them -- with the chain enqueued first (Model.side_backward_first) that
-        # is before the critic's backward pass, which then runs after the recurrence instead of under it.
+        # for this side stream at the moment the engine reaches them -- wherever the chain is enqueued ahead of the critic's backward
+        # pass, that pass then runs after the recurrence instead of under it.
         ctx.gt = _Deferred.targets(W, U, b)
         return h
 
@@ -2382,11 +2364,11 @@ class LSTMFn(torch.autograd.Function):
                     t.add_(g.view(t.shape))
             _Deferred.note_stream()             # flush_weight_grads() joins this stream before the optimiser reads the buffer
             dW = dU = db = None
-        return dx, dW, dU, db, None, None
+        return dx, dW, dU, db, None
 
 
-def lstm(v, W, U, b, reverse=False, pre=None):
-    return LSTMFn.apply(as_tensor(v).contiguous(), W, U, b, reverse, pre)
+def lstm(v, W, U, b, reverse=False):
+    return LSTMFn.apply(as_tensor(v).contiguous(), W, U, b, reverse)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -112,6 +112,7 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         self.critic = critic
         self.costs_tra_critic_batches = _DeviceCosts()
         self.generator_updates = 0
+        self._forget_step_state()
 
     def default_options(self, cfg):
         cfg.train_wgan_critic_learningrate_log10 = -4
@@ -133,18 +134,14 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         cfg.train_wgan_hipgraph = False              # True: every step replayed as a hipGraph; 'auto': only for batches of at most train_wgan_hipgraph_maxframes frames (launch-bound steps such as the reference's B = 10, run.py:125-126)
         cfg.train_wgan_hipgraph_maxframes = 8192
         cfg.train_wgan_parallel_streams = False      # the critic evaluations on separate HIP streams
-        cfg.train_wgan_side_backward_first = False   # generator step: the BLSTM's autograd node created last (its launches go out first), so that its backward chain is enqueued first.  Measured: the chain then ends 1 ms earlier, the step does not (the main stream's backward becomes the tail): off
         cfg.train_wgan_stack_real_fake = True        # critic(real) and critic(fake) as one stacked 2B pass (exact: no BatchNorm)
         cfg.train_wgan_graph_frozen_planes = True    # a replayed critic step reads the frozen generator's context-kernel planes from a buffer refreshed per generator update instead of rebuilding them in every replay
-        cfg.train_wgan_fake_ahead = False            # (measured, off) the frozen generator's sample of the NEXT critic-only batch drawn on a side stream beside this batch's critic step: cycle 29.55 -> 29.85 ms -- the step's graph then transforms the context input a second time, and the overlap does not pay for it
         cfg.train_wgan_generator_lookahead = True    # a generator step's forward launched one batch ahead when the caller names the next batch (hint_next_batch / device_step(nxt=...))
         cfg.train_wgan_pair_forward = True           # critic step: the forward of the stacked real / fake batch (2B) and of x^ (B) as ONE launch per layer over 3B rows (their backward passes stay separate)
-        cfg.train_wgan_ctx_stream = False            # critic step: the context branch on a side stream beside the spectral stacks (one fork / join per pass; measured, see DESIGN)
         cfg.train_wgan_feed_spectra = True           # the critic is fed at its spectral slice (real / fake / interpolated spectra built directly; False: whole 86-column samples through the slice, as the reference's graph does)
         cfg.train_wgan_reuse_ctx_conv = True         # generator step reuses the critic step's G-context-Conv1D product (same batch)
         cfg.train_wgan_early_critic = True           # generator step: critic starts on the spectral branch, BLSTM joins for the LS term
         cfg.train_wgan_hoist_side_backward = True    # ... and the BLSTM branch's BACKWARD too (its output is read by the least-squares term only: the branch is cut out of the tape, run on its own, its gradient injected at the cut).  Measured + 1 % (three A/B pairs, fp32 and bf16): both chains then run under the critic step
-        cfg.train_wgan_batch_graph = False           # 'tune': a batch that trains both networks may be replayed as ONE hipGraph (BLSTM fork kept), if that times faster.  It does not: 29.6 ms against 14.0 for the separate steps (cross-stream edges of a graph replay at half speed on this runtime) -- off, so that the timing runs are not made either
         cfg.train_wgan_hoist_generator = True        # a batch that trains both: G's forward (it does not depend on the critic) is launched BEFORE the critic step -- its BLSTM chain runs under that step -- and the critic step takes its fake sample from it
         cfg.train_wgan_graph_critic = None           # 'on' / 'off': pin the critic step's form (hipGraph replay / eager launches) whatever train_wgan_hipgraph would choose
         cfg.train_wgan_graph_generator = None        # ... and the generator step's
@@ -227,14 +224,26 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
 
         # these two names are what the reference exposes after prepare()
         generator.parallel_branches = bool(cfg.train_wgan_parallel_streams)
-        generator.side_backward_first = bool(getattr(cfg, 'train_wgan_side_backward_first', False))
         self.critic_model = self.critic_net
         self.generator_model = generator
         self._graphs = {}
         self._graph_choice = {}      # cfg.train_wgan_hipgraph = 'tune': (kind, shapes) -> replay the step as a hipGraph?
         self._graph_tuning = {}      # ... and the two timings behind the choice
-        self._pending = {}           # 'critic' / 'generator' -> event of an optimiser update still running on the communication stream
         self._comm = None
+        self._forget_step_state()
+
+    def _forget_step_state(self):
+        """The state a step leaves for a later one: what a new optimiser starts with, and what prepare() puts back.  A second prepare()
+        (the next hyper-parameter trial after an aborted one) FORGETS a pending look-ahead, it does not _drop_ahead it: the model has
+        just been reloaded, and the stale entry must not write its saved moving averages over it."""
+        self._pending = {}             # kind -> event of an update still on the communication stream.  Written: _update.  Read: _wait_update
+        self._next_batch = None        # the batch to come.  Written: hint_next_batch.  Read: train_on_batch, device_step
+        self._ahead = None             # a generator forward launched one batch ahead.  Written and read: _batch_steps (bench.py drops it)
+        self._gen_deferred = None      # weight-gradient queue of a hoisted forward.  Written: _batch_steps.  Read: _generator_grads
+        self._gen_cuts = None          # injection nodes at the side branch's cut.  Written: generator_forward_early.  Read: _generator_grads
+        self._graph_frozen = {}        # graph key -> frozen generator planes and their weight epoch.  Written and read: _graphed
+        self._side_tail_event = None   # end of the side branch's early backward.  Written: generator_forward_early.  Read: nobody yet
+        self._critic_per_sample = None   # cached answer.  Written and read: _critic_is_per_sample
 
     # ---- device-side losses ----------------------------------------------------------------------------------
     def _fake_sample(self, X, training):
@@ -285,7 +294,6 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
                 # no BatchNorm in the critic: critic(real) and critic(fake) are one pass over the stacked 2B batch (half the launches,
                 # one weight-gradient product per layer instead of two; the context branch stays shared, at B)
                 both, v_hat = self.critic_net.forward_multi_at(node, [spec2, x_hat], feed, training=training, parallel_streams=streams,
-                                                                shared_stream=bool(getattr(self.cfg, 'train_wgan_ctx_stream', False)),
                                                                 pair=bool(getattr(self.cfg, 'train_wgan_pair_forward', True)))
                 l_valid, l_fake = ops.wasserstein_pair(both, B)
             else:
@@ -316,7 +324,7 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
 
     def _critic_is_per_sample(self):
         """True when no critic layer couples the samples of a batch (no BatchNormalization): stacking evaluations is exact."""
-        ok = getattr(self, '_critic_per_sample', None)
+        ok = self._critic_per_sample
         if ok is None:
             from . import layers as _layers
             ok = not any(isinstance(l, _layers.BatchNormalization) for l in self.critic_net.layers_list)
@@ -394,9 +402,7 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
             # The critic reads the spectral columns only (the condition under which the critic step prunes the other
             # branches).  It is therefore fed the spectral branch as soon as that exists, while the latency-bound f0
             # branch (BLSTM, side stream) still runs; the final concatenation -- the join with the side stream -- is
-            # needed by the least-squares term alone and comes last.  Same values.  (cfg.train_wgan_side_backward_first creates
-            # the BLSTM's autograd node last -- launches first, layers.Model._run -- so that its backward chain is enqueued
-            # first: the chain then ends 1 ms earlier but the step does not, tools/gen_timeline.py events; off.)
+            # needed by the least-squares term alone and comes last.  Same values.
             out_node = m.outputs[0]
             if pre is not None:
                 feed, values = pre
@@ -442,7 +448,7 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
 
     def _wait_update(self, kind):
         """Make the current stream wait for a still-running update of that network's weights (no-op otherwise)."""
-        ev = self._pending.pop(kind, None) if getattr(self, '_pending', None) else None
+        ev = self._pending.pop(kind, None)
         if ev is not None:
             torch.cuda.current_stream().wait_event(ev)
 
@@ -505,11 +511,11 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         try:
             with ops.deferred_weight_grads():
                 if pre is not None:
-                    ops.deferred_attach(getattr(self, '_gen_deferred', None))
+                    ops.deferred_attach(self._gen_deferred)
                     self._gen_deferred = None
                 total, _ = self.generator_loss(X, Y, training=True, pre=pre)
                 ops._lstm_mark('loss')
-                cuts = getattr(self, '_gen_cuts', None) if pre is not None else None
+                cuts = self._gen_cuts if pre is not None else None
                 if cuts:
                     # the injection nodes at the side branch's cut add the gradient its early backward left behind; as extra roots (with a
                     # zero gradient) they are reached even if no later layer consumed them
@@ -615,23 +621,15 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
             sX, sY = X.clone(), Y.clone()
             sA = torch.rand(X.shape[0], device=X.device, dtype=torch.float32)
             sF = fake.detach().clone() if with_fake else None
-            if kind == 'batch':
-                assert whole, 'the whole-batch graph is a one-process form'
-                fn = lambda: self._batch_steps(sX, sY, sA, True, False, False)
-            elif whole:
+            if whole:
                 fn = (lambda: self.critic_step(sX, sY, sA, sF)) if kind == 'critic' else (lambda: self.generator_step(sX, sY))
             else:
                 fn = (lambda: self._critic_grads(sX, sY, sA, sF)) if kind == 'critic' else (lambda: self._generator_grads(sX, sY))
             from . import layers
             # the graph is captured on one stream: the evaluations' side streams would become cross-stream edges of the capture
             saved_streams = (self.cfg.train_wgan_parallel_streams, getattr(self._model.kerasmodel, 'parallel_branches', False))
-            if kind == 'batch':
-                # one fork: the generator's BLSTM branch stays on its side stream (its chain runs beside the critic step); the critic's
-                # three evaluations go on one stream (a capture with their cross-stream edges replayed at half the speed)
-                self.cfg.train_wgan_parallel_streams = False
-            elif not bool(getattr(self.cfg, 'train_wgan_graph_streams', False)):
-                self.cfg.train_wgan_parallel_streams = False
-                self._model.kerasmodel.parallel_branches = False
+            self.cfg.train_wgan_parallel_streams = False
+            self._model.kerasmodel.parallel_branches = False
             side = layers.side_streams(1, 'capture')[0]
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -661,8 +659,6 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
                 ops.clear_caches()         # ... and the graph's private copies are not for eager code
                 ops._C1FFT.frozen = frozen_prev
                 self.cfg.train_wgan_parallel_streams, self._model.kerasmodel.parallel_branches = saved_streams
-            if not hasattr(self, '_graph_frozen'):
-                self._graph_frozen = {}
             # the buffers this graph reads for the frozen generator's kernels, and the state of its weights they were built from
             self._graph_frozen[key] = {'items': frozen_items, 'epoch': self.gen_opti.flat.epoch}
             ent = (g, sX, sY, sA, out, sF)
@@ -672,11 +668,11 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         sX.copy_(X); sY.copy_(Y)
         if sF is not None:
             sF.copy_(fake)
-        if kind in ('critic', 'batch'):
+        if kind == 'critic':
             if alpha is None: sA.uniform_(0.0, 1.0)
             else: sA.copy_(alpha.reshape(-1))
         self.wait_updates()            # the replay reads (and, in one process, writes) both networks' weights
-        fz = getattr(self, '_graph_frozen', {}).get(key)
+        fz = self._graph_frozen.get(key)
         if fz is not None and fz['items'] and fz['epoch'] != self.gen_opti.flat.epoch:
             # the frozen generator's kernel planes the graph reads (see the capture): rebuilt if the generator's weights have changed
             ops._C1FFT.refresh_planes(fz['items'])
@@ -685,8 +681,7 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         if whole:
             # the replayed Adam / clip kernels changed the weights behind every weight-keyed cache (bf16 planes, Toeplitz
             # tables): the Python-side epoch bump of KerasAdam.step() is not part of the graph
-            if kind in ('critic', 'batch'): self.critic_opti.flat.epoch += 1
-            if kind in ('generator', 'batch'): self.gen_opti.flat.epoch += 1
+            (self.critic_opti if kind == 'critic' else self.gen_opti).flat.epoch += 1
         else:
             self._update(kind)
         return out
@@ -746,29 +741,22 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         use_graph = graph_c or graph_g
         ops.conv1d_cache(gen_too and not use_graph and bool(getattr(self.cfg, 'train_wgan_reuse_ctx_conv', True)))
         try:
-            if gen_too and not graph_g and self._use_batch_graph(X, Y, graph_c):
-                # the whole train_on_batch of this batch (hoisted generator forward, critic step, generator step) as ONE hipGraph with
-                # the BLSTM branch's fork / join kept: no host time at all
-                lc, lg = self._graphed('batch', X, Y, alpha)
-                self.generator_updates += 1
-                return lc, lg
             if nxt is None:
-                nxt, self._next_batch = getattr(self, '_next_batch', None), None
+                nxt, self._next_batch = self._next_batch, None
             next_gen = nxt is not None and not gen_too and (batchid + 1) % critic_runs == 0
-            lc, lg = self._batch_steps(X, Y, alpha, gen_too, graph_c, graph_g, nxt if next_gen else None,
-                                       nxt if (nxt is not None and not gen_too and not next_gen) else None)
+            lc, lg = self._batch_steps(X, Y, alpha, gen_too, graph_c, graph_g, nxt if next_gen else None)
             if gen_too:
                 self.generator_updates += 1
         finally:
             ops.conv1d_cache(False)
         return lc, lg
 
-    def _batch_steps(self, X, Y, alpha, gen_too, graph_c, graph_g, nxt=None, nxt_critic=None):
+    def _batch_steps(self, X, Y, alpha, gen_too, graph_c, graph_g, nxt=None):
         """The steps of one train_on_batch: critic step, and the generator step when `gen_too` (its forward hoisted in front of the
         critic step -- or of the previous batch's critic step, see device_step -- by generator_forward_early)."""
         pre = fake = None
         hoist = bool(getattr(self.cfg, 'train_wgan_hoist_generator', True)) and self._can_split_generator()
-        ahead, self._ahead = getattr(self, '_ahead', None), None
+        ahead, self._ahead = self._ahead, None
         if ahead is not None and not (gen_too and not graph_g and hoist and ahead['X'] is X and ahead['Y'] is Y and
                                       ahead['epoch'] == self.gen_opti.flat.epoch):
             self._drop_ahead(ahead)
@@ -785,15 +773,6 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
                     pre = self.generator_forward_early(X, Y, training=True)
                     self._gen_deferred = ops.deferred_detach()      # (joined and flushed by the generator step's own context)
             fake = self.fake_from_early(X, pre)
-        fa, self._fake_ahead = getattr(self, '_fake_ahead', None), None
-        if fa is not None and fake is None and fa['X'] is X and fa['epoch'] == self.gen_opti.flat.epoch:
-            # the frozen generator's sample of this batch was drawn one batch ago on a side stream (below)
-            cur = torch.cuda.current_stream()
-            cur.wait_event(fa['event'])
-            fake = fa['fake']
-            fake.record_stream(cur)
-        if nxt_critic is not None and bool(getattr(self.cfg, 'train_wgan_fake_ahead', False)):
-            self._fake_sample_ahead(nxt_critic[0])
         if nxt is not None and hoist and bool(getattr(self.cfg, 'train_wgan_generator_lookahead', True)) and \
                 not self._use_graph(nxt[0], 'generator', nxt[1]):
             # the NEXT batch trains the generator: its forward goes out now, in front of this batch's critic step
@@ -823,23 +802,6 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
                 lg = self.generator_step(X, Y) if pre is None else self.generator_step(X, Y, pre)
         return lc, lg
 
-    def _fake_sample_ahead(self, Xn):
-        """The next batch trains the critic alone and the generator is not updated before it: the frozen generator's sample of THAT batch
-        (reference optimizertts_wgan.py:126-131 -- it depends on the generator's weights and the batch's labels only) is drawn now, on a
-        side stream, beside this batch's critic step instead of in front of the next one.  The critic step's launches are single-round
-        and latency-bound: a second, independent chain of launches fills the compute units they leave idle.  The
-        step's own stream -- and its hipGraph, which then takes the sample as an input -- stays a single stream."""
-        cur = torch.cuda.current_stream()
-        self._wait_update('generator')                  # on the step's stream (the pending update is known to ONE waiter) ...
-        side = getattr(self, '_fake_stream', None)
-        if side is None:
-            side = self._fake_stream = kl.side_streams(2)[0]       # (an existing one: every stream created costs every later launch)
-        side.wait_stream(cur)                           # ... and the side stream behind it
-        with torch.cuda.stream(side):
-            f = self._fake_sample(Xn, True)
-            ev = side.record_event()
-        self._fake_ahead = {'X': Xn, 'fake': f, 'event': ev, 'epoch': self.gen_opti.flat.epoch}
-
     def _drop_ahead(self, ahead):
         """A generator forward launched one batch ahead for a batch that did not come (the caller named another one, the weights were
         restored, the step kind changed): everything it changed is put back -- the BatchNorm moving averages it moved, the gradient
@@ -856,43 +818,11 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
                 off += b.numel()
         self.gen_opti.zero_grad()
 
-    def _use_batch_graph(self, X, Y, graph_c):
-        """cfg.train_wgan_hipgraph = 'tune' (one process): is a batch that trains both networks replayed as ONE graph?  Timed on the first
-        such batch against the separate steps (critic step as chosen, eager generator step with its forward hoisted)."""
-        if self.cfg.train_wgan_hipgraph != 'tune' or self.world != 1 or not bool(getattr(self.cfg, 'train_wgan_batch_graph', False)):
-            return False
-        if X.shape[0] * X.shape[1] <= int(getattr(self.cfg, 'train_wgan_hipgraph_maxframes', 8192)):
-            return False
-        key = ('batch', tuple(X.shape), tuple(Y.shape))
-        if key in self._graph_choice:
-            return self._graph_choice[key]
-        snap = self._state_snapshot()
-        gu = self.generator_updates
-        def timed(fn, n=3):
-            torch.cuda.synchronize()
-            t = time.time()
-            for _ in range(n): fn()
-            torch.cuda.synchronize()
-            return (time.time() - t) / n
-        sep = lambda: self._batch_steps(X, Y, None, True, graph_c, False)
-        one = lambda: self._graphed('batch', X, Y)
-        for _ in range(2): sep()
-        one()
-        t_sep, t_one = [], []
-        for _ in range(2):
-            t_sep.append(timed(sep)); t_one.append(timed(one))
-        t_sep, t_one = min(t_sep), min(t_one)
-        self._state_restore(snap)
-        self.generator_updates = gu
-        self._graph_choice[key] = bool(t_one < t_sep)
-        self._graph_tuning[key] = {'separate_steps_ms': t_sep * 1e3, 'one_graph_ms': t_one * 1e3, 'graph': bool(t_one < t_sep)}
-        return self._graph_choice[key]
-
     # ---- the reference's hooks --------------------------------------------------------------------------------------
     def train_on_batch(self, batchid, X_trab, Y_trab):
         X_trab, Y_trab = self._local_shard(X_trab, Y_trab)
         X, Y = self._to_dev(X_trab), self._to_dev(Y_trab)
-        nb = getattr(self, '_next_batch', None)
+        nb = self._next_batch
         if nb is not None and torch.is_tensor(nb[0]) and nb[0].is_cuda:
             nb = (self._to_dev(nb[0]), self._to_dev(nb[1]))           # (identity for resident float32 tensors: the objects stay the same)
         else:

@@ -110,9 +110,9 @@ def test_training_run_with_and_without_the_generator_look_ahead(tmp_path, monkey
 
     launched = []
 
-    def spy(self, X, Y, alpha, gen_too, graph_c, graph_g, nxt=None, nxt_critic=None):
+    def spy(self, X, Y, alpha, gen_too, graph_c, graph_g, nxt=None):
         ahead_calls.append(nxt is not None)
-        r = orig(self, X, Y, alpha, gen_too, graph_c, graph_g, nxt, nxt_critic)
+        r = orig(self, X, Y, alpha, gen_too, graph_c, graph_g, nxt)
         launched.append(getattr(self, '_ahead', None) is not None)       # a generator forward was launched for the next batch
         return r
     monkeypatch.setattr(optimizertts_wgan.OptimizerTTSWGAN, '_batch_steps', spy)

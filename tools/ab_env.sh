@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B on the GPU box: bench.py headline loop (side legs off) for each value of one environment switch.
-#   bash tools/ab_env.sh PTTS_SIDE_BWD_FIRST "0 1" [extra bench args]
+#   bash tools/ab_env.sh PTTS_FROZEN_PLANES "1 0" [extra bench args]
 VAR=$1; VALS=$2; shift 2
 LEGS="--full --no-variants --no-unreduced --no-host-leg --no-reference-shape --no-bf16-leg --no-gated-leg --no-cpu-baseline"
 for dt in f32 bf16; do

@@ -9,7 +9,7 @@ import json,sys
 t=sys.stdin.read().strip().splitlines()
 j=json.loads(t[-1]) if t else {}
 h=j.get('config',{}).get('hipgraph',{})
-print('$dt $VAR=$v value %.3f M  ms/step %.3f' % (j.get('value',0)/1e6, j.get('ms_per_step',0)), h.get('critic'), h.get('generator'), h.get('batch_that_trains_both_as_one_graph'), h.get('tuning_ms',{}).get('batch'))
+print('$dt $VAR=$v value %.3f M  ms/step %.3f' % (j.get('value',0)/1e6, j.get('ms_per_step',0)), h.get('critic'), h.get('generator'))
 "
 done; done
 tail -3 gpurun_out/ab2.err | cut -c1-300

@@ -17,7 +17,7 @@ def run(bf16):
     import torch
     import bench
     from percivaltts_amd import parallel, backend_hip
-    graph = os.environ.get('TL_GRAPH', '0') == '1'       # whole-step hipGraph (with PTTS_GRAPH_STREAMS=1: fork / join kept): no host in the way
+    graph = os.environ.get('TL_GRAPH', '0') == '1'       # whole-step hipGraph: no host in the way
     sys.argv = ['bench.py', '--graph' if graph else '--no-graph'] + (['--dtype', 'bf16'] if bf16 else [])
     args = bench.parse()
     parallel.init()
