@@ -699,6 +699,46 @@ int ptts_pulse_segments(const float* spec, const float* mask, const float* noise
 int ptts_pulse_overlap_add(const float* seg, const int* itab, int P, int W, float* wav, long long wavlen, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Waveform analysis for the PML parameters (csrc/analysis.hip; the counterpart of the synthesis
+ * above, the definition is this build's own).  L = dftlen, K = L/2 + 1,
+ * rnd(x) = floor(x + 0.5).  fp32 in memory, fp64 arithmetic, every integer decision in fp64.
+ *
+ * ptts_frame_harmonics: one workgroup per frame; L a power of two in 256 .. 8192.  wav [N] at fs,
+ *   f0 [T] Hz (positive; frame i at i shift), Hcap: columns of u, at least H_i - 1 for every
+ *   frame, H_i = floor((fs/2 - f0_i/2) / f0_i).  A Blackman window of 2 int(1.5 fs / f0_i) + 1
+ *   samples around rnd(i shift fs), normalised to sum 1, zero-phase; its transform's peak in each
+ *   harmonic's stretch of bins times fs / f0_i gives a_h; spec [T, K] = exp of a_h interpolated in
+ *   Hz (log_out != 0: the logarithm itself); u [T, Hcap, 2] = the unit phasor of
+ *   X[k_{h+1}] conj(X[k_h]) conj(X[k_1]), k_h = rnd(h f0_i L / fs), at column h - 1, (0, 0) behind
+ *   H_i - 1.  A frame whose window does not fit L or that has more than Hcap + 1 harmonics is
+ *   skipped: nothing of it is read or written.
+ * ptts_phase_coherence: R [T, Hcap] = |sum of u over the frames within J_i = max(2, rnd(1 / (f0_i
+ *   shift))) of frame i that have the harmonic| / their number (1 behind H_i - 1); nm [T, nb] =
+ *   the hat-weighted share of bins in each band whose harmonic has R < exp(-0.75^2 / 2).
+ * ptts_fwbnd_compress: x [T, K] -> out [T, nb] on the band axis of ptts_fwbnd2spec, with W[k,b]
+ *   the weight with which ptts_fwbnd2spec reads band b at bin k.  PTTS_COMPRESS_MEAN:
+ *   sum_k W[k,b] x[k] / sum_k W[k,b].  PTTS_COMPRESS_LSQ: the least-squares solution y of
+ *   W y = v, v = ln max(|x|, FLT_MIN) (is_log != 0: v = x), the exact left inverse of
+ *   ptts_fwbnd2spec(log) wherever every band has weight.  dftlen even, 8 .. 2^20.
+ * Tables: fwtable is ptts_fwbnd_table(nb, fs, ., dftlen); ctable [6][nb rounded up to 4] fp64 is
+ *   built from it by ptts_fwbnd_compress_table, one small launch (a band's first and last + 1 bin,
+ *   sum_k W[k,b], and the factors of the tridiagonal W^T W); 32-byte aligned, the CALLER keeps
+ *   both.  Indices read from the tables are clamped.  T = 0 succeeds without a launch.
+ * ------------------------------------------------------------------------------------- */
+#define PTTS_COMPRESS_MEAN 0
+#define PTTS_COMPRESS_LSQ  1
+int ptts_frame_harmonics(const float* wav, long long N, const float* f0, float* spec, float* u, int T, int Hcap, double shift,
+                         double fs, int dftlen, int log_out, void* stream);
+int ptts_phase_coherence(const float* u, const float* f0, float* R, float* nm, int T, int Hcap, int nb, double shift, double fs,
+                         int dftlen, const double* fwtable, size_t fwtable_bytes, const double* ctable, size_t ctable_bytes,
+                         void* stream);
+size_t ptts_fwbnd_compress_table_bytes(int nb);
+int ptts_fwbnd_compress_table(double* ctable, size_t ctable_bytes, const double* fwtable, size_t fwtable_bytes, int nb, int dftlen,
+                              void* stream);
+int ptts_fwbnd_compress(const float* x, float* out, int T, int nb, int dftlen, int mode, int is_log, const double* fwtable,
+                        size_t fwtable_bytes, const double* ctable, size_t ctable_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Label front end (external/merlin/label_normalisation.py: pattern_matching_binary,
  * pattern_matching_continous_position, load_labels_with_state_alignment :661-710,
  * load_labels_with_phone_alignment :546-568): HTS full-context labels -> frame-level context rows.

@@ -1,5 +1,5 @@
 """Wrappers of the offline pipeline over the HIP kernels of libpercival_hip.so: parameter generation (MLPG), feature
-composition, spectral envelope decompression, pulse-and-noise synthesis and the label front end.
+composition, spectral envelope decompression, pulse-and-noise synthesis, waveform analysis and the label front end.
 
 Argument checks, scratch memory and one C-ABI call (include/percival_hip.h) each; no autograd nodes, no switches, nothing
 of the training path (ops.py, which re-exports the names of __all__).  There is no CPU path.
@@ -21,6 +21,8 @@ __all__ = [
     'fwbnd2spec',
     'PULSE_MIN_DFTLEN', 'PULSE_MAX_DFTLEN', 'PULSE_F0_FLOOR', 'PULSE_INT_ROWS', 'pulse_check', 'pulse_table', 'noise_mask',
     'pulse_synthesis',
+    'COMPRESS_MEAN', 'COMPRESS_LSQ', 'ANALYSIS_NOISY_BELOW', 'analysis_check', 'f0_track', 'frame_harmonics', 'phase_coherence',
+    'fwbnd_compress_check', 'fwbnd_compress',
     'LABELS_MAX_LABEL', 'LABELS_CC_POINTS', 'LABELS_ANCHOR_START', 'LABELS_ANCHOR_END', 'LABELS_WILD', 'LABELS_CAPTURE_DIGITS',
     'LABELS_CAPTURE_DECIMAL', 'LABELS_ERR_DIGITS', 'LABELS_ERR_FORMAT', 'LABELS_MODES', 'LABELS_FEATURES', 'labels_match',
     'labels_expand',
@@ -482,6 +484,167 @@ def pulse_synthesis(spec, mask, table, noise, fs, dftlen, wavlen):
          stream(), tag=(P, dftlen, W))
     call('ptts_pulse_overlap_add', ptr(seg), ptr(it), P, W, ptr(wav), wavlen, stream(), tag=(P, W, wavlen))
     return wav
+
+
+# ----------------------------------------------------------------------------------------------
+# waveform analysis for the PML parameters (the first half of run.py:146-153 features_extraction): csrc/analysis.hip
+# ----------------------------------------------------------------------------------------------
+COMPRESS_MEAN, COMPRESS_LSQ = 0, 1                      # PTTS_COMPRESS_MEAN / PTTS_COMPRESS_LSQ
+ANALYSIS_NOISY_BELOW = math.exp(-0.75 ** 2 / 2)         # a harmonic is noisy where its phase coherence R lies below this
+_COMPRESS_MODES = {'mean': COMPRESS_MEAN, 'lsq': COMPRESS_LSQ}
+_band_weight_sums = {}      # (nb, fs, dftlen) -> the smallest sum_k W[k,b], on the host
+
+
+def analysis_check(dftlen, fs, shift, f0_min, f0_max):
+    """ValueError for parameters the analysis kernels do not take: dftlen / fs as pulse_check, a positive
+    shift, 0 < f0_min <= f0_max <= fs/6 (every frame has two harmonics) and a window at f0_min, 2 int(1.5 fs / f0_min) + 1 samples,
+    that fits dftlen.  Returns Hcap = floor((fs/2 - f0_min/2) / f0_min) - 1, the phasor columns of a frame.  Touches no device."""
+    pulse_check(dftlen, fs)
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('shift={} has to be positive'.format(shift))
+    fs, f0_min, f0_max = float(fs), float(f0_min), float(f0_max)
+    if not 0.0 < f0_min <= f0_max:
+        raise ValueError('f0_min={} and f0_max={} have to be positive and ordered'.format(f0_min, f0_max))
+    if f0_max > fs / 6.0:
+        raise ValueError('f0_max={} above fs/6 = {}: a frame needs two harmonics'.format(f0_max, fs / 6.0))
+    if 2 * int(1.5 * fs / f0_min) + 1 > dftlen:
+        raise ValueError('the window at f0_min={} ({} samples) does not fit dftlen={}'.format(
+            f0_min, 2 * int(1.5 * fs / f0_min) + 1, dftlen))
+    return int(math.floor((0.5 * fs - 0.5 * f0_min) / f0_min)) - 1
+
+
+def f0_track(f0, f0_min, f0_max, fs, shift, dftlen, wavlen=None):
+    """The host step of the analysis: f0 [T] in Hz, one value per frame at shift * i, values <= 0 unvoiced ->
+    float32 [T']: unvoiced stretches interpolated linearly between their voiced neighbours (the end values held), clipped to
+    [f0_min, f0_max] (a float32 never rounds out of the interval).  With `wavlen` the frames whose centre rnd(shift i fs) lies beyond
+    wavlen are cropped and a printed line says so.  ValueError: analysis_check, an empty or non-finite track, no voiced frame."""
+    analysis_check(dftlen, fs, shift, f0_min, f0_max)
+    f0 = np.asarray(f0, dtype=np.float64)
+    if f0.ndim != 1 or f0.size < 1 or not np.isfinite(f0).all():
+        raise ValueError('ops.f0_track: f0 has to be [T] finite Hz values, T >= 1')
+    voiced = f0 > 0
+    if not voiced.any():
+        raise ValueError('ops.f0_track: no voiced frame')
+    idx = np.arange(f0.size)
+    track = np.clip(np.interp(idx, idx[voiced], f0[voiced]), float(f0_min), float(f0_max))
+    out = track.astype(np.float32)
+    low, high = out.astype(np.float64) < float(f0_min), out.astype(np.float64) > float(f0_max)
+    out[low] = np.nextafter(out[low], np.float32(np.inf))
+    out[high] = np.nextafter(out[high], np.float32(-np.inf))
+    if wavlen is not None:
+        keep = sum(1 for i in range(out.size) if _rnd(i * float(shift) * float(fs)) <= int(wavlen))
+        if keep < out.size:
+            print('    f0_track: {} of {} frames lie beyond the {} samples of the waveform and are cropped'.format(
+                out.size - keep, out.size, int(wavlen)))
+            out = out[:keep]
+    return out
+
+
+def _compress_table(device, nb, fs, dftlen):
+    key = ('compress', device, nb, float(fs), dftlen)
+    tab = _spectrum_tables.get(key)
+    if tab is None:
+        fw, fwbytes = _fwbnd_table(device, nb, fs, bark_alpha(fs), dftlen)
+        n = _hip.lib().ptts_fwbnd_compress_table_bytes(nb)
+        tab = torch.empty(n // 8, dtype=torch.float64, device=device)
+        call('ptts_fwbnd_compress_table', ptr(tab), n, ptr(fw), fwbytes, nb, int(dftlen), stream(), tag=(nb, dftlen))
+        _spectrum_tables[key] = tab
+    return tab, tab.numel() * 8
+
+
+def fwbnd_compress_check(nb, fs, dftlen):
+    """ValueError for a band axis the compression cannot invert: with W[k,b] the weight with which fwbnd2spec reads band b at bin
+    k fs / dftlen, every band needs sum_k W[k,b] >= 1 (nb is too large for dftlen otherwise).  Host arithmetic, no device."""
+    if not 0.0 < float(fs) < 1e9:
+        raise ValueError('fs={} has to be positive'.format(fs))
+    spectrum_check(dftlen, bark_alpha(fs), 1.4)
+    if int(nb) != nb or not 2 <= nb <= SPECTRUM_MAX_NB:
+        raise ValueError('nb={} outside [2, {}]'.format(nb, SPECTRUM_MAX_NB))
+    key = (int(nb), float(fs), int(dftlen))
+    if key not in _band_weight_sums:
+        K = dftlen // 2 + 1
+        melmax = 1127.0 * math.log(1.0 + 0.5 * float(fs) / 700.0)
+        fb = 700.0 * (np.exp(np.arange(nb) * melmax / ((nb - 1) * 1127.0)) - 1.0)
+        f = np.arange(K) * float(fs) / dftlen
+        b = np.clip(np.searchsorted(fb, f, side='right') - 1, 0, nb - 2)
+        fr = np.clip((f - fb[b]) / (fb[b + 1] - fb[b]), 0.0, 1.0)
+        _band_weight_sums[key] = float((np.bincount(b, 1.0 - fr, nb) + np.bincount(b + 1, fr, nb)).min())
+    if _band_weight_sums[key] < 1.0:
+        raise ValueError('nb={} bands are too many for dftlen={} at fs={}: a band weighs {:.3f} bins, below 1'.format(
+            nb, dftlen, fs, _band_weight_sums[key]))
+
+
+def frame_harmonics(wav, f0, shift, fs, dftlen, hcap, log=False):
+    """wav [N] and f0 [T] (fp32 device; Hz, as ops.f0_track returns them, frame i at shift * i) -> (SPEC [T, dftlen/2+1], the
+    harmonic amplitude envelope, `log`: its logarithm; u [T, hcap, 2], the unit phasors of the phase distortion between neighbouring
+    harmonics), one workgroup per frame (csrc/analysis.hip).  hcap: what ops.analysis_check returns for the
+    f0_min of the track; a frame below that f0_min, or whose window does not fit dftlen, is left unwritten."""
+    pulse_check(dftlen, fs)
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('shift={} has to be positive'.format(shift))
+    if not torch.is_tensor(wav) or wav.dim() != 1 or wav.numel() >= 1 << 40:
+        raise ValueError('ops.frame_harmonics: wav is not [N]')
+    if not torch.is_tensor(f0) or f0.dim() != 1 or f0.numel() >= 1 << 31:
+        raise ValueError('ops.frame_harmonics: f0 is not [T]')
+    if int(hcap) != hcap or not 1 <= hcap <= dftlen:
+        raise ValueError('ops.frame_harmonics: hcap={} outside [1, {}]'.format(hcap, dftlen))
+    _no_backward('frame_harmonics', wav, f0)
+    f32c(wav, 'frame_harmonics.wav'); f32c(f0, 'frame_harmonics.f0')
+    T, K = f0.numel(), dftlen // 2 + 1
+    spec = torch.empty((T, K), dtype=torch.float32, device=f0.device)
+    u = torch.empty((T, int(hcap), 2), dtype=torch.float32, device=f0.device)
+    if T == 0:
+        return spec, u
+    call('ptts_frame_harmonics', ptr(wav) if wav.numel() else None, wav.numel(), ptr(f0), ptr(spec), ptr(u), T, int(hcap), float(shift),
+         float(fs), int(dftlen), int(bool(log)), stream(), tag=(T, dftlen, int(hcap)))
+    return spec, u
+
+
+def phase_coherence(u, f0, shift, fs, dftlen, nb):
+    """u [T, hcap, 2] from ops.frame_harmonics and f0 [T] (fp32 device) -> (R [T, hcap], the length of the mean phasor over the
+    frames within max(2, rnd(1 / (f0 shift))) of each frame, 1 behind a frame's harmonics; NM [T, nb], the hat-weighted share of
+    noisy bins (R < ANALYSIS_NOISY_BELOW) per band of the fwbnd2spec axis) (csrc/analysis.hip)."""
+    pulse_check(dftlen, fs)
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('shift={} has to be positive'.format(shift))
+    if not torch.is_tensor(u) or u.dim() != 3 or u.shape[2] != 2 or not 1 <= u.shape[1] <= dftlen:
+        raise ValueError('ops.phase_coherence: u is not [T, hcap, 2]')
+    T, hcap = u.shape[0], u.shape[1]
+    if not torch.is_tensor(f0) or tuple(f0.shape) != (T,):
+        raise ValueError('ops.phase_coherence: f0 is not [{}]'.format(T))
+    fwbnd_compress_check(nb, fs, dftlen)
+    _no_backward('phase_coherence', u, f0)
+    f32c(u, 'phase_coherence.u'); f32c(f0, 'phase_coherence.f0')
+    R = torch.empty((T, hcap), dtype=torch.float32, device=u.device)
+    nm = torch.empty((T, int(nb)), dtype=torch.float32, device=u.device)
+    if T == 0:
+        return R, nm
+    fw, fwbytes = _fwbnd_table(u.device, int(nb), fs, bark_alpha(fs), dftlen)
+    ct, ctbytes = _compress_table(u.device, int(nb), fs, dftlen)
+    call('ptts_phase_coherence', ptr(u), ptr(f0), ptr(R), ptr(nm), T, hcap, int(nb), float(shift), float(fs), int(dftlen), ptr(fw),
+         fwbytes, ptr(ct), ctbytes, stream(), tag=(T, hcap, int(nb)))
+    return R, nm
+
+
+def fwbnd_compress(x, fs, nb, mode='lsq', log=False):
+    """x [T,K] or [B,T,K] fp32 device, K = dftlen/2 + 1 bins -> [.., nb] on the band axis of fwbnd2spec (csrc/analysis.hip).
+    mode 'mean': the hat-weighted mean of x in each band.  mode 'lsq': the band values whose fwbnd2spec(log=True) is closest in least
+    squares to ln|x| (`log`: to x, which is a logarithm already); fwbnd_compress(fwbnd2spec(y)) = y up to rounding."""
+    if mode not in _COMPRESS_MODES:
+        raise ValueError("ops.fwbnd_compress: mode is 'mean' or 'lsq', got {!r}".format(mode))
+    if not torch.is_tensor(x) or x.dim() not in (2, 3) or x.shape[-1] < 5:
+        raise ValueError('ops.fwbnd_compress: expected a [T,K] or [B,T,K] tensor')
+    dftlen = 2 * (x.shape[-1] - 1)
+    fwbnd_compress_check(nb, fs, dftlen)
+    x, T, K = _spectrum_rows(x, 'fwbnd_compress', 5, SPECTRUM_MAX_DFTLEN // 2 + 1, 'K')
+    out = torch.empty(tuple(x.shape[:-1]) + (int(nb),), dtype=torch.float32, device=x.device)
+    if T == 0:
+        return out
+    fw, fwbytes = _fwbnd_table(x.device, int(nb), fs, bark_alpha(fs), dftlen)
+    ct, ctbytes = _compress_table(x.device, int(nb), fs, dftlen)
+    call('ptts_fwbnd_compress', ptr(x), ptr(out), T, int(nb), dftlen, _COMPRESS_MODES[mode], int(bool(log)), ptr(fw), fwbytes, ptr(ct),
+         ctbytes, stream(), tag=(T, int(nb), dftlen))
+    return out
 
 
 # ----------------------------------------------------------------------------------------------

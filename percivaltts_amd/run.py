@@ -1,8 +1,9 @@
 """Experiment script with the shape of the reference's percivaltts/run.py:57-230: a module-level `cfg`,
 `build_model()`, `training(cont)`, `generate()`.  The corpus-preparation stages of the reference
-split in two.  The vocoder analysis of features_extraction (run.py:147-154) needs the pulsemodel front end and is outside
-this build; `synthesize_corpus()` writes a synthetic corpus of the same on-disk format (headerless float32 `path:(-1,D)`
-files + file_id_list.scp) so that the training stages run unchanged.  `contexts_extraction()` is the reference's stage of
+split in two.  `features_extraction()` is the reference's stage of that name (run.py:147-165) with the build's own waveform
+analysis (VocoderPML.analysisfid_device) in the place of pulsemodel's and a caller's F0 tracks in the place of
+the REAPER binary; `synthesize_corpus()` writes a synthetic corpus of the same on-disk format (headerless float32 `path:(-1,D)`
+files + file_id_list.scp) so that the training stages run without recordings.  `contexts_extraction()` is the reference's stage of
 that name (run.py:168-180): HTS labels through the label normaliser (percivaltts_amd.external.merlin, on the device), the
 time weights from the labels, and the min-max normalised inputs `cfg.inpath` points at.  `features_compose()` is the
 composition half of the reference's features_extraction (run.py:155-165): from raw per-stream feature files it writes the time weights and the composed, normalised outputs `cfg.outpath` points at
@@ -100,6 +101,25 @@ def features_compose(rawpaths, fids=None, win_convention='mlpg'):
     normfn = compose.normalise_meanstd_nmnoscale if isinstance(vocoder, vocoders.VocoderPML) else compose.normalise_meanstd
     return compose.compose(outpaths, fids, cfg.outpath, id_valid_start=cfg.id_valid_start, normfn=normfn, wins=vocoder.mlpg_wins,
                            win_convention=win_convention)
+
+
+def features_extraction(f0in_path, wav_path=None, rawpaths=None, fids=None, f0_min=70, f0_max=600, win_convention='mlpg'):
+    """The reference's features_extraction (run.py:147-165): every file id's waveform `wav_path` ('dir/*.wav', by default
+    <corpus>/wav/*.wav) goes through vocoder.analysisfid_device with the F0 track of `f0in_path` ('dir/*.f0': headerless float32 Hz
+    values, one per frame, <= 0 unvoiced; the reference runs REAPER here, this build has no F0 tracker), which writes the raw
+    streams `rawpaths` = [f0_path, spec_path, noise_path] (by default the reference's places beside the waveforms); then
+    features_compose.  f0_min / f0_max default to the reference's cfg.vocoder_f0_min / cfg.vocoder_f0_max."""
+    fids = readids(cfg.fileids) if fids is None else fids
+    if not hasattr(vocoder, 'analysisfid_device'):
+        raise ValueError('features_extraction: {} has no waveform analysis in this build'.format(vocoder.name()))
+    wav_path = cp + 'wav/*.wav' if wav_path is None else wav_path
+    if rawpaths is None:
+        base = os.path.dirname(wav_path) + '_PML'
+        rawpaths = [base + '_lf0/*.lf0', base + '_fwlspec' + str(vocoder.specsize()) + '/*.fwlspec',
+                    base + '_fwnm' + str(vocoder.noisesize()) + '/*.fwnm']
+    for fid in fids:
+        vocoder.analysisfid_device(fid, wav_path, f0in_path, f0_min, f0_max, {'f0': rawpaths[0], 'spec': rawpaths[1], 'noise': rawpaths[2]})
+    return features_compose(rawpaths, fids=fids, win_convention=win_convention)
 
 
 def contexts_extraction(lab_path, fids, lab_questions, labbin_path, labs_wpath, inpath, lab_type='state', id_valid_start=-1,

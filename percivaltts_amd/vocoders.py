@@ -8,9 +8,14 @@ network_final switches on (networktts.py:195,212).  The objective measures of vo
 (`objmeasures_clear / objmeasures_add / objmeasures_stats`) are plain numpy on a few hundred kilobytes per utterance.
 `decompress_spectrum` (vocoders.py:147-166), the frame-wise step in front of the waveform generator, runs on the device
 (csrc/spectrum.hip).  `VocoderPML.synthesis_device` is the build's own pulse-and-noise synthesiser (csrc/pulsesynth.hip, DESIGN.md
-section 3); `synthesis` keeps its name for pulsemodel's waveform and keeps raising.
+section 3); `synthesis` keeps its name for pulsemodel's waveform and keeps raising.  `VocoderPML.analysis_device` (with
+`analysisf_device` / `analysisfid_device` around it) is the build's own waveform analysis for the same parameters
+(csrc/analysis.hip), from a caller's F0 track; `compress_spectrum` is the inverse of `decompress_spectrum` for
+'fwbnd'.  `analysisf` / `analysisfid` keep their names for pulsemodel's analysis and keep raising.
 """
 from __future__ import print_function
+
+import os
 
 import numpy as np
 
@@ -44,6 +49,24 @@ def wavwrite(path, wav, fs):
         f.writeframes(pcm.tobytes())
     finally:
         f.close()
+
+
+def wavread(path):
+    """A 16-bit mono PCM file -> (float64 waveform in [-1, 1], fs): the inverse of wavwrite.  Anything else is a ValueError."""
+    import wave
+    try:
+        f = wave.open(path, 'rb')
+    except (wave.Error, EOFError) as e:
+        raise ValueError('wavread: {} is not a PCM wave file ({})'.format(path, e))
+    try:
+        if f.getnchannels() != 1 or f.getsampwidth() != 2 or f.getcomptype() != 'NONE':
+            raise ValueError('wavread: {} is not 16-bit mono PCM ({} channels, {} bytes a sample)'.format(
+                path, f.getnchannels(), f.getsampwidth()))
+        fs = f.getframerate()
+        pcm = np.frombuffer(f.readframes(f.getnframes()), dtype='<i2')
+    finally:
+        f.close()
+    return pcm.astype(np.float64) / 32767.0, fs
 
 
 class Vocoder(object):
@@ -116,6 +139,27 @@ class VocoderF0Spec(Vocoder):
             SPEC = ops.mcep2spec(x.contiguous(), bark_alpha(self.fs), dftlen=self.dftlen, pp=pp_mcep)
         return SPEC.cpu().numpy() if as_numpy else SPEC
 
+    def compress_spectrum(self, SPEC, spec_type=None, spec_size=None):
+        """Amplitude envelope [T, K] -> compressed spectral columns [T, spec_size] (vocoders.py:134-145), on the device: 'fwbnd'
+        log-bands by the least-squares inverse of decompress_spectrum (ops.fwbnd_compress), so that
+        compress_spectrum(decompress_spectrum(y)) = y; dftlen is read off K = dftlen/2 + 1 as in the reference.  'mcep' is a
+        ValueError: the SPTK fit behind it is not built.  As in the reference the dispatch is on self.spec_type and the `spec_type`
+        argument is not looked at; spec_size None means self.spec_size.  numpy in -> numpy out, device tensor in -> device tensor
+        out."""
+        import torch
+        from . import backend_hip, ops_offline as ops
+        if self.spec_type == 'mcep':
+            raise ValueError("compress_spectrum: the 'mcep' fit (SPTK) is not part of this build")
+        if self.spec_type != 'fwbnd':
+            raise ValueError("spec_type is 'fwbnd' or 'mcep', got {!r}".format(self.spec_type))
+        spec_size = self.spec_size if spec_size is None else spec_size
+        as_numpy = not torch.is_tensor(SPEC)
+        x = SPEC
+        if as_numpy:
+            x = torch.from_numpy(np.ascontiguousarray(SPEC, dtype=np.float32)).to(backend_hip.device())
+        COMPSPEC = ops.fwbnd_compress(x.contiguous(), self.fs, spec_size, mode='lsq')
+        return COMPSPEC.cpu().numpy() if as_numpy else COMPSPEC
+
     def _objmeasures_add_f0spec(self, CMP, REF):
         """F0[Hz]: RMS of the exp(f0) differences; SPEC[dB]: per-band RMS of the log2db differences."""
         self.features_err.setdefault('F0[Hz]', []).append(np.sqrt(np.mean((np.exp(REF[:, 0]) - np.exp(CMP[:, 0]))**2)))
@@ -173,6 +217,62 @@ class VocoderPML(VocoderF0Spec):
         if noise is None:
             noise = ops.normal((wavlen,), device=x.device, i0=0)
         return ops.pulse_synthesis(SPEC, mask, table, noise, self.fs, self.dftlen, wavlen).cpu().numpy()
+
+    def analysis_device(self, wav, f0, f0_min, f0_max):
+        """A mono waveform at self.fs (any float array) and an F0 track in Hz, one value per frame at shift * i (<= 0: unvoiced) ->
+        the parameters [T, featuressizeraw()] float32, columns ln f0 | spec bands | noise-mask bands, by the build's own analysis
+        (DESIGN.md section 3): ops.f0_track on the host, then the harmonic envelope and the phase-distortion phasors of every frame
+        (ops.frame_harmonics), their coherence over neighbouring frames as the noise mask (ops.phase_coherence) and the least-squares
+        band compression of the envelope (ops.fwbnd_compress).  F0 estimation is the caller's.  The counterpart of
+        synthesis_device."""
+        import torch
+        from . import backend_hip, ops_offline as ops
+        if self.spec_type != 'fwbnd':
+            raise ValueError("analysis_device: spec_type {!r} is not built, only 'fwbnd'".format(self.spec_type))
+        hcap = ops.analysis_check(self.dftlen, self.fs, self.shift, f0_min, f0_max)
+        ops.fwbnd_compress_check(self.spec_size, self.fs, self.dftlen)
+        ops.fwbnd_compress_check(self.nm_size, self.fs, self.dftlen)
+        wav = np.asarray(wav, dtype=np.float64)
+        if wav.ndim != 1 or not np.isfinite(wav).all():
+            raise ValueError('analysis_device: wav is not a finite [N] waveform')
+        track = ops.f0_track(f0, f0_min, f0_max, self.fs, self.shift, self.dftlen, wavlen=wav.size)
+        dev = backend_hip.device()
+        w = torch.from_numpy(wav.astype(np.float32)).to(dev)
+        f = torch.from_numpy(track).to(dev)
+        lspec, u = ops.frame_harmonics(w, f, self.shift, self.fs, self.dftlen, hcap, log=True)
+        _, nm = ops.phase_coherence(u, f, self.shift, self.fs, self.dftlen, self.nm_size)
+        bands = ops.fwbnd_compress(lspec, self.fs, self.spec_size, mode='lsq', log=True)
+        lf0 = np.log(track.astype(np.float64)).astype(np.float32)
+        return np.concatenate([lf0[:, None], bands.cpu().numpy(), nm.cpu().numpy()], axis=1)
+
+    def analysisf_device(self, fwav, f0_in, ff0, f0_min, f0_max, fspec, fnm, **kwargs):
+        """analysis_device from file to files, where the reference's analysisf writes them (vocoders.py:181-189): fwav a 16-bit mono
+        wave file at self.fs (another fs is a ValueError: resampling is not built), f0_in a headerless float32 file, or an array, of
+        Hz values per frame; ff0 gets ln f0, fspec the spectral bands, fnm the noise-mask bands, headerless float32.  The one keyword
+        taken is preproc_hp=None: the high-pass filter is not built."""
+        if kwargs.get('preproc_hp') is not None:
+            raise ValueError('analysisf_device: preproc_hp={!r}: the high-pass pre-processing is not built'.format(kwargs['preproc_hp']))
+        if set(kwargs) - {'preproc_hp'}:
+            raise ValueError('analysisf_device: unknown arguments {}'.format(sorted(set(kwargs) - {'preproc_hp'})))
+        print('Extracting PML features from: ' + fwav)
+        wav, fs = wavread(fwav)
+        if fs != int(round(self.fs)):
+            raise ValueError('analysisf_device: {} is sampled at {} Hz, the vocoder at {} (resampling is not built)'.format(fwav, fs, self.fs))
+        f0 = np.fromfile(f0_in, dtype=np.float32) if isinstance(f0_in, str) else f0_in
+        CMP = self.analysis_device(wav, f0, f0_min, f0_max)
+        s1 = 1 + self.spec_size
+        for path, cols in ((ff0, CMP[:, 0]), (fspec, CMP[:, 1:s1]), (fnm, CMP[:, s1:])):
+            if os.path.dirname(path) and not os.path.isdir(os.path.dirname(path)):
+                os.makedirs(os.path.dirname(path))
+            np.ascontiguousarray(cols, dtype=np.float32).tofile(path)
+        return CMP.shape[0]
+
+    def analysisfid_device(self, fid, wav_path, f0in_path, f0_min, f0_max, outputpathdicts, **kwargs):
+        """analysisf_device with the '*' of every path replaced by the file id, as the reference's analysisfid
+        (vocoders.py:191-192); outputpathdicts: {'f0': .., 'spec': .., 'noise': ..}."""
+        return self.analysisf_device(wav_path.replace('*', fid), f0in_path.replace('*', fid), outputpathdicts['f0'].replace('*', fid),
+                                     f0_min, f0_max, outputpathdicts['spec'].replace('*', fid),
+                                     outputpathdicts['noise'].replace('*', fid), **kwargs)
 
 
 class VocoderWORLD(VocoderF0Spec):
