@@ -739,6 +739,47 @@ int ptts_fwbnd_compress(const float* x, float* out, int T, int nb, int dftlen, i
                         size_t fwtable_bytes, const double* ctable, size_t ctable_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * F0 estimation (csrc/f0.hip; the track the analysis above takes as `f0`; the definition is this
+ * build's own, DESIGN.md section 3, after Boersma 1993: the autocorrelation method with a path
+ * finder).  L = dftlen, rnd(x) = floor(x + 0.5).  fp32 in memory, fp64 arithmetic, every decision
+ * in fp64.  hw = int(1.5 fs / f0_min), W = 2 hw + 1, lmin = ceil(fs / f0_max),
+ * lmax = floor(fs / f0_min).
+ *
+ * ptts_f0_candidates: one workgroup per frame; L a power of two in 256 .. 8192 with
+ *   W + lmax + 1 <= L and 0 < f0_min <= f0_max <= fs/2 (anything else: PTTS_EINVAL without a
+ *   launch), ncand = 2 .. 16 slots.  The W samples of wav [N] around rnd(i shift fs) (none outside
+ *   [0, N) is read), less their mean, under w[j] = 0.5 - 0.5 cos(2 pi (j + 1) / (W + 1)); the power
+ *   spectrum weighted by G (1 up to 2.5 f0_max, a cos^2 roll-off to 0 at 3.75 f0_max) goes back to
+ *   the autocorrelation rho, r[k] = (rho[k] / rho[0]) / rw[k], k = 0 .. lmax + 1 (0 unless
+ *   rho[0] > 0).  rw [lmax + 2] fp64 is the CALLER's table of the window's own normalised
+ *   autocorrelation sum_j w[j] w[j+k] / sum_j w[j]^2 (device memory, 8-byte aligned; its contents
+ *   are not checked).  Slot 0 of a frame is the unvoiced candidate: freq 0, strength
+ *   voicing_threshold + max(0, 2 - (lpeak / gpeak) / (silence_threshold / (1 + voicing_threshold))),
+ *   lpeak the frame's largest |sample - mean|, gpeak the waveform's as the host measured it
+ *   (gpeak = 0: voicing_threshold + 2).  Slots 1 .. n_i are the lags k in [lmin, lmax] with
+ *   r[k] > r[k-1], r[k] >= r[k+1], r[k] > voicing_threshold / 2, refined by the parabola through
+ *   the three values to (tau, peak), F = 1 / tau within [f0_min, f0_max], strength
+ *   min(peak, 1) - octave_cost log2(f0_min tau): the ncand - 1 strongest, strongest first, ties to
+ *   the smaller lag.  Out: freq, strength [T, ncand] fp32, n [T] and lag [T, ncand] int32 (the
+ *   integer lag of a kept candidate), zeros in the slots behind n_i; r [T, lmax + 2] fp32 or NULL.
+ * ptts_f0_viterbi: one wave64 for the utterance.  cost_0[j] = -S[0,j], cost_i[j] = min_p
+ *   (cost_{i-1}[p] + (0.01 / shift) trans(p, j)) - S[i,j] over the slots 0 .. n_i (n clamped to
+ *   [0, ncand - 1]), ties to the smaller p; trans = 0 between unvoiced slots,
+ *   voiced_unvoiced_cost between a voiced and an unvoiced one, octave_jump_cost
+ *   |log2 F_p - log2 F_j| between voiced ones.  The cheapest slot of the last frame (ties to the
+ *   smaller) is followed back: f0 [T] = the chosen slot's freq, 0 for slot 0; path [T] int32 (or
+ *   NULL) = the slot.  Back-pointers live in LDS, so T <= ptts_f0_viterbi_max_frames(ncand)
+ *   (32768 up to ncand = 8, 16384 above; 0 for an ncand outside 2 .. 16): more is PTTS_EINVAL.
+ * T = 0 succeeds without a launch.
+ * ------------------------------------------------------------------------------------- */
+int ptts_f0_candidates(const float* wav, long long N, const double* rw, size_t rw_bytes, float* freq, float* strength, int* n,
+                       int* lag, float* r, int T, int ncand, double shift, double fs, int dftlen, double f0_min, double f0_max,
+                       double gpeak, double voicing_threshold, double silence_threshold, double octave_cost, void* stream);
+int ptts_f0_viterbi_max_frames(int ncand);
+int ptts_f0_viterbi(const float* freq, const float* strength, const int* n, float* f0, int* path, int T, int ncand, double shift,
+                    double octave_jump_cost, double voiced_unvoiced_cost, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Label front end (external/merlin/label_normalisation.py: pattern_matching_binary,
  * pattern_matching_continous_position, load_labels_with_state_alignment :661-710,
  * load_labels_with_phone_alignment :546-568): HTS full-context labels -> frame-level context rows.

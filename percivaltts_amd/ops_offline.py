@@ -1,5 +1,5 @@
 """Wrappers of the offline pipeline over the HIP kernels of libpercival_hip.so: parameter generation (MLPG), feature
-composition, spectral envelope decompression, pulse-and-noise synthesis, waveform analysis and the label front end.
+composition, spectral envelope decompression, pulse-and-noise synthesis, waveform analysis, F0 estimation and the label front end.
 
 Argument checks, scratch memory and one C-ABI call (include/percival_hip.h) each; no autograd nodes, no switches, nothing
 of the training path (ops.py, which re-exports the names of __all__).  There is no CPU path.
@@ -23,6 +23,8 @@ __all__ = [
     'pulse_synthesis',
     'COMPRESS_MEAN', 'COMPRESS_LSQ', 'ANALYSIS_NOISY_BELOW', 'analysis_check', 'f0_track', 'frame_harmonics', 'phase_coherence',
     'fwbnd_compress_check', 'fwbnd_compress',
+    'F0_MIN_NCAND', 'F0_MAX_NCAND', 'F0_MAX_FRAMES', 'F0_CONSTANTS', 'f0_check', 'f0_frame_count', 'f0_window_table', 'f0_candidates',
+    'f0_viterbi', 'f0_estimate',
     'LABELS_MAX_LABEL', 'LABELS_CC_POINTS', 'LABELS_ANCHOR_START', 'LABELS_ANCHOR_END', 'LABELS_WILD', 'LABELS_CAPTURE_DIGITS',
     'LABELS_CAPTURE_DECIMAL', 'LABELS_ERR_DIGITS', 'LABELS_ERR_FORMAT', 'LABELS_MODES', 'LABELS_FEATURES', 'labels_match',
     'labels_expand',
@@ -645,6 +647,178 @@ def fwbnd_compress(x, fs, nb, mode='lsq', log=False):
     call('ptts_fwbnd_compress', ptr(x), ptr(out), T, int(nb), dftlen, _COMPRESS_MODES[mode], int(bool(log)), ptr(fw), fwbytes, ptr(ct),
          ctbytes, stream(), tag=(T, int(nb), dftlen))
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# F0 estimation (the pitch tracker the reference runs in front of run.py:146-153 features_extraction): csrc/f0.hip
+# ----------------------------------------------------------------------------------------------
+F0_MIN_NCAND, F0_MAX_NCAND = 2, 16
+F0_MAX_FRAMES = 32768               # frames of one ptts_f0_viterbi launch (its back-pointers live in LDS); half of it above 8 slots
+F0_CONSTANTS = {'voicing_threshold': 0.45, 'silence_threshold': 0.03, 'octave_cost': 0.01, 'octave_jump_cost': 0.35,
+                'voiced_unvoiced_cost': 0.14}
+_f0_window_tables = {}      # (fs, f0_min) -> rw on the host
+
+
+def f0_check(dftlen, fs, shift, f0_min, f0_max):
+    """ValueError for parameters the F0 kernels do not take: analysis_check, and the window at f0_min,
+    W = 2 int(1.5 fs / f0_min) + 1 samples, with its longest lag lmax = floor(fs / f0_min) has to fit: W + lmax + 1 <= dftlen.
+    Returns (hw, lmin, lmax) = (int(1.5 fs / f0_min), ceil(fs / f0_max), floor(fs / f0_min)).  Touches no device."""
+    analysis_check(dftlen, fs, shift, f0_min, f0_max)
+    fs, f0_min, f0_max = float(fs), float(f0_min), float(f0_max)
+    hw, lmin, lmax = int(1.5 * fs / f0_min), int(math.ceil(fs / f0_max)), int(math.floor(fs / f0_min))
+    if 2 * hw + 1 + lmax + 1 > dftlen:
+        raise ValueError('the window at f0_min={} ({} samples) and its longest lag ({}) do not fit dftlen={}'.format(
+            f0_min, 2 * hw + 1, lmax, dftlen))
+    return hw, lmin, lmax
+
+
+def f0_frame_count(wavlen, shift, fs):
+    """The number of frames i >= 0 whose centre rnd(i shift fs) is at most wavlen: the cropping rule of f0_track."""
+    wavlen, step = int(wavlen), float(shift) * float(fs)
+    if wavlen < 0 or not 0.0 < float(shift) < 1e3 or not 0.0 < float(fs) < 1e9:
+        raise ValueError('ops.f0_frame_count: wavlen={} shift={} fs={}'.format(wavlen, shift, fs))
+    T = int(wavlen / step) + 2
+    while T > 0 and _rnd((T - 1) * float(shift) * float(fs)) > wavlen:
+        T -= 1
+    while _rnd(T * float(shift) * float(fs)) <= wavlen:
+        T += 1
+    return T
+
+
+def f0_window_table(fs, f0_min, f0_max, device=None):
+    """rw [lmax + 2] fp64, the normalised autocorrelation sum_j w[j] w[j+k] / sum_j w[j]^2 of the F0 window
+    w[j] = 0.5 - 0.5 cos(2 pi (j + 1) / (W + 1)), built on the host once per (fs, f0_min) and kept: a numpy array, or with `device`
+    the device tensor ptts_f0_candidates reads."""
+    fs, f0_min, f0_max = float(fs), float(f0_min), float(f0_max)
+    if not (0.0 < fs < 1e9 and 0.0 < f0_min <= f0_max <= fs / 2.0) or 1.5 * fs / f0_min > SPECTRUM_MAX_DFTLEN:
+        raise ValueError('ops.f0_window_table: fs={} f0_min={} f0_max={}'.format(fs, f0_min, f0_max))
+    key = (fs, f0_min)
+    if key not in _f0_window_tables:
+        W, lmax = 2 * int(1.5 * fs / f0_min) + 1, int(math.floor(fs / f0_min))
+        w = 0.5 - 0.5 * np.cos(2.0 * np.pi * (np.arange(W) + 1.0) / (W + 1.0))
+        rw = np.array([np.dot(w[:W - k], w[k:]) for k in range(lmax + 2)]) / np.dot(w, w)
+        rw.setflags(write=False)
+        _f0_window_tables[key] = rw
+    if device is None:
+        return _f0_window_tables[key]
+    dkey = ('f0window', device, fs, f0_min)
+    if dkey not in _spectrum_tables:
+        _spectrum_tables[dkey] = torch.from_numpy(_f0_window_tables[key].copy()).to(device)
+    return _spectrum_tables[dkey]
+
+
+def _f0_number(fn, name, value, lo, hi, open_lo=True):
+    v = float(value)
+    if not ((lo < v if open_lo else lo <= v) and v < hi):
+        raise ValueError('ops.{}: {}={} outside {}{}, {})'.format(fn, name, value, '(' if open_lo else '[', lo, hi))
+    return v
+
+
+def _f0_ncand(fn, ncand):
+    if int(ncand) != ncand or not F0_MIN_NCAND <= ncand <= F0_MAX_NCAND:
+        raise ValueError('ops.{}: ncand={} outside [{}, {}]'.format(fn, ncand, F0_MIN_NCAND, F0_MAX_NCAND))
+    return int(ncand)
+
+
+def f0_candidates(wav, T, shift, fs, dftlen, f0_min, f0_max, gpeak, ncand=8, voicing_threshold=F0_CONSTANTS['voicing_threshold'],
+                  silence_threshold=F0_CONSTANTS['silence_threshold'], octave_cost=F0_CONSTANTS['octave_cost'], want_r=False):
+    """wav [N] (fp32 device) -> the pitch candidates of T frames, frame i centred at rnd(i shift fs), one workgroup per frame
+    (csrc/f0.hip): (freq [T, ncand] Hz, strength [T, ncand], n [T] int32, lag [T, ncand] int32), with `want_r`
+    also r [T, lmax + 2], the frame's normalised autocorrelation.  Slot 0 is the unvoiced candidate, slots 1 .. n_i the strongest
+    peaks of r within [f0_min, f0_max], strongest first; gpeak: max |wav - mean(wav)| of the whole waveform, measured by the caller
+    in fp64."""
+    _, _, lmax = f0_check(dftlen, fs, shift, f0_min, f0_max)
+    ncand = _f0_ncand('f0_candidates', ncand)
+    if not torch.is_tensor(wav) or wav.dim() != 1 or wav.numel() >= 1 << 40:
+        raise ValueError('ops.f0_candidates: wav is not [N]')
+    if int(T) != T or not 0 <= T < 1 << 31 or T * (lmax + 2) >= 1 << 40:
+        raise ValueError('ops.f0_candidates: T={} frames'.format(T))
+    gpeak = _f0_number('f0_candidates', 'gpeak', gpeak, 0.0, float('inf'), open_lo=False)
+    vt = _f0_number('f0_candidates', 'voicing_threshold', voicing_threshold, 0.0, 1e3)
+    st = _f0_number('f0_candidates', 'silence_threshold', silence_threshold, 0.0, 1e3)
+    oc = _f0_number('f0_candidates', 'octave_cost', octave_cost, 0.0, 1e3, open_lo=False)
+    _no_backward('f0_candidates', wav)
+    f32c(wav, 'f0_candidates.wav')
+    T, dev = int(T), wav.device
+    freq = torch.empty((T, ncand), dtype=torch.float32, device=dev)
+    strength = torch.empty((T, ncand), dtype=torch.float32, device=dev)
+    n = torch.empty(T, dtype=torch.int32, device=dev)
+    lag = torch.empty((T, ncand), dtype=torch.int32, device=dev)
+    r = torch.empty((T, lmax + 2), dtype=torch.float32, device=dev) if want_r else None
+    if T > 0:
+        rw = f0_window_table(fs, f0_min, f0_max, device=dev)
+        call('ptts_f0_candidates', ptr(wav) if wav.numel() else None, wav.numel(), ptr(rw), rw.numel() * 8, ptr(freq), ptr(strength),
+             ptr(n), ptr(lag), ptr(r), T, ncand, float(shift), float(fs), int(dftlen), float(f0_min), float(f0_max), gpeak, vt, st, oc,
+             stream(), tag=(T, int(dftlen), ncand))
+    return (freq, strength, n, lag, r) if want_r else (freq, strength, n, lag)
+
+
+def f0_viterbi(freq, strength, n, shift, octave_jump_cost=F0_CONSTANTS['octave_jump_cost'],
+               voiced_unvoiced_cost=F0_CONSTANTS['voiced_unvoiced_cost'], want_path=False):
+    """The candidate tables of ops.f0_candidates (freq, strength [T, ncand] fp32, n [T] int32, device) -> f0 [T] fp32 device, the
+    frequencies along the cheapest path through the slots, 0 where it takes the unvoiced slot 0 (csrc/f0.hip, DESIGN.md section 3;
+    one wave for the utterance); with `want_path` also the slots [T] int32.  T is at most F0_MAX_FRAMES (half of it above 8 slots):
+    the back-pointers live in LDS."""
+    if not torch.is_tensor(freq) or freq.dim() != 2:
+        raise ValueError('ops.f0_viterbi: freq is not [T, ncand]')
+    T, ncand = freq.shape[0], _f0_ncand('f0_viterbi', freq.shape[1])
+    if not torch.is_tensor(strength) or tuple(strength.shape) != (T, ncand):
+        raise ValueError('ops.f0_viterbi: strength is not [{},{}]'.format(T, ncand))
+    if not torch.is_tensor(n) or tuple(n.shape) != (T,):
+        raise ValueError('ops.f0_viterbi: n is not [{}]'.format(T))
+    cap = F0_MAX_FRAMES if ncand <= 8 else F0_MAX_FRAMES // 2
+    if T > cap:
+        raise ValueError('ops.f0_viterbi: {} frames, one launch takes at most {} with ncand={}'.format(T, cap, ncand))
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('shift={} has to be positive'.format(shift))
+    ojc = _f0_number('f0_viterbi', 'octave_jump_cost', octave_jump_cost, 0.0, 1e3, open_lo=False)
+    vuc = _f0_number('f0_viterbi', 'voiced_unvoiced_cost', voiced_unvoiced_cost, 0.0, 1e3, open_lo=False)
+    _no_backward('f0_viterbi', freq, strength)
+    f32c(freq, 'f0_viterbi.freq'); f32c(strength, 'f0_viterbi.strength')
+    _dev_tensor(n, torch.int32, 'f0_viterbi.n')
+    f0 = torch.empty(T, dtype=torch.float32, device=freq.device)
+    path = torch.empty(T, dtype=torch.int32, device=freq.device) if want_path else None
+    if T > 0:
+        call('ptts_f0_viterbi', ptr(freq), ptr(strength), ptr(n), ptr(f0), ptr(path), T, ncand, float(shift), ojc, vuc, stream(),
+             tag=(T, ncand))
+    return (f0, path) if want_path else f0
+
+
+def f0_estimate(wav, shift, fs, dftlen, f0_min, f0_max, ncand=8, **constants):
+    """A mono waveform at fs (any float array, or an fp32 device tensor) -> f0 [T] in Hz, numpy float32, one value per frame at
+    shift * i, 0 where unvoiced: what ops.f0_track and the .f0 files mean.  T = f0_frame_count(len(wav), shift, fs).  The build's
+    own estimator (after Boersma 1993): ops.f0_candidates, then ops.f0_viterbi; `constants`: any of
+    F0_CONSTANTS."""
+    if set(constants) - set(F0_CONSTANTS):
+        raise ValueError('ops.f0_estimate: unknown arguments {}'.format(sorted(set(constants) - set(F0_CONSTANTS))))
+    f0_check(dftlen, fs, shift, f0_min, f0_max)
+    ncand = _f0_ncand('f0_estimate', ncand)
+    if torch.is_tensor(wav):
+        if wav.dim() != 1:
+            raise ValueError('ops.f0_estimate: wav is not [N]')
+        _no_backward('f0_estimate', wav)
+        N = wav.numel()
+    else:
+        wav = np.asarray(wav, dtype=np.float64)
+        if wav.ndim != 1 or not np.isfinite(wav).all():
+            raise ValueError('ops.f0_estimate: wav is not a finite [N] waveform')
+        N = wav.size
+    T = f0_frame_count(N, shift, fs)
+    cap = F0_MAX_FRAMES if ncand <= 8 else F0_MAX_FRAMES // 2
+    if T > cap:
+        raise ValueError('ops.f0_estimate: {} frames, one utterance takes at most {} with ncand={}'.format(T, cap, ncand))
+    if not torch.is_tensor(wav):
+        from . import backend_hip
+        wav = torch.from_numpy(wav.astype(np.float32)).to(backend_hip.device())
+    f32c(wav, 'f0_estimate.wav')
+    x = wav.to(torch.float64)                                   # gpeak in fp64 from the fp32 samples the kernel reads
+    gpeak = float((x - x.mean()).abs().max().item()) if N else 0.0
+    if not math.isfinite(gpeak):
+        raise ValueError('ops.f0_estimate: wav is not finite')
+    cand = {k: constants[k] for k in ('voicing_threshold', 'silence_threshold', 'octave_cost') if k in constants}
+    path = {k: constants[k] for k in ('octave_jump_cost', 'voiced_unvoiced_cost') if k in constants}
+    freq, strength, n, _ = f0_candidates(wav, T, shift, fs, dftlen, f0_min, f0_max, gpeak, ncand=ncand, **cand)
+    return f0_viterbi(freq, strength, n, shift, **path).cpu().numpy()
 
 
 # ----------------------------------------------------------------------------------------------

@@ -1,8 +1,9 @@
 """Experiment script with the shape of the reference's percivaltts/run.py:57-230: a module-level `cfg`,
 `build_model()`, `training(cont)`, `generate()`.  The corpus-preparation stages of the reference
 split in two.  `features_extraction()` is the reference's stage of that name (run.py:147-165) with the build's own waveform
-analysis (VocoderPML.analysisfid_device) in the place of pulsemodel's and a caller's F0 tracks in the place of
-the REAPER binary; `synthesize_corpus()` writes a synthetic corpus of the same on-disk format (headerless float32 `path:(-1,D)`
+analysis (VocoderPML.analysisfid_device) in the place of pulsemodel's and the build's own F0 estimator (or a
+caller's F0 tracks) in the place of the REAPER binary; `synthesize_corpus()` writes a synthetic corpus of the same on-disk
+format (headerless float32 `path:(-1,D)`
 files + file_id_list.scp) so that the training stages run without recordings.  `contexts_extraction()` is the reference's stage of
 that name (run.py:168-180): HTS labels through the label normaliser (percivaltts_amd.external.merlin, on the device), the
 time weights from the labels, and the min-max normalised inputs `cfg.inpath` points at.  `features_compose()` is the
@@ -103,10 +104,11 @@ def features_compose(rawpaths, fids=None, win_convention='mlpg'):
                            win_convention=win_convention)
 
 
-def features_extraction(f0in_path, wav_path=None, rawpaths=None, fids=None, f0_min=70, f0_max=600, win_convention='mlpg'):
+def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None, f0_min=70, f0_max=600, win_convention='mlpg'):
     """The reference's features_extraction (run.py:147-165): every file id's waveform `wav_path` ('dir/*.wav', by default
     <corpus>/wav/*.wav) goes through vocoder.analysisfid_device with the F0 track of `f0in_path` ('dir/*.f0': headerless float32 Hz
-    values, one per frame, <= 0 unvoiced; the reference runs REAPER here, this build has no F0 tracker), which writes the raw
+    values, one per frame, <= 0 unvoiced) or, with f0in_path None, the track of the build's own estimator
+    (vocoder.f0_estimate_device; the reference runs REAPER here), which writes the raw
     streams `rawpaths` = [f0_path, spec_path, noise_path] (by default the reference's places beside the waveforms); then
     features_compose.  f0_min / f0_max default to the reference's cfg.vocoder_f0_min / cfg.vocoder_f0_max."""
     fids = readids(cfg.fileids) if fids is None else fids

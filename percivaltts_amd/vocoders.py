@@ -10,8 +10,9 @@ network_final switches on (networktts.py:195,212).  The objective measures of vo
 (csrc/spectrum.hip).  `VocoderPML.synthesis_device` is the build's own pulse-and-noise synthesiser (csrc/pulsesynth.hip, DESIGN.md
 section 3); `synthesis` keeps its name for pulsemodel's waveform and keeps raising.  `VocoderPML.analysis_device` (with
 `analysisf_device` / `analysisfid_device` around it) is the build's own waveform analysis for the same parameters
-(csrc/analysis.hip), from a caller's F0 track; `compress_spectrum` is the inverse of `decompress_spectrum` for
-'fwbnd'.  `analysisf` / `analysisfid` keep their names for pulsemodel's analysis and keep raising.
+(csrc/analysis.hip), from a caller's F0 track or, without one, from the build's own F0 estimator
+(`VocoderF0Spec.f0_estimate_device`, csrc/f0.hip); `compress_spectrum` is the inverse of `decompress_spectrum` for 'fwbnd'.
+`analysisf` / `analysisfid` keep their names for pulsemodel's analysis and keep raising.
 """
 from __future__ import print_function
 
@@ -160,6 +161,13 @@ class VocoderF0Spec(Vocoder):
         COMPSPEC = ops.fwbnd_compress(x.contiguous(), self.fs, spec_size, mode='lsq')
         return COMPSPEC.cpu().numpy() if as_numpy else COMPSPEC
 
+    def f0_estimate_device(self, wav, f0_min, f0_max):
+        """A mono waveform at self.fs (any float array) -> its F0 track in Hz, numpy float32, one value per frame at shift * i for
+        every frame whose centre lies within the waveform, 0 where unvoiced: the build's own estimator (ops.f0_estimate, csrc/f0.hip,
+        DESIGN.md section 3) in the place of the pitch tracker the reference runs."""
+        from . import ops_offline as ops
+        return ops.f0_estimate(wav, self.shift, self.fs, self.dftlen, f0_min, f0_max)
+
     def _objmeasures_add_f0spec(self, CMP, REF):
         """F0[Hz]: RMS of the exp(f0) differences; SPEC[dB]: per-band RMS of the log2db differences."""
         self.features_err.setdefault('F0[Hz]', []).append(np.sqrt(np.mean((np.exp(REF[:, 0]) - np.exp(CMP[:, 0]))**2)))
@@ -219,12 +227,12 @@ class VocoderPML(VocoderF0Spec):
         return ops.pulse_synthesis(SPEC, mask, table, noise, self.fs, self.dftlen, wavlen).cpu().numpy()
 
     def analysis_device(self, wav, f0, f0_min, f0_max):
-        """A mono waveform at self.fs (any float array) and an F0 track in Hz, one value per frame at shift * i (<= 0: unvoiced) ->
-        the parameters [T, featuressizeraw()] float32, columns ln f0 | spec bands | noise-mask bands, by the build's own analysis
+        """A mono waveform at self.fs (any float array) and an F0 track in Hz, one value per frame at shift * i (<= 0: unvoiced;
+        None: the track of f0_estimate_device) -> the parameters [T, featuressizeraw()] float32, columns ln f0 | spec bands |
+        noise-mask bands, by the build's own analysis
         (DESIGN.md section 3): ops.f0_track on the host, then the harmonic envelope and the phase-distortion phasors of every frame
         (ops.frame_harmonics), their coherence over neighbouring frames as the noise mask (ops.phase_coherence) and the least-squares
-        band compression of the envelope (ops.fwbnd_compress).  F0 estimation is the caller's.  The counterpart of
-        synthesis_device."""
+        band compression of the envelope (ops.fwbnd_compress).  The counterpart of synthesis_device."""
         import torch
         from . import backend_hip, ops_offline as ops
         if self.spec_type != 'fwbnd':
@@ -235,6 +243,8 @@ class VocoderPML(VocoderF0Spec):
         wav = np.asarray(wav, dtype=np.float64)
         if wav.ndim != 1 or not np.isfinite(wav).all():
             raise ValueError('analysis_device: wav is not a finite [N] waveform')
+        if f0 is None:
+            f0 = self.f0_estimate_device(wav, f0_min, f0_max)
         track = ops.f0_track(f0, f0_min, f0_max, self.fs, self.shift, self.dftlen, wavlen=wav.size)
         dev = backend_hip.device()
         w = torch.from_numpy(wav.astype(np.float32)).to(dev)
@@ -248,7 +258,8 @@ class VocoderPML(VocoderF0Spec):
     def analysisf_device(self, fwav, f0_in, ff0, f0_min, f0_max, fspec, fnm, **kwargs):
         """analysis_device from file to files, where the reference's analysisf writes them (vocoders.py:181-189): fwav a 16-bit mono
         wave file at self.fs (another fs is a ValueError: resampling is not built), f0_in a headerless float32 file, or an array, of
-        Hz values per frame; ff0 gets ln f0, fspec the spectral bands, fnm the noise-mask bands, headerless float32.  The one keyword
+        Hz values per frame, or None for the build's own estimate; ff0 gets ln f0, fspec the spectral bands, fnm the noise-mask
+        bands, headerless float32.  The one keyword
         taken is preproc_hp=None: the high-pass filter is not built."""
         if kwargs.get('preproc_hp') is not None:
             raise ValueError('analysisf_device: preproc_hp={!r}: the high-pass pre-processing is not built'.format(kwargs['preproc_hp']))
@@ -269,8 +280,9 @@ class VocoderPML(VocoderF0Spec):
 
     def analysisfid_device(self, fid, wav_path, f0in_path, f0_min, f0_max, outputpathdicts, **kwargs):
         """analysisf_device with the '*' of every path replaced by the file id, as the reference's analysisfid
-        (vocoders.py:191-192); outputpathdicts: {'f0': .., 'spec': .., 'noise': ..}."""
-        return self.analysisf_device(wav_path.replace('*', fid), f0in_path.replace('*', fid), outputpathdicts['f0'].replace('*', fid),
+        (vocoders.py:191-192); outputpathdicts: {'f0': .., 'spec': .., 'noise': ..}; f0in_path None: the build's own F0 estimate."""
+        f0_in = None if f0in_path is None else f0in_path.replace('*', fid)
+        return self.analysisf_device(wav_path.replace('*', fid), f0_in, outputpathdicts['f0'].replace('*', fid),
                                      f0_min, f0_max, outputpathdicts['spec'].replace('*', fid),
                                      outputpathdicts['noise'].replace('*', fid), **kwargs)
 
