@@ -780,6 +780,45 @@ int ptts_f0_viterbi(const float* freq, const float* strength, const int* n, floa
                     double octave_jump_cost, double voiced_unvoiced_cost, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Waveform pre-processing (csrc/preproc.hip; the reference's Vocoder.preprocwav,
+ * vocoders.py:45-63; both definitions are this build's own).  fp32 in
+ * memory, fp64 arithmetic, one rounding per sample.  Both entry points take a packed batch:
+ * utterance u is the samples off[u] .. off[u+1] of one array, the offsets [n_utts + 1] 64-bit
+ * in DEVICE memory, the totals as the host measured them; an utterance whose offsets do not lie
+ * inside the totals is skipped, nothing of it is read or written.  n_utts <= 65535.  No
+ * atomics, nothing between workgroups, no device allocation; an utterance's result does not
+ * depend on what else is in the launch.
+ *
+ * ptts_resample: up = fs_out / gcd, down = fs_in / gcd, up <= 1024; h [up][2 hw] fp64 is the
+ *   CALLER's table (device memory, at most 4 MiB) of the Kaiser-windowed sinc, row p column
+ *   j + hw - 1 = h(p / up - j), j = -hw + 1 .. hw.  Utterance u of N samples gives
+ *   M = (N up + down - 1) div down samples (no more than y_off[u+1] - y_off[u] are written):
+ *   y[m] = sum_j h[p][j] x[q + j], q = (m down) div up, p = (m down) mod up, x = 0 outside
+ *   [0, N), summed in increasing j.  max_out: the longest output of the batch (the grid).  One
+ *   thread per output sample.  n_utts = 0 or max_out = 0 succeeds without a launch.
+ * ptts_highpass_zerophase: the order-4 Butterworth high-pass at fc (fs / 4000 <= fc < fs / 2) as
+ *   two second-order sections, K = tan(pi fc / fs), Q = 1 / (2 cos(pi / 8)), 1 / (2 cos(3 pi / 8)),
+ *   n = 1 / (1 + K / Q + K^2), b = (n, -2 n, n), a1 = 2 (K^2 - 1) n, a2 = (1 - K / Q + K^2) n
+ *   (ptts_highpass_sections writes them as sos [2][6] = b0 b1 b2 1 a1 a2, on the host), run
+ *   forward and backward over the signal with padlen samples of odd extension at both ends
+ *   (every utterance longer than padlen, else it is skipped), each pass starting from the steady
+ *   state of its first sample: scipy.signal.sosfiltfilt(sos, x, padtype='odd', padlen=padlen).
+ *   y may not overlap x.  One workgroup per utterance walks it in tiles of
+ *   ptts_highpass_tile()'s `tile` samples, a lane owning `chunk` consecutive ones; the signal
+ *   between the passes is fp64 in the workspace, ptts_highpass_workspace_bytes(total, n_utts,
+ *   padlen) = 8 (total + 2 padlen n_utts) bytes (0 for arguments out of range), 8-byte aligned; a
+ *   shorter one is PTTS_EINVAL.  n_utts = 0 or total = 0 succeeds without a launch.
+ * ------------------------------------------------------------------------------------- */
+int ptts_resample(const float* x, const long long* x_off, long long total_in, float* y, const long long* y_off,
+                  long long total_out, long long max_out, int n_utts, const double* h, size_t h_bytes, int up, int down, int hw,
+                  void* stream);
+int ptts_highpass_tile(int* chunk, int* tile);
+int ptts_highpass_sections(double fs, double fc, double* sos);
+size_t ptts_highpass_workspace_bytes(long long total, int n_utts, int padlen);
+int ptts_highpass_zerophase(const float* x, float* y, const long long* off, long long total, int n_utts, double fs, double fc,
+                            int padlen, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Label front end (external/merlin/label_normalisation.py: pattern_matching_binary,
  * pattern_matching_continous_position, load_labels_with_state_alignment :661-710,
  * load_labels_with_phone_alignment :546-568): HTS full-context labels -> frame-level context rows.

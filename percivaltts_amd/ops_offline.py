@@ -1,5 +1,5 @@
 """Wrappers of the offline pipeline over the HIP kernels of libpercival_hip.so: parameter generation (MLPG), feature
-composition, spectral envelope decompression, pulse-and-noise synthesis, waveform analysis, F0 estimation and the label front end.
+composition, spectral envelope decompression, pulse-and-noise synthesis, waveform analysis, F0 estimation, waveform pre-processing and the label front end.
 
 Argument checks, scratch memory and one C-ABI call (include/percival_hip.h) each; no autograd nodes, no switches, nothing
 of the training path (ops.py, which re-exports the names of __all__).  There is no CPU path.
@@ -25,6 +25,8 @@ __all__ = [
     'fwbnd_compress_check', 'fwbnd_compress',
     'F0_MIN_NCAND', 'F0_MAX_NCAND', 'F0_MAX_FRAMES', 'F0_CONSTANTS', 'f0_check', 'f0_frame_count', 'f0_window_table', 'f0_candidates',
     'f0_viterbi', 'f0_estimate',
+    'RESAMPLE_MAX_UP', 'RESAMPLE_MAX_TABLE_BYTES', 'HIGHPASS_PADLEN', 'HIGHPASS_MAX_PADLEN', 'PREPROC_MAX_UTTS', 'preproc_check',
+    'resample_length', 'resample_table', 'resample', 'highpass_tile', 'highpass_zerophase',
     'LABELS_MAX_LABEL', 'LABELS_CC_POINTS', 'LABELS_ANCHOR_START', 'LABELS_ANCHOR_END', 'LABELS_WILD', 'LABELS_CAPTURE_DIGITS',
     'LABELS_CAPTURE_DECIMAL', 'LABELS_ERR_DIGITS', 'LABELS_ERR_FORMAT', 'LABELS_MODES', 'LABELS_FEATURES', 'labels_match',
     'labels_expand',
@@ -819,6 +821,147 @@ def f0_estimate(wav, shift, fs, dftlen, f0_min, f0_max, ncand=8, **constants):
     path = {k: constants[k] for k in ('octave_jump_cost', 'voiced_unvoiced_cost') if k in constants}
     freq, strength, n, _ = f0_candidates(wav, T, shift, fs, dftlen, f0_min, f0_max, gpeak, ncand=ncand, **cand)
     return f0_viterbi(freq, strength, n, shift, **path).cpu().numpy()
+
+
+# ----------------------------------------------------------------------------------------------
+# waveform pre-processing (vocoders.py:45-63 preprocwav): csrc/preproc.hip
+# ----------------------------------------------------------------------------------------------
+RESAMPLE_MAX_UP = 1024                      # rows of the resampler's table
+RESAMPLE_MAX_TABLE_BYTES = 4 << 20
+RESAMPLE_ZEROS, RESAMPLE_CUTOFF, RESAMPLE_BETA = 16, 0.95, 9.0
+HIGHPASS_PADLEN = 15                        # the default odd extension, samples at each end
+HIGHPASS_MAX_PADLEN = 1 << 20
+HIGHPASS_MIN_FC_RATIO = 1.0 / 4000.0        # fc >= fs / 4000: where the blocked recurrence was checked against the sequential one
+PREPROC_MAX_UTTS = 65535                    # utterances of one launch
+_resample_tables = {}       # (up, down) -> h [up, 2 hw] on the host
+
+
+def _rate(fn, name, value):
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or value != int(value) or not 0 < value < 1 << 30:
+        raise ValueError('ops.{}: {}={!r} is not a positive integer rate'.format(fn, name, value))
+    return int(value)
+
+
+def preproc_check(fs_in, fs_out, fc=None, padlen=HIGHPASS_PADLEN):
+    """ValueError for parameters the pre-processing kernels do not take: the rates positive integers with
+    up = fs_out / gcd at most RESAMPLE_MAX_UP and a table of at most RESAMPLE_MAX_TABLE_BYTES; with `fc`, the high-pass cut-off in Hz,
+    fs_out / 4000 <= fc < fs_out / 2 and padlen an integer in [0, HIGHPASS_MAX_PADLEN].  Returns (up, down, hw), hw = the half width
+    of the resampler's window in input samples.  Touches no device."""
+    fs_in, fs_out = _rate('preproc_check', 'fs_in', fs_in), _rate('preproc_check', 'fs_out', fs_out)
+    g = math.gcd(fs_in, fs_out)
+    up, down = fs_out // g, fs_in // g
+    hw = int(math.ceil(RESAMPLE_ZEROS / (RESAMPLE_CUTOFF * min(1.0, up / float(down)))))
+    if up > RESAMPLE_MAX_UP or up * 2 * hw * 8 > RESAMPLE_MAX_TABLE_BYTES:
+        raise ValueError('resampling {} -> {} Hz needs a table of {} x {} taps: at most {} rows and {} bytes'.format(
+            fs_in, fs_out, up, 2 * hw, RESAMPLE_MAX_UP, RESAMPLE_MAX_TABLE_BYTES))
+    if fc is not None:
+        if isinstance(fc, (str, bool)) or not fs_out * HIGHPASS_MIN_FC_RATIO <= float(fc) < fs_out / 2.0:
+            raise ValueError('the high-pass cut-off {!r} Hz is outside [fs / 4000, fs / 2) at fs={}'.format(fc, fs_out))
+        if isinstance(padlen, bool) or int(padlen) != padlen or not 0 <= padlen <= HIGHPASS_MAX_PADLEN:
+            raise ValueError('padlen={!r} is not an integer in [0, {}]'.format(padlen, HIGHPASS_MAX_PADLEN))
+    return up, down, hw
+
+
+def resample_length(N, up, down):
+    """Samples that N input samples give: ceil(N up / down)."""
+    return (int(N) * up + down - 1) // down
+
+
+def resample_table(fs_in, fs_out, device=None):
+    """h [up, 2 hw] fp64, the Kaiser-windowed sinc of ptts_resample: row p, column j + hw - 1 holds
+    c sinc(c tau) I0(beta sqrt(1 - (tau / R)^2)) / I0(beta) at tau = p / up - j (0 from |tau| = R on), c = 0.95 min(1, up / down),
+    R = 16 / c, beta = 9.  Built on the host once per (up, down) and kept: a numpy array, or with `device` the device tensor."""
+    up, down, hw = preproc_check(fs_in, fs_out)
+    key = (up, down)
+    if key not in _resample_tables:
+        c = RESAMPLE_CUTOFF * min(1.0, up / float(down))
+        R = RESAMPLE_ZEROS / c
+        tau = np.arange(up, dtype=np.float64)[:, None] / up - np.arange(-hw + 1, hw + 1, dtype=np.float64)[None, :]
+        inside = np.abs(tau) < R
+        win = np.i0(RESAMPLE_BETA * np.sqrt(np.where(inside, 1.0 - (tau / R) ** 2, 0.0))) / np.i0(RESAMPLE_BETA)
+        h = np.ascontiguousarray(np.where(inside, c * np.sinc(c * tau) * win, 0.0))
+        h.setflags(write=False)
+        _resample_tables[key] = h
+    if device is None:
+        return _resample_tables[key]
+    dkey = ('resample', device, up, down)
+    if dkey not in _spectrum_tables:
+        _spectrum_tables[dkey] = torch.from_numpy(_resample_tables[key].copy()).to(device)
+    return _spectrum_tables[dkey]
+
+
+def _waveforms(fn, wav):
+    """One [N] tensor or a list of them -> (list, was a list); ValueError for anything else, before the device is looked at."""
+    single = torch.is_tensor(wav)
+    wavs = [wav] if single else list(wav) if isinstance(wav, (list, tuple)) else None
+    if wavs is None or not all(torch.is_tensor(w) and w.dim() == 1 for w in wavs):
+        raise ValueError('ops.{}: wav is not an [N] tensor or a list of them'.format(fn))
+    if len(wavs) > PREPROC_MAX_UTTS or sum(w.numel() for w in wavs) >= 1 << 40:
+        raise ValueError('ops.{}: {} utterances, one launch takes at most {}'.format(fn, len(wavs), PREPROC_MAX_UTTS))
+    _no_backward(fn, *wavs)
+    return wavs, not single
+
+
+def _packed(fn, wavs):
+    """fp32 device waveforms -> (one packed array, its 64-bit offsets on the device)."""
+    for w in wavs:
+        f32c(w, '{}.wav'.format(fn))
+    x = wavs[0] if len(wavs) == 1 else torch.cat(wavs)
+    off = np.concatenate([[0], np.cumsum([w.numel() for w in wavs])]).astype(np.int64)
+    return x, torch.from_numpy(off).to(x.device)
+
+
+def resample(wav, fs_in, fs_out):
+    """wav [N] at fs_in (fp32 device), or a list of them -> the same at fs_out, ceil(N up / down) samples each, by the rational-ratio
+    Kaiser-windowed sinc of csrc/preproc.hip, all utterances in one launch, one thread per output sample.
+    fs_in == fs_out returns its input and launches nothing."""
+    up, down, hw = preproc_check(fs_in, fs_out)
+    wavs, as_list = _waveforms('resample', wav)
+    if up == down:
+        return wav
+    lens = [resample_length(w.numel(), up, down) for w in wavs]
+    if not wavs:
+        return []
+    x, x_off = _packed('resample', wavs)
+    y_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    y = torch.empty(int(y_off[-1]), dtype=torch.float32, device=x.device)
+    if y.numel():
+        h = resample_table(fs_in, fs_out, device=x.device)
+        y_off_dev = torch.from_numpy(y_off).to(x.device)
+        call('ptts_resample', ptr(x), ptr(x_off), x.numel(), ptr(y), ptr(y_off_dev), y.numel(), max(lens), len(wavs), ptr(h),
+             h.numel() * 8, up, down, hw, stream(), tag=(len(wavs), y.numel(), up, down))
+    out = [y[int(a):int(b)] for a, b in zip(y_off[:-1], y_off[1:])]
+    return out if as_list else out[0]
+
+
+def highpass_tile():
+    """(chunk, tile) of ptts_highpass_zerophase: the samples a lane owns and the samples a workgroup holds at a time."""
+    chunk, tile = ctypes.c_int(0), ctypes.c_int(0)
+    call('ptts_highpass_tile', ctypes.byref(chunk), ctypes.byref(tile))
+    return chunk.value, tile.value
+
+
+def highpass_zerophase(wav, fs, fc, padlen=HIGHPASS_PADLEN):
+    """wav [N] at fs (fp32 device), or a list of them -> the same, high-passed at `fc` Hz by the order-4 Butterworth filter run forward
+    and backward over the odd extension by `padlen` samples (csrc/preproc.hip): mathematically
+    scipy.signal.sosfiltfilt(butter(4, fc / (fs / 2), 'high', output='sos'), wav, padtype='odd', padlen=padlen).  All utterances in one
+    launch, one workgroup each; every one has to be longer than padlen."""
+    preproc_check(fs, fs, fc, padlen)
+    wavs, as_list = _waveforms('highpass_zerophase', wav)
+    for w in wavs:
+        if w.numel() <= padlen:
+            raise ValueError('ops.highpass_zerophase: a waveform of {} samples is not longer than padlen={}'.format(w.numel(), padlen))
+    if not wavs:
+        return []
+    x, off = _packed('highpass_zerophase', wavs)
+    y = torch.empty_like(x)
+    nws = _hip.lib().ptts_highpass_workspace_bytes(x.numel(), len(wavs), int(padlen))
+    ws = _workspace(nws, x.device)
+    call('ptts_highpass_zerophase', ptr(x), ptr(y), ptr(off), x.numel(), len(wavs), float(fs), float(fc), int(padlen), ptr(ws), nws,
+         stream(), tag=(len(wavs), x.numel()))
+    lens = [w.numel() for w in wavs]
+    out = list(torch.split(y, lens))
+    return out if as_list else out[0]
 
 
 # ----------------------------------------------------------------------------------------------

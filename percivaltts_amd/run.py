@@ -1,8 +1,9 @@
 """Experiment script with the shape of the reference's percivaltts/run.py:57-230: a module-level `cfg`,
 `build_model()`, `training(cont)`, `generate()`.  The corpus-preparation stages of the reference
 split in two.  `features_extraction()` is the reference's stage of that name (run.py:147-165) with the build's own waveform
-analysis (VocoderPML.analysisfid_device) in the place of pulsemodel's and the build's own F0 estimator (or a
-caller's F0 tracks) in the place of the REAPER binary; `synthesize_corpus()` writes a synthetic corpus of the same on-disk
+analysis (VocoderPML.analysisfid_device) in the place of pulsemodel's, the build's own F0 estimator (or a
+caller's F0 tracks) in the place of the REAPER binary, and Vocoder.preprocwav (resampling, high-pass) in front of both;
+`synthesize_corpus()` writes a synthetic corpus of the same on-disk
 format (headerless float32 `path:(-1,D)`
 files + file_id_list.scp) so that the training stages run without recordings.  `contexts_extraction()` is the reference's stage of
 that name (run.py:168-180): HTS labels through the label normaliser (percivaltts_amd.external.merlin, on the device), the
@@ -104,13 +105,18 @@ def features_compose(rawpaths, fids=None, win_convention='mlpg'):
                            win_convention=win_convention)
 
 
-def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None, f0_min=70, f0_max=600, win_convention='mlpg'):
+def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None, f0_min=70, f0_max=600, win_convention='mlpg',
+                        preproc_hp=None):
     """The reference's features_extraction (run.py:147-165): every file id's waveform `wav_path` ('dir/*.wav', by default
     <corpus>/wav/*.wav) goes through vocoder.analysisfid_device with the F0 track of `f0in_path` ('dir/*.f0': headerless float32 Hz
     values, one per frame, <= 0 unvoiced) or, with f0in_path None, the track of the build's own estimator
     (vocoder.f0_estimate_device; the reference runs REAPER here), which writes the raw
     streams `rawpaths` = [f0_path, spec_path, noise_path] (by default the reference's places beside the waveforms); then
-    features_compose.  f0_min / f0_max default to the reference's cfg.vocoder_f0_min / cfg.vocoder_f0_max."""
+    features_compose.  f0_min / f0_max default to the reference's cfg.vocoder_f0_min / cfg.vocoder_f0_max.  `preproc_hp`: the cut-off
+    in Hz of the high-pass filter in front of the analysis, 'auto' for f0_min as in the reference, None for no filter.  A file
+    that is not sampled at the vocoder's rate, or any file with preproc_hp, goes through vocoder.preprocwav (resampling, then the
+    filter; csrc/preproc.hip) and vocoder.analysis_device; a file at the vocoder's rate without preproc_hp takes
+    analysisfid_device as before."""
     fids = readids(cfg.fileids) if fids is None else fids
     if not hasattr(vocoder, 'analysisfid_device'):
         raise ValueError('features_extraction: {} has no waveform analysis in this build'.format(vocoder.name()))
@@ -119,8 +125,18 @@ def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None,
         base = os.path.dirname(wav_path) + '_PML'
         rawpaths = [base + '_lf0/*.lf0', base + '_fwlspec' + str(vocoder.specsize()) + '/*.fwlspec',
                     base + '_fwnm' + str(vocoder.noisesize()) + '/*.fwnm']
+    if preproc_hp == 'auto':
+        preproc_hp = f0_min
     for fid in fids:
-        vocoder.analysisfid_device(fid, wav_path, f0in_path, f0_min, f0_max, {'f0': rawpaths[0], 'spec': rawpaths[1], 'noise': rawpaths[2]})
+        fwav = wav_path.replace('*', fid)
+        if preproc_hp is None and vocoders.wavfs(fwav) == int(round(vocoder.fs)):
+            vocoder.analysisfid_device(fid, wav_path, f0in_path, f0_min, f0_max, {'f0': rawpaths[0], 'spec': rawpaths[1], 'noise': rawpaths[2]})
+            continue
+        print('Extracting PML features from: ' + fwav)
+        wav, fs = vocoders.wavread(fwav)
+        wav = vocoder.preprocwav(wav, fs, highpass=preproc_hp)
+        f0 = None if f0in_path is None else np.fromfile(f0in_path.replace('*', fid), dtype=np.float32)
+        vocoder.write_streams(vocoder.analysis_device(wav, f0, f0_min, f0_max), *[p.replace('*', fid) for p in rawpaths[:3]])
     return features_compose(rawpaths, fids=fids, win_convention=win_convention)
 
 

@@ -12,7 +12,9 @@ section 3); `synthesis` keeps its name for pulsemodel's waveform and keeps raisi
 `analysisf_device` / `analysisfid_device` around it) is the build's own waveform analysis for the same parameters
 (csrc/analysis.hip), from a caller's F0 track or, without one, from the build's own F0 estimator
 (`VocoderF0Spec.f0_estimate_device`, csrc/f0.hip); `compress_spectrum` is the inverse of `decompress_spectrum` for 'fwbnd'.
-`analysisf` / `analysisfid` keep their names for pulsemodel's analysis and keep raising.
+`analysisf` / `analysisfid` keep their names for pulsemodel's analysis and keep raising.  `Vocoder.preprocwav` (vocoders.py:45-63) is
+the step in front of the analysis, on the device (csrc/preproc.hip): the build's own rational-ratio resampler in
+the place of pulsemodel's, and the zero-phase order-4 Butterworth high-pass with `highpass` as the cut-off in Hz.
 """
 from __future__ import print_function
 
@@ -70,6 +72,19 @@ def wavread(path):
     return pcm.astype(np.float64) / 32767.0, fs
 
 
+def wavfs(path):
+    """The sampling rate in a wave file's header.  Anything that is not a PCM wave file is a ValueError."""
+    import wave
+    try:
+        f = wave.open(path, 'rb')
+    except (wave.Error, EOFError) as e:
+        raise ValueError('wavfs: {} is not a PCM wave file ({})'.format(path, e))
+    try:
+        return f.getframerate()
+    finally:
+        f.close()
+
+
 class Vocoder(object):
     def __init__(self, name, fs, shift, mlpg_wins=None):
         self._name, self.fs, self.shift, self.mlpg_wins = name, fs, shift, mlpg_wins
@@ -92,6 +107,44 @@ class Vocoder(object):
     def specsize(self): return -1
     def noisesize(self): return -1
     def vuvsize(self): return -1
+
+    def preprocwav(self, wav, fs, highpass=None):
+        """A mono waveform at `fs` -> the waveform the analysis takes (the reference's preprocwav, vocoders.py:45-63, with its name,
+        argument order and two printed lines), on the device (csrc/preproc.hip): resampled to self.fs when `fs`
+        differs (ops.resample), then, with `highpass`, the zero-phase order-4 Butterworth high-pass (ops.highpass_zerophase, odd
+        extension by padlen = ops.HIGHPASS_PADLEN samples).  `highpass` is the cut-off in Hz: the reference normalises it as
+        highpass / (fs / 0.5), which puts the cut-off at highpass / 4 Hz; that is not reproduced.  numpy (any float array) in ->
+        numpy float32 out, device tensor in -> device tensor out.  A waveform that is not finite, not 1-D, or not longer than
+        padlen where it is filtered, is a ValueError, and so are rates and cut-offs that ops.preproc_check refuses."""
+        import torch
+        from . import backend_hip, ops_offline as ops
+        padlen = ops.HIGHPASS_PADLEN
+        ops.preproc_check(fs, self.fs, highpass, padlen)
+        fs, fs_out = int(fs), int(self.fs)
+        as_numpy = not torch.is_tensor(wav)
+        if as_numpy:
+            wav = np.asarray(wav, dtype=np.float64)
+            if wav.ndim != 1 or not np.isfinite(wav).all():
+                raise ValueError('preprocwav: wav is not a finite [N] waveform')
+        elif wav.dim() != 1:
+            raise ValueError('preprocwav: wav is not an [N] waveform')
+        if highpass is not None:
+            up, down, _ = ops.preproc_check(fs, fs_out)
+            n = len(wav) if fs == fs_out else ops.resample_length(len(wav), up, down)
+            if n <= padlen:
+                raise ValueError('preprocwav: {} samples at {} Hz are not longer than padlen={}'.format(n, fs_out, padlen))
+        x = wav
+        if as_numpy:
+            x = torch.from_numpy(wav.astype(np.float32)).to(backend_hip.device())
+        elif not bool(torch.isfinite(x).all()):
+            raise ValueError('preprocwav: wav is not a finite [N] waveform')
+        if fs != fs_out:
+            print('    Resampling the waveform (new fs={}Hz)'.format(self.fs))
+            x = ops.resample(x, fs, fs_out)
+        if highpass is not None:
+            print('    High-pass filter the waveform (cutt-off={}Hz)'.format(highpass))
+            x = ops.highpass_zerophase(x, fs_out, highpass, padlen=padlen)
+        return x.cpu().numpy() if as_numpy else x
 
     # Objective measures (vocoders.py:112-117): lists of per-utterance errors, keyed by feature
     def objmeasures_clear(self):
@@ -257,10 +310,10 @@ class VocoderPML(VocoderF0Spec):
 
     def analysisf_device(self, fwav, f0_in, ff0, f0_min, f0_max, fspec, fnm, **kwargs):
         """analysis_device from file to files, where the reference's analysisf writes them (vocoders.py:181-189): fwav a 16-bit mono
-        wave file at self.fs (another fs is a ValueError: resampling is not built), f0_in a headerless float32 file, or an array, of
-        Hz values per frame, or None for the build's own estimate; ff0 gets ln f0, fspec the spectral bands, fnm the noise-mask
-        bands, headerless float32.  The one keyword
-        taken is preproc_hp=None: the high-pass filter is not built."""
+        wave file at self.fs, f0_in a headerless float32 file, or an array, of Hz values per frame, or None for the build's own
+        estimate; ff0 gets ln f0, fspec the spectral bands, fnm the noise-mask bands, headerless float32 (write_streams).  Another fs
+        and any preproc_hp (the one keyword taken, None) stay a ValueError here: a file that needs resampling or the high-pass
+        filter goes through preprocwav and analysis_device, as run.features_extraction(..., preproc_hp=) does."""
         if kwargs.get('preproc_hp') is not None:
             raise ValueError('analysisf_device: preproc_hp={!r}: the high-pass pre-processing is not built'.format(kwargs['preproc_hp']))
         if set(kwargs) - {'preproc_hp'}:
@@ -270,7 +323,11 @@ class VocoderPML(VocoderF0Spec):
         if fs != int(round(self.fs)):
             raise ValueError('analysisf_device: {} is sampled at {} Hz, the vocoder at {} (resampling is not built)'.format(fwav, fs, self.fs))
         f0 = np.fromfile(f0_in, dtype=np.float32) if isinstance(f0_in, str) else f0_in
-        CMP = self.analysis_device(wav, f0, f0_min, f0_max)
+        return self.write_streams(self.analysis_device(wav, f0, f0_min, f0_max), ff0, fspec, fnm)
+
+    def write_streams(self, CMP, ff0, fspec, fnm):
+        """The parameters [T, featuressizeraw()] of analysis_device -> the three headerless float32 files of analysisf_device: ff0
+        gets ln f0, fspec the spectral bands, fnm the noise-mask bands; missing directories are made.  Returns T."""
         s1 = 1 + self.spec_size
         for path, cols in ((ff0, CMP[:, 0]), (fspec, CMP[:, 1:s1]), (fnm, CMP[:, s1:])):
             if os.path.dirname(path) and not os.path.isdir(os.path.dirname(path)):
