@@ -384,6 +384,15 @@ int ptts_conv1d_freq_wgrad_inverse(const float* Gt, const float* t2, float* dW, 
 int ptts_dense_bf16x6_batched(const float* A, long long strideA, const void* planes, long long stride_planes_bytes,
                               const float* bias, float* C, long long strideC, int nbatch, int M, int N, int K,
                               long long lda, long long ldc, int planes_count, void* stream);
+/* nbatch transposed-reduction products of one shape in one launch: C_z[k][n] = sum_{m<M} A_z[m][k] B_z[m][n], k < Kin, n < N.  Both
+ * operands are fp32, row-major (lda, ldb) and are split inside the kernel, so a right operand that is used once needs no planes; A_z =
+ * A + z*strideA (0 shares it), B_z = B + z*strideB, C_z = C + z*strideC (floats), C row-major with ldc.  Only cells k < Kin, n < N of C
+ * are written.  The operands are read in quads: lda >= Kin and ldb >= N rounded up to 4.  Pointers, leading dimensions and strides keep
+ * 16-byte alignment.  planes_count as above.  The per-frequency correlations of the frequency-domain context Conv1D's weight
+ * gradient are one of these. */
+int ptts_dense_tn_bf16x6_batched(const float* A, long long strideA, const float* B, long long strideB, float* C, long long strideC,
+                                 int nbatch, int M, int Kin, int N, long long lda, long long ldb, long long ldc, int planes_count,
+                                 void* stream);
 
 /* The context Conv1D forward (reference networktts.py:116-120: kl.Conv1D(width, winlen, padding='same')) as an fp32
  * product on the bf16 matrix cores by a three-way operand split ("bf16x6"; split.hip): x = x1 + x2 + x3 in bf16 (round

@@ -981,6 +981,166 @@ __global__ __launch_bounds__(256) void dense_wgrad_reduce_kernel(DwReduceArgs a)
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------------------
+// Batched transposed-reduction product  C_z[Kin][N] = A_z[M][Kin]^T . B_z[M][N]  (gridDim.z members z): the construction of
+// dense_wgrad_bf16x6_kernel above -- 32-row slabs of both fp32 operands split on their way into the LDS (the same row layout, the same
+// transposed reads, the same six products, two buffers, waves 0-3 / 4-7 staging at different places) -- for products whose reduction
+// is short and whose batch is long (the frequency-domain context Conv1D: M = 2 B NS rows per frequency, S rows per segment): one
+// workgroup owns a whole 128 x 128 tile, so there is no split over M, no partial rows and no reduce launch; the tile goes straight
+// into C, every cell guarded by the true Kin and N.  No input transforms, no bias sums, no remainder tile.
+// blockIdx.x = tile (column tiles innermost), blockIdx.z = member: the tiles of a member are dispatched together.  (Regrouping the
+// workgroups so that a member's tiles share one XCD's L2 was measured on the correlation: 164.5 against 168 us, not kept.)
+// ------------------------------------------------------------------------------------------------------------
+struct TnArgs {
+    const float* A; const float* B; float* C;
+    long long strideA, strideB, strideC;     // floats between batch members (strideA = 0: a shared left operand)
+    long long lda, ldb, ldc;
+    int Kin, N, M;
+    int tiles_n;                             // 128-column tiles along N
+};
+
+template <int NPL>
+__global__ __launch_bounds__(THREADS) void dense_tn_bf16x6_kernel(TnArgs g) {
+    extern __shared__ __attribute__((aligned(16))) u16 lds_t[];          // [buffer][A planes 0..2 | B planes 0..2]: 96 KB
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, lg = lane >> 4;
+    const int member = blockIdx.z, tile = blockIdx.x, tk = tile / g.tiles_n, tn = tile - tk * g.tiles_n;
+    const int k0 = tk * WT, n0 = tn * WT;
+    const int nsteps = (g.M + 31) / 32;
+
+    // ---- staging slots as in dense_wgrad_bf16x6_kernel: float4 q = tid + 512 j (j = 0, 1) -> row q >> 5, columns 4 (q & 31) ..
+    // (a quad that straddles Kin or N is loaded whole -- lda, ldb cover the rounded-up width -- and its cells beyond are never stored)
+    const int c4 = tid & 31;
+    const bool a_ok = k0 + 4 * c4 < g.Kin, b_ok = n0 + 4 * c4 < g.N;
+    const float* pa = g.A + (long long)member * g.strideA + (a_ok ? k0 + 4 * c4 : 0);
+    const float* pb = g.B + (long long)member * g.strideB + (b_ok ? n0 + 4 * c4 : 0);
+    int dst[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int row = (tid + j * THREADS) >> 5;
+        dst[j] = row * WROW + ((((c4 >> 2) + row + 4 * (row >> 3)) & 7) << 4) + (c4 & 3) * 4;
+    }
+    struct Stage { f32x4 va[2], vb[2]; bool ok[2]; };
+    auto load = [&](int s, Stage& sg) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int m = s * 32 + ((tid + j * THREADS) >> 5);
+            sg.ok[j] = m < g.M;                                          // (also false for the steps behind the last)
+            const long long r = sg.ok[j] ? m : 0;
+            sg.va[j] = *reinterpret_cast<const f32x4*>(pa + r * g.lda);
+            sg.vb[j] = *reinterpret_cast<const f32x4*>(pb + r * g.ldb);
+        }
+    };
+    auto commit = [&](const Stage& sg, u16* ls) {
+        const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            f32x4 a = sg.va[j], d = sg.vb[j];
+            if (!(sg.ok[j] && a_ok)) a = z4;
+            if (!(sg.ok[j] && b_ok)) d = z4;
+            u16* q = ls + dst[j];
+            if (NPL == 3) {
+                unsigned a1, a2, a3, b1, b2, b3;
+                split3_pair(a[0], a[1], a1, a2, a3);
+                split3_pair(a[2], a[3], b1, b2, b3);
+                *reinterpret_cast<u32x2*>(q) = (u32x2){a1, b1};
+                *reinterpret_cast<u32x2*>(q + WPL) = (u32x2){a2, b2};
+                *reinterpret_cast<u32x2*>(q + 2 * WPL) = (u32x2){a3, b3};
+                split3_pair(d[0], d[1], a1, a2, a3);
+                split3_pair(d[2], d[3], b1, b2, b3);
+                q += 3 * WPL;
+                *reinterpret_cast<u32x2*>(q) = (u32x2){a1, b1};
+                *reinterpret_cast<u32x2*>(q + WPL) = (u32x2){a2, b2};
+                *reinterpret_cast<u32x2*>(q + 2 * WPL) = (u32x2){a3, b3};
+            } else {
+                *reinterpret_cast<u32x2*>(q) = (u32x2){pk_bf16(a[0], a[1]), pk_bf16(a[2], a[3])};
+                *reinterpret_cast<u32x2*>(q + 3 * WPL) = (u32x2){pk_bf16(d[0], d[1]), pk_bf16(d[2], d[3])};
+            }
+        }
+    };
+
+    // ---- MFMA tiles of this wave: A-column tiles 2 (wave & 3) + {0, 1}, B-column tiles 4 (wave >> 2) + {0..3}
+    auto tr_off = [&](int t, int half) {
+        const int row = 8 * lg + (li >> 2) + 4 * half;
+        return row * WROW + (((t + row + 4 * (row >> 3)) & 7) << 4) + (li & 3) * 4;
+    };
+    int ao[2][2], bo[4][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) ao[i][h] = tr_off(2 * (wave & 3) + i, h);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bo[i][h] = 3 * WPL + tr_off(4 * (wave >> 2) + i, h);
+    }
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto mfma_tile_row = [&](const u16* ls, int i, const bf16x8 (&bf)[4][NPL]) {
+        bf16x8 af[NPL];
+#pragma unroll
+        for (int p = 0; p < NPL; ++p) af[p] = cat8(tr_read(ls + p * WPL + ao[i][0]), tr_read(ls + p * WPL + ao[i][1]));
+#define DNS_MM(PA, PW)                                                                                       \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                        \
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[PA < NPL ? PA : 0], bf[j][PW < NPL ? PW : 0], acc[i][j], 0, 0, 0);
+        DNS_PRODUCTS_NPL(NPL, DNS_MM);
+#undef DNS_MM
+    };
+    auto read_bf = [&](const u16* ls, bf16x8 (&bf)[4][NPL]) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int p = 0; p < NPL; ++p) bf[j][p] = cat8(tr_read(ls + p * WPL + bo[j][0]), tr_read(ls + p * WPL + bo[j][1]));
+    };
+
+    u16* const buf0 = lds_t;
+    u16* const buf1 = lds_t + 6 * WPL;
+    Stage sg;
+    load(0, sg);
+    commit(sg, buf0);
+    load(1, sg);
+    __syncthreads();
+    auto step = [&](int s, const u16* cur, u16* nxt, bool stage_first) {
+        bf16x8 bf[4][NPL];
+        if (stage_first) { commit(sg, nxt); load(s + 2, sg); }
+        read_bf(cur, bf);
+        mfma_tile_row(cur, 0, bf);
+        if (!stage_first) { commit(sg, nxt); load(s + 2, sg); }
+        mfma_tile_row(cur, 1, bf);
+        __syncthreads();
+    };
+    if (wave < 4) {
+        int s = 0;
+        for (; s + 1 < nsteps; s += 2) { step(s, buf0, buf1, false); step(s + 1, buf1, buf0, false); }
+        if (s < nsteps) step(s, buf0, buf1, false);
+    } else {
+        int s = 0;
+        for (; s + 1 < nsteps; s += 2) { step(s, buf0, buf1, true); step(s + 1, buf1, buf0, true); }
+        if (s < nsteps) step(s, buf0, buf1, true);
+    }
+
+    // ---- the tile, straight from the accumulators: lane (li, lg) of acc[i][j] holds rows k = 32 (wave & 3) + 16 i + 4 lg + r, column
+    // 64 (wave >> 2) + 16 j + li, so one store instruction writes 64-byte segments of four rows; the four j of a row are issued back to
+    // back and complete 256 contiguous bytes of it
+    float* out = g.C + (long long)member * g.strideC;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = k0 + 32 * (wave & 3) + 16 * i + 4 * lg + r;
+            if (k >= g.Kin) continue;
+            float* row = out + (long long)k * g.ldc;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int n = n0 + 64 * (wave >> 2) + 16 * j + li;
+                if (n < g.N) row[n] = acc[i][j][r];
+            }
+        }
+}
+
 }  // namespace dns
 }  // namespace ptts
 
@@ -1269,6 +1429,35 @@ extern "C" int ptts_dense_bf16x6_batched(const float* A, long long strideA, cons
     }
 #undef DNS_B
     return check_launch("dense_bf16x6_batched");
+}
+
+// nbatch products C_z[Kin,N] = A_z[M,Kin]^T . B_z[M,N] of ONE shape in one launch (dense_tn_bf16x6_kernel): both operands fp32,
+// row-major, read once and split in the kernel -- for right operands that are activations used once, which ptts_dense_bf16x6_batched
+// wants pre-split.  Kin and N are the store guards; the operands are read in quads, so lda / ldb cover Kin / N rounded up to 4.
+extern "C" int ptts_dense_tn_bf16x6_batched(const float* A, long long strideA, const float* B, long long strideB, float* C,
+                                            long long strideC, int nbatch, int M, int Kin, int N, long long lda, long long ldb,
+                                            long long ldc, int planes_count, void* stream) {
+    PTTS_REQUIRE(A && B && C && nbatch > 0 && nbatch <= 65535, "dense_tn_bf16x6_batched: bad arguments");
+    PTTS_REQUIRE(M > 0 && Kin > 0 && N > 0, "dense_tn_bf16x6_batched: bad shape M=%d Kin=%d N=%d", M, Kin, N);
+    PTTS_REQUIRE(planes_count == 1 || planes_count == 3, "dense_tn_bf16x6_batched: planes_count %d is neither 1 nor 3", planes_count);
+    PTTS_REQUIRE(lda >= (Kin + 3) / 4 * 4 && ldb >= (N + 3) / 4 * 4 && ldc >= N, "dense_tn_bf16x6_batched: bad leading dims lda=%lld ldb=%lld ldc=%lld", lda, ldb, ldc);
+    PTTS_REQUIRE(strideA >= 0 && strideB >= 0 && strideC >= 0, "dense_tn_bf16x6_batched: negative stride");
+    PTTS_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && strideA % 4 == 0 && strideB % 4 == 0 && strideC % 4 == 0 &&
+                 (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, "dense_tn_bf16x6_batched: pointers, leading dims and strides must keep 16-byte alignment");
+    TnArgs g;
+    g.A = A; g.B = B; g.C = C; g.strideA = strideA; g.strideB = strideB; g.strideC = strideC;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.Kin = Kin; g.N = N; g.M = M;
+    g.tiles_n = (N + WT - 1) / WT;
+    const long long tiles = (long long)((Kin + WT - 1) / WT) * g.tiles_n;
+    PTTS_REQUIRE(tiles <= 0x7fffffffLL, "dense_tn_bf16x6_batched: too many tiles");
+    const dim3 grid((unsigned)tiles, 1, (unsigned)nbatch);
+    constexpr size_t lds = (size_t)2 * 6 * WPL * sizeof(u16);
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_tn_bf16x6_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_tn_bf16x6_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
+    if (planes_count == 1) hipLaunchKernelGGL((dense_tn_bf16x6_kernel<1>), grid, dim3(THREADS), lds, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL((dense_tn_bf16x6_kernel<3>), grid, dim3(THREADS), lds, (hipStream_t)stream, g);
+    return check_launch("dense_tn_bf16x6_batched");
 }
 
 // 1 when ptts_dense_wgrad_bf16x6 takes the shape

@@ -1556,6 +1556,10 @@ class _C1FFT(object):
     enabled = default
     KWS = (3, 5, 7, 9, 11, 21)      # instantiations of conv1d_wdft_planes_kernel<KW> / conv1d_freq_wgrad_inverse_kernel<KW>
     wgrad_enabled = os.environ.get('PTTS_CONV1D_FFT_WGRAD', '1') == '1'
+    # fp32 arithmetic: the per-frequency correlation of the weight gradient as a transposed-reduction product over the fp32 operands
+    # themselves (ptts_dense_tn_bf16x6_batched), without the split of X^ and the transpose of DY^ in front of it.  PTTS_CONV1D_FFT_TN=0:
+    # the older stage list.
+    tn_enabled = os.environ.get('PTTS_CONV1D_FFT_TN', '1') == '1'
     # BASELINE configs[2] (ops.bf16_products): the frequency-domain path with its BIG products -- the per-frequency product of the forward
     # and the per-frequency correlation of the weight gradient, 80 % of its flops -- as ONE bf16 product of the operands' roundings
     # (X^ and H^ / DY^ rounded once, fp32 accumulation), the small transforms (DFT, inverse DFT) still six products: the same single
@@ -1764,12 +1768,6 @@ class _C1FFT(object):
         lib = _hip.lib()
         dev = a.device
         Ap = cls.x_hat
-        # planes of [Xr | -Xi ; Xi | Xr]_f as the right operand [K = 2Z][N' = 2 Kh]: once per input
-        npx = lib.ptts_dense_planes_bytes(2 * Kh, 2 * Z)
-        if cls.xw_src is not a or cls.xw_key != cls.x_key or cls.xw_planes is None:
-            xw = cls._scratch('xw', NB * npx, dev)
-            call('ptts_split3_dense_weight_strided', ptr(Ap), 2 * Z * 2 * Kh, ptr(xw), npx, NB, 2 * Kh, 2 * Z, 2 * Kh, 0, stream(), tag=('xw', NB))
-            cls.xw_src, cls.xw_key, cls.xw_planes = a, cls.x_key, xw
         # DY' = DFT of the segments' gradient frames (S frames, zero-padded to P): [NB][2][Z][N]
         npd = lib.ptts_dense_planes_bytes(N, P)
         dpl = cls._scratch('dpl', Z * npd, dev)
@@ -1777,11 +1775,23 @@ class _C1FFT(object):
         DYh = cls._scratch('DYh', NB * 2 * Z * N * 4, dev)
         call('ptts_dense_bf16x6_batched', ptr(c['D']), 0, ptr(dpl), npd, None, ptr(DYh), N, Z, c['R'], N, P, P, Z * N, 3, stream(),
              tag=('dft_dy', Z, c['R'], N, P))
-        DYt = cls._scratch('DYt', NB * N * 2 * Z * 4, dev)                                         # [NB][N][2Z] fp32
-        call('ptts_transpose_batched', ptr(DYh), ptr(DYt), NB, 2 * Z, N, stream())
         Gt = cls._scratch('Gt', NB * N * 2 * Kh * 4, dev)                                          # [NB][N][2 Kh] fp32 = (Gr | -Gi)^T
-        call('ptts_dense_bf16x6_batched', ptr(DYt), N * 2 * Z, ptr(cls.xw_planes), npx, None, ptr(Gt), N * 2 * Kh, NB, N, 2 * Kh, 2 * Z,
-             2 * Z, 2 * Kh, 1 if _Flags.bf16_products else 3, stream(), tag=('corr', NB, N, 2 * Kh, 2 * Z))
+        if cls.tn_enabled and not _Flags.bf16_products:
+            # the correlation reduces over the ROW index of two row-major fp32 operands, Gt_f = DY'_f [2Z][N]^T . Ap_f [2Z][2 Kh]: both
+            # are read as they lie and split inside the kernel -- no planes of Ap, no transpose of DY'
+            call('ptts_dense_tn_bf16x6_batched', ptr(DYh), 2 * Z * N, ptr(Ap), 2 * Z * 2 * Kh, ptr(Gt), N * 2 * Kh, NB, 2 * Z, N, 2 * Kh, N, 2 * Kh,
+                 2 * Kh, 3, stream(), tag=('corr', NB, N, 2 * Kh, 2 * Z))
+        else:
+            # planes of [Xr | -Xi ; Xi | Xr]_f as the right operand [K = 2Z][N' = 2 Kh]: once per input
+            npx = lib.ptts_dense_planes_bytes(2 * Kh, 2 * Z)
+            if cls.xw_src is not a or cls.xw_key != cls.x_key or cls.xw_planes is None:
+                xw = cls._scratch('xw', NB * npx, dev)
+                call('ptts_split3_dense_weight_strided', ptr(Ap), 2 * Z * 2 * Kh, ptr(xw), npx, NB, 2 * Kh, 2 * Z, 2 * Kh, 0, stream(), tag=('xw', NB))
+                cls.xw_src, cls.xw_key, cls.xw_planes = a, cls.x_key, xw
+            DYt = cls._scratch('DYt', NB * N * 2 * Z * 4, dev)                                         # [NB][N][2Z] fp32
+            call('ptts_transpose_batched', ptr(DYh), ptr(DYt), NB, 2 * Z, N, stream())
+            call('ptts_dense_bf16x6_batched', ptr(DYt), N * 2 * Z, ptr(cls.xw_planes), npx, None, ptr(Gt), N * 2 * Kh, NB, N, 2 * Kh, 2 * Z,
+                 2 * Z, 2 * Kh, 1 if _Flags.bf16_products else 3, stream(), tag=('corr', NB, N, 2 * Kh, 2 * Z))
         dw = torch.empty((KW, Cin, N), dtype=torch.float32, device=dev)
         if KW in cls.KWS:
             ws = _workspace(lib.ptts_conv1d_freq_wgrad_inverse_workspace_bytes(KW, Cin, N), dev)
