@@ -384,6 +384,14 @@ int ptts_conv1d_freq_wgrad_inverse(const float* Gt, const float* t2, float* dW, 
 int ptts_dense_bf16x6_batched(const float* A, long long strideA, const void* planes, long long stride_planes_bytes,
                               const float* bias, float* C, long long strideC, int nbatch, int M, int N, int K,
                               long long lda, long long ldc, int planes_count, void* stream);
+/* The resident-left form of ptts_dense_bf16x6_batched: members that share a left operand (strideA == 0) of M <= 128 rows and K <= 128
+ * columns run on a kernel that splits A once per workgroup into the LDS and lets its waves walk (member, 32-column slice) work items,
+ * with no barrier after the prologue; the results are those of the general kernel bit for bit.  On by default; the environment variable
+ * PTTS_DENSE_BATCHED_RESIDENT=0 (read once) or ptts_set_dense_batched_resident(0) sends every batched product to the general kernel.
+ * ptts_set_dense_batched_resident returns the previous setting; ptts_dense_batched_resident_eligible returns 1 when a call of that
+ * shape takes the resident-left kernel while the switch is on, 0 otherwise, and launches nothing. */
+int ptts_set_dense_batched_resident(int on);
+int ptts_dense_batched_resident_eligible(long long strideA, int M, int N, int K, int planes_count);
 /* nbatch transposed-reduction products of one shape in one launch: C_z[k][n] = sum_{m<M} A_z[m][k] B_z[m][n], k < Kin, n < N.  Both
  * operands are fp32, row-major (lda, ldb) and are split inside the kernel, so a right operand that is used once needs no planes; A_z =
  * A + z*strideA (0 shares it), B_z = B + z*strideB, C_z = C + z*strideC (floats), C row-major with ldc.  Only cells k < Kin, n < N of C

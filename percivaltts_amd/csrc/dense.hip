@@ -637,6 +637,166 @@ static int pick_mt(int M, int col_blocks) {
     return best;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Batched products whose members SHARE a small left operand (ptts_dense_bf16x6_batched with strideA == 0, M <= 128, K <= 128: the
+// transforms of the frequency-domain context Conv1D, a constant twiddle matrix against one right operand per segment).
+// dense_bf16x6_kernel gives each member a workgroup of its own that lives KS <= 4 k-steps: every one of them loads, pads and splits
+// the same A, meets a barrier per k-step, and its prologue and store drain are a large share of its life.  Here A is split ONCE per
+// workgroup into the LDS -- the planes of all k-steps, in dense_bf16x6_kernel's row layout and swizzle: [k-step][plane][128 rows x 32 k]
+// -- and after the one barrier the workgroup's waves walk work items on their own: item = (member z, 32-column slice), wave w of
+// workgroup g takes items 8 g + w, + 8 G, ...  A wave loads the weight fragments of an item's two column tiles for all k-steps straight
+// from global memory (load_w's 1-KB loads), and refills the registers of k-step s with the NEXT item's as soon as step s is multiplied:
+// a whole item of loads (24 KB per wave) is in flight under the MFMAs and the stores.  No barrier, no LDS write and no word between
+// workgroups after the prologue.  The k-steps run in order and the six products of an accumulator in DNS_PRODUCTS_NPL's order, so every
+// output is dense_bf16x6_kernel's bit for bit (an MFMA's output cell depends on its own row and column alone, so the tiling is free).
+// Stores: 16-byte where the quad lies inside N and ldc / strideC / C keep the alignment (vec_out here says ONLY that: N % 4 != 0, the
+// 601 channels of the input's transform, stores its last quad of a row element-wise and the others whole), cells guarded by M and N.
+// ------------------------------------------------------------------------------------------------------------
+constexpr int RES_M = 128, RES_K = 128;
+constexpr int RES_KS = RES_K / BK;
+constexpr int RES_PL = RES_M * BK;            // elements of one plane of one k-step
+template <int NPL> constexpr size_t resident_lds_bytes() { return (size_t)RES_KS * NPL * RES_PL * sizeof(u16); }
+
+// MT = ceil(M / 16) row tiles.  KSC = the number of k-steps when it is RES_KS (the transforms: K = 120, 124), 0 = any (g.KS): with a
+// compile-time count the loads of an item are a fixed sequence, and the wait in front of k-step s covers the loads up to s alone -- not
+// the later k-steps' and not the stores of the item before.
+template <int NPL, int MT = RES_M / 16, int KSC = 0>
+__global__ __launch_bounds__(THREADS) void dense_bf16x6_resident_kernel(DenseArgs g, int slices, int items) {
+    extern __shared__ __attribute__((aligned(16))) u16 lds_r[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, lg = lane >> 4;
+    const int KS = KSC ? KSC : g.KS;
+    const size_t ps = (size_t)g.NT * KS * 512;
+    const int stride = 8 * (int)gridDim.x;
+    int item = 8 * (int)blockIdx.x + wave;
+    const bool live = item < items;           // (fewer items than waves: the others only help with the prologue)
+
+    // ---- prologue, first half: this lane's quads of A.  Quad q = tid + 512 j -> row q >> 5, k-quad q & 31 (k-step (q & 31) >> 3); rows
+    // >= M and quads >= K read A's first quad and are zeroed by a select
+    constexpr int NQ = RES_M * (RES_K / 4) / THREADS;
+    f32x4 va[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const int q = tid + j * THREADS, row = q >> 5, k4 = 4 * (q & 31);
+        const bool ok = row < g.M && k4 < g.K;                // K % 4 == 0: a quad is all inside or all outside
+        va[j] = *reinterpret_cast<const f32x4*>(g.A + (ok ? (long long)row * g.lda + k4 : 0));
+    }
+
+    // ---- weight fragments of an item: column tiles 2 sl, 2 sl + 1 of member z, k-step s
+    bf16x8 wf[RES_KS][2][NPL];
+    auto load_w = [&](int it, int s) {
+        const int z = it / slices, sl = it - z * slices;
+        const u16* wp = g.planes + (long long)z * g.bsP + (((size_t)(2 * sl) * KS + s) * 64 + lane) * 8;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int p = 0; p < NPL; ++p) wf[s][j][p] = *reinterpret_cast<const bf16x8*>(wp + p * ps + (size_t)j * KS * 512);
+    };
+    // the first item's fragments go out behind A's quads and in front of the split: no branch here -- a wave without an item loads the
+    // last item's and drops them -- so that the split waits for A alone
+#pragma unroll
+    for (int s = 0; s < RES_KS; ++s) {
+        if (s < KS) load_w(live ? item : items - 1, s);
+        __builtin_amdgcn_sched_barrier(0);                    // k-step by k-step: loads come back in the order they went out
+    }
+
+    // ---- prologue, second half: split into the planes of all k-steps in the LDS
+    {
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const int q = tid + j * THREADS, row = q >> 5, s = (q & 31) >> 3, kq = q & 7;
+            u16* d = lds_r + s * NPL * RES_PL + row * BK + ((((kq >> 1) ^ ((row >> 1) & 2))) << 3) + (kq & 1) * 4;
+            const f32x4 a = (row < g.M && 4 * (q & 31) < g.K) ? va[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+            if (NPL == 3) {
+                unsigned a1, a2, a3, b1, b2, b3;
+                split3_pair(a[0], a[1], a1, a2, a3);
+                split3_pair(a[2], a[3], b1, b2, b3);
+                *reinterpret_cast<u32x2*>(d) = (u32x2){a1, b1};
+                *reinterpret_cast<u32x2*>(d + RES_PL) = (u32x2){a2, b2};
+                *reinterpret_cast<u32x2*>(d + 2 * RES_PL) = (u32x2){a3, b3};
+            } else {
+                *reinterpret_cast<u32x2*>(d) = (u32x2){pk_bf16(a[0], a[1]), pk_bf16(a[2], a[3])};
+            }
+        }
+    }
+    __syncthreads();                                          // the only barrier
+    if (!live) return;
+
+    // activation fragment of row tile i: row 16 i + li, quad lg (swizzle = bit 2 of li), k-step s, plane p
+    const int boff = li * BK + ((lg ^ ((li >> 1) & 2)) << 3);
+    // One item.  The bias goes into registers in front of the k-steps: loads come back in order, and behind the next item's fragments
+    // it would hold the store until all of them are in.
+    auto run_item = [&](const int it, const bool has_next, const int next) __attribute__((always_inline)) {
+        const int z = it / slices, sl = it - z * slices;
+        f32x4 bv[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+        if (g.bias) {                                         // (four plain loads per tile, columns beyond N clamped and never stored: no branch per lane)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) bv[j][e] = g.bias[min(32 * sl + 16 * j + 4 * lg + e, g.N - 1)];
+        }
+        f32x4 acc[MT][2];
+#pragma unroll
+        for (int i = 0; i < MT; ++i) { acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll
+        for (int s = 0; s < RES_KS; ++s) {
+            if (s < KS) {
+                const u16* as = lds_r + s * NPL * RES_PL + boff;
+#pragma unroll
+                for (int i = 0; i < MT; ++i) {
+                    bf16x8 bf[NPL];
+#pragma unroll
+                    for (int p = 0; p < NPL; ++p) bf[p] = *reinterpret_cast<const bf16x8*>(as + p * RES_PL + i * 16 * BK);
+#define DNS_MM(PA, PW)                                                                                    \
+                    acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][0][PW < NPL ? PW : 0], bf[PA < NPL ? PA : 0], acc[i][0], 0, 0, 0);    \
+                    acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][1][PW < NPL ? PW : 0], bf[PA < NPL ? PA : 0], acc[i][1], 0, 0, 0);
+                    DNS_PRODUCTS_NPL(NPL, DNS_MM);
+#undef DNS_MM
+                }
+                if (has_next) load_w(next, s);                // this k-step's registers are free: the next item's loads go out
+                // (a compile-time KS makes the k-steps one basic block; moved up across this line, the later steps' LDS reads cost registers
+                // the fragments in flight need)
+                if (KSC) __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // ---- store: lane (li, lg) of acc[i][j] holds row 16 i + li, columns 32 sl + 16 j + 4 lg .. + 3 of member z
+        float* __restrict__ Cz = g.C + (long long)z * g.bsC;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = 32 * sl + 16 * j + 4 * lg;
+            if (n >= g.N) continue;
+            if (g.vec_out && n + 3 < g.N) {
+#pragma unroll
+                for (int i = 0; i < MT; ++i) {
+                    const int m = 16 * i + li;
+                    if (m < g.M) *reinterpret_cast<f32x4*>(Cz + (long long)m * g.ldc + n) = acc[i][j] + bv[j];
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (n + e >= g.N) continue;
+#pragma unroll
+                    for (int i = 0; i < MT; ++i) {
+                        const int m = 16 * i + li;
+                        if (m < g.M) Cz[(long long)m * g.ldc + n + e] = acc[i][j][e] + bv[j][e];
+                    }
+                }
+            }
+        }
+    };
+    // The first item apart from the loop: only loads are in flight in front of it, they come back in order, and the wait in front of
+    // k-step s is for the fragments up to s.  In the loop the stores of the item before are in flight too; loads and stores do not
+    // come back in one order, so there the first wait of an item is for everything.
+    int next = item + stride;
+    run_item(item, next < items, next);
+    while (next < items) {
+        item = next;
+        next = item + stride;
+        run_item(item, next < items, next);
+    }
+}
+
 
 // ------------------------------------------------------------------------------------------------------------
 // Weight gradient  dW[Kin][N] += T(A)[M][Kin]^T . dY[M][N],  db[N] += sum_m dY[m][:]   (reduction over the M frames).
@@ -1381,6 +1541,72 @@ extern "C" int ptts_conv1d_freq_kernel_planes(const float* w, const float* tw, v
     return check_launch("conv1d_freq_kernel_planes");
 }
 
+// ---- the resident-left form of the batched product (dense_bf16x6_resident_kernel) ----------------------------------------------
+// PTTS_DENSE_BATCHED_RESIDENT=0 (read once) or ptts_set_dense_batched_resident(0): every batched product on dense_bf16x6_kernel
+static int g_batched_resident = -1;
+static int batched_resident_on() {
+    if (g_batched_resident < 0) { const char* e = getenv("PTTS_DENSE_BATCHED_RESIDENT"); g_batched_resident = e ? (atoi(e) != 0 ? 1 : 0) : 1; }
+    return g_batched_resident;
+}
+extern "C" int ptts_set_dense_batched_resident(int on) {
+    const int prev = batched_resident_on();
+    g_batched_resident = on ? 1 : 0;
+    return prev;
+}
+extern "C" int ptts_dense_batched_resident_eligible(long long strideA, int M, int N, int K, int planes_count) {
+    return (strideA == 0 && M > 0 && M <= RES_M && N > 0 && K > 0 && K <= RES_K && K % 4 == 0 &&
+            (planes_count == 1 || planes_count == 3)) ? 1 : 0;
+}
+
+template <int NPL, int MT>
+static void resident_set_lds() {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bf16x6_resident_kernel<NPL, MT, 0>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)resident_lds_bytes<NPL>());
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bf16x6_resident_kernel<NPL, MT, RES_KS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)resident_lds_bytes<NPL>());
+    if constexpr (MT > 1) resident_set_lds<NPL, MT - 1>();
+}
+// compute units of the current device (asked once per device; the first call also raises the kernels' LDS limit there); 0: error set
+static int resident_cus() {
+    constexpr int MAXDEV = 64;
+    static int cus[MAXDEV];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) { set_error("dense_bf16x6_batched: no current device"); return 0; }
+    if (!cus[dev]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+            set_error("dense_bf16x6_batched: the device does not tell its compute units"); return 0;
+        }
+        resident_set_lds<3, RES_M / 16>();
+        resident_set_lds<1, RES_M / 16>();
+        cus[dev] = n;
+    }
+    return cus[dev];
+}
+// g as ptts_dense_bf16x6_batched filled it; items = nbatch x 32-column slices
+static int resident_launch(DenseArgs g, int slices, int items, int planes_count, hipStream_t st) {
+    const int cus = resident_cus();
+    if (!cus) return PTTS_ELAUNCH;
+    const int wgs = (items + 7) / 8;
+    const dim3 grid((unsigned)(wgs < cus ? wgs : cus));
+#define DNS_RK(NPL, MT) do { if (g.KS == RES_KS) hipLaunchKernelGGL((dense_bf16x6_resident_kernel<NPL, MT, RES_KS>), grid, dim3(THREADS), resident_lds_bytes<NPL>(), st, g, slices, items); \
+                             else hipLaunchKernelGGL((dense_bf16x6_resident_kernel<NPL, MT, 0>), grid, dim3(THREADS), resident_lds_bytes<NPL>(), st, g, slices, items); } while (0)
+#define DNS_R(MT) do { if (planes_count == 1) DNS_RK(1, MT); else DNS_RK(3, MT); } while (0)
+    switch ((g.M + 15) / 16) {
+        case 1: DNS_R(1); break;
+        case 2: DNS_R(2); break;
+        case 3: DNS_R(3); break;
+        case 4: DNS_R(4); break;
+        case 5: DNS_R(5); break;
+        case 6: DNS_R(6); break;
+        case 7: DNS_R(7); break;
+        default: DNS_R(8); break;
+    }
+#undef DNS_R
+#undef DNS_RK
+    return check_launch("dense_bf16x6_batched");
+}
+
 // nbatch products C_z[M,N] = A_z[M,K] . B_z (+ bias) of ONE shape in one launch (blockIdx.z = z): A_z = A + z strideA, C_z = C + z strideC
 // (floats; strideA = 0: the same left operand for every product), B_z = the planes at planes + z stride_planes_bytes.  No input
 // transform, no masks.  planes_count: 3 = fp32 arithmetic (six products), 1 = one bf16 product -- explicit here, whatever
@@ -1401,6 +1627,13 @@ extern "C" int ptts_dense_bf16x6_batched(const float* A, long long strideA, cons
     g.res = nullptr; g.res_rows = 1; g.ldr = 0;
     g.bsA = strideA; g.bsP = stride_planes_bytes / 2; g.bsC = strideC;
     g.stats = nullptr; g.om_scale = g.om_shift = nullptr;
+    // a shared left operand of at most 128 x 128 stays in the LDS and the waves walk (member, 32-column slice) items (the transforms of
+    // the frequency-domain Conv1D are the callers with strideA == 0); the same bits as the kernel below
+    const long long items = (long long)nbatch * ((N + 31) / 32);
+    if (batched_resident_on() && ptts_dense_batched_resident_eligible(strideA, M, N, K, planes_count) && items <= 0x3fffffffLL) {     // (item + 8 G stays an int)
+        g.vec_out = ldc % 4 == 0 && strideC % 4 == 0 && ((uintptr_t)C & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0);      // (per quad: n + 3 < N)
+        return resident_launch(g, (N + 31) / 32, (int)items, planes_count, (hipStream_t)stream);
+    }
     const int cb = (N + NBLK - 1) / NBLK;
     // rows per workgroup: every workgroup of a product reads that product's planes, so fewer row tiles = fewer reads of the right
     // operand, which is most of the traffic of these small-M products
