@@ -680,6 +680,22 @@ int ptts_compose_normalise(const float* y, const int* keepidx, const float* a, c
  * built by one small launch on `stream`; 32-byte aligned.  The entry points above take the table
  * that was built with THEIR parameters: alpha (and fs, nb) are checked, the table's contents
  * are not (band indices read from it are clamped).
+ *
+ * ptts_spec2mcep: out [T, M1] mel-cepstra from x [T, K], the inverse of ptts_mcep2spec: with
+ *   v_k = ln max(|x_k|, FLT_MIN) (is_log != 0: v_k = x_k, a log-envelope already), C[m,k] =
+ *   cos(m wt_k) and the trapezoid weights q_k above, the weighted least-squares fit
+ *     c = argmin sum_k q_k (v_k - sum_m c_m C[m,k])^2 = W v,   W = G^-1 C diag(q),  G = C diag(q) C^T,
+ *   the exact left inverse of ptts_mcep2spec(log_out) for a cepstrum of the same order and the
+ *   L2 projection on the warped axis otherwise (the discrete form of real cepstrum -> SPTK freqt).
+ *   M1 = 2 .. min(512, floor((L/2) (1 - |alpha|) / (1 + |alpha|))): G has condition number about 2
+ *   up to that order and turns singular beyond it (PTTS_EINVAL).  One [T, K] x [K, M1] product,
+ *   fp64 accumulation in a fixed order.
+ *   ptts_spec2mcep_table, for (M1, alpha, dftlen), all fp64: W first, [K][M1p] with M1p = M1 rounded
+ *   up to 4, W[m,k] at table[k * M1p + m], zeros for M1 <= m < M1p; behind it the scratch of the
+ *   build (the nodes wt_k, q_k; sum_k q_k cos(n wt_k), n <= 2 M1 - 2; the Cholesky factor of G),
+ *   which ptts_spec2mcep does not read.  ptts_spec2mcep_table_bytes covers both; four small
+ *   launches on `stream`; 32-byte aligned; a parameter set whose table would exceed 32 MiB is
+ *   PTTS_EINVAL at both entry points.
  * ------------------------------------------------------------------------------------- */
 size_t ptts_mcep_table_bytes(int M1, int dftlen);
 int ptts_mcep_table(float* table, size_t table_bytes, int M1, double alpha, int dftlen, void* stream);
@@ -691,6 +707,10 @@ int ptts_mcep2spec(const float* mcep, float* spec, int T, int M1, double alpha, 
                    double pf_coef, const float* table, size_t table_bytes, void* stream);
 int ptts_fwbnd2spec(const float* fw, float* spec, int T, int nb, double fs, double alpha, int dftlen, int log_out,
                     int postfilter, double pf_coef, const double* table, size_t table_bytes, void* stream);
+size_t ptts_spec2mcep_table_bytes(int M1, int dftlen);
+int ptts_spec2mcep_table(double* table, size_t table_bytes, int M1, double alpha, int dftlen, void* stream);
+int ptts_spec2mcep(const float* x, float* out, int T, int M1, double alpha, int dftlen, int is_log, const double* table,
+                   size_t table_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Pulse-and-noise waveform synthesis of the PML vocoder (csrc/pulsesynth.hip; the definition

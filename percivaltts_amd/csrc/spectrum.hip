@@ -22,6 +22,22 @@
 // order through LDS.  No atomics; a frame's result does not depend on T, on its position or on what else is in the batch.
 // With the post-filter the spectrum kernels recompute the product for the store pass instead of keeping [frames, K] values.
 //
+// spectrum -> mcep:      with v_k = ln max(|x_k|, FLT_MIN) (or x_k, a logarithm already), C[m,k] = cos(m wt_k), q_k as above:
+//                        c = argmin sum_k q_k (v_k - sum_m c_m C[m,k])^2 = W v,  W = G^-1 C diag(q),  G = C diag(q) C^T
+//                        the exact left inverse of mcep -> spectrum (log) for a cepstrum of the same order.  G is well conditioned
+//                        (cond about 2) while M1 <= floor((L/2) (1 - |alpha|) / (1 + |alpha|)): beyond that the widest node
+//                        spacing on the warped axis no longer resolves cos(m wt) and G turns singular.
+// W depends on (M1, alpha, dftlen) only: ptts_spec2mcep_table builds it once, in fp64 throughout.  The nodes wt_k, q_k; the sums
+// S_n = sum_k q_k cos(n wt_k), n <= 2 M1 - 2, which hold all of G because cos a cos b = (cos(a - b) + cos(a + b)) / 2; the
+// Cholesky factor of G in one workgroup (left-looking, a thread owns a row); W by a forward and a backward substitution per bin
+// column, S2M_BN columns per workgroup with the right-hand sides in LDS.  The factor is stored mirrored, A[c][r] = L[max][min],
+// so that both substitutions read the contiguous column A[j][.] at step j.
+// The fit itself is a [T, K] x [K, M1] product with K the reduction axis: a workgroup takes SPEC_TT frames, stages their v over
+// S2M_KC bins in LDS as fp64 (one log per element), and a thread owns one coefficient m and every (256 / MW)-th bin of the chunk,
+// MW = M1 rounded up to a power of two (256 at the most; beyond it blockIdx.y picks the coefficients).  W is stored [K][M1p] so
+// that the threads of a bin read neighbouring addresses.  A coefficient's partial sums meet in a fixed order: butterflies between
+// the lanes of a wave that share m, then the groups' partials in group order through LDS.
+//
 // Rows of the output are K floats long and K is odd, so only every fourth row starts on a 16-byte boundary: the stores are
 // 16 bytes wide with 4-byte alignment (dword-aligned vector stores are legal on gfx950 global memory); a wave's store covers one
 // contiguous KiB.
@@ -36,12 +52,22 @@ constexpr int SPEC_MAX_NB = 1024;       // bands staged in LDS as fp32 [SPEC_TT]
 constexpr int SPEC_MAX_DFTLEN = 1 << 20;
 constexpr int FW_ROWS = 4;              // rows of the fwbnd table: band index, fraction, cos wt_k, q_k
 constexpr double SPEC_PI = 3.14159265358979323846;
+constexpr double SPEC_FLT_MIN = 1.17549435082228751e-38;
+constexpr int S2M_KC = 256;             // bins of a staged chunk of ptts_spec2mcep: fp64 [S2M_KC][SPEC_TT], 16 KiB
+constexpr int S2M_BN = 8;               // bin columns a workgroup of the table's substitutions solves
+constexpr size_t S2M_MAX_TABLE_BYTES = (size_t)32 << 20;    // W and the scratch behind it
 
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
 __device__ __forceinline__ double warp_freq(int k, int L, double alpha) {
     const double w = 2.0 * SPEC_PI * (double)k / (double)L;
     return w + 2.0 * atan2(alpha * sin(w), 1.0 - alpha * cos(w));
+}
+
+// q_k: the trapezoid weight of node wt = wt_k among the nodes wt_0 .. wt_{K-1} on [0, pi]
+__device__ __forceinline__ double warp_weight(int k, int K, int L, double alpha, double wt) {
+    const double below = k > 0 ? warp_freq(k - 1, L, alpha) : wt, above = k < K - 1 ? warp_freq(k + 1, L, alpha) : wt;
+    return 0.5 * (above - below);
 }
 
 // [M1][Kp] fp32: cos(m wt_k), 0 for K <= k < Kp
@@ -73,8 +99,7 @@ __global__ void fwbnd_table_kernel(double* __restrict__ tab, int nb, double fs, 
         idx = (double)b;
         const double wt = warp_freq(k, L, alpha);
         cw = cos(wt);
-        const double below = k > 0 ? warp_freq(k - 1, L, alpha) : wt, above = k < K - 1 ? warp_freq(k + 1, L, alpha) : wt;
-        q = 0.5 * (above - below);
+        q = warp_weight(k, K, L, alpha, wt);
     }
     tab[k] = idx;
     tab[(size_t)Kp + k] = frac;
@@ -339,6 +364,177 @@ __global__ __launch_bounds__(SPEC_MAX_THREADS) void fwbnd_kernel(const float* __
     }
 }
 
+// ---- spectrum -> mcep: the table ----
+// nodes [2][Kp] fp64: wt_k, q_k; zeros for K <= k < Kp
+__global__ void s2m_nodes_kernel(double* __restrict__ nodes, int K, int Kp, int L, double alpha) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= Kp) return;
+    double wt = 0.0, q = 0.0;
+    if (k < K) {
+        wt = warp_freq(k, L, alpha);
+        q = warp_weight(k, K, L, alpha, wt);
+    }
+    nodes[k] = wt;
+    nodes[(size_t)Kp + k] = q;
+}
+
+// S[n] = sum_k q_k cos(n wt_k), one workgroup per n: butterflies, then the waves' partials in wave order
+__global__ __launch_bounds__(SPEC_MAX_THREADS) void s2m_sums_kernel(const double* __restrict__ nodes, double* __restrict__ S, int K,
+                                                                   int Kp) {
+    __shared__ double red[SPEC_MAX_THREADS / 64];
+    const int tid = threadIdx.x, n = blockIdx.x;
+    double s = 0.0;
+    for (int k = tid; k < K; k += SPEC_MAX_THREADS) s += nodes[(size_t)Kp + k] * cos((double)n * nodes[k]);
+    s = wave_sum(s);
+    if ((tid & 63) == 0) red[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+        double t = red[0];
+        for (int w = 1; w < SPEC_MAX_THREADS / 64; ++w) t += red[w];
+        S[n] = t;
+    }
+}
+
+// One workgroup.  A [M1][M1]: G[r][c] = (S[r-c] + S[r+c]) / 2 goes to A[c][r], r >= c, and is factored in place, G = L L^T,
+// left-looking: at column j the thread of row i >= j subtracts sum_{k<j} L[i][k] L[j][k] (A[k][i]: neighbouring threads,
+// neighbouring addresses).  L[i][j] is stored at A[j][i] and at A[i][j].  M1 <= 2 * SPEC_MAX_THREADS rows.
+__global__ __launch_bounds__(SPEC_MAX_THREADS) void s2m_factor_kernel(const double* __restrict__ S, double* A, int M1) {
+    __shared__ double pivot;
+    const int tid = threadIdx.x;
+    for (int idx = tid; idx < M1 * M1; idx += SPEC_MAX_THREADS) {
+        const int c = idx / M1, r = idx - c * M1;
+        if (r >= c) A[idx] = 0.5 * (S[r - c] + S[r + c]);
+    }
+    __syncthreads();
+    for (int j = 0; j < M1; ++j) {
+        double s[2] = {0.0, 0.0};
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = j + tid + u * SPEC_MAX_THREADS;
+            if (i < M1) {
+                double acc = A[(size_t)j * M1 + i];
+                for (int k = 0; k < j; ++k) acc -= A[(size_t)k * M1 + i] * A[(size_t)k * M1 + j];
+                s[u] = acc;
+            }
+        }
+        if (tid == 0) pivot = sqrt(s[0]);       // row j itself
+        __syncthreads();
+        const double d = pivot;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = j + tid + u * SPEC_MAX_THREADS;
+            if (i < M1) {
+                const double v = i == j ? d : s[u] / d;
+                A[(size_t)j * M1 + i] = v;
+                A[(size_t)i * M1 + j] = v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// W[k][.] = G^-1 (q_k cos(m wt_k))_m for the S2M_BN bins from blockIdx.x * S2M_BN: L y = b, then L^T x = y, column-oriented, the
+// right-hand sides B [M1][S2M_BN] in LDS (dynamic: M1 * S2M_BN doubles).  A thread owns a bin and every (256 / S2M_BN)-th row;
+// the pivot's division is repeated by every thread that needs it and written once, after the sweep.
+__global__ __launch_bounds__(SPEC_MAX_THREADS) void s2m_solve_kernel(const double* __restrict__ nodes, const double* __restrict__ A,
+                                                                    double* __restrict__ W, int M1, int M1p, int K, int Kp) {
+    extern __shared__ double B[];
+    constexpr int NR = SPEC_MAX_THREADS / S2M_BN;
+    const int tid = threadIdx.x, b = tid % S2M_BN, r = tid / S2M_BN;
+    const int k0 = blockIdx.x * S2M_BN;
+    for (int i = tid; i < M1 * S2M_BN; i += SPEC_MAX_THREADS) {
+        const int m = i / S2M_BN, k = k0 + i % S2M_BN;
+        B[i] = k < K ? nodes[(size_t)Kp + k] * cos((double)m * nodes[k]) : 0.0;
+    }
+    __syncthreads();
+    for (int j = 0; j < M1; ++j) {
+        const double* col = A + (size_t)j * M1;
+        const double xj = B[j * S2M_BN + b] / col[j];
+        for (int i = j + 1 + r; i < M1; i += NR) B[i * S2M_BN + b] -= col[i] * xj;
+        __syncthreads();
+    }
+    for (int i = tid; i < M1 * S2M_BN; i += SPEC_MAX_THREADS) {
+        const int m = i / S2M_BN;
+        B[i] /= A[(size_t)m * M1 + m];
+    }
+    __syncthreads();
+    for (int j = M1 - 1; j >= 0; --j) {
+        const double* col = A + (size_t)j * M1;                     // col[i] = L[j][i] for i < j
+        const double xj = B[j * S2M_BN + b] / col[j];
+        for (int i = r; i < j; i += NR) B[i * S2M_BN + b] -= col[i] * xj;
+        __syncthreads();
+    }
+    for (int i = tid; i < M1p * S2M_BN; i += SPEC_MAX_THREADS) {
+        const int bb = i / M1p, m = i - bb * M1p, k = k0 + bb;
+        if (k < K) W[(size_t)k * M1p + m] = m < M1 ? B[m * S2M_BN + bb] / A[(size_t)m * M1 + m] : 0.0;
+    }
+}
+
+// ---- spectrum -> mcep: the product ----
+// One workgroup of SPEC_MAX_THREADS threads: frames blockIdx.x * SPEC_TT ..., coefficients blockIdx.y * MW ... (MW a power of
+// two, 2 .. 256).  Thread tid: coefficient tid % MW, bins tid / MW, + 256 / MW, ... of every chunk.
+__global__ __launch_bounds__(SPEC_MAX_THREADS) void spec2mcep_kernel(const float* __restrict__ x, const double* __restrict__ W,
+                                                                    float* __restrict__ out, const int T, const int M1,
+                                                                    const int M1p, const int K, const int MW, const bool is_log) {
+    __shared__ double sv[S2M_KC * SPEC_TT];                         // [bin][frame]; frames behind T and bins behind K are zeros
+    __shared__ double red[SPEC_MAX_THREADS * SPEC_TT];              // [group][MW][SPEC_TT], groups * MW <= SPEC_MAX_THREADS
+    const int tid = threadIdx.x;
+    const int ml = tid & (MW - 1), slice = tid / MW, nslices = SPEC_MAX_THREADS / MW;
+    const int m = blockIdx.y * MW + ml;
+    const long long t0 = (long long)blockIdx.x * SPEC_TT;
+    double acc[SPEC_TT];
+#pragma unroll
+    for (int t = 0; t < SPEC_TT; ++t) acc[t] = 0.0;
+
+    for (int k0 = 0; k0 < K; k0 += S2M_KC) {
+        const int nk = K - k0 < S2M_KC ? K - k0 : S2M_KC;
+        __syncthreads();                                            // the chunk before is used up
+        for (int i = tid; i < S2M_KC * SPEC_TT; i += SPEC_MAX_THREADS) {
+            const int t = i / S2M_KC, kk = i - t * S2M_KC;
+            double v = 0.0;
+            if (t0 + t < T && kk < nk) {
+                v = (double)x[(size_t)(t0 + t) * K + k0 + kk];
+                if (!is_log) {
+                    v = fabs(v);
+                    v = log(v > SPEC_FLT_MIN ? v : SPEC_FLT_MIN);
+                }
+            }
+            sv[kk * SPEC_TT + t] = v;
+        }
+        __syncthreads();
+        if (m < M1) {
+            const double* wp = W + (size_t)k0 * M1p + m;
+            for (int kk = slice; kk < nk; kk += nslices) {
+                const double w = wp[(size_t)kk * M1p];
+#pragma unroll
+                for (int t = 0; t < SPEC_TT; ++t) acc[t] = fma(w, sv[kk * SPEC_TT + t], acc[t]);
+            }
+        }
+    }
+
+    // the slices of one coefficient: first those inside a wave (MW < 64), then one partial per group of max(MW, 64) threads
+    const int GW = MW > 64 ? MW : 64, group = tid / GW, ngroups = SPEC_MAX_THREADS / GW;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        if (o >= MW) {
+#pragma unroll
+            for (int t = 0; t < SPEC_TT; ++t) acc[t] += __shfl_xor(acc[t], o, 64);
+        }
+    if (tid - group * GW < MW) {
+#pragma unroll
+        for (int t = 0; t < SPEC_TT; ++t) red[(group * MW + ml) * SPEC_TT + t] = acc[t];
+    }
+    __syncthreads();
+    for (int i = tid; i < MW * SPEC_TT; i += SPEC_MAX_THREADS) {
+        const int t = i / MW, c = i - t * MW, mo = blockIdx.y * MW + c;
+        if (mo < M1 && t0 + t < T) {
+            double s = red[c * SPEC_TT + t];
+            for (int g = 1; g < ngroups; ++g) s += red[(g * MW + c) * SPEC_TT + t];
+            out[(size_t)(t0 + t) * M1 + mo] = (float)s;
+        }
+    }
+}
+
 static int spec_padded_bins(int dftlen) { return (dftlen / 2 + 1 + 3) / 4 * 4; }
 
 // threads of a workgroup: one per 4 bins, whole waves, at most SPEC_MAX_THREADS
@@ -447,4 +643,69 @@ extern "C" int ptts_fwbnd2spec(const float* fw, float* spec, int T, int nb, doub
                        (hipStream_t)stream, fw, table, spec, T, nb, K, spec_padded_bins(dftlen), log_out != 0, postfilter != 0,
                        pf_coef);
     return check_launch("fwbnd2spec");
+}
+
+// the table of ptts_spec2mcep_table in doubles: W [K][M1p], the nodes [2][Kp], S [2 M1p], A [M1][M1]
+static int s2m_padded_order(int M1) { return (M1 + 3) / 4 * 4; }
+static size_t s2m_nodes_offset(int M1, int dftlen) { return (size_t)(dftlen / 2 + 1) * s2m_padded_order(M1); }
+static size_t s2m_sums_offset(int M1, int dftlen) { return s2m_nodes_offset(M1, dftlen) + 2 * (size_t)spec_padded_bins(dftlen); }
+static size_t s2m_factor_offset(int M1, int dftlen) { return s2m_sums_offset(M1, dftlen) + 2 * (size_t)s2m_padded_order(M1); }
+
+// the largest M1 whose G is well conditioned
+static int s2m_order_limit(double alpha, int dftlen) {
+    return (int)floor((double)(dftlen / 2) * (1.0 - fabs(alpha)) / (1.0 + fabs(alpha)));
+}
+
+extern "C" size_t ptts_spec2mcep_table_bytes(int M1, int dftlen) {
+    if (M1 < 2 || M1 > SPEC_MAX_M1 || !spec_dftlen_ok(dftlen)) return 16;
+    return align_up((s2m_factor_offset(M1, dftlen) + (size_t)M1 * M1) * sizeof(double), 256);
+}
+
+// the checks of (M1, alpha, dftlen) the two spec2mcep entry points share
+static int s2m_args(const char* what, int M1, double alpha, int dftlen) {
+    PTTS_REQUIRE(M1 >= 2 && M1 <= SPEC_MAX_M1, "%s: M1=%d outside [2, %d]", what, M1, SPEC_MAX_M1);
+    PTTS_REQUIRE(spec_dftlen_ok(dftlen), "%s: dftlen=%d (even, 8 .. %d)", what, dftlen, SPEC_MAX_DFTLEN);
+    PTTS_REQUIRE(spec_alpha_ok(alpha), "%s: |alpha|=%g is not below 1", what, alpha);
+    PTTS_REQUIRE(M1 <= s2m_order_limit(alpha, dftlen),
+                 "%s: M1=%d above floor((dftlen/2) (1 - |alpha|) / (1 + |alpha|)) = %d: the fit is singular beyond it", what, M1,
+                 s2m_order_limit(alpha, dftlen));
+    PTTS_REQUIRE(ptts_spec2mcep_table_bytes(M1, dftlen) <= S2M_MAX_TABLE_BYTES, "%s: the table of M1=%d, dftlen=%d takes %zu bytes, above %zu",
+                 what, M1, dftlen, ptts_spec2mcep_table_bytes(M1, dftlen), S2M_MAX_TABLE_BYTES);
+    return PTTS_OK;
+}
+
+extern "C" int ptts_spec2mcep_table(double* table, size_t table_bytes, int M1, double alpha, int dftlen, void* stream) {
+    const int rc = s2m_args("spec2mcep_table", M1, alpha, dftlen);
+    if (rc != PTTS_OK) return rc;
+    PTTS_REQUIRE(table && ((size_t)table & 31) == 0, "spec2mcep_table: null or unaligned table");
+    PTTS_REQUIRE(table_bytes >= ptts_spec2mcep_table_bytes(M1, dftlen), "spec2mcep_table: table %zu < %zu bytes", table_bytes,
+                 ptts_spec2mcep_table_bytes(M1, dftlen));
+    const int K = dftlen / 2 + 1, Kp = spec_padded_bins(dftlen), M1p = s2m_padded_order(M1);
+    double* nodes = table + s2m_nodes_offset(M1, dftlen);
+    double* S = table + s2m_sums_offset(M1, dftlen);
+    double* A = table + s2m_factor_offset(M1, dftlen);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(s2m_nodes_kernel, dim3((Kp + 255) / 256), dim3(256), 0, st, nodes, K, Kp, dftlen, alpha);
+    hipLaunchKernelGGL(s2m_sums_kernel, dim3(2 * M1 - 1), dim3(SPEC_MAX_THREADS), 0, st, nodes, S, K, Kp);
+    hipLaunchKernelGGL(s2m_factor_kernel, dim3(1), dim3(SPEC_MAX_THREADS), 0, st, S, A, M1);
+    hipLaunchKernelGGL(s2m_solve_kernel, dim3((K + S2M_BN - 1) / S2M_BN), dim3(SPEC_MAX_THREADS), (size_t)M1 * S2M_BN * sizeof(double),
+                       st, nodes, A, table, M1, M1p, K, Kp);
+    return check_launch("spec2mcep_table");
+}
+
+extern "C" int ptts_spec2mcep(const float* x, float* out, int T, int M1, double alpha, int dftlen, int is_log, const double* table,
+                              size_t table_bytes, void* stream) {
+    PTTS_REQUIRE(T >= 0, "spec2mcep: T=%d", T);
+    const int rc = s2m_args("spec2mcep", M1, alpha, dftlen);
+    if (rc != PTTS_OK) return rc;
+    if (T == 0) return PTTS_OK;
+    PTTS_REQUIRE(x && out && table, "spec2mcep: null tensor");
+    PTTS_REQUIRE(((size_t)table & 31) == 0 && table_bytes >= ptts_spec2mcep_table_bytes(M1, dftlen),
+                 "spec2mcep: the table of ptts_spec2mcep_table(M1=%d, dftlen=%d) needs %zu aligned bytes, got %zu", M1, dftlen,
+                 ptts_spec2mcep_table_bytes(M1, dftlen), table_bytes);
+    int MW = 2;
+    while (MW < M1 && MW < SPEC_MAX_THREADS) MW *= 2;
+    hipLaunchKernelGGL(spec2mcep_kernel, dim3((T + SPEC_TT - 1) / SPEC_TT, (M1 + MW - 1) / MW), dim3(SPEC_MAX_THREADS), 0,
+                       (hipStream_t)stream, x, table, out, T, M1, s2m_padded_order(M1), dftlen / 2 + 1, MW, is_log != 0);
+    return check_launch("spec2mcep");
 }

@@ -18,7 +18,7 @@ __all__ = [
     'NORM_MEANSTD', 'NORM_MINMAX', 'COMPOSE_MAX_WINS', 'compose_window_taps', 'compose_stats_buffers', 'compose_windows',
     'compose_sqdev', 'compose_normalise',
     'SPECTRUM_MAX_M1', 'SPECTRUM_MAX_NB', 'SPECTRUM_MAX_DFTLEN', 'spectrum_check', 'bark_alpha', 'mcep_postfilter', 'mcep2spec',
-    'fwbnd2spec',
+    'fwbnd2spec', 'SPEC2MCEP_MAX_TABLE_BYTES', 'spec2mcep_order_limit', 'spec2mcep_table_bytes', 'spec2mcep_check', 'spec2mcep',
     'PULSE_MIN_DFTLEN', 'PULSE_MAX_DFTLEN', 'PULSE_F0_FLOOR', 'PULSE_INT_ROWS', 'pulse_check', 'pulse_table', 'noise_mask',
     'pulse_synthesis',
     'COMPRESS_MEAN', 'COMPRESS_LSQ', 'ANALYSIS_NOISY_BELOW', 'analysis_check', 'f0_track', 'frame_harmonics', 'phase_coherence',
@@ -341,6 +341,73 @@ def fwbnd2spec(fw, fs, dftlen=4096, log=False, pp=False, pf_coef=1.4):
     tab, nbytes = _fwbnd_table(fw.device, nbands, fs, alpha, dftlen)
     call('ptts_fwbnd2spec', ptr(fw), ptr(out), T, nbands, float(fs), float(alpha), int(dftlen), int(bool(log)), int(bool(pp)),
          float(pf_coef), ptr(tab), nbytes, stream(), tag=(T, nbands, dftlen))
+    return out
+
+
+SPEC2MCEP_MAX_TABLE_BYTES = 32 << 20      # the table of one (M1, alpha, dftlen): W and the scratch of its build
+
+
+def spec2mcep_order_limit(alpha, dftlen):
+    """The largest M1 = order + 1 whose fit is well conditioned: floor((dftlen/2) (1 - |alpha|) / (1 + |alpha|)).  Beyond it the
+    widest node spacing on the warped axis no longer resolves cos(m wt) and the normal matrix turns singular."""
+    return int(math.floor(float(dftlen // 2) * (1.0 - abs(float(alpha))) / (1.0 + abs(float(alpha)))))
+
+
+def spec2mcep_table_bytes(M1, dftlen):
+    """What ptts_spec2mcep_table_bytes returns, on the host: fp64 W [K][M1p], nodes [2][Kp], sums [2 M1p], factor [M1][M1]."""
+    K, Kp, M1p = dftlen // 2 + 1, (dftlen // 2 + 1 + 3) // 4 * 4, (M1 + 3) // 4 * 4
+    return (8 * (K * M1p + 2 * Kp + 2 * M1p + M1 * M1) + 255) // 256 * 256
+
+
+def spec2mcep_check(order, alpha, dftlen):
+    """ValueError for an (order, alpha, dftlen) the mel-cepstral fit does not take, the conditions of ptts_spec2mcep: dftlen and
+    alpha as spectrum_check, 2 <= order + 1 <= SPECTRUM_MAX_M1, order + 1 within spec2mcep_order_limit, the table within
+    SPEC2MCEP_MAX_TABLE_BYTES.  Touches no device."""
+    spectrum_check(dftlen, alpha, 1.4)
+    if int(order) != order or not 1 <= order <= SPECTRUM_MAX_M1 - 1:
+        raise ValueError('order={} outside [1, {}]'.format(order, SPECTRUM_MAX_M1 - 1))
+    M1, limit = int(order) + 1, spec2mcep_order_limit(alpha, dftlen)
+    if M1 > limit:
+        raise ValueError('order={}: order + 1 is above floor((dftlen/2) (1 - |alpha|) / (1 + |alpha|)) = {} at alpha={}, dftlen={}; '
+                         'the fit is singular beyond it'.format(order, limit, alpha, dftlen))
+    if spec2mcep_table_bytes(M1, int(dftlen)) > SPEC2MCEP_MAX_TABLE_BYTES:
+        raise ValueError('order={} at dftlen={}: the table takes {} bytes, above {}'.format(
+            order, dftlen, spec2mcep_table_bytes(M1, int(dftlen)), SPEC2MCEP_MAX_TABLE_BYTES))
+
+
+def _spec2mcep_table(device, M1, alpha, dftlen):
+    key = ('spec2mcep', device, M1, float(alpha), dftlen)
+    tab = _spectrum_tables.get(key)
+    if tab is None:
+        n = _hip.lib().ptts_spec2mcep_table_bytes(M1, dftlen)
+        tab = torch.empty(n // 8, dtype=torch.float64, device=device)
+        call('ptts_spec2mcep_table', ptr(tab), n, M1, float(alpha), dftlen, stream(), tag=(M1, dftlen))
+        _spectrum_tables[key] = tab
+    return tab, tab.numel() * 8
+
+
+def spec2mcep(spec, alpha, order, log=False):
+    """Amplitude envelope [T,K] or [B,T,K] fp32 device, K = dftlen/2 + 1 bins (`log`: its logarithm) -> mel-cepstra [.., order+1]:
+    the least-squares fit of sum_m c_m cos(m wt_k) to ln max(|spec|, FLT_MIN) under the trapezoid weights of the warped axis
+    (csrc/spectrum.hip), so that spec2mcep(mcep2spec(c)) = c up to rounding.  The argument order is the
+    reference's sp.spec2mcep(SPEC, alpha, order); dftlen is read off K.  The reference's call scales the envelope by fs first
+    (vocoders.py:141), which adds ln fs to c_0 and which its own decompress_spectrum does not undo; that is not reproduced: this
+    is the inverse of the build's mcep2spec."""
+    if not torch.is_tensor(spec) or spec.dim() not in (2, 3):
+        raise ValueError('ops.spec2mcep: expected a [T,K] or [B,T,K] tensor')
+    K = spec.shape[-1]
+    if K < 5 or K > SPECTRUM_MAX_DFTLEN // 2 + 1:
+        raise ValueError('ops.spec2mcep: K={} is not dftlen/2 + 1 of a dftlen in [8, {}]'.format(K, SPECTRUM_MAX_DFTLEN))
+    dftlen = 2 * (K - 1)
+    spec2mcep_check(order, alpha, dftlen)
+    spec, T, K = _spectrum_rows(spec, 'spec2mcep', 5, SPECTRUM_MAX_DFTLEN // 2 + 1, 'K')
+    M1 = int(order) + 1
+    out = torch.empty(tuple(spec.shape[:-1]) + (M1,), dtype=torch.float32, device=spec.device)
+    if T == 0:
+        return out
+    tab, nbytes = _spec2mcep_table(spec.device, M1, alpha, dftlen)
+    call('ptts_spec2mcep', ptr(spec), ptr(out), T, M1, float(alpha), dftlen, int(bool(log)), ptr(tab), nbytes, stream(),
+         tag=(T, M1, dftlen))
     return out
 
 

@@ -98,7 +98,8 @@ def features_compose(rawpaths, fids=None, win_convention='mlpg'):
     windows with MLPG (see compose.compose); 'reference' reproduces the reference's files."""
     fids = readids(cfg.fileids) if fids is None else fids
     spec_path = rawpaths[1] + ':(-1,' + str(vocoder.specsize()) + ')'
-    compose.create_weights_spec(spec_path, fids, cfg.wpath)
+    mcep = getattr(vocoder, 'spec_type', 'fwbnd') == 'mcep'         # the energy is in c_0 then, not in the bands' mean
+    compose.create_weights_spec(spec_path, fids, cfg.wpath, spec_type='mcep' if mcep else 'fwlspec')
     outpaths = [rawpaths[0], spec_path, rawpaths[2] + ':(-1,' + str(vocoder.noisesize()) + ')'] + list(rawpaths[3:])
     normfn = compose.normalise_meanstd_nmnoscale if isinstance(vocoder, vocoders.VocoderPML) else compose.normalise_meanstd
     return compose.compose(outpaths, fids, cfg.outpath, id_valid_start=cfg.id_valid_start, normfn=normfn, wins=vocoder.mlpg_wins,
@@ -111,7 +112,8 @@ def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None,
     <corpus>/wav/*.wav) goes through vocoder.analysisfid_device with the F0 track of `f0in_path` ('dir/*.f0': headerless float32 Hz
     values, one per frame, <= 0 unvoiced) or, with f0in_path None, the track of the build's own estimator
     (vocoder.f0_estimate_device; the reference runs REAPER here), which writes the raw
-    streams `rawpaths` = [f0_path, spec_path, noise_path] (by default the reference's places beside the waveforms); then
+    streams `rawpaths` = [f0_path, spec_path, noise_path] (by default the reference's places beside the waveforms; for a vocoder
+    with spec_type 'mcep' the spectral stream goes to <base>_mcep<N>/*.mcep and the weights come from c_0); then
     features_compose.  f0_min / f0_max default to the reference's cfg.vocoder_f0_min / cfg.vocoder_f0_max.  `preproc_hp`: the cut-off
     in Hz of the high-pass filter in front of the analysis, 'auto' for f0_min as in the reference, None for no filter.  A file
     that is not sampled at the vocoder's rate, or any file with preproc_hp, goes through vocoder.preprocwav (resampling, then the
@@ -123,7 +125,9 @@ def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None,
     wav_path = cp + 'wav/*.wav' if wav_path is None else wav_path
     if rawpaths is None:
         base = os.path.dirname(wav_path) + '_PML'
-        rawpaths = [base + '_lf0/*.lf0', base + '_fwlspec' + str(vocoder.specsize()) + '/*.fwlspec',
+        spec_raw = ('_mcep' + str(vocoder.specsize()) + '/*.mcep' if getattr(vocoder, 'spec_type', 'fwbnd') == 'mcep'
+                    else '_fwlspec' + str(vocoder.specsize()) + '/*.fwlspec')
+        rawpaths = [base + '_lf0/*.lf0', base + spec_raw,
                     base + '_fwnm' + str(vocoder.noisesize()) + '/*.fwnm']
     if preproc_hp == 'auto':
         preproc_hp = f0_min

@@ -12,6 +12,9 @@ section 3); `synthesis` keeps its name for pulsemodel's waveform and keeps raisi
 `analysisf_device` / `analysisfid_device` around it) is the build's own waveform analysis for the same parameters
 (csrc/analysis.hip), from a caller's F0 track or, without one, from the build's own F0 estimator
 (`VocoderF0Spec.f0_estimate_device`, csrc/f0.hip); `compress_spectrum` is the inverse of `decompress_spectrum` for 'fwbnd'.
+`VocoderF0Spec.compress_spectrum_device` is that inverse for both spectral types: for 'mcep' the build's own least-squares fit on
+the warped axis (ops.spec2mcep, csrc/spectrum.hip) in the place of SPTK's, for which `compress_spectrum` keeps
+its name and keeps raising; `analysis_device` takes either type.
 `analysisf` / `analysisfid` keep their names for pulsemodel's analysis and keep raising.  `Vocoder.preprocwav` (vocoders.py:45-63) is
 the step in front of the analysis, on the device (csrc/preproc.hip): the build's own rational-ratio resampler in
 the place of pulsemodel's, and the zero-phase order-4 Butterworth high-pass with `highpass` as the cut-off in Hz.
@@ -197,13 +200,14 @@ class VocoderF0Spec(Vocoder):
         """Amplitude envelope [T, K] -> compressed spectral columns [T, spec_size] (vocoders.py:134-145), on the device: 'fwbnd'
         log-bands by the least-squares inverse of decompress_spectrum (ops.fwbnd_compress), so that
         compress_spectrum(decompress_spectrum(y)) = y; dftlen is read off K = dftlen/2 + 1 as in the reference.  'mcep' is a
-        ValueError: the SPTK fit behind it is not built.  As in the reference the dispatch is on self.spec_type and the `spec_type`
-        argument is not looked at; spec_size None means self.spec_size.  numpy in -> numpy out, device tensor in -> device tensor
-        out."""
+        ValueError: the SPTK fit behind it is not built (compress_spectrum_device has the build's own).  As in the reference the
+        dispatch is on self.spec_type and the `spec_type` argument is not looked at; spec_size None means self.spec_size.  numpy
+        in -> numpy out, device tensor in -> device tensor out."""
         import torch
         from . import backend_hip, ops_offline as ops
         if self.spec_type == 'mcep':
-            raise ValueError("compress_spectrum: the 'mcep' fit (SPTK) is not part of this build")
+            raise ValueError("compress_spectrum: the 'mcep' fit (SPTK) is not part of this build; "
+                             "compress_spectrum_device has the build's own mel-cepstral fit")
         if self.spec_type != 'fwbnd':
             raise ValueError("spec_type is 'fwbnd' or 'mcep', got {!r}".format(self.spec_type))
         spec_size = self.spec_size if spec_size is None else spec_size
@@ -212,6 +216,28 @@ class VocoderF0Spec(Vocoder):
         if as_numpy:
             x = torch.from_numpy(np.ascontiguousarray(SPEC, dtype=np.float32)).to(backend_hip.device())
         COMPSPEC = ops.fwbnd_compress(x.contiguous(), self.fs, spec_size, mode='lsq')
+        return COMPSPEC.cpu().numpy() if as_numpy else COMPSPEC
+
+    def compress_spectrum_device(self, SPEC, spec_size=None, log=False):
+        """Amplitude envelope [T, K] (`log`: its logarithm) -> compressed spectral columns [T, spec_size], the inverse of
+        decompress_spectrum for either spectral type, on the device: 'fwbnd' as compress_spectrum; 'mcep' the mel-cepstrum of order
+        spec_size - 1 by the build's own fit, ops.spec2mcep(SPEC, bark_alpha(fs), spec_size - 1, log).  The
+        reference's 'mcep' branch scales SPEC by fs first (vocoders.py:141), which its decompress_spectrum does not undo; that is
+        not reproduced.  dftlen is read off K; spec_size None means self.spec_size.  numpy in -> numpy out, device tensor in ->
+        device tensor out."""
+        import torch
+        from . import backend_hip, ops_offline as ops
+        if self.spec_type not in ('fwbnd', 'mcep'):
+            raise ValueError("spec_type is 'fwbnd' or 'mcep', got {!r}".format(self.spec_type))
+        spec_size = self.spec_size if spec_size is None else spec_size
+        as_numpy = not torch.is_tensor(SPEC)
+        x = SPEC
+        if as_numpy:
+            x = torch.from_numpy(np.ascontiguousarray(SPEC, dtype=np.float32)).to(backend_hip.device())
+        if self.spec_type == 'fwbnd':
+            COMPSPEC = ops.fwbnd_compress(x.contiguous(), self.fs, spec_size, mode='lsq', log=log)
+        else:
+            COMPSPEC = ops.spec2mcep(x.contiguous(), bark_alpha(self.fs), spec_size - 1, log=log)
         return COMPSPEC.cpu().numpy() if as_numpy else COMPSPEC
 
     def f0_estimate_device(self, wav, f0_min, f0_max):
@@ -281,17 +307,22 @@ class VocoderPML(VocoderF0Spec):
 
     def analysis_device(self, wav, f0, f0_min, f0_max):
         """A mono waveform at self.fs (any float array) and an F0 track in Hz, one value per frame at shift * i (<= 0: unvoiced;
-        None: the track of f0_estimate_device) -> the parameters [T, featuressizeraw()] float32, columns ln f0 | spec bands |
-        noise-mask bands, by the build's own analysis
+        None: the track of f0_estimate_device) -> the parameters [T, featuressizeraw()] float32, columns ln f0 | spec bands or
+        mel-cepstrum | noise-mask bands, by the build's own analysis
         (DESIGN.md section 3): ops.f0_track on the host, then the harmonic envelope and the phase-distortion phasors of every frame
-        (ops.frame_harmonics), their coherence over neighbouring frames as the noise mask (ops.phase_coherence) and the least-squares
-        band compression of the envelope (ops.fwbnd_compress).  The counterpart of synthesis_device."""
+        (ops.frame_harmonics), their coherence over neighbouring frames as the noise mask (ops.phase_coherence) and the compression
+        of the log-envelope by self.spec_type: 'fwbnd' the least-squares band values (ops.fwbnd_compress), 'mcep' the mel-cepstrum
+        of order spec_size - 1 (ops.spec2mcep).  The noise mask is on the fwbnd axis either way.  The counterpart of
+        synthesis_device."""
         import torch
         from . import backend_hip, ops_offline as ops
-        if self.spec_type != 'fwbnd':
-            raise ValueError("analysis_device: spec_type {!r} is not built, only 'fwbnd'".format(self.spec_type))
+        if self.spec_type not in ('fwbnd', 'mcep'):
+            raise ValueError("analysis_device: spec_type is 'fwbnd' or 'mcep', got {!r}".format(self.spec_type))
         hcap = ops.analysis_check(self.dftlen, self.fs, self.shift, f0_min, f0_max)
-        ops.fwbnd_compress_check(self.spec_size, self.fs, self.dftlen)
+        if self.spec_type == 'fwbnd':
+            ops.fwbnd_compress_check(self.spec_size, self.fs, self.dftlen)
+        else:
+            ops.spec2mcep_check(self.spec_size - 1, bark_alpha(self.fs), self.dftlen)
         ops.fwbnd_compress_check(self.nm_size, self.fs, self.dftlen)
         wav = np.asarray(wav, dtype=np.float64)
         if wav.ndim != 1 or not np.isfinite(wav).all():
@@ -304,7 +335,7 @@ class VocoderPML(VocoderF0Spec):
         f = torch.from_numpy(track).to(dev)
         lspec, u = ops.frame_harmonics(w, f, self.shift, self.fs, self.dftlen, hcap, log=True)
         _, nm = ops.phase_coherence(u, f, self.shift, self.fs, self.dftlen, self.nm_size)
-        bands = ops.fwbnd_compress(lspec, self.fs, self.spec_size, mode='lsq', log=True)
+        bands = self.compress_spectrum_device(lspec, log=True)
         lf0 = np.log(track.astype(np.float64)).astype(np.float32)
         return np.concatenate([lf0[:, None], bands.cpu().numpy(), nm.cpu().numpy()], axis=1)
 

@@ -4,10 +4,12 @@ section 6: ptts_mcep2spec and ptts_fwbnd2spec as GB/s against the 4 T K bytes th
 figure bench.py's roofline uses (8 TB/s), beside a device-to-device copy_ of the same size on the same box; ptts_mcep_postfilter
 as frames/s, beside the numpy closed form on the host (a sample of the frames, on the threads the environment allows); and, for
 the same inputs, e32 (the float32 closed form's worst error against fp64) next to the kernel's, on a sample of the frames.
+The spec2mcep leg runs ptts_spec2mcep on the log-envelopes of --fit-frames of the cepstra and reports the time of one build of
+its table, the time of a call, the rate against the 4 T K bytes it has to read, and the round trip's worst error.
 
 Default size: T = 100 000 frames, M1 = 60 mel-cepstra, nb = 129 bands, dftlen = 4096, fs = 32 000.
 
-    python tools/spectrum_probe.py [--frames 100000] [--M1 60] [--nb 129] [--dftlen 4096] [--fs 32000] [--reps 20] [--host-frames 2000]
+    python tools/spectrum_probe.py [--frames 100000] [--M1 60] [--nb 129] [--dftlen 4096] [--fs 32000] [--reps 20] [--host-frames 2000] [--fit-frames 4000]
 """
 from __future__ import print_function
 
@@ -70,6 +72,7 @@ def main():
     ap.add_argument('--fs', type=float, default=32000.0)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--host-frames', type=int, default=2000)
+    ap.add_argument('--fit-frames', type=int, default=4000)
     args = ap.parse_args()
 
     import torch
@@ -102,6 +105,21 @@ def main():
         res[name] = {'s': t, 'GBps_written': out_bytes / t * 1e-9, 'frac_of_8TBps': out_bytes / t * 1e-9 / PEAK_HBM_GBPS}
     t = timed(lambda: ops.mcep_postfilter(cd, alpha, dftlen=L), args.reps)
     res['mcep_postfilter'] = {'s': t, 'frames_per_s': T / t, 'fp64_fma_per_s': 1.0 * T * K * M1 / t}
+
+    # the fit: table build (its four launches on a fresh buffer), then the product on log-envelopes of the same cepstra
+    from percivaltts_amd import _hip
+    nf = min(args.fit_frames, T)
+    nbytes = _hip.lib().ptts_spec2mcep_table_bytes(M1, L)
+    tab = torch.empty(nbytes // 8, dtype=torch.float64, device='cuda')
+    tb = timed(lambda: _hip.call('ptts_spec2mcep_table', _hip.ptr(tab), nbytes, M1, float(alpha), L, _hip.stream()), args.reps)
+    la = ops.mcep2spec(cd[:nf], alpha, dftlen=L, log=True)
+    t = timed(lambda: ops.spec2mcep(la, alpha, M1 - 1, log=True), args.reps)
+    tl = timed(lambda: ops.spec2mcep(la, alpha, M1 - 1), args.reps)            # with the logarithm of every element
+    res['spec2mcep'] = {'frames': nf, 'table_bytes': nbytes, 'table_build_s': tb, 's': t, 's_linear_input': tl,
+                        'frames_per_s': nf / t, 'GBps_read': 4.0 * nf * K / t * 1e-9,
+                        'frac_of_8TBps': 4.0 * nf * K / t * 1e-9 / PEAK_HBM_GBPS, 'fp64_fma_per_s': 1.0 * nf * K * M1 / t,
+                        'round_trip_worst': float((ops.spec2mcep(la, alpha, M1 - 1, log=True) - cd[:nf]).abs().max())}
+    del la, tab
 
     # host: the numpy closed form in fp64 on a sample of the frames
     n = min(args.host_frames, T)
