@@ -380,7 +380,27 @@ int ptts_conv1d_freq_wgrad_inverse(const float* Gt, const float* t2, float* dW, 
 /* nbatch products of one shape in one launch: C_z[M,N] = A_z[M,K] . B_z (+ bias), A_z = A + z*strideA and C_z = C + z*strideC (floats;
  * strideA = 0 shares the left operand), B_z = the planes at planes + z*stride_planes_bytes (ptts_split3_dense_weight[_grouped] layout).
  * planes_count 3 = fp32 arithmetic (six bf16 products), 1 = one bf16 product.  The building block of the frequency-domain context
- * Conv1D (kl.Conv1D of networktts.py:116-120 as DFT -> per-frequency products -> inverse DFT). */
+ * Conv1D (kl.Conv1D of networktts.py:116-120 as DFT -> per-frequency products -> inverse DFT).
+ *
+ * The fp32-rows form of the right operand: planes_count = 3 | PTTS_PLANES_ROWS or 1 | PTTS_PLANES_ROWS.  `planes` is then a HOST pointer
+ * to one ptts_dense_rows_desc, read during the call, and stride_planes_bytes is ignored: the kernel reads B_z [K][N] as fp32 where it
+ * lies and splits it in front of each k-step's matrix instructions, so a right operand that is used once needs no split pass.
+ *   windows == 0: row k of member z is B + z*strideB + k*ldb.
+ *   windows == 1: z = b*NS + s (nbatch = nB*NS) is the window of ptts_split3_frame_windows: row k = row row_off + s*S + k of
+ *                 utterance b of B [nB][T][ldb]; rows outside [0, T) are zero.
+ *   Rows k >= kvalid (kvalid <= K) are zero in both forms.  A row that counts as zero is never read.
+ *   mirror_cols = Kh > 0 (a multiple of 4, N <= Kh, Kh + N <= ldc, M even): the lane that stores C_z[m][n] also stores C_z[m ^ 1][Kh + n],
+ *                 the value itself for even m and the negated value for odd m -- what ptts_dft_mirror writes, bit for bit.
+ * The results are those of the planes form on the planes of the same rows, bit for bit.  The form exists on the resident-left kernel
+ * only: where ptts_dense_batched_resident_eligible says 0 or the switch is off the call returns PTTS_EINVAL and launches nothing.  The
+ * source may span at most 2^30 floats (offsets are 32-bit byte offsets). */
+#define PTTS_PLANES_ROWS 0x100
+typedef struct ptts_dense_rows_desc {
+    const float* B;
+    long long strideB, ldb;
+    int windows, nB, T, NS, S, row_off;
+    int kvalid, mirror_cols;
+} ptts_dense_rows_desc;
 int ptts_dense_bf16x6_batched(const float* A, long long strideA, const void* planes, long long stride_planes_bytes,
                               const float* bias, float* C, long long strideC, int nbatch, int M, int N, int K,
                               long long lda, long long ldc, int planes_count, void* stream);
@@ -389,8 +409,10 @@ int ptts_dense_bf16x6_batched(const float* A, long long strideA, const void* pla
  * with no barrier after the prologue; the results are those of the general kernel bit for bit.  On by default; the environment variable
  * PTTS_DENSE_BATCHED_RESIDENT=0 (read once) or ptts_set_dense_batched_resident(0) sends every batched product to the general kernel.
  * ptts_set_dense_batched_resident returns the previous setting; ptts_dense_batched_resident_eligible returns 1 when a call of that
- * shape takes the resident-left kernel while the switch is on, 0 otherwise, and launches nothing. */
+ * shape takes the resident-left kernel while the switch is on, 0 otherwise, and launches nothing; ptts_dense_batched_resident_enabled
+ * returns the switch. */
 int ptts_set_dense_batched_resident(int on);
+int ptts_dense_batched_resident_enabled(void);
 int ptts_dense_batched_resident_eligible(long long strideA, int M, int N, int K, int planes_count);
 /* nbatch transposed-reduction products of one shape in one launch: C_z[k][n] = sum_{m<M} A_z[m][k] B_z[m][n], k < Kin, n < N.  Both
  * operands are fp32, row-major (lda, ldb) and are split inside the kernel, so a right operand that is used once needs no planes; A_z =

@@ -95,6 +95,19 @@ WGradDesc = _structure('WGradDesc', 'ptts_wgrad_desc')                          
 DenseWgradReduceDesc = _structure('DenseWgradReduceDesc', 'ptts_dense_wgrad_reduce_desc')   # the partial rows of one weight-gradient product
 DenseSplitDesc = _structure('DenseSplitDesc', 'ptts_dense_split_desc')                   # one weight of a grouped plane split
 Conv2dReduceDesc = _structure('Conv2dReduceDesc', 'ptts_conv2d_reduce_desc')             # one queued conv2d backward pass
+DenseRowsDesc = _structure('DenseRowsDesc', 'ptts_dense_rows_desc')                      # the fp32-rows form of a batched product's right operand
+
+
+def _define(name):
+    """The integer value of `#define NAME value` in the header."""
+    with open(HEADER_PATH) as f:
+        m = re.search(r'^[ \t]*#[ \t]*define[ \t]+{}[ \t]+(\w+)'.format(name), f.read(), flags=re.M)
+    if m is None:
+        raise HipLibraryError('percival_hip.h: no #define {}'.format(name))
+    return int(m.group(1), 0)
+
+
+PLANES_ROWS = _define('PTTS_PLANES_ROWS')            # flag bit in planes_count of ptts_dense_bf16x6_batched: `planes` is a DenseRowsDesc
 
 _lib = None
 

@@ -660,9 +660,28 @@ template <int NPL> constexpr size_t resident_lds_bytes() { return (size_t)RES_KS
 // MT = ceil(M / 16) row tiles.  KSC = the number of k-steps when it is RES_KS (the transforms: K = 120, 124), 0 = any (g.KS): with a
 // compile-time count the loads of an item are a fixed sequence, and the wait in front of k-step s covers the loads up to s alone -- not
 // the later k-steps' and not the stores of the item before.
-template <int NPL, int MT = RES_M / 16, int KSC = 0>
-__global__ __launch_bounds__(THREADS) void dense_bf16x6_resident_kernel(DenseArgs g, int slices, int items) {
+//
+// ROWS: the right operand as fp32 rows (ptts_dense_rows_desc: strided rows, or the windows of a frame sequence) instead of planes.  A
+// wave loads an item's fragments as the split pass did -- a lane's 8 consecutive k of one column, eight 4-byte loads per column tile and
+// k-step, 64 VGPRs for an item instead of the planes' 96 -- and splits the 16 values of a k-step right in front of that k-step's MFMAs;
+// the registers are refilled with the next item's rows behind them, as above.  Through registers and not through the free 64 KB of LDS:
+// the waves stay independent of each other (no barrier, no LDS write after the prologue), and the access pattern is the one the split
+// pass already had.  A row or column that counts as zero is not read: the lane's offset is clamped to the source's first float, and the
+// select that makes the zero waits with the split, so that it does not wait for the load in front of the k-steps before.
+// r.mirror = Kh > 0: the store of row m, column n is repeated at row m ^ 1, column Kh + n, negated for odd m (dft_mirror_kernel).
+struct RowsArgs {
+    const float* B; long long strideB;
+    int ldb, windows, T, NS, S, row_off, kvalid, mirror;
+};
+// what a lane knows of an item's rows: for column tile j its offset of (k = 8 lg, its column) from r.B and the number of rows that are
+// read, len (0 for a column beyond N); t0 = 8 lg - (first row that is read).  Row k = 8 lg + c is read when t0 + c < len.
+template <bool ROWS> struct RowsItemT { unsigned base[2], len[2], t0; };       // (base in bytes)
+template <> struct RowsItemT<false> {};
+
+template <int NPL, int MT = RES_M / 16, int KSC = 0, bool ROWS = false>
+__global__ __launch_bounds__(THREADS) void dense_bf16x6_resident_kernel(DenseArgs g, int slices, int items, RowsArgs r) {
     extern __shared__ __attribute__((aligned(16))) u16 lds_r[];
+    using RowsItem = RowsItemT<ROWS>;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
@@ -693,11 +712,53 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_resident_kernel(DenseArg
 #pragma unroll
             for (int p = 0; p < NPL; ++p) wf[s][j][p] = *reinterpret_cast<const bf16x8*>(wp + p * ps + (size_t)j * KS * 512);
     };
+    // ---- ROWS: the same fragments as fp32, wr[s][j][e] = B_z[32 s + 8 lg + e][32 sl + 16 j + li]
+    float wr[ROWS ? RES_KS : 1][2][8];
+    auto rows_item = [&](int it) {
+        RowsItem q;
+        if constexpr (ROWS) {
+            const int z = it / slices, sl = it - z * slices;
+            long long zoff; int rlo = 0, rhi = r.kvalid;
+            if (r.windows) {
+                const int b = z / r.NS, sg = z - b * r.NS;
+                const int r0 = r.row_off + sg * r.S;              // source row of window row 0 (may be negative)
+                zoff = ((long long)b * r.T + r0) * r.ldb;
+                rlo = r0 < 0 ? -r0 : 0;
+                rhi = min(r.kvalid, r.T - r0);
+            } else {
+                zoff = (long long)z * r.strideB;
+            }
+            const unsigned len = (unsigned)max(rhi - rlo, 0);
+            q.t0 = (unsigned)(8 * lg - rlo);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int n = 32 * sl + 16 * j + li;
+                q.len[j] = n < g.N ? len : 0u;
+                q.base[j] = 4u * ((unsigned)zoff + (unsigned)(8 * lg) * (unsigned)r.ldb + (unsigned)n);      // (bytes, modulo 2^32; right wherever it is used)
+            }
+        }
+        return q;
+    };
+    auto load_r = [&](const RowsItem& q, int s) {
+        if constexpr (ROWS) {
+            const unsigned ldb4 = 4u * (unsigned)r.ldb;            // a 32-bit byte offset from a uniform base: one address register per load
+            unsigned a[2] = {q.base[0] + 32u * s * ldb4, q.base[1] + 32u * s * ldb4};
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {                     // (the two column tiles of a row lie side by side: one after the other)
+                    const unsigned c = 32 * s + e;
+                    wr[ROWS ? s : 0][j][e] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(r.B) + (q.t0 + c < q.len[j] ? a[j] : 0u));
+                    a[j] += ldb4;                                 // (row by row: one scalar, not one per row)
+                }
+        }
+    };
     // the first item's fragments go out behind A's quads and in front of the split: no branch here -- a wave without an item loads the
     // last item's and drops them -- so that the split waits for A alone
+    RowsItem qcur = rows_item(live ? item : items - 1);
 #pragma unroll
     for (int s = 0; s < RES_KS; ++s) {
-        if (s < KS) load_w(live ? item : items - 1, s);
+        if (s < KS) { if constexpr (ROWS) load_r(qcur, s); else load_w(live ? item : items - 1, s); }
         __builtin_amdgcn_sched_barrier(0);                    // k-step by k-step: loads come back in the order they went out
     }
 
@@ -727,7 +788,7 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_resident_kernel(DenseArg
     const int boff = li * BK + ((lg ^ ((li >> 1) & 2)) << 3);
     // One item.  The bias goes into registers in front of the k-steps: loads come back in order, and behind the next item's fragments
     // it would hold the store until all of them are in.
-    auto run_item = [&](const int it, const bool has_next, const int next) __attribute__((always_inline)) {
+    auto run_item = [&](const int it, const bool has_next, const int next, const RowsItem& qc, const RowsItem& qn) __attribute__((always_inline)) {
         const int z = it / slices, sl = it - z * slices;
         f32x4 bv[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
         if (g.bias) {                                         // (four plain loads per tile, columns beyond N clamped and never stored: no branch per lane)
@@ -743,18 +804,37 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_resident_kernel(DenseArg
         for (int s = 0; s < RES_KS; ++s) {
             if (s < KS) {
                 const u16* as = lds_r + s * NPL * RES_PL + boff;
+                bf16x8 ws[2][NPL];                            // ROWS: this k-step's planes, made here (split3_dense_weight_strided_kernel's)
+                if constexpr (ROWS) {
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        unsigned q[3][4];
+#pragma unroll
+                        for (int h = 0; h < 4; ++h) {
+                            const unsigned c = 32 * s + 2 * h;
+                            const float v0 = qc.t0 + c < qc.len[j] ? wr[ROWS ? s : 0][j][2 * h] : 0.f;
+                            const float v1 = qc.t0 + c + 1 < qc.len[j] ? wr[ROWS ? s : 0][j][2 * h + 1] : 0.f;
+                            if (NPL == 3) split3_pair(v0, v1, q[0][h], q[1][h], q[2][h]);
+                            else q[0][h] = pk_bf16(v0, v1);
+                        }
+#pragma unroll
+                        for (int p = 0; p < NPL; ++p) ws[j][p] = __builtin_bit_cast(bf16x8, make_uint4(q[p][0], q[p][1], q[p][2], q[p][3]));
+                    }
+                }
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {
                     bf16x8 bf[NPL];
 #pragma unroll
                     for (int p = 0; p < NPL; ++p) bf[p] = *reinterpret_cast<const bf16x8*>(as + p * RES_PL + i * 16 * BK);
+#define DNS_WF(J, PW) (ROWS ? ws[J][PW < NPL ? PW : 0] : wf[s][J][PW < NPL ? PW : 0])
 #define DNS_MM(PA, PW)                                                                                    \
-                    acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][0][PW < NPL ? PW : 0], bf[PA < NPL ? PA : 0], acc[i][0], 0, 0, 0);    \
-                    acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][1][PW < NPL ? PW : 0], bf[PA < NPL ? PA : 0], acc[i][1], 0, 0, 0);
+                    acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(DNS_WF(0, PW), bf[PA < NPL ? PA : 0], acc[i][0], 0, 0, 0);    \
+                    acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(DNS_WF(1, PW), bf[PA < NPL ? PA : 0], acc[i][1], 0, 0, 0);
                     DNS_PRODUCTS_NPL(NPL, DNS_MM);
 #undef DNS_MM
+#undef DNS_WF
                 }
-                if (has_next) load_w(next, s);                // this k-step's registers are free: the next item's loads go out
+                if (has_next) { if constexpr (ROWS) load_r(qn, s); else load_w(next, s); }      // this k-step's registers are free: the next item's loads go out
                 // (a compile-time KS makes the k-steps one basic block; moved up across this line, the later steps' LDS reads cost registers
                 // the fragments in flight need)
                 if (KSC) __builtin_amdgcn_sched_barrier(0);
@@ -770,7 +850,11 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_resident_kernel(DenseArg
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {
                     const int m = 16 * i + li;
-                    if (m < g.M) *reinterpret_cast<f32x4*>(Cz + (long long)m * g.ldc + n) = acc[i][j] + bv[j];
+                    if (m < g.M) {
+                        const f32x4 v = acc[i][j] + bv[j];
+                        *reinterpret_cast<f32x4*>(Cz + (long long)m * g.ldc + n) = v;
+                        if (ROWS && r.mirror > 0) *reinterpret_cast<f32x4*>(Cz + (long long)(m ^ 1) * g.ldc + r.mirror + n) = (li & 1) ? -v : v;
+                    }
                 }
             } else {
 #pragma unroll
@@ -779,7 +863,11 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_resident_kernel(DenseArg
 #pragma unroll
                     for (int i = 0; i < MT; ++i) {
                         const int m = 16 * i + li;
-                        if (m < g.M) Cz[(long long)m * g.ldc + n + e] = acc[i][j][e] + bv[j][e];
+                        if (m < g.M) {
+                            const float v = acc[i][j][e] + bv[j][e];
+                            Cz[(long long)m * g.ldc + n + e] = v;
+                            if (ROWS && r.mirror > 0) Cz[(long long)(m ^ 1) * g.ldc + r.mirror + n + e] = (li & 1) ? -v : v;
+                        }
                     }
                 }
             }
@@ -789,11 +877,15 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_resident_kernel(DenseArg
     // k-step s is for the fragments up to s.  In the loop the stores of the item before are in flight too; loads and stores do not
     // come back in one order, so there the first wait of an item is for everything.
     int next = item + stride;
-    run_item(item, next < items, next);
+    RowsItem qnext = qcur;
+    if (ROWS && next < items) qnext = rows_item(next);
+    run_item(item, next < items, next, qcur, qnext);
     while (next < items) {
         item = next;
         next = item + stride;
-        run_item(item, next < items, next);
+        qcur = qnext;
+        if (ROWS && next < items) qnext = rows_item(next);
+        run_item(item, next < items, next, qcur, qnext);
     }
 }
 
@@ -1553,18 +1645,19 @@ extern "C" int ptts_set_dense_batched_resident(int on) {
     g_batched_resident = on ? 1 : 0;
     return prev;
 }
+extern "C" int ptts_dense_batched_resident_enabled(void) { return batched_resident_on(); }
 extern "C" int ptts_dense_batched_resident_eligible(long long strideA, int M, int N, int K, int planes_count) {
     return (strideA == 0 && M > 0 && M <= RES_M && N > 0 && K > 0 && K <= RES_K && K % 4 == 0 &&
             (planes_count == 1 || planes_count == 3)) ? 1 : 0;
 }
 
-template <int NPL, int MT>
+template <int NPL, int MT, bool ROWS>
 static void resident_set_lds() {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bf16x6_resident_kernel<NPL, MT, 0>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bf16x6_resident_kernel<NPL, MT, 0, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)resident_lds_bytes<NPL>());
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bf16x6_resident_kernel<NPL, MT, RES_KS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bf16x6_resident_kernel<NPL, MT, RES_KS, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)resident_lds_bytes<NPL>());
-    if constexpr (MT > 1) resident_set_lds<NPL, MT - 1>();
+    if constexpr (MT > 1) resident_set_lds<NPL, MT - 1, ROWS>();
 }
 // compute units of the current device (asked once per device; the first call also raises the kernels' LDS limit there); 0: error set
 static int resident_cus() {
@@ -1577,20 +1670,24 @@ static int resident_cus() {
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
             set_error("dense_bf16x6_batched: the device does not tell its compute units"); return 0;
         }
-        resident_set_lds<3, RES_M / 16>();
-        resident_set_lds<1, RES_M / 16>();
+        resident_set_lds<3, RES_M / 16, false>();
+        resident_set_lds<1, RES_M / 16, false>();
+        resident_set_lds<3, RES_M / 16, true>();
+        resident_set_lds<1, RES_M / 16, true>();
         cus[dev] = n;
     }
     return cus[dev];
 }
-// g as ptts_dense_bf16x6_batched filled it; items = nbatch x 32-column slices
-static int resident_launch(DenseArgs g, int slices, int items, int planes_count, hipStream_t st) {
+// g as ptts_dense_bf16x6_batched filled it; items = nbatch x 32-column slices; rows: the fp32-rows form of the right operand, or NULL
+static int resident_launch(DenseArgs g, int slices, int items, int planes_count, const RowsArgs* rows, hipStream_t st) {
     const int cus = resident_cus();
     if (!cus) return PTTS_ELAUNCH;
     const int wgs = (items + 7) / 8;
     const dim3 grid((unsigned)(wgs < cus ? wgs : cus));
-#define DNS_RK(NPL, MT) do { if (g.KS == RES_KS) hipLaunchKernelGGL((dense_bf16x6_resident_kernel<NPL, MT, RES_KS>), grid, dim3(THREADS), resident_lds_bytes<NPL>(), st, g, slices, items); \
-                             else hipLaunchKernelGGL((dense_bf16x6_resident_kernel<NPL, MT, 0>), grid, dim3(THREADS), resident_lds_bytes<NPL>(), st, g, slices, items); } while (0)
+    const RowsArgs r = rows ? *rows : RowsArgs{};
+#define DNS_RKR(NPL, MT, KSC) do { if (rows) hipLaunchKernelGGL((dense_bf16x6_resident_kernel<NPL, MT, KSC, true>), grid, dim3(THREADS), resident_lds_bytes<NPL>(), st, g, slices, items, r); \
+                                   else hipLaunchKernelGGL((dense_bf16x6_resident_kernel<NPL, MT, KSC, false>), grid, dim3(THREADS), resident_lds_bytes<NPL>(), st, g, slices, items, r); } while (0)
+#define DNS_RK(NPL, MT) do { if (g.KS == RES_KS) DNS_RKR(NPL, MT, RES_KS); else DNS_RKR(NPL, MT, 0); } while (0)
 #define DNS_R(MT) do { if (planes_count == 1) DNS_RK(1, MT); else DNS_RK(3, MT); } while (0)
     switch ((g.M + 15) / 16) {
         case 1: DNS_R(1); break;
@@ -1604,6 +1701,7 @@ static int resident_launch(DenseArgs g, int slices, int items, int planes_count,
     }
 #undef DNS_R
 #undef DNS_RK
+#undef DNS_RKR
     return check_launch("dense_bf16x6_batched");
 }
 
@@ -1611,13 +1709,41 @@ static int resident_launch(DenseArgs g, int slices, int items, int planes_count,
 // (floats; strideA = 0: the same left operand for every product), B_z = the planes at planes + z stride_planes_bytes.  No input
 // transform, no masks.  planes_count: 3 = fp32 arithmetic (six products), 1 = one bf16 product -- explicit here, whatever
 // ptts_set_bf16_products says.  What the frequency-domain context Conv1D is made of (ops._C1FFT): DFT, per-frequency products, inverse DFT.
+// planes_count | PTTS_PLANES_ROWS: `planes` is a HOST pointer to one ptts_dense_rows_desc, read here -- B_z as fp32 rows (strided, or the
+// windows of a frame sequence) that the resident-left kernel reads and splits itself, with the mirrored store if asked for; on a shape
+// or a switch setting that does not take that kernel: PTTS_EINVAL, nothing launched.
 extern "C" int ptts_dense_bf16x6_batched(const float* A, long long strideA, const void* planes, long long stride_planes_bytes,
                                          const float* bias, float* C, long long strideC, int nbatch, int M, int N, int K,
                                          long long lda, long long ldc, int planes_count, void* stream) {
+    const bool rows = (planes_count & PTTS_PLANES_ROWS) != 0;         // `planes` is a host ptts_dense_rows_desc: the right operand as fp32 rows
+    planes_count &= ~PTTS_PLANES_ROWS;
     PTTS_REQUIRE(A && planes && C && nbatch > 0 && nbatch <= 65535, "dense_bf16x6_batched: bad arguments");
     PTTS_REQUIRE(ptts_dense_bf16x6_supported(M, N, K, lda, ldc), "dense_bf16x6_batched: unsupported shape M=%d N=%d K=%d lda=%lld ldc=%lld", M, N, K, lda, ldc);
     PTTS_REQUIRE(lda >= K && ldc >= N && planes_count >= 1 && planes_count <= 3 && planes_count != 2, "dense_bf16x6_batched: bad leading dims / planes");
-    PTTS_REQUIRE(stride_planes_bytes % 16 == 0 && strideA % 4 == 0 && ((uintptr_t)A & 15) == 0, "dense_bf16x6_batched: strides of A / planes must keep 16-byte alignment");
+    PTTS_REQUIRE((rows || stride_planes_bytes % 16 == 0) && strideA % 4 == 0 && ((uintptr_t)A & 15) == 0, "dense_bf16x6_batched: strides of A / planes must keep 16-byte alignment");
+    RowsArgs ra = {};
+    if (rows) {
+        const ptts_dense_rows_desc& d = *(const ptts_dense_rows_desc*)planes;
+        PTTS_REQUIRE(batched_resident_on() && ptts_dense_batched_resident_eligible(strideA, M, N, K, planes_count),
+                     "dense_bf16x6_batched: the fp32-rows form of the right operand exists on the resident-left kernel only (strideA == 0, M <= %d, K <= %d, "
+                     "the switch on): strideA=%lld M=%d K=%d", RES_M, RES_K, strideA, M, K);
+        PTTS_REQUIRE(d.B && d.ldb >= N && d.kvalid > 0 && d.kvalid <= K, "dense_bf16x6_batched: rows form: bad source, ldb=%lld or kvalid=%d", d.ldb, d.kvalid);
+        // the last float a lane may read lies below 2^30 (32-bit byte offsets from d.B)
+        long long span;
+        if (d.windows) {
+            PTTS_REQUIRE(d.nB > 0 && d.T > 0 && d.NS > 0 && d.S > 0 && (long long)d.nB * d.NS == nbatch && d.row_off > -(1 << 24) && d.row_off < (1 << 24),
+                         "dense_bf16x6_batched: rows form: bad windows nB=%d T=%d NS=%d S=%d row_off=%d for %d members", d.nB, d.T, d.NS, d.S, d.row_off, nbatch);
+            span = ((long long)d.nB * d.T - 1) * d.ldb + N;
+        } else {
+            PTTS_REQUIRE(d.strideB >= 0, "dense_bf16x6_batched: rows form: negative strideB");
+            span = (long long)(nbatch - 1) * d.strideB + (long long)(d.kvalid - 1) * d.ldb + N;
+        }
+        PTTS_REQUIRE(span <= (1LL << 30), "dense_bf16x6_batched: rows form: the source spans more than 2^30 floats");
+        PTTS_REQUIRE(d.mirror_cols >= 0 && (d.mirror_cols == 0 || (d.mirror_cols % 4 == 0 && d.mirror_cols >= N && (long long)d.mirror_cols + N <= ldc && M % 2 == 0)),
+                     "dense_bf16x6_batched: rows form: mirror_cols=%d needs a multiple of 4, N <= mirror_cols, mirror_cols + N <= ldc and an even M", d.mirror_cols);
+        ra.B = d.B; ra.strideB = d.strideB; ra.ldb = (int)d.ldb; ra.windows = d.windows ? 1 : 0;
+        ra.T = d.T; ra.NS = d.NS; ra.S = d.S; ra.row_off = d.row_off; ra.kvalid = d.kvalid; ra.mirror = d.mirror_cols;
+    }
     const bool vec_out = N % 4 == 0 && ldc % 4 == 0 && strideC % 4 == 0 && ((uintptr_t)C & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0);
     DenseArgs g;
     g.A = A; g.mask_src = nullptr; g.in_scale = nullptr; g.in_shift = nullptr; g.planes = (const u16*)planes; g.bias = bias;
@@ -1632,8 +1758,10 @@ extern "C" int ptts_dense_bf16x6_batched(const float* A, long long strideA, cons
     const long long items = (long long)nbatch * ((N + 31) / 32);
     if (batched_resident_on() && ptts_dense_batched_resident_eligible(strideA, M, N, K, planes_count) && items <= 0x3fffffffLL) {     // (item + 8 G stays an int)
         g.vec_out = ldc % 4 == 0 && strideC % 4 == 0 && ((uintptr_t)C & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0);      // (per quad: n + 3 < N)
-        return resident_launch(g, (N + 31) / 32, (int)items, planes_count, (hipStream_t)stream);
+        if (rows) g.planes = nullptr;
+        return resident_launch(g, (N + 31) / 32, (int)items, planes_count, rows ? &ra : nullptr, (hipStream_t)stream);
     }
+    PTTS_REQUIRE(!rows, "dense_bf16x6_batched: rows form: too many work items");
     const int cb = (N + NBLK - 1) / NBLK;
     // rows per workgroup: every workgroup of a product reads that product's planes, so fewer row tiles = fewer reads of the right
     // operand, which is most of the traffic of these small-M products

@@ -1560,6 +1560,12 @@ class _C1FFT(object):
     # themselves (ptts_dense_tn_bf16x6_batched), without the split of X^ and the transpose of DY^ in front of it.  PTTS_CONV1D_FFT_TN=0:
     # the older stage list.
     tn_enabled = os.environ.get('PTTS_CONV1D_FFT_TN', '1') == '1'
+    # The transforms read their single-use right operands as fp32 rows (planes_count | PLANES_ROWS of ptts_dense_bf16x6_batched: the split
+    # happens inside the product): bit 0 = 'dft' on the windows of the input, with the mirrored store -- no 'x' split pass, no
+    # ptts_dft_mirror; bit 1 = 'idft' on Yh -- no 'y' split pass.  The same bits as the older stage lists.  Only where the product runs on
+    # the resident-left kernel (eligible, switch on); otherwise, and with PTTS_CONV1D_FFT_ROWS=0 / conv1d_fft_rows(False), the older lists.
+    rows_default = int(os.environ.get('PTTS_CONV1D_FFT_ROWS', '3'))
+    rows_sites = rows_default
     # BASELINE configs[2] (ops.bf16_products): the frequency-domain path with its BIG products -- the per-frequency product of the forward
     # and the per-frequency correlation of the weight gradient, 80 % of its flops -- as ONE bf16 product of the operands' roundings
     # (X^ and H^ / DY^ rounded once, fp32 accumulation), the small transforms (DFT, inverse DFT) still six products: the same single
@@ -1656,6 +1662,14 @@ class _C1FFT(object):
         return c
 
     @classmethod
+    def rows_enabled(cls, site, M, N, K, span):
+        """True when call site `site` (1: 'dft', 2: 'idft') hands its right operand, `span` floats, to an M x N x K product as fp32 rows."""
+        if not (cls.rows_sites & site) or span > (1 << 30):
+            return False
+        lib = _hip.lib()
+        return bool(lib.ptts_dense_batched_resident_enabled() and lib.ptts_dense_batched_resident_eligible(0, M, N, K, 3))
+
+    @classmethod
     def x_transform(cls, a, KW):
         """[Xr | -Xi ; Xi | Xr] per frequency: Ap [NB][2][B NS][2 Kh] fp32, kept for the tensor it was made from."""
         B, T, Cin = a.shape
@@ -1667,6 +1681,12 @@ class _C1FFT(object):
         Z = B * NS
         Ap = cls._buf('Ap', (B, T, Cin, KW, S), NB * 2 * Z * 2 * Kh, a.device)                     # pad columns stay zero
         lib = _hip.lib()
+        if cls.rows_enabled(1, c['R'], Cin, P, B * T * Cin):
+            d = _hip.DenseRowsDesc(B=a.data_ptr(), strideB=0, ldb=Cin, windows=1, nB=B, T=T, NS=NS, S=S, row_off=-c['pl'], kvalid=P, mirror_cols=Kh)
+            call('ptts_dense_bf16x6_batched', ptr(c['D']), 0, ctypes.byref(d), 0, None, ptr(Ap), 2 * Kh, Z, c['R'], Cin, P, P, Z * 2 * Kh,
+                 3 | _hip.PLANES_ROWS, stream(), tag=('dft', Z, c['R'], Cin, P))
+            cls.x_src, cls.x_key, cls.x_hat = a, key, Ap
+            return Ap
         npb = lib.ptts_dense_planes_bytes(Cin, P)
         xpl = cls._scratch('xpl', Z * npb, a.device)
         call('ptts_split3_frame_windows', ptr(a), B, T, Cin, NS, S, -c['pl'], P, P, ptr(xpl), npb, stream(), tag=('x', Z))
@@ -1746,6 +1766,12 @@ class _C1FFT(object):
         Yh = cls._scratch('Yh', NB * 2 * Z * N * 4, a.device)                                        # [NB][2][Z][N] fp32
         call('ptts_dense_bf16x6_batched', ptr(Ap), 2 * Z * 2 * Kh, ptr(wpl), npw, None, ptr(Yh), 2 * Z * N, NB, 2 * Z, N, 2 * Kh,
              2 * Kh, N, 1 if _Flags.bf16_products else 3, stream(), tag=('freq', NB, 2 * Z, N, 2 * Kh))
+        if cls.rows_enabled(2, S, N, c['Rp'], c['R'] * Z * N):
+            # member z reads its rows of Yh where the product left them: row r = (f, part) at Yh + r Z N + z N
+            d = _hip.DenseRowsDesc(B=Yh.data_ptr(), strideB=N, ldb=Z * N, windows=0, nB=0, T=0, NS=0, S=0, row_off=0, kvalid=c['R'], mirror_cols=0)
+            call('ptts_dense_bf16x6_batched', ptr(c['E']), 0, ctypes.byref(d), 0, ptr(b), ptr(y), S * N, Z, S, N, c['Rp'], c['Rp'], N,
+                 3 | _hip.PLANES_ROWS, stream(), tag=('idft', Z, S, N, c['Rp']))
+            return
         npy = lib.ptts_dense_planes_bytes(N, c['R'])
         ypl = cls._scratch('ypl', Z * npy, a.device)
         call('ptts_split3_dense_weight_strided', ptr(Yh), N, ptr(ypl), npy, Z, Z * N, c['R'], N, 0, stream(), tag=('y', Z))
@@ -1815,6 +1841,13 @@ class _C1FFT(object):
 def conv1d_fft(on):
     """Context Conv1D forward in the frequency domain (see _C1FFT): True / False, None = the default (PTTS_CONV1D_FFT)."""
     _C1FFT.enabled = _C1FFT.default if on is None else bool(on)
+    _C1FFT.clear()
+
+
+def conv1d_fft_rows(on):
+    """The frequency-domain Conv1D's transforms on fp32 rows instead of pre-split planes (see _C1FFT.rows_sites): True / False, a mask of
+    call sites (1: 'dft', 2: 'idft'), None = the default (PTTS_CONV1D_FFT_ROWS)."""
+    _C1FFT.rows_sites = _C1FFT.rows_default if on is None else (3 if on is True else int(on))
     _C1FFT.clear()
 
 
