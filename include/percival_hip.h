@@ -758,6 +758,29 @@ int ptts_pulse_segments(const float* spec, const float* mask, const float* noise
 int ptts_pulse_overlap_add(const float* seg, const int* itab, int P, int W, float* wav, long long wavlen, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Periodic-plus-aperiodic waveform synthesis for the WORLD parameters (csrc/worldsynth.hip; the
+ * definition is this build's own).  L = dftlen, a power of two in 256 .. 8192
+ * (anything else: PTTS_EINVAL without a launch), K = L/2 + 1.  fp32 in memory, fp64 arithmetic.
+ *
+ * ptts_aper_rows: aper [T, nb] band aperiodicities in dB, vuv [T] -> out [T, K]: 10^(x/20) per
+ *   band, those values interpolated at k fs / L with the band / fraction rows of
+ *   ptts_fwbnd_table(nb, fs, ., dftlen), clipped to [0, 1]; the row of a frame with vuv < 0.5 is 1.
+ * ptts_world_segments: one workgroup per pulse; seg [P][W] gets the first winlen samples of
+ *   irfft(E_p D + E_a N) (the rest of a row is neither written nor read).  spec (amplitude), aper
+ *   (rows of ptts_aper_rows) [T, K], blended as (1 - w) row i0 + w row i1; E_a the minimum phase of
+ *   spec aper, E_p that of spec sqrt(1 - aper^2) hp for a pulse with v = 1 and 0 otherwise; noise
+ *   [wavlen] N(0,1) samples; itab [8][P] int32 rows start, winlen, lb, rb, fr, i0, i1, v
+ *   (winlen <= W <= L, 0 <= lb <= rb <= wavlen, start <= lb and rb - start <= L where lb < rb,
+ *   0 <= fr, i0, i1 < T; a pulse whose row breaks this is skipped); dtab [3][P] fp64 rows delay,
+ *   f0, w (0 <= w <= 1).  P = 0 or T = 0 succeeds without a launch.  The segments are summed by
+ *   ptts_pulse_overlap_add, which reads the first two rows of itab.
+ * ------------------------------------------------------------------------------------- */
+int ptts_aper_rows(const float* aper, const float* vuv, float* out, int T, int nb, double fs, int dftlen, const double* table,
+                   size_t table_bytes, void* stream);
+int ptts_world_segments(const float* spec, const float* aper, const float* noise, const int* itab, const double* dtab, int P, int T,
+                        int dftlen, double fs, long long wavlen, float* seg, int W, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Waveform analysis for the PML parameters (csrc/analysis.hip; the counterpart of the synthesis
  * above, the definition is this build's own).  L = dftlen, K = L/2 + 1,
  * rnd(x) = floor(x + 0.5).  fp32 in memory, fp64 arithmetic, every integer decision in fp64.

@@ -20,39 +20,19 @@
 // order (wave butterflies, then wave order through LDS); the overlap-add gathers, so nothing here uses an atomic and a result does
 // not depend on the grid.
 #include "common.h"
-#include "realfft.h"
+#include "synthchain.h"
 
 namespace ptts {
 
-constexpr int PS_THREADS = 256;
-constexpr int PS_MIN_DFTLEN = 256, PS_MAX_DFTLEN = 8192;
 constexpr int PS_ITAB_ROWS = 5, PS_DTAB_ROWS = 2;      // {start, winlen, lb, rb, fr} int32 [5][P]; {delay, f0} fp64 [2][P]
 constexpr int NM_TAPS = 17, NM_HALF = 8;
 constexpr int NM_MAX_NB = 1024;
 
 struct NmTaps { double h[NM_TAPS]; };
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    const double s = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    double tot = red[0];
-    for (int w = 1; w < nwaves; ++w) tot += red[w];
-    return tot;
-}
-
 // ln(max(SPEC_k hp_k, 1e-10)); tc = tan(pi fcut / fs)
 __device__ __forceinline__ double log_amplitude(const float* __restrict__ row, int k, int L, double tc) {
-    double hp = 0.0;
-    if (k > 0) {
-        double s, c;
-        sincospi((double)k / (double)L, &s, &c);
-        const double r = tc * c / s, r2 = r * r, r4 = r2 * r2;
-        hp = 1.0 / sqrt(1.0 + r4 * r4);
-    }
-    const double v = (double)row[k] * hp;
+    const double v = (double)row[k] * hp_gain(k, L, tc);
     return log(v > 1e-10 ? v : 1e-10);
 }
 
@@ -64,7 +44,7 @@ __global__ __launch_bounds__(PS_THREADS) void pulse_segments_kernel(const float*
                                                                     const long long wavlen, float* __restrict__ seg, const int W) {
     extern __shared__ double2 lds[];
     __shared__ double red[PS_THREADS / 64];
-    const int M = 1 << logM, L = M << 1, K = M + 1, Mq = M >> 2;
+    const int M = 1 << logM, L = M << 1, K = M + 1;
     double2* bufe = lds;            // the minimum-phase chain, E at the end
     double2* bufn = lds + M;        // the noise, then the product
     double2* wq = lds + 2 * M;
@@ -76,85 +56,15 @@ __global__ __launch_bounds__(PS_THREADS) void pulse_segments_kernel(const float*
     const float* srow = spec + (size_t)fr * K;
     const float* mrow = mask + (size_t)fr * K;
 
-    for (int j = tid; j < Mq; j += nthr) {
-        double s, c;
-        sincospi(2.0 * (double)j / (double)M, &s, &c);
-        wq[j] = make_double2(c, -s);
-    }
+    fill_twiddles(wq, M);
+    noise_fill(bufn, noise, start, lb, rb, taper, M);
 
-    // the noise segment, packed; position p of the frame holds g[start + p] for lb <= start + p < rb
-    const long long p0 = (long long)lb - start, p1 = (long long)rb - start;
-    const int len = rb - lb;
-    const bool tapered = taper > 0 && len >= 2 * (taper + 1);
-    for (int i = tid; i < M; i += nthr) {
-        double v[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const long long p = 2 * (long long)i + h;
-            v[h] = 0.0;
-            if (p >= p0 && p < p1) {
-                const int q = (int)(p - p0);
-                double g = (double)noise[(long long)lb + q];
-                if (tapered) {
-                    if (q <= taper) g *= 0.5 - 0.5 * cospi((double)q / (double)taper);
-                    if (len - 1 - q <= taper) g *= 0.5 - 0.5 * cospi((double)(len - 1 - q) / (double)taper);
-                }
-                v[h] = g;
-            }
-        }
-        bufn[i] = make_double2(v[0], v[1]);
-    }
-
-    // la is real: the packed spectrum of c = irfft(la)
     double s0, c0;
     sincospi(0.5 * f0 / fs, &s0, &c0);
     const double tc = s0 / c0;
-    for (int k = tid; k <= (M >> 1); k += nthr) {
-        const double lk = log_amplitude(srow, k, L, tc), lm = log_amplitude(srow, M - k, L, tc);
-        double2 zk, zm;
-        pack_pair(make_double2(lk, 0.0), make_double2(lm, 0.0), pair_twiddle(k, L), zk, zm);
-        if (k == 0) {
-            bufe[0] = make_double2(0.5 * (lk + lm), 0.5 * (lk - lm));
-        } else {
-            bufe[bitrev(k, logM)] = zk;
-            if (k != (M >> 1)) bufe[bitrev(M - k, logM)] = zm;
-        }
-    }
-    fft_inverse(bufe, wq, logM);
-    // c[2i] + i c[2i+1] = bufe[i] / M; fold the cepstrum onto its causal half
+    minimum_phase(bufe, wq, logM, [&](int k) { return log_amplitude(srow, k, L, tc); });
+    const double gain = noise_spectrum(bufn, wq, logM, red);
     const double inv_m = 1.0 / (double)M;
-    for (int i = tid; i < M; i += nthr) {
-        const double2 z = bufe[i];
-        double2 o = make_double2(0.0, 0.0);
-        if (i == 0) o = make_double2(z.x * inv_m, 2.0 * z.y * inv_m);
-        else if (i < (M >> 1)) o = make_double2(2.0 * z.x * inv_m, 2.0 * z.y * inv_m);
-        else if (i == (M >> 1)) o = make_double2(z.x * inv_m, 0.0);
-        bufe[i] = o;
-    }
-    fft_forward(bufe, wq, logM);
-    unpack_real(bufe, logM);
-    for (int k = tid; k < M; k += nthr) {
-        const int r = bitrev(k, logM);
-        const double2 c = bufe[r];
-        if (k == 0) {
-            bufe[0] = make_double2(exp(c.x), exp(c.y));       // E_0 and E_M, both real
-        } else {
-            double s, cs;
-            sincos(c.y, &s, &cs);
-            const double m = exp(c.x);
-            bufe[r] = make_double2(m * cs, m * s);
-        }
-    }
-
-    fft_forward(bufn, wq, logM);
-    unpack_real(bufn, logM);
-    double e = 0.0;
-    for (int k = tid; k < M; k += nthr) {
-        const double2 z = bufn[bitrev(k, logM)];
-        e += k == 0 ? z.x * z.x + z.y * z.y : 2.0 * (z.x * z.x + z.y * z.y);
-    }
-    e = block_sum(e, red) / (double)L;
-    const double gain = e > 0.0 ? 1.0 / sqrt(e) : 0.0;
 
     // S = E ((1 - m) D + m N), packed for the inverse transform in the same pass
     for (int k = tid; k <= (M >> 1); k += nthr) {
@@ -244,12 +154,6 @@ __global__ __launch_bounds__(256) void noise_mask_kernel(const float* __restrict
         for (int i = 0; i < NM_TAPS; ++i) acc += taps.h[i] * (double)x[k + i - NM_HALF];
         out[(size_t)t * K + k] = (float)(acc < 0.0 ? 0.0 : (acc > 1.0 ? 1.0 : acc));
     }
-}
-
-static int ps_log2(int dftlen) {
-    for (int l = 8; l <= 13; ++l)
-        if (dftlen == (1 << l)) return l;
-    return -1;
 }
 
 }  // namespace ptts

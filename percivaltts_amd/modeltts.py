@@ -6,7 +6,8 @@ modeltts.py:68-130; the model file trio keeps its stems (`.arch.json`, `.weights
 because h5py is not part of this image, `.cfgextras.pkl`).  generate_params is generate_wav (modeltts.py:144-205) up to
 the vocoder call: de-normalisation, MLPG on the device (csrc/mlpg.hip), parameter files and objective measures.  The
 reference's own waveform needs the vocoder DSP it delegates to and stays out of scope; with `wavdir`
-generate_params writes the waveform of the build's pulse-and-noise synthesiser (csrc/pulsesynth.hip) instead.
+generate_params writes the waveform of the build's own synthesiser for the vocoder's parameters instead (VocoderPML: pulse and noise,
+csrc/pulsesynth.hip; VocoderWORLDDevice: periodic plus aperiodic, csrc/worldsynth.hip).
 """
 from __future__ import print_function
 
@@ -139,9 +140,9 @@ class ModelTTS:
         too, measures before the post-filter); without `specdir` no spectrum kernel is launched.
 
         With `wavdir` each utterance's generated parameters also go through the vocoder's synthesis_device(pp_mcep=pp_mcep) while
-        they are on the device (csrc/pulsesynth.hip) and `wavdir/<fid>.wav` is written as 16-bit PCM at the vocoder's fs; the noise
+        they are on the device (csrc/pulsesynth.hip for VocoderPML, csrc/worldsynth.hip for VocoderWORLDDevice) and `wavdir/<fid>.wav` is written as 16-bit PCM at the vocoder's fs; the noise
         comes from the library's generator (ops.rng_seed).  The .cmp and .spec files are what they are without it.  A vocoder
-        without synthesis_device is a ValueError."""
+        without synthesis_device (VocoderWORLD itself among them) is a ValueError."""
         Ymean = np.fromfile(os.path.join(os.path.dirname(outpath), 'mean4norm.dat'), dtype='float32')
         Ystd = np.fromfile(os.path.join(os.path.dirname(outpath), 'std4norm.dat'), dtype='float32')
         nout, nraw = self.vocoder.featuressize(), self.vocoder.featuressizeraw()

@@ -1,5 +1,5 @@
 """Wrappers of the offline pipeline over the HIP kernels of libpercival_hip.so: parameter generation (MLPG), feature
-composition, spectral envelope decompression, pulse-and-noise synthesis, waveform analysis, F0 estimation, waveform pre-processing and the label front end.
+composition, spectral envelope decompression, pulse-and-noise synthesis (PML) and periodic-plus-aperiodic synthesis (WORLD), waveform analysis, F0 estimation, waveform pre-processing and the label front end.
 
 Argument checks, scratch memory and one C-ABI call (include/percival_hip.h) each; no autograd nodes, no switches, nothing
 of the training path (ops.py, which re-exports the names of __all__).  There is no CPU path.
@@ -21,6 +21,7 @@ __all__ = [
     'fwbnd2spec', 'SPEC2MCEP_MAX_TABLE_BYTES', 'spec2mcep_order_limit', 'spec2mcep_table_bytes', 'spec2mcep_check', 'spec2mcep',
     'PULSE_MIN_DFTLEN', 'PULSE_MAX_DFTLEN', 'PULSE_F0_FLOOR', 'PULSE_INT_ROWS', 'pulse_check', 'pulse_table', 'noise_mask',
     'pulse_synthesis',
+    'WORLD_UNVOICED_RATE', 'WORLD_INT_ROWS', 'world_pulse_table', 'aper_rows', 'world_synthesis',
     'COMPRESS_MEAN', 'COMPRESS_LSQ', 'ANALYSIS_NOISY_BELOW', 'analysis_check', 'f0_track', 'frame_harmonics', 'phase_coherence',
     'fwbnd_compress_check', 'fwbnd_compress',
     'F0_MIN_NCAND', 'F0_MAX_NCAND', 'F0_MAX_FRAMES', 'F0_CONSTANTS', 'f0_check', 'f0_frame_count', 'f0_window_table', 'f0_candidates',
@@ -473,33 +474,36 @@ def pulse_table(f0, shift, fs, wavlen, dftlen):
     return tab
 
 
-def _pulse_table_rows(table, T, dftlen, wavlen):
-    """(itab [5,P] int32, dtab [2,P] fp64, W) of a pulse table after the checks that keep the kernels inside their buffers."""
+def _pulse_table_rows(table, T, dftlen, wavlen, fn='pulse_synthesis', maker='pulse_table', int_rows=PULSE_INT_ROWS,
+                      dbl_rows=('delay', 'f0')):
+    """(itab [len(int_rows),P] int32, dtab [len(dbl_rows),P] fp64, W) of a pulse table after the checks that keep the kernels inside
+    their buffers; the first five int rows are PULSE_INT_ROWS, the first two fp64 rows delay and f0."""
     try:
-        rows = [np.asarray(table[k]) for k in PULSE_INT_ROWS + ('delay', 'f0')]
+        rows = [np.asarray(table[k]) for k in int_rows + dbl_rows]
     except (KeyError, TypeError, IndexError):
-        raise ValueError('ops.pulse_synthesis: table is what ops.pulse_table returns')
+        raise ValueError('ops.{}: table is what ops.{} returns'.format(fn, maker))
+    ni, nd = len(int_rows), len(dbl_rows)
     P = rows[0].shape[0] if rows[0].ndim == 1 else -1
     if any(r.shape != (P,) for r in rows):
-        raise ValueError('ops.pulse_synthesis: the rows of the table are not all [P]')
-    itab = np.ascontiguousarray(np.stack(rows[:5]) if P else np.zeros((5, 0)), dtype=np.int64)
-    dtab = np.ascontiguousarray(np.stack(rows[5:]) if P else np.zeros((2, 0)), dtype=np.float64)
+        raise ValueError('ops.{}: the rows of the table are not all [P]'.format(fn))
+    itab = np.ascontiguousarray(np.stack(rows[:ni]) if P else np.zeros((ni, 0)), dtype=np.int64)
+    dtab = np.ascontiguousarray(np.stack(rows[ni:]) if P else np.zeros((nd, 0)), dtype=np.float64)
     if P == 0:
         return itab.astype(np.int32), dtab, 1
-    start, winlen, lb, rb, fr = itab
+    start, winlen, lb, rb, fr = itab[:5]
     if winlen.min() < 1 or winlen.max() > dftlen:
-        raise ValueError('ops.pulse_synthesis: a window of {} samples does not fit dftlen={}'.format(winlen.max(), dftlen))
+        raise ValueError('ops.{}: a window of {} samples does not fit dftlen={}'.format(fn, winlen.max(), dftlen))
     if (np.diff(start) < 0).any():
-        raise ValueError('ops.pulse_synthesis: the pulses\' start samples have to ascend (f0 falls too fast between two pulses)')
+        raise ValueError('ops.{}: the pulses\' start samples have to ascend (f0 falls too fast between two pulses)'.format(fn))
     filled = rb > lb
     if lb.min() < 0 or rb.max() > wavlen or (rb < lb).any() or (filled & ((lb < start) | (rb - start > dftlen))).any():
-        raise ValueError('ops.pulse_synthesis: a noise segment lies outside the waveform or its pulse\'s frame')
+        raise ValueError('ops.{}: a noise segment lies outside the waveform or its pulse\'s frame'.format(fn))
     if fr.min() < 0 or fr.max() >= T:
-        raise ValueError('ops.pulse_synthesis: frame {} of the table is outside the {} frames given'.format(fr.max(), T))
+        raise ValueError('ops.{}: frame {} of the table is outside the {} frames given'.format(fn, fr.max(), T))
     if not (np.isfinite(dtab).all() and (dtab[1] > 0).all()):
-        raise ValueError('ops.pulse_synthesis: delay / f0 of the table are not finite and positive')
+        raise ValueError('ops.{}: delay / f0 of the table are not finite and positive'.format(fn))
     if np.abs(start).max() >= 1 << 30:
-        raise ValueError('ops.pulse_synthesis: a start sample exceeds the int32 table')
+        raise ValueError('ops.{}: a start sample exceeds the int32 table'.format(fn))
     return itab.astype(np.int32), dtab, int(winlen.max())
 
 
@@ -552,6 +556,127 @@ def pulse_synthesis(spec, mask, table, noise, fs, dftlen, wavlen):
     dt = torch.from_numpy(dtab).to(spec.device)
     seg = torch.empty((P, W), dtype=torch.float32, device=spec.device)
     call('ptts_pulse_segments', ptr(spec), ptr(mask), ptr(noise), ptr(it), ptr(dt), P, T, int(dftlen), float(fs), wavlen, ptr(seg), W,
+         stream(), tag=(P, dftlen, W))
+    call('ptts_pulse_overlap_add', ptr(seg), ptr(it), P, W, ptr(wav), wavlen, stream(), tag=(P, W, wavlen))
+    return wav
+
+
+# ----------------------------------------------------------------------------------------------
+# periodic-plus-aperiodic synthesis for the WORLD parameters (the step behind vocoders.py:300-330, which calls pyworld; the
+# definition is the build's own): csrc/worldsynth.hip
+# ----------------------------------------------------------------------------------------------
+WORLD_UNVOICED_RATE = 500.0         # pulses per second through an unvoiced frame (WORLD's default F0): noise in 2-ms pieces
+WORLD_INT_ROWS = PULSE_INT_ROWS + ('i0', 'i1', 'v')
+
+
+def world_pulse_table(f0, voiced, shift, fs, wavlen, dftlen):
+    """The pulse table of ops.pulse_table for the WORLD synthesiser, on the host in fp64: f0 [T] in Hz
+    (continuous: positive in unvoiced frames too) and voiced [T] booleans at the frame times shift * i.  The rate at t is
+    max(interp(t), 50) where the frame nearest to t is voiced and 500 Hz where it is not; every pulse leads its window by the same
+    pos = int((2 int(0.050 fs / 2) + 1) / 4) samples, whatever its winlen, so start ascends with t.  Returns ops.pulse_table's
+    entries ('f0' is the rate at the pulse) and, per pulse, the frames 'i0', 'i1' (int32) whose rows are blended with the weight
+    'w' (fp64) on i1, and 'v' (int32), 1 where frame 'fr' is voiced.  ValueError when a window does not fit dftlen."""
+    pulse_check(dftlen, fs)
+    f0 = np.ascontiguousarray(f0, dtype=np.float64)
+    if f0.ndim != 1 or f0.size < 1 or not (np.isfinite(f0).all() and (f0 > 0).all()):
+        raise ValueError('ops.world_pulse_table: f0 has to be [T] positive finite Hz values')
+    voiced = np.asarray(voiced)
+    if voiced.shape != f0.shape or voiced.dtype.kind not in 'biu':
+        raise ValueError('ops.world_pulse_table: voiced has to be [T] booleans')
+    voiced = voiced.astype(bool)
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('ops.world_pulse_table: shift={}'.format(shift))
+    T, fs, shift = f0.size, float(fs), float(shift)
+    if int(wavlen) != int(round(shift * (T - 1) * fs)) or wavlen >= 1 << 31:
+        raise ValueError('ops.world_pulse_table: wavlen={} is not round(shift (T-1) fs) = {}'.format(
+            wavlen, int(round(shift * (T - 1) * fs))))
+    wavlen = int(wavlen)
+    times = shift * np.arange(T)
+    frame = lambda x: min(max(_rnd(x / shift), 0), T - 1)
+    rate = lambda x: max(float(np.interp(x, times, f0)), PULSE_F0_FLOOR) if voiced[frame(x)] else WORLD_UNVOICED_RATE
+    t = [0.0]
+    while t[-1] < wavlen / fs:
+        t.append(t[-1] + 1.0 / rate(t[-1]))
+    P = len(t)
+    tab = {'t': np.array(t, dtype=np.float64)}
+    for key in ('delay', 'f0', 'w'):
+        tab[key] = np.zeros(P, dtype=np.float64)
+    for key in WORLD_INT_ROWS:
+        tab[key] = np.zeros(P, dtype=np.int32)
+    pos = int((2 * int(0.050 * fs / 2) + 1) / 4)
+    for n in range(P):
+        f0n = rate(t[n])
+        winlen = 2 * int(max(0.050 * fs, 4.0 * fs / f0n) / 2) + 1
+        if winlen > dftlen:
+            raise ValueError('ops.world_pulse_table: the window of pulse {} ({} samples at f0 = {:.1f} Hz) does not fit dftlen={}'.format(
+                n, winlen, f0n, dftlen))
+        c = _rnd(fs * t[n])
+        lb = _rnd(fs * (t[n - 1] + t[n]) / 2) if n > 0 else _rnd(fs * (t[n] - 0.5 / f0n))
+        rb = _rnd(fs * (t[n] + t[n + 1]) / 2) if n < P - 1 else _rnd(fs * (t[n] + 0.5 / f0n))
+        tab['start'][n], tab['winlen'][n] = c - pos, winlen
+        tab['lb'][n], tab['rb'][n] = min(max(lb, 0), wavlen), min(max(rb, 0), wavlen)
+        tab['fr'][n] = frame(t[n])
+        tab['delay'][n], tab['f0'][n] = pos + (fs * t[n] - c), f0n
+        i0 = min(int(t[n] / shift), T - 1)
+        tab['i0'][n], tab['i1'][n] = i0, min(i0 + 1, T - 1)
+        tab['w'][n] = t[n] / shift - i0 if i0 < T - 1 else 0.0
+        tab['v'][n] = int(voiced[tab['fr'][n]])
+    return tab
+
+
+def aper_rows(aper_db, vuv, fs, dftlen=4096):
+    """Band aperiodicities [T,A] in dB and vuv [T] (fp32 device) -> the aperiodicity of every bin, [T, dftlen/2+1] in [0, 1]
+    (csrc/worldsynth.hip): 10^(x/20) per band, those values interpolated at k fs / dftlen on the band axis of fwbnd2spec, clipped;
+    the row of an unvoiced frame (vuv < 0.5) is 1 throughout."""
+    pulse_check(dftlen, fs)
+    if not torch.is_tensor(aper_db) or aper_db.dim() != 2 or not 2 <= aper_db.shape[1] <= SPECTRUM_MAX_NB:
+        raise ValueError('ops.aper_rows: expected a [T,A] tensor with A in [2, {}]'.format(SPECTRUM_MAX_NB))
+    T, nbands = aper_db.shape
+    if not torch.is_tensor(vuv) or tuple(vuv.shape) != (T,):
+        raise ValueError('ops.aper_rows: vuv is not [{}]'.format(T))
+    _no_backward('aper_rows', aper_db, vuv)
+    f32c(aper_db, 'aper_rows.aper_db'); f32c(vuv, 'aper_rows.vuv')
+    out = torch.empty((T, dftlen // 2 + 1), dtype=torch.float32, device=aper_db.device)
+    if T == 0:
+        return out
+    tab, nbytes = _fwbnd_table(aper_db.device, nbands, fs, bark_alpha(fs), dftlen)
+    call('ptts_aper_rows', ptr(aper_db), ptr(vuv), ptr(out), T, nbands, float(fs), int(dftlen), ptr(tab), nbytes, stream(),
+         tag=(T, nbands, dftlen))
+    return out
+
+
+def world_synthesis(spec, aper, table, noise, fs, dftlen, wavlen):
+    """The waveform [wavlen] (fp32 device) of one utterance: spec (amplitude envelope) and aper (ops.aper_rows) [T, dftlen/2+1] fp32
+    device, table from ops.world_pulse_table (host), noise [wavlen] N(0,1) fp32 device.  One workgroup per pulse blends the rows of
+    its two frames and builds its segment (the minimum-phase periodic filter times a delayed pulse, for a voiced pulse, plus the
+    minimum-phase aperiodic filter times the pulse's stretch of the noise), then ops.pulse_synthesis's overlap-add sums the
+    segments in pulse order (csrc/worldsynth.hip, csrc/pulsesynth.hip).  Same input, same bytes."""
+    pulse_check(dftlen, fs)
+    K = dftlen // 2 + 1
+    if not torch.is_tensor(spec) or spec.dim() != 2 or spec.shape[1] != K:
+        raise ValueError('ops.world_synthesis: spec is not [T,{}]'.format(K))
+    T = spec.shape[0]
+    if not torch.is_tensor(aper) or tuple(aper.shape) != (T, K):
+        raise ValueError('ops.world_synthesis: aper is not [{},{}]'.format(T, K))
+    wavlen = int(wavlen)
+    if wavlen < 0 or not torch.is_tensor(noise) or tuple(noise.shape) != (wavlen,):
+        raise ValueError('ops.world_synthesis: noise is not [wavlen={}]'.format(wavlen))
+    _no_backward('world_synthesis', spec, aper, noise)
+    f32c(spec, 'world_synthesis.spec'); f32c(aper, 'world_synthesis.aper'); f32c(noise, 'world_synthesis.noise')
+    itab, dtab, W = _pulse_table_rows(table, T, dftlen, wavlen, 'world_synthesis', 'world_pulse_table', WORLD_INT_ROWS,
+                                      ('delay', 'f0', 'w'))
+    P = itab.shape[1]
+    if P and (itab[5:7].min() < 0 or itab[5:7].max() >= T or not ((dtab[2] >= 0) & (dtab[2] <= 1)).all()):
+        raise ValueError('ops.world_synthesis: the frames i0 / i1 or the weight w of the table are outside the {} frames given'.format(T))
+    wav = torch.empty(wavlen, dtype=torch.float32, device=spec.device)
+    if wavlen == 0:
+        return wav
+    if P == 0 or T == 0:
+        return wav.zero_()
+    it = torch.from_numpy(itab).to(spec.device)
+    dt = torch.from_numpy(dtab).to(spec.device)
+    seg = torch.empty((P, W), dtype=torch.float32, device=spec.device)
+    call('ptts_world_segments', ptr(spec), ptr(aper), ptr(noise), ptr(it), ptr(dt), P, T, int(dftlen), float(fs), wavlen, ptr(seg), W,
          stream(), tag=(P, dftlen, W))
     call('ptts_pulse_overlap_add', ptr(seg), ptr(it), P, W, ptr(wav), wavlen, stream(), tag=(P, W, wavlen))
     return wav

@@ -189,7 +189,8 @@ def generate(fparams=None):
     fid_lst_test = fids[cfg.id_valid_start + cfg.id_valid_nb:cfg.id_valid_start + cfg.id_valid_nb + cfg.id_test_nb]
     mod.generate_cmp(cfg.inpath, os.path.splitext(fparams)[0] + '-gen/*.cmp', fid_lst_test)
     # where the reference calls generate_wav (run.py:218): everything of it up to the vocoder's synthesis, and, for a vocoder
-    # with synthesis_device, the waveforms of the build's own synthesiser in <model>-demo-snd (cfg.wavdir overrides the place)
+    # with synthesis_device (VocoderPML, VocoderWORLDDevice), the waveforms of the build's own synthesiser in <model>-demo-snd
+    # (cfg.wavdir overrides the place)
     demostart = cfg.id_test_demostart if hasattr(cfg, 'id_test_demostart') else 0
     # cfg.specdir / cfg.pp_mcep, if present: also write the decompressed (post-filtered) spectral envelopes
     mod.generate_params(cfg.inpath, cfg.outpath, fid_lst_test[demostart:demostart + 10], os.path.splitext(fparams)[0] + '-demo-params',

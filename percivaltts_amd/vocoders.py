@@ -8,7 +8,8 @@ network_final switches on (networktts.py:195,212).  The objective measures of vo
 (`objmeasures_clear / objmeasures_add / objmeasures_stats`) are plain numpy on a few hundred kilobytes per utterance.
 `decompress_spectrum` (vocoders.py:147-166), the frame-wise step in front of the waveform generator, runs on the device
 (csrc/spectrum.hip).  `VocoderPML.synthesis_device` is the build's own pulse-and-noise synthesiser (csrc/pulsesynth.hip, DESIGN.md
-section 3); `synthesis` keeps its name for pulsemodel's waveform and keeps raising.  `VocoderPML.analysis_device` (with
+section 3), `VocoderWORLDDevice.synthesis_device` its periodic-plus-aperiodic synthesiser for the WORLD parameters (csrc/worldsynth.hip,
+DESIGN.md section 3; VocoderWORLD itself has none); `synthesis` keeps its name for pulsemodel's / pyworld's waveform and keeps raising.  `VocoderPML.analysis_device` (with
 `analysisf_device` / `analysisfid_device` around it) is the build's own waveform analysis for the same parameters
 (csrc/analysis.hip), from a caller's F0 track or, without one, from the build's own F0 estimator
 (`VocoderF0Spec.f0_estimate_device`, csrc/f0.hip); `compress_spectrum` is the inverse of `decompress_spectrum` for 'fwbnd'.
@@ -163,7 +164,7 @@ class Vocoder(object):
 
     def _out_of_scope(self, *a, **k):
         """analysisf / analysisfid / synthesis promise pulsemodel's or pyworld's signal processing, which this build does not have.
-        The build's own synthesiser is VocoderPML.synthesis_device."""
+        The build's own synthesisers are VocoderPML.synthesis_device and VocoderWORLDDevice.synthesis_device."""
         raise NotImplementedError('waveform analysis/synthesis is outside the MI355X hot-path build '
                                   '(needs the pulsemodel/pyworld DSP of the reference)')
     analysisf = analysisfid = synthesis = _out_of_scope
@@ -389,3 +390,42 @@ class VocoderWORLD(VocoderF0Spec):
         """As VocoderPML's, the aperiodicity bands in place of the noise mask (vocoders.py:333-342; no VUV measure there)."""
         self._objmeasures_add_f0spec(CMP, REF)
         self._objmeasures_add_band('APER[dB]', CMP, REF, self.aper_size)
+
+
+class VocoderWORLDDevice(VocoderWORLD):
+    """VocoderWORLD with the build's own synthesiser for its parameters.  A class of its own because VocoderWORLD carries the
+    reference's name and, like the reference's class without pyworld, produces no waveform; the networks and run.features_compose
+    treat this one as a WORLD vocoder (isinstance)."""
+
+    def synthesis_device(self, CMP, pp_mcep=False, pp_f0_smooth=None, noise=None):
+        """De-normalised parameters [T, featuressizeraw()] (numpy or a device tensor), columns ln f0 | spec | aperiodicity [dB] |
+        vuv -> the waveform, numpy float32 [round(shift (T-1) fs)], by the build's periodic-plus-aperiodic synthesiser (DESIGN.md
+        section 3): exp(lf0) as it is (the reference writes a continuous ln f0), frames with vuv >= 0.5 voiced, decompress_spectrum
+        (`pp_mcep` passed through; an amplitude envelope), the aperiodicity of every bin (ops.aper_rows), the pulse table on the
+        host (ops.world_pulse_table), one segment per pulse and their overlap-add (csrc/worldsynth.hip).  `noise`: a [wavlen] fp32
+        device tensor of N(0,1) samples, used as it is; None draws them from the library's generator, so ops.rng_seed makes a
+        waveform reproducible.  Not built: f0 smoothing (`pp_f0_smooth` other than None is a ValueError, as in the reference's
+        WORLD synthesis), WORLD's per-sample spectral interpolation inside a pulse, its safeguards on minimum-phase underflow."""
+        import torch
+        from . import backend_hip, ops
+        if pp_f0_smooth is not None:
+            raise ValueError('pp_f0_smooth={!r}: f0 smoothing is not part of this synthesiser'.format(pp_f0_smooth))
+        if not hasattr(CMP, 'shape') or len(CMP.shape) != 2 or CMP.shape[1] != self.featuressizeraw() or CMP.shape[0] < 1:
+            raise ValueError('synthesis_device: CMP is not [T, {}] with T >= 1'.format(self.featuressizeraw()))
+        ops.pulse_check(self.dftlen, self.fs)
+        x = CMP
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.ascontiguousarray(CMP, dtype=np.float32)).to(backend_hip.device())
+        if x.requires_grad:
+            raise ValueError('synthesis_device has no backward pass: detach its input')
+        T = x.shape[0]
+        s1 = 1 + self.spec_size
+        wavlen = int(round(self.shift * (T - 1) * self.fs))
+        f0 = torch.exp(x[:, 0])
+        vuv = x[:, -1].contiguous()
+        table = ops.world_pulse_table(f0.cpu().numpy(), vuv.cpu().numpy() >= 0.5, self.shift, self.fs, wavlen, self.dftlen)
+        SPEC = self.decompress_spectrum(x[:, 1:s1].contiguous(), pp_mcep=pp_mcep)
+        aper = ops.aper_rows(x[:, s1:s1 + self.aper_size].contiguous(), vuv, self.fs, self.dftlen)
+        if noise is None:
+            noise = ops.normal((wavlen,), device=x.device, i0=0)
+        return ops.world_synthesis(SPEC, aper, table, noise, self.fs, self.dftlen, wavlen).cpu().numpy()
