@@ -821,6 +821,37 @@ int ptts_fwbnd_compress(const float* x, float* out, int T, int nb, int dftlen, i
                         size_t fwtable_bytes, const double* ctable, size_t ctable_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Waveform analysis for the WORLD parameters (csrc/worldanalysis.hip; the counterpart of
+ * ptts_world_segments, the definition is this build's own).  L = dftlen, a
+ * power of two in 256 .. 8192 (anything else: PTTS_EINVAL without a launch; both kernels fit the
+ * 160 KiB of LDS at 8192, so there is no lower cap), K = L/2 + 1, rnd(x) = floor(x + 0.5).  fp32
+ * in memory, fp64 arithmetic, every integer decision in fp64.  One workgroup per frame; frame i is
+ * centred at c = rnd(i shift fs); wav [N] at fs, no sample outside [0, N) is read.  The window at
+ * rate r is w_j = 0.5 + 0.5 cos(pi j / (hw + 1)), j = -hw .. hw, hw = int(1.5 fs / r), scaled to
+ * sum w^2 = 1, placed zero-phase.  A frame with r outside (0, fs/2) or 2 hw + 1 > L is skipped:
+ * nothing of it is read or written.  T = 0 succeeds without a launch.
+ *
+ * ptts_world_envelope: rate [T] Hz (f0 of a voiced frame, 500 for an unvoiced one) -> spec [T, K],
+ *   the amplitude envelope ptts_world_segments reads (log_out != 0: its logarithm).  P = |rfft|^2
+ *   of the frame; below kappa = r L / fs, P_k += P(kappa - k) (linear between bins); the mean of P
+ *   over k +- d, d = r L / (3 fs), bins as cells of width 1 mirrored at 0 and L/2;
+ *   la = ln max(sqrt(S fs / r), 1e-10); the cepstrum of la times
+ *   sinc(r q / fs) (1.3 - 0.3 cos(2 pi r q / fs)) goes back to ln spec.  Three transforms a frame.
+ * ptts_world_aperiodicity: f0 [T] Hz, voiced [T] (>= 0.5: voiced) -> aper [T, nb] dB in [-60, 0]
+ *   on the band axis of fwtable = ptts_fwbnd_table(nb, fs, ., dftlen) (32-byte aligned, the CALLER
+ *   keeps it; band indices read from it are clamped), nb in 2 .. 1024.  Voiced: n0 = rnd(fs / f0),
+ *   delta = fs / f0 - n0, X1 and X2 the transforms of the frames at c - (n0 >> 1) and n0 samples
+ *   later, X2_k turned by exp(+2 pi i k delta / L); rho_b = sum_k W[k,b] |X1_k - X2_k|^2 /
+ *   sum_k W[k,b] (|X1_k|^2 + |X2_k|^2) over the bins k >= f0 L / fs (W as in ptts_fwbnd_compress);
+ *   aper = 10 log10(clip(rho, 1e-6, 1)); a band without weight takes the nearest band above that
+ *   has some, else 0 dB.  Unvoiced: the row is 0 dB and no transform runs.
+ * ------------------------------------------------------------------------------------- */
+int ptts_world_envelope(const float* wav, long long N, const float* rate, float* spec, int T, double shift, double fs, int dftlen,
+                        int log_out, void* stream);
+int ptts_world_aperiodicity(const float* wav, long long N, const float* f0, const float* voiced, float* aper, int T, int nb,
+                            double shift, double fs, int dftlen, const double* fwtable, size_t fwtable_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * F0 estimation (csrc/f0.hip; the track the analysis above takes as `f0`; the definition is this
  * build's own, DESIGN.md section 3, after Boersma 1993: the autocorrelation method with a path
  * finder).  L = dftlen, rnd(x) = floor(x + 0.5).  fp32 in memory, fp64 arithmetic, every decision

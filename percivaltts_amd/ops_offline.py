@@ -1,5 +1,5 @@
 """Wrappers of the offline pipeline over the HIP kernels of libpercival_hip.so: parameter generation (MLPG), feature
-composition, spectral envelope decompression, pulse-and-noise synthesis (PML) and periodic-plus-aperiodic synthesis (WORLD), waveform analysis, F0 estimation, waveform pre-processing and the label front end.
+composition, spectral envelope decompression, pulse-and-noise synthesis (PML) and periodic-plus-aperiodic synthesis (WORLD), waveform analysis (PML and WORLD), F0 estimation, waveform pre-processing and the label front end.
 
 Argument checks, scratch memory and one C-ABI call (include/percival_hip.h) each; no autograd nodes, no switches, nothing
 of the training path (ops.py, which re-exports the names of __all__).  There is no CPU path.
@@ -24,6 +24,7 @@ __all__ = [
     'WORLD_UNVOICED_RATE', 'WORLD_INT_ROWS', 'world_pulse_table', 'aper_rows', 'world_synthesis',
     'COMPRESS_MEAN', 'COMPRESS_LSQ', 'ANALYSIS_NOISY_BELOW', 'analysis_check', 'f0_track', 'frame_harmonics', 'phase_coherence',
     'fwbnd_compress_check', 'fwbnd_compress',
+    'world_analysis_check', 'world_envelope', 'world_aperiodicity',
     'F0_MIN_NCAND', 'F0_MAX_NCAND', 'F0_MAX_FRAMES', 'F0_CONSTANTS', 'f0_check', 'f0_frame_count', 'f0_window_table', 'f0_candidates',
     'f0_viterbi', 'f0_estimate',
     'RESAMPLE_MAX_UP', 'RESAMPLE_MAX_TABLE_BYTES', 'HIGHPASS_PADLEN', 'HIGHPASS_MAX_PADLEN', 'PREPROC_MAX_UTTS', 'preproc_check',
@@ -841,6 +842,77 @@ def fwbnd_compress(x, fs, nb, mode='lsq', log=False):
     call('ptts_fwbnd_compress', ptr(x), ptr(out), T, int(nb), dftlen, _COMPRESS_MODES[mode], int(bool(log)), ptr(fw), fwbytes, ptr(ct),
          ctbytes, stream(), tag=(T, int(nb), dftlen))
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# waveform analysis for the WORLD parameters (the step behind vocoders.py:234-284, which calls pyworld; the definition is the
+# build's own): csrc/worldanalysis.hip
+# ----------------------------------------------------------------------------------------------
+def world_analysis_check(dftlen, fs, shift, f0_min, f0_max):
+    """ValueError for parameters the WORLD analysis kernels do not take: analysis_check's rules (dftlen / fs
+    as pulse_check, a positive shift, 0 < f0_min <= f0_max <= fs/6, the window at f0_min, 2 int(1.5 fs / f0_min) + 1 samples, within
+    dftlen) and the same window rule at WORLD_UNVOICED_RATE, the rate of an unvoiced frame, which has to lie below fs/2.  Touches
+    no device."""
+    analysis_check(dftlen, fs, shift, f0_min, f0_max)
+    fs = float(fs)
+    if not WORLD_UNVOICED_RATE < 0.5 * fs:
+        raise ValueError('fs={}: the rate of an unvoiced frame, {} Hz, has to lie below fs/2'.format(fs, WORLD_UNVOICED_RATE))
+    if 2 * int(1.5 * fs / WORLD_UNVOICED_RATE) + 1 > dftlen:
+        raise ValueError('the window at the unvoiced rate {} Hz ({} samples) does not fit dftlen={}'.format(
+            WORLD_UNVOICED_RATE, 2 * int(1.5 * fs / WORLD_UNVOICED_RATE) + 1, dftlen))
+
+
+def _world_frames(fn, wav, shift, fs, dftlen, **rows):
+    """The checks the two WORLD analysis ops share: wav [N] and the rows [T] (fp32 device, no backward) -> T."""
+    pulse_check(dftlen, fs)
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('shift={} has to be positive'.format(shift))
+    if not torch.is_tensor(wav) or wav.dim() != 1 or wav.numel() >= 1 << 40:
+        raise ValueError('ops.{}: wav is not [N]'.format(fn))
+    T = None
+    for name, t in rows.items():
+        if not torch.is_tensor(t) or t.dim() != 1 or t.numel() >= 1 << 31 or (T is not None and t.numel() != T):
+            raise ValueError('ops.{}: {} is not [{}]'.format(fn, name, 'T' if T is None else T))
+        T = t.numel()
+    _no_backward(fn, wav, *rows.values())
+    f32c(wav, '{}.wav'.format(fn))
+    for name, t in rows.items():
+        f32c(t, '{}.{}'.format(fn, name))
+    return T
+
+
+def world_envelope(wav, rate, shift, fs, dftlen, log=False):
+    """wav [N] and rate [T] (fp32 device; Hz: f0 in a voiced frame, WORLD_UNVOICED_RATE in an unvoiced one, frame i at shift * i)
+    -> SPEC [T, dftlen/2+1], the amplitude envelope that world_synthesis reads (`log`: its logarithm), one workgroup per frame
+    (csrc/worldanalysis.hip, DESIGN.md section 3, after CheapTrick): the power spectrum under a unit-energy Hann window of
+    2 int(1.5 fs / rate) + 1 samples, mirrored below the rate, smoothed over 2/3 of the rate, scaled by fs / rate, and liftered so
+    that the smoothing is undone at the harmonics.  A frame whose window does not fit dftlen is left unwritten."""
+    T = _world_frames('world_envelope', wav, shift, fs, dftlen, rate=rate)
+    spec = torch.empty((T, dftlen // 2 + 1), dtype=torch.float32, device=rate.device)
+    if T == 0:
+        return spec
+    call('ptts_world_envelope', ptr(wav) if wav.numel() else None, wav.numel(), ptr(rate), ptr(spec), T, float(shift), float(fs),
+         int(dftlen), int(bool(log)), stream(), tag=(T, dftlen))
+    return spec
+
+
+def world_aperiodicity(wav, f0, voiced, shift, fs, dftlen, nb):
+    """wav [N], f0 [T] in Hz and voiced [T] (fp32 device; voiced >= 0.5 where the frame is voiced, a bool tensor is converted) ->
+    the band aperiodicities [T, nb] in dB within [-60, 0], on the band axis of fwbnd2spec, one workgroup per frame
+    (csrc/worldanalysis.hip): the energy of the difference of two windows one period apart over their mean
+    energy, per band, from the bins at and above f0.  The row of an unvoiced frame is 0 dB.  The build's own estimator in the place
+    of D4C."""
+    if torch.is_tensor(voiced) and voiced.dtype == torch.bool:
+        voiced = voiced.to(torch.float32)
+    T = _world_frames('world_aperiodicity', wav, shift, fs, dftlen, f0=f0, voiced=voiced)
+    fwbnd_compress_check(nb, fs, dftlen)
+    aper = torch.empty((T, int(nb)), dtype=torch.float32, device=f0.device)
+    if T == 0:
+        return aper
+    fw, fwbytes = _fwbnd_table(f0.device, int(nb), fs, bark_alpha(fs), dftlen)
+    call('ptts_world_aperiodicity', ptr(wav) if wav.numel() else None, wav.numel(), ptr(f0), ptr(voiced), ptr(aper), T, int(nb),
+         float(shift), float(fs), int(dftlen), ptr(fw), fwbytes, stream(), tag=(T, dftlen, int(nb)))
+    return aper
 
 
 # ----------------------------------------------------------------------------------------------

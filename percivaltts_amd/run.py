@@ -1,7 +1,8 @@
 """Experiment script with the shape of the reference's percivaltts/run.py:57-230: a module-level `cfg`,
 `build_model()`, `training(cont)`, `generate()`.  The corpus-preparation stages of the reference
 split in two.  `features_extraction()` is the reference's stage of that name (run.py:147-165) with the build's own waveform
-analysis (VocoderPML.analysisfid_device) in the place of pulsemodel's, the build's own F0 estimator (or a
+analysis (VocoderPML.analysisfid_device or VocoderWORLDAnalysisDevice.analysisfid_device) in the place of
+pulsemodel's or pyworld's, the build's own F0 estimator (or a
 caller's F0 tracks) in the place of the REAPER binary, and Vocoder.preprocwav (resampling, high-pass) in front of both;
 `synthesize_corpus()` writes a synthetic corpus of the same on-disk
 format (headerless float32 `path:(-1,D)`
@@ -118,29 +119,39 @@ def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None,
     in Hz of the high-pass filter in front of the analysis, 'auto' for f0_min as in the reference, None for no filter.  A file
     that is not sampled at the vocoder's rate, or any file with preproc_hp, goes through vocoder.preprocwav (resampling, then the
     filter; csrc/preproc.hip) and vocoder.analysis_device; a file at the vocoder's rate without preproc_hp takes
-    analysisfid_device as before."""
+    analysisfid_device as before.  A WORLD vocoder with an analysis (vocoders.VocoderWORLDAnalysisDevice) has four streams,
+    `rawpaths` = [f0_path, spec_path, noise_path, vuv_path], by default the reference's <wavdir>_WORLD_lf0, .._fwlspec<N>,
+    .._fwdbap<N>/*.fwdbap and .._vuv1/*.vuv (run.py:103-105)."""
     fids = readids(cfg.fileids) if fids is None else fids
     if not hasattr(vocoder, 'analysisfid_device'):
         raise ValueError('features_extraction: {} has no waveform analysis in this build'.format(vocoder.name()))
     wav_path = cp + 'wav/*.wav' if wav_path is None else wav_path
+    world = isinstance(vocoder, vocoders.VocoderWORLD)      # four streams: the noise stream is 'fwdbap', and there is a 'vuv' one
     if rawpaths is None:
-        base = os.path.dirname(wav_path) + '_PML'
+        base = os.path.dirname(wav_path) + ('_WORLD' if world else '_PML')
+        noisetag = 'fwdbap' if world else 'fwnm'
         spec_raw = ('_mcep' + str(vocoder.specsize()) + '/*.mcep' if getattr(vocoder, 'spec_type', 'fwbnd') == 'mcep'
                     else '_fwlspec' + str(vocoder.specsize()) + '/*.fwlspec')
         rawpaths = [base + '_lf0/*.lf0', base + spec_raw,
-                    base + '_fwnm' + str(vocoder.noisesize()) + '/*.fwnm']
+                    base + '_' + noisetag + str(vocoder.noisesize()) + '/*.' + noisetag]
+        if world:
+            rawpaths.append(base + '_vuv1/*.vuv')
+    nstreams = 4 if world else 3
+    outputpathdicts = {'f0': rawpaths[0], 'spec': rawpaths[1], 'noise': rawpaths[2]}
+    if world:
+        outputpathdicts['vuv'] = rawpaths[3]
     if preproc_hp == 'auto':
         preproc_hp = f0_min
     for fid in fids:
         fwav = wav_path.replace('*', fid)
         if preproc_hp is None and vocoders.wavfs(fwav) == int(round(vocoder.fs)):
-            vocoder.analysisfid_device(fid, wav_path, f0in_path, f0_min, f0_max, {'f0': rawpaths[0], 'spec': rawpaths[1], 'noise': rawpaths[2]})
+            vocoder.analysisfid_device(fid, wav_path, f0in_path, f0_min, f0_max, outputpathdicts)
             continue
-        print('Extracting PML features from: ' + fwav)
+        print('Extracting {} features from: '.format('WORLD' if world else 'PML') + fwav)
         wav, fs = vocoders.wavread(fwav)
         wav = vocoder.preprocwav(wav, fs, highpass=preproc_hp)
         f0 = None if f0in_path is None else np.fromfile(f0in_path.replace('*', fid), dtype=np.float32)
-        vocoder.write_streams(vocoder.analysis_device(wav, f0, f0_min, f0_max), *[p.replace('*', fid) for p in rawpaths[:3]])
+        vocoder.write_streams(vocoder.analysis_device(wav, f0, f0_min, f0_max), *[p.replace('*', fid) for p in rawpaths[:nstreams]])
     return features_compose(rawpaths, fids=fids, win_convention=win_convention)
 
 

@@ -15,8 +15,11 @@ DESIGN.md section 3; VocoderWORLD itself has none); `synthesis` keeps its name f
 (`VocoderF0Spec.f0_estimate_device`, csrc/f0.hip); `compress_spectrum` is the inverse of `decompress_spectrum` for 'fwbnd'.
 `VocoderF0Spec.compress_spectrum_device` is that inverse for both spectral types: for 'mcep' the build's own least-squares fit on
 the warped axis (ops.spec2mcep, csrc/spectrum.hip) in the place of SPTK's, for which `compress_spectrum` keeps
-its name and keeps raising; `analysis_device` takes either type.
-`analysisf` / `analysisfid` keep their names for pulsemodel's analysis and keep raising.  `Vocoder.preprocwav` (vocoders.py:45-63) is
+its name and keeps raising; `analysis_device` takes either type.  `VocoderWORLDAnalysisDevice` adds the same three methods and
+`write_streams` for the WORLD parameters (ln f0 | spec | aperiodicity [dB] | vuv): the build's own analysis, the counterpart of
+`VocoderWORLDDevice.synthesis_device` (csrc/worldanalysis.hip, DESIGN.md section 3: an envelope after CheapTrick, band
+aperiodicities from two windows one period apart), in the place of pyworld's; VocoderWORLD and VocoderWORLDDevice have none.
+`analysisf` / `analysisfid` keep their names for pulsemodel's / pyworld's analysis and keep raising.  `Vocoder.preprocwav` (vocoders.py:45-63) is
 the step in front of the analysis, on the device (csrc/preproc.hip): the build's own rational-ratio resampler in
 the place of pulsemodel's, and the zero-phase order-4 Butterworth high-pass with `highpass` as the cut-off in Hz.
 """
@@ -429,3 +432,84 @@ class VocoderWORLDDevice(VocoderWORLD):
         if noise is None:
             noise = ops.normal((wavlen,), device=x.device, i0=0)
         return ops.world_synthesis(SPEC, aper, table, noise, self.fs, self.dftlen, wavlen).cpu().numpy()
+
+
+class VocoderWORLDAnalysisDevice(VocoderWORLDDevice):
+    """VocoderWORLDDevice with the build's own waveform analysis for its parameters, the counterpart of its synthesis_device.  A
+    class of its own because VocoderWORLDDevice, like VocoderWORLD, is known to have no analysis; run.features_extraction takes
+    this one (isinstance VocoderWORLD, with analysisfid_device)."""
+
+    def analysis_device(self, wav, f0, f0_min, f0_max):
+        """A mono waveform at self.fs (any float array) and an F0 track in Hz, one value per frame at shift * i (<= 0: unvoiced;
+        None: the track of f0_estimate_device) -> the parameters [T, featuressizeraw()] float32, columns ln f0 | spec bands or
+        mel-cepstrum | aperiodicity bands [dB] | vuv, by the build's own analysis (DESIGN.md section 3): vuv_i = 1 where f0_i > 0;
+        ln of ops.f0_track's continuous track (the reference interpolates before np.log as well); the envelope of every frame at
+        the rate f0_i where voiced and ops.WORLD_UNVOICED_RATE where not (ops.world_envelope), compressed by self.spec_type
+        (compress_spectrum_device, log=True); the band aperiodicities of the voiced frames, 0 dB in the unvoiced ones
+        (ops.world_aperiodicity).  Not built: a StoneMask-style refinement of f0, D4C's group-delay statistics, the reference's
+        linbnd2fwbnd of a per-bin aperiodicity (the bands are estimated directly)."""
+        import torch
+        from . import backend_hip, ops_offline as ops
+        if self.spec_type not in ('fwbnd', 'mcep'):
+            raise ValueError("analysis_device: spec_type is 'fwbnd' or 'mcep', got {!r}".format(self.spec_type))
+        ops.world_analysis_check(self.dftlen, self.fs, self.shift, f0_min, f0_max)
+        if self.spec_type == 'fwbnd':
+            ops.fwbnd_compress_check(self.spec_size, self.fs, self.dftlen)
+        else:
+            ops.spec2mcep_check(self.spec_size - 1, bark_alpha(self.fs), self.dftlen)
+        ops.fwbnd_compress_check(self.aper_size, self.fs, self.dftlen)
+        wav = np.asarray(wav, dtype=np.float64)
+        if wav.ndim != 1 or not np.isfinite(wav).all():
+            raise ValueError('analysis_device: wav is not a finite [N] waveform')
+        if f0 is None:
+            f0 = self.f0_estimate_device(wav, f0_min, f0_max)
+        track = ops.f0_track(f0, f0_min, f0_max, self.fs, self.shift, self.dftlen, wavlen=wav.size)
+        vuv = (np.asarray(f0, dtype=np.float64)[:track.size] > 0).astype(np.float32)
+        rate = np.where(vuv > 0, track, np.float32(ops.WORLD_UNVOICED_RATE)).astype(np.float32)
+        dev = backend_hip.device()
+        w = torch.from_numpy(wav.astype(np.float32)).to(dev)
+        lspec = ops.world_envelope(w, torch.from_numpy(rate).to(dev), self.shift, self.fs, self.dftlen, log=True)
+        aper = ops.world_aperiodicity(w, torch.from_numpy(track).to(dev), torch.from_numpy(vuv).to(dev), self.shift, self.fs,
+                                      self.dftlen, self.aper_size)
+        bands = self.compress_spectrum_device(lspec, log=True)
+        lf0 = np.log(track.astype(np.float64)).astype(np.float32)
+        return np.concatenate([lf0[:, None], bands.cpu().numpy(), aper.cpu().numpy(), vuv[:, None]], axis=1)
+
+    def analysisf_device(self, fwav, f0_in, ff0, f0_min, f0_max, fspec, faper, fvuv, **kwargs):
+        """analysis_device from file to files, where the reference's analysisf writes them (vocoders.py:234-284): fwav a 16-bit mono
+        wave file at self.fs, f0_in a headerless float32 file, or an array, of Hz values per frame, or None for the build's own
+        estimate; ff0 gets ln f0, fspec the spectral bands, faper the aperiodicity bands in dB, fvuv the voicing decisions,
+        headerless float32 (write_streams).  Another fs and any preproc_hp (the one keyword taken, None) stay a ValueError here, as
+        in VocoderPML.analysisf_device: such a file goes through preprocwav and analysis_device, as
+        run.features_extraction(..., preproc_hp=) does."""
+        if kwargs.get('preproc_hp') is not None:
+            raise ValueError('analysisf_device: preproc_hp={!r}: the high-pass pre-processing is not built'.format(kwargs['preproc_hp']))
+        if set(kwargs) - {'preproc_hp'}:
+            raise ValueError('analysisf_device: unknown arguments {}'.format(sorted(set(kwargs) - {'preproc_hp'})))
+        print('Extracting WORLD features from: ' + fwav)
+        wav, fs = wavread(fwav)
+        if fs != int(round(self.fs)):
+            raise ValueError('analysisf_device: {} is sampled at {} Hz, the vocoder at {} (resampling is not built)'.format(fwav, fs, self.fs))
+        f0 = np.fromfile(f0_in, dtype=np.float32) if isinstance(f0_in, str) else f0_in
+        return self.write_streams(self.analysis_device(wav, f0, f0_min, f0_max), ff0, fspec, faper, fvuv)
+
+    def write_streams(self, CMP, ff0, fspec, faper, fvuv):
+        """The parameters [T, featuressizeraw()] of analysis_device -> the four headerless float32 files of analysisf_device: ff0
+        gets ln f0, fspec the spectral bands, faper the aperiodicity bands, fvuv the voicing decisions; missing directories are
+        made.  Returns T."""
+        s1 = 1 + self.spec_size
+        s2 = s1 + self.aper_size
+        for path, cols in ((ff0, CMP[:, 0]), (fspec, CMP[:, 1:s1]), (faper, CMP[:, s1:s2]), (fvuv, CMP[:, s2:])):
+            if os.path.dirname(path) and not os.path.isdir(os.path.dirname(path)):
+                os.makedirs(os.path.dirname(path))
+            np.ascontiguousarray(cols, dtype=np.float32).tofile(path)
+        return CMP.shape[0]
+
+    def analysisfid_device(self, fid, wav_path, f0in_path, f0_min, f0_max, outputpathdicts, **kwargs):
+        """analysisf_device with the '*' of every path replaced by the file id, as the reference's analysisfid
+        (vocoders.py:297-298); outputpathdicts: {'f0': .., 'spec': .., 'noise': .., 'vuv': ..}; f0in_path None: the build's own F0
+        estimate."""
+        f0_in = None if f0in_path is None else f0in_path.replace('*', fid)
+        return self.analysisf_device(wav_path.replace('*', fid), f0_in, outputpathdicts['f0'].replace('*', fid),
+                                     f0_min, f0_max, outputpathdicts['spec'].replace('*', fid),
+                                     outputpathdicts['noise'].replace('*', fid), outputpathdicts['vuv'].replace('*', fid), **kwargs)
