@@ -883,6 +883,26 @@ int ptts_world_aperiodicity(const float* wav, long long N, const float* f0, cons
  *   smaller) is followed back: f0 [T] = the chosen slot's freq, 0 for slot 0; path [T] int32 (or
  *   NULL) = the slot.  Back-pointers live in LDS, so T <= ptts_f0_viterbi_max_frames(ncand)
  *   (32768 up to ncand = 8, 16384 above; 0 for an ncand outside 2 .. 16): more is PTTS_EINVAL.
+ * ptts_f0_refine: the instantaneous frequency of the harmonics around a given track (after the
+ *   published StoneMask; the definition is this build's own), one workgroup per frame, no
+ *   transform.  c = rnd(i shift fs), f = f0[i]; out [T] fp32, status [T] int32 or NULL:
+ *   1. f > 0 is false (NaN included): out 0, status 0 (unvoiced).
+ *   2. f < f0_min or f > f0_max: out f, status 2; nothing of the waveform is read.
+ *   3. hw = rnd(1.5 fs / f), j = -hw .. hw; c - hw < 0 or c + hw >= N: out f, status 2.
+ *   4. u = j / (2 (hw + 1)), w_j = 0.42 + 0.5 cos(2 pi u) + 0.08 cos(4 pi u), its derivative per
+ *      sample w'_j = -(pi / (hw + 1)) (0.5 sin(2 pi u) + 0.16 sin(4 pi u)).
+ *   5. X(nu) = sum_j wav[c + j] w_j e^{-2 pi i nu j / fs}, Xd(nu) the same sum with w'_j,
+ *      IF(nu) = nu - (fs / 2 pi) (Im Xd Re X - Re Xd Im X) / |X|^2.
+ *   6. A pass with H harmonics from g: h = 1 .. H, stopping at the first h with h g >= fs/2;
+ *      nu = h g; a harmonic whose |X|^2 > 0 is false is skipped; num += |X| IF(nu),
+ *      den += |X| h.  den > 0 is false: out f, status 3.  Otherwise g = num / den.
+ *   7. Two passes: H = 2 from g = f, then H = 6 from the result; the window stays that of f.
+ *   8. g finite, |g / f - 1| <= 0.2 and f0_min <= g <= f0_max: out (float) g, status 1;
+ *      otherwise out f, status 3.
+ *   PTTS_EINVAL without a launch unless 0 < f0_min <= f0_max <= fs/2, shift > 0, fs > 0,
+ *   2 rnd(1.5 fs / f0_min) + 1 <= 16384, T >= 0, N >= 0 and wav (unless N = 0), f0, out are not
+ *   NULL.  N = 0 with T > 0 is legal: every voiced frame gets status 2.  Frames are independent,
+ *   no atomics: the same input gives the same bytes.
  * T = 0 succeeds without a launch.
  * ------------------------------------------------------------------------------------- */
 int ptts_f0_candidates(const float* wav, long long N, const double* rw, size_t rw_bytes, float* freq, float* strength, int* n,
@@ -891,6 +911,8 @@ int ptts_f0_candidates(const float* wav, long long N, const double* rw, size_t r
 int ptts_f0_viterbi_max_frames(int ncand);
 int ptts_f0_viterbi(const float* freq, const float* strength, const int* n, float* f0, int* path, int T, int ncand, double shift,
                     double octave_jump_cost, double voiced_unvoiced_cost, void* stream);
+int ptts_f0_refine(const float* wav, long long N, const float* f0, float* out, int* status /* or NULL */, int T,
+                   double shift, double fs, double f0_min, double f0_max, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Waveform pre-processing (csrc/preproc.hip; the reference's Vocoder.preprocwav,

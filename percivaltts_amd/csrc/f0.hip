@@ -19,14 +19,24 @@
 //                  smaller p, corr = 0.01 / shift; trans = 0 between unvoiced slots, voiced_unvoiced_cost between a voiced and an
 //                  unvoiced one, octave_jump_cost |log2 F_p - log2 F_j| between voiced ones.  The last frame's smallest cost (ties to
 //                  the smaller slot) is followed back.
+// refinement       (ptts_f0_refine; after the published StoneMask, the definition is the build's own.)  Frame i with f = f0[i]:
+//                  f > 0 false: 0, status 0.  f outside [f0_min, f0_max]: f, status 2, nothing of the waveform is read.
+//                  hw = rnd(1.5 fs / f), j = -hw .. hw; c_i - hw < 0 or c_i + hw >= N: f, status 2.  u = j / (2 (hw + 1)),
+//                  w_j = 0.42 + 0.5 cos(2 pi u) + 0.08 cos(4 pi u), w'_j = -(pi / (hw + 1)) (0.5 sin(2 pi u) + 0.16 sin(4 pi u));
+//                  X(nu) = sum_j wav[c_i + j] w_j e^{-2 pi i nu j / fs}, Xd(nu) the same with w'_j,
+//                  IF(nu) = nu - (fs / 2 pi) (Im Xd Re X - Re Xd Im X) / |X|^2.  A pass with H harmonics from g: h = 1 .. H up to
+//                  the first with h g >= fs/2, nu = h g, a harmonic whose |X|^2 > 0 is false is skipped, num += |X| IF(nu),
+//                  den += |X| h; den > 0 false: f, status 3; else g = num / den.  Two passes, H = 2 from g = f, then H = 6, the
+//                  window that of f.  g finite, |g / f - 1| <= 0.2 and f0_min <= g <= f0_max: (float)g, status 1; else f, status 3.
 //
 // Data is fp32 in memory, arithmetic fp64, every decision is taken in fp64 with the operation order written here (no fused
 // contraction), so that a host restatement takes the same ones.  ptts_f0_candidates: one workgroup per frame holds ONE packed
 // L-point buffer (the frame, its spectrum, the power spectrum, then r in place), a quarter circle of twiddles and one strength per
 // lag: 1.25 M complex fp64 + (lmax + 2) fp64, 80 KiB + 16 KiB at L = 8192.  ptts_f0_viterbi: one wave64 for the utterance, lane
 // (j, p) evaluates one transition, the minimum over p is a butterfly inside the group of lanes that share j, costs stay in
-// registers; back-pointers are four bits a slot, one or two words a frame, in LDS.  No atomics, no polling, nothing between
-// workgroups.
+// registers; back-pointers are four bits a slot, one or two words a frame, in LDS.  ptts_f0_refine: one workgroup per frame, no
+// transform: the spectrum is read at the at most eight frequencies a frame needs by direct sums over the window.  No atomics, no
+// polling, nothing between workgroups.
 #include <climits>
 #include <cmath>
 #include "common.h"
@@ -377,6 +387,117 @@ __global__ __launch_bounds__(64) void f0_viterbi_kernel(const float* __restrict_
     }
 }
 
+constexpr int F0_REFINE_MAX_WINDOW = 16384;             // samples of the window at f0_min
+constexpr int F0_REFINE_H1 = 2, F0_REFINE_H2 = 6;       // harmonics of the two passes
+
+// f0_block_sum over NV values at once, in the same fixed order: the wave's butterfly, then the waves in turn.  red: [nwaves * NV]
+template <int NV> __device__ __forceinline__ void f0_block_sum_n(double* v, double* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+#pragma unroll
+    for (int q = 0; q < NV; ++q) v[q] = wave_sum(v[q]);
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) red[wave * NV + q] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        double tot = red[q];
+        for (int w = 1; w < nwaves; ++w) tot += red[w * NV + q];
+        v[q] = tot;
+    }
+}
+
+// One pass of the refinement from g over the harmonics h = 1 .. H (those below fs/2): the new value num / den, or false where
+// den > 0 is false.  x = wav + c is the window's centre; every lane returns the same.  One sincospi a sample gives the phasor of the
+// fundamental, its powers those of the harmonics; the window comes from one more and the double angle.
+template <int H> __device__ __forceinline__ bool f0_refine_pass(const float* __restrict__ x, const int hw, const double fs, double& g,
+                                                                double* red) {
+    int nh = 0;
+    while (nh < H && !((double)(nh + 1) * g >= 0.5 * fs)) ++nh;
+    double acc[4 * H];                                          // Re X, Im X, Re Xd, Im Xd of every harmonic
+#pragma unroll
+    for (int q = 0; q < 4 * H; ++q) acc[q] = 0.0;
+    const double span = 2.0 * (double)(hw + 1);
+    for (int n = threadIdx.x; n <= 2 * hw; n += blockDim.x) {
+        const int j = n - hw;
+        double s1, c1, sp, cp;
+        sincospi(2.0 * ((double)j / span), &s1, &c1);
+        const double s2 = 2.0 * s1 * c1, c2 = 2.0 * c1 * c1 - 1.0;
+        const double v = (double)x[j];
+        const double a = v * (0.42 + 0.5 * c1 + 0.08 * c2);
+        const double b = v * (-(M_PI / (double)(hw + 1)) * (0.5 * s1 + 0.16 * s2));
+        sincospi(2.0 * g * (double)j / fs, &sp, &cp);
+        double zr = cp, zi = -sp;                               // e^{-2 pi i h g j / fs}
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+            if (h < nh) {
+                acc[4 * h + 0] += a * zr;
+                acc[4 * h + 1] += a * zi;
+                acc[4 * h + 2] += b * zr;
+                acc[4 * h + 3] += b * zi;
+                const double t = zr * cp + zi * sp;
+                zi = zi * cp - zr * sp;
+                zr = t;
+            }
+        }
+    }
+    f0_block_sum_n<4 * H>(acc, red);
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        if (h < nh) {
+            const double xr = acc[4 * h], xi = acc[4 * h + 1], dr = acc[4 * h + 2], di = acc[4 * h + 3];
+            const double p = xr * xr + xi * xi;
+            if (p > 0.0) {
+                const double nu = (double)(h + 1) * g, m = sqrt(p);
+                num += m * (nu - (fs / (2.0 * M_PI)) * (di * xr - dr * xi) / p);
+                den += m * (double)(h + 1);
+            }
+        }
+    }
+    if (!(den > 0.0)) return false;
+    g = num / den;
+    return true;
+}
+
+// One workgroup per frame: its lanes share the window's samples, one block sum a pass.  Every exit before or between the block sums
+// depends on f0[i], the launch's scalars and the block sums alone, the same in every lane.  static LDS: 4 waves * 24 doubles.
+// The host has checked 2 rnd(1.5 fs / f0_min) + 1 <= F0_REFINE_MAX_WINDOW, so hw fits an int.
+__global__ __launch_bounds__(F0_THREADS) void f0_refine_kernel(const float* __restrict__ wav, const long long N,
+                                                               const float* __restrict__ f0, float* __restrict__ out,
+                                                               int* __restrict__ status, const double shift, const double fs,
+                                                               const double f0_min, const double f0_max) {
+    __shared__ double red[(F0_THREADS / 64) * 4 * F0_REFINE_H2];
+    const int i = blockIdx.x;
+    const float fin = f0[i];
+    const double f = (double)fin;
+    float res = fin;
+    int st = 2;
+    if (!(f > 0.0)) {
+        res = 0.f;
+        st = 0;
+    } else if (!(f < f0_min || f > f0_max)) {
+        const double hwd = f0_rnd(1.5 * fs / f), cd = f0_rnd((double)i * shift * fs);
+        if (!(cd - hwd < 0.0 || cd + hwd >= (double)N)) {       // the whole window lies inside the waveform
+            const int hw = (int)hwd;
+            const float* x = wav + (long long)cd;
+            double g = f;
+            st = 3;
+            if (f0_refine_pass<F0_REFINE_H1>(x, hw, fs, g, red) && f0_refine_pass<F0_REFINE_H2>(x, hw, fs, g, red) &&
+                g - g == 0.0 && fabs(g / f - 1.0) <= 0.2 && g >= f0_min && g <= f0_max) {
+                res = (float)g;
+                st = 1;
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        out[i] = res;
+        if (status) status[i] = st;
+    }
+}
+
 static int f0_log2(int dftlen) {
     for (int l = 8; l <= 13; ++l)
         if (dftlen == (1 << l)) return l;
@@ -455,4 +576,21 @@ extern "C" int ptts_f0_viterbi(const float* freq, const float* strength, const i
     hipLaunchKernelGGL(f0_viterbi_kernel, dim3(1), dim3(64), (size_t)lds, (hipStream_t)stream, freq, strength, n, f0, path, T, ncand, log_group,
                        words, 0.01 / shift, octave_jump_cost, voiced_unvoiced_cost);
     return check_launch("f0_viterbi");
+}
+
+extern "C" int ptts_f0_refine(const float* wav, long long N, const float* f0, float* out, int* status, int T, double shift, double fs,
+                              double f0_min, double f0_max, void* stream) {
+    PTTS_REQUIRE(T >= 0 && N >= 0, "f0_refine: T=%d N=%lld", T, N);
+    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "f0_refine: fs=%g", fs);
+    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "f0_refine: shift=%g", shift);
+    PTTS_REQUIRE(f0_min > 0.0 && f0_min <= f0_max && f0_max <= 0.5 * fs, "f0_refine: f0_min=%g f0_max=%g (positive, ordered, at most fs/2)",
+                 f0_min, f0_max);
+    const double W = 2.0 * floor(1.5 * fs / f0_min + 0.5) + 1.0;
+    PTTS_REQUIRE(W <= (double)F0_REFINE_MAX_WINDOW, "f0_refine: the window at f0_min=%g (%.0f samples) is longer than %d", f0_min, W,
+                 F0_REFINE_MAX_WINDOW);
+    if (T == 0) return PTTS_OK;
+    PTTS_REQUIRE(f0 && out && (wav || N == 0), "f0_refine: null tensor");
+    hipLaunchKernelGGL(f0_refine_kernel, dim3(T), dim3(F0_THREADS), 0, (hipStream_t)stream, wav, N, f0, out, status, shift, fs, f0_min,
+                       f0_max);
+    return check_launch("f0_refine");
 }

@@ -26,7 +26,7 @@ __all__ = [
     'fwbnd_compress_check', 'fwbnd_compress',
     'world_analysis_check', 'world_envelope', 'world_aperiodicity',
     'F0_MIN_NCAND', 'F0_MAX_NCAND', 'F0_MAX_FRAMES', 'F0_CONSTANTS', 'f0_check', 'f0_frame_count', 'f0_window_table', 'f0_candidates',
-    'f0_viterbi', 'f0_estimate',
+    'f0_viterbi', 'f0_estimate', 'F0_REFINE_MAX_WINDOW', 'f0_refine_check', 'f0_refine',
     'RESAMPLE_MAX_UP', 'RESAMPLE_MAX_TABLE_BYTES', 'HIGHPASS_PADLEN', 'HIGHPASS_MAX_PADLEN', 'PREPROC_MAX_UTTS', 'preproc_check',
     'resample_length', 'resample_table', 'resample', 'highpass_tile', 'highpass_zerophase',
     'LABELS_MAX_LABEL', 'LABELS_CC_POINTS', 'LABELS_ANCHOR_START', 'LABELS_ANCHOR_END', 'LABELS_WILD', 'LABELS_CAPTURE_DIGITS',
@@ -1085,6 +1085,67 @@ def f0_estimate(wav, shift, fs, dftlen, f0_min, f0_max, ncand=8, **constants):
     path = {k: constants[k] for k in ('octave_jump_cost', 'voiced_unvoiced_cost') if k in constants}
     freq, strength, n, _ = f0_candidates(wav, T, shift, fs, dftlen, f0_min, f0_max, gpeak, ncand=ncand, **cand)
     return f0_viterbi(freq, strength, n, shift, **path).cpu().numpy()
+
+
+F0_REFINE_MAX_WINDOW = 16384        # samples of the refinement's window at f0_min, 2 rnd(1.5 fs / f0_min) + 1
+
+
+def f0_refine_check(fs, shift, f0_min, f0_max):
+    """ValueError for parameters ptts_f0_refine does not take: a positive shift and fs,
+    0 < f0_min <= f0_max <= fs/2 and a window at f0_min, 2 rnd(1.5 fs / f0_min) + 1 samples, of at most F0_REFINE_MAX_WINDOW.
+    Returns that window length.  Touches no device."""
+    fs, shift, f0_min, f0_max = float(fs), float(shift), float(f0_min), float(f0_max)
+    if not 0.0 < shift < 1e3:
+        raise ValueError('shift={} has to be positive'.format(shift))
+    if not 0.0 < fs < 1e9:
+        raise ValueError('fs={} has to be positive'.format(fs))
+    if not 0.0 < f0_min <= f0_max <= 0.5 * fs:
+        raise ValueError('f0_min={} and f0_max={} have to be positive, ordered and at most fs/2 = {}'.format(f0_min, f0_max, 0.5 * fs))
+    W = 2.0 * math.floor(1.5 * fs / f0_min + 0.5) + 1.0
+    if W > F0_REFINE_MAX_WINDOW:
+        raise ValueError('the window at f0_min={} ({:.0f} samples) is longer than {}'.format(f0_min, W, F0_REFINE_MAX_WINDOW))
+    return int(W)
+
+
+def f0_refine(wav, f0, shift, fs, f0_min, f0_max, want_status=False):
+    """A mono waveform at fs (any float array, or an fp32 device tensor) and an F0 track f0 [T] in Hz (an array or a tensor; frame i
+    at shift * i, <= 0 or NaN: unvoiced) -> the track refined by the instantaneous frequency of its harmonics, numpy float32 [T]
+    (ptts_f0_refine, csrc/f0.hip; after the published StoneMask, one workgroup per frame); with `want_status`
+    also status [T] int32: 0 unvoiced (the value is 0), 1 refined, 2 left as it was (outside [f0_min, f0_max], or the window of
+    2 rnd(1.5 fs / f0_i) + 1 samples leaves the waveform), 3 left as it was (no energy at the harmonics, or a result more than 20 %
+    away or outside [f0_min, f0_max]).  The voicing pattern does not change."""
+    f0_refine_check(fs, shift, f0_min, f0_max)
+    if torch.is_tensor(wav):
+        if wav.dim() != 1 or wav.numel() >= 1 << 40:
+            raise ValueError('ops.f0_refine: wav is not [N]')
+        _no_backward('f0_refine', wav)
+    else:
+        wav = np.asarray(wav, dtype=np.float64)
+        if wav.ndim != 1 or not np.isfinite(wav).all():
+            raise ValueError('ops.f0_refine: wav is not a finite [N] waveform')
+    if torch.is_tensor(f0):
+        _no_backward('f0_refine', f0)
+        if f0.dim() != 1 or not (f0.is_floating_point() or f0.numel() == 0):
+            raise ValueError('ops.f0_refine: f0 is not [T] Hz values')
+    else:
+        f0 = np.array(f0, dtype=np.float32)                     # a copy: the caller's array may be read-only
+        if f0.ndim != 1:
+            raise ValueError('ops.f0_refine: f0 is not [T] Hz values')
+        f0 = torch.from_numpy(f0)
+    T = f0.numel()
+    if T >= 1 << 31:
+        raise ValueError('ops.f0_refine: T={} frames'.format(T))
+    if not torch.is_tensor(wav):
+        from . import backend_hip
+        wav = torch.from_numpy(wav.astype(np.float32)).to(backend_hip.device())
+    f32c(wav, 'f0_refine.wav')
+    f0 = f0.to(device=wav.device, dtype=torch.float32).contiguous()
+    out = torch.empty(T, dtype=torch.float32, device=wav.device)
+    status = torch.empty(T, dtype=torch.int32, device=wav.device) if want_status else None
+    if T > 0:
+        call('ptts_f0_refine', ptr(wav) if wav.numel() else None, wav.numel(), ptr(f0), ptr(out), ptr(status), T, float(shift),
+             float(fs), float(f0_min), float(f0_max), stream(), tag=(T,))
+    return (out.cpu().numpy(), status.cpu().numpy()) if want_status else out.cpu().numpy()
 
 
 # ----------------------------------------------------------------------------------------------

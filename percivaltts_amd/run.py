@@ -108,7 +108,7 @@ def features_compose(rawpaths, fids=None, win_convention='mlpg'):
 
 
 def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None, f0_min=70, f0_max=600, win_convention='mlpg',
-                        preproc_hp=None):
+                        f0_refine=None, preproc_hp=None):
     """The reference's features_extraction (run.py:147-165): every file id's waveform `wav_path` ('dir/*.wav', by default
     <corpus>/wav/*.wav) goes through vocoder.analysisfid_device with the F0 track of `f0in_path` ('dir/*.f0': headerless float32 Hz
     values, one per frame, <= 0 unvoiced) or, with f0in_path None, the track of the build's own estimator
@@ -121,10 +121,19 @@ def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None,
     filter; csrc/preproc.hip) and vocoder.analysis_device; a file at the vocoder's rate without preproc_hp takes
     analysisfid_device as before.  A WORLD vocoder with an analysis (vocoders.VocoderWORLDAnalysisDevice) has four streams,
     `rawpaths` = [f0_path, spec_path, noise_path, vuv_path], by default the reference's <wavdir>_WORLD_lf0, .._fwlspec<N>,
-    .._fwdbap<N>/*.fwdbap and .._vuv1/*.vuv (run.py:103-105)."""
+    .._fwdbap<N>/*.fwdbap and .._vuv1/*.vuv (run.py:103-105).  `f0_refine`: True or False sets vocoder.f0_refine (the F0
+    refinement in front of the analysis, vocoders.VocoderF0Spec.f0_refine_device) for the duration of the call, None leaves the
+    vocoder as it is."""
     fids = readids(cfg.fileids) if fids is None else fids
     if not hasattr(vocoder, 'analysisfid_device'):
         raise ValueError('features_extraction: {} has no waveform analysis in this build'.format(vocoder.name()))
+    with vocoder.f0_refine_as(f0_refine):
+        rawpaths = _extract_raw_streams(f0in_path, wav_path, rawpaths, fids, f0_min, f0_max, preproc_hp)
+    return features_compose(rawpaths, fids=fids, win_convention=win_convention)
+
+
+def _extract_raw_streams(f0in_path, wav_path, rawpaths, fids, f0_min, f0_max, preproc_hp):
+    """The analysis loop of features_extraction: writes the raw streams of every file id and returns `rawpaths`."""
     wav_path = cp + 'wav/*.wav' if wav_path is None else wav_path
     world = isinstance(vocoder, vocoders.VocoderWORLD)      # four streams: the noise stream is 'fwdbap', and there is a 'vuv' one
     if rawpaths is None:
@@ -152,7 +161,7 @@ def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None,
         wav = vocoder.preprocwav(wav, fs, highpass=preproc_hp)
         f0 = None if f0in_path is None else np.fromfile(f0in_path.replace('*', fid), dtype=np.float32)
         vocoder.write_streams(vocoder.analysis_device(wav, f0, f0_min, f0_max), *[p.replace('*', fid) for p in rawpaths[:nstreams]])
-    return features_compose(rawpaths, fids=fids, win_convention=win_convention)
+    return rawpaths
 
 
 def contexts_extraction(lab_path, fids, lab_questions, labbin_path, labs_wpath, inpath, lab_type='state', id_valid_start=-1,

@@ -12,7 +12,9 @@ section 3), `VocoderWORLDDevice.synthesis_device` its periodic-plus-aperiodic sy
 DESIGN.md section 3; VocoderWORLD itself has none); `synthesis` keeps its name for pulsemodel's / pyworld's waveform and keeps raising.  `VocoderPML.analysis_device` (with
 `analysisf_device` / `analysisfid_device` around it) is the build's own waveform analysis for the same parameters
 (csrc/analysis.hip), from a caller's F0 track or, without one, from the build's own F0 estimator
-(`VocoderF0Spec.f0_estimate_device`, csrc/f0.hip); `compress_spectrum` is the inverse of `decompress_spectrum` for 'fwbnd'.
+(`VocoderF0Spec.f0_estimate_device`, csrc/f0.hip); with `VocoderF0Spec.f0_refine` set, either track goes through the build's F0
+refinement first (`f0_refine_device`, csrc/f0.hip; the StoneMask step of the reference's WORLD chain); `compress_spectrum` is the
+inverse of `decompress_spectrum` for 'fwbnd'.
 `VocoderF0Spec.compress_spectrum_device` is that inverse for both spectral types: for 'mcep' the build's own least-squares fit on
 the warped axis (ops.spec2mcep, csrc/spectrum.hip) in the place of SPTK's, for which `compress_spectrum` keeps
 its name and keeps raising; `analysis_device` takes either type.  `VocoderWORLDAnalysisDevice` adds the same three methods and
@@ -25,6 +27,7 @@ the place of pulsemodel's, and the zero-phase order-4 Butterworth high-pass with
 """
 from __future__ import print_function
 
+import contextlib
 import os
 
 import numpy as np
@@ -34,6 +37,11 @@ def bark_alpha(fs):
     """All-pass coefficient of the Bark-like warping at sampling frequency fs (the reference's sigproc.bark_alpha)."""
     from . import ops_offline as ops
     return ops.bark_alpha(fs)
+
+
+def _check_f0_refine(value):
+    if value is not None and not isinstance(value, bool):
+        raise ValueError('f0_refine={!r} is not None, True or False'.format(value))
 
 
 def log2db(x):
@@ -251,6 +259,37 @@ class VocoderF0Spec(Vocoder):
         from . import ops_offline as ops
         return ops.f0_estimate(wav, self.shift, self.fs, self.dftlen, f0_min, f0_max)
 
+    # True: the analysis_device of a subclass passes its F0 track, the caller's or the estimated one, through f0_refine_device.
+    # A class attribute: it does not enter the instance dictionaries, so stored vocoders stay as they are.
+    f0_refine = False
+
+    def f0_refine_device(self, wav, f0, f0_min, f0_max):
+        """A mono waveform at self.fs (any float array) and an F0 track in Hz, one value per frame at shift * i (<= 0: unvoiced) ->
+        the track refined by the instantaneous frequency of its harmonics, numpy float32, the voicing pattern unchanged
+        (ops.f0_refine, csrc/f0.hip): the build's counterpart of the reference's StoneMask step
+        (vocoders.py:261)."""
+        from . import ops_offline as ops
+        return ops.f0_refine(wav, f0, self.shift, self.fs, f0_min, f0_max)
+
+    @contextlib.contextmanager
+    def f0_refine_as(self, value):
+        """Inside the `with` block self.f0_refine is `value` (True or False); None leaves it alone.  Afterwards, also on an
+        exception, the vocoder is as it was: an instance without the attribute of its own has none again."""
+        _check_f0_refine(value)
+        if value is None:
+            yield self
+            return
+        own = 'f0_refine' in vars(self)
+        before = self.f0_refine
+        self.f0_refine = value
+        try:
+            yield self
+        finally:
+            if own:
+                self.f0_refine = before
+            else:
+                del self.f0_refine
+
     def _objmeasures_add_f0spec(self, CMP, REF):
         """F0[Hz]: RMS of the exp(f0) differences; SPEC[dB]: per-band RMS of the log2db differences."""
         self.features_err.setdefault('F0[Hz]', []).append(np.sqrt(np.mean((np.exp(REF[:, 0]) - np.exp(CMP[:, 0]))**2)))
@@ -317,7 +356,7 @@ class VocoderPML(VocoderF0Spec):
         (ops.frame_harmonics), their coherence over neighbouring frames as the noise mask (ops.phase_coherence) and the compression
         of the log-envelope by self.spec_type: 'fwbnd' the least-squares band values (ops.fwbnd_compress), 'mcep' the mel-cepstrum
         of order spec_size - 1 (ops.spec2mcep).  The noise mask is on the fwbnd axis either way.  The counterpart of
-        synthesis_device."""
+        synthesis_device.  Where self.f0_refine is true the track, given or estimated, goes through f0_refine_device first."""
         import torch
         from . import backend_hip, ops_offline as ops
         if self.spec_type not in ('fwbnd', 'mcep'):
@@ -333,6 +372,8 @@ class VocoderPML(VocoderF0Spec):
             raise ValueError('analysis_device: wav is not a finite [N] waveform')
         if f0 is None:
             f0 = self.f0_estimate_device(wav, f0_min, f0_max)
+        if self.f0_refine:
+            f0 = self.f0_refine_device(wav, f0, f0_min, f0_max)
         track = ops.f0_track(f0, f0_min, f0_max, self.fs, self.shift, self.dftlen, wavlen=wav.size)
         dev = backend_hip.device()
         w = torch.from_numpy(wav.astype(np.float32)).to(dev)
@@ -346,19 +387,23 @@ class VocoderPML(VocoderF0Spec):
     def analysisf_device(self, fwav, f0_in, ff0, f0_min, f0_max, fspec, fnm, **kwargs):
         """analysis_device from file to files, where the reference's analysisf writes them (vocoders.py:181-189): fwav a 16-bit mono
         wave file at self.fs, f0_in a headerless float32 file, or an array, of Hz values per frame, or None for the build's own
-        estimate; ff0 gets ln f0, fspec the spectral bands, fnm the noise-mask bands, headerless float32 (write_streams).  Another fs
-        and any preproc_hp (the one keyword taken, None) stay a ValueError here: a file that needs resampling or the high-pass
-        filter goes through preprocwav and analysis_device, as run.features_extraction(..., preproc_hp=) does."""
+        estimate; ff0 gets ln f0, fspec the spectral bands, fnm the noise-mask bands, headerless float32 (write_streams).  The
+        keyword f0_refine (None, True or False) overrides self.f0_refine for this call.  Another fs and any preproc_hp (the other
+        keyword taken, None) stay a ValueError here: a file that needs resampling or the high-pass filter goes through preprocwav
+        and analysis_device, as run.features_extraction(..., preproc_hp=) does."""
         if kwargs.get('preproc_hp') is not None:
             raise ValueError('analysisf_device: preproc_hp={!r}: the high-pass pre-processing is not built'.format(kwargs['preproc_hp']))
-        if set(kwargs) - {'preproc_hp'}:
-            raise ValueError('analysisf_device: unknown arguments {}'.format(sorted(set(kwargs) - {'preproc_hp'})))
+        if set(kwargs) - {'preproc_hp', 'f0_refine'}:
+            raise ValueError('analysisf_device: unknown arguments {}'.format(sorted(set(kwargs) - {'preproc_hp', 'f0_refine'})))
+        _check_f0_refine(kwargs.get('f0_refine'))
         print('Extracting PML features from: ' + fwav)
         wav, fs = wavread(fwav)
         if fs != int(round(self.fs)):
             raise ValueError('analysisf_device: {} is sampled at {} Hz, the vocoder at {} (resampling is not built)'.format(fwav, fs, self.fs))
         f0 = np.fromfile(f0_in, dtype=np.float32) if isinstance(f0_in, str) else f0_in
-        return self.write_streams(self.analysis_device(wav, f0, f0_min, f0_max), ff0, fspec, fnm)
+        with self.f0_refine_as(kwargs.get('f0_refine')):
+            CMP = self.analysis_device(wav, f0, f0_min, f0_max)
+        return self.write_streams(CMP, ff0, fspec, fnm)
 
     def write_streams(self, CMP, ff0, fspec, fnm):
         """The parameters [T, featuressizeraw()] of analysis_device -> the three headerless float32 files of analysisf_device: ff0
@@ -446,8 +491,9 @@ class VocoderWORLDAnalysisDevice(VocoderWORLDDevice):
         ln of ops.f0_track's continuous track (the reference interpolates before np.log as well); the envelope of every frame at
         the rate f0_i where voiced and ops.WORLD_UNVOICED_RATE where not (ops.world_envelope), compressed by self.spec_type
         (compress_spectrum_device, log=True); the band aperiodicities of the voiced frames, 0 dB in the unvoiced ones
-        (ops.world_aperiodicity).  Not built: a StoneMask-style refinement of f0, D4C's group-delay statistics, the reference's
-        linbnd2fwbnd of a per-bin aperiodicity (the bands are estimated directly)."""
+        (ops.world_aperiodicity).  Where self.f0_refine is true the track, given or estimated, goes through f0_refine_device first
+        (the StoneMask step of the reference's chain; the voicing pattern does not change).  Not built: D4C's group-delay
+        statistics, the reference's linbnd2fwbnd of a per-bin aperiodicity (the bands are estimated directly)."""
         import torch
         from . import backend_hip, ops_offline as ops
         if self.spec_type not in ('fwbnd', 'mcep'):
@@ -463,6 +509,8 @@ class VocoderWORLDAnalysisDevice(VocoderWORLDDevice):
             raise ValueError('analysis_device: wav is not a finite [N] waveform')
         if f0 is None:
             f0 = self.f0_estimate_device(wav, f0_min, f0_max)
+        if self.f0_refine:
+            f0 = self.f0_refine_device(wav, f0, f0_min, f0_max)
         track = ops.f0_track(f0, f0_min, f0_max, self.fs, self.shift, self.dftlen, wavlen=wav.size)
         vuv = (np.asarray(f0, dtype=np.float64)[:track.size] > 0).astype(np.float32)
         rate = np.where(vuv > 0, track, np.float32(ops.WORLD_UNVOICED_RATE)).astype(np.float32)
@@ -479,19 +527,23 @@ class VocoderWORLDAnalysisDevice(VocoderWORLDDevice):
         """analysis_device from file to files, where the reference's analysisf writes them (vocoders.py:234-284): fwav a 16-bit mono
         wave file at self.fs, f0_in a headerless float32 file, or an array, of Hz values per frame, or None for the build's own
         estimate; ff0 gets ln f0, fspec the spectral bands, faper the aperiodicity bands in dB, fvuv the voicing decisions,
-        headerless float32 (write_streams).  Another fs and any preproc_hp (the one keyword taken, None) stay a ValueError here, as
+        headerless float32 (write_streams).  The keyword f0_refine (None, True or False) overrides self.f0_refine for this call.
+        Another fs and any preproc_hp (the other keyword taken, None) stay a ValueError here, as
         in VocoderPML.analysisf_device: such a file goes through preprocwav and analysis_device, as
         run.features_extraction(..., preproc_hp=) does."""
         if kwargs.get('preproc_hp') is not None:
             raise ValueError('analysisf_device: preproc_hp={!r}: the high-pass pre-processing is not built'.format(kwargs['preproc_hp']))
-        if set(kwargs) - {'preproc_hp'}:
-            raise ValueError('analysisf_device: unknown arguments {}'.format(sorted(set(kwargs) - {'preproc_hp'})))
+        if set(kwargs) - {'preproc_hp', 'f0_refine'}:
+            raise ValueError('analysisf_device: unknown arguments {}'.format(sorted(set(kwargs) - {'preproc_hp', 'f0_refine'})))
+        _check_f0_refine(kwargs.get('f0_refine'))
         print('Extracting WORLD features from: ' + fwav)
         wav, fs = wavread(fwav)
         if fs != int(round(self.fs)):
             raise ValueError('analysisf_device: {} is sampled at {} Hz, the vocoder at {} (resampling is not built)'.format(fwav, fs, self.fs))
         f0 = np.fromfile(f0_in, dtype=np.float32) if isinstance(f0_in, str) else f0_in
-        return self.write_streams(self.analysis_device(wav, f0, f0_min, f0_max), ff0, fspec, faper, fvuv)
+        with self.f0_refine_as(kwargs.get('f0_refine')):
+            CMP = self.analysis_device(wav, f0, f0_min, f0_max)
+        return self.write_streams(CMP, ff0, fspec, faper, fvuv)
 
     def write_streams(self, CMP, ff0, fspec, faper, fvuv):
         """The parameters [T, featuressizeraw()] of analysis_device -> the four headerless float32 files of analysisf_device: ff0
