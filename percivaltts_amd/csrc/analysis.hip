@@ -24,12 +24,11 @@
 // 1.25 M complex fp64 = 40 KiB at L = 4096, 80 KiB at 8192.  Every sum runs in a fixed order inside one lane (bins ascending,
 // frames ascending); nothing here uses an atomic and a result does not depend on the grid.
 #include "common.h"
-#include "realfft.h"
+#include "frame.h"
 
 namespace ptts {
 
 constexpr int AN_THREADS = 256;
-constexpr int AN_MIN_DFTLEN = 256, AN_MAX_DFTLEN = 8192;
 constexpr int AN_MAX_HCAP = 8192;                       // harmonics a frame may have: below K at the largest dftlen
 constexpr int AN_MAX_NB = 1024;
 constexpr int CT_ROWS = 6;                              // rows of the compress table: klo, khi, sum_k W, e_b, 1 / m_b, c'_b
@@ -37,18 +36,8 @@ constexpr int CT_FRAMES = AN_THREADS / 64;              // frames of one ptts_fw
 constexpr double AN_NOISY_BELOW = 0.75483960198900735;  // exp(-0.75^2 / 2)
 constexpr double AN_FLT_MIN = 1.17549435082228751e-38;
 
-__device__ __forceinline__ double an_rnd(double x) { return floor(x + 0.5); }
-
 // H = floor((fs/2 - f0/2) / f0) as a double; f0 > 0
 __device__ __forceinline__ double harmonics_of(double f0, double fs) { return floor((0.5 * fs - 0.5 * f0) / f0); }
-
-// bin k (0 .. M) of the unpacked spectrum
-__device__ __forceinline__ double2 spectrum_bin(const double2* a, int k, int logM) {
-    const int M = 1 << logM;
-    if (k <= 0) return make_double2(a[0].x, 0.0);
-    if (k >= M) return make_double2(a[0].y, 0.0);
-    return a[bitrev(k, logM)];
-}
 
 // One workgroup per frame.  dynamic LDS: (M + M/4) double2 + (Hcap + 2) doubles.
 __global__ __launch_bounds__(AN_THREADS) void frame_harmonics_kernel(const float* __restrict__ wav, const long long N,
@@ -67,37 +56,19 @@ __global__ __launch_bounds__(AN_THREADS) void frame_harmonics_kernel(const float
     const double hwd = 1.5 * fs / f0, Hd = harmonics_of(f0, fs);
     if (!(hwd < (double)L) || 2 * (int)hwd + 1 > L || !(Hd >= 1.0) || !(Hd <= (double)(Hcap + 1))) return;
     const int hw = (int)hwd, H = (int)Hd;
-    const long long c = (long long)an_rnd((double)i * shift * fs);
+    const long long c = (long long)rnd((double)i * shift * fs);
 
-    for (int j = tid; j < Mq; j += nthr) {
-        double s, cs;
-        sincospi(2.0 * (double)j / (double)M, &s, &cs);
-        wq[j] = make_double2(cs, -s);
-    }
-    // position p of the buffer holds sample c + j with j = p (p <= hw) or j = p - L (p >= L - hw); 2 hw + 1 <= L keeps them apart
+    fill_twiddles(wq, M);
     const double wnorm = 1.0 / (0.84 * (double)hw);
-    for (int n = tid; n < M; n += nthr) {
-        double v[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int p = 2 * n + q;
-            v[q] = 0.0;
-            if (p <= hw || p >= L - hw) {
-                const int j = p <= hw ? p : p - L;
-                const long long s = c + j;
-                if (s >= 0 && s < N) {
-                    const double r = (double)(j + hw) / (double)hw;
-                    v[q] = (double)wav[s] * ((0.42 - 0.5 * cospi(r) + 0.08 * cospi(2.0 * r)) * wnorm);
-                }
-            }
-        }
-        a[n] = make_double2(v[0], v[1]);
-    }
+    frame_fill(a, wav, N, c, hw, M, [&](int j) {        // blackman(2 hw + 1) / (0.84 hw)
+        const double r = (double)(j + hw) / (double)hw;
+        return (0.42 - 0.5 * cospi(r) + 0.08 * cospi(2.0 * r)) * wnorm;
+    });
     fft_forward(a, wq, logM);
     unpack_real(a, logM);
 
     for (int h = 1 + tid; h <= H; h += nthr) {
-        long long lo = (long long)an_rnd(((double)h - 0.5) * f0 * (double)L / fs), hi = (long long)an_rnd(((double)h + 0.5) * f0 * (double)L / fs);
+        long long lo = (long long)rnd(((double)h - 0.5) * f0 * (double)L / fs), hi = (long long)rnd(((double)h + 0.5) * f0 * (double)L / fs);
         lo = lo < 0 ? 0 : lo;
         hi = hi > K ? K : hi;
         double p2 = 0.0;
@@ -112,13 +83,13 @@ __global__ __launch_bounds__(AN_THREADS) void frame_harmonics_kernel(const float
     __syncthreads();
 
     float* urow = u + (size_t)i * Hcap * 2;
-    const long long k1l = (long long)an_rnd(1.0 * f0 * (double)L / fs);
+    const long long k1l = (long long)rnd(1.0 * f0 * (double)L / fs);
     const int k1 = (int)(k1l > M ? M : k1l);
     for (int j = tid; j < Hcap; j += nthr) {
         const int h = j + 1;
         double2 o = make_double2(0.0, 0.0);
         if (h <= H - 1) {
-            long long ka = (long long)an_rnd((double)h * f0 * (double)L / fs), kb = (long long)an_rnd((double)(h + 1) * f0 * (double)L / fs);
+            long long ka = (long long)rnd((double)h * f0 * (double)L / fs), kb = (long long)rnd((double)(h + 1) * f0 * (double)L / fs);
             ka = ka > M ? M : ka;
             kb = kb > M ? M : kb;
             const double2 z = cmul(cmul(spectrum_bin(a, (int)kb, logM), cconj(spectrum_bin(a, (int)ka, logM))),
@@ -146,9 +117,9 @@ __global__ __launch_bounds__(AN_THREADS) void frame_harmonics_kernel(const float
 
 // W[k,b] from the band / fraction rows of the fwbnd table (band indices clamped, whatever the table holds)
 __device__ __forceinline__ double hat_weight(const double* __restrict__ fw, int Kp, int nb, int k, int b) {
-    int bk = (int)fw[k];
-    bk = bk < 0 ? 0 : (bk > nb - 2 ? nb - 2 : bk);
-    const double fr = fw[(size_t)Kp + k];
+    int bk;
+    double fr;
+    band_of(fw, Kp, nb, k, bk, fr);
     return bk == b ? 1.0 - fr : (bk == b - 1 ? fr : 0.0);
 }
 
@@ -170,7 +141,7 @@ __global__ __launch_bounds__(AN_THREADS) void phase_coherence_kernel(const float
     const double f0 = (double)f0v[i];
     int H = 0, J = 2;
     if (f0 > 0.0 && f0 < fs) {
-        const double Hd = harmonics_of(f0, fs), Jd = an_rnd(1.0 / (f0 * shift));
+        const double Hd = harmonics_of(f0, fs), Jd = rnd(1.0 / (f0 * shift));
         H = Hd < 0.0 ? 0 : (Hd > (double)(Hcap + 1) ? Hcap + 1 : (int)Hd);
         J = Jd > (double)T ? T : (Jd < 2.0 ? 2 : (int)Jd);
     }
@@ -226,9 +197,7 @@ __global__ __launch_bounds__(AN_THREADS) void compress_table_kernel(double* __re
             int lo = 0, hi = K;
             while (lo < hi) {
                 const int mid = (lo + hi) >> 1;
-                int bk = (int)fw[mid];
-                bk = bk < 0 ? 0 : (bk > nb - 2 ? nb - 2 : bk);
-                if (bk >= want) hi = mid; else lo = mid + 1;
+                if (lower_band(fw, nb, mid) >= want) hi = mid; else lo = mid + 1;
             }
             bound[q] = lo;
         }
@@ -312,12 +281,6 @@ __global__ __launch_bounds__(AN_THREADS) void fwbnd_compress_kernel(const float*
         for (int b = lane; b < nb; b += 64) out[(size_t)t * nb + b] = (float)y[b];
 }
 
-static int an_log2(int dftlen) {
-    for (int l = 8; l <= 13; ++l)
-        if (dftlen == (1 << l)) return l;
-    return -1;
-}
-
 static int an_padded_bins(int dftlen) { return (dftlen / 2 + 1 + 3) / 4 * 4; }
 static int an_padded_bands(int nb) { return (nb + 3) / 4 * 4; }
 static bool an_dftlen_even(int dftlen) { return dftlen >= 8 && dftlen % 2 == 0 && dftlen <= (1 << 20); }
@@ -341,24 +304,18 @@ extern "C" int ptts_frame_harmonics(const float* wav, long long N, const float* 
                                     double fs, int dftlen, int log_out, void* stream) {
     PTTS_REQUIRE(T >= 0 && N >= 0, "frame_harmonics: T=%d N=%lld", T, N);
     PTTS_REQUIRE(Hcap >= 1 && Hcap <= AN_MAX_HCAP, "frame_harmonics: Hcap=%d outside [1, %d]", Hcap, AN_MAX_HCAP);
-    const int logL = an_log2(dftlen);
-    PTTS_REQUIRE(logL > 0, "frame_harmonics: dftlen=%d is not a power of two in [%d, %d]", dftlen, AN_MIN_DFTLEN, AN_MAX_DFTLEN);
+    const int logL = frame_log2(dftlen);
+    PTTS_REQUIRE(logL > 0, "frame_harmonics: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN, FRAME_MAX_DFTLEN);
     PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "frame_harmonics: fs=%g", fs);
     PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "frame_harmonics: shift=%g", shift);
     if (T == 0) return PTTS_OK;
     PTTS_REQUIRE(f0 && spec && u && (wav || N == 0), "frame_harmonics: null tensor");
     const int M = dftlen / 2;
     const int lds = (M + M / 4) * (int)sizeof(double2) + (Hcap + 2) * (int)sizeof(double);
-    static int lds_reserved = 0;
-    if (lds > lds_reserved) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(frame_harmonics_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { set_error("frame_harmonics: cannot reserve %d B of LDS: %s", lds, hipGetErrorString(e)); return PTTS_ELAUNCH; }
-        lds_reserved = lds;
-    }
-    const int threads = M / 4 < 64 ? 64 : (M / 4 > AN_THREADS ? AN_THREADS : M / 4);
-    hipLaunchKernelGGL(frame_harmonics_kernel, dim3(T), dim3(threads), (size_t)lds, (hipStream_t)stream, wav, N, f0, spec, u, Hcap,
-                       logL - 1, shift, fs, log_out != 0);
+    const int rc = reserve_lds<frame_harmonics_kernel>("frame_harmonics", lds);
+    if (rc != PTTS_OK) return rc;
+    hipLaunchKernelGGL(frame_harmonics_kernel, dim3(T), dim3(frame_threads(M, AN_THREADS)), (size_t)lds, (hipStream_t)stream, wav, N, f0,
+                       spec, u, Hcap, logL - 1, shift, fs, log_out != 0);
     return check_launch("frame_harmonics");
 }
 
@@ -368,7 +325,8 @@ extern "C" int ptts_phase_coherence(const float* u, const float* f0, float* R, f
     PTTS_REQUIRE(T >= 0, "phase_coherence: T=%d", T);
     PTTS_REQUIRE(Hcap >= 1 && Hcap <= AN_MAX_HCAP, "phase_coherence: Hcap=%d outside [1, %d]", Hcap, AN_MAX_HCAP);
     PTTS_REQUIRE(nb >= 2 && nb <= AN_MAX_NB, "phase_coherence: nb=%d outside [2, %d]", nb, AN_MAX_NB);
-    PTTS_REQUIRE(an_log2(dftlen) > 0, "phase_coherence: dftlen=%d is not a power of two in [%d, %d]", dftlen, AN_MIN_DFTLEN, AN_MAX_DFTLEN);
+    PTTS_REQUIRE(frame_log2(dftlen) > 0, "phase_coherence: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN,
+                 FRAME_MAX_DFTLEN);
     PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "phase_coherence: fs=%g", fs);
     PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "phase_coherence: shift=%g", shift);
     if (T == 0) return PTTS_OK;

@@ -40,27 +40,13 @@
 #include <climits>
 #include <cmath>
 #include "common.h"
-#include "realfft.h"
+#include "frame.h"
 
 namespace ptts {
 
 constexpr int F0_THREADS = 256;
-constexpr int F0_MIN_DFTLEN = 256, F0_MAX_DFTLEN = 8192;
 constexpr int F0_MIN_NCAND = 2, F0_MAX_NCAND = 16;
 constexpr int F0_MAX_FRAMES = 32768;                    // of ptts_f0_viterbi with one back-pointer word a frame (ncand <= 8): 128 KiB of LDS
-
-__device__ __forceinline__ double f0_rnd(double x) { return floor(x + 0.5); }
-
-__device__ __forceinline__ double f0_block_sum(double v, double* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    const double s = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    double tot = red[0];
-    for (int w = 1; w < nwaves; ++w) tot += red[w];
-    return tot;
-}
 
 __device__ __forceinline__ double f0_block_max(double v, double* red) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
@@ -143,13 +129,9 @@ __global__ __launch_bounds__(F0_THREADS) void f0_candidates_kernel(const float* 
     int* redk = reinterpret_cast<int*>(red + 4);
     const int i = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
 
-    for (int j = tid; j < Mq; j += nthr) {
-        double s, c;
-        sincospi(2.0 * (double)j / (double)M, &s, &c);
-        wq[j] = make_double2(c, -s);
-    }
+    fill_twiddles(wq, M);
     // position p of the buffer holds sample s0 + p; [j0, j1) are the positions of the window that lie inside the waveform
-    const long long s0 = (long long)f0_rnd((double)i * shift * fs) - hw;
+    const long long s0 = (long long)rnd((double)i * shift * fs) - hw;
     long long j0 = s0 < 0 ? -s0 : 0, j1 = N - s0;
     j0 = j0 > W ? W : j0;
     j1 = j1 > W ? W : j1;
@@ -168,7 +150,7 @@ __global__ __launch_bounds__(F0_THREADS) void f0_candidates_kernel(const float* 
         }
         a[n] = make_double2(v[0], v[1]);
     }
-    sum = f0_block_sum(sum, red);
+    sum = block_sum(sum, red);
     const double mean = j1 > j0 ? sum / (double)(j1 - j0) : 0.0;
     double pk = 0.0;
     for (int n = tid; n < M; n += nthr) {
@@ -390,7 +372,7 @@ __global__ __launch_bounds__(64) void f0_viterbi_kernel(const float* __restrict_
 constexpr int F0_REFINE_MAX_WINDOW = 16384;             // samples of the window at f0_min
 constexpr int F0_REFINE_H1 = 2, F0_REFINE_H2 = 6;       // harmonics of the two passes
 
-// f0_block_sum over NV values at once, in the same fixed order: the wave's butterfly, then the waves in turn.  red: [nwaves * NV]
+// block_sum of frame.h over NV values at once, in the same fixed order: the wave's butterfly, then the waves in turn.  red: [nwaves * NV]
 template <int NV> __device__ __forceinline__ void f0_block_sum_n(double* v, double* red) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
 #pragma unroll
@@ -479,7 +461,7 @@ __global__ __launch_bounds__(F0_THREADS) void f0_refine_kernel(const float* __re
         res = 0.f;
         st = 0;
     } else if (!(f < f0_min || f > f0_max)) {
-        const double hwd = f0_rnd(1.5 * fs / f), cd = f0_rnd((double)i * shift * fs);
+        const double hwd = rnd(1.5 * fs / f), cd = rnd((double)i * shift * fs);
         if (!(cd - hwd < 0.0 || cd + hwd >= (double)N)) {       // the whole window lies inside the waveform
             const int hw = (int)hwd;
             const float* x = wav + (long long)cd;
@@ -498,12 +480,6 @@ __global__ __launch_bounds__(F0_THREADS) void f0_refine_kernel(const float* __re
     }
 }
 
-static int f0_log2(int dftlen) {
-    for (int l = 8; l <= 13; ++l)
-        if (dftlen == (1 << l)) return l;
-    return -1;
-}
-
 }  // namespace ptts
 
 using namespace ptts;
@@ -514,8 +490,8 @@ extern "C" int ptts_f0_candidates(const float* wav, long long N, const double* r
     PTTS_REQUIRE(T >= 0 && N >= 0, "f0_candidates: T=%d N=%lld", T, N);
     PTTS_REQUIRE(ncand >= F0_MIN_NCAND && ncand <= F0_MAX_NCAND, "f0_candidates: ncand=%d outside [%d, %d]", ncand, F0_MIN_NCAND,
                  F0_MAX_NCAND);
-    const int logL = f0_log2(dftlen);
-    PTTS_REQUIRE(logL > 0, "f0_candidates: dftlen=%d is not a power of two in [%d, %d]", dftlen, F0_MIN_DFTLEN, F0_MAX_DFTLEN);
+    const int logL = frame_log2(dftlen);
+    PTTS_REQUIRE(logL > 0, "f0_candidates: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN, FRAME_MAX_DFTLEN);
     PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "f0_candidates: fs=%g", fs);
     PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "f0_candidates: shift=%g", shift);
     PTTS_REQUIRE(f0_min > 0.0 && f0_min <= f0_max && f0_max <= 0.5 * fs, "f0_candidates: f0_min=%g f0_max=%g (positive, ordered, at most fs/2)",
@@ -536,15 +512,11 @@ extern "C" int ptts_f0_candidates(const float* wav, long long N, const double* r
                  "f0_candidates: the window table needs %zu bytes, got %zu", (size_t)(lmax + 2) * sizeof(double), rw_bytes);
     const int M = dftlen / 2;
     const int lds = (M + M / 4) * (int)sizeof(double2) + (lmax + 2 + 4) * (int)sizeof(double) + 4 * (int)sizeof(int);
-    static int lds_reserved = 0;
-    if (lds > lds_reserved) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(f0_candidates_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { set_error("f0_candidates: cannot reserve %d B of LDS: %s", lds, hipGetErrorString(e)); return PTTS_ELAUNCH; }
-        lds_reserved = lds;
-    }
-    const int threads = M / 4 < 64 ? 64 : (M / 4 > F0_THREADS ? F0_THREADS : M / 4);
-    hipLaunchKernelGGL(f0_candidates_kernel, dim3(T), dim3(threads), (size_t)lds, (hipStream_t)stream, wav, N, rw, freq, strength, n, lag, r,
-                       logL - 1, hw, lmin, lmax, ncand, shift, fs, f0_min, f0_max, gpeak, voicing_threshold, silence_threshold, octave_cost);
+    const int rc = reserve_lds<f0_candidates_kernel>("f0_candidates", lds);
+    if (rc != PTTS_OK) return rc;
+    hipLaunchKernelGGL(f0_candidates_kernel, dim3(T), dim3(frame_threads(M, F0_THREADS)), (size_t)lds, (hipStream_t)stream, wav, N, rw, freq,
+                       strength, n, lag, r, logL - 1, hw, lmin, lmax, ncand, shift, fs, f0_min, f0_max, gpeak, voicing_threshold,
+                       silence_threshold, octave_cost);
     return check_launch("f0_candidates");
 }
 
@@ -567,12 +539,8 @@ extern "C" int ptts_f0_viterbi(const float* freq, const float* strength, const i
     while ((1 << log_group) < ncand) ++log_group;
     const int words = ncand <= 8 ? 1 : 2;
     const int lds = T * words * (int)sizeof(unsigned);
-    static int lds_reserved = 0;
-    if (lds > lds_reserved) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(f0_viterbi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { set_error("f0_viterbi: cannot reserve %d B of LDS: %s", lds, hipGetErrorString(e)); return PTTS_ELAUNCH; }
-        lds_reserved = lds;
-    }
+    const int rc = reserve_lds<f0_viterbi_kernel>("f0_viterbi", lds);
+    if (rc != PTTS_OK) return rc;
     hipLaunchKernelGGL(f0_viterbi_kernel, dim3(1), dim3(64), (size_t)lds, (hipStream_t)stream, freq, strength, n, f0, path, T, ncand, log_group,
                        words, 0.01 / shift, octave_jump_cost, voiced_unvoiced_cost);
     return check_launch("f0_viterbi");

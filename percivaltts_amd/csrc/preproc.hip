@@ -28,6 +28,7 @@
 // No atomics, no polling, nothing between workgroups; an utterance's result does not depend on what else is in the launch.
 #include <cmath>
 #include "common.h"
+#include "frame.h"      // reserve_lds
 
 namespace ptts {
 
@@ -282,12 +283,8 @@ extern "C" int ptts_highpass_zerophase(const float* x, float* y, const long long
                  "highpass_zerophase: the workspace needs %zu bytes, got %zu", need, workspace_bytes);
     HpCoef c;
     hp_coefficients(fs, fc, c);
-    static bool lds_reserved = false;
-    if (!lds_reserved) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(highpass_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, HP_LDS_BYTES);
-        if (e != hipSuccess) { set_error("highpass_zerophase: cannot reserve %d B of LDS: %s", HP_LDS_BYTES, hipGetErrorString(e)); return PTTS_ELAUNCH; }
-        lds_reserved = true;
-    }
+    const int rc = reserve_lds<highpass_kernel>("highpass_zerophase", HP_LDS_BYTES);
+    if (rc != PTTS_OK) return rc;
     hipLaunchKernelGGL(highpass_kernel, dim3(n_utts), dim3(HP_THREADS), (size_t)HP_LDS_BYTES, (hipStream_t)stream, x, y, off,
                        static_cast<double*>(workspace), total, padlen, c);
     return check_launch("highpass_zerophase");

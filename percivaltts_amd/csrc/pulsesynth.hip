@@ -64,7 +64,6 @@ __global__ __launch_bounds__(PS_THREADS) void pulse_segments_kernel(const float*
     const double tc = s0 / c0;
     minimum_phase(bufe, wq, logM, [&](int k) { return log_amplitude(srow, k, L, tc); });
     const double gain = noise_spectrum(bufn, wq, logM, red);
-    const double inv_m = 1.0 / (double)M;
 
     // S = E ((1 - m) D + m N), packed for the inverse transform in the same pass
     for (int k = tid; k <= (M >> 1); k += nthr) {
@@ -89,11 +88,7 @@ __global__ __launch_bounds__(PS_THREADS) void pulse_segments_kernel(const float*
         }
     }
     fft_inverse(bufn, wq, logM);
-    float* out = seg + (size_t)n * W;
-    for (int p = tid; p < winlen; p += nthr) {
-        const double2 z = bufn[p >> 1];
-        out[p] = (float)(((p & 1) ? z.y : z.x) * inv_m);
-    }
+    write_segment(bufn, M, seg, n, W, winlen);
 }
 
 // One lane per sample: the pulses whose window covers it lie between two binary searches over the ascending starts.
@@ -135,10 +130,11 @@ __global__ __launch_bounds__(256) void noise_mask_kernel(const float* __restrict
     __syncthreads();
     const int kcut = (int)(2.0 * (double)f0[t] * (double)L / fs);
     for (int k = tid; k < K; k += nthr) {
-        int b = (int)tab[k];
-        b = b < 0 ? 0 : (b > nb - 2 ? nb - 2 : b);      // whatever the table holds
+        int b;
+        double fr;
+        band_of(tab, Kp, nb, k, b, fr);
         const double lo = (double)sb[b], hi = (double)sb[b + 1];
-        const double v = fma(tab[(size_t)Kp + k], hi - lo, lo);
+        const double v = fma(fr, hi - lo, lo);
         x[k] = (k >= kcut && v > 0.5) ? 1.f : 0.f;
     }
     __syncthreads();
@@ -165,7 +161,8 @@ extern "C" int ptts_noise_mask(const float* nmb, const float* f0, float* out, in
     PTTS_REQUIRE(T >= 0, "noise_mask: T=%d", T);
     PTTS_REQUIRE(nb >= 2 && nb <= NM_MAX_NB, "noise_mask: nb=%d outside [2, %d]", nb, NM_MAX_NB);
     PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "noise_mask: fs=%g", fs);
-    PTTS_REQUIRE(ps_log2(dftlen) > 0, "noise_mask: dftlen=%d is not a power of two in [%d, %d]", dftlen, PS_MIN_DFTLEN, PS_MAX_DFTLEN);
+    PTTS_REQUIRE(frame_log2(dftlen) > 0, "noise_mask: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN,
+                 FRAME_MAX_DFTLEN);
     if (T == 0) return PTTS_OK;
     PTTS_REQUIRE(nmb && f0 && out && table, "noise_mask: null tensor");
     const int K = dftlen / 2 + 1, Kp = (K + 3) / 4 * 4;
@@ -190,27 +187,7 @@ extern "C" int ptts_noise_mask(const float* nmb, const float* f0, float* out, in
 
 extern "C" int ptts_pulse_segments(const float* spec, const float* mask, const float* noise, const int* itab, const double* dtab,
                                    int P, int T, int dftlen, double fs, long long wavlen, float* seg, int W, void* stream) {
-    PTTS_REQUIRE(P >= 0 && T >= 0 && wavlen >= 0, "pulse_segments: P=%d T=%d wavlen=%lld", P, T, wavlen);
-    const int logL = ps_log2(dftlen);
-    PTTS_REQUIRE(logL > 0, "pulse_segments: dftlen=%d is not a power of two in [%d, %d]", dftlen, PS_MIN_DFTLEN, PS_MAX_DFTLEN);
-    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "pulse_segments: fs=%g", fs);
-    PTTS_REQUIRE(W >= 1 && W <= dftlen, "pulse_segments: W=%d outside [1, dftlen]", W);
-    if (P == 0 || T == 0) return PTTS_OK;
-    PTTS_REQUIRE(spec && mask && itab && dtab && seg && (noise || wavlen == 0), "pulse_segments: null tensor");
-    const int M = dftlen / 2;
-    const int lds = (2 * M + M / 4) * (int)sizeof(double2);
-    static int lds_reserved = 0;
-    if (lds > lds_reserved) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pulse_segments_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { set_error("pulse_segments: cannot reserve %d B of LDS: %s", lds, hipGetErrorString(e)); return PTTS_ELAUNCH; }
-        lds_reserved = lds;
-    }
-    const int threads = M / 4 < 64 ? 64 : (M / 4 > PS_THREADS ? PS_THREADS : M / 4);
-    const int taper = (int)floor(0.001 * fs + 0.5);
-    hipLaunchKernelGGL(pulse_segments_kernel, dim3(P), dim3(threads), (size_t)lds, (hipStream_t)stream, spec, mask, noise, itab, dtab,
-                       P, T, logL - 1, fs, taper, wavlen, seg, W);
-    return check_launch("pulse_segments");
+    return launch_segments<pulse_segments_kernel>("pulse_segments", spec, mask, noise, itab, dtab, P, T, dftlen, fs, wavlen, seg, W, stream);
 }
 
 extern "C" int ptts_pulse_overlap_add(const float* seg, const int* itab, int P, int W, float* wav, long long wavlen, void* stream) {

@@ -1,4 +1,4 @@
-// The in-LDS radix-2 real transform that pulsesynth.hip and analysis.hip share.
+// The in-LDS radix-2 real transform that the kernels of the offline vocoder chain share (frame.h holds what they share around it).
 //
 // A real transform of length L is a complex transform of length M = L/2 on the packed sequence z[n] = x[2n] + i x[2n+1] plus one
 // pass over the bin pairs (k, M - k); the complex transform is radix-2 in LDS, decimation in frequency forwards (natural in,
@@ -42,6 +42,25 @@ __device__ void fft_forward(double2* a, const double2* wq, int logM) {
             const double2 u = a[i], v = a[i + half];
             a[i] = cadd(u, v);
             a[i + half] = cmul(csub(u, v), twiddle(wq, j << (logM - 1 - s), Mq));
+        }
+        __syncthreads();
+    }
+}
+
+// fft_forward on two buffers at once: the same butterflies, half the barriers
+__device__ void fft_forward2(double2* a, double2* b, const double2* wq, int logM) {
+    const int M = 1 << logM, Mq = M >> 2;
+    __syncthreads();
+    for (int s = logM - 1; s >= 0; --s) {
+        const int half = 1 << s;
+        for (int t = threadIdx.x; t < (M >> 1); t += blockDim.x) {
+            const int j = t & (half - 1), i = ((t >> s) << (s + 1)) | j;
+            const double2 w = twiddle(wq, j << (logM - 1 - s), Mq);
+            const double2 ua = a[i], va = a[i + half], ub = b[i], vb = b[i + half];
+            a[i] = cadd(ua, va);
+            a[i + half] = cmul(csub(ua, va), w);
+            b[i] = cadd(ub, vb);
+            b[i + half] = cmul(csub(ub, vb), w);
         }
         __syncthreads();
     }

@@ -1,27 +1,15 @@
 // What the two waveform synthesisers share (pulsesynth.hip for the PML parameters, worldsynth.hip for the WORLD parameters),
-// on the in-LDS transforms of realfft.h: the quarter circle of twiddles, the minimum-phase chain, the pulse's stretch of the
-// noise and its normalisation, the high-pass gain.  Notation as there: L = dftlen, M = L/2 complex points, K = M + 1 bins, a
-// spectrum at bit-reversed addresses with X_0 and X_M in slot 0.  fp64 throughout; every routine but hp_gain is called by the
-// whole workgroup.
+// on the in-LDS transforms of realfft.h and the scaffold of frame.h: the minimum-phase chain, the pulse's stretch of the noise and
+// its normalisation, the high-pass gain, the segment's write-out and the launch of a segments kernel.  Notation as there:
+// L = dftlen, M = L/2 complex points, K = M + 1 bins, a spectrum at bit-reversed addresses with X_0 and X_M in slot 0.  fp64
+// throughout; every device routine but hp_gain is called by the whole workgroup.
 #pragma once
 #include "common.h"
-#include "realfft.h"
+#include "frame.h"
 
 namespace ptts {
 
 constexpr int PS_THREADS = 256;
-constexpr int PS_MIN_DFTLEN = 256, PS_MAX_DFTLEN = 8192;
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    const double s = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    double tot = red[0];
-    for (int w = 1; w < nwaves; ++w) tot += red[w];
-    return tot;
-}
 
 // hp_k = (1 + (tc / tan(pi k / L))^8)^(-1/2), hp_0 = 0; tc = tan(pi fcut / fs)
 __device__ __forceinline__ double hp_gain(int k, int L, double tc) {
@@ -33,15 +21,6 @@ __device__ __forceinline__ double hp_gain(int k, int L, double tc) {
         hp = 1.0 / sqrt(1.0 + r4 * r4);
     }
     return hp;
-}
-
-// wq[j] = exp(-2 pi i j / M), 0 <= j < M/4
-__device__ __forceinline__ void fill_twiddles(double2* wq, int M) {
-    for (int j = threadIdx.x; j < (M >> 2); j += blockDim.x) {
-        double s, c;
-        sincospi(2.0 * (double)j / (double)M, &s, &c);
-        wq[j] = make_double2(c, -s);
-    }
 }
 
 // The noise segment, packed: position p of the frame holds g[start + p] for lb <= start + p < rb, tapered over `taper` samples at
@@ -129,10 +108,37 @@ __device__ __forceinline__ void minimum_phase(double2* bufe, const double2* wq, 
     }
 }
 
-static int ps_log2(int dftlen) {
-    for (int l = 8; l <= 13; ++l)
-        if (dftlen == (1 << l)) return l;
-    return -1;
+// seg[n, 0 .. winlen) out of buf, M times the packed segment as fft_inverse leaves it
+__device__ __forceinline__ void write_segment(const double2* buf, int M, float* seg, int n, int W, int winlen) {
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const double inv_m = 1.0 / (double)M;
+    float* out = seg + (size_t)n * W;
+    for (int p = tid; p < winlen; p += nthr) {
+        const double2 z = buf[p >> 1];
+        out[p] = (float)(((p & 1) ? z.y : z.x) * inv_m);
+    }
+}
+
+// The entry point of a segments kernel: one workgroup per pulse with (2 M + M/4) double2 of dynamic LDS.  rows: the [T,K] rows
+// beside the envelope, the noise mask or the aperiodicity.
+template <auto Kernel>
+int launch_segments(const char* name, const float* spec, const float* rows, const float* noise, const int* itab, const double* dtab,
+                    int P, int T, int dftlen, double fs, long long wavlen, float* seg, int W, void* stream) {
+    PTTS_REQUIRE(P >= 0 && T >= 0 && wavlen >= 0, "%s: P=%d T=%d wavlen=%lld", name, P, T, wavlen);
+    const int logL = frame_log2(dftlen);
+    PTTS_REQUIRE(logL > 0, "%s: dftlen=%d is not a power of two in [%d, %d]", name, dftlen, FRAME_MIN_DFTLEN, FRAME_MAX_DFTLEN);
+    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "%s: fs=%g", name, fs);
+    PTTS_REQUIRE(W >= 1 && W <= dftlen, "%s: W=%d outside [1, dftlen]", name, W);
+    if (P == 0 || T == 0) return PTTS_OK;
+    PTTS_REQUIRE(spec && rows && itab && dtab && seg && (noise || wavlen == 0), "%s: null tensor", name);
+    const int M = dftlen / 2;
+    const int lds = (2 * M + M / 4) * (int)sizeof(double2);
+    const int rc = reserve_lds<Kernel>(name, lds);
+    if (rc != PTTS_OK) return rc;
+    const int taper = (int)floor(0.001 * fs + 0.5);
+    hipLaunchKernelGGL(Kernel, dim3(P), dim3(frame_threads(M, PS_THREADS)), (size_t)lds, (hipStream_t)stream, spec, rows, noise, itab,
+                       dtab, P, T, logL - 1, fs, taper, wavlen, seg, W);
+    return check_launch(name);
 }
 
 }  // namespace ptts

@@ -34,21 +34,18 @@
 // inside one lane (bins ascending; a band's sum is cut into G stretches of its bins, G a function of nb and L, each summed by one
 // lane, and one lane adds the G partial sums in order); nothing here uses an atomic and a result does not depend on the grid.
 #include "common.h"
-#include "realfft.h"
+#include "frame.h"
 
 namespace ptts {
 
 constexpr int WA_THREADS = 256;
-constexpr int WA_MIN_DFTLEN = 256, WA_MAX_DFTLEN = 8192;
 constexpr int WA_MAX_NB = 1024;
 constexpr double WA_Q1 = -0.15;                         // the lifter's q1
 constexpr double WA_PI = 3.14159265358979323846;
 
-__device__ __forceinline__ double wa_rnd(double x) { return floor(x + 0.5); }
-
 __device__ __forceinline__ double wa_mag2(double2 z) { return z.x * z.x + z.y * z.y; }
 
-// |X_k|^2 of the unpacked spectrum, 0 <= k <= M
+// |X_k|^2 of the unpacked spectrum, 0 <= k <= M.  Not wa_mag2(spectrum_bin()): bins 0 and M are x * x, without a + 0 * 0 behind it.
 __device__ __forceinline__ double wa_power_bin(const double2* a, int k, int logM) {
     const int M = 1 << logM;
     if (k <= 0) return a[0].x * a[0].x;
@@ -56,33 +53,10 @@ __device__ __forceinline__ double wa_power_bin(const double2* a, int k, int logM
     return wa_mag2(a[bitrev(k, logM)]);
 }
 
-__device__ __forceinline__ void wa_fill_twiddles(double2* wq, int M) {
-    for (int j = threadIdx.x; j < (M >> 2); j += blockDim.x) {
-        double s, c;
-        sincospi(2.0 * (double)j / (double)M, &s, &c);
-        wq[j] = make_double2(c, -s);
-    }
-}
-
-// The windowed frame around sample c, packed: position p of the frame holds sample c + j with j = p (p <= hw) or j = p - L
-// (p >= L - hw); 2 hw + 1 <= L keeps them apart.
-__device__ __forceinline__ void wa_frame_fill(double2* a, const float* __restrict__ wav, long long N, long long c, int hw, int M) {
-    const int L = M << 1;
+// The window of frame_fill for half width hw: w_j = (0.5 + 0.5 cos(pi j / (hw + 1))) / sqrt(0.75 (hw + 1))
+__device__ __forceinline__ auto wa_hann(int hw) {
     const double wnorm = 1.0 / sqrt(0.75 * (double)(hw + 1));
-    for (int n = threadIdx.x; n < M; n += blockDim.x) {
-        double v[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int p = 2 * n + q;
-            v[q] = 0.0;
-            if (p <= hw || p >= L - hw) {
-                const int j = p <= hw ? p : p - L;
-                const long long s = c + j;
-                if (s >= 0 && s < N) v[q] = (double)wav[s] * ((0.5 + 0.5 * cospi((double)j / (double)(hw + 1))) * wnorm);
-            }
-        }
-        a[n] = make_double2(v[0], v[1]);
-    }
+    return [=](int j) { return (0.5 + 0.5 * cospi((double)j / (double)(hw + 1))) * wnorm; };
 }
 
 // the window of a frame at rate r: false for a frame the host checks would have refused
@@ -136,10 +110,10 @@ __global__ __launch_bounds__(WA_THREADS) void world_envelope_kernel(const float*
     int hw;
     // a frame the host checks would have refused: nothing of it is read or written
     if (!wa_window(r, fs, L, hw)) return;
-    const long long c = (long long)wa_rnd((double)i * shift * fs);
+    const long long c = (long long)rnd((double)i * shift * fs);
 
-    wa_fill_twiddles(wq, M);
-    wa_frame_fill(a, wav, N, c, hw, M);
+    fill_twiddles(wq, M);
+    frame_fill(a, wav, N, c, hw, M, wa_hann(hw));
     fft_forward(a, wq, logM);
     unpack_real(a, logM);
 
@@ -194,31 +168,6 @@ __global__ __launch_bounds__(WA_THREADS) void world_envelope_kernel(const float*
     }
 }
 
-// the lower band of bin k as the fwbnd table has it (band indices clamped, whatever the table holds)
-__device__ __forceinline__ int wa_lower_band(const double* __restrict__ fw, int nb, int k) {
-    const int bk = (int)fw[k];
-    return bk < 0 ? 0 : (bk > nb - 2 ? nb - 2 : bk);
-}
-
-// fft_forward of realfft.h on two buffers at once: the same butterflies, half the barriers
-__device__ void wa_fft_forward2(double2* a, double2* b, const double2* wq, int logM) {
-    const int M = 1 << logM, Mq = M >> 2;
-    __syncthreads();
-    for (int s = logM - 1; s >= 0; --s) {
-        const int half = 1 << s;
-        for (int t = threadIdx.x; t < (M >> 1); t += blockDim.x) {
-            const int j = t & (half - 1), i = ((t >> s) << (s + 1)) | j;
-            const double2 w = twiddle(wq, j << (logM - 1 - s), Mq);
-            const double2 ua = a[i], va = a[i + half], ub = b[i], vb = b[i + half];
-            a[i] = cadd(ua, va);
-            a[i + half] = cmul(csub(ua, va), w);
-            b[i] = cadd(ub, vb);
-            b[i + half] = cmul(csub(ub, vb), w);
-        }
-        __syncthreads();
-    }
-}
-
 // One workgroup per frame.  dynamic LDS: (2 M + M/4 + 2) double2 + nb doubles.
 __global__ __launch_bounds__(WA_THREADS) void world_aperiodicity_kernel(const float* __restrict__ wav, const long long N,
                                                                         const float* __restrict__ f0v,
@@ -243,14 +192,14 @@ __global__ __launch_bounds__(WA_THREADS) void world_aperiodicity_kernel(const fl
     int hw;
     // a frame the host checks would have refused: nothing of it is read or written
     if (!wa_window(f0, fs, L, hw)) return;
-    const long long c = (long long)wa_rnd((double)i * shift * fs);
-    const double T0 = fs / f0, n0d = wa_rnd(T0), delta = T0 - n0d;
+    const long long c = (long long)rnd((double)i * shift * fs);
+    const double T0 = fs / f0, n0d = rnd(T0), delta = T0 - n0d;
     const long long n0 = (long long)n0d, c1 = c - (n0 >> 1), c2 = c1 + n0;
 
-    wa_fill_twiddles(wq, M);
-    wa_frame_fill(a1, wav, N, c1, hw, M);
-    wa_frame_fill(a2, wav, N, c2, hw, M);
-    wa_fft_forward2(a1, a2, wq, logM);
+    fill_twiddles(wq, M);
+    frame_fill(a1, wav, N, c1, hw, M, wa_hann(hw));
+    frame_fill(a2, wav, N, c2, hw, M, wa_hann(hw));
+    fft_forward2(a1, a2, wq, logM);
     unpack_real(a1, logM);
     unpack_real(a2, logM);
 
@@ -272,7 +221,12 @@ __global__ __launch_bounds__(WA_THREADS) void world_aperiodicity_kernel(const fl
     }
     __syncthreads();
     // the band axis out of global memory, once per workgroup: the band sums below walk LDS alone
-    for (int k = tid; k < K; k += nthr) (k < M ? a2[k] : xm[1]) = make_double2((double)wa_lower_band(fw, nb, k), fw[(size_t)Kp + k]);
+    for (int k = tid; k < K; k += nthr) {
+        int b;
+        double fr;
+        band_of(fw, Kp, nb, k, b, fr);
+        (k < M ? a2[k] : xm[1]) = make_double2((double)b, fr);
+    }
     __syncthreads();
 
     // W[k,b] = 1 - fraction where b is the bin's lower band, the fraction where it is the band above; the band index ascends with
@@ -331,22 +285,6 @@ __global__ __launch_bounds__(WA_THREADS) void world_aperiodicity_kernel(const fl
     }
 }
 
-static int wa_log2(int dftlen) {
-    for (int l = 8; l <= 13; ++l)
-        if (dftlen == (1 << l)) return l;
-    return -1;
-}
-
-template <class Kernel>
-static int wa_reserve_lds(Kernel kernel, int lds, int& reserved, const char* what) {
-    if (lds > reserved) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { set_error("%s: cannot reserve %d B of LDS: %s", what, lds, hipGetErrorString(e)); return PTTS_ELAUNCH; }
-        reserved = lds;
-    }
-    return PTTS_OK;
-}
-
 }  // namespace ptts
 
 using namespace ptts;
@@ -354,20 +292,18 @@ using namespace ptts;
 extern "C" int ptts_world_envelope(const float* wav, long long N, const float* rate, float* spec, int T, double shift, double fs,
                                    int dftlen, int log_out, void* stream) {
     PTTS_REQUIRE(T >= 0 && N >= 0, "world_envelope: T=%d N=%lld", T, N);
-    const int logL = wa_log2(dftlen);
-    PTTS_REQUIRE(logL > 0, "world_envelope: dftlen=%d is not a power of two in [%d, %d]", dftlen, WA_MIN_DFTLEN, WA_MAX_DFTLEN);
+    const int logL = frame_log2(dftlen);
+    PTTS_REQUIRE(logL > 0, "world_envelope: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN, FRAME_MAX_DFTLEN);
     PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "world_envelope: fs=%g", fs);
     PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "world_envelope: shift=%g", shift);
     if (T == 0) return PTTS_OK;
     PTTS_REQUIRE(rate && spec && (wav || N == 0), "world_envelope: null tensor");
     const int M = dftlen / 2;
     const int lds = (M + M / 4) * (int)sizeof(double2) + (M + 1) * (int)sizeof(double);
-    static int lds_reserved = 0;
-    const int rc = wa_reserve_lds(world_envelope_kernel, lds, lds_reserved, "world_envelope");
+    const int rc = reserve_lds<world_envelope_kernel>("world_envelope", lds);
     if (rc != PTTS_OK) return rc;
-    const int threads = M / 4 < 64 ? 64 : (M / 4 > WA_THREADS ? WA_THREADS : M / 4);
-    hipLaunchKernelGGL(world_envelope_kernel, dim3(T), dim3(threads), (size_t)lds, (hipStream_t)stream, wav, N, rate, spec, logL - 1,
-                       shift, fs, log_out != 0);
+    hipLaunchKernelGGL(world_envelope_kernel, dim3(T), dim3(frame_threads(M, WA_THREADS)), (size_t)lds, (hipStream_t)stream, wav, N, rate,
+                       spec, logL - 1, shift, fs, log_out != 0);
     return check_launch("world_envelope");
 }
 
@@ -376,8 +312,9 @@ extern "C" int ptts_world_aperiodicity(const float* wav, long long N, const floa
                                        void* stream) {
     PTTS_REQUIRE(T >= 0 && N >= 0, "world_aperiodicity: T=%d N=%lld", T, N);
     PTTS_REQUIRE(nb >= 2 && nb <= WA_MAX_NB, "world_aperiodicity: nb=%d outside [2, %d]", nb, WA_MAX_NB);
-    const int logL = wa_log2(dftlen);
-    PTTS_REQUIRE(logL > 0, "world_aperiodicity: dftlen=%d is not a power of two in [%d, %d]", dftlen, WA_MIN_DFTLEN, WA_MAX_DFTLEN);
+    const int logL = frame_log2(dftlen);
+    PTTS_REQUIRE(logL > 0, "world_aperiodicity: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN,
+                 FRAME_MAX_DFTLEN);
     PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "world_aperiodicity: fs=%g", fs);
     PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "world_aperiodicity: shift=%g", shift);
     if (T == 0) return PTTS_OK;
@@ -387,11 +324,9 @@ extern "C" int ptts_world_aperiodicity(const float* wav, long long N, const floa
                  ptts_fwbnd_table_bytes(dftlen), fwtable_bytes);
     const int M = dftlen / 2, Kp = (M + 1 + 3) / 4 * 4;
     const int lds = (2 * M + M / 4 + 2) * (int)sizeof(double2) + nb * (int)sizeof(double);
-    static int lds_reserved = 0;
-    const int rc = wa_reserve_lds(world_aperiodicity_kernel, lds, lds_reserved, "world_aperiodicity");
+    const int rc = reserve_lds<world_aperiodicity_kernel>("world_aperiodicity", lds);
     if (rc != PTTS_OK) return rc;
-    const int threads = M / 4 < 64 ? 64 : (M / 4 > WA_THREADS ? WA_THREADS : M / 4);
-    hipLaunchKernelGGL(world_aperiodicity_kernel, dim3(T), dim3(threads), (size_t)lds, (hipStream_t)stream, wav, N, f0, voiced, aper,
-                       nb, Kp, logL - 1, shift, fs, fwtable);
+    hipLaunchKernelGGL(world_aperiodicity_kernel, dim3(T), dim3(frame_threads(M, WA_THREADS)), (size_t)lds, (hipStream_t)stream, wav, N,
+                       f0, voiced, aper, nb, Kp, logL - 1, shift, fs, fwtable);
     return check_launch("world_aperiodicity");
 }

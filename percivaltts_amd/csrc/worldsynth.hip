@@ -17,7 +17,7 @@
 // pulse_segments_kernel (2.25 M complex fp64 = 72 KiB at L = 4096): buffer A runs the E_a chain, buffer B takes the noise, becomes
 // N and then E_a N, buffer A runs the E_p chain, B += E_p D while it is packed, B is transformed back: six transforms for a voiced
 // pulse, four for an unvoiced one.  fp64 arithmetic, the segment is rounded to fp32 once; the noise energy is summed in the fixed
-// order of synthchain.h; no atomics, a result does not depend on the grid.
+// order of block_sum (frame.h); no atomics, a result does not depend on the grid.
 #include "common.h"
 #include "synthchain.h"
 
@@ -111,12 +111,7 @@ __global__ __launch_bounds__(PS_THREADS) void world_segments_kernel(const float*
         }
     }
     fft_inverse(bufb, wq, logM);
-    const double inv_m = 1.0 / (double)M;
-    float* out = seg + (size_t)n * W;
-    for (int p = tid; p < winlen; p += nthr) {
-        const double2 z = bufb[p >> 1];
-        out[p] = (float)(((p & 1) ? z.y : z.x) * inv_m);
-    }
+    write_segment(bufb, M, seg, n, W, winlen);
 }
 
 // One workgroup per frame.  dynamic LDS: nb doubles (the frame's bands as amplitudes).
@@ -133,10 +128,11 @@ __global__ __launch_bounds__(256) void aper_rows_kernel(const float* __restrict_
     for (int i = tid; i < nb; i += nthr) ar_lds[i] = pow(10.0, (double)aper[(size_t)t * nb + i] / 20.0);
     __syncthreads();
     for (int k = tid; k < K; k += nthr) {
-        int b = (int)tab[k];
-        b = b < 0 ? 0 : (b > nb - 2 ? nb - 2 : b);      // whatever the table holds
+        int b;
+        double fr;
+        band_of(tab, Kp, nb, k, b, fr);
         const double lo = ar_lds[b], hi = ar_lds[b + 1];
-        const double v = fma(tab[(size_t)Kp + k], hi - lo, lo);
+        const double v = fma(fr, hi - lo, lo);
         out[(size_t)t * K + k] = (float)(v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v));
     }
 }
@@ -150,7 +146,8 @@ extern "C" int ptts_aper_rows(const float* aper, const float* vuv, float* out, i
     PTTS_REQUIRE(T >= 0, "aper_rows: T=%d", T);
     PTTS_REQUIRE(nb >= 2 && nb <= AR_MAX_NB, "aper_rows: nb=%d outside [2, %d]", nb, AR_MAX_NB);
     PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "aper_rows: fs=%g", fs);
-    PTTS_REQUIRE(ps_log2(dftlen) > 0, "aper_rows: dftlen=%d is not a power of two in [%d, %d]", dftlen, PS_MIN_DFTLEN, PS_MAX_DFTLEN);
+    PTTS_REQUIRE(frame_log2(dftlen) > 0, "aper_rows: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN,
+                 FRAME_MAX_DFTLEN);
     if (T == 0) return PTTS_OK;
     PTTS_REQUIRE(aper && vuv && out && table, "aper_rows: null tensor");
     const int K = dftlen / 2 + 1, Kp = (K + 3) / 4 * 4;
@@ -164,25 +161,5 @@ extern "C" int ptts_aper_rows(const float* aper, const float* vuv, float* out, i
 
 extern "C" int ptts_world_segments(const float* spec, const float* aper, const float* noise, const int* itab, const double* dtab,
                                    int P, int T, int dftlen, double fs, long long wavlen, float* seg, int W, void* stream) {
-    PTTS_REQUIRE(P >= 0 && T >= 0 && wavlen >= 0, "world_segments: P=%d T=%d wavlen=%lld", P, T, wavlen);
-    const int logL = ps_log2(dftlen);
-    PTTS_REQUIRE(logL > 0, "world_segments: dftlen=%d is not a power of two in [%d, %d]", dftlen, PS_MIN_DFTLEN, PS_MAX_DFTLEN);
-    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "world_segments: fs=%g", fs);
-    PTTS_REQUIRE(W >= 1 && W <= dftlen, "world_segments: W=%d outside [1, dftlen]", W);
-    if (P == 0 || T == 0) return PTTS_OK;
-    PTTS_REQUIRE(spec && aper && itab && dtab && seg && (noise || wavlen == 0), "world_segments: null tensor");
-    const int M = dftlen / 2;
-    const int lds = (2 * M + M / 4) * (int)sizeof(double2);
-    static int lds_reserved = 0;
-    if (lds > lds_reserved) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(world_segments_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { set_error("world_segments: cannot reserve %d B of LDS: %s", lds, hipGetErrorString(e)); return PTTS_ELAUNCH; }
-        lds_reserved = lds;
-    }
-    const int threads = M / 4 < 64 ? 64 : (M / 4 > PS_THREADS ? PS_THREADS : M / 4);
-    const int taper = (int)floor(0.001 * fs + 0.5);
-    hipLaunchKernelGGL(world_segments_kernel, dim3(P), dim3(threads), (size_t)lds, (hipStream_t)stream, spec, aper, noise, itab, dtab,
-                       P, T, logL - 1, fs, taper, wavlen, seg, W);
-    return check_launch("world_segments");
+    return launch_segments<world_segments_kernel>("world_segments", spec, aper, noise, itab, dtab, P, T, dftlen, fs, wavlen, seg, W, stream);
 }

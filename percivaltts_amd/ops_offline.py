@@ -271,28 +271,25 @@ def _spectrum_rows(x, name, lo, hi, what):
     return x, rows, W
 
 
-def _mcep_table(device, M1, alpha, dftlen):
-    key = ('mcep', device, M1, float(alpha), dftlen)
+def _device_table(kind, device, params, dtype, size_args, args=None):
+    """(table, bytes) of ptts_<kind>_table(table, bytes, *args) on `device`, made once per (kind, device, params): a flat `dtype`
+    tensor of ptts_<kind>_table_bytes(*size_args) bytes.  params = (order or bands, .., dftlen); args: params unless given."""
+    key = (kind, device) + params
     tab = _spectrum_tables.get(key)
     if tab is None:
-        l = _hip.lib()
-        n = l.ptts_mcep_table_bytes(M1, dftlen)
-        tab = torch.empty(n // 4, dtype=torch.float32, device=device)
-        call('ptts_mcep_table', ptr(tab), n, M1, float(alpha), dftlen, stream(), tag=(M1, dftlen))
+        n = getattr(_hip.lib(), 'ptts_{}_table_bytes'.format(kind))(*size_args)
+        tab = torch.empty(n // dtype.itemsize, dtype=dtype, device=device)
+        call('ptts_{}_table'.format(kind), ptr(tab), n, *(params if args is None else args), stream(), tag=(params[0], params[-1]))
         _spectrum_tables[key] = tab
-    return tab, tab.numel() * 4
+    return tab, tab.numel() * dtype.itemsize
+
+
+def _mcep_table(device, M1, alpha, dftlen):
+    return _device_table('mcep', device, (M1, float(alpha), dftlen), torch.float32, (M1, dftlen))
 
 
 def _fwbnd_table(device, nb, fs, alpha, dftlen):
-    key = ('fwbnd', device, nb, float(fs), float(alpha), dftlen)
-    tab = _spectrum_tables.get(key)
-    if tab is None:
-        l = _hip.lib()
-        n = l.ptts_fwbnd_table_bytes(dftlen)
-        tab = torch.empty(n // 8, dtype=torch.float64, device=device)
-        call('ptts_fwbnd_table', ptr(tab), n, nb, float(fs), float(alpha), dftlen, stream(), tag=(nb, dftlen))
-        _spectrum_tables[key] = tab
-    return tab, tab.numel() * 8
+    return _device_table('fwbnd', device, (nb, float(fs), float(alpha), dftlen), torch.float64, (dftlen,))
 
 
 def bark_alpha(fs):
@@ -378,14 +375,7 @@ def spec2mcep_check(order, alpha, dftlen):
 
 
 def _spec2mcep_table(device, M1, alpha, dftlen):
-    key = ('spec2mcep', device, M1, float(alpha), dftlen)
-    tab = _spectrum_tables.get(key)
-    if tab is None:
-        n = _hip.lib().ptts_spec2mcep_table_bytes(M1, dftlen)
-        tab = torch.empty(n // 8, dtype=torch.float64, device=device)
-        call('ptts_spec2mcep_table', ptr(tab), n, M1, float(alpha), dftlen, stream(), tag=(M1, dftlen))
-        _spectrum_tables[key] = tab
-    return tab, tab.numel() * 8
+    return _device_table('spec2mcep', device, (M1, float(alpha), dftlen), torch.float64, (M1, dftlen))
 
 
 def spec2mcep(spec, alpha, order, log=False):
@@ -433,46 +423,67 @@ def _rnd(x):
     return int(math.floor(x + 0.5))
 
 
+def _pulse_table(fn, world, f0, voiced, shift, fs, wavlen, dftlen):
+    """ops.pulse_table and, with `world`, ops.world_pulse_table.  The two differ in the rate at t (the interpolated f0 everywhere,
+    or WORLD_UNVOICED_RATE where the nearest frame is unvoiced), in the lead of a pulse over its window (a quarter of the pulse's
+    window, or of the 50-ms window for every pulse) and in the rows 'w', 'i0', 'i1', 'v' that only WORLD has."""
+    pulse_check(dftlen, fs)
+    f0 = np.ascontiguousarray(f0, dtype=np.float64)
+    if f0.ndim != 1 or f0.size < 1 or not (np.isfinite(f0).all() and (f0 > 0).all()):
+        raise ValueError('ops.{}: f0 has to be [T] positive finite Hz values'.format(fn))
+    if world:
+        voiced = np.asarray(voiced)
+        if voiced.shape != f0.shape or voiced.dtype.kind not in 'biu':
+            raise ValueError('ops.{}: voiced has to be [T] booleans'.format(fn))
+        voiced = voiced.astype(bool)
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('ops.{}: shift={}'.format(fn, shift))
+    T, fs, shift = f0.size, float(fs), float(shift)
+    if int(wavlen) != int(round(shift * (T - 1) * fs)) or wavlen >= 1 << 31:
+        raise ValueError('ops.{}: wavlen={} is not round(shift (T-1) fs) = {}'.format(fn, wavlen, int(round(shift * (T - 1) * fs))))
+    wavlen = int(wavlen)
+    times = shift * np.arange(T)
+    frame = lambda x: min(max(_rnd(x / shift), 0), T - 1)
+    f0_at = lambda x: max(float(np.interp(x, times, f0)), PULSE_F0_FLOOR)
+    rate = (lambda x: f0_at(x) if voiced[frame(x)] else WORLD_UNVOICED_RATE) if world else f0_at
+    t = [0.0]
+    while t[-1] < wavlen / fs:
+        t.append(t[-1] + 1.0 / rate(t[-1]))
+    P = len(t)
+    tab = {'t': np.array(t, dtype=np.float64)}
+    for key in ('delay', 'f0', 'w') if world else ('delay', 'f0'):
+        tab[key] = np.zeros(P, dtype=np.float64)
+    for key in WORLD_INT_ROWS if world else PULSE_INT_ROWS:
+        tab[key] = np.zeros(P, dtype=np.int32)
+    for n in range(P):
+        f0n = rate(t[n])
+        winlen = 2 * int(max(0.050 * fs, 4.0 * fs / f0n) / 2) + 1
+        if winlen > dftlen:
+            raise ValueError('ops.{}: the window of pulse {} ({} samples at f0 = {:.1f} Hz) does not fit dftlen={}'.format(
+                fn, n, winlen, f0n, dftlen))
+        pos = int((2 * int(0.050 * fs / 2) + 1) / 4) if world else int(winlen / 4)
+        c = _rnd(fs * t[n])
+        lb = _rnd(fs * (t[n - 1] + t[n]) / 2) if n > 0 else _rnd(fs * (t[n] - 0.5 / f0n))
+        rb = _rnd(fs * (t[n] + t[n + 1]) / 2) if n < P - 1 else _rnd(fs * (t[n] + 0.5 / f0n))
+        tab['start'][n], tab['winlen'][n] = c - pos, winlen
+        tab['lb'][n], tab['rb'][n] = min(max(lb, 0), wavlen), min(max(rb, 0), wavlen)
+        tab['fr'][n] = frame(t[n])
+        tab['delay'][n], tab['f0'][n] = pos + (fs * t[n] - c), f0n
+        if world:
+            i0 = min(int(t[n] / shift), T - 1)
+            tab['i0'][n], tab['i1'][n] = i0, min(i0 + 1, T - 1)
+            tab['w'][n] = t[n] / shift - i0 if i0 < T - 1 else 0.0
+            tab['v'][n] = int(voiced[tab['fr'][n]])
+    return tab
+
+
 def pulse_table(f0, shift, fs, wavlen, dftlen):
     """The pulse positions of one utterance and everything the kernels need per pulse, on the host in fp64:
     f0 [T] in Hz at the frame times shift * i (values below 50 Hz are synthesised at 50 Hz), wavlen = round(shift (T-1) fs).
     Returns a dict of numpy arrays, one entry per pulse: 't' fp64 (t_0 = 0, t_{n+1} = t_n + 1 / f0(t_n), the last one at or beyond
     the end), the int32 rows 'start', 'winlen', 'lb', 'rb', 'fr' and the fp64 rows 'delay', 'f0'.  The noise segments [lb, rb) tile
     [0, wavlen).  ValueError when a window does not fit dftlen."""
-    pulse_check(dftlen, fs)
-    f0 = np.ascontiguousarray(f0, dtype=np.float64)
-    if f0.ndim != 1 or f0.size < 1 or not (np.isfinite(f0).all() and (f0 > 0).all()):
-        raise ValueError('ops.pulse_table: f0 has to be [T] positive finite Hz values')
-    if not 0.0 < float(shift) < 1e3:
-        raise ValueError('ops.pulse_table: shift={}'.format(shift))
-    T, fs, shift = f0.size, float(fs), float(shift)
-    if int(wavlen) != int(round(shift * (T - 1) * fs)) or wavlen >= 1 << 31:
-        raise ValueError('ops.pulse_table: wavlen={} is not round(shift (T-1) fs) = {}'.format(wavlen, int(round(shift * (T - 1) * fs))))
-    wavlen = int(wavlen)
-    times = shift * np.arange(T)
-    f0_at = lambda x: max(float(np.interp(x, times, f0)), PULSE_F0_FLOOR)
-    t = [0.0]
-    while t[-1] < wavlen / fs:
-        t.append(t[-1] + 1.0 / f0_at(t[-1]))
-    P = len(t)
-    tab = {'t': np.array(t, dtype=np.float64), 'delay': np.zeros(P, dtype=np.float64), 'f0': np.zeros(P, dtype=np.float64)}
-    for key in PULSE_INT_ROWS:
-        tab[key] = np.zeros(P, dtype=np.int32)
-    for n in range(P):
-        f0n = f0_at(t[n])
-        winlen = 2 * int(max(0.050 * fs, 4.0 * fs / f0n) / 2) + 1
-        if winlen > dftlen:
-            raise ValueError('ops.pulse_table: the window of pulse {} ({} samples at f0 = {:.1f} Hz) does not fit dftlen={}'.format(
-                n, winlen, f0n, dftlen))
-        pos = int(winlen / 4)
-        c = _rnd(fs * t[n])
-        lb = _rnd(fs * (t[n - 1] + t[n]) / 2) if n > 0 else _rnd(fs * (t[n] - 0.5 / f0n))
-        rb = _rnd(fs * (t[n] + t[n + 1]) / 2) if n < P - 1 else _rnd(fs * (t[n] + 0.5 / f0n))
-        tab['start'][n], tab['winlen'][n] = c - pos, winlen
-        tab['lb'][n], tab['rb'][n] = min(max(lb, 0), wavlen), min(max(rb, 0), wavlen)
-        tab['fr'][n] = min(max(_rnd(t[n] / shift), 0), T - 1)
-        tab['delay'][n], tab['f0'][n] = pos + (fs * t[n] - c), f0n
-    return tab
+    return _pulse_table('pulse_table', False, f0, None, shift, fs, wavlen, dftlen)
 
 
 def _pulse_table_rows(table, T, dftlen, wavlen, fn='pulse_synthesis', maker='pulse_table', int_rows=PULSE_INT_ROWS,
@@ -508,45 +519,46 @@ def _pulse_table_rows(table, T, dftlen, wavlen, fn='pulse_synthesis', maker='pul
     return itab.astype(np.int32), dtab, int(winlen.max())
 
 
-def noise_mask(nmb, f0, fs, dftlen=4096):
-    """Noise-mask bands [T,nb] in [0,1] and f0 [T] in Hz (fp32 device) -> the binary mask smoothed along frequency, [T, dftlen/2+1]
-    (csrc/pulsesynth.hip): interpolation at k fs / dftlen on the band axis of fwbnd2spec, zero below the second harmonic, threshold at
-    0.5, a forward-backward pass of hanning(9), clip."""
+def _band_rows(fn, bands, bands_name, width, per_frame, per_frame_name, fs, dftlen):
+    """ops.noise_mask and ops.aper_rows: bands [T,width] and one value per frame [T] (fp32 device) -> [T, dftlen/2+1] from
+    ptts_<fn>, which reads the band axis of fwbnd2spec."""
     pulse_check(dftlen, fs)
-    if not torch.is_tensor(nmb) or nmb.dim() != 2 or not 2 <= nmb.shape[1] <= SPECTRUM_MAX_NB:
-        raise ValueError('ops.noise_mask: expected a [T,nb] tensor with nb in [2, {}]'.format(SPECTRUM_MAX_NB))
-    T, nbands = nmb.shape
-    if not torch.is_tensor(f0) or tuple(f0.shape) != (T,):
-        raise ValueError('ops.noise_mask: f0 is not [{}]'.format(T))
-    _no_backward('noise_mask', nmb, f0)
-    f32c(nmb, 'noise_mask.nmb'); f32c(f0, 'noise_mask.f0')
-    out = torch.empty((T, dftlen // 2 + 1), dtype=torch.float32, device=nmb.device)
+    if not torch.is_tensor(bands) or bands.dim() != 2 or not 2 <= bands.shape[1] <= SPECTRUM_MAX_NB:
+        raise ValueError('ops.{}: expected a [T,{w}] tensor with {w} in [2, {}]'.format(fn, SPECTRUM_MAX_NB, w=width))
+    T, nbands = bands.shape
+    if not torch.is_tensor(per_frame) or tuple(per_frame.shape) != (T,):
+        raise ValueError('ops.{}: {} is not [{}]'.format(fn, per_frame_name, T))
+    _no_backward(fn, bands, per_frame)
+    f32c(bands, '{}.{}'.format(fn, bands_name)); f32c(per_frame, '{}.{}'.format(fn, per_frame_name))
+    out = torch.empty((T, dftlen // 2 + 1), dtype=torch.float32, device=bands.device)
     if T == 0:
         return out
-    tab, nbytes = _fwbnd_table(nmb.device, nbands, fs, bark_alpha(fs), dftlen)
-    call('ptts_noise_mask', ptr(nmb), ptr(f0), ptr(out), T, nbands, float(fs), int(dftlen), ptr(tab), nbytes, stream(),
+    tab, nbytes = _fwbnd_table(bands.device, nbands, fs, bark_alpha(fs), dftlen)
+    call('ptts_' + fn, ptr(bands), ptr(per_frame), ptr(out), T, nbands, float(fs), int(dftlen), ptr(tab), nbytes, stream(),
          tag=(T, nbands, dftlen))
     return out
 
 
-def pulse_synthesis(spec, mask, table, noise, fs, dftlen, wavlen):
-    """The waveform [wavlen] (fp32 device) of one utterance: spec and mask [T, dftlen/2+1] fp32 device, table from
-    ops.pulse_table (host), noise [wavlen] N(0,1) fp32 device.  One workgroup per pulse builds its segment (minimum-phase envelope
-    times the mix of a delayed pulse and the pulse's stretch of the noise), then one lane per sample adds the segments that cover
-    it, in pulse order (csrc/pulsesynth.hip).  Same input, same bytes."""
+def _segments_synthesis(fn, segments, maker, int_rows, dbl_rows, spec, rows, rows_name, table, noise, fs, dftlen, wavlen,
+                        check_table=None):
+    """ops.pulse_synthesis and ops.world_synthesis: the argument checks, the table of ops.<maker> on the device, the kernel
+    `segments` (one workgroup per pulse), then the overlap-add.  rows: the [T,K] input beside spec; check_table(itab, dtab, T):
+    what a synthesiser asks of its own table rows."""
     pulse_check(dftlen, fs)
     K = dftlen // 2 + 1
     if not torch.is_tensor(spec) or spec.dim() != 2 or spec.shape[1] != K:
-        raise ValueError('ops.pulse_synthesis: spec is not [T,{}]'.format(K))
+        raise ValueError('ops.{}: spec is not [T,{}]'.format(fn, K))
     T = spec.shape[0]
-    if not torch.is_tensor(mask) or tuple(mask.shape) != (T, K):
-        raise ValueError('ops.pulse_synthesis: mask is not [{},{}]'.format(T, K))
+    if not torch.is_tensor(rows) or tuple(rows.shape) != (T, K):
+        raise ValueError('ops.{}: {} is not [{},{}]'.format(fn, rows_name, T, K))
     wavlen = int(wavlen)
     if wavlen < 0 or not torch.is_tensor(noise) or tuple(noise.shape) != (wavlen,):
-        raise ValueError('ops.pulse_synthesis: noise is not [wavlen={}]'.format(wavlen))
-    _no_backward('pulse_synthesis', spec, mask, noise)
-    f32c(spec, 'pulse_synthesis.spec'); f32c(mask, 'pulse_synthesis.mask'); f32c(noise, 'pulse_synthesis.noise')
-    itab, dtab, W = _pulse_table_rows(table, T, dftlen, wavlen)
+        raise ValueError('ops.{}: noise is not [wavlen={}]'.format(fn, wavlen))
+    _no_backward(fn, spec, rows, noise)
+    f32c(spec, '{}.spec'.format(fn)); f32c(rows, '{}.{}'.format(fn, rows_name)); f32c(noise, '{}.noise'.format(fn))
+    itab, dtab, W = _pulse_table_rows(table, T, dftlen, wavlen, fn, maker, int_rows, dbl_rows)
+    if check_table is not None:
+        check_table(itab, dtab, T)
     P = itab.shape[1]
     wav = torch.empty(wavlen, dtype=torch.float32, device=spec.device)
     if wavlen == 0:
@@ -556,10 +568,26 @@ def pulse_synthesis(spec, mask, table, noise, fs, dftlen, wavlen):
     it = torch.from_numpy(itab).to(spec.device)
     dt = torch.from_numpy(dtab).to(spec.device)
     seg = torch.empty((P, W), dtype=torch.float32, device=spec.device)
-    call('ptts_pulse_segments', ptr(spec), ptr(mask), ptr(noise), ptr(it), ptr(dt), P, T, int(dftlen), float(fs), wavlen, ptr(seg), W,
-         stream(), tag=(P, dftlen, W))
+    call(segments, ptr(spec), ptr(rows), ptr(noise), ptr(it), ptr(dt), P, T, int(dftlen), float(fs), wavlen, ptr(seg), W, stream(),
+         tag=(P, dftlen, W))
     call('ptts_pulse_overlap_add', ptr(seg), ptr(it), P, W, ptr(wav), wavlen, stream(), tag=(P, W, wavlen))
     return wav
+
+
+def noise_mask(nmb, f0, fs, dftlen=4096):
+    """Noise-mask bands [T,nb] in [0,1] and f0 [T] in Hz (fp32 device) -> the binary mask smoothed along frequency, [T, dftlen/2+1]
+    (csrc/pulsesynth.hip): interpolation at k fs / dftlen on the band axis of fwbnd2spec, zero below the second harmonic, threshold at
+    0.5, a forward-backward pass of hanning(9), clip."""
+    return _band_rows('noise_mask', nmb, 'nmb', 'nb', f0, 'f0', fs, dftlen)
+
+
+def pulse_synthesis(spec, mask, table, noise, fs, dftlen, wavlen):
+    """The waveform [wavlen] (fp32 device) of one utterance: spec and mask [T, dftlen/2+1] fp32 device, table from
+    ops.pulse_table (host), noise [wavlen] N(0,1) fp32 device.  One workgroup per pulse builds its segment (minimum-phase envelope
+    times the mix of a delayed pulse and the pulse's stretch of the noise), then one lane per sample adds the segments that cover
+    it, in pulse order (csrc/pulsesynth.hip).  Same input, same bytes."""
+    return _segments_synthesis('pulse_synthesis', 'ptts_pulse_segments', 'pulse_table', PULSE_INT_ROWS, ('delay', 'f0'), spec, mask, 'mask',
+                               table, noise, fs, dftlen, wavlen)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -577,73 +605,14 @@ def world_pulse_table(f0, voiced, shift, fs, wavlen, dftlen):
     pos = int((2 int(0.050 fs / 2) + 1) / 4) samples, whatever its winlen, so start ascends with t.  Returns ops.pulse_table's
     entries ('f0' is the rate at the pulse) and, per pulse, the frames 'i0', 'i1' (int32) whose rows are blended with the weight
     'w' (fp64) on i1, and 'v' (int32), 1 where frame 'fr' is voiced.  ValueError when a window does not fit dftlen."""
-    pulse_check(dftlen, fs)
-    f0 = np.ascontiguousarray(f0, dtype=np.float64)
-    if f0.ndim != 1 or f0.size < 1 or not (np.isfinite(f0).all() and (f0 > 0).all()):
-        raise ValueError('ops.world_pulse_table: f0 has to be [T] positive finite Hz values')
-    voiced = np.asarray(voiced)
-    if voiced.shape != f0.shape or voiced.dtype.kind not in 'biu':
-        raise ValueError('ops.world_pulse_table: voiced has to be [T] booleans')
-    voiced = voiced.astype(bool)
-    if not 0.0 < float(shift) < 1e3:
-        raise ValueError('ops.world_pulse_table: shift={}'.format(shift))
-    T, fs, shift = f0.size, float(fs), float(shift)
-    if int(wavlen) != int(round(shift * (T - 1) * fs)) or wavlen >= 1 << 31:
-        raise ValueError('ops.world_pulse_table: wavlen={} is not round(shift (T-1) fs) = {}'.format(
-            wavlen, int(round(shift * (T - 1) * fs))))
-    wavlen = int(wavlen)
-    times = shift * np.arange(T)
-    frame = lambda x: min(max(_rnd(x / shift), 0), T - 1)
-    rate = lambda x: max(float(np.interp(x, times, f0)), PULSE_F0_FLOOR) if voiced[frame(x)] else WORLD_UNVOICED_RATE
-    t = [0.0]
-    while t[-1] < wavlen / fs:
-        t.append(t[-1] + 1.0 / rate(t[-1]))
-    P = len(t)
-    tab = {'t': np.array(t, dtype=np.float64)}
-    for key in ('delay', 'f0', 'w'):
-        tab[key] = np.zeros(P, dtype=np.float64)
-    for key in WORLD_INT_ROWS:
-        tab[key] = np.zeros(P, dtype=np.int32)
-    pos = int((2 * int(0.050 * fs / 2) + 1) / 4)
-    for n in range(P):
-        f0n = rate(t[n])
-        winlen = 2 * int(max(0.050 * fs, 4.0 * fs / f0n) / 2) + 1
-        if winlen > dftlen:
-            raise ValueError('ops.world_pulse_table: the window of pulse {} ({} samples at f0 = {:.1f} Hz) does not fit dftlen={}'.format(
-                n, winlen, f0n, dftlen))
-        c = _rnd(fs * t[n])
-        lb = _rnd(fs * (t[n - 1] + t[n]) / 2) if n > 0 else _rnd(fs * (t[n] - 0.5 / f0n))
-        rb = _rnd(fs * (t[n] + t[n + 1]) / 2) if n < P - 1 else _rnd(fs * (t[n] + 0.5 / f0n))
-        tab['start'][n], tab['winlen'][n] = c - pos, winlen
-        tab['lb'][n], tab['rb'][n] = min(max(lb, 0), wavlen), min(max(rb, 0), wavlen)
-        tab['fr'][n] = frame(t[n])
-        tab['delay'][n], tab['f0'][n] = pos + (fs * t[n] - c), f0n
-        i0 = min(int(t[n] / shift), T - 1)
-        tab['i0'][n], tab['i1'][n] = i0, min(i0 + 1, T - 1)
-        tab['w'][n] = t[n] / shift - i0 if i0 < T - 1 else 0.0
-        tab['v'][n] = int(voiced[tab['fr'][n]])
-    return tab
+    return _pulse_table('world_pulse_table', True, f0, voiced, shift, fs, wavlen, dftlen)
 
 
 def aper_rows(aper_db, vuv, fs, dftlen=4096):
     """Band aperiodicities [T,A] in dB and vuv [T] (fp32 device) -> the aperiodicity of every bin, [T, dftlen/2+1] in [0, 1]
     (csrc/worldsynth.hip): 10^(x/20) per band, those values interpolated at k fs / dftlen on the band axis of fwbnd2spec, clipped;
     the row of an unvoiced frame (vuv < 0.5) is 1 throughout."""
-    pulse_check(dftlen, fs)
-    if not torch.is_tensor(aper_db) or aper_db.dim() != 2 or not 2 <= aper_db.shape[1] <= SPECTRUM_MAX_NB:
-        raise ValueError('ops.aper_rows: expected a [T,A] tensor with A in [2, {}]'.format(SPECTRUM_MAX_NB))
-    T, nbands = aper_db.shape
-    if not torch.is_tensor(vuv) or tuple(vuv.shape) != (T,):
-        raise ValueError('ops.aper_rows: vuv is not [{}]'.format(T))
-    _no_backward('aper_rows', aper_db, vuv)
-    f32c(aper_db, 'aper_rows.aper_db'); f32c(vuv, 'aper_rows.vuv')
-    out = torch.empty((T, dftlen // 2 + 1), dtype=torch.float32, device=aper_db.device)
-    if T == 0:
-        return out
-    tab, nbytes = _fwbnd_table(aper_db.device, nbands, fs, bark_alpha(fs), dftlen)
-    call('ptts_aper_rows', ptr(aper_db), ptr(vuv), ptr(out), T, nbands, float(fs), int(dftlen), ptr(tab), nbytes, stream(),
-         tag=(T, nbands, dftlen))
-    return out
+    return _band_rows('aper_rows', aper_db, 'aper_db', 'A', vuv, 'vuv', fs, dftlen)
 
 
 def world_synthesis(spec, aper, table, noise, fs, dftlen, wavlen):
@@ -652,35 +621,11 @@ def world_synthesis(spec, aper, table, noise, fs, dftlen, wavlen):
     its two frames and builds its segment (the minimum-phase periodic filter times a delayed pulse, for a voiced pulse, plus the
     minimum-phase aperiodic filter times the pulse's stretch of the noise), then ops.pulse_synthesis's overlap-add sums the
     segments in pulse order (csrc/worldsynth.hip, csrc/pulsesynth.hip).  Same input, same bytes."""
-    pulse_check(dftlen, fs)
-    K = dftlen // 2 + 1
-    if not torch.is_tensor(spec) or spec.dim() != 2 or spec.shape[1] != K:
-        raise ValueError('ops.world_synthesis: spec is not [T,{}]'.format(K))
-    T = spec.shape[0]
-    if not torch.is_tensor(aper) or tuple(aper.shape) != (T, K):
-        raise ValueError('ops.world_synthesis: aper is not [{},{}]'.format(T, K))
-    wavlen = int(wavlen)
-    if wavlen < 0 or not torch.is_tensor(noise) or tuple(noise.shape) != (wavlen,):
-        raise ValueError('ops.world_synthesis: noise is not [wavlen={}]'.format(wavlen))
-    _no_backward('world_synthesis', spec, aper, noise)
-    f32c(spec, 'world_synthesis.spec'); f32c(aper, 'world_synthesis.aper'); f32c(noise, 'world_synthesis.noise')
-    itab, dtab, W = _pulse_table_rows(table, T, dftlen, wavlen, 'world_synthesis', 'world_pulse_table', WORLD_INT_ROWS,
-                                      ('delay', 'f0', 'w'))
-    P = itab.shape[1]
-    if P and (itab[5:7].min() < 0 or itab[5:7].max() >= T or not ((dtab[2] >= 0) & (dtab[2] <= 1)).all()):
-        raise ValueError('ops.world_synthesis: the frames i0 / i1 or the weight w of the table are outside the {} frames given'.format(T))
-    wav = torch.empty(wavlen, dtype=torch.float32, device=spec.device)
-    if wavlen == 0:
-        return wav
-    if P == 0 or T == 0:
-        return wav.zero_()
-    it = torch.from_numpy(itab).to(spec.device)
-    dt = torch.from_numpy(dtab).to(spec.device)
-    seg = torch.empty((P, W), dtype=torch.float32, device=spec.device)
-    call('ptts_world_segments', ptr(spec), ptr(aper), ptr(noise), ptr(it), ptr(dt), P, T, int(dftlen), float(fs), wavlen, ptr(seg), W,
-         stream(), tag=(P, dftlen, W))
-    call('ptts_pulse_overlap_add', ptr(seg), ptr(it), P, W, ptr(wav), wavlen, stream(), tag=(P, W, wavlen))
-    return wav
+    def frames_and_weight(itab, dtab, T):
+        if itab.shape[1] and (itab[5:7].min() < 0 or itab[5:7].max() >= T or not ((dtab[2] >= 0) & (dtab[2] <= 1)).all()):
+            raise ValueError('ops.world_synthesis: the frames i0 / i1 or the weight w of the table are outside the {} frames given'.format(T))
+    return _segments_synthesis('world_synthesis', 'ptts_world_segments', 'world_pulse_table', WORLD_INT_ROWS, ('delay', 'f0', 'w'), spec, aper,
+                               'aper', table, noise, fs, dftlen, wavlen, frames_and_weight)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -738,15 +683,9 @@ def f0_track(f0, f0_min, f0_max, fs, shift, dftlen, wavlen=None):
 
 
 def _compress_table(device, nb, fs, dftlen):
-    key = ('compress', device, nb, float(fs), dftlen)
-    tab = _spectrum_tables.get(key)
-    if tab is None:
-        fw, fwbytes = _fwbnd_table(device, nb, fs, bark_alpha(fs), dftlen)
-        n = _hip.lib().ptts_fwbnd_compress_table_bytes(nb)
-        tab = torch.empty(n // 8, dtype=torch.float64, device=device)
-        call('ptts_fwbnd_compress_table', ptr(tab), n, ptr(fw), fwbytes, nb, int(dftlen), stream(), tag=(nb, dftlen))
-        _spectrum_tables[key] = tab
-    return tab, tab.numel() * 8
+    fw, fwbytes = _fwbnd_table(device, nb, fs, bark_alpha(fs), dftlen)
+    return _device_table('fwbnd_compress', device, (nb, float(fs), dftlen), torch.float64, (nb,),
+                         args=(ptr(fw), fwbytes, nb, int(dftlen)))
 
 
 def fwbnd_compress_check(nb, fs, dftlen):

@@ -301,6 +301,77 @@ class VocoderF0Spec(Vocoder):
         lo = 1 + self.spec_size
         self.features_err.setdefault(key, []).append(np.sqrt(np.mean((REF[:, lo:lo + size] - CMP[:, lo:lo + size])**2, 0)))
 
+    # What the synthesis_device / analysis_device / analysisf_device / write_streams / analysisfid_device of the subclasses share.
+    def _synthesis_input(self, CMP, pp_f0_smooth):
+        """The checks of a synthesis_device -> (CMP as a device tensor, T, wavlen)."""
+        import torch
+        from . import backend_hip, ops
+        if pp_f0_smooth is not None:
+            raise ValueError('pp_f0_smooth={!r}: f0 smoothing is not part of this synthesiser'.format(pp_f0_smooth))
+        if not hasattr(CMP, 'shape') or len(CMP.shape) != 2 or CMP.shape[1] != self.featuressizeraw() or CMP.shape[0] < 1:
+            raise ValueError('synthesis_device: CMP is not [T, {}] with T >= 1'.format(self.featuressizeraw()))
+        ops.pulse_check(self.dftlen, self.fs)
+        x = CMP
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.ascontiguousarray(CMP, dtype=np.float32)).to(backend_hip.device())
+        if x.requires_grad:
+            raise ValueError('synthesis_device has no backward pass: detach its input')
+        T = x.shape[0]
+        return x, T, int(round(self.shift * (T - 1) * self.fs))
+
+    def _analysis_input(self, check, wav, f0, f0_min, f0_max):
+        """The checks of an analysis_device (check: ops.analysis_check or ops.world_analysis_check) and its F0 steps -> (wav as
+        float64, f0 as given, estimated or refined, the continuous track of ops.f0_track)."""
+        from . import ops_offline as ops
+        if self.spec_type not in ('fwbnd', 'mcep'):
+            raise ValueError("analysis_device: spec_type is 'fwbnd' or 'mcep', got {!r}".format(self.spec_type))
+        check(self.dftlen, self.fs, self.shift, f0_min, f0_max)
+        if self.spec_type == 'fwbnd':
+            ops.fwbnd_compress_check(self.spec_size, self.fs, self.dftlen)
+        else:
+            ops.spec2mcep_check(self.spec_size - 1, bark_alpha(self.fs), self.dftlen)
+        ops.fwbnd_compress_check(self.noisesize(), self.fs, self.dftlen)
+        wav = np.asarray(wav, dtype=np.float64)
+        if wav.ndim != 1 or not np.isfinite(wav).all():
+            raise ValueError('analysis_device: wav is not a finite [N] waveform')
+        if f0 is None:
+            f0 = self.f0_estimate_device(wav, f0_min, f0_max)
+        if self.f0_refine:
+            f0 = self.f0_refine_device(wav, f0, f0_min, f0_max)
+        return wav, f0, ops.f0_track(f0, f0_min, f0_max, self.fs, self.shift, self.dftlen, wavlen=wav.size)
+
+    def _analysisf_device(self, label, fwav, f0_in, f0_min, f0_max, streams, kwargs):
+        """analysis_device from the wave file fwav to the files `streams`, in the order of write_streams' arguments."""
+        if kwargs.get('preproc_hp') is not None:
+            raise ValueError('analysisf_device: preproc_hp={!r}: the high-pass pre-processing is not built'.format(kwargs['preproc_hp']))
+        if set(kwargs) - {'preproc_hp', 'f0_refine'}:
+            raise ValueError('analysisf_device: unknown arguments {}'.format(sorted(set(kwargs) - {'preproc_hp', 'f0_refine'})))
+        _check_f0_refine(kwargs.get('f0_refine'))
+        print('Extracting {} features from: '.format(label) + fwav)
+        wav, fs = wavread(fwav)
+        if fs != int(round(self.fs)):
+            raise ValueError('analysisf_device: {} is sampled at {} Hz, the vocoder at {} (resampling is not built)'.format(fwav, fs, self.fs))
+        f0 = np.fromfile(f0_in, dtype=np.float32) if isinstance(f0_in, str) else f0_in
+        with self.f0_refine_as(kwargs.get('f0_refine')):
+            CMP = self.analysis_device(wav, f0, f0_min, f0_max)
+        return self.write_streams(CMP, *streams)
+
+    def _write_streams(self, CMP, paths_and_columns):
+        """Each (path, columns of CMP) pair as a headerless float32 file; missing directories are made.  Returns T."""
+        for path, cols in paths_and_columns:
+            if os.path.dirname(path) and not os.path.isdir(os.path.dirname(path)):
+                os.makedirs(os.path.dirname(path))
+            np.ascontiguousarray(cols, dtype=np.float32).tofile(path)
+        return CMP.shape[0]
+
+    def _analysisfid_device(self, fid, wav_path, f0in_path, f0_min, f0_max, outputpathdicts, keys, kwargs):
+        """analysisf_device with the '*' of every path replaced by fid; keys: those of outputpathdicts in the order of ff0, fspec
+        and the streams behind them."""
+        f0_in = None if f0in_path is None else f0in_path.replace('*', fid)
+        fwav = wav_path.replace('*', fid)
+        out = [outputpathdicts[key].replace('*', fid) for key in keys]
+        return self.analysisf_device(fwav, f0_in, out[0], f0_min, f0_max, *out[1:], **kwargs)
+
 
 class VocoderPML(VocoderF0Spec):
     """f0 | spec | noise mask"""
@@ -326,20 +397,9 @@ class VocoderPML(VocoderF0Spec):
         library's generator, so ops.rng_seed makes a waveform reproducible.  Not built: f0 smoothing (`pp_f0_smooth` other than
         None is a ValueError), ener_multT0, nm_cont, pp_atten1stharminsilences."""
         import torch
-        from . import backend_hip, ops
-        if pp_f0_smooth is not None:
-            raise ValueError('pp_f0_smooth={!r}: f0 smoothing is not part of this synthesiser'.format(pp_f0_smooth))
-        if not hasattr(CMP, 'shape') or len(CMP.shape) != 2 or CMP.shape[1] != self.featuressizeraw() or CMP.shape[0] < 1:
-            raise ValueError('synthesis_device: CMP is not [T, {}] with T >= 1'.format(self.featuressizeraw()))
-        ops.pulse_check(self.dftlen, self.fs)
-        x = CMP
-        if not torch.is_tensor(x):
-            x = torch.from_numpy(np.ascontiguousarray(CMP, dtype=np.float32)).to(backend_hip.device())
-        if x.requires_grad:
-            raise ValueError('synthesis_device has no backward pass: detach its input')
-        T = x.shape[0]
+        from . import ops
+        x, T, wavlen = self._synthesis_input(CMP, pp_f0_smooth)
         s1 = 1 + self.spec_size
-        wavlen = int(round(self.shift * (T - 1) * self.fs))
         f0 = torch.exp(x[:, 0]).contiguous()
         table = ops.pulse_table(f0.cpu().numpy(), self.shift, self.fs, wavlen, self.dftlen)
         SPEC = self.decompress_spectrum(x[:, 1:s1].contiguous(), pp_mcep=pp_mcep)
@@ -359,22 +419,8 @@ class VocoderPML(VocoderF0Spec):
         synthesis_device.  Where self.f0_refine is true the track, given or estimated, goes through f0_refine_device first."""
         import torch
         from . import backend_hip, ops_offline as ops
-        if self.spec_type not in ('fwbnd', 'mcep'):
-            raise ValueError("analysis_device: spec_type is 'fwbnd' or 'mcep', got {!r}".format(self.spec_type))
+        wav, f0, track = self._analysis_input(ops.analysis_check, wav, f0, f0_min, f0_max)
         hcap = ops.analysis_check(self.dftlen, self.fs, self.shift, f0_min, f0_max)
-        if self.spec_type == 'fwbnd':
-            ops.fwbnd_compress_check(self.spec_size, self.fs, self.dftlen)
-        else:
-            ops.spec2mcep_check(self.spec_size - 1, bark_alpha(self.fs), self.dftlen)
-        ops.fwbnd_compress_check(self.nm_size, self.fs, self.dftlen)
-        wav = np.asarray(wav, dtype=np.float64)
-        if wav.ndim != 1 or not np.isfinite(wav).all():
-            raise ValueError('analysis_device: wav is not a finite [N] waveform')
-        if f0 is None:
-            f0 = self.f0_estimate_device(wav, f0_min, f0_max)
-        if self.f0_refine:
-            f0 = self.f0_refine_device(wav, f0, f0_min, f0_max)
-        track = ops.f0_track(f0, f0_min, f0_max, self.fs, self.shift, self.dftlen, wavlen=wav.size)
         dev = backend_hip.device()
         w = torch.from_numpy(wav.astype(np.float32)).to(dev)
         f = torch.from_numpy(track).to(dev)
@@ -391,37 +437,18 @@ class VocoderPML(VocoderF0Spec):
         keyword f0_refine (None, True or False) overrides self.f0_refine for this call.  Another fs and any preproc_hp (the other
         keyword taken, None) stay a ValueError here: a file that needs resampling or the high-pass filter goes through preprocwav
         and analysis_device, as run.features_extraction(..., preproc_hp=) does."""
-        if kwargs.get('preproc_hp') is not None:
-            raise ValueError('analysisf_device: preproc_hp={!r}: the high-pass pre-processing is not built'.format(kwargs['preproc_hp']))
-        if set(kwargs) - {'preproc_hp', 'f0_refine'}:
-            raise ValueError('analysisf_device: unknown arguments {}'.format(sorted(set(kwargs) - {'preproc_hp', 'f0_refine'})))
-        _check_f0_refine(kwargs.get('f0_refine'))
-        print('Extracting PML features from: ' + fwav)
-        wav, fs = wavread(fwav)
-        if fs != int(round(self.fs)):
-            raise ValueError('analysisf_device: {} is sampled at {} Hz, the vocoder at {} (resampling is not built)'.format(fwav, fs, self.fs))
-        f0 = np.fromfile(f0_in, dtype=np.float32) if isinstance(f0_in, str) else f0_in
-        with self.f0_refine_as(kwargs.get('f0_refine')):
-            CMP = self.analysis_device(wav, f0, f0_min, f0_max)
-        return self.write_streams(CMP, ff0, fspec, fnm)
+        return self._analysisf_device('PML', fwav, f0_in, f0_min, f0_max, (ff0, fspec, fnm), kwargs)
 
     def write_streams(self, CMP, ff0, fspec, fnm):
         """The parameters [T, featuressizeraw()] of analysis_device -> the three headerless float32 files of analysisf_device: ff0
         gets ln f0, fspec the spectral bands, fnm the noise-mask bands; missing directories are made.  Returns T."""
         s1 = 1 + self.spec_size
-        for path, cols in ((ff0, CMP[:, 0]), (fspec, CMP[:, 1:s1]), (fnm, CMP[:, s1:])):
-            if os.path.dirname(path) and not os.path.isdir(os.path.dirname(path)):
-                os.makedirs(os.path.dirname(path))
-            np.ascontiguousarray(cols, dtype=np.float32).tofile(path)
-        return CMP.shape[0]
+        return self._write_streams(CMP, ((ff0, CMP[:, 0]), (fspec, CMP[:, 1:s1]), (fnm, CMP[:, s1:])))
 
     def analysisfid_device(self, fid, wav_path, f0in_path, f0_min, f0_max, outputpathdicts, **kwargs):
         """analysisf_device with the '*' of every path replaced by the file id, as the reference's analysisfid
         (vocoders.py:191-192); outputpathdicts: {'f0': .., 'spec': .., 'noise': ..}; f0in_path None: the build's own F0 estimate."""
-        f0_in = None if f0in_path is None else f0in_path.replace('*', fid)
-        return self.analysisf_device(wav_path.replace('*', fid), f0_in, outputpathdicts['f0'].replace('*', fid),
-                                     f0_min, f0_max, outputpathdicts['spec'].replace('*', fid),
-                                     outputpathdicts['noise'].replace('*', fid), **kwargs)
+        return self._analysisfid_device(fid, wav_path, f0in_path, f0_min, f0_max, outputpathdicts, ('f0', 'spec', 'noise'), kwargs)
 
 
 class VocoderWORLD(VocoderF0Spec):
@@ -455,20 +482,9 @@ class VocoderWORLDDevice(VocoderWORLD):
         waveform reproducible.  Not built: f0 smoothing (`pp_f0_smooth` other than None is a ValueError, as in the reference's
         WORLD synthesis), WORLD's per-sample spectral interpolation inside a pulse, its safeguards on minimum-phase underflow."""
         import torch
-        from . import backend_hip, ops
-        if pp_f0_smooth is not None:
-            raise ValueError('pp_f0_smooth={!r}: f0 smoothing is not part of this synthesiser'.format(pp_f0_smooth))
-        if not hasattr(CMP, 'shape') or len(CMP.shape) != 2 or CMP.shape[1] != self.featuressizeraw() or CMP.shape[0] < 1:
-            raise ValueError('synthesis_device: CMP is not [T, {}] with T >= 1'.format(self.featuressizeraw()))
-        ops.pulse_check(self.dftlen, self.fs)
-        x = CMP
-        if not torch.is_tensor(x):
-            x = torch.from_numpy(np.ascontiguousarray(CMP, dtype=np.float32)).to(backend_hip.device())
-        if x.requires_grad:
-            raise ValueError('synthesis_device has no backward pass: detach its input')
-        T = x.shape[0]
+        from . import ops
+        x, T, wavlen = self._synthesis_input(CMP, pp_f0_smooth)
         s1 = 1 + self.spec_size
-        wavlen = int(round(self.shift * (T - 1) * self.fs))
         f0 = torch.exp(x[:, 0])
         vuv = x[:, -1].contiguous()
         table = ops.world_pulse_table(f0.cpu().numpy(), vuv.cpu().numpy() >= 0.5, self.shift, self.fs, wavlen, self.dftlen)
@@ -496,23 +512,8 @@ class VocoderWORLDAnalysisDevice(VocoderWORLDDevice):
         statistics, the reference's linbnd2fwbnd of a per-bin aperiodicity (the bands are estimated directly)."""
         import torch
         from . import backend_hip, ops_offline as ops
-        if self.spec_type not in ('fwbnd', 'mcep'):
-            raise ValueError("analysis_device: spec_type is 'fwbnd' or 'mcep', got {!r}".format(self.spec_type))
-        ops.world_analysis_check(self.dftlen, self.fs, self.shift, f0_min, f0_max)
-        if self.spec_type == 'fwbnd':
-            ops.fwbnd_compress_check(self.spec_size, self.fs, self.dftlen)
-        else:
-            ops.spec2mcep_check(self.spec_size - 1, bark_alpha(self.fs), self.dftlen)
-        ops.fwbnd_compress_check(self.aper_size, self.fs, self.dftlen)
-        wav = np.asarray(wav, dtype=np.float64)
-        if wav.ndim != 1 or not np.isfinite(wav).all():
-            raise ValueError('analysis_device: wav is not a finite [N] waveform')
-        if f0 is None:
-            f0 = self.f0_estimate_device(wav, f0_min, f0_max)
-        if self.f0_refine:
-            f0 = self.f0_refine_device(wav, f0, f0_min, f0_max)
-        track = ops.f0_track(f0, f0_min, f0_max, self.fs, self.shift, self.dftlen, wavlen=wav.size)
-        vuv = (np.asarray(f0, dtype=np.float64)[:track.size] > 0).astype(np.float32)
+        wav, f0, track = self._analysis_input(ops.world_analysis_check, wav, f0, f0_min, f0_max)
+        vuv =(np.asarray(f0, dtype=np.float64)[:track.size] > 0).astype(np.float32)
         rate = np.where(vuv > 0, track, np.float32(ops.WORLD_UNVOICED_RATE)).astype(np.float32)
         dev = backend_hip.device()
         w = torch.from_numpy(wav.astype(np.float32)).to(dev)
@@ -531,19 +532,7 @@ class VocoderWORLDAnalysisDevice(VocoderWORLDDevice):
         Another fs and any preproc_hp (the other keyword taken, None) stay a ValueError here, as
         in VocoderPML.analysisf_device: such a file goes through preprocwav and analysis_device, as
         run.features_extraction(..., preproc_hp=) does."""
-        if kwargs.get('preproc_hp') is not None:
-            raise ValueError('analysisf_device: preproc_hp={!r}: the high-pass pre-processing is not built'.format(kwargs['preproc_hp']))
-        if set(kwargs) - {'preproc_hp', 'f0_refine'}:
-            raise ValueError('analysisf_device: unknown arguments {}'.format(sorted(set(kwargs) - {'preproc_hp', 'f0_refine'})))
-        _check_f0_refine(kwargs.get('f0_refine'))
-        print('Extracting WORLD features from: ' + fwav)
-        wav, fs = wavread(fwav)
-        if fs != int(round(self.fs)):
-            raise ValueError('analysisf_device: {} is sampled at {} Hz, the vocoder at {} (resampling is not built)'.format(fwav, fs, self.fs))
-        f0 = np.fromfile(f0_in, dtype=np.float32) if isinstance(f0_in, str) else f0_in
-        with self.f0_refine_as(kwargs.get('f0_refine')):
-            CMP = self.analysis_device(wav, f0, f0_min, f0_max)
-        return self.write_streams(CMP, ff0, fspec, faper, fvuv)
+        return self._analysisf_device('WORLD', fwav, f0_in, f0_min, f0_max, (ff0, fspec, faper, fvuv), kwargs)
 
     def write_streams(self, CMP, ff0, fspec, faper, fvuv):
         """The parameters [T, featuressizeraw()] of analysis_device -> the four headerless float32 files of analysisf_device: ff0
@@ -551,17 +540,10 @@ class VocoderWORLDAnalysisDevice(VocoderWORLDDevice):
         made.  Returns T."""
         s1 = 1 + self.spec_size
         s2 = s1 + self.aper_size
-        for path, cols in ((ff0, CMP[:, 0]), (fspec, CMP[:, 1:s1]), (faper, CMP[:, s1:s2]), (fvuv, CMP[:, s2:])):
-            if os.path.dirname(path) and not os.path.isdir(os.path.dirname(path)):
-                os.makedirs(os.path.dirname(path))
-            np.ascontiguousarray(cols, dtype=np.float32).tofile(path)
-        return CMP.shape[0]
+        return self._write_streams(CMP, ((ff0, CMP[:, 0]), (fspec, CMP[:, 1:s1]), (faper, CMP[:, s1:s2]), (fvuv, CMP[:, s2:])))
 
     def analysisfid_device(self, fid, wav_path, f0in_path, f0_min, f0_max, outputpathdicts, **kwargs):
         """analysisf_device with the '*' of every path replaced by the file id, as the reference's analysisfid
         (vocoders.py:297-298); outputpathdicts: {'f0': .., 'spec': .., 'noise': .., 'vuv': ..}; f0in_path None: the build's own F0
         estimate."""
-        f0_in = None if f0in_path is None else f0in_path.replace('*', fid)
-        return self.analysisf_device(wav_path.replace('*', fid), f0_in, outputpathdicts['f0'].replace('*', fid),
-                                     f0_min, f0_max, outputpathdicts['spec'].replace('*', fid),
-                                     outputpathdicts['noise'].replace('*', fid), outputpathdicts['vuv'].replace('*', fid), **kwargs)
+        return self._analysisfid_device(fid, wav_path, f0in_path, f0_min, f0_max, outputpathdicts, ('f0', 'spec', 'noise', 'vuv'), kwargs)
