@@ -127,6 +127,31 @@ typedef struct ptts_conv2d_reduce_desc {
 int ptts_conv2d_reduce_grouped(const ptts_conv2d_reduce_desc* descs, int n, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The same convolution for the wide and non-square layers -- Cin and Cout each 1 or a multiple of 4 up to 16, KT and KF each
+ * odd in 3 .. 7 and chosen independently, any dilation whose tile fits the LDS -- as implicit GEMMs on the fp32-input matrix
+ * instruction (csrc/conv2d_wide.hip; exact fp32, the tolerances of the fp32 stencil).  Same semantics as ptts_conv2d_fwd /
+ * ptts_conv2d_bwd.  Shapes the packed-FMA stencil or the 4 -> 4 5x5 matrix-core kernels take are NOT supported here.
+ *   ptts_conv2d_wide_supported     1 where the entry points below take the shape; anywhere else they return PTTS_EINVAL and
+ *                                  launch nothing.  x, dy, mask_src, in_scale and in_shift must be 16-byte aligned.
+ *   ptts_conv2d_wide_fwd           y = bias + conv(transform(x), w)
+ *   ptts_conv2d_wide_bwd_partials  dx (NULL to skip; includes lrelu'(p) and scale) and, where want_dw / want_affine, per-workgroup
+ *                                  partial sums as rows [*nblocks_out][*npart_out] at the START of the workspace (no head), a row =
+ *                                  dw (KT*KF*Cin*Cout) | dbias (Cout) | dscale (Cin) | dshift (Cin); columns not asked for are
+ *                                  undefined.  ptts_conv2d_reduce_grouped adds them up.  At most 256 rows in deterministic mode.
+ *   ptts_conv2d_wide_bwd_workspace_bytes   bytes of those rows (0 for an unsupported shape)
+ * ------------------------------------------------------------------------------------- */
+int ptts_conv2d_wide_supported(int F, int Cin, int Cout, int KT, int KF, int dil_t);
+int ptts_conv2d_wide_fwd(const float* x, const float* w, const float* bias, const float* in_scale, const float* in_shift,
+                         const float* mask_src, float* y, int B, int T, int F, int Cin, int Cout, int KT, int KF,
+                         int dil_t, int pad_mode, int in_mode, float alpha, void* stream);
+size_t ptts_conv2d_wide_bwd_workspace_bytes(int B, int T, int F, int Cin, int Cout, int KT, int KF, int dil_t);
+int ptts_conv2d_wide_bwd_partials(const float* dy, const float* x, const float* w, const float* in_scale, const float* in_shift,
+                                  const float* mask_src, float* dx, void* workspace, size_t workspace_bytes,
+                                  int* nblocks_out, int* npart_out, int want_dw, int want_affine,
+                                  int B, int T, int F, int Cin, int Cout, int KT, int KF,
+                                  int dil_t, int pad_mode, int in_mode, float alpha, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * The same convolution for the 4 -> 4 channel, 5x5 layers (the critic's stack, networks_critic.py:66-68, and the
  * generator's, networktts.py:122-126) on the bf16 matrix cores, in fp32 arithmetic: both operands are split three ways
  * into bf16 (x = x1 + x2 + x3 exactly), the six products of order >= 2^-16 are formed by v_mfma_f32_16x16x32_bf16 and

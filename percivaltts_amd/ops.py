@@ -397,9 +397,53 @@ def conv2d_mfma(on):
     _C2M.clear()
 
 
-def conv2d_path_description():
-    return ('4->4 5x5 layers: bf16x6 split on the bf16 matrix cores (fp32 accumulate); 1->4 / 4->1 layers: fp32 packed-FMA stencil'
+class _C2W(object):
+    """The wide and non-square Conv2D layers (8 / 12 / 16 filters, 5x3 or 7x5 windows, the 1 -> C and C -> 1 layers around such a
+    stack) on the fp32-input matrix instructions (csrc/conv2d_wide.hip): exact fp32.  ptts_conv2d_wide_supported decides by shape;
+    PTTS_CONV2D_WIDE=0 or conv2d_wide(False) send those shapes back to the generic kernels of csrc/conv2d.hip."""
+    default = os.environ.get('PTTS_CONV2D_WIDE', '1') == '1'
+    enabled = default
+    shapes = {}         # (F, Cin, Cout, KT, KF, dil_t) -> ptts_conv2d_wide_supported: the layers of the tuned corner ask at every call
+
+    @staticmethod
+    def eligible(x, w, dil_t, *others):
+        """The wide kernels take this layer: the switch, the shape, and 16-byte aligned operands (their float4 loads)."""
+        if not (_C2W.enabled and x.is_cuda):
+            return False
+        KT, KF, Cin, Cout = w.shape
+        key = (x.shape[2], Cin, Cout, KT, KF, dil_t)
+        ok = _C2W.shapes.get(key)
+        if ok is None:
+            ok = _C2W.shapes[key] = bool(_hip.lib().ptts_conv2d_wide_supported(*key))
+        if not ok:
+            return False
+        if x.numel() // Cin * 16 >= 2 ** 31:
+            return False
+        return all(t is None or t.data_ptr() % 16 == 0 for t in (x,) + others)
+
+
+def conv2d_wide(on):
+    """Switch the wide / non-square Conv2D kernels on or off (None: the default)."""
+    _C2W.enabled = _C2W.default if on is None else bool(on)
+
+
+def conv2d_path_description(shape=None):
+    """The kernels the Conv2D layers take.  shape = (F, Cin, Cout, KT, KF[, dil_t]): the tier of that one layer."""
+    if shape is not None:
+        F, Cin, Cout, KT, KF = shape[:5]
+        dil_t = shape[5] if len(shape) > 5 else 1
+        if _C2M.enabled and (Cin, Cout, KT, KF) == (4, 4, 5, 5) and dil_t in (1, 2, 4, 8):
+            return 'bf16x6 split on the bf16 matrix cores (csrc/conv2d_mfma.hip)'
+        if _C2W.enabled and _hip.lib().ptts_conv2d_wide_supported(F, Cin, Cout, KT, KF, dil_t):
+            return 'fp32 matrix-core implicit GEMM (csrc/conv2d_wide.hip)'
+        if Cin in (1, 2, 4) and Cout in (1, 2, 4) and KT == KF and KT in (3, 5):
+            return 'fp32 packed-FMA stencil (csrc/conv2d.hip)'
+        return 'generic fp32 kernels (csrc/conv2d.hip)'
+    base = ('4->4 5x5 layers: bf16x6 split on the bf16 matrix cores (fp32 accumulate); 1->4 / 4->1 layers: fp32 packed-FMA stencil'
             if _C2M.enabled else 'fp32 packed-FMA stencil')
+    wide = ('; wide / non-square layers (1 or 4..16 channels, odd windows 3..7): fp32 matrix-core implicit GEMM' if _C2W.enabled
+            else '; wide / non-square layers: generic fp32 kernels')
+    return base + wide
 
 
 def _is16(t):
@@ -530,6 +574,10 @@ def _conv2d_fwd_raw(x, w, b, scale, shift, mask_src, mode, alpha, dil_t, pad_mod
         return _conv2d_mfma_fwd(x, w, _C2M.table(w, False), b, scale, shift, mask_src, None, mode, alpha, dil_t,
                                 _C2M.pad_t(dil_t, pad_mode))
     y = torch.empty((B, T, F, Cout), dtype=torch.float32, device=x.device)
+    if _C2W.eligible(x, w, dil_t, scale, shift, mask_src):
+        call('ptts_conv2d_wide_fwd', ptr(x), ptr(w), ptr(b), ptr(scale), ptr(shift), ptr(mask_src), ptr(y),
+             B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha, stream(), tag=(B, T, F, Cin, Cout, mode))
+        return y
     call('ptts_conv2d_fwd', ptr(x), ptr(w), ptr(b), ptr(scale), ptr(shift), ptr(mask_src), ptr(y),
          B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha, stream(), tag=(B, T, F, Cin, Cout, mode))
     return y
@@ -553,6 +601,24 @@ def _conv2d_mfma_bwd(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_dx, 
         if want_rows:
             buf, nblocks, npart = _conv2d_mfma_wgrad(dy, x, mask_src, mode, alpha, dil_t, pad_t, planes)
     return dx, ((buf, 4096, nblocks, npart, w.numel(), w.shape[3]) if want_rows else None)
+
+
+def _conv2d_wide_bwd(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_rows, want_affine):
+    """The wide kernels' backward: dx (or None) and the partial rows dw | dbias | dscale | dshift of the pass as
+    (buffer, nblocks, npart); the rows start at the buffer's first byte.  (None, 0, npart) where no sums are wanted."""
+    B, T, F, Cin = x.shape
+    KT, KF, _, Cout = w.shape
+    dx = torch.empty_like(x) if want_dx else None
+    buf = None
+    if want_rows or want_affine:
+        nws = _hip.lib().ptts_conv2d_wide_bwd_workspace_bytes(B, T, F, Cin, Cout, KT, KF, dil_t)
+        buf = torch.empty(int(nws), dtype=torch.uint8, device=x.device)
+    nblocks, npart = ctypes.c_int(0), ctypes.c_int(0)
+    call('ptts_conv2d_wide_bwd_partials', ptr(dy), ptr(x), ptr(w), ptr(scale), ptr(shift), ptr(mask_src), ptr(dx), ptr(buf),
+         0 if buf is None else buf.numel(), ctypes.byref(nblocks), ctypes.byref(npart), int(want_rows), int(want_affine),
+         B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha, stream(),
+         tag=(B, T, F, Cin, Cout, mode, int(want_dx), int(want_rows), int(want_affine)))
+    return dx, buf, nblocks.value, npart.value
 
 
 def _conv2d_bwd_raw(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode,
@@ -594,6 +660,22 @@ def _conv2d_bwd_raw(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mo
         if passes:
             _conv2d_reduce(passes)
         return dx, dw, db, (daff[:Cin] if want_affine else None), (daff[Cin:] if want_affine else None)
+    if planes == 3 and _C2W.eligible(x, w, dil_t, dy, scale, shift, mask_src):
+        # fp32 matrix-core kernels; the partial rows (dw | dbias | dscale | dshift) are reduced at once into fresh tensors
+        dx, buf, nblocks, npart = _conv2d_wide_bwd(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode,
+                                                   want_dx, want_dw or want_db, want_affine)
+        nw = KT * KF * Cin * Cout
+        dw = torch.zeros_like(w) if want_dw else None
+        db = torch.zeros(Cout, dtype=torch.float32, device=dev) if want_db else None
+        daff = torch.zeros(2 * Cin, dtype=torch.float32, device=dev) if want_affine else None
+        passes = []
+        if want_dw or want_db:
+            passes.append((buf, 0, nblocks, npart, nw, Cout, dw, db))
+        if want_affine:
+            passes.append((buf, 4 * (nw + Cout), nblocks, npart, Cin, Cin, daff[:Cin], daff[Cin:]))
+        if passes:
+            _conv2d_reduce(passes)
+        return dx, dw, db, (daff[:Cin] if want_affine else None), (daff[Cin:] if want_affine else None)
     dx = torch.empty_like(x) if want_dx else None
     dw = torch.empty_like(w) if (want_dw or want_db) else None
     db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_db else None
@@ -611,12 +693,16 @@ def _conv2d_bwd_raw(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mo
 def _conv2d_bwd_deferred(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_dx, gw, gb, planes=3):
     """conv2d backward whose dw / dbias stay as per-workgroup partial sums in a buffer of their own; the reduction into
     the gradient buffers gw / gb is queued for the grouped launch at flush time.  Returns dx (or None), or False when
-    this shape has no tiled kernel."""
+    neither the stencil nor the wide tier has a tiled kernel for this shape."""
     B, T, F, Cin = x.shape
     KT, KF, _, Cout = w.shape
     if (planes == 1 or _C2M.enabled) and _C2M.eligible(x, w, dil_t) and 0.0 <= alpha <= 1.0:
         dx, rows = _conv2d_mfma_bwd(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_dx, True, planes)
         _Deferred.queue_conv(rows + (gw, gb))
+        return dx
+    if planes == 3 and _C2W.eligible(x, w, dil_t, dy, mask_src):
+        dx, buf, nblocks, npart = _conv2d_wide_bwd(dy, x, w, None, None, mask_src, mode, alpha, dil_t, pad_mode, want_dx, True, False)
+        _Deferred.queue_conv((buf, 0, nblocks, npart, KT * KF * Cin * Cout, Cout, gw, gb))
         return dx
     nws = _hip.lib().ptts_conv2d_bwd_workspace_bytes(B, T, F, Cin, Cout, KT, KF, dil_t)
     if nws <= 16:
