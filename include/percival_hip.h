@@ -806,6 +806,40 @@ int ptts_world_segments(const float* spec, const float* aper, const float* noise
                         int dftlen, double fs, long long wavlen, float* seg, int W, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The pulse table of the two synthesisers on the device, for a batch of utterances (csrc/pulsetable.hip;
+ * the definition is ops.pulse_table's and ops.world_pulse_table's, DESIGN.md section 3, reproduced bit
+ * for bit: fp64, no contraction).  B utterances are packed one after the other: f0 [sum T] in Hz,
+ * voiced [sum T] bytes (NULL: the PML form, otherwise the WORLD form), offs [2][B+1] int64 with the
+ * utterances' first frames in row 0 and first samples in row 1 (wavlen_b = round(shift (T_b - 1) fs),
+ * computed by the caller).  cap: pulse slots per utterance.
+ *
+ * ptts_pulse_walk: one wave per utterance; t [B][cap] gets t_0 = 0, t_{n+1} = t_n + 1 / rate(t_n) while
+ *   t_n < wavlen_b / fs; info [B][4] int32 gets the pulse count (<= cap), the largest winlen, the walk's
+ *   status bits and a zero for ptts_pulse_rows.  An utterance that sets a bit is not walked further.
+ * ptts_pulse_rows: one lane per pulse; P = the sum of the counts, known on the device only.  itab_rel
+ *   and itab_off get the int32 rows start, winlen, lb, rb, fr (WORLD: i0, i1, v) at [row * P + pulse],
+ *   relative to the own utterance and offset into the packed frames / samples (there winlen = 0 for
+ *   the pulse of an utterance with wavlen_b = 0); dtab the fp64 rows delay, f0 (WORLD: w).  The three
+ *   buffers hold 5 (8), 5 (8) and 2 (3) times B * cap values.  pulse_off [B+1] gets the utterances'
+ *   first pulses; info[b][3] the rows' status bits.  An utterance the walk refused gets no rows.
+ * ptts_pulse_overlap_add_batch: ptts_pulse_overlap_add over packed utterances; a sample sums the
+ *   pulses of its own utterance (pulse_off, samp_off [B+1]), start ascending within each.
+ * ------------------------------------------------------------------------------------- */
+#define PTTS_PULSE_BAD_F0 1          /* f0 not finite or not positive */
+#define PTTS_PULSE_WINDOW 2          /* a window does not fit dftlen */
+#define PTTS_PULSE_TOO_MANY 4        /* more than cap pulses */
+#define PTTS_PULSE_RATE 8            /* a rate above f0_cap */
+#define PTTS_PULSE_DESCENDING 16     /* starts not ascending */
+#define PTTS_PULSE_SEGMENT 32        /* a noise segment outside the waveform or its pulse's frame */
+#define PTTS_PULSE_START_RANGE 64    /* |start| >= 2^30 */
+int ptts_pulse_walk(const float* f0, const unsigned char* voiced, const long long* offs, int B, double shift, double fs, int dftlen,
+                    int cap, double f0_cap, double* t, int* info, void* stream);
+int ptts_pulse_rows(const float* f0, const unsigned char* voiced, const long long* offs, int B, double shift, double fs, int dftlen,
+                    int cap, const double* t, int* info, int* pulse_off, int* itab_rel, int* itab_off, double* dtab, void* stream);
+int ptts_pulse_overlap_add_batch(const float* seg, const int* itab, const int* pulse_off, const long long* samp_off, int B, int P,
+                                 int W, float* wav, long long wavlen, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Waveform analysis for the PML parameters (csrc/analysis.hip; the counterpart of the synthesis
  * above, the definition is this build's own).  L = dftlen, K = L/2 + 1,
  * rnd(x) = floor(x + 0.5).  fp32 in memory, fp64 arithmetic, every integer decision in fp64.

@@ -120,6 +120,13 @@ class ModelTTS:
         out = ops.mlpg(torch.from_numpy(np.ascontiguousarray(CMP)).to(dev), self.vocoder.mlpg_wins, std * std, mean=mean, std=std)
         return out.cpu().numpy()
 
+    def _synthesise(self, CMPs, pp_mcep):
+        """The waveforms of one batch's generated parameters (device tensors): one synthesis_device_batch call where the vocoder
+        has it, its synthesis_device utterance by utterance otherwise.  The two give the same bytes."""
+        if hasattr(self.vocoder, 'synthesis_device_batch'):
+            return self.vocoder.synthesis_device_batch(CMPs, pp_mcep=pp_mcep)
+        return [self.vocoder.synthesis_device(c, pp_mcep=pp_mcep) for c in CMPs]
+
     def generate_params(self, inpath, outpath, fid_lst, gendir, do_objmeas=True, batch_size=8, pp_mcep=False, specdir=None,
                         wavdir=None):
         """The reference's generate_wav (modeltts.py:144-205) up to the vocoder call: read mean4norm.dat / std4norm.dat beside
@@ -139,7 +146,8 @@ class ModelTTS:
         the envelope a waveform generator reads.  The .cmp files and the measures are what they are without it (the reference,
         too, measures before the post-filter); without `specdir` no spectrum kernel is launched.
 
-        With `wavdir` each utterance's generated parameters also go through the vocoder's synthesis_device(pp_mcep=pp_mcep) while
+        With `wavdir` each batch's generated parameters also go through the vocoder's synthesis_device_batch(pp_mcep=pp_mcep), or
+        utterance by utterance through its synthesis_device where it has no batched form (the files are the same either way), while
         they are on the device (csrc/pulsesynth.hip for VocoderPML, csrc/worldsynth.hip for VocoderWORLDDevice) and `wavdir/<fid>.wav` is written as 16-bit PCM at the vocoder's fs; the noise
         comes from the library's generator (ops.rng_seed).  The .cmp and .spec files are what they are without it.  A vocoder
         without synthesis_device (VocoderWORLD itself among them) is a ValueError."""
@@ -195,7 +203,7 @@ class ModelTTS:
                 if specdir is not None:
                     specs = [self.vocoder.decompress_spectrum(gen[i, :lens[i], s0:s1], pp_mcep=pp_mcep) for i in range(len(ys))]
                 if wavdir is not None:
-                    wavs = [self.vocoder.synthesis_device(gen[i, :lens[i]], pp_mcep=pp_mcep) for i in range(len(ys))]
+                    wavs = self._synthesise([gen[i, :lens[i]] for i in range(len(ys))], pp_mcep)
                 gen = gen.cpu().numpy()
                 CMPs = [gen[i, :lens[i]] for i in range(len(ys))]
             else:
@@ -204,8 +212,8 @@ class ModelTTS:
                     specs = [self.vocoder.decompress_spectrum(torch.from_numpy(np.ascontiguousarray(c[:, s0:s1])).to(self.to_device()),
                                                               pp_mcep=pp_mcep) for c in CMPs]
                 if wavdir is not None:
-                    wavs = [self.vocoder.synthesis_device(torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)).to(self.to_device()),
-                                                          pp_mcep=pp_mcep) for c in CMPs]
+                    wavs = self._synthesise([torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)).to(self.to_device()) for c in CMPs],
+                                            pp_mcep)
             if specdir is not None:
                 for vi, spec in zip(vis, specs):
                     spec.cpu().numpy().tofile(os.path.join(specdir, fid_lst[vi] + '.spec'))

@@ -1,5 +1,6 @@
 """Wrappers of the offline pipeline over the HIP kernels of libpercival_hip.so: parameter generation (MLPG), feature
-composition, spectral envelope decompression, pulse-and-noise synthesis (PML) and periodic-plus-aperiodic synthesis (WORLD), waveform analysis (PML and WORLD), F0 estimation, waveform pre-processing and the label front end.
+composition, spectral envelope decompression, pulse-and-noise synthesis (PML) and periodic-plus-aperiodic synthesis (WORLD), each per
+utterance with a host pulse table or over a batch with the table built on the device, waveform analysis (PML and WORLD), F0 estimation, waveform pre-processing and the label front end.
 
 Argument checks, scratch memory and one C-ABI call (include/percival_hip.h) each; no autograd nodes, no switches, nothing
 of the training path (ops.py, which re-exports the names of __all__).  There is no CPU path.
@@ -22,6 +23,8 @@ __all__ = [
     'PULSE_MIN_DFTLEN', 'PULSE_MAX_DFTLEN', 'PULSE_F0_FLOOR', 'PULSE_INT_ROWS', 'pulse_check', 'pulse_table', 'noise_mask',
     'pulse_synthesis',
     'WORLD_UNVOICED_RATE', 'WORLD_INT_ROWS', 'world_pulse_table', 'aper_rows', 'world_synthesis',
+    'PULSE_F0_CAP', 'PULSE_MAX_UTTS', 'pulse_table_cap', 'PulseTableDevice', 'pulse_table_device', 'pulse_synthesis_batch',
+    'world_synthesis_batch',
     'COMPRESS_MEAN', 'COMPRESS_LSQ', 'ANALYSIS_NOISY_BELOW', 'analysis_check', 'f0_track', 'frame_harmonics', 'phase_coherence',
     'fwbnd_compress_check', 'fwbnd_compress',
     'world_analysis_check', 'world_envelope', 'world_aperiodicity',
@@ -626,6 +629,185 @@ def world_synthesis(spec, aper, table, noise, fs, dftlen, wavlen):
             raise ValueError('ops.world_synthesis: the frames i0 / i1 or the weight w of the table are outside the {} frames given'.format(T))
     return _segments_synthesis('world_synthesis', 'ptts_world_segments', 'world_pulse_table', WORLD_INT_ROWS, ('delay', 'f0', 'w'), spec, aper,
                                'aper', table, noise, fs, dftlen, wavlen, frames_and_weight)
+
+
+# ----------------------------------------------------------------------------------------------
+# the pulse table on the device and both synthesisers over a batch of utterances: csrc/pulsetable.hip
+# ----------------------------------------------------------------------------------------------
+PULSE_F0_CAP = 1000.0               # the default f0_cap of pulse_table_device
+PULSE_MAX_UTTS = 65535              # utterances of one launch
+# (status bit of include/percival_hip.h, what the ValueError says); the first four are set by the walk, the others by the rows
+_PULSE_STATUS = tuple((_hip._define('PTTS_PULSE_' + name), text) for name, text in (
+    ('BAD_F0', 'f0 has to be [T] positive finite Hz values'),
+    ('WINDOW', 'the window of a pulse ({maxwin} samples) does not fit dftlen={dftlen}'),
+    ('TOO_MANY', 'more than cap={cap} pulses'),
+    ('RATE', 'a rate above f0_cap={f0_cap} Hz'),
+    ('DESCENDING', 'the pulses\' start samples have to ascend (f0 falls too fast between two pulses)'),
+    ('SEGMENT', 'a noise segment lies outside the waveform or its pulse\'s frame'),
+    ('START_RANGE', 'a start sample exceeds the int32 table')))
+
+
+def pulse_table_cap(T_max, shift, f0_cap=PULSE_F0_CAP):
+    """Pulse slots per utterance of pulse_table_device: ceil(shift (T_max - 1) max(f0_cap, WORLD_UNVOICED_RATE)) + 2.  Touches no
+    device."""
+    if int(T_max) != T_max or T_max < 1 or not 0.0 < float(shift) < 1e3 or not 0.0 < float(f0_cap) < 1e9:
+        raise ValueError('ops.pulse_table_cap: T_max={} shift={} f0_cap={}'.format(T_max, shift, f0_cap))
+    return int(math.ceil(float(shift) * (int(T_max) - 1) * max(float(f0_cap), WORLD_UNVOICED_RATE))) + 2
+
+
+def _pulse_batch_layout(fn, lengths, shift, fs, dftlen, f0_cap):
+    """The checks of pulse_table_device that need no device -> (lengths, wavlens, frame_off, sample_off, cap)."""
+    pulse_check(dftlen, fs)
+    try:
+        lengths = [int(n) for n in lengths]
+    except (TypeError, ValueError):
+        raise ValueError('ops.{}: lengths has to be the utterances\' frame counts'.format(fn))
+    if not 1 <= len(lengths) <= PULSE_MAX_UTTS or min(lengths) < 1:
+        raise ValueError('ops.{}: lengths has to hold 1 to {} frame counts of at least 1'.format(fn, PULSE_MAX_UTTS))
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('ops.{}: shift={}'.format(fn, shift))
+    if not 0.0 < float(f0_cap) < 1e9:
+        raise ValueError('ops.{}: f0_cap={} has to be positive'.format(fn, f0_cap))
+    fs, shift = float(fs), float(shift)
+    wavlens = [int(round(shift * (T - 1) * fs)) for T in lengths]
+    frame_off = np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)])
+    sample_off = np.concatenate([[0], np.cumsum(wavlens, dtype=np.int64)])
+    cap = pulse_table_cap(max(lengths), shift, f0_cap)
+    if frame_off[-1] >= 1 << 30 or sample_off[-1] >= 1 << 30 or cap * len(lengths) >= 1 << 28:
+        raise ValueError('ops.{}: {} frames, {} samples or {} pulse slots exceed the int32 tables'.format(
+            fn, frame_off[-1], sample_off[-1], cap * len(lengths)))
+    return lengths, wavlens, frame_off, sample_off, cap
+
+
+class PulseTableDevice(object):
+    """What pulse_table_device returns.  On the device: t [B,cap] fp64 (utterance b's pulse times in t[b, :counts[b]]); itab
+    [5,P] or [8,P] int32 and dtab [2,P] or [3,P] fp64, the rows of ops.pulse_table / ops.world_pulse_table with all utterances one
+    after the other along P, every value relative to its own utterance; itab_packed, the same with fr / i0 / i1 shifted by the
+    utterance's first frame and start / lb / rb by its first sample, which the segment kernels read on packed buffers (winlen is 0
+    there for the one pulse of an utterance without samples); offs [2,B+1] int64 and pulse_off_dev [B+1] int32.  On the host:
+    world, lengths, wavlens, counts, pulse_off, frame_off, sample_off (numpy int64, offsets [B+1]), P, W (the largest winlen), cap,
+    shift, fs, dftlen."""
+
+    def rows(self, b):
+        """Utterance b's table as the dict of numpy arrays that ops.pulse_table / ops.world_pulse_table return."""
+        if not 0 <= b < len(self.lengths):
+            raise IndexError('utterance {} of {}'.format(b, len(self.lengths)))
+        p0, p1 = int(self.pulse_off[b]), int(self.pulse_off[b + 1])
+        itab, dtab = self.itab[:, p0:p1].cpu().numpy(), self.dtab[:, p0:p1].cpu().numpy()
+        tab = {'t': self.t[b, :p1 - p0].cpu().numpy()}
+        for key, row in zip(('delay', 'f0', 'w') if self.world else ('delay', 'f0'), dtab):
+            tab[key] = np.ascontiguousarray(row)
+        for key, row in zip(WORLD_INT_ROWS if self.world else PULSE_INT_ROWS, itab):
+            tab[key] = np.ascontiguousarray(row)
+        return tab
+
+
+def pulse_table_device(f0, lengths, shift, fs, dftlen, voiced=None, f0_cap=PULSE_F0_CAP):
+    """ops.pulse_table, or with `voiced` ops.world_pulse_table, of a batch of utterances, built by two kernels
+    (csrc/pulsetable.hip) and bit for bit the host's: f0 [sum T] fp32 device in Hz, the utterances one after the other, lengths
+    their frame counts T_b (wavlen_b = round(shift (T_b - 1) fs)), voiced [sum T] bool or uint8 device.  One wave per utterance
+    walks t_{n+1} = t_n + 1 / rate(t_n), one lane per pulse fills the rows; the host reads the counts, the largest window and the
+    status words back once and does nothing per pulse.  Returns a PulseTableDevice.
+
+    f0_cap bounds the table's memory: an utterance gets cap = ops.pulse_table_cap(max T, shift, f0_cap) pulse slots, and a
+    voiced rate above f0_cap is refused.  The default, 1000 Hz, lies above any f0_max a vocoder of this build is configured with.
+
+    What ops.pulse_table refuses is a ValueError here too, raised after the read-back; it names the utterance's index in the
+    batch.  Nothing of such a batch is to be synthesised."""
+    fn = 'pulse_table_device'
+    lengths, wavlens, frame_off, sample_off, cap = _pulse_batch_layout(fn, lengths, shift, fs, dftlen, f0_cap)
+    B, total = len(lengths), int(frame_off[-1])
+    f32c(f0, fn + '.f0')
+    if tuple(f0.shape) != (total,):
+        raise ValueError('ops.{}: f0 {} is not [sum(lengths)={}]'.format(fn, tuple(f0.shape), total))
+    _no_backward(fn, f0)
+    world = voiced is not None
+    if world:
+        if not (torch.is_tensor(voiced) and voiced.is_cuda and voiced.dtype in (torch.bool, torch.uint8) and voiced.is_contiguous()):
+            raise _hip.HipLibraryError('{}.voiced: expected a contiguous bool or uint8 device tensor'.format(fn))
+        if tuple(voiced.shape) != (total,):
+            raise ValueError('ops.{}: voiced {} is not [sum(lengths)={}]'.format(fn, tuple(voiced.shape), total))
+    dev = f0.device
+    ni, nd = (len(WORLD_INT_ROWS), 3) if world else (len(PULSE_INT_ROWS), 2)
+    tab = PulseTableDevice()
+    tab.world, tab.lengths, tab.wavlens, tab.frame_off, tab.sample_off = world, lengths, wavlens, frame_off, sample_off
+    tab.cap, tab.shift, tab.fs, tab.dftlen = cap, float(shift), float(fs), int(dftlen)
+    tab.offs = torch.from_numpy(np.stack([frame_off, sample_off])).to(dev)
+    tab.t = torch.empty((B, cap), dtype=torch.float64, device=dev)
+    tab.pulse_off_dev = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    irel = torch.empty(ni * B * cap, dtype=torch.int32, device=dev)
+    ioff = torch.empty(ni * B * cap, dtype=torch.int32, device=dev)
+    dbl = torch.empty(nd * B * cap, dtype=torch.float64, device=dev)
+    args = (ptr(f0), ptr(voiced), ptr(tab.offs), B, tab.shift, tab.fs, tab.dftlen, cap)
+    call('ptts_pulse_walk', *args, float(f0_cap), ptr(tab.t), ptr(info), stream(), tag=(B, total, cap))
+    call('ptts_pulse_rows', *args, ptr(tab.t), ptr(info), ptr(tab.pulse_off_dev), ptr(irel), ptr(ioff), ptr(dbl), stream(),
+         tag=(B, cap))
+    info = info.cpu().numpy()
+    for b in range(B):
+        for bit, text in _PULSE_STATUS:
+            if (info[b, 2] | info[b, 3]) & bit:
+                raise ValueError('ops.{}: utterance {}: {}'.format(fn, b, text.format(maxwin=info[b, 1], dftlen=dftlen, cap=cap,
+                                                                                      f0_cap=f0_cap)))
+    tab.counts = info[:, 0].astype(np.int64)
+    tab.pulse_off = np.concatenate([[0], np.cumsum(tab.counts)])
+    tab.P, tab.W = int(tab.pulse_off[-1]), int(info[:, 1].max())
+    P = tab.P
+    tab.itab, tab.itab_packed, tab.dtab = irel[:ni * P].view(ni, P), ioff[:ni * P].view(ni, P), dbl[:nd * P].view(nd, P)
+    return tab
+
+
+def _segments_synthesis_batch(fn, segments, world, spec, rows, rows_name, table, noise, fs, dftlen):
+    """ops.pulse_synthesis_batch and ops.world_synthesis_batch: the argument checks of _segments_synthesis, the kernel `segments`
+    once over all pulses of the batch on the packed rows, then the overlap-add over the packed waveform."""
+    pulse_check(dftlen, fs)
+    K = dftlen // 2 + 1
+    if not isinstance(table, PulseTableDevice) or table.world != world:
+        raise ValueError('ops.{}: table is what ops.pulse_table_device returns {} voiced'.format(fn, 'with' if world else 'without'))
+    if table.dftlen != int(dftlen) or table.fs != float(fs):
+        raise ValueError('ops.{}: the table was built for fs={} dftlen={}'.format(fn, table.fs, table.dftlen))
+    T, total, B = int(table.frame_off[-1]), int(table.sample_off[-1]), len(table.lengths)
+    if not torch.is_tensor(spec) or tuple(spec.shape) != (T, K):
+        raise ValueError('ops.{}: spec is not [sum T={},{}]'.format(fn, T, K))
+    if not torch.is_tensor(rows) or tuple(rows.shape) != (T, K):
+        raise ValueError('ops.{}: {} is not [{},{}]'.format(fn, rows_name, T, K))
+    if torch.is_tensor(noise):
+        if tuple(noise.shape) != (total,):
+            raise ValueError('ops.{}: noise is not [sum wavlen={}]'.format(fn, total))
+        pieces = [noise]
+    else:
+        pieces = list(noise)
+        if len(pieces) != B or any(not torch.is_tensor(g) or tuple(g.shape) != (n,) for g, n in zip(pieces, table.wavlens)):
+            raise ValueError('ops.{}: noise is not one [wavlen] tensor per utterance, wavlen = {}'.format(fn, table.wavlens))
+    _no_backward(fn, spec, rows, *pieces)
+    f32c(spec, '{}.spec'.format(fn)); f32c(rows, '{}.{}'.format(fn, rows_name))
+    for g in pieces:
+        f32c(g, '{}.noise'.format(fn))
+    wav = torch.empty(total, dtype=torch.float32, device=spec.device)
+    if total > 0:
+        noise = pieces[0] if len(pieces) == 1 else torch.cat(pieces)
+        P, W = table.P, table.W
+        seg = torch.empty((P, W), dtype=torch.float32, device=spec.device)
+        call(segments, ptr(spec), ptr(rows), ptr(noise), ptr(table.itab_packed), ptr(table.dtab), P, T, int(dftlen), float(fs), total,
+             ptr(seg), W, stream(), tag=(P, dftlen, W))
+        call('ptts_pulse_overlap_add_batch', ptr(seg), ptr(table.itab_packed), ptr(table.pulse_off_dev), ptr(table.offs[1]), B, P, W,
+             ptr(wav), total, stream(), tag=(B, P, W, total))
+    return list(wav.split(table.wavlens))
+
+
+def pulse_synthesis_batch(spec, mask, table, noise, fs, dftlen):
+    """ops.pulse_synthesis of a batch of utterances in one launch per kernel: spec and mask [sum T, dftlen/2+1] fp32 device, the
+    utterances' rows one after the other, table from ops.pulse_table_device(f0, lengths, ...), noise a list of [wavlen_b] N(0,1)
+    fp32 device tensors or one packed [sum wavlen] tensor.  Returns the list of [wavlen_b] fp32 device waveforms (views of one
+    buffer), each byte for byte what ops.pulse_synthesis gives for that utterance alone; an utterance of one frame yields an empty
+    tensor and no pulse work."""
+    return _segments_synthesis_batch('pulse_synthesis_batch', 'ptts_pulse_segments', False, spec, mask, 'mask', table, noise, fs, dftlen)
+
+
+def world_synthesis_batch(spec, aper, table, noise, fs, dftlen):
+    """ops.world_synthesis of a batch of utterances in one launch per kernel: as ops.pulse_synthesis_batch, with aper
+    (ops.aper_rows of the packed rows) and a table from ops.pulse_table_device(..., voiced=...)."""
+    return _segments_synthesis_batch('world_synthesis_batch', 'ptts_world_segments', True, spec, aper, 'aper', table, noise, fs, dftlen)
 
 
 # ----------------------------------------------------------------------------------------------

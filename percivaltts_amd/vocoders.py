@@ -319,6 +319,40 @@ class VocoderF0Spec(Vocoder):
         T = x.shape[0]
         return x, T, int(round(self.shift * (T - 1) * self.fs))
 
+    def _synthesis_batch_input(self, CMPs, noise):
+        """The checks of a synthesis_device_batch -> (the utterances' rows packed into one device tensor [sum T, raw], their
+        lengths, their wavlens, the noise as a list with one entry per utterance: the caller's tensors, or None to draw)."""
+        import torch
+        from . import backend_hip, ops
+        CMPs = list(CMPs)
+        if not CMPs:
+            raise ValueError('synthesis_device_batch: no utterance given')
+        for c in CMPs:
+            if not hasattr(c, 'shape') or len(c.shape) != 2 or c.shape[1] != self.featuressizeraw() or c.shape[0] < 1:
+                raise ValueError('synthesis_device_batch: a CMP is not [T, {}] with T >= 1'.format(self.featuressizeraw()))
+            if torch.is_tensor(c) and c.requires_grad:
+                raise ValueError('synthesis_device_batch has no backward pass: detach its input')
+        ops.pulse_check(self.dftlen, self.fs)
+        noise = [None] * len(CMPs) if noise is None else list(noise)
+        if len(noise) != len(CMPs):
+            raise ValueError('synthesis_device_batch: noise is not one [wavlen] tensor per utterance')
+        if not any(torch.is_tensor(c) for c in CMPs):
+            x = torch.from_numpy(np.concatenate([np.asarray(c, dtype=np.float32) for c in CMPs])).to(backend_hip.device())
+        else:
+            dev = next(c.device for c in CMPs if torch.is_tensor(c))
+            x = torch.cat([c.to(torch.float32) if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)).to(dev)
+                           for c in CMPs])
+        lengths = [int(c.shape[0]) for c in CMPs]
+        wavlens = [int(round(self.shift * (T - 1) * self.fs)) for T in lengths]
+        return x, lengths, wavlens, noise
+
+    @staticmethod
+    def _draw_noise(noise, wavlens, device):
+        """Every missing entry drawn by its own ops.normal call, in utterance order: the generator's call counter advances as
+        under a loop of synthesis_device calls."""
+        from . import ops
+        return [ops.normal((n,), device=device, i0=0) if g is None else g for g, n in zip(noise, wavlens)]
+
     def _analysis_input(self, check, wav, f0, f0_min, f0_max):
         """The checks of an analysis_device (check: ops.analysis_check or ops.world_analysis_check) and its F0 steps -> (wav as
         float64, f0 as given, estimated or refined, the continuous track of ops.f0_track)."""
@@ -408,6 +442,26 @@ class VocoderPML(VocoderF0Spec):
             noise = ops.normal((wavlen,), device=x.device, i0=0)
         return ops.pulse_synthesis(SPEC, mask, table, noise, self.fs, self.dftlen, wavlen).cpu().numpy()
 
+    def synthesis_device_batch(self, CMPs, pp_mcep=False, noise=None):
+        """synthesis_device over a list of utterances, [T_b, featuressizeraw()] each (numpy or device tensors) -> the list of their
+        waveforms, numpy float32, each byte for byte what synthesis_device gives for that utterance alone.  The rows are packed
+        once; exp(lf0), decompress_spectrum and the noise mask run once over the packed rows, the pulse table is built on the
+        device (ops.pulse_table_device: no f0 comes back to the host, no loop over the pulses), and the segments and the
+        overlap-add are one launch each for the whole batch (ops.pulse_synthesis_batch).  `noise`: a list with one [wavlen_b] fp32
+        device tensor per utterance; None draws each utterance's by its own call of the library's generator, in utterance order,
+        as a loop of synthesis_device calls would (so, as there, an utterance of one frame, which has no samples, needs its empty
+        noise given: the generator draws no empty tensor).  An f0 above ops.PULSE_F0_CAP is a ValueError."""
+        import torch
+        from . import ops
+        x, lengths, wavlens, noise = self._synthesis_batch_input(CMPs, noise)
+        s1 = 1 + self.spec_size
+        f0 = torch.exp(x[:, 0]).contiguous()
+        table = ops.pulse_table_device(f0, lengths, self.shift, self.fs, self.dftlen)
+        SPEC = self.decompress_spectrum(x[:, 1:s1].contiguous(), pp_mcep=pp_mcep)
+        mask = ops.noise_mask(x[:, s1:s1 + self.nm_size].contiguous(), f0, self.fs, self.dftlen)
+        noise = self._draw_noise(noise, wavlens, x.device)
+        return [w.cpu().numpy() for w in ops.pulse_synthesis_batch(SPEC, mask, table, noise, self.fs, self.dftlen)]
+
     def analysis_device(self, wav, f0, f0_min, f0_max):
         """A mono waveform at self.fs (any float array) and an F0 track in Hz, one value per frame at shift * i (<= 0: unvoiced;
         None: the track of f0_estimate_device) -> the parameters [T, featuressizeraw()] float32, columns ln f0 | spec bands or
@@ -493,6 +547,23 @@ class VocoderWORLDDevice(VocoderWORLD):
         if noise is None:
             noise = ops.normal((wavlen,), device=x.device, i0=0)
         return ops.world_synthesis(SPEC, aper, table, noise, self.fs, self.dftlen, wavlen).cpu().numpy()
+
+    def synthesis_device_batch(self, CMPs, pp_mcep=False, noise=None):
+        """synthesis_device over a list of utterances, [T_b, featuressizeraw()] each (numpy or device tensors) -> the list of their
+        waveforms, numpy float32, each byte for byte what synthesis_device gives for that utterance alone: VocoderPML's
+        synthesis_device_batch with the WORLD form of the table (ops.pulse_table_device(..., voiced=vuv >= 0.5)), ops.aper_rows
+        over the packed rows and ops.world_synthesis_batch."""
+        import torch
+        from . import ops
+        x, lengths, wavlens, noise = self._synthesis_batch_input(CMPs, noise)
+        s1 = 1 + self.spec_size
+        f0 = torch.exp(x[:, 0]).contiguous()
+        vuv = x[:, -1].contiguous()
+        table = ops.pulse_table_device(f0, lengths, self.shift, self.fs, self.dftlen, voiced=vuv >= 0.5)
+        SPEC = self.decompress_spectrum(x[:, 1:s1].contiguous(), pp_mcep=pp_mcep)
+        aper = ops.aper_rows(x[:, s1:s1 + self.aper_size].contiguous(), vuv, self.fs, self.dftlen)
+        noise = self._draw_noise(noise, wavlens, x.device)
+        return [w.cpu().numpy() for w in ops.world_synthesis_batch(SPEC, aper, table, noise, self.fs, self.dftlen)]
 
 
 class VocoderWORLDAnalysisDevice(VocoderWORLDDevice):
