@@ -22,6 +22,7 @@
 // Per k-step and wave: 3 MT ds_read_b128, 6 global 16-byte loads, 12 MT MFMAs.
 #include "common.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace ptts {
 namespace dns {
@@ -257,6 +258,101 @@ __global__ __launch_bounds__(256) void split3_dense_weight_strided_lds_kernel(Sp
     }
 }
 
+template <int B, int E, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (B < E) { f(std::integral_constant<int, B>{}); static_for<B + 1, E>(f); }
+}
+// ---- The staging of one 32-row slab of both operands (commit below) cut into ISSUE SLICES of at most two 4-cycle vector slots, so that
+// the k-loop can put one slice behind each of the issuing wave's own MFMAs: a v_mfma_f32_16x16x32_bf16 holds the SIMD's vector issue for 8
+// of its 16 cycles, the other 8 take two VALU / LDS instructions (a conversion counts as two) for nearly nothing -- and vector work of the
+// OTHER wave of the SIMD does not run under this wave's MFMAs, which is what the stagger of waves 0-3 / 4-7 relied on.
+// A lane's four quads (A rows j = 0, 1; dY rows j = 0, 1) are eight chains of two values, chain c = 2 quad + pair; a chain's operations
+// in order: [scale] [shift] zero-select [transform: two operations] [bias sum], then split3_pair's seven (convert, widen, subtract,
+// convert, widen, subtract, convert).  The slices run level by level over the chains (eight independent chains side by side), and a
+// quad's LDS write of plane p follows the slice that finished the plane's second pair.  The arithmetic and its order per value, and the
+// order of the bias sums, are commit's.
+enum : int { SL_AFM, SL_AFA, SL_SEL, SL_M1, SL_M2, SL_BS, SL_C1, SL_B1, SL_S1, SL_C2, SL_B2, SL_S2, SL_C3, SL_W };
+struct SliceTab { int n; int op[128], who[128], plane[128]; };      // who: the chain, for SL_W the quad
+template <int MODE, bool AFFINE, bool BSUM, int NQA, int NQD>
+constexpr SliceTab make_slices() {
+    SliceTab t{};
+    int ops[8][16] = {}, len[8] = {};
+    for (int c = 0; c < 2 * (NQA + NQD); ++c) {
+        const bool is_a = c < 2 * NQA;
+        int n = 0;
+        if (is_a && AFFINE) { ops[c][n++] = SL_AFM; ops[c][n++] = SL_AFA; }
+        ops[c][n++] = SL_SEL;
+        if (is_a && MODE != PTTS_IN_NONE) { ops[c][n++] = SL_M1; ops[c][n++] = SL_M2; }
+        if (!is_a && BSUM) ops[c][n++] = SL_BS;
+        for (int o = SL_C1; o <= SL_C3; ++o) ops[c][n++] = o;
+        len[c] = n;
+    }
+    int done[8] = {}, written[4] = {};
+    for (int l = 0; l < 16; ++l)
+        for (int c = 0; c < 2 * (NQA + NQD); ++c) {
+            if (l >= len[c]) continue;
+            const int o = ops[c][l], q = c >> 1;
+            t.op[t.n] = o; t.who[t.n] = c; t.plane[t.n] = 0; ++t.n;
+            if (o == SL_C1 || o == SL_C2 || o == SL_C3) ++done[c];
+            while (written[q] < (done[2 * q] < done[2 * q + 1] ? done[2 * q] : done[2 * q + 1])) {
+                t.op[t.n] = SL_W; t.who[t.n] = q; t.plane[t.n] = written[q]++; ++t.n;
+            }
+        }
+    return t;
+}
+// NQA quads with the input transform (A), then NQD without (dY); dense_bf16x6_kernel stages NA quads of A alone
+template <int MODE, bool AFFINE, bool BSUM, int PLSTRIDE, int NQA = 2, int NQD = 2>
+struct StageSlices {
+    static constexpr SliceTab TAB = make_slices<MODE, AFFINE, BSUM, NQA, NQD>();
+    static constexpr int N = TAB.n;
+    f32x2 x[8], y[8], mk[4];         // per chain: its two values, a temporary, the mask source's two values
+    unsigned pk[3][8];               // [plane][chain]: a quad's two chains side by side, as its LDS write takes them
+    bool ok[4];                      // per quad: its row and its columns are inside
+    u16* dst[4];                     // per quad: its 8 bytes of plane 0
+    f32x4 sc, sh;
+    float alpha;
+    // quads: va[0], va[1], vd[0], vd[1] (vm: the mask source of va)
+    __device__ __forceinline__ void begin(const f32x4* va, const f32x4* vm, const f32x4* vd) {
+#pragma unroll
+        for (int c = 0; c < 2 * (NQA + NQD); ++c) {
+            const int q = c >> 1, e = 2 * (c & 1);
+            const f32x4 v = q < NQA ? va[q < NQA ? q : 0] : vd[q < NQA ? 0 : q - NQA];
+            x[c] = (f32x2){v[e], v[e + 1]};
+            if (MODE == PTTS_IN_MASKMUL && q < NQA) mk[c & 3] = (f32x2){vm[q < NQA ? q : 0][e], vm[q < NQA ? q : 0][e + 1]};
+        }
+    }
+    template <int I>
+    __device__ __forceinline__ void run(f32x4& bsum) {
+        if constexpr (I < N) {
+            constexpr int op = TAB.op[I], c = TAB.who[I], e = 2 * (c & 1);
+            if constexpr (op == SL_AFM) { x[c] = x[c] * (f32x2){sc[e], sc[e + 1]}; }
+            else if constexpr (op == SL_AFA) { x[c] = x[c] + (f32x2){sh[e], sh[e + 1]}; }
+            else if constexpr (op == SL_SEL) { x[c] = (f32x2){ok[c >> 1] ? x[c][0] : 0.f, ok[c >> 1] ? x[c][1] : 0.f}; }
+            else if constexpr (op == SL_M1) {
+                if (MODE == PTTS_IN_LRELU) y[c] = (f32x2){alpha * x[c][0], alpha * x[c][1]};
+                else y[c] = (f32x2){mk[c & 3][0] > 0.f ? 1.f : alpha, mk[c & 3][1] > 0.f ? 1.f : alpha};
+            } else if constexpr (op == SL_M2) {
+                if (MODE == PTTS_IN_LRELU) x[c] = (f32x2){max_fast(x[c][0], y[c][0]), max_fast(x[c][1], y[c][1])};
+                else x[c] = (f32x2){x[c][0] * y[c][0], x[c][1] * y[c][1]};
+            } else if constexpr (op == SL_BS) { bsum[e] += x[c][0]; bsum[e + 1] += x[c][1]; }
+            else if constexpr (op == SL_C1 || op == SL_C2 || op == SL_C3) {
+                pk[(op - SL_C1) / 3][c] = __builtin_bit_cast(unsigned, __builtin_convertvector(x[c], bf16x2));
+            } else if constexpr (op == SL_B1 || op == SL_B2) {
+                const unsigned p = pk[(op - SL_B1) / 3][c];
+                y[c] = (f32x2){__builtin_bit_cast(float, p << 16), __builtin_bit_cast(float, p & 0xffff0000u)};
+            } else if constexpr (op == SL_S1 || op == SL_S2) { x[c] = x[c] - y[c]; }
+            else {                                                      // SL_W: c is the quad
+                constexpr int p = TAB.plane[I];
+                *reinterpret_cast<u32x2*>(dst[c] + p * PLSTRIDE) = (u32x2){pk[p][2 * c], pk[p][2 * c + 1]};
+            }
+        }
+    }
+};
+
+// DNS_PRODUCTS' order as tables: product pr multiplies plane prod_pa(pr) of the staged (activation) operand with plane prod_pw(pr) of the other
+constexpr int prod_pa(int pr) { constexpr int t[6] = {2, 1, 0, 1, 0, 0}; return t[pr]; }
+constexpr int prod_pw(int pr) { constexpr int t[6] = {0, 1, 2, 0, 1, 0}; return t[pr]; }
+
 #ifndef DNS_DEPTH
 #define DNS_DEPTH 2        // register stages of the A operand in dense_bf16x6_kernel (1 = the single stage of rounds 2-3; measured 1 / 2 / 3 / 4 / 6:
                            // 25.6 / 25.0 / 25.6 / 26.5 / 29.8 us at 25 600 rows, 82.4 / 75.3 / 80.3 / 83.0 / 86.0 at 76 800: the loads are not what bounds it)
@@ -420,6 +516,7 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
     // from 25 600 rows up (tools/dense_ramp_probe.py: 1.0 us per 1000 rows, 130 TF) and hardly moves with DEPTH: what bounds a k-step is
     // the matrix pipe -- TWO waves per SIMD x 84 six-product MFMAs x 16 cycles = 2 700 cycles at the ~1.8 GHz it holds under that load.
     constexpr int DEPTH = DNS_DEPTH;
+    constexpr bool OWN_GAPS = NPL == 3;                       // (one plane: 2 MT MFMAs per step, the k-step above)
     Stage sg[DEPTH];
     bf16x8 wc[2][NPL], wn[2][NPL];
     bf16x8 wx[XT ? NPL : 1];                                  // (no second stage: loaded at the head of its k-step, used at its end)
@@ -451,6 +548,51 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
             for (int p = 0; p < NPL; ++p) wc[j][p] = wn[j][p];
         __syncthreads();
     };
+    // Three planes: the same k-step with everything but the MFMAs in this wave's OWN MFMA gaps (StageSlices), the same
+    // in every wave.  Row tile i's three fragments are read in the first three gaps of tile i - 1 (two register sets), every other gap
+    // takes one slice of the staging of step s + 1; the weight loads of step s + 1 and the A loads of step s + 1 + DEPTH go out in front
+    // of the first MFMA, under the latency of tile 0's fragment reads; slices that are left run behind the last MFMA.
+    // (wcur / wnext: the weight fragments of this step and the registers the next step's are loaded into -- the caller swaps them, no copy)
+    auto step_own = [&](int s, Stage& nx, const bf16x8 (&wcur)[2][NPL], bf16x8 (&wnext)[2][NPL]) __attribute__((always_inline)) {
+        if constexpr (NPL == 3) {
+            using ST = StageSlices<MODE, AFFINE, false, PL, NA, 0>;
+            constexpr int NM = 12 * MT, NR = 3 * (MT - 1);           // MFMAs; fragment reads that stand in gaps
+            const u16* as = As[s & 1];
+            u16* an = As[(s + 1) & 1];                                // the other buffer: every wave left it at the last barrier
+            ST st;
+            st.begin(nx.va, nx.vm, nx.va);
+#pragma unroll
+            for (int j = 0; j < NA; ++j) { st.ok[j] = oka[j] && nx.kok; st.dst[j] = an + dst[j]; }
+            st.sc = nx.sc; st.sh = nx.sh; st.alpha = g.alpha;
+            f32x4 none = {0.f, 0.f, 0.f, 0.f};
+            bf16x8 bf[2][NPL];
+            auto read = [&](auto I, auto P) {
+                constexpr int i = decltype(I)::value, p = decltype(P)::value;
+                bf[i & 1][p] = *reinterpret_cast<const bf16x8*>(as + p * PL + boff + i * 16 * BK);
+            };
+            static_for<0, 3>([&](auto P) { read(std::integral_constant<int, 0>{}, P); });
+            load_w(s + 1 < KS ? s + 1 : s, wnext);
+            if constexpr (XT) load_wx(s, wx);
+            load_a(s + 1 + DEPTH, nx);
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<0, NM>([&](auto Q) {
+                constexpr int q = decltype(Q)::value, i = q / 12, r = q % 12, pr = r / 2, j = r % 2;
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wcur[j][prod_pw(pr)], bf[i & 1][prod_pa(pr)], acc[i][j], 0, 0, 0);
+                if constexpr (i + 1 < MT && r < 3) read(std::integral_constant<int, i + 1>{}, std::integral_constant<int, r>{});
+                else st.template run<q - (i + 1 < MT ? 3 * i + 3 : NR)>(none);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            static_for<NM - NR, ST::N>([&](auto I) { st.template run<decltype(I)::value>(none); });
+            if constexpr (XT) {
+                if (xt_wave) {                                        // (wave-uniform, in front of the barrier and not around it)
+                    bf16x8 bx[NPL];
+                    read_x(as, bx);
+                    mfma_x(wx, bx);
+                }
+            }
+            __syncthreads();
+        }
+    };
     auto step_dead = [&](int s, Stage& nx) {                  // the staging and the barrier of `step`, nothing else
         commit(nx, As[(s + 1) & 1]);
         load_a(s + 1 + DEPTH, nx);
@@ -466,6 +608,12 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
         for (int j = 0; j < DEPTH; ++j)
             if (s + j < KS) step(s + j, cut, sg[(j + 1) % DEPTH]);
     };
+    auto run_own = [&]() {                                   // two steps per trip: wc and wn change places
+        static_assert(!OWN_GAPS || DEPTH == 2, "run_own swaps the weight registers over a trip of two steps");
+        int s = 0;
+        for (; s + 2 <= KS; s += 2) { step_own(s, sg[1], wc, wn); step_own(s + 1, sg[0], wn, wc); }
+        if (s < KS) step_own(s, sg[1], wc, wn);
+    };
     auto run_dead = [&]() {
         int s = 0;
         for (; s + DEPTH <= KS; s += DEPTH) {
@@ -477,6 +625,7 @@ __global__ __launch_bounds__(THREADS) void dense_bf16x6_kernel(DenseArgs g) {
             if (s + j < KS) step_dead(s + j, sg[(j + 1) % DEPTH]);
     };
     if (DNS_SKIP_DEAD && !XT && !wave_live) run_dead();       // (XT: every column block is full)
+    else if (OWN_GAPS) run_own();
     else if (wave < 4) run(2); else run(MT - 2);
     if constexpr (XT) {
         // ---- store of the extra tile: lane (li, lg) of accx holds row m0 + 16 wave + li, columns n0 + 256 + 4 lg .. + 3
@@ -909,6 +1058,17 @@ __device__ __forceinline__ bf16x4 tr_read(const u16* p) {
 }
 __device__ __forceinline__ bf16x8 cat8(bf16x4 a, bf16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
 
+// The k-step of the two transposed-reduction kernels with three planes: 48 MFMAs (tile row, product, dY-column tile), 18 transposed
+// fragment reads and the StageSlices of the next slab.  Fragment ids: 3 i + p = A fragment of tile row i, plane p; 6 + 3 j + p = dY (B)
+// fragment of column tile j, plane p.  Seven fragments are read in front of the first MFMA (with the global loads of the slab after the
+// next behind them, under the LDS latency), the other eleven one per gap, each four or more MFMAs ahead of its first use; from gap 11 on a
+// gap takes one slice; what is left of the slices runs behind the last MFMA, in front of the barrier.
+constexpr int TN_HEAD_FRAGS = 7, TN_READ_GAPS = 11, TN_MFMAS = 48;
+constexpr int tn_read_order(int r) {
+    constexpr int ro[18] = {2, 6, 9, 12, 15, 1, 7,   10, 13, 16, 0, 8, 11, 14, 17, 5, 4, 3};
+    return ro[r];
+}
+
 struct WgradArgs {
     const float* A; const float* dY; const float* mask_src; const float* in_scale; const float* in_shift;
     float* partials;                         // [tile][split][part]: the workgroups' partial tiles (+ 128 bias sums, + the remainder tile)
@@ -932,6 +1092,35 @@ constexpr int WPARTX = WXR * WT;              // floats it adds to every partial
 __host__ __device__ inline bool wgrad_has_rem(int Kin) { return Kin > WT && Kin % WT >= 1 && Kin % WT <= WXR; }
 __host__ __device__ inline int wgrad_tiles_k(int Kin) { return wgrad_has_rem(Kin) ? Kin / WT : (Kin + WT - 1) / WT; }
 __host__ __device__ inline int wgrad_part(int Kin) { return WPART + (wgrad_has_rem(Kin) ? WPARTX : 0); }
+
+// (cur: the buffer that is multiplied; ao / bo: the lane's fragment offsets; st: the slices of the next slab, already begun;
+// load_next: the global loads of the slab after the next)
+template <class ST, class LoadF>
+__device__ __forceinline__ void tn_step_own(const u16* cur, const int (&ao)[2][2], const int (&bo)[4][2], f32x4 (&acc)[2][4], ST& st,
+                                            f32x4& bsum, LoadF&& load_next) {
+    bf16x8 af[2][3], bf[4][3];
+    auto read = [&](auto R) {
+        constexpr int id = tn_read_order(decltype(R)::value);
+        if constexpr (id < 6) {
+            constexpr int i = id / 3, p = id % 3;
+            af[i][p] = cat8(tr_read(cur + p * WPL + ao[i][0]), tr_read(cur + p * WPL + ao[i][1]));
+        } else {
+            constexpr int j = (id - 6) / 3, p = (id - 6) % 3;
+            bf[j][p] = cat8(tr_read(cur + p * WPL + bo[j][0]), tr_read(cur + p * WPL + bo[j][1]));
+        }
+    };
+    static_for<0, TN_HEAD_FRAGS>(read);
+    load_next();
+    __builtin_amdgcn_sched_barrier(0);
+    static_for<0, TN_MFMAS>([&](auto Q) {
+        constexpr int q = decltype(Q)::value, i = q / 24, pr = (q % 24) / 4, j = q % 4;
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][prod_pa(pr)], bf[j][prod_pw(pr)], acc[i][j], 0, 0, 0);
+        if constexpr (q < TN_READ_GAPS) read(std::integral_constant<int, TN_HEAD_FRAGS + q>{});
+        else st.template run<q - TN_READ_GAPS>(bsum);
+        __builtin_amdgcn_sched_barrier(0);
+    });
+    static_for<TN_MFMAS - TN_READ_GAPS, ST::N>([&](auto I) { st.template run<decltype(I)::value>(bsum); });
+}
 
 template <int MODE, bool AFFINE, int NPL, bool XR = false>
 __global__ __launch_bounds__(THREADS) void dense_wgrad_bf16x6_kernel(WgradArgs g) {
@@ -1136,10 +1325,33 @@ __global__ __launch_bounds__(THREADS) void dense_wgrad_bf16x6_kernel(WgradArgs g
         if (XR && xr_wg) mfma_rem(cur, curx);                        // (workgroup-uniform, in front of the barrier)
         __syncthreads();
     };
-    // The two waves of a SIMD leave every barrier together: waves 0-3 run half of their MFMAs before the staging of the next
-    // step, waves 4-7 stage first -- one wave's vector work under the other's matrix work.  Two steps per trip: the
-    // buffers are compile-time.
-    if (wave < 4) {
+    // the staging of step s + 1 in this wave's own MFMA gaps (StageSlices), the same in every wave.  Not with one plane (8 MFMAs), not
+    // with the remainder tile (256 registers already) and not with the affine input, whose trace row did not shrink:
+    // those keep the k-step above.
+    constexpr bool OWN_GAPS = NPL == 3 && !XR && !AFFINE;
+    auto step_own = [&](int s, const u16* cur, u16* nxt) {
+        if constexpr (OWN_GAPS) {
+            using ST = StageSlices<MODE, AFFINE, true, WPL>;
+            ST st;
+            st.begin(sg.va, sg.vm, sg.vd);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                st.ok[j] = sg.ok[j] && a_ok; st.ok[2 + j] = sg.ok[j] && d_ok;
+                st.dst[j] = nxt + dst[j]; st.dst[2 + j] = nxt + dst[j] + 3 * WPL;
+            }
+            st.sc = sc; st.sh = sh; st.alpha = g.alpha;
+            tn_step_own(cur, ao, bo, acc, st, bsum, [&]() { load(s + 2, sg); });   // (rows of a step beyond the share are staged as zeros)
+            __syncthreads();
+        }
+    };
+    // Two steps per trip: the buffers are compile-time.  The forms that keep `step`: the two waves of a SIMD leave every barrier together,
+    // so waves 0-3 run half of their MFMAs before the staging of the next step and waves 4-7 stage first -- one wave's vector work
+    // under the other's matrix work.
+    if (OWN_GAPS) {
+        int s = 0;
+        for (; s + 1 < nsteps; s += 2) { step_own(s, buf0, buf1); step_own(s + 1, buf1, buf0); }
+        if (s < nsteps) step_own(s, buf0, buf1);
+    } else if (wave < 4) {
         int s = 0;
         for (; s + 1 < nsteps; s += 2) { step(s, buf0, buf1, xbuf0, xbuf1, false); step(s + 1, buf1, buf0, xbuf1, xbuf0, false); }
         if (s < nsteps) step(s, buf0, buf1, xbuf0, xbuf1, false);
@@ -1237,7 +1449,7 @@ __global__ __launch_bounds__(256) void dense_wgrad_reduce_kernel(DwReduceArgs a)
 // ------------------------------------------------------------------------------------------------------------
 // Batched transposed-reduction product  C_z[Kin][N] = A_z[M][Kin]^T . B_z[M][N]  (gridDim.z members z): the construction of
 // dense_wgrad_bf16x6_kernel above -- 32-row slabs of both fp32 operands split on their way into the LDS (the same row layout, the same
-// transposed reads, the same six products, two buffers, waves 0-3 / 4-7 staging at different places) -- for products whose reduction
+// transposed reads, the same six products, two buffers, the same two k-step forms: step_own with three planes) -- for products whose reduction
 // is short and whose batch is long (the frequency-domain context Conv1D: M = 2 B NS rows per frequency, S rows per segment): one
 // workgroup owns a whole 128 x 128 tile, so there is no split over M, no partial rows and no reduce launch; the tile goes straight
 // into C, every cell guarded by the true Kin and N.  No input transforms, no bias sums, no remainder tile.
@@ -1364,7 +1576,27 @@ __global__ __launch_bounds__(THREADS) void dense_tn_bf16x6_kernel(TnArgs g) {
         mfma_tile_row(cur, 1, bf);
         __syncthreads();
     };
-    if (wave < 4) {
+    // three planes: dense_wgrad_bf16x6_kernel's step_own
+    auto step_own = [&](int s, const u16* cur, u16* nxt) {
+        if constexpr (NPL == 3) {
+            using ST = StageSlices<PTTS_IN_NONE, false, false, WPL>;
+            ST st;
+            st.begin(sg.va, nullptr, sg.vb);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                st.ok[j] = sg.ok[j] && a_ok; st.ok[2 + j] = sg.ok[j] && b_ok;
+                st.dst[j] = nxt + dst[j]; st.dst[2 + j] = nxt + dst[j] + 3 * WPL;
+            }
+            f32x4 none = {0.f, 0.f, 0.f, 0.f};
+            tn_step_own(cur, ao, bo, acc, st, none, [&]() { load(s + 2, sg); });
+            __syncthreads();
+        }
+    };
+    if (NPL == 3) {
+        int s = 0;
+        for (; s + 1 < nsteps; s += 2) { step_own(s, buf0, buf1); step_own(s + 1, buf1, buf0); }
+        if (s < nsteps) step_own(s, buf0, buf1);
+    } else if (wave < 4) {
         int s = 0;
         for (; s + 1 < nsteps; s += 2) { step(s, buf0, buf1, false); step(s + 1, buf1, buf0, false); }
         if (s < nsteps) step(s, buf0, buf1, false);
