@@ -974,6 +974,73 @@ int ptts_f0_refine(const float* wav, long long N, const float* f0, float* out, i
                    double shift, double fs, double f0_min, double f0_max, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Waveform analysis over a batch of utterances (csrc/analysisbatch.hip and the *_batch kernels of
+ * csrc/f0.hip, csrc/analysis.hip, csrc/worldanalysis.hip).  B <= 65535 utterances are packed one
+ * after the other: wav [wav_total] fp32 with wav_off [B+1], every per-frame tensor [T, ..] with
+ * frame_off [B+1], T the packed total (the <= 2^31 row limits of the single forms apply to it);
+ * the offsets are int64 in DEVICE memory, ascending from 0.  Global frame g of utterance b is that
+ * utterance's frame i = g - frame_off[b], centred at rnd(i shift fs) in its own waveform of
+ * N_b = wav_off[b+1] - wav_off[b] samples; a workgroup finds b by a binary search in frame_off.
+ * An utterance whose offsets do not lie inside the totals is skipped: nothing of it is read or
+ * written.  Each launch runs once for the whole batch; no atomics, nothing between workgroups.
+ *
+ * ptts_f0_candidates_batch, ptts_f0_refine_batch, ptts_frame_harmonics_batch,
+ * ptts_world_envelope_batch, ptts_world_aperiodicity_batch: the single form's frame, computed by
+ *   the same device function on the utterance's samples and rows, so utterance b's rows are, bit
+ *   for bit, what the single entry point writes for that utterance alone.  ptts_f0_candidates_batch
+ *   reads each utterance's gpeak from gpeak [B] fp64 in device memory (ptts_wave_peak's, or the
+ *   caller's; a value that is not finite or negative counts as 0).
+ * ptts_phase_coherence_batch: as above; the neighbourhood i - J_i .. i + J_i and the clamp
+ *   J_i <= T_b are those of the frame's own utterance, never a neighbour's rows.
+ * ptts_f0_viterbi_batch: grid B, one wave64 per utterance with its own back-pointers in LDS.
+ *   max_frames: the longest utterance (the LDS of a workgroup), at most
+ *   ptts_f0_viterbi_max_frames(ncand): the cap is per utterance, not for the batch.  A longer
+ *   utterance is skipped.
+ * ptts_wave_peak: one workgroup per utterance; gpeak [B] fp64 = max |x - mean(x)| over the
+ *   utterance's fp32 samples in fp64, the mean by a fixed-order sum (the same input gives the same
+ *   bytes); 0 for N_b = 0.  A sample that is not finite: gpeak 0 and PTTS_ANALYSIS_BAD_WAV.
+ * ptts_f0_track: ops.f0_track for every utterance, one workgroup each.
+ *   f0 [in_total] Hz, fp32 or (f0_is_double != 0) fp64, <= 0 unvoiced, packed by in_off [B+1];
+ *   the unvoiced stretches are interpolated linearly over the frame index between their voiced
+ *   neighbours (numpy.interp restated in fp64: the end values held), clipped to [f0_min, f0_max],
+ *   rounded to fp32 and moved by one ulp where the rounding left the interval; the first
+ *   Tout_b = out_off[b+1] - out_off[b] <= T_b frames go to track [out_total] fp32, and
+ *   vuv [out_total] = 1 where f0 > 0, else 0.  An utterance without frames or with a value that
+ *   is not finite: PTTS_ANALYSIS_BAD_F0; without a voiced frame: PTTS_ANALYSIS_NO_VOICED; such
+ *   an utterance gets no rows.
+ * info [B] int32: the status bits of an utterance are OR-ed into info[b]; the CALLER zeroes it
+ *   before the first launch and reads it back once after the last.
+ * T = 0 or B = 0 succeeds without a launch.
+ * ------------------------------------------------------------------------------------- */
+#define PTTS_ANALYSIS_BAD_WAV 1      /* a sample of the waveform is not finite */
+#define PTTS_ANALYSIS_BAD_F0 2       /* the track is empty or has a value that is not finite */
+#define PTTS_ANALYSIS_NO_VOICED 4    /* the track has no voiced frame */
+int ptts_wave_peak(const float* wav, const long long* wav_off, long long wav_total, int B, double* gpeak, int* info, void* stream);
+int ptts_f0_track(const void* f0, int f0_is_double, const long long* in_off, long long in_total, const long long* out_off,
+                  long long out_total, int B, float* track, float* vuv, int* info, double f0_min, double f0_max, void* stream);
+int ptts_f0_candidates_batch(const float* wav, const long long* wav_off, long long wav_total, const long long* frame_off, int B, int T,
+                             const double* rw, size_t rw_bytes, float* freq, float* strength, int* n, int* lag, float* r /* or NULL */,
+                             int ncand, double shift, double fs, int dftlen, double f0_min, double f0_max, const double* gpeak,
+                             double voicing_threshold, double silence_threshold, double octave_cost, void* stream);
+int ptts_f0_viterbi_batch(const float* freq, const float* strength, const int* n, float* f0, int* path /* or NULL */,
+                          const long long* frame_off, int B, int T, int max_frames, int ncand, double shift, double octave_jump_cost,
+                          double voiced_unvoiced_cost, void* stream);
+int ptts_f0_refine_batch(const float* wav, const long long* wav_off, long long wav_total, const long long* frame_off, int B, int T,
+                         const float* f0, float* out, int* status /* or NULL */, double shift, double fs, double f0_min, double f0_max,
+                         void* stream);
+int ptts_frame_harmonics_batch(const float* wav, const long long* wav_off, long long wav_total, const long long* frame_off, int B, int T,
+                               const float* f0, float* spec, float* u, int Hcap, double shift, double fs, int dftlen, int log_out,
+                               void* stream);
+int ptts_phase_coherence_batch(const float* u, const float* f0, float* R, float* nm, const long long* frame_off, int B, int T, int Hcap,
+                               int nb, double shift, double fs, int dftlen, const double* fwtable, size_t fwtable_bytes,
+                               const double* ctable, size_t ctable_bytes, void* stream);
+int ptts_world_envelope_batch(const float* wav, const long long* wav_off, long long wav_total, const long long* frame_off, int B, int T,
+                              const float* rate, float* spec, double shift, double fs, int dftlen, int log_out, void* stream);
+int ptts_world_aperiodicity_batch(const float* wav, const long long* wav_off, long long wav_total, const long long* frame_off, int B,
+                                  int T, const float* f0, const float* voiced, float* aper, int nb, double shift, double fs, int dftlen,
+                                  const double* fwtable, size_t fwtable_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Waveform pre-processing (csrc/preproc.hip; the reference's Vocoder.preprocwav,
  * vocoders.py:45-63; both definitions are this build's own).  fp32 in
  * memory, fp64 arithmetic, one rounding per sample.  Both entry points take a packed batch:

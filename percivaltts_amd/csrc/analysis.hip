@@ -39,17 +39,17 @@ constexpr double AN_FLT_MIN = 1.17549435082228751e-38;
 // H = floor((fs/2 - f0/2) / f0) as a double; f0 > 0
 __device__ __forceinline__ double harmonics_of(double f0, double fs) { return floor((0.5 * fs - 0.5 * f0) / f0); }
 
-// One workgroup per frame.  dynamic LDS: (M + M/4) double2 + (Hcap + 2) doubles.
-__global__ __launch_bounds__(AN_THREADS) void frame_harmonics_kernel(const float* __restrict__ wav, const long long N,
-                                                                     const float* __restrict__ f0v, float* __restrict__ spec,
-                                                                     float* __restrict__ u, const int Hcap, const int logM,
-                                                                     const double shift, const double fs, const bool log_out) {
+// Frame i of one utterance: wav [N] its samples, f0v, spec and u its own rows.  The workgroup's work; dynamic LDS:
+// (M + M/4) double2 + (Hcap + 2) doubles.
+__device__ __forceinline__ void frame_harmonics_frame(const float* __restrict__ wav, const long long N, const float* __restrict__ f0v,
+                                                      float* __restrict__ spec, float* __restrict__ u, const int i, const int Hcap,
+                                                      const int logM, const double shift, const double fs, const bool log_out) {
     extern __shared__ double2 lds[];
     const int M = 1 << logM, L = M << 1, K = M + 1, Mq = M >> 2;
     double2* a = lds;
     double2* wq = lds + M;
     double* ah = reinterpret_cast<double*>(lds + M + Mq);       // a_h at [h], h = 1 .. H
-    const int i = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int tid = threadIdx.x, nthr = blockDim.x;
     const double f0 = (double)f0v[i];
     // a frame the host checks would have refused: nothing of it is read or written
     if (!(f0 > 0.0) || !(f0 < fs)) return;
@@ -115,6 +115,27 @@ __global__ __launch_bounds__(AN_THREADS) void frame_harmonics_kernel(const float
     }
 }
 
+// One workgroup per frame.
+__global__ __launch_bounds__(AN_THREADS) void frame_harmonics_kernel(const float* __restrict__ wav, const long long N,
+                                                                     const float* __restrict__ f0v, float* __restrict__ spec,
+                                                                     float* __restrict__ u, const int Hcap, const int logM,
+                                                                     const double shift, const double fs, const bool log_out) {
+    frame_harmonics_frame(wav, N, f0v, spec, u, blockIdx.x, Hcap, logM, shift, fs, log_out);
+}
+
+// One workgroup per frame of the packed batch.
+__global__ __launch_bounds__(AN_THREADS) void frame_harmonics_batch_kernel(const float* __restrict__ wav, const long long* __restrict__ wav_off,
+                                                                           const long long wav_total, const long long* __restrict__ frame_off,
+                                                                           const int B, const int T, const float* __restrict__ f0v,
+                                                                           float* __restrict__ spec, float* __restrict__ u, const int Hcap,
+                                                                           const int logM, const double shift, const double fs,
+                                                                           const bool log_out) {
+    const PackedFrame f = packed_frame(wav_off, wav_total, frame_off, B, T, blockIdx.x);
+    if (!f.ok) return;
+    frame_harmonics_frame(wav + f.woff, f.N, f0v + f.foff, spec + (size_t)f.foff * ((1 << logM) + 1), u + (size_t)f.foff * Hcap * 2, f.i, Hcap,
+                          logM, shift, fs, log_out);
+}
+
 // W[k,b] from the band / fraction rows of the fwbnd table (band indices clamped, whatever the table holds)
 __device__ __forceinline__ double hat_weight(const double* __restrict__ fw, int Kp, int nb, int k, int b) {
     int bk;
@@ -130,14 +151,24 @@ __device__ __forceinline__ void band_bins(const double* __restrict__ ct, int nbp
     hi = h >= 0.0 && h <= (double)K ? (int)h : K;
 }
 
-// One workgroup per frame.  dynamic LDS: Hcap ints (the harmonics' flags).
-__global__ __launch_bounds__(AN_THREADS) void phase_coherence_kernel(const float* __restrict__ u, const float* __restrict__ f0v,
-                                                                     float* __restrict__ R, float* __restrict__ nm, const int T,
-                                                                     const int Hcap, const int nb, const int nbp, const int K,
-                                                                     const int Kp, const int L, const double shift, const double fs,
-                                                                     const double* __restrict__ fw, const double* __restrict__ ct) {
+// The scalars of a ptts_phase_coherence launch that every frame shares
+struct CoherenceArgs {
+    int Hcap, nb, nbp, K, Kp, L;
+    double shift, fs;
+    const double* fw;
+    const double* ct;
+};
+
+// Frame i of one utterance of T frames: u, f0v, R and nm its own rows, so the neighbourhood m0 .. m1 and the clamp J <= T are the
+// utterance's.  The workgroup's work; dynamic LDS: Hcap ints (the harmonics' flags).
+__device__ __forceinline__ void phase_coherence_frame(const float* __restrict__ u, const float* __restrict__ f0v, float* __restrict__ R,
+                                                      float* __restrict__ nm, const int i, const int T, const CoherenceArgs& A) {
     extern __shared__ int noisy[];
-    const int i = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int Hcap = A.Hcap, nb = A.nb, nbp = A.nbp, K = A.K, Kp = A.Kp, L = A.L;
+    const double shift = A.shift, fs = A.fs;
+    const double* __restrict__ fw = A.fw;
+    const double* __restrict__ ct = A.ct;
+    const int tid = threadIdx.x, nthr = blockDim.x;
     const double f0 = (double)f0v[i];
     int H = 0, J = 2;
     if (f0 > 0.0 && f0 < fs) {
@@ -178,6 +209,23 @@ __global__ __launch_bounds__(AN_THREADS) void phase_coherence_kernel(const float
         const double s = ct[2 * (size_t)nbp + b];
         nm[(size_t)i * nb + b] = (float)(s > 0.0 ? acc / s : 0.0);
     }
+}
+
+// One workgroup per frame.
+__global__ __launch_bounds__(AN_THREADS) void phase_coherence_kernel(const float* __restrict__ u, const float* __restrict__ f0v,
+                                                                     float* __restrict__ R, float* __restrict__ nm, const int T,
+                                                                     const CoherenceArgs A) {
+    phase_coherence_frame(u, f0v, R, nm, blockIdx.x, T, A);
+}
+
+// One workgroup per frame of the packed batch: a frame sees the rows of its own utterance alone.
+__global__ __launch_bounds__(AN_THREADS) void phase_coherence_batch_kernel(const float* __restrict__ u, const float* __restrict__ f0v,
+                                                                           float* __restrict__ R, float* __restrict__ nm,
+                                                                           const long long* __restrict__ frame_off, const int B,
+                                                                           const int T, const CoherenceArgs A) {
+    const PackedFrame f = packed_frame(nullptr, 0, frame_off, B, T, blockIdx.x);
+    if (!f.ok) return;
+    phase_coherence_frame(u + (size_t)f.foff * A.Hcap * 2, f0v + f.foff, R + (size_t)f.foff * A.Hcap, nm + (size_t)f.foff * A.nb, f.i, f.T, A);
 }
 
 // One workgroup.  The band index row of the fwbnd table ascends with k, so a band's bins are the run between two binary searches.
@@ -300,42 +348,89 @@ static int band_tables(const char* what, int nb, int dftlen, const double* fw, s
 
 using namespace ptts;
 
+static int frame_harmonics_args(const char* what, int Hcap, double shift, double fs, int dftlen, int& logL, int& lds) {
+    PTTS_REQUIRE(Hcap >= 1 && Hcap <= AN_MAX_HCAP, "%s: Hcap=%d outside [1, %d]", what, Hcap, AN_MAX_HCAP);
+    logL = frame_log2(dftlen);
+    PTTS_REQUIRE(logL > 0, "%s: dftlen=%d is not a power of two in [%d, %d]", what, dftlen, FRAME_MIN_DFTLEN, FRAME_MAX_DFTLEN);
+    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "%s: fs=%g", what, fs);
+    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "%s: shift=%g", what, shift);
+    const int M = dftlen / 2;
+    lds = (M + M / 4) * (int)sizeof(double2) + (Hcap + 2) * (int)sizeof(double);
+    return PTTS_OK;
+}
+
 extern "C" int ptts_frame_harmonics(const float* wav, long long N, const float* f0, float* spec, float* u, int T, int Hcap, double shift,
                                     double fs, int dftlen, int log_out, void* stream) {
     PTTS_REQUIRE(T >= 0 && N >= 0, "frame_harmonics: T=%d N=%lld", T, N);
-    PTTS_REQUIRE(Hcap >= 1 && Hcap <= AN_MAX_HCAP, "frame_harmonics: Hcap=%d outside [1, %d]", Hcap, AN_MAX_HCAP);
-    const int logL = frame_log2(dftlen);
-    PTTS_REQUIRE(logL > 0, "frame_harmonics: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN, FRAME_MAX_DFTLEN);
-    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "frame_harmonics: fs=%g", fs);
-    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "frame_harmonics: shift=%g", shift);
+    int logL, lds;
+    int rc = frame_harmonics_args("frame_harmonics", Hcap, shift, fs, dftlen, logL, lds);
+    if (rc != PTTS_OK) return rc;
     if (T == 0) return PTTS_OK;
     PTTS_REQUIRE(f0 && spec && u && (wav || N == 0), "frame_harmonics: null tensor");
-    const int M = dftlen / 2;
-    const int lds = (M + M / 4) * (int)sizeof(double2) + (Hcap + 2) * (int)sizeof(double);
-    const int rc = reserve_lds<frame_harmonics_kernel>("frame_harmonics", lds);
+    rc = reserve_lds<frame_harmonics_kernel>("frame_harmonics", lds);
     if (rc != PTTS_OK) return rc;
-    hipLaunchKernelGGL(frame_harmonics_kernel, dim3(T), dim3(frame_threads(M, AN_THREADS)), (size_t)lds, (hipStream_t)stream, wav, N, f0,
-                       spec, u, Hcap, logL - 1, shift, fs, log_out != 0);
+    hipLaunchKernelGGL(frame_harmonics_kernel, dim3(T), dim3(frame_threads(dftlen / 2, AN_THREADS)), (size_t)lds, (hipStream_t)stream, wav, N,
+                       f0, spec, u, Hcap, logL - 1, shift, fs, log_out != 0);
     return check_launch("frame_harmonics");
+}
+
+extern "C" int ptts_frame_harmonics_batch(const float* wav, const long long* wav_off, long long wav_total, const long long* frame_off, int B,
+                                          int T, const float* f0, float* spec, float* u, int Hcap, double shift, double fs, int dftlen,
+                                          int log_out, void* stream) {
+    PTTS_REQUIRE(T >= 0 && wav_total >= 0 && B >= 0 && B <= PACKED_MAX_UTTS, "frame_harmonics_batch: T=%d wav_total=%lld B=%d", T, wav_total, B);
+    int logL, lds;
+    int rc = frame_harmonics_args("frame_harmonics_batch", Hcap, shift, fs, dftlen, logL, lds);
+    if (rc != PTTS_OK) return rc;
+    if (T == 0 || B == 0) return PTTS_OK;
+    PTTS_REQUIRE(f0 && spec && u && wav_off && frame_off && (wav || wav_total == 0), "frame_harmonics_batch: null tensor");
+    rc = reserve_lds<frame_harmonics_batch_kernel>("frame_harmonics_batch", lds);
+    if (rc != PTTS_OK) return rc;
+    hipLaunchKernelGGL(frame_harmonics_batch_kernel, dim3(T), dim3(frame_threads(dftlen / 2, AN_THREADS)), (size_t)lds, (hipStream_t)stream,
+                       wav, wav_off, wav_total, frame_off, B, T, f0, spec, u, Hcap, logL - 1, shift, fs, log_out != 0);
+    return check_launch("frame_harmonics_batch");
+}
+
+// The checks of ptts_phase_coherence and its batched form in front of the T = 0 exit (the tables are looked at behind it)
+static int phase_coherence_args(const char* what, int Hcap, int nb, double shift, double fs, int dftlen, const double* fwtable,
+                                size_t fwtable_bytes, const double* ctable, size_t ctable_bytes, CoherenceArgs& A) {
+    PTTS_REQUIRE(Hcap >= 1 && Hcap <= AN_MAX_HCAP, "%s: Hcap=%d outside [1, %d]", what, Hcap, AN_MAX_HCAP);
+    PTTS_REQUIRE(nb >= 2 && nb <= AN_MAX_NB, "%s: nb=%d outside [2, %d]", what, nb, AN_MAX_NB);
+    PTTS_REQUIRE(frame_log2(dftlen) > 0, "%s: dftlen=%d is not a power of two in [%d, %d]", what, dftlen, FRAME_MIN_DFTLEN, FRAME_MAX_DFTLEN);
+    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "%s: fs=%g", what, fs);
+    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "%s: shift=%g", what, shift);
+    A = CoherenceArgs{Hcap, nb, an_padded_bands(nb), dftlen / 2 + 1, an_padded_bins(dftlen), dftlen, shift, fs, fwtable, ctable};
+    return PTTS_OK;
 }
 
 extern "C" int ptts_phase_coherence(const float* u, const float* f0, float* R, float* nm, int T, int Hcap, int nb, double shift, double fs,
                                     int dftlen, const double* fwtable, size_t fwtable_bytes, const double* ctable, size_t ctable_bytes,
                                     void* stream) {
     PTTS_REQUIRE(T >= 0, "phase_coherence: T=%d", T);
-    PTTS_REQUIRE(Hcap >= 1 && Hcap <= AN_MAX_HCAP, "phase_coherence: Hcap=%d outside [1, %d]", Hcap, AN_MAX_HCAP);
-    PTTS_REQUIRE(nb >= 2 && nb <= AN_MAX_NB, "phase_coherence: nb=%d outside [2, %d]", nb, AN_MAX_NB);
-    PTTS_REQUIRE(frame_log2(dftlen) > 0, "phase_coherence: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN,
-                 FRAME_MAX_DFTLEN);
-    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "phase_coherence: fs=%g", fs);
-    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "phase_coherence: shift=%g", shift);
+    CoherenceArgs A;
+    int rc = phase_coherence_args("phase_coherence", Hcap, nb, shift, fs, dftlen, fwtable, fwtable_bytes, ctable, ctable_bytes, A);
+    if (rc != PTTS_OK) return rc;
     if (T == 0) return PTTS_OK;
     PTTS_REQUIRE(u && f0 && R && nm, "phase_coherence: null tensor");
-    const int rc = band_tables("phase_coherence", nb, dftlen, fwtable, fwtable_bytes, ctable, ctable_bytes);
+    rc = band_tables("phase_coherence", nb, dftlen, fwtable, fwtable_bytes, ctable, ctable_bytes);
     if (rc != PTTS_OK) return rc;
-    hipLaunchKernelGGL(phase_coherence_kernel, dim3(T), dim3(AN_THREADS), (size_t)Hcap * sizeof(int), (hipStream_t)stream, u, f0, R, nm, T,
-                       Hcap, nb, an_padded_bands(nb), dftlen / 2 + 1, an_padded_bins(dftlen), dftlen, shift, fs, fwtable, ctable);
+    hipLaunchKernelGGL(phase_coherence_kernel, dim3(T), dim3(AN_THREADS), (size_t)Hcap * sizeof(int), (hipStream_t)stream, u, f0, R, nm, T, A);
     return check_launch("phase_coherence");
+}
+
+extern "C" int ptts_phase_coherence_batch(const float* u, const float* f0, float* R, float* nm, const long long* frame_off, int B, int T,
+                                          int Hcap, int nb, double shift, double fs, int dftlen, const double* fwtable,
+                                          size_t fwtable_bytes, const double* ctable, size_t ctable_bytes, void* stream) {
+    PTTS_REQUIRE(T >= 0 && B >= 0 && B <= PACKED_MAX_UTTS, "phase_coherence_batch: T=%d B=%d", T, B);
+    CoherenceArgs A;
+    int rc = phase_coherence_args("phase_coherence_batch", Hcap, nb, shift, fs, dftlen, fwtable, fwtable_bytes, ctable, ctable_bytes, A);
+    if (rc != PTTS_OK) return rc;
+    if (T == 0 || B == 0) return PTTS_OK;
+    PTTS_REQUIRE(u && f0 && R && nm && frame_off, "phase_coherence_batch: null tensor");
+    rc = band_tables("phase_coherence_batch", nb, dftlen, fwtable, fwtable_bytes, ctable, ctable_bytes);
+    if (rc != PTTS_OK) return rc;
+    hipLaunchKernelGGL(phase_coherence_batch_kernel, dim3(T), dim3(AN_THREADS), (size_t)Hcap * sizeof(int), (hipStream_t)stream, u, f0, R, nm,
+                       frame_off, B, T, A);
+    return check_launch("phase_coherence_batch");
 }
 
 extern "C" size_t ptts_fwbnd_compress_table_bytes(int nb) {

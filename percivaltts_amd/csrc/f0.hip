@@ -110,24 +110,28 @@ __device__ __forceinline__ bool f0_candidate(const double* r, int k, double fs, 
     return true;
 }
 
-// One workgroup per frame.  dynamic LDS: (M + M/4) double2 + (lmax + 2) doubles + 4 doubles + 4 ints.
-// The host has checked 1 <= lmin <= lmax and 2 hw + 1 + lmax + 1 <= L.
-__global__ __launch_bounds__(F0_THREADS) void f0_candidates_kernel(const float* __restrict__ wav, const long long N,
-                                                                   const double* __restrict__ rw, float* __restrict__ freq,
-                                                                   float* __restrict__ strength, int* __restrict__ nout,
-                                                                   int* __restrict__ lag, float* __restrict__ rout, const int logM,
-                                                                   const int hw, const int lmin, const int lmax, const int ncand,
-                                                                   const double shift, const double fs, const double f0_min,
-                                                                   const double f0_max, const double gpeak, const double vt,
-                                                                   const double st, const double oc) {
+// The scalars of a ptts_f0_candidates launch that every frame shares
+struct F0CandArgs {
+    int logM, hw, lmin, lmax, ncand;
+    double shift, fs, f0_min, f0_max, vt, st, oc;
+};
+
+// Frame i of one utterance: wav [N] its samples, the output rows its own, gpeak its peak.  The workgroup's work; dynamic LDS:
+// (M + M/4) double2 + (lmax + 2) doubles + 4 doubles + 4 ints.  The host has checked 1 <= lmin <= lmax and 2 hw + 1 + lmax + 1 <= L.
+__device__ __forceinline__ void f0_candidates_frame(const float* __restrict__ wav, const long long N, const double* __restrict__ rw,
+                                                    float* __restrict__ freq, float* __restrict__ strength, int* __restrict__ nout,
+                                                    int* __restrict__ lag, float* __restrict__ rout, const int i, const double gpeak,
+                                                    const F0CandArgs& A) {
     extern __shared__ double2 lds[];
+    const int logM = A.logM, hw = A.hw, lmin = A.lmin, lmax = A.lmax, ncand = A.ncand;
+    const double shift = A.shift, fs = A.fs, f0_min = A.f0_min, f0_max = A.f0_max, vt = A.vt, st = A.st, oc = A.oc;
     const int M = 1 << logM, L = M << 1, Mq = M >> 2, W = 2 * hw + 1;
     double2* a = lds;
     double2* wq = lds + M;
     double* cs = reinterpret_cast<double*>(lds + M + Mq);       // [lmax + 2]: the strength of a lag that is a candidate, else -inf
     double* red = cs + (lmax + 2);
     int* redk = reinterpret_cast<int*>(red + 4);
-    const int i = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int tid = threadIdx.x, nthr = blockDim.x;
 
     fill_twiddles(wq, M);
     // position p of the buffer holds sample s0 + p; [j0, j1) are the positions of the window that lie inside the waveform
@@ -248,6 +252,32 @@ __global__ __launch_bounds__(F0_THREADS) void f0_candidates_kernel(const float* 
     }
 }
 
+// One workgroup per frame.
+__global__ __launch_bounds__(F0_THREADS) void f0_candidates_kernel(const float* __restrict__ wav, const long long N,
+                                                                   const double* __restrict__ rw, float* __restrict__ freq,
+                                                                   float* __restrict__ strength, int* __restrict__ nout,
+                                                                   int* __restrict__ lag, float* __restrict__ rout, const double gpeak,
+                                                                   const F0CandArgs A) {
+    f0_candidates_frame(wav, N, rw, freq, strength, nout, lag, rout, blockIdx.x, gpeak, A);
+}
+
+// One workgroup per frame of the packed batch: the frame's utterance, then f0_candidates_frame on that utterance's samples and rows
+// with its own peak from gpeak [B].
+__global__ __launch_bounds__(F0_THREADS) void f0_candidates_batch_kernel(const float* __restrict__ wav, const long long* __restrict__ wav_off,
+                                                                         const long long wav_total, const long long* __restrict__ frame_off,
+                                                                         const int B, const int T, const double* __restrict__ rw,
+                                                                         float* __restrict__ freq, float* __restrict__ strength,
+                                                                         int* __restrict__ nout, int* __restrict__ lag,
+                                                                         float* __restrict__ rout, const double* __restrict__ gpeak,
+                                                                         const F0CandArgs A) {
+    const PackedFrame f = packed_frame(wav_off, wav_total, frame_off, B, T, blockIdx.x);
+    if (!f.ok) return;
+    const double gp = gpeak[f.b];
+    f0_candidates_frame(wav + f.woff, f.N, rw, freq + (size_t)f.foff * A.ncand, strength + (size_t)f.foff * A.ncand, nout + f.foff,
+                        lag + (size_t)f.foff * A.ncand, rout ? rout + (size_t)f.foff * (A.lmax + 2) : nullptr, f.i,
+                        gp >= 0.0 && gp < INFINITY ? gp : 0.0, A);
+}
+
 // v of another lane of the row of 16 by a DPP move (no LDS crossbar): CTRL 0xB1 = lane ^ 1, 0x4E = lane ^ 2, 0x141 = the mirror lane of
 // the half row (7 - lane), 0x140 = the mirror lane of the row (15 - lane)
 template <int CTRL> __device__ __forceinline__ int f0_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
@@ -269,10 +299,10 @@ template <int CTRL> __device__ __forceinline__ void f0_min_step(double& v, int& 
 // quads, then the mirror lane of the half row and of the row: once the quads agree, the mirror lane holds the other quad's value),
 // the new cost_i[p] comes back to the lanes of column p by one shuffle.  dynamic LDS: T * words unsigned, the back-pointers of frame i
 // at [i * words, (i + 1) * words), four bits a slot; the way back leaves the chosen slot of frame i in the first of them.
-__global__ __launch_bounds__(64) void f0_viterbi_kernel(const float* __restrict__ freq, const float* __restrict__ strength,
-                                                        const int* __restrict__ nv, float* __restrict__ f0, int* __restrict__ path,
-                                                        const int T, const int nc, const int log_group, const int words,
-                                                        const double corr, const double ojc, const double vuc) {
+__device__ __forceinline__ void f0_viterbi_wave(const float* __restrict__ freq, const float* __restrict__ strength,
+                                                const int* __restrict__ nv, float* __restrict__ f0, int* __restrict__ path,
+                                                const int T, const int nc, const int log_group, const int words,
+                                                const double corr, const double ojc, const double vuc) {
     extern __shared__ unsigned bpw[];
     unsigned char* bpb = reinterpret_cast<unsigned char*>(bpw);
     const int lane = threadIdx.x, group = 1 << log_group, log_rows = 6 - log_group, rows = 1 << log_rows;
@@ -369,6 +399,26 @@ __global__ __launch_bounds__(64) void f0_viterbi_kernel(const float* __restrict_
     }
 }
 
+__global__ __launch_bounds__(64) void f0_viterbi_kernel(const float* __restrict__ freq, const float* __restrict__ strength,
+                                                        const int* __restrict__ nv, float* __restrict__ f0, int* __restrict__ path,
+                                                        const int T, const int nc, const int log_group, const int words,
+                                                        const double corr, const double ojc, const double vuc) {
+    f0_viterbi_wave(freq, strength, nv, f0, path, T, nc, log_group, words, corr, ojc, vuc);
+}
+
+// One wave per utterance of the packed batch, its back-pointers in its own workgroup's LDS (max_frames * words unsigned, the
+// longest utterance's).  An utterance whose rows do not lie inside the packed total, or longer than max_frames, is skipped.
+__global__ __launch_bounds__(64) void f0_viterbi_batch_kernel(const float* __restrict__ freq, const float* __restrict__ strength,
+                                                              const int* __restrict__ nv, float* __restrict__ f0, int* __restrict__ path,
+                                                              const long long* __restrict__ frame_off, const int T,
+                                                              const int max_frames, const int nc, const int log_group, const int words,
+                                                              const double corr, const double ojc, const double vuc) {
+    const long long fo = frame_off[blockIdx.x], fe = frame_off[blockIdx.x + 1];
+    if (fo < 0 || fe <= fo || fe > (long long)T || fe - fo > (long long)max_frames) return;
+    f0_viterbi_wave(freq + (size_t)fo * nc, strength + (size_t)fo * nc, nv + fo, f0 + fo, path ? path + fo : nullptr, (int)(fe - fo), nc,
+                    log_group, words, corr, ojc, vuc);
+}
+
 constexpr int F0_REFINE_MAX_WINDOW = 16384;             // samples of the window at f0_min
 constexpr int F0_REFINE_H1 = 2, F0_REFINE_H2 = 6;       // harmonics of the two passes
 
@@ -447,12 +497,10 @@ template <int H> __device__ __forceinline__ bool f0_refine_pass(const float* __r
 // One workgroup per frame: its lanes share the window's samples, one block sum a pass.  Every exit before or between the block sums
 // depends on f0[i], the launch's scalars and the block sums alone, the same in every lane.  static LDS: 4 waves * 24 doubles.
 // The host has checked 2 rnd(1.5 fs / f0_min) + 1 <= F0_REFINE_MAX_WINDOW, so hw fits an int.
-__global__ __launch_bounds__(F0_THREADS) void f0_refine_kernel(const float* __restrict__ wav, const long long N,
-                                                               const float* __restrict__ f0, float* __restrict__ out,
-                                                               int* __restrict__ status, const double shift, const double fs,
-                                                               const double f0_min, const double f0_max) {
+__device__ __forceinline__ void f0_refine_frame(const float* __restrict__ wav, const long long N, const float* __restrict__ f0,
+                                                float* __restrict__ out, int* __restrict__ status, const int i, const double shift,
+                                                const double fs, const double f0_min, const double f0_max) {
     __shared__ double red[(F0_THREADS / 64) * 4 * F0_REFINE_H2];
-    const int i = blockIdx.x;
     const float fin = f0[i];
     const double f = (double)fin;
     float res = fin;
@@ -480,6 +528,69 @@ __global__ __launch_bounds__(F0_THREADS) void f0_refine_kernel(const float* __re
     }
 }
 
+__global__ __launch_bounds__(F0_THREADS) void f0_refine_kernel(const float* __restrict__ wav, const long long N,
+                                                               const float* __restrict__ f0, float* __restrict__ out,
+                                                               int* __restrict__ status, const double shift, const double fs,
+                                                               const double f0_min, const double f0_max) {
+    f0_refine_frame(wav, N, f0, out, status, blockIdx.x, shift, fs, f0_min, f0_max);
+}
+
+// One workgroup per frame of the packed batch.
+__global__ __launch_bounds__(F0_THREADS) void f0_refine_batch_kernel(const float* __restrict__ wav, const long long* __restrict__ wav_off,
+                                                                     const long long wav_total, const long long* __restrict__ frame_off,
+                                                                     const int B, const int T, const float* __restrict__ f0,
+                                                                     float* __restrict__ out, int* __restrict__ status,
+                                                                     const double shift, const double fs, const double f0_min,
+                                                                     const double f0_max) {
+    const PackedFrame f = packed_frame(wav_off, wav_total, frame_off, B, T, blockIdx.x);
+    if (!f.ok) return;
+    f0_refine_frame(wav + f.woff, f.N, f0 + f.foff, out + f.foff, status ? status + f.foff : nullptr, f.i, shift, fs, f0_min, f0_max);
+}
+
+// The checks of ptts_f0_candidates and its batched form that do not depend on the tensors -> the launch's scalars and LDS bytes
+static int f0_candidates_args(const char* what, int ncand, double shift, double fs, int dftlen, double f0_min, double f0_max,
+                              double voicing_threshold, double silence_threshold, double octave_cost, F0CandArgs& A, int& lds) {
+    PTTS_REQUIRE(ncand >= F0_MIN_NCAND && ncand <= F0_MAX_NCAND, "%s: ncand=%d outside [%d, %d]", what, ncand, F0_MIN_NCAND, F0_MAX_NCAND);
+    const int logL = frame_log2(dftlen);
+    PTTS_REQUIRE(logL > 0, "%s: dftlen=%d is not a power of two in [%d, %d]", what, dftlen, FRAME_MIN_DFTLEN, FRAME_MAX_DFTLEN);
+    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "%s: fs=%g", what, fs);
+    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "%s: shift=%g", what, shift);
+    PTTS_REQUIRE(f0_min > 0.0 && f0_min <= f0_max && f0_max <= 0.5 * fs, "%s: f0_min=%g f0_max=%g (positive, ordered, at most fs/2)", what,
+                 f0_min, f0_max);
+    PTTS_REQUIRE(voicing_threshold > 0.0 && voicing_threshold < 1e3 && silence_threshold > 0.0 && silence_threshold < 1e3 &&
+                 octave_cost >= 0.0 && octave_cost < 1e3, "%s: voicing_threshold=%g silence_threshold=%g octave_cost=%g", what,
+                 voicing_threshold, silence_threshold, octave_cost);
+    const double hwd = 1.5 * fs / f0_min;
+    PTTS_REQUIRE(hwd < (double)dftlen, "%s: the window at f0_min=%g does not fit dftlen=%d", what, f0_min, dftlen);
+    const int hw = (int)hwd, lmin = (int)ceil(fs / f0_max), lmax = (int)floor(fs / f0_min);
+    PTTS_REQUIRE(2 * hw + 1 + lmax + 1 <= dftlen, "%s: the window at f0_min=%g (%d samples) and its longest lag (%d) do not fit dftlen=%d",
+                 what, f0_min, 2 * hw + 1, lmax, dftlen);
+    PTTS_REQUIRE(lmin >= 1 && lmin <= lmax, "%s: lags %d .. %d", what, lmin, lmax);
+    const int M = dftlen / 2;
+    lds = (M + M / 4) * (int)sizeof(double2) + (lmax + 2 + 4) * (int)sizeof(double) + 4 * (int)sizeof(int);
+    A = F0CandArgs{logL - 1, hw, lmin, lmax, ncand, shift, fs, f0_min, f0_max, voicing_threshold, silence_threshold, octave_cost};
+    return PTTS_OK;
+}
+
+static int f0_viterbi_args(const char* what, int ncand, double shift, double octave_jump_cost, double voiced_unvoiced_cost) {
+    PTTS_REQUIRE(ncand >= F0_MIN_NCAND && ncand <= F0_MAX_NCAND, "%s: ncand=%d outside [%d, %d]", what, ncand, F0_MIN_NCAND, F0_MAX_NCAND);
+    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "%s: shift=%g", what, shift);
+    PTTS_REQUIRE(octave_jump_cost >= 0.0 && octave_jump_cost < 1e3 && voiced_unvoiced_cost >= 0.0 && voiced_unvoiced_cost < 1e3,
+                 "%s: octave_jump_cost=%g voiced_unvoiced_cost=%g", what, octave_jump_cost, voiced_unvoiced_cost);
+    return PTTS_OK;
+}
+
+static int f0_refine_args(const char* what, double shift, double fs, double f0_min, double f0_max) {
+    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "%s: fs=%g", what, fs);
+    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "%s: shift=%g", what, shift);
+    PTTS_REQUIRE(f0_min > 0.0 && f0_min <= f0_max && f0_max <= 0.5 * fs, "%s: f0_min=%g f0_max=%g (positive, ordered, at most fs/2)", what,
+                 f0_min, f0_max);
+    const double W = 2.0 * floor(1.5 * fs / f0_min + 0.5) + 1.0;
+    PTTS_REQUIRE(W <= (double)F0_REFINE_MAX_WINDOW, "%s: the window at f0_min=%g (%.0f samples) is longer than %d", what, f0_min, W,
+                 F0_REFINE_MAX_WINDOW);
+    return PTTS_OK;
+}
+
 }  // namespace ptts
 
 using namespace ptts;
@@ -488,36 +599,43 @@ extern "C" int ptts_f0_candidates(const float* wav, long long N, const double* r
                                   int* lag, float* r, int T, int ncand, double shift, double fs, int dftlen, double f0_min, double f0_max,
                                   double gpeak, double voicing_threshold, double silence_threshold, double octave_cost, void* stream) {
     PTTS_REQUIRE(T >= 0 && N >= 0, "f0_candidates: T=%d N=%lld", T, N);
-    PTTS_REQUIRE(ncand >= F0_MIN_NCAND && ncand <= F0_MAX_NCAND, "f0_candidates: ncand=%d outside [%d, %d]", ncand, F0_MIN_NCAND,
-                 F0_MAX_NCAND);
-    const int logL = frame_log2(dftlen);
-    PTTS_REQUIRE(logL > 0, "f0_candidates: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN, FRAME_MAX_DFTLEN);
-    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "f0_candidates: fs=%g", fs);
-    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "f0_candidates: shift=%g", shift);
-    PTTS_REQUIRE(f0_min > 0.0 && f0_min <= f0_max && f0_max <= 0.5 * fs, "f0_candidates: f0_min=%g f0_max=%g (positive, ordered, at most fs/2)",
-                 f0_min, f0_max);
+    F0CandArgs A;
+    int lds;
+    int rc = f0_candidates_args("f0_candidates", ncand, shift, fs, dftlen, f0_min, f0_max, voicing_threshold, silence_threshold,
+                                octave_cost, A, lds);
+    if (rc != PTTS_OK) return rc;
     PTTS_REQUIRE(gpeak >= 0.0 && gpeak < INFINITY, "f0_candidates: gpeak=%g", gpeak);
-    PTTS_REQUIRE(voicing_threshold > 0.0 && voicing_threshold < 1e3 && silence_threshold > 0.0 && silence_threshold < 1e3 &&
-                 octave_cost >= 0.0 && octave_cost < 1e3, "f0_candidates: voicing_threshold=%g silence_threshold=%g octave_cost=%g",
-                 voicing_threshold, silence_threshold, octave_cost);
-    const double hwd = 1.5 * fs / f0_min;
-    PTTS_REQUIRE(hwd < (double)dftlen, "f0_candidates: the window at f0_min=%g does not fit dftlen=%d", f0_min, dftlen);
-    const int hw = (int)hwd, lmin = (int)ceil(fs / f0_max), lmax = (int)floor(fs / f0_min);
-    PTTS_REQUIRE(2 * hw + 1 + lmax + 1 <= dftlen, "f0_candidates: the window at f0_min=%g (%d samples) and its longest lag (%d) do not fit dftlen=%d",
-                 f0_min, 2 * hw + 1, lmax, dftlen);
-    PTTS_REQUIRE(lmin >= 1 && lmin <= lmax, "f0_candidates: lags %d .. %d", lmin, lmax);
     if (T == 0) return PTTS_OK;
     PTTS_REQUIRE(freq && strength && n && lag && (wav || N == 0), "f0_candidates: null tensor");
-    PTTS_REQUIRE(rw && ((size_t)rw & 7) == 0 && rw_bytes >= (size_t)(lmax + 2) * sizeof(double),
-                 "f0_candidates: the window table needs %zu bytes, got %zu", (size_t)(lmax + 2) * sizeof(double), rw_bytes);
-    const int M = dftlen / 2;
-    const int lds = (M + M / 4) * (int)sizeof(double2) + (lmax + 2 + 4) * (int)sizeof(double) + 4 * (int)sizeof(int);
-    const int rc = reserve_lds<f0_candidates_kernel>("f0_candidates", lds);
+    PTTS_REQUIRE(rw && ((size_t)rw & 7) == 0 && rw_bytes >= (size_t)(A.lmax + 2) * sizeof(double),
+                 "f0_candidates: the window table needs %zu bytes, got %zu", (size_t)(A.lmax + 2) * sizeof(double), rw_bytes);
+    rc = reserve_lds<f0_candidates_kernel>("f0_candidates", lds);
     if (rc != PTTS_OK) return rc;
-    hipLaunchKernelGGL(f0_candidates_kernel, dim3(T), dim3(frame_threads(M, F0_THREADS)), (size_t)lds, (hipStream_t)stream, wav, N, rw, freq,
-                       strength, n, lag, r, logL - 1, hw, lmin, lmax, ncand, shift, fs, f0_min, f0_max, gpeak, voicing_threshold,
-                       silence_threshold, octave_cost);
+    hipLaunchKernelGGL(f0_candidates_kernel, dim3(T), dim3(frame_threads(dftlen / 2, F0_THREADS)), (size_t)lds, (hipStream_t)stream, wav, N,
+                       rw, freq, strength, n, lag, r, gpeak, A);
     return check_launch("f0_candidates");
+}
+
+extern "C" int ptts_f0_candidates_batch(const float* wav, const long long* wav_off, long long wav_total, const long long* frame_off, int B,
+                                        int T, const double* rw, size_t rw_bytes, float* freq, float* strength, int* n, int* lag,
+                                        float* r, int ncand, double shift, double fs, int dftlen, double f0_min, double f0_max,
+                                        const double* gpeak, double voicing_threshold, double silence_threshold, double octave_cost,
+                                        void* stream) {
+    PTTS_REQUIRE(T >= 0 && wav_total >= 0 && B >= 0 && B <= PACKED_MAX_UTTS, "f0_candidates_batch: T=%d wav_total=%lld B=%d", T, wav_total, B);
+    F0CandArgs A;
+    int lds;
+    int rc = f0_candidates_args("f0_candidates_batch", ncand, shift, fs, dftlen, f0_min, f0_max, voicing_threshold, silence_threshold,
+                                octave_cost, A, lds);
+    if (rc != PTTS_OK) return rc;
+    if (T == 0 || B == 0) return PTTS_OK;
+    PTTS_REQUIRE(freq && strength && n && lag && wav_off && frame_off && gpeak && (wav || wav_total == 0), "f0_candidates_batch: null tensor");
+    PTTS_REQUIRE(rw && ((size_t)rw & 7) == 0 && rw_bytes >= (size_t)(A.lmax + 2) * sizeof(double),
+                 "f0_candidates_batch: the window table needs %zu bytes, got %zu", (size_t)(A.lmax + 2) * sizeof(double), rw_bytes);
+    rc = reserve_lds<f0_candidates_batch_kernel>("f0_candidates_batch", lds);
+    if (rc != PTTS_OK) return rc;
+    hipLaunchKernelGGL(f0_candidates_batch_kernel, dim3(T), dim3(frame_threads(dftlen / 2, F0_THREADS)), (size_t)lds, (hipStream_t)stream,
+                       wav, wav_off, wav_total, frame_off, B, T, rw, freq, strength, n, lag, r, gpeak, A);
+    return check_launch("f0_candidates_batch");
 }
 
 extern "C" int ptts_f0_viterbi_max_frames(int ncand) {
@@ -527,38 +645,66 @@ extern "C" int ptts_f0_viterbi_max_frames(int ncand) {
 
 extern "C" int ptts_f0_viterbi(const float* freq, const float* strength, const int* n, float* f0, int* path, int T, int ncand, double shift,
                                double octave_jump_cost, double voiced_unvoiced_cost, void* stream) {
-    PTTS_REQUIRE(ncand >= F0_MIN_NCAND && ncand <= F0_MAX_NCAND, "f0_viterbi: ncand=%d outside [%d, %d]", ncand, F0_MIN_NCAND, F0_MAX_NCAND);
+    int rc = f0_viterbi_args("f0_viterbi", ncand, shift, octave_jump_cost, voiced_unvoiced_cost);
+    if (rc != PTTS_OK) return rc;
     PTTS_REQUIRE(T >= 0 && T <= ptts_f0_viterbi_max_frames(ncand), "f0_viterbi: T=%d frames, at most %d with ncand=%d", T,
                  ptts_f0_viterbi_max_frames(ncand), ncand);
-    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "f0_viterbi: shift=%g", shift);
-    PTTS_REQUIRE(octave_jump_cost >= 0.0 && octave_jump_cost < 1e3 && voiced_unvoiced_cost >= 0.0 && voiced_unvoiced_cost < 1e3,
-                 "f0_viterbi: octave_jump_cost=%g voiced_unvoiced_cost=%g", octave_jump_cost, voiced_unvoiced_cost);
     if (T == 0) return PTTS_OK;
     PTTS_REQUIRE(freq && strength && n && f0, "f0_viterbi: null tensor");
     int log_group = 1;
     while ((1 << log_group) < ncand) ++log_group;
     const int words = ncand <= 8 ? 1 : 2;
     const int lds = T * words * (int)sizeof(unsigned);
-    const int rc = reserve_lds<f0_viterbi_kernel>("f0_viterbi", lds);
+    rc = reserve_lds<f0_viterbi_kernel>("f0_viterbi", lds);
     if (rc != PTTS_OK) return rc;
     hipLaunchKernelGGL(f0_viterbi_kernel, dim3(1), dim3(64), (size_t)lds, (hipStream_t)stream, freq, strength, n, f0, path, T, ncand, log_group,
                        words, 0.01 / shift, octave_jump_cost, voiced_unvoiced_cost);
     return check_launch("f0_viterbi");
 }
 
+extern "C" int ptts_f0_viterbi_batch(const float* freq, const float* strength, const int* n, float* f0, int* path,
+                                     const long long* frame_off, int B, int T, int max_frames, int ncand, double shift,
+                                     double octave_jump_cost, double voiced_unvoiced_cost, void* stream) {
+    int rc = f0_viterbi_args("f0_viterbi_batch", ncand, shift, octave_jump_cost, voiced_unvoiced_cost);
+    if (rc != PTTS_OK) return rc;
+    PTTS_REQUIRE(T >= 0 && B >= 0 && B <= PACKED_MAX_UTTS, "f0_viterbi_batch: T=%d B=%d", T, B);
+    PTTS_REQUIRE(max_frames >= 0 && max_frames <= ptts_f0_viterbi_max_frames(ncand),
+                 "f0_viterbi_batch: max_frames=%d, an utterance has at most %d with ncand=%d", max_frames,
+                 ptts_f0_viterbi_max_frames(ncand), ncand);
+    if (T == 0 || B == 0 || max_frames == 0) return PTTS_OK;
+    PTTS_REQUIRE(freq && strength && n && f0 && frame_off, "f0_viterbi_batch: null tensor");
+    int log_group = 1;
+    while ((1 << log_group) < ncand) ++log_group;
+    const int words = ncand <= 8 ? 1 : 2;
+    const int lds = max_frames * words * (int)sizeof(unsigned);
+    rc = reserve_lds<f0_viterbi_batch_kernel>("f0_viterbi_batch", lds);
+    if (rc != PTTS_OK) return rc;
+    hipLaunchKernelGGL(f0_viterbi_batch_kernel, dim3(B), dim3(64), (size_t)lds, (hipStream_t)stream, freq, strength, n, f0, path, frame_off,
+                       T, max_frames, ncand, log_group, words, 0.01 / shift, octave_jump_cost, voiced_unvoiced_cost);
+    return check_launch("f0_viterbi_batch");
+}
+
 extern "C" int ptts_f0_refine(const float* wav, long long N, const float* f0, float* out, int* status, int T, double shift, double fs,
                               double f0_min, double f0_max, void* stream) {
     PTTS_REQUIRE(T >= 0 && N >= 0, "f0_refine: T=%d N=%lld", T, N);
-    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "f0_refine: fs=%g", fs);
-    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "f0_refine: shift=%g", shift);
-    PTTS_REQUIRE(f0_min > 0.0 && f0_min <= f0_max && f0_max <= 0.5 * fs, "f0_refine: f0_min=%g f0_max=%g (positive, ordered, at most fs/2)",
-                 f0_min, f0_max);
-    const double W = 2.0 * floor(1.5 * fs / f0_min + 0.5) + 1.0;
-    PTTS_REQUIRE(W <= (double)F0_REFINE_MAX_WINDOW, "f0_refine: the window at f0_min=%g (%.0f samples) is longer than %d", f0_min, W,
-                 F0_REFINE_MAX_WINDOW);
+    const int rc = f0_refine_args("f0_refine", shift, fs, f0_min, f0_max);
+    if (rc != PTTS_OK) return rc;
     if (T == 0) return PTTS_OK;
     PTTS_REQUIRE(f0 && out && (wav || N == 0), "f0_refine: null tensor");
     hipLaunchKernelGGL(f0_refine_kernel, dim3(T), dim3(F0_THREADS), 0, (hipStream_t)stream, wav, N, f0, out, status, shift, fs, f0_min,
                        f0_max);
     return check_launch("f0_refine");
+}
+
+extern "C" int ptts_f0_refine_batch(const float* wav, const long long* wav_off, long long wav_total, const long long* frame_off, int B,
+                                    int T, const float* f0, float* out, int* status, double shift, double fs, double f0_min,
+                                    double f0_max, void* stream) {
+    PTTS_REQUIRE(T >= 0 && wav_total >= 0 && B >= 0 && B <= PACKED_MAX_UTTS, "f0_refine_batch: T=%d wav_total=%lld B=%d", T, wav_total, B);
+    const int rc = f0_refine_args("f0_refine_batch", shift, fs, f0_min, f0_max);
+    if (rc != PTTS_OK) return rc;
+    if (T == 0 || B == 0) return PTTS_OK;
+    PTTS_REQUIRE(f0 && out && wav_off && frame_off && (wav || wav_total == 0), "f0_refine_batch: null tensor");
+    hipLaunchKernelGGL(f0_refine_batch_kernel, dim3(T), dim3(F0_THREADS), 0, (hipStream_t)stream, wav, wav_off, wav_total, frame_off, B, T,
+                       f0, out, status, shift, fs, f0_min, f0_max);
+    return check_launch("f0_refine_batch");
 }

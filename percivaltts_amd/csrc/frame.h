@@ -46,6 +46,38 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     return tot;
 }
 
+// A batch of utterances packed one after the other (the *_batch forms of the analysis kernels): utterance b has the samples
+// wav_off[b] .. wav_off[b+1] of one waveform buffer and the frame rows frame_off[b] .. frame_off[b+1] of every per-frame tensor,
+// both offset rows [B+1] int64 in device memory, ascending from 0.
+constexpr int PACKED_MAX_UTTS = 65535;
+
+struct PackedFrame {
+    int b, i, T;                // the utterance, the frame's index within it, the utterance's frames
+    long long N, woff, foff;    // the utterance's samples, its first sample, its first frame
+    bool ok;                    // false: the offsets do not lie inside the totals; nothing of the frame is read or written
+};
+
+// Global frame g (0 <= g < T_total) of the packing: a binary search for the first utterance with frame_off[b + 1] > g.
+__device__ __forceinline__ PackedFrame packed_frame(const long long* __restrict__ wav_off, long long wav_total,
+                                                    const long long* __restrict__ frame_off, int B, int T_total, long long g) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (frame_off[mid + 1] > g) hi = mid; else lo = mid + 1;
+    }
+    PackedFrame f;
+    f.b = lo;
+    f.foff = frame_off[lo];
+    const long long fe = frame_off[lo + 1];
+    f.woff = wav_off ? wav_off[lo] : 0;
+    const long long we = wav_off ? wav_off[lo + 1] : 0;
+    f.N = we - f.woff;
+    f.i = (int)(g - f.foff);
+    f.T = (int)(fe - f.foff);
+    f.ok = f.foff >= 0 && g >= f.foff && g < fe && fe <= (long long)T_total && f.woff >= 0 && we >= f.woff && we <= wav_total;
+    return f;
+}
+
 // wq[j] = exp(-2 pi i j / M), 0 <= j < M/4.  Not followed by a barrier: the transforms open with one.
 __device__ __forceinline__ void fill_twiddles(double2* wq, int M) {
     for (int j = threadIdx.x; j < (M >> 2); j += blockDim.x) {

@@ -95,17 +95,17 @@ __device__ __forceinline__ double wa_lifter(int q, double r, double fs) {
     return sinc * ((1.0 - 2.0 * WA_Q1) + 2.0 * WA_Q1 * cospi(2.0 * x));
 }
 
-// One workgroup per frame.  dynamic LDS: (M + M/4) double2 + K doubles.
-__global__ __launch_bounds__(WA_THREADS) void world_envelope_kernel(const float* __restrict__ wav, const long long N,
-                                                                    const float* __restrict__ ratev, float* __restrict__ spec,
-                                                                    const int logM, const double shift, const double fs,
-                                                                    const bool log_out) {
+// Frame i of one utterance: wav [N] its samples, ratev and spec its own rows.  The workgroup's work; dynamic LDS:
+// (M + M/4) double2 + K doubles.
+__device__ __forceinline__ void world_envelope_frame(const float* __restrict__ wav, const long long N, const float* __restrict__ ratev,
+                                                     float* __restrict__ spec, const int i, const int logM, const double shift,
+                                                     const double fs, const bool log_out) {
     extern __shared__ double2 lds[];
     const int M = 1 << logM, L = M << 1, K = M + 1, Mq = M >> 2;
     double2* a = lds;
     double2* wq = lds + M;
     double* P = reinterpret_cast<double*>(lds + M + Mq);
-    const int i = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int tid = threadIdx.x, nthr = blockDim.x;
     const double r = (double)ratev[i];
     int hw;
     // a frame the host checks would have refused: nothing of it is read or written
@@ -168,13 +168,31 @@ __global__ __launch_bounds__(WA_THREADS) void world_envelope_kernel(const float*
     }
 }
 
-// One workgroup per frame.  dynamic LDS: (2 M + M/4 + 2) double2 + nb doubles.
-__global__ __launch_bounds__(WA_THREADS) void world_aperiodicity_kernel(const float* __restrict__ wav, const long long N,
-                                                                        const float* __restrict__ f0v,
-                                                                        const float* __restrict__ voicedv, float* __restrict__ aper,
-                                                                        const int nb, const int Kp, const int logM,
-                                                                        const double shift, const double fs,
-                                                                        const double* __restrict__ fw) {
+// One workgroup per frame.
+__global__ __launch_bounds__(WA_THREADS) void world_envelope_kernel(const float* __restrict__ wav, const long long N,
+                                                                    const float* __restrict__ ratev, float* __restrict__ spec,
+                                                                    const int logM, const double shift, const double fs,
+                                                                    const bool log_out) {
+    world_envelope_frame(wav, N, ratev, spec, blockIdx.x, logM, shift, fs, log_out);
+}
+
+// One workgroup per frame of the packed batch.
+__global__ __launch_bounds__(WA_THREADS) void world_envelope_batch_kernel(const float* __restrict__ wav, const long long* __restrict__ wav_off,
+                                                                          const long long wav_total, const long long* __restrict__ frame_off,
+                                                                          const int B, const int T, const float* __restrict__ ratev,
+                                                                          float* __restrict__ spec, const int logM, const double shift,
+                                                                          const double fs, const bool log_out) {
+    const PackedFrame f = packed_frame(wav_off, wav_total, frame_off, B, T, blockIdx.x);
+    if (!f.ok) return;
+    world_envelope_frame(wav + f.woff, f.N, ratev + f.foff, spec + (size_t)f.foff * ((1 << logM) + 1), f.i, logM, shift, fs, log_out);
+}
+
+// Frame i of one utterance: wav [N] its samples, f0v, voicedv and aper its own rows.  The workgroup's work; dynamic LDS:
+// (2 M + M/4 + 2) double2 + nb doubles.
+__device__ __forceinline__ void world_aperiodicity_frame(const float* __restrict__ wav, const long long N, const float* __restrict__ f0v,
+                                                         const float* __restrict__ voicedv, float* __restrict__ aper, const int i,
+                                                         const int nb, const int Kp, const int logM, const double shift,
+                                                         const double fs, const double* __restrict__ fw) {
     extern __shared__ double2 lds[];
     const int M = 1 << logM, L = M << 1, K = M + 1, Mq = M >> 2;
     double2* a1 = lds;                  // X1, then (D_k, E_k) at the bit-reversed address of k, bin 0 in slot 0
@@ -182,7 +200,7 @@ __global__ __launch_bounds__(WA_THREADS) void world_aperiodicity_kernel(const fl
     double2* wq = lds + 2 * M;
     double2* xm = lds + 2 * M + Mq;     // bin M: (D_M, E_M), (lower band, fraction)
     double* rho = reinterpret_cast<double*>(lds + 2 * M + Mq + 2);
-    const int i = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    const int tid = threadIdx.x, nthr = blockDim.x;
     float* row = aper + (size_t)i * nb;
     if (!((double)voicedv[i] >= 0.5)) {
         for (int b = tid; b < nb; b += nthr) row[b] = 0.f;
@@ -285,6 +303,28 @@ __global__ __launch_bounds__(WA_THREADS) void world_aperiodicity_kernel(const fl
     }
 }
 
+// One workgroup per frame.
+__global__ __launch_bounds__(WA_THREADS) void world_aperiodicity_kernel(const float* __restrict__ wav, const long long N,
+                                                                        const float* __restrict__ f0v,
+                                                                        const float* __restrict__ voicedv, float* __restrict__ aper,
+                                                                        const int nb, const int Kp, const int logM,
+                                                                        const double shift, const double fs,
+                                                                        const double* __restrict__ fw) {
+    world_aperiodicity_frame(wav, N, f0v, voicedv, aper, blockIdx.x, nb, Kp, logM, shift, fs, fw);
+}
+
+// One workgroup per frame of the packed batch.
+__global__ __launch_bounds__(WA_THREADS) void world_aperiodicity_batch_kernel(const float* __restrict__ wav, const long long* __restrict__ wav_off,
+                                                                              const long long wav_total, const long long* __restrict__ frame_off,
+                                                                              const int B, const int T, const float* __restrict__ f0v,
+                                                                              const float* __restrict__ voicedv, float* __restrict__ aper,
+                                                                              const int nb, const int Kp, const int logM, const double shift,
+                                                                              const double fs, const double* __restrict__ fw) {
+    const PackedFrame f = packed_frame(wav_off, wav_total, frame_off, B, T, blockIdx.x);
+    if (!f.ok) return;
+    world_aperiodicity_frame(wav + f.woff, f.N, f0v + f.foff, voicedv + f.foff, aper + (size_t)f.foff * nb, f.i, nb, Kp, logM, shift, fs, fw);
+}
+
 }  // namespace ptts
 
 using namespace ptts;
@@ -329,4 +369,48 @@ extern "C" int ptts_world_aperiodicity(const float* wav, long long N, const floa
     hipLaunchKernelGGL(world_aperiodicity_kernel, dim3(T), dim3(frame_threads(M, WA_THREADS)), (size_t)lds, (hipStream_t)stream, wav, N,
                        f0, voiced, aper, nb, Kp, logL - 1, shift, fs, fwtable);
     return check_launch("world_aperiodicity");
+}
+
+extern "C" int ptts_world_envelope_batch(const float* wav, const long long* wav_off, long long wav_total, const long long* frame_off, int B,
+                                         int T, const float* rate, float* spec, double shift, double fs, int dftlen, int log_out,
+                                         void* stream) {
+    PTTS_REQUIRE(T >= 0 && wav_total >= 0 && B >= 0 && B <= PACKED_MAX_UTTS, "world_envelope_batch: T=%d wav_total=%lld B=%d", T, wav_total, B);
+    const int logL = frame_log2(dftlen);
+    PTTS_REQUIRE(logL > 0, "world_envelope_batch: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN, FRAME_MAX_DFTLEN);
+    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "world_envelope_batch: fs=%g", fs);
+    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "world_envelope_batch: shift=%g", shift);
+    if (T == 0 || B == 0) return PTTS_OK;
+    PTTS_REQUIRE(rate && spec && wav_off && frame_off && (wav || wav_total == 0), "world_envelope_batch: null tensor");
+    const int M = dftlen / 2;
+    const int lds = (M + M / 4) * (int)sizeof(double2) + (M + 1) * (int)sizeof(double);
+    const int rc = reserve_lds<world_envelope_batch_kernel>("world_envelope_batch", lds);
+    if (rc != PTTS_OK) return rc;
+    hipLaunchKernelGGL(world_envelope_batch_kernel, dim3(T), dim3(frame_threads(M, WA_THREADS)), (size_t)lds, (hipStream_t)stream, wav, wav_off,
+                       wav_total, frame_off, B, T, rate, spec, logL - 1, shift, fs, log_out != 0);
+    return check_launch("world_envelope_batch");
+}
+
+extern "C" int ptts_world_aperiodicity_batch(const float* wav, const long long* wav_off, long long wav_total, const long long* frame_off,
+                                             int B, int T, const float* f0, const float* voiced, float* aper, int nb, double shift,
+                                             double fs, int dftlen, const double* fwtable, size_t fwtable_bytes, void* stream) {
+    PTTS_REQUIRE(T >= 0 && wav_total >= 0 && B >= 0 && B <= PACKED_MAX_UTTS, "world_aperiodicity_batch: T=%d wav_total=%lld B=%d", T, wav_total,
+                 B);
+    PTTS_REQUIRE(nb >= 2 && nb <= WA_MAX_NB, "world_aperiodicity_batch: nb=%d outside [2, %d]", nb, WA_MAX_NB);
+    const int logL = frame_log2(dftlen);
+    PTTS_REQUIRE(logL > 0, "world_aperiodicity_batch: dftlen=%d is not a power of two in [%d, %d]", dftlen, FRAME_MIN_DFTLEN,
+                 FRAME_MAX_DFTLEN);
+    PTTS_REQUIRE(fs > 0.0 && fs < 1e9, "world_aperiodicity_batch: fs=%g", fs);
+    PTTS_REQUIRE(shift > 0.0 && shift < 1e3, "world_aperiodicity_batch: shift=%g", shift);
+    if (T == 0 || B == 0) return PTTS_OK;
+    PTTS_REQUIRE(f0 && voiced && aper && wav_off && frame_off && (wav || wav_total == 0), "world_aperiodicity_batch: null tensor");
+    PTTS_REQUIRE(fwtable && ((size_t)fwtable & 31) == 0 && fwtable_bytes >= ptts_fwbnd_table_bytes(dftlen),
+                 "world_aperiodicity_batch: the table of ptts_fwbnd_table(dftlen=%d) needs %zu aligned bytes, got %zu", dftlen,
+                 ptts_fwbnd_table_bytes(dftlen), fwtable_bytes);
+    const int M = dftlen / 2, Kp = (M + 1 + 3) / 4 * 4;
+    const int lds = (2 * M + M / 4 + 2) * (int)sizeof(double2) + nb * (int)sizeof(double);
+    const int rc = reserve_lds<world_aperiodicity_batch_kernel>("world_aperiodicity_batch", lds);
+    if (rc != PTTS_OK) return rc;
+    hipLaunchKernelGGL(world_aperiodicity_batch_kernel, dim3(T), dim3(frame_threads(M, WA_THREADS)), (size_t)lds, (hipStream_t)stream, wav,
+                       wav_off, wav_total, frame_off, B, T, f0, voiced, aper, nb, Kp, logL - 1, shift, fs, fwtable);
+    return check_launch("world_aperiodicity_batch");
 }

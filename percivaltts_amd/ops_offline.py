@@ -1,6 +1,7 @@
 """Wrappers of the offline pipeline over the HIP kernels of libpercival_hip.so: parameter generation (MLPG), feature
 composition, spectral envelope decompression, pulse-and-noise synthesis (PML) and periodic-plus-aperiodic synthesis (WORLD), each per
-utterance with a host pulse table or over a batch with the table built on the device, waveform analysis (PML and WORLD), F0 estimation, waveform pre-processing and the label front end.
+utterance with a host pulse table or over a batch with the table built on the device, waveform analysis (PML and WORLD), F0 estimation,
+both per utterance or over a packed batch in one launch per kernel, waveform pre-processing and the label front end.
 
 Argument checks, scratch memory and one C-ABI call (include/percival_hip.h) each; no autograd nodes, no switches, nothing
 of the training path (ops.py, which re-exports the names of __all__).  There is no CPU path.
@@ -30,6 +31,9 @@ __all__ = [
     'world_analysis_check', 'world_envelope', 'world_aperiodicity',
     'F0_MIN_NCAND', 'F0_MAX_NCAND', 'F0_MAX_FRAMES', 'F0_CONSTANTS', 'f0_check', 'f0_frame_count', 'f0_window_table', 'f0_candidates',
     'f0_viterbi', 'f0_estimate', 'F0_REFINE_MAX_WINDOW', 'f0_refine_check', 'f0_refine',
+    'ANALYSIS_MAX_UTTS', 'PackedOffsets', 'packed_offsets', 'analysis_status', 'wave_peak', 'f0_track_lengths', 'f0_track_device',
+    'f0_candidates_batch', 'f0_viterbi_batch', 'f0_estimate_batch', 'f0_refine_batch', 'frame_harmonics_batch',
+    'phase_coherence_batch', 'world_envelope_batch', 'world_aperiodicity_batch',
     'RESAMPLE_MAX_UP', 'RESAMPLE_MAX_TABLE_BYTES', 'HIGHPASS_PADLEN', 'HIGHPASS_MAX_PADLEN', 'PREPROC_MAX_UTTS', 'preproc_check',
     'resample_length', 'resample_table', 'resample', 'highpass_tile', 'highpass_zerophase',
     'LABELS_MAX_LABEL', 'LABELS_CC_POINTS', 'LABELS_ANCHOR_START', 'LABELS_ANCHOR_END', 'LABELS_WILD', 'LABELS_CAPTURE_DIGITS',
@@ -1267,6 +1271,354 @@ def f0_refine(wav, f0, shift, fs, f0_min, f0_max, want_status=False):
         call('ptts_f0_refine', ptr(wav) if wav.numel() else None, wav.numel(), ptr(f0), ptr(out), ptr(status), T, float(shift),
              float(fs), float(f0_min), float(f0_max), stream(), tag=(T,))
     return (out.cpu().numpy(), status.cpu().numpy()) if want_status else out.cpu().numpy()
+
+
+# ----------------------------------------------------------------------------------------------
+# waveform analysis over a batch of utterances: csrc/analysisbatch.hip and the *_batch kernels of csrc/f0.hip, csrc/analysis.hip,
+# csrc/worldanalysis.hip.  Device tensors in, device tensors out: nothing here reads a device value back unless it says so.
+# ----------------------------------------------------------------------------------------------
+ANALYSIS_MAX_UTTS = 65535           # utterances of one launch
+# (status bit of include/percival_hip.h, what the ValueError says: the wording of the single-utterance path for the same condition)
+_ANALYSIS_STATUS = tuple((_hip._define('PTTS_ANALYSIS_' + name), text) for name, text in (
+    ('BAD_WAV', 'wav is not a finite [N] waveform'),
+    ('BAD_F0', 'ops.f0_track: f0 has to be [T] finite Hz values, T >= 1'),
+    ('NO_VOICED', 'ops.f0_track: no voiced frame')))
+
+
+class PackedOffsets(object):
+    """The layout of a packed batch along one axis: lengths (a list of ints), off (numpy int64 [B+1]), total, and dev, the offsets as
+    an int64 device tensor (what the *_batch kernels read).  Made by ops.packed_offsets; every batched op takes one wherever it
+    takes a list of lengths, so that a chain of ops uploads the offsets once."""
+
+    def __init__(self, lengths, device):
+        self.lengths = lengths
+        self.off = np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)]).astype(np.int64)
+        self.total = int(self.off[-1])
+        self.dev = torch.from_numpy(self.off).to(device)
+
+    def __len__(self):
+        return len(self.lengths)
+
+
+def packed_offsets(lengths, device, fn='packed_offsets', what='lengths'):
+    """A list of non-negative lengths (or a PackedOffsets, returned as it is) -> the PackedOffsets on `device`."""
+    if isinstance(lengths, PackedOffsets):
+        return lengths
+    try:
+        lengths = [int(n) for n in lengths]
+    except (TypeError, ValueError):
+        raise ValueError('ops.{}: {} has to be the utterances\' lengths'.format(fn, what))
+    if not 1 <= len(lengths) <= ANALYSIS_MAX_UTTS or min(lengths) < 0:
+        raise ValueError('ops.{}: {} has to hold 1 to {} lengths of at least 0'.format(fn, what, ANALYSIS_MAX_UTTS))
+    if sum(lengths) >= 1 << 40:
+        raise ValueError('ops.{}: {} sum to {}'.format(fn, what, sum(lengths)))
+    return PackedOffsets(lengths, device)
+
+
+def analysis_status(fn, info):
+    """The one read-back of a batched analysis: info [B] int32 device, the PTTS_ANALYSIS_* bits of every utterance -> ValueError
+    naming the first utterance that has one set."""
+    info = info.cpu().numpy()
+    for b in range(info.size):
+        for bit, text in _ANALYSIS_STATUS:
+            if info[b] & bit:
+                raise ValueError('{}: utterance {}: {}'.format(fn, b, text))
+
+
+def _batch_layout(fn, wav, wav_lengths, frame_lengths, **rows):
+    """The checks the batched frame ops share: wav [sum N] or None, and the per-frame rows [sum T, ..] (fp32 device unless said
+    otherwise, no backward) -> (wav layout or None, frame layout)."""
+    first = next(t for t in list(rows.values()) + [wav] if t is not None)
+    if not torch.is_tensor(first):
+        raise ValueError('ops.{}: expected device tensors'.format(fn))
+    fo = packed_offsets(frame_lengths, first.device, fn, 'frame_lengths')
+    if fo.total >= 1 << 31:
+        raise ValueError('ops.{}: {} frames'.format(fn, fo.total))
+    wo = None
+    if wav is not None:
+        wo = packed_offsets(wav_lengths, first.device, fn, 'wav_lengths')
+        if len(wo) != len(fo):
+            raise ValueError('ops.{}: {} waveforms and {} frame counts'.format(fn, len(wo), len(fo)))
+        if not torch.is_tensor(wav) or tuple(wav.shape) != (wo.total,):
+            raise ValueError('ops.{}: wav is not [sum(wav_lengths)={}]'.format(fn, wo.total))
+        f32c(wav, '{}.wav'.format(fn))
+        _no_backward(fn, wav)
+    for name, t in rows.items():
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.dim() < 1 or t.shape[0] != fo.total:
+            raise ValueError('ops.{}: {} is not [sum(frame_lengths)={}, ..]'.format(fn, name, fo.total))
+        _no_backward(fn, t)
+    return wo, fo
+
+
+def _wav_args(wav, wo):
+    return ptr(wav) if wo.total else None, ptr(wo.dev), wo.total
+
+
+def _info(info, B, device, fn):
+    if info is None:
+        return torch.zeros(B, dtype=torch.int32, device=device), True
+    _dev_tensor(info, torch.int32, '{}.info'.format(fn), (B,))
+    return info, False
+
+
+def wave_peak(wav, wav_lengths, info=None):
+    """wav [sum N] fp32 device, the utterances one after the other -> gpeak [B] fp64 device, max |x - mean(x)| of every utterance
+    in fp64, what ops.f0_estimate measures for ptts_f0_candidates (csrc/analysisbatch.hip; one workgroup per utterance, a
+    fixed-order sum: the same input gives the same bytes; 0 for an utterance without samples).  A sample that is not finite sets
+    PTTS_ANALYSIS_BAD_WAV in `info` [B] int32 (zeroed by the caller, read by ops.analysis_status); without `info` the op reads the
+    status back itself and raises the ValueError."""
+    fn = 'wave_peak'
+    if not torch.is_tensor(wav):
+        raise ValueError('ops.{}: wav is not a packed device tensor'.format(fn))
+    wo = packed_offsets(wav_lengths, wav.device, fn, 'wav_lengths')
+    if tuple(wav.shape) != (wo.total,):
+        raise ValueError('ops.{}: wav is not [sum(wav_lengths)={}]'.format(fn, wo.total))
+    f32c(wav, fn + '.wav')
+    _no_backward(fn, wav)
+    B = len(wo)
+    info, own = _info(info, B, wav.device, fn)
+    gpeak = torch.empty(B, dtype=torch.float64, device=wav.device)
+    call('ptts_wave_peak', *_wav_args(wav, wo), B, ptr(gpeak), ptr(info), stream(), tag=(B, wo.total))
+    if own:
+        analysis_status('ops.' + fn, info)
+    return gpeak
+
+
+def f0_track_lengths(fn, frame_lengths, wav_lengths, shift, fs):
+    """T'_b = min(T_b, f0_frame_count(N_b, shift, fs)), f0_track's cropping rule, with its printed line per cropped utterance."""
+    out = []
+    for T, N in zip(frame_lengths, wav_lengths):
+        keep = min(T, f0_frame_count(N, shift, fs))
+        if keep < T:
+            print('    f0_track: {} of {} frames lie beyond the {} samples of the waveform and are cropped'.format(T - keep, T, N))
+        out.append(keep)
+    return out
+
+
+def f0_track_device(f0, frame_lengths, wav_lengths, f0_min, f0_max, fs, shift, dftlen, info=None):
+    """ops.f0_track for every utterance of a batch, on the device (ptts_f0_track, csrc/analysisbatch.hip; one workgroup per
+    utterance): f0 [sum T] fp32 or fp64 device in Hz (<= 0 unvoiced), the utterances one after the other, frame_lengths their T_b,
+    wav_lengths their waveforms' N_b (lists, or PackedOffsets) -> (track [sum T'] fp32 device, bit for bit ops.f0_track(f0_b, ...,
+    wavlen=N_b) of every utterance; vuv [sum T'] fp32, 1 where f0 > 0; the PackedOffsets of T'_b = min(T_b, f0_frame_count(N_b))).
+    A cropped utterance prints f0_track's line.  What ops.f0_track refuses per utterance (no voiced frame, a value that is not
+    finite) is a PTTS_ANALYSIS_* bit in `info` [B] int32, as in ops.wave_peak; such an utterance's rows are not written."""
+    fn = 'f0_track_device'
+    analysis_check(dftlen, fs, shift, f0_min, f0_max)
+    _, fo = _batch_layout(fn, None, None, frame_lengths, f0=f0)
+    if not (f0.is_cuda and f0.dtype in (torch.float32, torch.float64) and f0.is_contiguous() and f0.dim() == 1):
+        raise _hip.HipLibraryError('{}.f0: expected a contiguous [sum T] float32 or float64 device tensor'.format(fn))
+    wav_lengths = wav_lengths.lengths if isinstance(wav_lengths, PackedOffsets) else [int(n) for n in wav_lengths]
+    if len(wav_lengths) != len(fo) or min(fo.lengths) < 1:
+        raise ValueError('ops.{}: {} waveforms for {} tracks of at least one frame'.format(fn, len(wav_lengths), len(fo)))
+    oo = packed_offsets(f0_track_lengths(fn, fo.lengths, wav_lengths, shift, fs), f0.device, fn)
+    B = len(fo)
+    info, own = _info(info, B, f0.device, fn)
+    track = torch.zeros(oo.total, dtype=torch.float32, device=f0.device)         # zeros: the frame kernels skip a refused utterance's rows
+    vuv = torch.zeros(oo.total, dtype=torch.float32, device=f0.device)
+    call('ptts_f0_track', ptr(f0), int(f0.dtype == torch.float64), ptr(fo.dev), fo.total, ptr(oo.dev), oo.total, B,
+         ptr(track) if oo.total else None, ptr(vuv) if oo.total else None, ptr(info), float(f0_min), float(f0_max), stream(),
+         tag=(B, fo.total))
+    if own:
+        analysis_status('ops.' + fn, info)
+    return track, vuv, oo
+
+
+def f0_candidates_batch(wav, wav_lengths, frame_lengths, shift, fs, dftlen, f0_min, f0_max, gpeak, ncand=8,
+                        voicing_threshold=F0_CONSTANTS['voicing_threshold'], silence_threshold=F0_CONSTANTS['silence_threshold'],
+                        octave_cost=F0_CONSTANTS['octave_cost'], want_r=False):
+    """ops.f0_candidates of a batch in one launch: wav [sum N] fp32 device, frame_lengths the T_b, gpeak [B] fp64 device (ops.wave_peak)
+    -> (freq, strength [sum T, ncand], n [sum T], lag [sum T, ncand]) (and r [sum T, lmax + 2]), utterance b's rows bit for bit
+    ops.f0_candidates(wav_b, T_b, ..., gpeak=gpeak[b])."""
+    fn = 'f0_candidates_batch'
+    _, _, lmax = f0_check(dftlen, fs, shift, f0_min, f0_max)
+    ncand = _f0_ncand(fn, ncand)
+    wo, fo = _batch_layout(fn, wav, wav_lengths, frame_lengths)
+    vt = _f0_number(fn, 'voicing_threshold', voicing_threshold, 0.0, 1e3)
+    st = _f0_number(fn, 'silence_threshold', silence_threshold, 0.0, 1e3)
+    oc = _f0_number(fn, 'octave_cost', octave_cost, 0.0, 1e3, open_lo=False)
+    _dev_tensor(gpeak, torch.float64, fn + '.gpeak', (len(wo),))
+    T, dev = fo.total, wav.device
+    freq = torch.empty((T, ncand), dtype=torch.float32, device=dev)
+    strength = torch.empty((T, ncand), dtype=torch.float32, device=dev)
+    n = torch.empty(T, dtype=torch.int32, device=dev)
+    lag = torch.empty((T, ncand), dtype=torch.int32, device=dev)
+    r = torch.empty((T, lmax + 2), dtype=torch.float32, device=dev) if want_r else None
+    if T > 0:
+        rw = f0_window_table(fs, f0_min, f0_max, device=dev)
+        call('ptts_f0_candidates_batch', *_wav_args(wav, wo), ptr(fo.dev), len(fo), T, ptr(rw), rw.numel() * 8, ptr(freq), ptr(strength),
+             ptr(n), ptr(lag), ptr(r), ncand, float(shift), float(fs), int(dftlen), float(f0_min), float(f0_max), ptr(gpeak), vt, st, oc,
+             stream(), tag=(len(fo), T, int(dftlen), ncand))
+    return (freq, strength, n, lag, r) if want_r else (freq, strength, n, lag)
+
+
+def f0_viterbi_batch(freq, strength, n, frame_lengths, shift, octave_jump_cost=F0_CONSTANTS['octave_jump_cost'],
+                     voiced_unvoiced_cost=F0_CONSTANTS['voiced_unvoiced_cost'], want_path=False):
+    """ops.f0_viterbi of a batch in one launch, one wave per utterance: the packed tables of ops.f0_candidates_batch -> f0 [sum T]
+    fp32 device (with `want_path` also the slots), utterance b's values bit for bit ops.f0_viterbi of its rows.  The frame cap
+    F0_MAX_FRAMES (half of it above 8 slots) holds for each utterance, not for the batch."""
+    fn = 'f0_viterbi_batch'
+    if not torch.is_tensor(freq) or freq.dim() != 2:
+        raise ValueError('ops.{}: freq is not [sum T, ncand]'.format(fn))
+    ncand = _f0_ncand(fn, freq.shape[1])
+    _, fo = _batch_layout(fn, None, None, frame_lengths, freq=freq, strength=strength, n=n)
+    T = fo.total
+    if tuple(strength.shape) != (T, ncand) or tuple(n.shape) != (T,):
+        raise ValueError('ops.{}: strength is not [{},{}] or n is not [{}]'.format(fn, T, ncand, T))
+    cap = F0_MAX_FRAMES if ncand <= 8 else F0_MAX_FRAMES // 2
+    if max(fo.lengths) > cap:
+        raise ValueError('ops.{}: {} frames, one utterance takes at most {} with ncand={}'.format(fn, max(fo.lengths), cap, ncand))
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('shift={} has to be positive'.format(shift))
+    ojc = _f0_number(fn, 'octave_jump_cost', octave_jump_cost, 0.0, 1e3, open_lo=False)
+    vuc = _f0_number(fn, 'voiced_unvoiced_cost', voiced_unvoiced_cost, 0.0, 1e3, open_lo=False)
+    f32c(freq, fn + '.freq'); f32c(strength, fn + '.strength')
+    _dev_tensor(n, torch.int32, fn + '.n')
+    f0 = torch.empty(T, dtype=torch.float32, device=freq.device)
+    path = torch.empty(T, dtype=torch.int32, device=freq.device) if want_path else None
+    if T > 0:
+        call('ptts_f0_viterbi_batch', ptr(freq), ptr(strength), ptr(n), ptr(f0), ptr(path), ptr(fo.dev), len(fo), T, max(fo.lengths), ncand,
+             float(shift), ojc, vuc, stream(), tag=(len(fo), T, ncand))
+    return (f0, path) if want_path else f0
+
+
+def f0_estimate_batch(wav, wav_lengths, shift, fs, dftlen, f0_min, f0_max, ncand=8, info=None, want_gpeak=False, **constants):
+    """ops.f0_estimate of a batch without a read-back: wav [sum N] fp32 device -> (f0 [sum T] fp32 device, 0 where unvoiced, the
+    PackedOffsets of T_b = f0_frame_count(N_b, shift, fs)) (with `want_gpeak` also gpeak [B] fp64 device): ops.wave_peak,
+    ops.f0_candidates_batch, ops.f0_viterbi_batch, one launch each.  Utterance b's track is bit for bit ops.f0_candidates(wav_b,
+    T_b, ..., gpeak=gpeak[b]) followed by ops.f0_viterbi; gpeak[b] and the torch value of ops.f0_estimate may differ in the last
+    bit.  `info` as in ops.wave_peak."""
+    fn = 'f0_estimate_batch'
+    if set(constants) - set(F0_CONSTANTS):
+        raise ValueError('ops.{}: unknown arguments {}'.format(fn, sorted(set(constants) - set(F0_CONSTANTS))))
+    f0_check(dftlen, fs, shift, f0_min, f0_max)
+    ncand = _f0_ncand(fn, ncand)
+    if not torch.is_tensor(wav):
+        raise ValueError('ops.{}: wav is not a packed device tensor'.format(fn))
+    wo = packed_offsets(wav_lengths, wav.device, fn, 'wav_lengths')
+    lengths = [f0_frame_count(N, shift, fs) for N in wo.lengths]
+    cap = F0_MAX_FRAMES if ncand <= 8 else F0_MAX_FRAMES // 2
+    if max(lengths) > cap:
+        raise ValueError('ops.{}: {} frames, one utterance takes at most {} with ncand={}'.format(fn, max(lengths), cap, ncand))
+    fo = packed_offsets(lengths, wav.device, fn)
+    info, own = _info(info, len(wo), wav.device, fn)
+    gpeak = wave_peak(wav, wo, info=info)
+    cand = {k: constants[k] for k in ('voicing_threshold', 'silence_threshold', 'octave_cost') if k in constants}
+    path = {k: constants[k] for k in ('octave_jump_cost', 'voiced_unvoiced_cost') if k in constants}
+    freq, strength, n, _ = f0_candidates_batch(wav, wo, fo, shift, fs, dftlen, f0_min, f0_max, gpeak, ncand=ncand, **cand)
+    f0 = f0_viterbi_batch(freq, strength, n, fo, shift, **path)
+    if own:
+        analysis_status('ops.' + fn, info)
+    return (f0, fo, gpeak) if want_gpeak else (f0, fo)
+
+
+def f0_refine_batch(wav, wav_lengths, f0, frame_lengths, shift, fs, f0_min, f0_max, want_status=False):
+    """ops.f0_refine of a batch in one launch: wav [sum N] and f0 [sum T] fp32 device -> the refined track [sum T] fp32 device (with
+    `want_status` also status [sum T] int32), utterance b's values bit for bit ops.f0_refine(wav_b, f0_b, ...)."""
+    fn = 'f0_refine_batch'
+    f0_refine_check(fs, shift, f0_min, f0_max)
+    wo, fo = _batch_layout(fn, wav, wav_lengths, frame_lengths, f0=f0)
+    if f0.dim() != 1:
+        raise ValueError('ops.{}: f0 is not [sum T]'.format(fn))
+    f32c(f0, fn + '.f0')
+    T = fo.total
+    out = torch.empty(T, dtype=torch.float32, device=wav.device)
+    status = torch.empty(T, dtype=torch.int32, device=wav.device) if want_status else None
+    if T > 0:
+        call('ptts_f0_refine_batch', *_wav_args(wav, wo), ptr(fo.dev), len(fo), T, ptr(f0), ptr(out), ptr(status), float(shift), float(fs),
+             float(f0_min), float(f0_max), stream(), tag=(len(fo), T))
+    return (out, status) if want_status else out
+
+
+def frame_harmonics_batch(wav, wav_lengths, f0, frame_lengths, shift, fs, dftlen, hcap, log=False):
+    """ops.frame_harmonics of a batch in one launch: wav [sum N], f0 [sum T] fp32 device -> (SPEC [sum T, dftlen/2+1], u [sum T, hcap,
+    2]), utterance b's rows bit for bit ops.frame_harmonics(wav_b, f0_b, ...)."""
+    fn = 'frame_harmonics_batch'
+    pulse_check(dftlen, fs)
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('shift={} has to be positive'.format(shift))
+    if int(hcap) != hcap or not 1 <= hcap <= dftlen:
+        raise ValueError('ops.{}: hcap={} outside [1, {}]'.format(fn, hcap, dftlen))
+    wo, fo = _batch_layout(fn, wav, wav_lengths, frame_lengths, f0=f0)
+    if f0.dim() != 1:
+        raise ValueError('ops.{}: f0 is not [sum T]'.format(fn))
+    f32c(f0, fn + '.f0')
+    T, K = fo.total, dftlen // 2 + 1
+    spec = torch.empty((T, K), dtype=torch.float32, device=f0.device)
+    u = torch.empty((T, int(hcap), 2), dtype=torch.float32, device=f0.device)
+    if T > 0:
+        call('ptts_frame_harmonics_batch', *_wav_args(wav, wo), ptr(fo.dev), len(fo), T, ptr(f0), ptr(spec), ptr(u), int(hcap),
+             float(shift), float(fs), int(dftlen), int(bool(log)), stream(), tag=(len(fo), T, dftlen, int(hcap)))
+    return spec, u
+
+
+def phase_coherence_batch(u, f0, frame_lengths, shift, fs, dftlen, nb):
+    """ops.phase_coherence of a batch in one launch: u [sum T, hcap, 2] and f0 [sum T] fp32 device -> (R [sum T, hcap], NM [sum T,
+    nb]), utterance b's rows bit for bit ops.phase_coherence(u_b, f0_b, ...): a frame's neighbourhood ends where its utterance
+    ends."""
+    fn = 'phase_coherence_batch'
+    pulse_check(dftlen, fs)
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('shift={} has to be positive'.format(shift))
+    if not torch.is_tensor(u) or u.dim() != 3 or u.shape[2] != 2 or not 1 <= u.shape[1] <= dftlen:
+        raise ValueError('ops.{}: u is not [sum T, hcap, 2]'.format(fn))
+    _, fo = _batch_layout(fn, None, None, frame_lengths, u=u, f0=f0)
+    T, hcap = fo.total, u.shape[1]
+    if f0.dim() != 1:
+        raise ValueError('ops.{}: f0 is not [{}]'.format(fn, T))
+    fwbnd_compress_check(nb, fs, dftlen)
+    f32c(u, fn + '.u'); f32c(f0, fn + '.f0')
+    R = torch.empty((T, hcap), dtype=torch.float32, device=u.device)
+    nm = torch.empty((T, int(nb)), dtype=torch.float32, device=u.device)
+    if T > 0:
+        fw, fwbytes = _fwbnd_table(u.device, int(nb), fs, bark_alpha(fs), dftlen)
+        ct, ctbytes = _compress_table(u.device, int(nb), fs, dftlen)
+        call('ptts_phase_coherence_batch', ptr(u), ptr(f0), ptr(R), ptr(nm), ptr(fo.dev), len(fo), T, hcap, int(nb), float(shift),
+             float(fs), int(dftlen), ptr(fw), fwbytes, ptr(ct), ctbytes, stream(), tag=(len(fo), T, hcap, int(nb)))
+    return R, nm
+
+
+def _world_frames_batch(fn, wav, wav_lengths, frame_lengths, shift, fs, dftlen, **rows):
+    pulse_check(dftlen, fs)
+    if not 0.0 < float(shift) < 1e3:
+        raise ValueError('shift={} has to be positive'.format(shift))
+    wo, fo = _batch_layout(fn, wav, wav_lengths, frame_lengths, **rows)
+    for name, t in rows.items():
+        if t.dim() != 1:
+            raise ValueError('ops.{}: {} is not [sum T]'.format(fn, name))
+        f32c(t, '{}.{}'.format(fn, name))
+    return wo, fo
+
+
+def world_envelope_batch(wav, wav_lengths, rate, frame_lengths, shift, fs, dftlen, log=False):
+    """ops.world_envelope of a batch in one launch: wav [sum N], rate [sum T] fp32 device -> SPEC [sum T, dftlen/2+1], utterance b's
+    rows bit for bit ops.world_envelope(wav_b, rate_b, ...)."""
+    fn = 'world_envelope_batch'
+    wo, fo = _world_frames_batch(fn, wav, wav_lengths, frame_lengths, shift, fs, dftlen, rate=rate)
+    T = fo.total
+    spec = torch.empty((T, dftlen // 2 + 1), dtype=torch.float32, device=rate.device)
+    if T > 0:
+        call('ptts_world_envelope_batch', *_wav_args(wav, wo), ptr(fo.dev), len(fo), T, ptr(rate), ptr(spec), float(shift), float(fs),
+             int(dftlen), int(bool(log)), stream(), tag=(len(fo), T, dftlen))
+    return spec
+
+
+def world_aperiodicity_batch(wav, wav_lengths, f0, voiced, frame_lengths, shift, fs, dftlen, nb):
+    """ops.world_aperiodicity of a batch in one launch: wav [sum N], f0 and voiced [sum T] fp32 device (a bool `voiced` is
+    converted) -> the band aperiodicities [sum T, nb] in dB, utterance b's rows bit for bit ops.world_aperiodicity(wav_b, ...)."""
+    fn = 'world_aperiodicity_batch'
+    if torch.is_tensor(voiced) and voiced.dtype == torch.bool:
+        voiced = voiced.to(torch.float32)
+    wo, fo = _world_frames_batch(fn, wav, wav_lengths, frame_lengths, shift, fs, dftlen, f0=f0, voiced=voiced)
+    fwbnd_compress_check(nb, fs, dftlen)
+    T = fo.total
+    aper = torch.empty((T, int(nb)), dtype=torch.float32, device=f0.device)
+    if T > 0:
+        fw, fwbytes = _fwbnd_table(f0.device, int(nb), fs, bark_alpha(fs), dftlen)
+        call('ptts_world_aperiodicity_batch', *_wav_args(wav, wo), ptr(fo.dev), len(fo), T, ptr(f0), ptr(voiced), ptr(aper), int(nb),
+             float(shift), float(fs), int(dftlen), ptr(fw), fwbytes, stream(), tag=(len(fo), T, dftlen, int(nb)))
+    return aper
 
 
 # ----------------------------------------------------------------------------------------------

@@ -108,7 +108,7 @@ def features_compose(rawpaths, fids=None, win_convention='mlpg'):
 
 
 def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None, f0_min=70, f0_max=600, win_convention='mlpg',
-                        f0_refine=None, preproc_hp=None):
+                        f0_refine=None, batch_size=None, preproc_hp=None):
     """The reference's features_extraction (run.py:147-165): every file id's waveform `wav_path` ('dir/*.wav', by default
     <corpus>/wav/*.wav) goes through vocoder.analysisfid_device with the F0 track of `f0in_path` ('dir/*.f0': headerless float32 Hz
     values, one per frame, <= 0 unvoiced) or, with f0in_path None, the track of the build's own estimator
@@ -123,17 +123,28 @@ def features_extraction(f0in_path=None, wav_path=None, rawpaths=None, fids=None,
     `rawpaths` = [f0_path, spec_path, noise_path, vuv_path], by default the reference's <wavdir>_WORLD_lf0, .._fwlspec<N>,
     .._fwdbap<N>/*.fwdbap and .._vuv1/*.vuv (run.py:103-105).  `f0_refine`: True or False sets vocoder.f0_refine (the F0
     refinement in front of the analysis, vocoders.VocoderF0Spec.f0_refine_device) for the duration of the call, None leaves the
-    vocoder as it is."""
+    vocoder as it is.  `batch_size`: None analyses file by file as above; k >= 1 collects up to k files (each read with wavread, and
+    passed through vocoder.preprocwav under the same conditions) and analyses them with one vocoder.analysis_device_batch call,
+    every kernel launching once per batch; the files written are the same bytes for every batch_size.  (It stands in front of
+    preproc_hp, which callers pass by keyword and which stays the last parameter.)"""
+    _check_batch_size(batch_size)
     fids = readids(cfg.fileids) if fids is None else fids
     if not hasattr(vocoder, 'analysisfid_device'):
         raise ValueError('features_extraction: {} has no waveform analysis in this build'.format(vocoder.name()))
     with vocoder.f0_refine_as(f0_refine):
-        rawpaths = _extract_raw_streams(f0in_path, wav_path, rawpaths, fids, f0_min, f0_max, preproc_hp)
+        rawpaths = _extract_raw_streams(f0in_path, wav_path, rawpaths, fids, f0_min, f0_max, preproc_hp, batch_size=batch_size)
     return features_compose(rawpaths, fids=fids, win_convention=win_convention)
 
 
-def _extract_raw_streams(f0in_path, wav_path, rawpaths, fids, f0_min, f0_max, preproc_hp):
-    """The analysis loop of features_extraction: writes the raw streams of every file id and returns `rawpaths`."""
+def _check_batch_size(batch_size):
+    if batch_size is not None and (int(batch_size) != batch_size or batch_size < 1):
+        raise ValueError('features_extraction: batch_size={!r} is not None or an integer >= 1'.format(batch_size))
+
+
+def _extract_raw_streams(f0in_path, wav_path, rawpaths, fids, f0_min, f0_max, preproc_hp, batch_size=None):
+    """The analysis loop of features_extraction: writes the raw streams of every file id and returns `rawpaths`.  With
+    `batch_size` the files go through vocoder.analysis_device_batch, up to batch_size of them a call."""
+    _check_batch_size(batch_size)
     wav_path = cp + 'wav/*.wav' if wav_path is None else wav_path
     world = isinstance(vocoder, vocoders.VocoderWORLD)      # four streams: the noise stream is 'fwdbap', and there is a 'vuv' one
     if rawpaths is None:
@@ -151,6 +162,22 @@ def _extract_raw_streams(f0in_path, wav_path, rawpaths, fids, f0_min, f0_max, pr
         outputpathdicts['vuv'] = rawpaths[3]
     if preproc_hp == 'auto':
         preproc_hp = f0_min
+    if batch_size is not None:
+        for first in range(0, len(fids), int(batch_size)):
+            chunk = fids[first:first + int(batch_size)]
+            wavs, f0s = [], []
+            for fid in chunk:
+                fwav = wav_path.replace('*', fid)
+                print('Extracting {} features from: '.format('WORLD' if world else 'PML') + fwav)
+                wav, fs = vocoders.wavread(fwav)
+                if preproc_hp is not None or fs != int(round(vocoder.fs)):
+                    wav = vocoder.preprocwav(wav, fs, highpass=preproc_hp)
+                wavs.append(wav)
+                f0s.append(None if f0in_path is None else np.fromfile(f0in_path.replace('*', fid), dtype=np.float32))
+            CMPs = vocoder.analysis_device_batch(wavs, None if f0in_path is None else f0s, f0_min, f0_max)
+            for fid, CMP in zip(chunk, CMPs):
+                vocoder.write_streams(CMP, *[p.replace('*', fid) for p in rawpaths[:nstreams]])
+        return rawpaths
     for fid in fids:
         fwav = wav_path.replace('*', fid)
         if preproc_hp is None and vocoders.wavfs(fwav) == int(round(vocoder.fs)):

@@ -21,6 +21,8 @@ its name and keeps raising; `analysis_device` takes either type.  `VocoderWORLDA
 `write_streams` for the WORLD parameters (ln f0 | spec | aperiodicity [dB] | vuv): the build's own analysis, the counterpart of
 `VocoderWORLDDevice.synthesis_device` (csrc/worldanalysis.hip, DESIGN.md section 3: an envelope after CheapTrick, band
 aperiodicities from two windows one period apart), in the place of pyworld's; VocoderWORLD and VocoderWORLDDevice have none.
+`analysis_device_batch` of both analysing vocoders is `analysis_device` over a list of utterances, every kernel launching once per
+batch and nothing coming back to the host before the end (csrc/analysisbatch.hip and the *_batch kernels).
 `analysisf` / `analysisfid` keep their names for pulsemodel's / pyworld's analysis and keep raising.  `Vocoder.preprocwav` (vocoders.py:45-63) is
 the step in front of the analysis, on the device (csrc/preproc.hip): the build's own rational-ratio resampler in
 the place of pulsemodel's, and the zero-phase order-4 Butterworth high-pass with `highpass` as the cut-off in Hz.
@@ -374,6 +376,69 @@ class VocoderF0Spec(Vocoder):
             f0 = self.f0_refine_device(wav, f0, f0_min, f0_max)
         return wav, f0, ops.f0_track(f0, f0_min, f0_max, self.fs, self.shift, self.dftlen, wavlen=wav.size)
 
+    def _analysis_device_batch(self, check, frames, wavs, f0s, f0_min, f0_max, want_f0):
+        """What the analysis_device_batch of the subclasses share (check: ops.analysis_check or ops.world_analysis_check; frames:
+        (wav, wav layout, track, vuv, frame layout) -> (the log-envelope [sum T, K], the columns behind the spectral ones), all on
+        the device).  Every check that needs no device runs first, once per batch; then the waveforms (and the given tracks) go up
+        in one packed tensor each, the F0 steps of _analysis_input and the frame kernels launch once per batch
+        (ops.f0_estimate_batch, ops.f0_refine_batch, ops.f0_track_device, `frames`, compress_spectrum_device), and the host reads
+        the status words and the packed matrix back, once each, and takes column 0's logarithm as analysis_device does."""
+        import torch
+        from . import backend_hip, ops_offline as ops
+        fn = 'analysis_device_batch'
+        if self.spec_type not in ('fwbnd', 'mcep'):
+            raise ValueError("{}: spec_type is 'fwbnd' or 'mcep', got {!r}".format(fn, self.spec_type))
+        check(self.dftlen, self.fs, self.shift, f0_min, f0_max)
+        if self.spec_type == 'fwbnd':
+            ops.fwbnd_compress_check(self.spec_size, self.fs, self.dftlen)
+        else:
+            ops.spec2mcep_check(self.spec_size - 1, bark_alpha(self.fs), self.dftlen)
+        ops.fwbnd_compress_check(self.noisesize(), self.fs, self.dftlen)
+        wavs = list(wavs)
+        if not wavs:
+            raise ValueError('{}: no utterance given'.format(fn))
+        if f0s is not None:
+            f0s = list(f0s)
+            if len(f0s) != len(wavs) or any(f is None for f in f0s):
+                raise ValueError('{}: f0s is None (every track is estimated) or one track per utterance, not a mixture'.format(fn))
+        else:
+            ops.f0_check(self.dftlen, self.fs, self.shift, f0_min, f0_max)
+        if self.f0_refine:
+            ops.f0_refine_check(self.fs, self.shift, f0_min, f0_max)
+        for b, w in enumerate(wavs):
+            wavs[b] = w = np.asarray(w, dtype=np.float64)
+            if w.ndim != 1 or not np.isfinite(w).all():
+                raise ValueError('{}: utterance {}: wav is not a finite [N] waveform'.format(fn, b))
+        if f0s is not None:
+            for b, f in enumerate(f0s):
+                # as the single path: ops.f0_refine takes the track as float32 (NaN: unvoiced), ops.f0_track as float64
+                f0s[b] = f = np.array(f, dtype=np.float32) if self.f0_refine else np.asarray(f, dtype=np.float64)
+                if f.ndim != 1 or f.size < 1 or not (self.f0_refine or np.isfinite(f).all()):
+                    raise ValueError('{}: utterance {}: ops.f0_track: f0 has to be [T] finite Hz values, T >= 1'.format(fn, b))
+        dev = backend_hip.device()
+        wav = torch.from_numpy(np.concatenate([w.astype(np.float32) for w in wavs])).to(dev)
+        wo = ops.packed_offsets([w.size for w in wavs], dev, fn)
+        info = torch.zeros(len(wavs), dtype=torch.int32, device=dev)
+        if f0s is None:
+            f0, fo = ops.f0_estimate_batch(wav, wo, self.shift, self.fs, self.dftlen, f0_min, f0_max, info=info)
+        else:
+            f0 = torch.from_numpy(np.concatenate(f0s)).to(dev)
+            fo = ops.packed_offsets([f.size for f in f0s], dev, fn)
+        f0_in = f0
+        if self.f0_refine:
+            f0 = ops.f0_refine_batch(wav, wo, f0, fo, self.shift, self.fs, f0_min, f0_max)
+        track, vuv, oo = ops.f0_track_device(f0, fo, wo, f0_min, f0_max, self.fs, self.shift, self.dftlen, info=info)
+        lspec, columns = frames(wav, wo, track, vuv, oo)
+        bands = self.compress_spectrum_device(lspec, log=True)
+        CMP = torch.cat([track[:, None], bands] + list(columns), dim=1)
+        ops.analysis_status(fn, info)
+        CMP = CMP.cpu().numpy()
+        CMP[:, 0] = np.log(CMP[:, 0].astype(np.float64)).astype(np.float32)
+        out = [np.ascontiguousarray(c) for c in np.split(CMP, oo.off[1:-1])]
+        if want_f0:
+            return out, [np.ascontiguousarray(f) for f in np.split(f0_in.cpu().numpy(), fo.off[1:-1])]
+        return out
+
     def _analysisf_device(self, label, fwav, f0_in, f0_min, f0_max, streams, kwargs):
         """analysis_device from the wave file fwav to the files `streams`, in the order of write_streams' arguments."""
         if kwargs.get('preproc_hp') is not None:
@@ -483,6 +548,26 @@ class VocoderPML(VocoderF0Spec):
         bands = self.compress_spectrum_device(lspec, log=True)
         lf0 = np.log(track.astype(np.float64)).astype(np.float32)
         return np.concatenate([lf0[:, None], bands.cpu().numpy(), nm.cpu().numpy()], axis=1)
+
+    def analysis_device_batch(self, wavs, f0s, f0_min, f0_max, want_f0=False):
+        """analysis_device over a list of utterances: wavs mono waveforms at self.fs (any float arrays), f0s None (every track is
+        estimated) or a list with one F0 track per utterance (a list that mixes tracks and None is a ValueError) -> the list of
+        their [T_b, featuressizeraw()] float32 matrices, each byte for byte what analysis_device gives for that utterance alone
+        (with f0s None: for that utterance and the batch's own estimated track, which `want_f0` returns as a second list, as it
+        is in front of the refinement; the waveform's peak is measured by ops.wave_peak, whose last bit may differ from the
+        single path's).  The waveforms are uploaded once, every kernel launches once per batch (ops.f0_estimate_batch,
+        ops.f0_refine_batch where self.f0_refine is true, ops.f0_track_device, ops.frame_harmonics_batch,
+        ops.phase_coherence_batch, the compression), and the host reads the status words and the packed matrix back at the end,
+        nothing in between.  What analysis_device refuses is a ValueError that names the utterance's index; nothing is returned
+        then."""
+        from . import ops_offline as ops
+        hcap = ops.analysis_check(self.dftlen, self.fs, self.shift, f0_min, f0_max)
+
+        def frames(wav, wo, track, vuv, oo):
+            lspec, u = ops.frame_harmonics_batch(wav, wo, track, oo, self.shift, self.fs, self.dftlen, hcap, log=True)
+            _, nm = ops.phase_coherence_batch(u, track, oo, self.shift, self.fs, self.dftlen, self.nm_size)
+            return lspec, [nm]
+        return self._analysis_device_batch(ops.analysis_check, frames, wavs, f0s, f0_min, f0_max, want_f0)
 
     def analysisf_device(self, fwav, f0_in, ff0, f0_min, f0_max, fspec, fnm, **kwargs):
         """analysis_device from file to files, where the reference's analysisf writes them (vocoders.py:181-189): fwav a 16-bit mono
@@ -594,6 +679,21 @@ class VocoderWORLDAnalysisDevice(VocoderWORLDDevice):
         bands = self.compress_spectrum_device(lspec, log=True)
         lf0 = np.log(track.astype(np.float64)).astype(np.float32)
         return np.concatenate([lf0[:, None], bands.cpu().numpy(), aper.cpu().numpy(), vuv[:, None]], axis=1)
+
+    def analysis_device_batch(self, wavs, f0s, f0_min, f0_max, want_f0=False):
+        """analysis_device over a list of utterances, as VocoderPML.analysis_device_batch: the list of their [T_b,
+        featuressizeraw()] float32 matrices, each byte for byte what analysis_device gives for that utterance alone, with
+        ops.world_envelope_batch and ops.world_aperiodicity_batch as the frame kernels; vuv and the rate of every frame (the track
+        where voiced, ops.WORLD_UNVOICED_RATE where not) stay on the device."""
+        import torch
+        from . import ops_offline as ops
+
+        def frames(wav, wo, track, vuv, oo):
+            rate = torch.where(vuv > 0, track, torch.full_like(track, ops.WORLD_UNVOICED_RATE))
+            lspec = ops.world_envelope_batch(wav, wo, rate, oo, self.shift, self.fs, self.dftlen, log=True)
+            aper = ops.world_aperiodicity_batch(wav, wo, track, vuv, oo, self.shift, self.fs, self.dftlen, self.aper_size)
+            return lspec, [aper, vuv[:, None]]
+        return self._analysis_device_batch(ops.world_analysis_check, frames, wavs, f0s, f0_min, f0_max, want_f0)
 
     def analysisf_device(self, fwav, f0_in, ff0, f0_min, f0_max, fspec, faper, fvuv, **kwargs):
         """analysis_device from file to files, where the reference's analysisf writes them (vocoders.py:234-284): fwav a 16-bit mono
