@@ -536,6 +536,11 @@ int ptts_bn_bwd_coefs_acc(const float* dscale, const float* dshift, const float*
 /* y = act(x*scale[c]+shift[c]) materialised (used where no consumer can fuse it: LSTM input, final outputs). */
 int ptts_affine_act(const float* x, const float* scale, const float* shift, float* y,
                     long long rows, int C, int act, float alpha, void* stream);
+/* The same over a zero-padded batch x [B,T,inner] with a length per row (ragged inference): frames t >= lens[b] give 0.
+ * y[b,t,i] = t < lens[b] ? act(x*scale[c]+shift[c]) : 0, c = i % C; inner = elements per frame, a multiple of C (C for
+ * [B,T,C], F*C for a Conv2D map).  lens: device int [B].  scale/shift NULL together = identity.  y == x is allowed. */
+int ptts_affine_act_rows(const float* x, const float* scale, const float* shift, float* y, const int* lens,
+                         int B, int T, int inner, int C, int act, float alpha, void* stream);
 /* dx = dy * act'(.) * scale ; dscale/dshift reductions (NULL to skip).  `y` is the forward output (sigmoid/tanh use it). */
 int ptts_affine_act_bwd(const float* dy, const float* x, const float* y, const float* scale, const float* shift,
                         float* dx, double* dsums /*[2C]: dscale, dshift; or NULL*/,
@@ -595,6 +600,15 @@ size_t ptts_lstm_fwd_workspace_bytes(int B, int T, int H, int ndir);   /* packed
 int ptts_lstm_fwd(const float* xproj, const float* U, float* h_out, float* gates, float* c_out,
                   void* workspace, size_t workspace_bytes,
                   int B, int T, int H, int ndir, int reverse, void* stream);
+/* Forward for inference over a zero-padded batch with a length per row: lens is a device int [B], 1 <= lens[b] <= T.
+ * Row b is active for its first lens[b] steps; a backward direction (direction 1, or reverse) starts at the row's own
+ * last frame t = lens[b]-1 with zero state.  On t < lens[b] h_out holds what ptts_lstm_fwd gives for that row alone
+ * (B = 1, T = lens[b]), bit for bit; on t >= lens[b] it is 0.0f.  gates and c_out may be NULL (they are stored on real
+ * frames where given).  workspace: the cell-state carry, ndir*B*H floats rounded up to 256 bytes, followed by
+ * ptts_lstm_fwd_workspace_bytes for the packed recurrent kernel (without the latter, as ptts_lstm_fwd without one). */
+int ptts_lstm_fwd_ragged(const float* xproj, const float* U, float* h_out, float* gates /*or NULL*/,
+                         float* c_out /*or NULL*/, const int* lens, void* workspace, size_t workspace_bytes,
+                         int B, int T, int H, int ndir, int reverse, void* stream);
 /* dgates [B,T,ndir*4H] out: gradients w.r.t. the gate PRE-activations; dW, dU, db and dx follow from
  * them as ptts_gemm products.  workspace: ptts_lstm_bwd_workspace_bytes */
 size_t ptts_lstm_bwd_workspace_bytes(int B, int T, int H, int ndir);
@@ -620,6 +634,12 @@ int ptts_lstm_graph_stats(unsigned long long* hits, unsigned long long* captures
 size_t ptts_gru_fwd_workspace_bytes(int B, int T, int H, int ndir);    /* packed recurrent kernel */
 int ptts_gru_fwd(const float* xproj, const float* U, float* h_out, float* gates, float* rh,
                  void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, void* stream);
+/* Forward for inference over a zero-padded batch with a length per row (see ptts_lstm_fwd_ragged): real frames as
+ * ptts_gru_fwd on the row alone, bit for bit; pad frames 0.0f.  gates and rh may be NULL.  workspace:
+ * ptts_gru_fwd_workspace_bytes followed by 2*ndir*B*H floats (z and r*h from a step's first launch to its second). */
+int ptts_gru_fwd_ragged(const float* xproj, const float* U, float* h_out, float* gates /*or NULL*/, float* rh /*or NULL*/,
+                        const int* lens, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir,
+                        void* stream);
 /* dgates [B,T,ndir*3H] out: gradients w.r.t. the gate PRE-activations (hs' = 0.2 inside (0,1), 0
  * where clipped, taken from the stored gate); dx, dW, dU and db follow from them as ptts_gemm
  * products.  workspace: ptts_gru_bwd_workspace_bytes (packed U^T + the [ndir,B,H] carries) */

@@ -652,6 +652,43 @@ __global__ void affine_act_kernel4(const float4* __restrict__ x, const float* __
     }
 }
 
+// affine_act with the end of every row of a ragged batch folded in: x [B][T][inner], channel c = i % C, frames t >= lens[b]
+// give 0.  One pass for a pending BatchNorm affine + activation and the mask.  VEC = 4 needs C % 4 == 0 (so inner % 4 == 0:
+// a float4 never crosses a frame).
+template <int VEC>
+__global__ void affine_act_rows_kernel(const float* __restrict__ x, const float* __restrict__ scale,
+                                       const float* __restrict__ shift, float* __restrict__ y,
+                                       const int* __restrict__ lens, long long nv, int T, int inner, int C, int act,
+                                       float alpha) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nv;
+         i += (long long)gridDim.x * blockDim.x) {
+        const long long e0 = i * VEC;
+        const long long frame = e0 / inner;
+        const int t = (int)(frame % T), b = (int)(frame / T);
+        float p[VEC];
+        if (t < lens[b]) {
+            if (VEC == 4) {
+                const float4 v = *reinterpret_cast<const float4*>(x + e0);
+                p[0] = v.x; p[1 % VEC] = v.y; p[2 % VEC] = v.z; p[3 % VEC] = v.w;
+            } else {
+                p[0] = x[e0];
+            }
+            if (scale) {
+                const int c = (int)(e0 % C);
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) p[e] = p[e] * scale[c + e] + shift[c + e];
+            }
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) p[e] = act_fwd(p[e], act, alpha);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) p[e] = 0.f;
+        }
+        if (VEC == 4) *reinterpret_cast<float4*>(y + e0) = make_float4(p[0], p[1 % VEC], p[2 % VEC], p[3 % VEC]);
+        else y[e0] = p[0];
+    }
+}
+
 __global__ void axpby_cols_kernel(const float* __restrict__ a, const float* __restrict__ c1,
                                   const float* __restrict__ x, const float* __restrict__ c2,
                                   const float* __restrict__ c0, float* __restrict__ out, long long n, int C) {
@@ -956,6 +993,25 @@ extern "C" int ptts_affine_act(const float* x, const float* scale, const float* 
                            act, alpha);
     }
     return check_launch("affine_act");
+}
+
+// y[b,t,i] = t < lens[b] ? act(x[b,t,i] * scale[i % C] + shift[i % C]) : 0 for x [B][T][inner], inner a multiple of C;
+// lens is a device array [B].  In place (y == x) is allowed.
+extern "C" int ptts_affine_act_rows(const float* x, const float* scale, const float* shift, float* y, const int* lens,
+                                    int B, int T, int inner, int C, int act, float alpha, void* stream) {
+    PTTS_REQUIRE(x && y && lens && B > 0 && T > 0 && inner > 0 && C > 0, "affine_act_rows: bad args");
+    PTTS_REQUIRE(inner % C == 0, "affine_act_rows: inner=%d is no multiple of C=%d", inner, C);
+    PTTS_REQUIRE((scale == nullptr) == (shift == nullptr), "affine_act_rows: scale/shift must come together");
+    const long long n = (long long)B * T * inner;
+    hipStream_t st = (hipStream_t)stream;
+    if (C % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0)) {
+        hipLaunchKernelGGL(affine_act_rows_kernel<4>, dim3(ew_blocks(n / 4, 2)), dim3(EW_THREADS), 0, st, x, scale, shift,
+                           y, lens, n / 4, T, inner, C, act, alpha);
+    } else {
+        hipLaunchKernelGGL(affine_act_rows_kernel<1>, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, st, x, scale, shift, y,
+                           lens, n, T, inner, C, act, alpha);
+    }
+    return check_launch("affine_act_rows");
 }
 
 // ---- gated product of a gated convolution: y = a * sigmoid(b) (reference networktts.py:128-134, pGCNN2D: the second

@@ -76,22 +76,33 @@ __device__ __forceinline__ void gru_wave_tile(const float* __restrict__ bp, int 
     for (int r = 0; r < 4; ++r) red[(q * 4 + r) * 16 + r16] = acc0[r] + acc1[r];
 }
 
+// Ragged inference (RAG): lens [B] holds each row's own length, 1 <= lens[b] <= T (a larger value is read as T).  Row b is active
+// while s < lens[b]; the backward direction works on t = lens[b] - 1 - s and reads its previous state at the row's own t + 1.  An inactive row gives a
+// zero operand, writes h = 0 at t = s (launch B) and nothing else.  z and rh pass from launch A to launch B through
+// zc, rhc [ndir][B][H]; gates and rh are stored only where the caller passes them.  Both launches are bodies templated on RAG
+// behind two __global__ entries: with RAG = false the extra pointers are compile-time null and the code is the training kernel's.
+
 // Forward launch A of step s: grid (tiles16(2H), ceil(B/16), ndir), 256 threads.
-__global__ __launch_bounds__(256) void gru_fwd_zr_kernel(
+template <bool RAG>
+__device__ __forceinline__ void gru_fwd_zr_body(
     const float* __restrict__ xproj, const float* __restrict__ Upk, const float* __restrict__ h_out, float* __restrict__ gates,
-    float* __restrict__ rh, int B, int T, int H, int ndir, int s) {
+    float* __restrict__ rh, int B, int T, int H, int ndir, int s, const int* __restrict__ lens, float* __restrict__ zc,
+    float* __restrict__ rhc) {
     __shared__ float red[4][256];
     // a latency chain that shares its CUs with the wide kernels of other streams: its waves go first at the issue arbiter
     __builtin_amdgcn_s_setprio(3);
     const int d = blockIdx.z;
-    const int t = d == 1 ? T - 1 - s : s, tp = d == 1 ? t + 1 : t - 1;
+    int t = d == 1 ? T - 1 - s : s, tp = d == 1 ? t + 1 : t - 1;
     const int jt = blockIdx.x, b0 = blockIdx.y * 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
     const int KS = round16(H) / 16, NT = tiles16(2 * H);
     const long long G3 = 3LL * H, GG = ndir * G3, HH = (long long)ndir * H;
     // epilogue inputs first: sample eb, column c of the z|r block
     const int eb = b0 + (tid >> 4), c = jt * 16 + (tid & 15);
-    const bool epi = eb < B && c < 2 * H;
+    const int len_e = RAG ? (eb < B ? min(lens[eb], T) : 0) : T;
+    const int len_a = RAG ? (b0 + r16 < B ? min(lens[b0 + r16], T) : 0) : T;
+    const bool epi = eb < B && c < 2 * H && (!RAG || s < len_e);
+    if (RAG && d == 1) { t = len_e - 1 - s; tp = t + 1; }
     float xv = 0.f, hp = 0.f;
     if (epi) {
         xv = xproj[((long long)eb * T + t) * GG + d * G3 + c];
@@ -99,8 +110,9 @@ __global__ __launch_bounds__(256) void gru_fwd_zr_kernel(
     }
     if (s > 0) {
         const int b = b0 + r16;
-        const bool bok = b < B;
-        const float* hrow = h_out + ((long long)(bok ? b : 0) * T + tp) * HH + (long long)d * H;
+        const bool bok = RAG ? s < len_a : b < B;
+        const int tpa = RAG ? (bok ? (d == 1 ? len_a - s : s - 1) : 0) : tp;
+        const float* hrow = h_out + ((long long)(bok ? b : 0) * T + tpa) * HH + (long long)d * H;
         const float* bp = Upk + ((((long long)d * NT + jt) * 4 + wave) * 64 + lane) * KS;
         gru_wave_tile(bp, KS, wave * 4 * KS + q * KS, [&](int k) { return bok && k < H ? hrow[k] : 0.f; }, red[wave]);
         __syncthreads();
@@ -110,45 +122,84 @@ __global__ __launch_bounds__(256) void gru_fwd_zr_kernel(
     if (s > 0) a += red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
     const float g = hard_sigmoid(a);
     const long long row = (long long)eb * T + t;
-    gates[row * GG + d * G3 + c] = g;
-    if (c >= H) rh[row * HH + (long long)d * H + c - H] = g * hp;
+    if (!RAG || gates) gates[row * GG + d * G3 + c] = g;
+    if (RAG) {
+        const long long si = ((long long)d * B + eb) * H;
+        if (c < H) zc[si + c] = g;
+        else rhc[si + c - H] = g * hp;
+    }
+    if (c >= H && (!RAG || rh)) rh[row * HH + (long long)d * H + c - H] = g * hp;
+}
+
+__global__ __launch_bounds__(256) void gru_fwd_zr_kernel(
+    const float* __restrict__ xproj, const float* __restrict__ Upk, const float* __restrict__ h_out, float* __restrict__ gates,
+    float* __restrict__ rh, int B, int T, int H, int ndir, int s) {
+    gru_fwd_zr_body<false>(xproj, Upk, h_out, gates, rh, B, T, H, ndir, s, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void gru_fwd_zr_ragged_kernel(
+    const float* __restrict__ xproj, const float* __restrict__ Upk, const float* __restrict__ h_out, float* __restrict__ gates,
+    float* __restrict__ rh, int B, int T, int H, int ndir, int s, const int* __restrict__ lens, float* __restrict__ zc,
+    float* __restrict__ rhc) {
+    gru_fwd_zr_body<true>(xproj, Upk, h_out, gates, rh, B, T, H, ndir, s, lens, zc, rhc);
 }
 
 // Forward launch B of step s: grid (tiles16(H), ceil(B/16), ndir), 256 threads.
-__global__ __launch_bounds__(256) void gru_fwd_h_kernel(
+template <bool RAG>
+__device__ __forceinline__ void gru_fwd_h_body(
     const float* __restrict__ xproj, const float* __restrict__ Upk, float* __restrict__ h_out, float* __restrict__ gates,
-    const float* __restrict__ rh, int B, int T, int H, int ndir, int s) {
+    const float* __restrict__ rh, int B, int T, int H, int ndir, int s, const int* __restrict__ lens,
+    const float* __restrict__ zc, const float* __restrict__ rhc) {
     __shared__ float red[4][256];
     __builtin_amdgcn_s_setprio(3);
     const int d = blockIdx.z;
-    const int t = d == 1 ? T - 1 - s : s, tp = d == 1 ? t + 1 : t - 1;
+    int t = d == 1 ? T - 1 - s : s, tp = d == 1 ? t + 1 : t - 1;
     const int jt = blockIdx.x, b0 = blockIdx.y * 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
     const int KS = round16(H) / 16, NT = tiles16(H);
     const long long G3 = 3LL * H, GG = ndir * G3, HH = (long long)ndir * H;
     const int eb = b0 + (tid >> 4), j = jt * 16 + (tid & 15);
-    const bool epi = eb < B && j < H;
+    const int len_e = RAG ? (eb < B ? min(lens[eb], T) : 0) : T;
+    const int len_a = RAG ? (b0 + r16 < B ? min(lens[b0 + r16], T) : 0) : T;
+    const bool own = eb < B && j < H;
+    const bool epi = own && (!RAG || s < len_e);
+    if (RAG && d == 1) { t = len_e - 1 - s; tp = t + 1; }
     const long long row = (long long)eb * T + t;
     float xv = 0.f, z = 0.f, hp = 0.f;
     if (epi) {
         xv = xproj[row * GG + d * G3 + 2 * H + j];
-        z = gates[row * GG + d * G3 + j];
+        z = RAG ? zc[((long long)d * B + eb) * H + j] : gates[row * GG + d * G3 + j];
         if (s > 0) hp = h_out[((long long)eb * T + tp) * HH + (long long)d * H + j];
     }
     if (s > 0) {      // at s = 0, rh = r * h_{-1} = 0
         const int b = b0 + r16;
-        const bool bok = b < B;
-        const float* rrow = rh + ((long long)(bok ? b : 0) * T + t) * HH + (long long)d * H;
+        const bool bok = RAG ? s < len_a : b < B;
+        const float* rrow = RAG ? rhc + ((long long)d * B + (bok ? b : 0)) * H
+                                : rh + ((long long)(bok ? b : 0) * T + t) * HH + (long long)d * H;
         const float* bp = Upk + ((((long long)d * NT + jt) * 4 + wave) * 64 + lane) * KS;
         gru_wave_tile(bp, KS, wave * 4 * KS + q * KS, [&](int k) { return bok && k < H ? rrow[k] : 0.f; }, red[wave]);
         __syncthreads();
     }
+    if (RAG && own && !epi) h_out[((long long)eb * T + s) * HH + (long long)d * H + j] = 0.f;
     if (!epi) return;
     float a = xv;
     if (s > 0) a += red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
     const float hh = tanhf(a);
-    gates[row * GG + d * G3 + 2 * H + j] = hh;
+    if (!RAG || gates) gates[row * GG + d * G3 + 2 * H + j] = hh;
     h_out[row * HH + (long long)d * H + j] = z * hp + (1.f - z) * hh;
+}
+
+__global__ __launch_bounds__(256) void gru_fwd_h_kernel(
+    const float* __restrict__ xproj, const float* __restrict__ Upk, float* __restrict__ h_out, float* __restrict__ gates,
+    const float* __restrict__ rh, int B, int T, int H, int ndir, int s) {
+    gru_fwd_h_body<false>(xproj, Upk, h_out, gates, rh, B, T, H, ndir, s, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void gru_fwd_h_ragged_kernel(
+    const float* __restrict__ xproj, const float* __restrict__ Upk, float* __restrict__ h_out, float* __restrict__ gates,
+    const float* __restrict__ rh, int B, int T, int H, int ndir, int s, const int* __restrict__ lens,
+    const float* __restrict__ zc, const float* __restrict__ rhc) {
+    gru_fwd_h_body<true>(xproj, Upk, h_out, gates, rh, B, T, H, ndir, s, lens, zc, rhc);
 }
 
 // Backward launch A' of forward step s (launched for s = T-1 .. 0): grid (tiles16(H), ceil(B/16), ndir), 256 threads.
@@ -272,6 +323,36 @@ extern "C" int ptts_gru_fwd(const float* xproj, const float* U, float* h_out, fl
                            B, T, H, ndir, s);
     }
     return check_launch("gru_fwd");
+}
+
+// Forward for inference over a zero-padded batch with a length per row (see gru_fwd_zr_body); both directions of a
+// bidirectional pair, no single reversed direction (as ptts_gru_fwd).  gates and rh may be NULL.  workspace: the two packed
+// operands of ptts_gru_fwd_workspace_bytes, then the z and r*h carries, 2*ndir*B*H floats.
+extern "C" int ptts_gru_fwd_ragged(const float* xproj, const float* U, float* h_out, float* gates, float* rh,
+                                   const int* lens, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir,
+                                   void* stream) {
+    PTTS_REQUIRE(xproj && U && h_out && lens, "gru_fwd_ragged: null tensor");
+    PTTS_REQUIRE(B > 0 && T > 0 && H > 0 && (ndir == 1 || ndir == 2), "gru_fwd_ragged: bad dims B=%d T=%d H=%d ndir=%d", B, T, H, ndir);
+    const size_t need = ptts_gru_fwd_workspace_bytes(B, T, H, ndir) + (size_t)2 * ndir * B * H * sizeof(float);
+    if (!workspace || workspace_bytes < need) {
+        set_error("gru_fwd_ragged: workspace %zu < %zu", workspace_bytes, need);
+        return PTTS_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float* Uzr = (float*)workspace;
+    float* Uh = Uzr + packed_floats(ndir, H, 2 * H);
+    float* zc = Uh + packed_floats(ndir, H, H);
+    float* rhc = zc + (size_t)ndir * B * H;
+    launch_pack(U, Uzr, H, ndir, H, 2 * H, 0, 0, st);
+    launch_pack(U, Uh, H, ndir, H, H, 2 * H, 0, st);
+    const dim3 gzr(tiles16(2 * H), tiles16(B), ndir), gh(tiles16(H), tiles16(B), ndir);
+    for (int s = 0; s < T; ++s) {
+        hipLaunchKernelGGL(gru_fwd_zr_ragged_kernel, gzr, dim3(256), 0, st, xproj, (const float*)Uzr, (const float*)h_out,
+                           gates, rh, B, T, H, ndir, s, lens, zc, rhc);
+        hipLaunchKernelGGL(gru_fwd_h_ragged_kernel, gh, dim3(256), 0, st, xproj, (const float*)Uh, h_out, gates,
+                           (const float*)rh, B, T, H, ndir, s, lens, (const float*)zc, (const float*)rhc);
+    }
+    return check_launch("gru_fwd_ragged");
 }
 
 extern "C" size_t ptts_gru_bwd_workspace_bytes(int B, int T, int H, int ndir) {

@@ -10,6 +10,8 @@
 //   MFMA        : every other H % 16 == 0 (16, 32, 48, 80, ..., 320, 384, ...)
 //   scalar      : any other H; one lane per (sample, unit), h_{t-1} staged in LDS
 // Limits: H <= 4096 forward, H <= 1024 backward (the scalar kernels' LDS rows bound every path).
+// ptts_lstm_fwd_ragged runs the same three forward paths, chosen the same way, for inference over a zero-padded batch with a
+// length per row (compile-time variants of the step kernels, see lstm_fwd_step_body).
 #include "common.h"
 
 namespace ptts {
@@ -18,27 +20,58 @@ constexpr int LX = 64, LY = 4;   // lanes along units, samples per workgroup
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
-__global__ __launch_bounds__(LX * LY) void lstm_fwd_step_kernel(
+// Ragged inference (RAG): lens [B] holds each row's own length, 1 <= lens[b] <= T.  Row b is active while s < lens[b]; a
+// backward direction works on t = lens[b] - 1 - s, so it starts at the row's last real frame with zero state, and reads its
+// previous state at the row's own t -/+ 1.  An inactive row gives a zero operand, writes h = 0 at t = s (so every (b, t) is
+// written exactly once over the T steps) and leaves the state alone.  The cell state is carried in carry [ndir][B][H], read
+// and written by the same lane; gates and c_out are stored only where the caller passes them.  A length above T is read as T,
+// one below 1 as an empty row: no value of lens can send an access outside the arrays.  Every step kernel below is a
+// compile-time variant of its training kernel: without the ragged arguments the code is the training kernel's, with no extra
+// argument and no branch.
+// The scalar kernel is a body templated on RAG behind two __global__ entries.  The two MFMA kernels take the ragged arguments as a
+// trailing parameter pack instead (empty: the training kernel; <const int* lens, float* carry>: ragged), because inlining a body
+// into a kernel turns the __restrict__ parameters into scoped-alias metadata and the packed kernel's <8> and <16> then schedule
+// differently: with the pack, every training instantiation compiles to the instructions it had before the ragged variants existed.
+__device__ __forceinline__ void rag_args(const int*& lens, float*& carry) { lens = nullptr; carry = nullptr; }
+__device__ __forceinline__ void rag_args(const int*& lens, float*& carry, const int* l, float* c) { lens = l; carry = c; }
+
+template <bool RAG>
+__device__ __forceinline__ void lstm_fwd_step_body(
     const float* __restrict__ xproj, const float* __restrict__ U, float* __restrict__ h_out,
-    float* __restrict__ gates, float* __restrict__ c_out, int B, int T, int H, int ndir, int reverse, int s) {
+    float* __restrict__ gates, float* __restrict__ c_out, int B, int T, int H, int ndir, int reverse, int s,
+    const int* __restrict__ lens, float* __restrict__ carry) {
     extern __shared__ float hs[];   // [LY][H]
     const int d = blockIdx.z;
     const bool rev = ndir == 2 ? d == 1 : reverse != 0;
-    const int t = rev ? T - 1 - s : s;
-    const int tp = rev ? t + 1 : t - 1;
+    int t = rev ? T - 1 - s : s;
+    int tp = rev ? t + 1 : t - 1;
     const int tid = threadIdx.y * LX + threadIdx.x;
     const long long HH = (long long)ndir * H;
     if (s > 0) {
         for (int idx = tid; idx < LY * H; idx += LX * LY) {
             const int by = idx / H, k = idx - by * H;
             const int b = blockIdx.y * LY + by;
-            hs[idx] = b < B ? h_out[((long long)b * T + tp) * HH + (long long)d * H + k] : 0.f;
+            if (RAG) {
+                const int len = b < B ? min(lens[b], T) : 0;
+                const int tpb = rev ? len - s : s - 1;
+                hs[idx] = s < len ? h_out[((long long)b * T + tpb) * HH + (long long)d * H + k] : 0.f;
+            } else {
+                hs[idx] = b < B ? h_out[((long long)b * T + tp) * HH + (long long)d * H + k] : 0.f;
+            }
         }
         __syncthreads();
     }
     const int j = blockIdx.x * LX + threadIdx.x;
     const int b = blockIdx.y * LY + threadIdx.y;
     if (j >= H || b >= B) return;
+    if (RAG) {
+        const int len = min(lens[b], T);
+        if (s >= len) {
+            h_out[((long long)b * T + s) * HH + (long long)d * H + j] = 0.f;
+            return;
+        }
+        if (rev) { t = len - 1 - s; tp = t + 1; }
+    }
     const long long G4 = 4LL * H;
     const float* xp = xproj + (((long long)b * T + t) * ndir + d) * G4;
     float a0 = xp[j], a1 = xp[H + j], a2 = xp[2 * H + j], a3 = xp[3 * H + j];
@@ -57,12 +90,29 @@ __global__ __launch_bounds__(LX * LY) void lstm_fwd_step_kernel(
     }
     const float gi = sigmoidf_(a0), gf = sigmoidf_(a1), gc = tanhf(a2), go = sigmoidf_(a3);
     const long long so = ((long long)b * T + t) * HH + (long long)d * H + j;
-    const float cp = s > 0 ? c_out[((long long)b * T + tp) * HH + (long long)d * H + j] : 0.f;
+    const long long si = ((long long)d * B + b) * H + j;
+    const float cp = s > 0 ? (RAG ? carry[si] : c_out[((long long)b * T + tp) * HH + (long long)d * H + j]) : 0.f;
     const float c = gf * cp + gi * gc;
-    c_out[so] = c;
+    if (RAG) carry[si] = c;
+    if (!RAG || c_out) c_out[so] = c;
     h_out[so] = go * tanhf(c);
-    float* gp = gates + (((long long)b * T + t) * ndir + d) * G4;
-    gp[j] = gi; gp[H + j] = gf; gp[2 * H + j] = gc; gp[3 * H + j] = go;
+    if (!RAG || gates) {
+        float* gp = gates + (((long long)b * T + t) * ndir + d) * G4;
+        gp[j] = gi; gp[H + j] = gf; gp[2 * H + j] = gc; gp[3 * H + j] = go;
+    }
+}
+
+__global__ __launch_bounds__(LX * LY) void lstm_fwd_step_kernel(
+    const float* __restrict__ xproj, const float* __restrict__ U, float* __restrict__ h_out,
+    float* __restrict__ gates, float* __restrict__ c_out, int B, int T, int H, int ndir, int reverse, int s) {
+    lstm_fwd_step_body<false>(xproj, U, h_out, gates, c_out, B, T, H, ndir, reverse, s, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(LX * LY) void lstm_fwd_step_ragged_kernel(
+    const float* __restrict__ xproj, const float* __restrict__ U, float* __restrict__ h_out,
+    float* __restrict__ gates, float* __restrict__ c_out, int B, int T, int H, int ndir, int reverse, int s,
+    const int* __restrict__ lens, float* __restrict__ carry) {
+    lstm_fwd_step_body<true>(xproj, U, h_out, gates, c_out, B, T, H, ndir, reverse, s, lens, carry);
 }
 
 // UT[d][n][k] = U[d][k][n]
@@ -141,14 +191,18 @@ __global__ __launch_bounds__(LX * LY) void lstm_bwd_step_kernel(
 // ------------------------------------------------------------------------------------------------
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
+template <class... R>   // R: empty, or <const int* lens, float* carry> for ragged inference
 __global__ __launch_bounds__(256) void lstm_fwd_step_mfma_kernel(
     const float* __restrict__ xproj, const float* __restrict__ U, float* __restrict__ h_out,
-    float* __restrict__ gates, float* __restrict__ c_out, int B, int T, int H, int ndir, int reverse, int s) {
+    float* __restrict__ gates, float* __restrict__ c_out, int B, int T, int H, int ndir, int reverse, int s, R... rag) {
+    constexpr bool RAG = sizeof...(R) != 0;
+    const int* lens; float* carry;
+    rag_args(lens, carry, rag...);
     __shared__ float red[4][2][256];
     const int d = blockIdx.z;
     const bool rev = ndir == 2 ? d == 1 : reverse != 0;
-    const int t = rev ? T - 1 - s : s;
-    const int tp = rev ? t + 1 : t - 1;
+    int t = rev ? T - 1 - s : s;
+    int tp = rev ? t + 1 : t - 1;
     const int j0 = blockIdx.x * 8, b0 = blockIdx.y * 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, q = lane >> 4;
@@ -157,6 +211,11 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_mfma_kernel(
         const int ksteps = H / 16;                 // k-steps of 4 per wave
         const int kbase = wave * (H / 4);
         const int b = b0 + r16;
+        int len_a = T;                             // RAG, an inactive row: a valid address, a zero operand
+        if (RAG) {
+            len_a = b < B ? min(lens[b], T) : 0;
+            if (rev) tp = s < len_a ? len_a - s : 0;
+        }
         const float* hp = h_out + ((long long)(b < B ? b : 0) * T + tp) * HH + (long long)d * H + kbase + q;
         const float* Ud = U + (long long)d * H * G4 + (long long)(kbase + q) * G4 + j0 + (r16 & 7);
         const int gx = (r16 >> 3) * H, gy = (2 + (r16 >> 3)) * H;
@@ -167,7 +226,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_mfma_kernel(
             for (int i = 0; i < 8; ++i) {
                 const int st = s0 + i;
                 if (st < ksteps) {
-                    a[i] = b < B ? hp[4 * st] : 0.f;
+                    a[i] = (RAG ? s < len_a : b < B) ? hp[4 * st] : 0.f;
                     const float* u = Ud + (long long)(4 * st) * G4;
                     bx[i] = u[gx];
                     by[i] = u[gy];
@@ -190,6 +249,14 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_mfma_kernel(
     const int bb = tid >> 3, jj = tid & 7;
     const int b = b0 + bb, j = j0 + jj;
     if (b >= B) return;
+    if (RAG) {
+        const int len = min(lens[b], T);
+        if (s >= len) {
+            h_out[((long long)b * T + s) * HH + (long long)d * H + j] = 0.f;
+            return;
+        }
+        if (rev) { t = len - 1 - s; tp = t + 1; }
+    }
     const float* xp = xproj + (((long long)b * T + t) * ndir + d) * G4;
     float a4[4];
 #pragma unroll
@@ -203,12 +270,16 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_mfma_kernel(
     }
     const float gi = sigmoidf_(a4[0]), gf = sigmoidf_(a4[1]), gc = tanhf(a4[2]), go = sigmoidf_(a4[3]);
     const long long so = ((long long)b * T + t) * HH + (long long)d * H + j;
-    const float cp = s > 0 ? c_out[((long long)b * T + tp) * HH + (long long)d * H + j] : 0.f;
+    const long long si = ((long long)d * B + b) * H + j;
+    const float cp = s > 0 ? (RAG ? carry[si] : c_out[((long long)b * T + tp) * HH + (long long)d * H + j]) : 0.f;
     const float c = gf * cp + gi * gc;
-    c_out[so] = c;
+    if (RAG) carry[si] = c;
+    if (!RAG || c_out) c_out[so] = c;
     h_out[so] = go * tanhf(c);
-    float* gp = gates + (((long long)b * T + t) * ndir + d) * G4;
-    gp[j] = gi; gp[H + j] = gf; gp[2 * H + j] = gc; gp[3 * H + j] = go;
+    if (!RAG || gates) {
+        float* gp = gates + (((long long)b * T + t) * ndir + d) * G4;
+        gp[j] = gi; gp[H + j] = gf; gp[2 * H + j] = gc; gp[3 * H + j] = go;
+    }
 }
 
 __global__ __launch_bounds__(256) void lstm_bwd_step_mfma_kernel(
@@ -320,17 +391,23 @@ __global__ void lstm_pack_u_bwd_kernel(const float* __restrict__ U, float* __res
     }
 }
 
-template <int CH>   // k-steps per register chunk (4, 8 or 16)
+// RAG: a lane needs two lengths, its tile row's (A operand) and its epilogue sample's; both loads go out first.  In a forward
+// direction no address depends on them (t = s is inside the padded arrays for every row), so the step keeps its one exposed
+// L2 round trip and the lengths only mask; in a backward direction the addresses wait for the lengths: one more L2 hit.
+template <int CH, class... R>   // CH: k-steps per register chunk (4, 8 or 16); R: empty, or <const int* lens, float* carry>
 __global__ __launch_bounds__(256) void lstm_fwd_step_pk_kernel(
     const float* __restrict__ xproj, const float* __restrict__ Upk, float* __restrict__ h_out,
-    float* __restrict__ gates, float* __restrict__ c_out, int B, int T, int H, int ndir, int reverse, int s) {
+    float* __restrict__ gates, float* __restrict__ c_out, int B, int T, int H, int ndir, int reverse, int s, R... rag) {
+    constexpr bool RAG = sizeof...(R) != 0;
+    const int* lens; float* carry;
+    rag_args(lens, carry, rag...);
     __shared__ float red[4][2][256];
     // a latency chain that shares its CUs with the wide kernels of the other streams: its waves go first at the issue arbiter
     __builtin_amdgcn_s_setprio(3);
     const int d = blockIdx.z;
     const bool rev = ndir == 2 ? d == 1 : reverse != 0;
-    const int t = rev ? T - 1 - s : s;
-    const int tp = rev ? t + 1 : t - 1;
+    int t = rev ? T - 1 - s : s;
+    int tp = rev ? t + 1 : t - 1;
     const int jt = blockIdx.x, j0 = jt * 8, b0 = blockIdx.y * 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, q = lane >> 4;
@@ -340,15 +417,29 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_pk_kernel(
     const int bb = tid >> 3, jj = tid & 7;
     const int eb = b0 + bb, ej = j0 + jj;
     const bool epi = tid < 128 && eb < B;
+    int len_e = T, len_a = T;
+    if (RAG) {
+        len_e = epi ? min(lens[eb], T) : 0;
+        len_a = b0 + r16 < B ? min(lens[b0 + r16], T) : 0;
+    }
     float xv[4] = {0.f, 0.f, 0.f, 0.f}, cp = 0.f;
-    if (epi) {
+    if (RAG && rev) {
+        if (s < len_e) {
+            t = len_e - 1 - s;
+            const float* xp = xproj + (((long long)eb * T + t) * ndir + d) * G4;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) xv[g] = xp[g * H + ej];
+            if (s > 0) cp = carry[((long long)d * B + eb) * H + ej];
+        }
+    } else if (epi) {
         const float* xp = xproj + (((long long)eb * T + t) * ndir + d) * G4;
 #pragma unroll
         for (int g = 0; g < 4; ++g) xv[g] = xp[g * H + ej];
-        if (s > 0) cp = c_out[((long long)eb * T + tp) * HH + (long long)d * H + ej];
+        if (s > 0) cp = RAG ? carry[((long long)d * B + eb) * H + ej] : c_out[((long long)eb * T + tp) * HH + (long long)d * H + ej];
     }
     if (s > 0) {
         const int b = b0 + r16;
+        if (RAG && rev) tp = s < len_a ? len_a - s : 0;   // an inactive row: a valid address, a zero operand
         const float* hp = h_out + ((long long)(b < B ? b : 0) * T + tp) * HH + (long long)d * H + wave * (H / 4) + q * KS;
         const float* up = Upk + ((((long long)d * (H / 8) + jt) * 4 + wave) * 64 + lane) * KS * 2;
         f32x4v acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -360,7 +451,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_pk_kernel(
             for (int i = 0; i < CH / 2; ++i) uv[i] = *reinterpret_cast<const f32x4a*>(up + 2 * s0 + 4 * i);
 #pragma unroll
             for (int i = 0; i < CH; ++i) {
-                const float a = b < B ? hv[i / 4][i % 4] : 0.f;
+                const float a = (RAG ? s < len_a : b < B) ? hv[i / 4][i % 4] : 0.f;
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, uv[i / 2][(i % 2) * 2], acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, uv[i / 2][(i % 2) * 2 + 1], acc1, 0, 0, 0);
             }
@@ -373,6 +464,10 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_pk_kernel(
         __syncthreads();
     }
     if (!epi) return;
+    if (RAG && s >= len_e) {
+        h_out[((long long)eb * T + s) * HH + (long long)d * H + ej] = 0.f;
+        return;
+    }
     float a4[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -386,11 +481,15 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_pk_kernel(
     const float gi = sigmoidf_(a4[0]), gf = sigmoidf_(a4[1]), gc = tanhf(a4[2]), go = sigmoidf_(a4[3]);
     const long long so = ((long long)eb * T + t) * HH + (long long)d * H + ej;
     const float c = gf * cp + gi * gc;
-    c_out[so] = c;
+    if (RAG) carry[((long long)d * B + eb) * H + ej] = c;
+    if (!RAG || c_out) c_out[so] = c;
     h_out[so] = go * tanhf(c);
-    float* gp = gates + (((long long)eb * T + t) * ndir + d) * G4;
-    gp[ej] = gi; gp[H + ej] = gf; gp[2 * H + ej] = gc; gp[3 * H + ej] = go;
+    if (!RAG || gates) {
+        float* gp = gates + (((long long)eb * T + t) * ndir + d) * G4;
+        gp[ej] = gi; gp[H + ej] = gf; gp[2 * H + ej] = gc; gp[3 * H + ej] = go;
+    }
 }
+
 
 template <int NW>   // waves per workgroup: 4, or 8 (H = 256: the K = 4H reduction over eight waves -- half the dependent MFMA chain and
                     // half the load rounds per wave of this latency-bound step)
@@ -515,6 +614,55 @@ extern "C" int ptts_lstm_fwd(const float* xproj, const float* U, float* h_out, f
                            reverse, s);
     }
     return check_launch("lstm_fwd");
+}
+
+// bytes of the ragged forward's cell-state carry [ndir][B][H] at the head of its workspace (whole 256-byte lines, so the
+// packed operand behind it keeps its 16-byte loads)
+static inline size_t lstm_carry_bytes(int B, int H, int ndir) {
+    return ((size_t)ndir * B * H * sizeof(float) + 255) & ~(size_t)255;
+}
+
+// Forward for inference over a zero-padded batch with a length per row (see lstm_fwd_step_body).  gates and c_out may be
+// NULL.  workspace: the cell-state carry, ndir*B*H floats rounded up to 256 bytes, then the packed recurrent operand of
+// ptts_lstm_fwd_workspace_bytes; without room for the latter a packed-path H takes the MFMA path, as in ptts_lstm_fwd.
+extern "C" int ptts_lstm_fwd_ragged(const float* xproj, const float* U, float* h_out, float* gates, float* c_out,
+                                    const int* lens, void* workspace, size_t workspace_bytes, int B, int T, int H,
+                                    int ndir, int reverse, void* stream) {
+    PTTS_REQUIRE(xproj && U && h_out && lens, "lstm_fwd_ragged: null tensor");
+    PTTS_REQUIRE(B > 0 && T > 0 && H > 0 && (ndir == 1 || ndir == 2), "lstm_fwd_ragged: bad dims");
+    PTTS_REQUIRE((size_t)LY * H * sizeof(float) <= 64 * 1024, "lstm_fwd_ragged: H=%d too large", H);
+    const size_t cb = lstm_carry_bytes(B, H, ndir);
+    if (!workspace || workspace_bytes < cb) {
+        set_error("lstm_fwd_ragged: workspace %zu < %zu", workspace_bytes, cb);
+        return PTTS_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float* carry = (float*)workspace;
+    if (lstm_pk_ok(H) && workspace_bytes >= cb + ptts_lstm_fwd_workspace_bytes(B, T, H, ndir)) {
+        float* Upk = (float*)((char*)workspace + cb);
+        dim3 mgrid(H / 8, (B + 15) / 16, ndir);
+        const int KS = H / 16;
+        hipLaunchKernelGGL(lstm_pack_u_fwd_kernel, dim3(1024), dim3(256), 0, st, U, Upk, H, ndir);
+        for (int s = 0; s < T; ++s) {
+            if (KS % 16 == 0) hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<16>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s, lens, carry);
+            else if (KS % 8 == 0) hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<8>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s, lens, carry);
+            else hipLaunchKernelGGL(lstm_fwd_step_pk_kernel<4>, mgrid, dim3(256), 0, st, xproj, (const float*)Upk, h_out, gates, c_out, B, T, H, ndir, reverse, s, lens, carry);
+        }
+        return check_launch("lstm_fwd_ragged_pk");
+    }
+    if (H % 16 == 0) {
+        dim3 mgrid(H / 8, (B + 15) / 16, ndir);
+        for (int s = 0; s < T; ++s)
+            hipLaunchKernelGGL(lstm_fwd_step_mfma_kernel, mgrid, dim3(256), 0, st, xproj, U, h_out, gates, c_out, B,
+                               T, H, ndir, reverse, s, lens, carry);
+        return check_launch("lstm_fwd_ragged_mfma");
+    }
+    dim3 grid((H + LX - 1) / LX, (B + LY - 1) / LY, ndir), block(LX, LY);
+    const size_t lds = (size_t)LY * H * sizeof(float);
+    for (int s = 0; s < T; ++s)
+        hipLaunchKernelGGL(lstm_fwd_step_ragged_kernel, grid, block, lds, st, xproj, U, h_out, gates, c_out, B, T, H, ndir,
+                           reverse, s, lens, carry);
+    return check_launch("lstm_fwd_ragged");
 }
 
 extern "C" size_t ptts_lstm_bwd_workspace_bytes(int B, int T, int H, int ndir) {

@@ -46,6 +46,24 @@ def to_tensor(v):
     return v
 
 
+def ragged_lengths(memo):
+    """The per-row lengths of a ragged inference pass (memo['lengths'], an int32 device tensor [B]), or None."""
+    return None if memo is None else memo.get('lengths')
+
+
+def ragged_input(v, memo):
+    """Ragged inference: the input of a layer that reads across time, with its pending affine / LeakyReLU applied and the frames
+    t >= length zeroed in one pass (ops.affine_act_rows); otherwise `v` itself.  The masked tensor is kept in `memo` for the other
+    consumers of the same value (the two convolutions of a gated pair)."""
+    lengths = ragged_lengths(memo)
+    if lengths is None:
+        return v
+    key = ('ragged_input', id(v))
+    if key not in memo:
+        memo[key] = (v, ops.affine_act_rows(v.tensor() if isinstance(v, LazyConcat) else v, lengths))
+    return memo[key][1]
+
+
 # --------------------------------------------------------------------------------------------
 # initialisers (numpy global RNG: the reference seeds it with 123 at import, percivaltts.py:30-33)
 # --------------------------------------------------------------------------------------------
@@ -285,7 +303,7 @@ class Conv1D(Layer):
         return (self.filters,)
 
     def compute(self, vals, training, memo):
-        return ops.conv1d(to_tensor(vals[0]), self.kernel, self.bias)
+        return ops.conv1d(to_tensor(ragged_input(vals[0], memo)), self.kernel, self.bias)
 
 
 class Conv2D(Layer):
@@ -307,7 +325,7 @@ class Conv2D(Layer):
         return (in_shapes[0][0], self.filters)
 
     def compute(self, vals, training, memo):
-        v = vals[0]
+        v = ragged_input(vals[0], memo)
         if isinstance(v, LazyConcat):
             v = v.tensor()
         if getattr(self, 'bn_follows', False) and training and self.activation in (None, 'linear') and self.bf16 is None:
@@ -359,6 +377,9 @@ class Conv2DStack(Layer):
         return [getattr(self, 'kernel_{}'.format(li)) for li in range(self.nlayers)], [getattr(self, 'bias_{}'.format(li)) for li in range(self.nlayers)]
 
     def compute(self, vals, training, memo):
+        if ragged_lengths(memo) is not None:
+            raise ValueError('Conv2DStack {!r} does not take per-row lengths: ragged inference covers the generator\'s layers only'
+                             .format(self.lname))
         x0 = to_tensor(vals[0])
         ws, bs = self.kernels()
         if x0.is_cuda and ops._C2C.supported(x0.shape[-1], ws):
@@ -394,6 +415,8 @@ class LSTM(Layer):
 
     def compute(self, vals, training, memo):
         x = to_tensor(vals[0] if not isinstance(vals[0], LazyConcat) else vals[0].tensor()).contiguous()
+        if ragged_lengths(memo) is not None:
+            return ops.lstm_infer(x, self.kernel, self.recurrent_kernel, self.bias, ragged_lengths(memo))
         return ops.lstm(x, self.kernel, self.recurrent_kernel, self.bias)
 
 
@@ -418,6 +441,8 @@ class GRU(Layer):
 
     def compute(self, vals, training, memo):
         x = to_tensor(vals[0] if not isinstance(vals[0], LazyConcat) else vals[0].tensor()).contiguous()
+        if ragged_lengths(memo) is not None:
+            return ops.gru_infer(x, self.kernel, self.recurrent_kernel, self.bias, ragged_lengths(memo))
         return ops.gru(x, self.kernel, self.recurrent_kernel, self.bias)
 
 
@@ -674,7 +699,19 @@ class Model(nn.Module):
             xs = tuple(xs[0])
         assert len(xs) == len(self.inputs), 'model expects {} inputs'.format(len(self.inputs))
         feed = {id(n): x for n, x in zip(self.inputs, xs)}
+        lengths = ragged_lengths(memo)
+        if lengths is not None:
+            # ragged inference: a zero-padded batch with a length per row (see ops.affine_act_rows)
+            if training:
+                raise ValueError('lengths are for inference: training=True is not supported')
+            ops.check_lengths(lengths, xs[0].shape[0], xs[0].shape[1])
         values = self._run(feed, training, memo)
+        if lengths is not None:
+            outs = []
+            for o in self.outputs:         # pad rows of the result are zero
+                v = values[id(o)]
+                outs.append(ops.affine_act_rows(v.tensor() if isinstance(v, LazyConcat) else v, lengths))
+            return outs[0] if self.single_output else outs
         outs = [to_tensor(values[id(o)]) for o in self.outputs]
         return outs[0] if self.single_output else outs
 

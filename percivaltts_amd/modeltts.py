@@ -56,6 +56,33 @@ class ModelTTS:
         """Inference forward (BatchNorm uses its moving statistics): numpy [B,T,ctx] -> numpy [B,T,out]."""
         return self.predict_device(x).cpu().numpy()
 
+    def predict_device_batch(self, xs):
+        """Ragged inference: `xs` is a list of [T_i, ctx] arrays or tensors of unequal lengths; returns the list of [T_i, out]
+        float32 device tensors.  The utterances are zero-padded to the longest and go through ONE forward with a length per row:
+        every layer that reads across time (Conv1D, Conv2D, LSTM, GRU) sees zeros behind each row's end, which is what 'same'
+        padding shows a lone utterance, and the recurrences walk each row over its own length (layers.ragged_input,
+        ops.lstm_infer / gru_infer).  Each result is what predict_device gives for that utterance alone up to the rounding of
+        products that run at another row count."""
+        if len(xs) == 0:
+            return []
+        dev = self.to_device()
+        with torch.no_grad():
+            ts = [torch.as_tensor(x if torch.is_tensor(x) else np.ascontiguousarray(x), dtype=torch.float32) for x in xs]
+            for t in ts:
+                if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != ts[0].shape[1]:
+                    raise ValueError('predict_device_batch: every utterance has to be [T >= 1, ctx], got {}'.format(tuple(t.shape)))
+            lens = [int(t.shape[0]) for t in ts]
+            xpad = torch.zeros((len(ts), max(lens), ts[0].shape[1]), dtype=torch.float32, device=dev)
+            for i, t in enumerate(ts):
+                xpad[i, :lens[i]] = t.to(dev)
+            lengths = torch.tensor(lens, dtype=torch.int32, device=dev)
+            y = self.kerasmodel(xpad, training=False, memo={'lengths': lengths})
+            return [y[i, :lens[i]] for i in range(len(ts))]
+
+    def predict_batch(self, xs):
+        """predict_device_batch with the results copied back: a list of numpy [T_i, out]."""
+        return [y.cpu().numpy() for y in self.predict_device_batch(xs)]
+
     def count_params(self):
         return self.kerasmodel.count_params()
 
@@ -128,7 +155,7 @@ class ModelTTS:
         return [self.vocoder.synthesis_device(c, pp_mcep=pp_mcep) for c in CMPs]
 
     def generate_params(self, inpath, outpath, fid_lst, gendir, do_objmeas=True, batch_size=8, pp_mcep=False, specdir=None,
-                        wavdir=None):
+                        *, predict_batched=False, wavdir=None):
         """The reference's generate_wav (modeltts.py:144-205) up to the vocoder call: read mean4norm.dat / std4norm.dat beside
         `outpath`, predict each file of `fid_lst`, de-normalise (with MLPG when the vocoder has `mlpg_wins`), write
         `gendir/<fid>.cmp` as headerless float32 [T, featuressizeraw()], and, with `do_objmeas`, feed the vocoder's objective
@@ -140,6 +167,12 @@ class ModelTTS:
         reference: padding would change what a context Conv1D or a BLSTM computes for an utterance's real frames wherever it
         looks across the pad, and the files must not depend on how they were batched.  Only the MLPG launch is batched; its
         systems are independent, so the files are bit-identical for every `batch_size`.
+
+        With `predict_batched` the utterances of each `batch_size` group go through the network together as well
+        (predict_device_batch: one forward over the zero-padded group with a length per row, no layer looking across a row's end).
+        Each utterance's result is then the lone one up to rounding only -- the products run at another row count and may pick
+        another kernel or summation split -- so the files agree with the default's to about 5e-4 relative (times std4norm per
+        column), they are not bit-identical, and they can depend on `batch_size`.  Off by default.
 
         With `specdir` each utterance's spectral columns also go through the vocoder's decompress_spectrum(pp_mcep=pp_mcep) while
         they are on the device (csrc/spectrum.hip) and `specdir/<fid>.spec` is written as headerless float32 [T, dftlen/2+1]:
@@ -184,13 +217,17 @@ class ModelTTS:
             var = std * std                 # "Simplification!" (modeltts.py:176): the global variance at every frame
         for v0 in range(0, len(fid_lst), batch_size):
             vis = list(range(v0, min(v0 + batch_size, len(fid_lst))))
-            ys = []
-            for vi in vis:
-                print('Generating {}/{} fid={} ...'.format(1 + vi, len(fid_lst), fid_lst[vi]))
-                y = self.predict_device(np.reshape(X_test[vi], [1] + [s for s in X_test[vi].shape]))[0]
+            if predict_batched:
+                print('Generating {}-{}/{} ...'.format(1 + vis[0], 1 + vis[-1], len(fid_lst)))
+                ys = self.predict_device_batch([X_test[vi] for vi in vis])
+            else:
+                ys = []
+                for vi in vis:
+                    print('Generating {}/{} fid={} ...'.format(1 + vi, len(fid_lst), fid_lst[vi]))
+                    ys.append(self.predict_device(np.reshape(X_test[vi], [1] + [s for s in X_test[vi].shape]))[0])
+            for y in ys:
                 if y.shape[-1] != nout:
                     raise ValueError('the model predicts {} features, the vocoder expects {}'.format(y.shape[-1], nout))
-                ys.append(y)
             if use_mlpg:
                 lens = [int(y.shape[0]) for y in ys]
                 if len(ys) == 1:

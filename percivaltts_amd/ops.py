@@ -2206,6 +2206,38 @@ def affine_act(x, scale=None, shift=None, act=None, alpha=0.3):
 
 
 # ----------------------------------------------------------------------------------------------
+# ragged inference: a zero-padded batch [B, Tmax, ...] with a length per row.  Every layer that reads across time sees zeros at
+# t >= lengths[b] (affine_act_rows in front of the convolutions; the recurrences take the lengths themselves), so each row's real
+# frames are what that utterance gives alone.  No autograd nodes: inference only.
+# ----------------------------------------------------------------------------------------------
+def check_lengths(lengths, B, T):
+    """`lengths` must be an int32 device tensor [B]; the values (1 <= lengths[b] <= T) are the caller's to guarantee."""
+    if not (torch.is_tensor(lengths) and lengths.dtype == torch.int32 and lengths.is_cuda and lengths.dim() == 1
+            and lengths.is_contiguous()):
+        raise ValueError('lengths must be a contiguous int32 device tensor [B]')
+    if lengths.numel() != B:
+        raise ValueError('lengths has {} entries for a batch of {}'.format(lengths.numel(), B))
+    if torch.is_grad_enabled():
+        raise ValueError('lengths are for inference: run under torch.no_grad()')
+    return lengths
+
+
+def affine_act_rows(v, lengths, act=None, alpha=0.3):
+    """v [B,T,...,C], a tensor or a Lazy -> its pending affine and LeakyReLU (a plain tensor: `act`) applied and the frames
+    t >= lengths[b] zeroed, in one pass (ptts_affine_act_rows).  Returns a new plain tensor."""
+    lz = as_lazy(v)
+    x = f32c(lz.z.contiguous(), 'affine_act_rows.x')
+    B, T, C = x.shape[0], x.shape[1], x.shape[-1]
+    check_lengths(lengths, B, T)
+    if lz.lrelu:
+        act, alpha = 'lrelu', lz.alpha
+    y = torch.empty_like(x)
+    call('ptts_affine_act_rows', ptr(x), ptr(lz.scale), ptr(lz.shift), ptr(y), ptr(lengths), B, T, x.numel() // (B * T), C,
+         ACT_CODES[act], alpha, stream())
+    return y
+
+
+# ----------------------------------------------------------------------------------------------
 # random layers on the library's counter-based generator (csrc/random.hip): Dropout (networktts.py:65-70) and the noise
 # channels of GaussianNoiseInput (networktts.py:36-56)
 # ----------------------------------------------------------------------------------------------
@@ -2500,6 +2532,27 @@ def lstm(v, W, U, b, reverse=False):
     return LSTMFn.apply(as_tensor(v).contiguous(), W, U, b, reverse)
 
 
+def lstm_infer(x, W, U, b, lengths, reverse=False):
+    """LSTM forward over a zero-padded batch x [B,Tmax,In] with a length per row (ptts_lstm_fwd_ragged): h [B,Tmax,ndir*H], on
+    each row's real frames what lstm() gives for that row alone, zero behind them.  No autograd node; neither the gates nor the
+    cell states are stored."""
+    x = as_tensor(x).contiguous()
+    f32c(x, 'lstm.x'); f32c(W); f32c(U); f32c(b)
+    B, T, In = x.shape
+    ndir, H, G4 = U.shape
+    assert G4 == 4 * H and W.shape == (In, ndir * G4)
+    check_lengths(lengths, B, T)
+    dev = x.device
+    xproj = torch.empty((B, T, ndir * G4), dtype=torch.float32, device=dev)
+    h = torch.empty((B, T, ndir * H), dtype=torch.float32, device=dev)
+    gemm_raw(x, W, xproj, B * T, ndir * G4, In, bias=b)
+    carry = (ndir * B * H * 4 + 255) // 256 * 256
+    ws = _workspace(carry + _hip.lib().ptts_lstm_fwd_workspace_bytes(B, T, H, ndir), dev)
+    call('ptts_lstm_fwd_ragged', ptr(xproj), ptr(U), ptr(h), None, None, ptr(lengths), ptr(ws), ws.numel(), B, T, H, ndir,
+         int(reverse), stream())
+    return h
+
+
 # ----------------------------------------------------------------------------------------------
 # GRU / Bidirectional GRU, reset_after=False, hard-sigmoid gates (networktts.py:101-114)
 # ----------------------------------------------------------------------------------------------
@@ -2566,6 +2619,26 @@ class GRUFn(torch.autograd.Function):
 
 def gru(v, W, U, b):
     return GRUFn.apply(as_tensor(v).contiguous(), W, U, b)
+
+
+def gru_infer(x, W, U, b, lengths):
+    """GRU forward over a zero-padded batch with a length per row (ptts_gru_fwd_ragged); see lstm_infer."""
+    x = as_tensor(x).contiguous()
+    f32c(x, 'gru.x'); f32c(W); f32c(U); f32c(b)
+    B, T, In = x.shape
+    ndir, H, G3 = U.shape
+    assert G3 == 3 * H and W.shape == (ndir, In, G3) and b.shape == (ndir, G3)
+    check_lengths(lengths, B, T)
+    dev, M = x.device, B * T
+    xproj = torch.empty((B, T, ndir * G3), dtype=torch.float32, device=dev)
+    h = torch.empty((B, T, ndir * H), dtype=torch.float32, device=dev)
+    xp2 = xproj.view(M, ndir * G3)
+    for d in range(ndir):
+        gemm_raw(x, W[d], xp2[:, d * G3:], M, G3, In, ldc=ndir * G3, bias=b[d])
+    ws = _workspace(_hip.lib().ptts_gru_fwd_workspace_bytes(B, T, H, ndir) + 2 * ndir * B * H * 4, dev)
+    call('ptts_gru_fwd_ragged', ptr(xproj), ptr(U), ptr(h), None, None, ptr(lengths), ptr(ws), ws.numel(), B, T, H, ndir,
+         stream(), tag=(B, T, H, ndir))
+    return h
 
 
 # ----------------------------------------------------------------------------------------------

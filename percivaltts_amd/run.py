@@ -239,11 +239,13 @@ def generate(fparams=None):
     # with synthesis_device (VocoderPML, VocoderWORLDDevice), the waveforms of the build's own synthesiser in <model>-demo-snd
     # (cfg.wavdir overrides the place)
     demostart = cfg.id_test_demostart if hasattr(cfg, 'id_test_demostart') else 0
-    # cfg.specdir / cfg.pp_mcep, if present: also write the decompressed (post-filtered) spectral envelopes
+    # cfg.specdir / cfg.pp_mcep, if present: also write the decompressed (post-filtered) spectral envelopes;
+    # cfg.predict_batched, if present and true: the network runs on each group of utterances at once (ragged inference)
     mod.generate_params(cfg.inpath, cfg.outpath, fid_lst_test[demostart:demostart + 10], os.path.splitext(fparams)[0] + '-demo-params',
                         do_objmeas=True, pp_mcep=getattr(cfg, 'pp_mcep', False), specdir=getattr(cfg, 'specdir', None),
                         wavdir=(getattr(cfg, 'wavdir', os.path.splitext(fparams)[0] + '-demo-snd')
-                                if hasattr(mod.vocoder, 'synthesis_device') else None))
+                                if hasattr(mod.vocoder, 'synthesis_device') else None),
+                        predict_batched=bool(getattr(cfg, 'predict_batched', False)))
 
 
 if __name__ == "__main__":
