@@ -541,6 +541,11 @@ int ptts_affine_act(const float* x, const float* scale, const float* shift, floa
  * [B,T,C], F*C for a Conv2D map).  lens: device int [B].  scale/shift NULL together = identity.  y == x is allowed. */
 int ptts_affine_act_rows(const float* x, const float* scale, const float* shift, float* y, const int* lens,
                          int B, int T, int inner, int C, int act, float alpha, void* stream);
+/* Its backward with respect to x (evaluation with an input gradient: no parameter gradients):
+ * dx[b,t,i] = t < lens[b] ? dy * act'(x*scale[c]+shift[c]) * scale[c] : +0.  act: PTTS_ACT_NONE or PTTS_ACT_LRELU (x may be
+ * NULL for NONE).  The same indexing; a float4 path where C % 4 == 0 and the pointers are 16-byte aligned.  dx == dy is allowed. */
+int ptts_affine_act_rows_bwd(const float* dy, const float* x, const float* scale, const float* shift, float* dx,
+                             const int* lens, int B, int T, int inner, int C, int act, float alpha, void* stream);
 /* dx = dy * act'(.) * scale ; dscale/dshift reductions (NULL to skip).  `y` is the forward output (sigmoid/tanh use it). */
 int ptts_affine_act_bwd(const float* dy, const float* x, const float* y, const float* scale, const float* shift,
                         float* dx, double* dsums /*[2C]: dscale, dshift; or NULL*/,
@@ -568,6 +573,17 @@ int ptts_gp_penalty(const float* sq /*[B]*/, float* penalty /*[1]*/, float* coef
 /* dg = upstream[0] * coef[b] * g */
 int ptts_gp_scale_rows(const float* g, const float* coef, const float* upstream /*[1] or NULL(=1)*/, float* dg,
                        int B, long long TD, void* stream);
+
+/* Per-row costs of a ragged batch [B,T,...] with a length per row (lens: device int [B], 1 <= lens[b] <= T): one workgroup per
+ * row, fp64 partials summed in a fixed order, no atomics -- a row's result depends on nothing but that row. */
+/* out[b] = sign * mean over t < lens[b] and all `inner` elements of v [B,T,inner] */
+int ptts_rows_mean(const float* v, const int* lens, int B, int T, int inner, float sign, float* out /*[B]*/, void* stream);
+/* out_ls[b] = mean_{t<lens[b],d} (y-yhat)^2 * w[d] (specweighted_lse_loss of that row alone; w NULL = 1) and the unweighted
+ * out_sq[b] = sum_{t<lens[b],d} (y-yhat)^2 in one pass; either output may be NULL */
+int ptts_wlse_rows(const float* y, const float* yhat, const float* w /*[D] or NULL*/, const int* lens, int B, int T, int D,
+                   float* out_ls /*[B] or NULL*/, double* out_sq /*[B] or NULL*/, void* stream);
+/* out[b] = (1 - sqrt(sq[b]))^2: the gradient penalty per sample, from ptts_gp_sqnorm's sq */
+int ptts_gp_penalty_rows(const float* sq /*[B]*/, float* out /*[B]*/, int B, void* stream);
 
 /* wasserstein_loss (:70-71): out[0] = sign * mean(v) ; specweighted_lse_loss (:73-79): out[0] = mean((y-yhat)^2 * w[d]) */
 int ptts_mean_scaled(const float* v, long long n, float sign, float* out, void* stream);

@@ -269,9 +269,80 @@ def cost_model_mfn(fn, Xs):
     return cost / len(Xs[0])
 
 
-def cost_model_prediction_rmse(mod, Xs, Y_val, inouttimesync=True):
+def upload(t, dev):
+    """A host tensor on the device `dev` without making the host wait for the device: staged in pinned memory, copied
+    asynchronously on the current stream (the pinned block is recycled only once that copy has run)."""
+    import torch
+    if t.is_cuda or torch.device(dev).type != 'cuda':
+        return t.to(dev)
+    return t.contiguous().pin_memory().to(dev, non_blocking=True)
+
+
+def pad_to_device(xs, dev, what='pad_to_device'):
+    """A list of [T_i >= 1, D] arrays or tensors -> (zero-padded float32 device tensor [B, max T_i, D], the lengths as an int32 device
+    tensor [B], the lengths as a list): the form ragged inference takes (memo['lengths']).  Host utterances are padded on the host
+    and go up in one asynchronous copy (`upload`)."""
+    import torch
+    ts = [torch.as_tensor(x if torch.is_tensor(x) else np.ascontiguousarray(x), dtype=torch.float32) for x in xs]
+    for t in ts:
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != ts[0].shape[1]:
+            raise ValueError('{}: every utterance has to be [T >= 1, ctx], got {}'.format(what, tuple(t.shape)))
+    lens = [int(t.shape[0]) for t in ts]
+    on_host = not any(t.is_cuda for t in ts)
+    xpad = torch.zeros((len(ts), max(lens), ts[0].shape[1]), dtype=torch.float32, device='cpu' if on_host else dev)
+    for i, t in enumerate(ts):
+        xpad[i, :lens[i]] = t if on_host else t.to(dev)
+    return upload(xpad, dev), upload(torch.tensor(lens, dtype=torch.int32), dev), lens
+
+
+def _padding(lens, groups):
+    return sum(len(g) * max(lens[i] for i in g) - sum(lens[i] for i in g) for g in groups)
+
+
+def length_groups(lens, batch_size, sort=True):
+    """Index groups of at most `batch_size` utterances for ragged batches: every index of range(len(lens)) once.  Without `sort`
+    the groups are consecutive runs of the input order.  With it they are runs of the stable sort by length, so that utterances of
+    similar length share a group and the frames spent on padding (group size x longest - frames, summed) are as few as groups of
+    these sizes allow; the one short group (when batch_size does not divide the count) stands where that sum is least, the first
+    such place.  The caller scatters its results back to input order."""
+    n, k = len(lens), int(batch_size)
+    if k < 1:
+        raise ValueError('batch_size has to be at least 1')
+    chunk = lambda order, sizes: [[order.pop(0) for _ in range(s)] for s in sizes]
+    sizes = [k] * (n // k) + ([n % k] if n % k else [])
+    if not sort:
+        return chunk(list(range(n)), sizes)
+    order = [int(i) for i in np.argsort(np.asarray(lens, dtype=np.int64), kind='stable')]
+    if n % k == 0 or n < k:
+        return chunk(order, sizes)
+    best = None
+    for pos in range(len(sizes)):
+        s = [k] * pos + [n % k] + [k] * (len(sizes) - 1 - pos)
+        groups = chunk(list(order), s)
+        pad = _padding(lens, groups)
+        if best is None or pad < best[0]:
+            best = (pad, groups)
+    return best[1]
+
+
+def cost_model_prediction_rmse(mod, Xs, Y_val, inouttimesync=True, batch_size=None, sort=True):
+    """sqrt(sum of squared errors / number of values) over the whole set.  `batch_size`: the utterances are predicted in ragged
+    batches (data.length_groups(lengths, batch_size, sort): of similar length; mod.predict_device_padded) and the squared errors are summed on the device (ptts_wlse_rows), one
+    download at the end; None: one utterance at a time through mod.predict, as the reference does."""
     if not isinstance(Xs[0], list):
         return 0.0
+    if batch_size is not None:
+        import torch
+        from . import ops
+        sq, nbel = [], 0
+        for g in length_groups([x.shape[0] for x in Xs[0]], batch_size, sort=sort):
+            ypred, lengths, lens = mod.predict_device_padded([Xs[0][i] for i in g])
+            ypad, _, ylens = pad_to_device([Y_val[i] for i in g], ypred.device, 'cost_model_prediction_rmse')
+            if ylens != lens or ypad.shape != ypred.shape:
+                raise ValueError('cost_model_prediction_rmse: inputs and targets differ in shape')
+            sq.append(ops.wlse_rows(ypad, ypred, None, lengths, want_ls=False)[1])
+            nbel += sum(lens) * int(ypred.shape[-1])
+        return float(np.sqrt(float(torch.cat(sq).sum().item()) / nbel))
     cost, nbel = 0.0, 0
     for xi, ins in _one_by_one(Xs):
         ypred = mod.predict(*ins)

@@ -51,6 +51,28 @@ def ragged_lengths(memo):
     return None if memo is None else memo.get('lengths')
 
 
+def ragged_input_grad(memo):
+    """True in the input-gradient mode of a ragged pass (memo['lengths_input_grad'] beside memo['lengths']): evaluation with
+    gradients enabled, the row masks carrying the masked gradient back to the input (ops.AffineActRowsFn)."""
+    return memo is not None and bool(memo.get('lengths_input_grad', False))
+
+
+def ragged_begin(memo, training, x):
+    """The checks every ragged evaluation of a Model starts with; returns the lengths, or None for a dense pass."""
+    lengths = ragged_lengths(memo)
+    if lengths is not None:
+        # a zero-padded batch with a length per row (see ops.affine_act_rows)
+        if training:
+            raise ValueError('lengths are for inference: training=True is not supported')
+        ops.check_lengths(lengths, x.shape[0], x.shape[1], allow_grad=ragged_input_grad(memo))
+    return lengths
+
+
+def ragged_output(v, memo):
+    """A result of a ragged evaluation as a tensor, its pad rows zero."""
+    return ops.affine_act_rows(v.tensor() if isinstance(v, LazyConcat) else v, ragged_lengths(memo), input_grad=ragged_input_grad(memo))
+
+
 def ragged_input(v, memo):
     """Ragged inference: the input of a layer that reads across time, with its pending affine / LeakyReLU applied and the frames
     t >= length zeroed in one pass (ops.affine_act_rows); otherwise `v` itself.  The masked tensor is kept in `memo` for the other
@@ -60,7 +82,8 @@ def ragged_input(v, memo):
         return v
     key = ('ragged_input', id(v))
     if key not in memo:
-        memo[key] = (v, ops.affine_act_rows(v.tensor() if isinstance(v, LazyConcat) else v, lengths))
+        memo[key] = (v, ops.affine_act_rows(v.tensor() if isinstance(v, LazyConcat) else v, lengths,
+                                            input_grad=ragged_input_grad(memo)))
     return memo[key][1]
 
 
@@ -699,26 +722,23 @@ class Model(nn.Module):
             xs = tuple(xs[0])
         assert len(xs) == len(self.inputs), 'model expects {} inputs'.format(len(self.inputs))
         feed = {id(n): x for n, x in zip(self.inputs, xs)}
-        lengths = ragged_lengths(memo)
-        if lengths is not None:
-            # ragged inference: a zero-padded batch with a length per row (see ops.affine_act_rows)
-            if training:
-                raise ValueError('lengths are for inference: training=True is not supported')
-            ops.check_lengths(lengths, xs[0].shape[0], xs[0].shape[1])
+        lengths = ragged_begin(memo, training, xs[0])
         values = self._run(feed, training, memo)
-        if lengths is not None:
-            outs = []
-            for o in self.outputs:         # pad rows of the result are zero
-                v = values[id(o)]
-                outs.append(ops.affine_act_rows(v.tensor() if isinstance(v, LazyConcat) else v, lengths))
-            return outs[0] if self.single_output else outs
-        outs = [to_tensor(values[id(o)]) for o in self.outputs]
+        return self._results(values, memo if lengths is not None else None)
+
+    def _results(self, values, ragged_memo=None):
+        """The outputs out of `values` as tensors; `ragged_memo`: of a ragged evaluation, so the pad rows of the results are zero."""
+        if ragged_memo is not None:
+            outs = [ragged_output(values[id(o)], ragged_memo) for o in self.outputs]
+        else:
+            outs = [to_tensor(values[id(o)]) for o in self.outputs]
         return outs[0] if self.single_output else outs
 
     def forward_multi(self, varying_index, variants, fixed, training=False, memo=None, parallel_streams=False):
         """Evaluate the model for several values of input `varying_index` while every node that does not
         depend on it (the critic's context branch) is computed once and shared."""
         memo = {} if memo is None else memo
+        ragged_begin(memo, training, variants[0])
         vin = self.inputs[varying_index]
         feed = {}
         fi = 0
@@ -748,6 +768,7 @@ class Model(nn.Module):
         inputs they would be sliced from).  `feed` = {input node: tensor} for the inputs the rest of the graph needs; nodes that only
         `node` depends on (its own inputs) are not evaluated.  Everything that does not depend on `node` is computed once and shared."""
         memo = {} if memo is None else memo
+        ragged = ragged_begin(memo, training, variants[0]) is not None
         desc = set([id(node)])
         for n in self.order:
             if any(id(p) in desc for p in n.parents):
@@ -779,7 +800,7 @@ class Model(nn.Module):
                     if i > 0 and id(pn) in shared and shared[id(pn)] is not None:
                         n.layer.prime_part(i, [pp.shape[-1] for pp in n.parents[0].parents], shared[id(pn)], memo)
         results = []
-        if pair and len(variants) == 2 and not parallel_streams and ops._PairFlags.enabled and \
+        if pair and not ragged and len(variants) == 2 and not parallel_streams and ops._PairFlags.enabled and \
                 not any(getattr(n, 'stream', 0) for n in self.order if id(n) in desc):
             # LOCKSTEP: the two evaluations walk the graph together, layer by layer; a layer that can (Conv2D, Dense: compute_pair) runs
             # both forwards as ONE launch when their inputs lie back to back in one buffer -- which its own two outputs then do for the
@@ -807,6 +828,7 @@ class Model(nn.Module):
         results = []
         streams = side_streams(len(variants) - 1) if parallel_streams else None
         cur = torch.cuda.current_stream() if parallel_streams else None
+        ragged_memo = memo if ragged_lengths(memo) is not None else None
         for vi, x in enumerate(variants):
             values = dict(shared)
             values[node_id] = x
@@ -814,12 +836,10 @@ class Model(nn.Module):
                 st = streams[vi - 1]
                 st.wait_stream(cur)
                 with torch.cuda.stream(st):
-                    values = self._run({}, training, memo, values)
-                    outs = [to_tensor(values[id(o)]) for o in self.outputs]
+                    res = self._results(self._run({}, training, memo, values), ragged_memo)
             else:
-                values = self._run({}, training, memo, values)
-                outs = [to_tensor(values[id(o)]) for o in self.outputs]
-            results.append(outs[0] if self.single_output else outs)
+                res = self._results(self._run({}, training, memo, values), ragged_memo)
+            results.append(res)
         if streams is not None:
             for vi in range(1, len(variants)):
                 cur.wait_stream(streams[vi - 1])

@@ -65,19 +65,16 @@ class ModelTTS:
         products that run at another row count."""
         if len(xs) == 0:
             return []
+        y, _, lens = self.predict_device_padded(xs)
+        return [y[i, :lens[i]] for i in range(len(lens))]
+
+    def predict_device_padded(self, xs):
+        """predict_device_batch before the results are cut out: (the padded result [B, Tmax, out] with zero pad rows, the lengths as
+        the int32 device tensor [B] the forward was given, the same lengths as a list)."""
         dev = self.to_device()
         with torch.no_grad():
-            ts = [torch.as_tensor(x if torch.is_tensor(x) else np.ascontiguousarray(x), dtype=torch.float32) for x in xs]
-            for t in ts:
-                if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != ts[0].shape[1]:
-                    raise ValueError('predict_device_batch: every utterance has to be [T >= 1, ctx], got {}'.format(tuple(t.shape)))
-            lens = [int(t.shape[0]) for t in ts]
-            xpad = torch.zeros((len(ts), max(lens), ts[0].shape[1]), dtype=torch.float32, device=dev)
-            for i, t in enumerate(ts):
-                xpad[i, :lens[i]] = t.to(dev)
-            lengths = torch.tensor(lens, dtype=torch.int32, device=dev)
-            y = self.kerasmodel(xpad, training=False, memo={'lengths': lengths})
-            return [y[i, :lens[i]] for i in range(len(ts))]
+            xpad, lengths, lens = data.pad_to_device(xs, dev, 'predict_device_batch')
+            return self.kerasmodel(xpad, training=False, memo={'lengths': lengths}), lengths, lens
 
     def predict_batch(self, xs):
         """predict_device_batch with the results copied back: a list of numpy [T_i, out]."""
@@ -155,7 +152,7 @@ class ModelTTS:
         return [self.vocoder.synthesis_device(c, pp_mcep=pp_mcep) for c in CMPs]
 
     def generate_params(self, inpath, outpath, fid_lst, gendir, do_objmeas=True, batch_size=8, pp_mcep=False, specdir=None,
-                        *, predict_batched=False, wavdir=None):
+                        *, predict_batched=False, group_by_length=False, wavdir=None):
         """The reference's generate_wav (modeltts.py:144-205) up to the vocoder call: read mean4norm.dat / std4norm.dat beside
         `outpath`, predict each file of `fid_lst`, de-normalise (with MLPG when the vocoder has `mlpg_wins`), write
         `gendir/<fid>.cmp` as headerless float32 [T, featuressizeraw()], and, with `do_objmeas`, feed the vocoder's objective
@@ -173,6 +170,10 @@ class ModelTTS:
         Each utterance's result is then the lone one up to rounding only -- the products run at another row count and may pick
         another kernel or summation split -- so the files agree with the default's to about 5e-4 relative (times std4norm per
         column), they are not bit-identical, and they can depend on `batch_size`.  Off by default.
+
+        With `group_by_length` (beside `predict_batched`) the groups are made of utterances of similar length (data.length_groups:
+        runs of the stable sort by length) instead of consecutive ones, which spares the padded frames of a group whose lengths are
+        far apart; the files are written group by group and agree with the consecutive groups' to the same bound.  Off by default.
 
         With `specdir` each utterance's spectral columns also go through the vocoder's decompress_spectrum(pp_mcep=pp_mcep) while
         they are on the device (csrc/spectrum.hip) and `specdir/<fid>.spec` is written as headerless float32 [T, dftlen/2+1]:
@@ -215,8 +216,9 @@ class ModelTTS:
             dev = self.to_device()
             mean, std = torch.from_numpy(Ymean).to(dev), torch.from_numpy(Ystd).to(dev)
             var = std * std                 # "Simplification!" (modeltts.py:176): the global variance at every frame
-        for v0 in range(0, len(fid_lst), batch_size):
-            vis = list(range(v0, min(v0 + batch_size, len(fid_lst))))
+        if group_by_length and not predict_batched:
+            raise ValueError('group_by_length groups the batches of predict_batched: set both')
+        for vis in data.length_groups([x.shape[0] for x in X_test], batch_size, sort=bool(group_by_length)):
             if predict_batched:
                 print('Generating {}-{}/{} ...'.format(1 + vis[0], 1 + vis[-1], len(fid_lst)))
                 ys = self.predict_device_batch([X_test[vi] for vi in vis])

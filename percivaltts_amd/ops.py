@@ -2208,33 +2208,103 @@ def affine_act(x, scale=None, shift=None, act=None, alpha=0.3):
 # ----------------------------------------------------------------------------------------------
 # ragged inference: a zero-padded batch [B, Tmax, ...] with a length per row.  Every layer that reads across time sees zeros at
 # t >= lengths[b] (affine_act_rows in front of the convolutions; the recurrences take the lengths themselves), so each row's real
-# frames are what that utterance gives alone.  No autograd nodes: inference only.
+# frames are what that utterance gives alone.  No autograd nodes: inference only -- except in the input-gradient mode
+# (memo['lengths_input_grad'], evaluation of the critic's gradient penalty): there the mask is an autograd Function whose backward
+# is the masked gradient (ptts_affine_act_rows_bwd), so d sum_{t<len} D(x^)_b / d x^_b on the padded batch is the lone utterance's
+# gradient on its real frames and exactly zero behind them.  The recurrences refuse gradients in either mode.
 # ----------------------------------------------------------------------------------------------
-def check_lengths(lengths, B, T):
-    """`lengths` must be an int32 device tensor [B]; the values (1 <= lengths[b] <= T) are the caller's to guarantee."""
+def check_lengths(lengths, B, T, allow_grad=False):
+    """`lengths` must be an int32 device tensor [B]; the values (1 <= lengths[b] <= T) are the caller's to guarantee.
+    `allow_grad`: the input-gradient mode, the only one in which gradients may be enabled."""
     if not (torch.is_tensor(lengths) and lengths.dtype == torch.int32 and lengths.is_cuda and lengths.dim() == 1
             and lengths.is_contiguous()):
         raise ValueError('lengths must be a contiguous int32 device tensor [B]')
     if lengths.numel() != B:
         raise ValueError('lengths has {} entries for a batch of {}'.format(lengths.numel(), B))
-    if torch.is_grad_enabled():
+    if torch.is_grad_enabled() and not allow_grad:
         raise ValueError('lengths are for inference: run under torch.no_grad()')
     return lengths
 
 
-def affine_act_rows(v, lengths, act=None, alpha=0.3):
+def _affine_act_rows_raw(x, scale, shift, lengths, act, alpha):
+    B, T, C = x.shape[0], x.shape[1], x.shape[-1]
+    y = torch.empty_like(x)
+    call('ptts_affine_act_rows', ptr(x), ptr(scale), ptr(shift), ptr(y), ptr(lengths), B, T, x.numel() // (B * T), C,
+         act, alpha, stream())
+    return y
+
+
+class AffineActRowsFn(torch.autograd.Function):
+    """affine_act_rows with a gradient for its input (and for nothing else: evaluation never differentiates with respect to
+    weights, so a pending BatchNorm affine is a constant here)."""
+    @staticmethod
+    def forward(ctx, x, scale, shift, lengths, act, alpha):
+        ctx.save_for_backward(x, scale, shift, lengths)
+        ctx.cfg = (act, alpha)
+        return _affine_act_rows_raw(x, scale, shift, lengths, act, alpha)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, scale, shift, lengths = ctx.saved_tensors
+        act, alpha = ctx.cfg
+        dy = f32c(dy.contiguous(), 'affine_act_rows.dy')
+        B, T, C = x.shape[0], x.shape[1], x.shape[-1]
+        dx = torch.empty_like(x)
+        call('ptts_affine_act_rows_bwd', ptr(dy), ptr(x), ptr(scale), ptr(shift), ptr(dx), ptr(lengths), B, T,
+             x.numel() // (B * T), C, act, alpha, stream())
+        return dx, None, None, None, None, None
+
+
+def affine_act_rows(v, lengths, act=None, alpha=0.3, input_grad=False):
     """v [B,T,...,C], a tensor or a Lazy -> its pending affine and LeakyReLU (a plain tensor: `act`) applied and the frames
-    t >= lengths[b] zeroed, in one pass (ptts_affine_act_rows).  Returns a new plain tensor."""
+    t >= lengths[b] zeroed, in one pass (ptts_affine_act_rows).  Returns a new plain tensor.  `input_grad`: the input-gradient
+    mode -- gradients may be enabled and the result carries the masked gradient back to `v` (act none / lrelu)."""
     lz = as_lazy(v)
     x = f32c(lz.z.contiguous(), 'affine_act_rows.x')
-    B, T, C = x.shape[0], x.shape[1], x.shape[-1]
-    check_lengths(lengths, B, T)
+    check_lengths(lengths, x.shape[0], x.shape[1], allow_grad=input_grad)
     if lz.lrelu:
         act, alpha = 'lrelu', lz.alpha
-    y = torch.empty_like(x)
-    call('ptts_affine_act_rows', ptr(x), ptr(lz.scale), ptr(lz.shift), ptr(y), ptr(lengths), B, T, x.numel() // (B * T), C,
-         ACT_CODES[act], alpha, stream())
-    return y
+    if input_grad and torch.is_grad_enabled():
+        if act not in (None, 'linear', 'lrelu'):
+            raise ValueError('affine_act_rows: the input-gradient mode knows no activation {!r}'.format(act))
+        return AffineActRowsFn.apply(x, lz.scale, lz.shift, lengths, ACT_CODES[act], alpha)
+    return _affine_act_rows_raw(x, lz.scale, lz.shift, lengths, ACT_CODES[act], alpha)
+
+
+def rows_mean(v, lengths, sign=1.0):
+    """sign * mean over the real frames (t < lengths[b]) and everything behind the time axis of v [B,T,...] -> [B] (ptts_rows_mean)."""
+    v = f32c(v.detach().contiguous(), 'rows_mean.v')
+    B, T = v.shape[0], v.shape[1]
+    check_lengths(lengths, B, T, allow_grad=True)
+    out = torch.empty(B, dtype=torch.float32, device=v.device)
+    call('ptts_rows_mean', ptr(v), ptr(lengths), B, T, v.numel() // (B * T), float(sign), ptr(out), stream())
+    return out
+
+
+def wlse_rows(y, yhat, w, lengths, want_ls=True, want_sq=True):
+    """Per row of the ragged pair y, yhat [B,T,D]: (mean_{t<len,d} (y - yhat)^2 w[d] as float32 [B], sum_{t<len,d} (y - yhat)^2 as
+    float64 [B]) in one pass (ptts_wlse_rows); an output not wanted is None.  w [D] or None."""
+    y, yhat = f32c(y.detach().contiguous(), 'wlse_rows.y'), f32c(yhat.detach().contiguous(), 'wlse_rows.yhat')
+    f32c(w, 'wlse_rows.w')
+    assert y.shape == yhat.shape and y.dim() == 3 and (w is None or w.numel() == y.shape[-1])
+    B, T, D = y.shape
+    check_lengths(lengths, B, T, allow_grad=True)
+    ls = torch.empty(B, dtype=torch.float32, device=y.device) if want_ls else None
+    sq = torch.empty(B, dtype=torch.float64, device=y.device) if want_sq else None
+    call('ptts_wlse_rows', ptr(y), ptr(yhat), ptr(w), ptr(lengths), B, T, D, ptr(ls), ptr(sq), stream())
+    return ls, sq
+
+
+def gp_penalty_rows(g):
+    """(1 - ||g_b||_2)^2 per sample of g [B,...] -> [B] (ptts_gp_sqnorm, ptts_gp_penalty_rows); no autograd node."""
+    g = f32c(g.detach().contiguous(), 'gp.g')
+    B = g.shape[0]
+    sq = torch.empty(B, dtype=torch.float32, device=g.device)
+    out = torch.empty(B, dtype=torch.float32, device=g.device)
+    call('ptts_gp_sqnorm', ptr(g), ptr(sq), B, g.numel() // B, stream())
+    call('ptts_gp_penalty_rows', ptr(sq), ptr(out), B, stream())
+    return out
 
 
 # ----------------------------------------------------------------------------------------------

@@ -71,6 +71,8 @@ class OptimizerTTS:
         cfg.train_batch_length = None
         cfg.train_batch_lengthmax = None
         cfg.train_nbtrials = 1
+        cfg.train_validation_batch_size = None         # build extension: n >= 1 computes the validation costs on ragged batches of up to n utterances of similar length (data.length_groups); None: one utterance at a time, as the reference does
+        cfg.train_validation_sort_by_length = True     # ... grouped by length (False: consecutive groups in the order of the validation set)
         cfg.train_hypers = []
         cfg = self.default_options(cfg)
         cfg.train_log_plot = True
@@ -136,7 +138,7 @@ class OptimizerTTS:
         worst_val = data.cost_0pred_rmse(Y_vals)
         print("    0-pred validation RMSE = {} (100%)".format(worst_val))
         print('    initial RMS of prediction = {}'.format(data.prediction_rms(self._model, [X_vals])))
-        init_val = data.cost_model_prediction_rmse(self._model, [X_vals], Y_vals)
+        init_val = data.cost_model_prediction_rmse(self._model, [X_vals], Y_vals, batch_size=self._validation_batch_size())
         best_val = None
         print("    initial validation RMSE = {} ({:.4f}%)".format(init_val, 100.0 * init_val / worst_val))
 
@@ -409,8 +411,19 @@ class OptimizerTTS:
         self.opti.step(parallel.allreduce_sum_(self.opti.flat.grad))
         return float(np.sqrt(float(loss.item())))   # a cost related to the generator's error, whatever the loss type
 
+    def _validation_batch_size(self):
+        """cfg.train_validation_batch_size as an int >= 1, or None (one utterance at a time)."""
+        bs = getattr(self.cfg, 'train_validation_batch_size', None)
+        if bs is None:
+            return None
+        if int(bs) < 1:
+            raise ValueError('train_validation_batch_size has to be None or at least 1, got {!r}'.format(bs))
+        return int(bs)
+
     def update_validation_cost(self, costs, X_vals, Y_vals):
-        costs['model_rmse_validation'].append(data.cost_model_prediction_rmse(self._model, [X_vals], Y_vals))
+        costs['model_rmse_validation'].append(data.cost_model_prediction_rmse(self._model, [X_vals], Y_vals,
+                                                                              batch_size=self._validation_batch_size(),
+                                                                              sort=bool(getattr(self.cfg, 'train_validation_sort_by_length', True))))
         return costs['model_rmse_validation'][-1]
 
     def saveTrainingStateLossSpecific(self, fstate):

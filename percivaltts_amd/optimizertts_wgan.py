@@ -112,6 +112,7 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         self.critic = critic
         self.costs_tra_critic_batches = _DeviceCosts()
         self.generator_updates = 0
+        self.validation_alphas = None      # update_validation_cost: the penalty's interpolation weight per validation utterance (None: drawn)
         self._forget_step_state()
 
     def default_options(self, cfg):
@@ -179,6 +180,10 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         self.device = dev = self._model.to_device()
         self.world, self.rank = parallel.init()
 
+        if self._validation_batch_size() is not None and self._critic_stack_layers():
+            raise ValueError('cfg.train_validation_batch_size = {} needs a critic that takes per-row lengths, and the Conv2DStack of '
+                             'cfg.arch_critic_bf16 = {!r} does not: unset one of the two'.format(
+                                 cfg.train_validation_batch_size, getattr(self.critic.cfgarch, 'arch_critic_bf16', None)))
         generator = self._model.kerasmodel
         critic = self.critic.model
         critic.to(dev)
@@ -833,22 +838,127 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         self.costs_tra_critic_batches.append_device(lc)
         return None if lg is None else float(lg.item())
 
+    # ---- evaluation on ragged batches (cfg.train_validation_batch_size) -----------------------------------------------
+    def _critic_stack_layers(self):
+        return [l for l in self.critic.model.layers_list if isinstance(l, kl.Conv2DStack)]
+
+    def _validation_costs_group(self, Xs, Ys, alpha):
+        """validation_costs_batch for ONE group: the utterances zero-padded to the longest, one ragged generator forward, the critic
+        on real / fake / x^ of the same padded group under the input-gradient rule (layers.ragged_input_grad)."""
+        dev = self.device
+        X, lengths, lens = data.pad_to_device(Xs, dev, 'validation_costs_batch')
+        Y, _, ylens = data.pad_to_device(Ys, dev, 'validation_costs_batch')
+        if ylens != lens:
+            raise ValueError('validation_costs_batch: inputs and targets differ in length: {} / {}'.format(lens, ylens))
+        B = len(lens)
+        with torch.no_grad():
+            pred = self._model.kerasmodel(X, training=False, memo={'lengths': lengths})      # pad rows zero
+            gen_ls, sq_err = ops.wlse_rows(Y, pred, self._w_ls, lengths)
+            alpha = torch.rand(B, device=dev, dtype=torch.float32) if alpha is None else alpha.reshape(-1).contiguous()
+            node = getattr(self.critic, 'node_spec_in', None)
+            at_slice = node is not None and getattr(self.cfg, 'train_wgan_feed_spectra', True)
+            real, fake = (self._spec_of(Y).contiguous(), self._spec_of(pred).contiguous()) if at_slice else (Y, pred)
+            x_hat = ops.gp_interpolate(real, fake, alpha).requires_grad_(True)     # zero on the pad rows, as both its sources
+        memo = {'lengths': lengths, 'lengths_input_grad': True}
+        with torch.enable_grad():
+            # three B-row evaluations over ONE evaluation of the context branch; every convolution reads its input through the row
+            # mask, and so does the result: d sum(v_hat) / d x_hat is each utterance's own gradient, exactly zero on the pad rows
+            if at_slice:
+                valid, fake_v, v_hat = self.critic_net.forward_multi_at(node, [real, fake, x_hat], {self.critic.input_ctx: X},
+                                                                        training=False, memo=memo)
+            else:
+                valid, fake_v, v_hat = self.critic_net.forward_multi(0, [real, fake, x_hat], [X], training=False, memo=memo)
+            with ops.input_grad_only():
+                g = torch.autograd.grad(v_hat, x_hat, grad_outputs=torch.ones_like(v_hat))[0]
+        with torch.no_grad():
+            l_valid = ops.rows_mean(valid, lengths, -1.0)
+            l_fake = ops.rows_mean(fake_v, lengths, +1.0)
+            gen_wgan = ops.rows_mean(fake_v, lengths, -1.0)        # D(G(x)) of the generator's cost IS the critic's fake term
+            gp = ops.gp_penalty_rows(g)
+            critic_total = l_valid + l_fake + float(self.cfg.train_wgan_pg_lambda) * gp
+            if self._errtype == 'WGAN':
+                gen_total, gen_ls = gen_wgan, torch.zeros_like(gen_wgan)
+            else:
+                gen_total = self._wgan_weight * gen_wgan + gen_ls
+            nbel = lengths.to(torch.float64) * float(Y.shape[-1])
+        return {'sq_err': sq_err, 'nbel': nbel, 'gen_total': gen_total, 'gen_wgan': gen_wgan, 'gen_ls': gen_ls,
+                'critic_total': critic_total, 'l_valid': l_valid, 'l_fake': l_fake, 'gp': gp}
+
+    def validation_costs_batch(self, Xs, Ys, alphas=None, batch_size=None, sort=True):
+        """The evaluation-mode costs of every utterance of the lists Xs ([T_i, ctx]) / Ys ([T_i, out]), computed on ragged batches:
+        a dict of device tensors [N] in the order of the lists -- sq_err (float64, the sum of squared errors), nbel (float64, the
+        number of values), gen_total, gen_wgan, gen_ls (generator_loss(training=False) and its parts), critic_total, l_valid,
+        l_fake, gp (critic_loss(training=False) and its parts) -- each what the utterance gives alone, up to rounding.  Nothing is
+        downloaded and the host never waits for the device (host inputs go up through pinned memory: data.upload).
+
+        The utterances are grouped by data.length_groups(lengths, batch_size, sort) (`batch_size` None:
+        cfg.train_validation_batch_size, or all in one group).  Per group ONE ragged generator forward feeds all three costs, the
+        critic and its gradient penalty run on the same padded group, and nothing goes to the host.  `alphas`: the interpolation
+        weight of each utterance's penalty, [N] in the order of the lists (None: torch.rand per group).  WGAN: gen_ls is zero."""
+        if self._critic_stack_layers():
+            raise ValueError('validation_costs_batch: a critic built with arch_critic_bf16 (Conv2DStack) takes no per-row lengths; '
+                             'unset cfg.train_validation_batch_size or cfg.arch_critic_bf16')
+        if len(Xs) != len(Ys) or len(Xs) == 0:
+            raise ValueError('validation_costs_batch: {} inputs for {} targets'.format(len(Xs), len(Ys)))
+        if batch_size is None:
+            batch_size = self._validation_batch_size() or len(Xs)
+        self.wait_updates()
+        if alphas is not None:
+            alphas = torch.as_tensor(alphas if torch.is_tensor(alphas) else np.asarray(alphas), dtype=torch.float32).reshape(-1)
+            if alphas.numel() != len(Xs):
+                raise ValueError('validation_costs_batch: {} alphas for {} utterances'.format(alphas.numel(), len(Xs)))
+        groups = data.length_groups([int(x.shape[0]) for x in Xs], batch_size, sort=sort)
+        order = torch.tensor([i for g in groups for i in g], dtype=torch.long)
+        if alphas is not None:
+            alphas = data.upload(alphas[order.to(alphas.device)], self.device)      # in the order of the groups: one upload
+        parts, done = [], 0
+        for g in groups:
+            parts.append(self._validation_costs_group([Xs[i] for i in g], [Ys[i] for i in g],
+                                                      None if alphas is None else alphas[done:done + len(g)]))
+            done += len(g)
+        # back to the order of the lists: out[order[j]] = cat[j]
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(len(Xs), dtype=torch.long)
+        inv = data.upload(inv, self.device)
+        return {k: torch.cat([p[k] for p in parts])[inv] for k in parts[0]}
+
     def update_validation_cost(self, costs, X_vals, Y_vals):
         self.wait_updates()
+        bs = self._validation_batch_size()
+        alphas = getattr(self, 'validation_alphas', None)      # [N], one per validation utterance; None: drawn (parity tests set it)
+        if bs is not None and isinstance(X_vals, list):
+            # one sweep over ragged batches of similar length, one download: the reference's definitions -- the pooled RMSE and
+            # the per-utterance costs averaged over the utterances
+            vc = self.validation_costs_batch(X_vals, Y_vals, alphas, batch_size=bs,
+                                             sort=bool(getattr(self.cfg, 'train_validation_sort_by_length', True)))
+            sq, nbel, gen, cri = torch.stack([vc['sq_err'].sum(), vc['nbel'].sum(), vc['gen_total'].double().mean(),
+                                              vc['critic_total'].double().mean()]).cpu().tolist()
+            costs['model_rmse_validation'].append(float(np.sqrt(sq / nbel)))
+            costs['model_validation'].append(gen)
+            critic_batches = [c for c in self.costs_tra_critic_batches]
+            costs['critic_training'].append(np.mean(critic_batches))
+            costs['critic_validation'].append(cri)
+            return self._validation_cost_ltm(costs, critic_batches)
         costs['model_rmse_validation'].append(data.cost_model_prediction_rmse(self._model, [X_vals], Y_vals))
 
         def gen_cost(x, y):
             with torch.no_grad():
                 return float(self.generator_loss(self._to_dev(x), self._to_dev(y), training=False)[0].item())
 
+        seen = [0]
         def critic_cost(y, x):
-            total, _ = self.critic_loss(self._to_dev(x), self._to_dev(y), None, training=False)
+            alpha = None if alphas is None else self._to_dev(alphas).reshape(-1)[seen[0]:seen[0] + 1]
+            seen[0] += 1
+            total, _ = self.critic_loss(self._to_dev(x), self._to_dev(y), alpha, training=False)
             return float(total.item())
 
         costs['model_validation'].append(data.cost_model_mfn(gen_cost, [X_vals, Y_vals]))
         critic_batches = [c for c in self.costs_tra_critic_batches]      # (fetches the device-side entries)
         costs['critic_training'].append(np.mean(critic_batches))
         costs['critic_validation'].append(data.cost_model_mfn(critic_cost, [Y_vals, X_vals]))
+        return self._validation_cost_ltm(costs, critic_batches)
+
+    def _validation_cost_ltm(self, costs, critic_batches):
         costs['critic_validation_ltm'].append(np.mean(costs['critic_validation'][-self.cfg.train_wgan_validation_ltm_winlen:]))
         cost_val = costs['critic_validation_ltm'][-1]
 

@@ -222,6 +222,9 @@ def training(cont=False):
     fid_lst_tra = fids[:cfg.id_train_nb()]
     fid_lst_val = fids[cfg.id_valid_start:cfg.id_valid_start + cfg.id_valid_nb]
     mod = build_model()
+    # cfg.train_validation_batch_size = n (unset here: one utterance at a time, as the reference does): the validation costs of every
+    # epoch on ragged batches of up to n utterances of similar length -- one generator forward per batch feeds the RMSE, the
+    # generator's and the critic's cost (OptimizerTTSWGAN.validation_costs_batch); not with cfg.arch_critic_bf16
     if errtype == 'LSE': opti = optimizertts.OptimizerTTS(cfg, mod)
     else:                opti = optimizertts_wgan.OptimizerTTSWGAN(cfg, mod, errtype=errtype, critic=networks_critic.Critic(vocoder, ctxsize, cfg))
     opti.train(cfg.inpath, cfg.outpath, cfg.wpath, fid_lst_tra, fid_lst_val, cfg.fparams_fullset, cont=cont)
@@ -241,11 +244,14 @@ def generate(fparams=None):
     demostart = cfg.id_test_demostart if hasattr(cfg, 'id_test_demostart') else 0
     # cfg.specdir / cfg.pp_mcep, if present: also write the decompressed (post-filtered) spectral envelopes;
     # cfg.predict_batched, if present and true: the network runs on each group of utterances at once (ragged inference)
+    # (cfg.group_by_length beside it: the groups hold utterances of similar length); the counterpart for the validation sweep of
+    # training() is cfg.train_validation_batch_size -- all three unset here
     mod.generate_params(cfg.inpath, cfg.outpath, fid_lst_test[demostart:demostart + 10], os.path.splitext(fparams)[0] + '-demo-params',
                         do_objmeas=True, pp_mcep=getattr(cfg, 'pp_mcep', False), specdir=getattr(cfg, 'specdir', None),
                         wavdir=(getattr(cfg, 'wavdir', os.path.splitext(fparams)[0] + '-demo-snd')
                                 if hasattr(mod.vocoder, 'synthesis_device') else None),
-                        predict_batched=bool(getattr(cfg, 'predict_batched', False)))
+                        predict_batched=bool(getattr(cfg, 'predict_batched', False)),
+                        group_by_length=bool(getattr(cfg, 'group_by_length', False)))
 
 
 if __name__ == "__main__":
