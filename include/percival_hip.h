@@ -585,6 +585,20 @@ int ptts_wlse_rows(const float* y, const float* yhat, const float* w /*[D] or NU
 /* out[b] = (1 - sqrt(sq[b]))^2: the gradient penalty per sample, from ptts_gp_sqnorm's sq */
 int ptts_gp_penalty_rows(const float* sq /*[B]*/, float* out /*[B]*/, int B, void* stream);
 
+/* One batch cut out of a corpus resident on the device (data.DeviceCorpus, csrc/batchgather.hip).  Up to three streams
+ * (nstreams = 1..3: inputs, outputs, time weights; the unused ones NULL / 0) are packed row-wise, src_k [N_total][D_k] fp32,
+ * and share row_off [U+1] (device long long, in rows): utterance u is rows row_off[u] .. row_off[u+1]-1.  Row b of the batch is
+ * described by the device int arrays utt, shift, n [B]:
+ *   dst_k[b][t][:] = src_k[row_off[utt[b]] + shift[b] + t][:]  for t < n[b],   exactly 0 for n[b] <= t < T.
+ * Every element of every dst_k [B][T][D_k] is written once (no memset needed), all streams in ONE launch.  Source indices are
+ * 64-bit, so N_total * D_k is not limited; T * D_k has to fit an int and B <= 65535.  The caller guarantees 0 <= utt[b] < U,
+ * 0 <= shift[b], 0 <= n[b] <= T and shift[b] + n[b] <= the utterance's length (ops.batch_windows checks them on the host); a
+ * row that breaks this is not read at all and comes out as zeros.  Pointers need 4-byte alignment only: the destination is
+ * written in 16-byte aligned float4 groups with a scalar head and tail per batch row, the source read at 4-byte boundaries. */
+int ptts_batch_windows(const float* src0, const float* src1, const float* src2, float* dst0, float* dst1, float* dst2,
+                       int D0, int D1, int D2, int nstreams, const long long* row_off /*[U+1]*/, int U, const int* utt /*[B]*/,
+                       const int* shift /*[B]*/, const int* n /*[B]*/, int B, int T, void* stream);
+
 /* wasserstein_loss (:70-71): out[0] = sign * mean(v) ; specweighted_lse_loss (:73-79): out[0] = mean((y-yhat)^2 * w[d]) */
 int ptts_mean_scaled(const float* v, long long n, float sign, float* out, void* stream);
 int ptts_wlse_fwd(const float* y, const float* yhat, const float* w /*[D] or NULL*/, float* out,

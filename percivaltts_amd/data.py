@@ -246,6 +246,121 @@ def load_inoutset(indir, outdir, outwdir, fid_lst, inouttimesync=True, length=No
     return X, Y, W
 
 
+class DeviceCorpusTooLarge(ValueError):
+    """The packed training set needs more device memory than DeviceCorpus was allowed (`needed` and `maxbytes`, in bytes)."""
+
+    def __init__(self, needed, maxbytes):
+        ValueError.__init__(self, 'the packed corpus needs {} bytes of device memory, {} are allowed'.format(needed, maxbytes))
+        self.needed, self.maxbytes = int(needed), int(maxbytes)
+
+
+class DeviceCorpus(object):
+    """A training set read, cropped and uploaded ONCE: what load_inoutset(inouttimesync=True) does for every batch, up to the
+    windowing.  The three files of every id are loaded, croplen cuts them to their common length and croplen_weight drops the
+    silences (`cropmode`) -- the functions above, one utterance at a time -- and the cropped utterances are packed row-wise into
+    X [N,ctx], Y [N,out], W [N,1] on `device` (upload), utterance u in the rows row_off[u] .. row_off[u+1]-1.  A batch is then
+    a window plan made on the host (plan: the very shifts batching would draw, from the same numpy generator) and ONE gather
+    launch (ops.batch_windows); no file is read and no frame crosses the host interface again.
+
+    lens: the kept lengths, raw_out_frames: the frames of each output file as read; both stay on the host.  `ids` of the
+    methods are file ids of fid_lst or indices into it.  maxbytes: the device memory the packed set may take, None for half of
+    what is free on `device` now; a larger set raises DeviceCorpusTooLarge before anything is uploaded.  device None: the current
+    HIP device, the host without one (plan, window_length and the packed rows work there; batch needs the device)."""
+
+    def __init__(self, indir, outdir, outwdir, fid_lst, cropmode='begend', device=None, maxbytes=None):
+        Xs, Ys, Ws, raw = [], [], [], []
+        for fid in fid_lst:
+            X, Y, W = load(indir, [fid]), load(outdir, [fid]), load(outwdir, [fid])
+            raw.append(int(Y[0].shape[0]))
+            X, Y, W = croplen([X, Y, W])
+            [X, Y], W = croplen_weight([X, Y], W, cropmode=cropmode)
+            Xs.append(X[0]); Ys.append(Y[0]); Ws.append(W[0])
+        self.cropmode, self.raw_out_frames = cropmode, raw
+        self._pack(Xs, Ys, Ws, fid_lst, device, maxbytes)
+
+    @classmethod
+    def from_utterances(cls, Xs, Ys, Ws, fid_lst=None, device=None, maxbytes=None):
+        """The corpus of utterances that are cropped already: three lists of [T_u, D] arrays, of equal T_u across the lists."""
+        self = cls.__new__(cls)
+        self.cropmode, self.raw_out_frames = None, [int(y.shape[0]) for y in Ys]
+        self._pack(list(Xs), list(Ys), list(Ws), fid_lst if fid_lst is not None else [str(u) for u in range(len(Xs))], device, maxbytes)
+        return self
+
+    def _pack(self, Xs, Ys, Ws, fid_lst, device, maxbytes):
+        import torch
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else 'cpu'
+        self.device = torch.device(device)
+        self.fid_lst = list(fid_lst)
+        self._index = dict((fid, u) for u, fid in enumerate(self.fid_lst))
+        if not (len(Xs) == len(Ys) == len(Ws) == len(self.fid_lst) >= 1) or any(not (x.shape[0] == y.shape[0] == w.shape[0]) for x, y, w in zip(Xs, Ys, Ws)):
+            raise ValueError('the size of the data sets are not identical')
+        self.lens = np.array([x.shape[0] for x in Xs], dtype=np.int64)
+        self.row_off = np.concatenate(([0], np.cumsum(self.lens))).astype(np.int64)
+        pack = lambda xs: np.ascontiguousarray(np.concatenate([x.reshape(x.shape[0], -1) for x in xs], axis=0), dtype=np.float32)
+        self.nbytes = 4 * int(self.row_off[-1]) * sum(int(np.prod(xs[0].shape[1:])) for xs in (Xs, Ys, Ws))
+        if maxbytes is None and self.device.type == 'cuda':
+            maxbytes = torch.cuda.mem_get_info(self.device)[0] // 2
+        if maxbytes is not None and self.nbytes > maxbytes:
+            raise DeviceCorpusTooLarge(self.nbytes, maxbytes)
+        self.maxbytes = maxbytes
+        streams = []
+        for xs in (Xs, Ys, Ws):            # one stream at a time: the host holds one packed copy beside the utterances
+            streams.append(upload(torch.from_numpy(pack(xs)), self.device))
+            del xs[:]
+        self.X, self.Y, self.W = streams
+        self._row_off_host = torch.from_numpy(self.row_off)
+        self._row_off_dev = upload(self._row_off_host, self.device)
+
+    def __len__(self):
+        return len(self.fid_lst)
+
+    def _utts(self, ids):
+        return np.array([self._index[i] if isinstance(i, str) else int(i) for i in ids], dtype=np.int64)
+
+    def window_length(self, ids, length=None, lengthmax=None, padtype='randshift'):
+        """The T of the batch `ids`: what batch_window_length finds for them, from the kept lengths (no file is touched)."""
+        if length is None:
+            lens = self.lens[self._utts(ids)]
+            length = lens.max() if padtype == 'padright' else lens.min()
+        if lengthmax is not None and length > lengthmax:
+            length = lengthmax
+        return int(length)
+
+    def plan(self, ids, length=None, lengthmax=None, padtype='randshift', rand=None):
+        """(T, utt, shift, n) of the batch `ids` (int32 arrays [B]), exactly as batching chooses them: 'randshift' draws one
+        np.random.randint(0, len - T + 1) per row, in row order -- the global numpy generator is left as load_inoutset leaves it
+        -- or takes floor(rand[b] * number of shifts); 'padright' draws nothing.  n[b] = min(len, T) real frames.  Host only."""
+        utt = self._utts(ids)
+        T = self.window_length(utt, length, lengthmax, padtype)
+        shift = np.zeros(len(utt), dtype=np.int32)
+        n = np.minimum(self.lens[utt], T).astype(np.int32)
+        if padtype == 'randshift':
+            for b, samplelen in enumerate(self.lens[utt]):
+                samplelen = int(samplelen)
+                if rand is None:
+                    shift[b] = np.random.randint(0, (samplelen - T) + 1)       # (raises for an utterance shorter than `length`, as in batching)
+                elif samplelen < T:
+                    raise ValueError('utterance {} has {} frames, fewer than the window of {}'.format(self.fid_lst[utt[b]], samplelen, T))
+                else:
+                    shift[b] = min(int(rand[b] * ((samplelen - T) + 1)), samplelen - T)
+        return T, utt.astype(np.int32), shift, n
+
+    def batch(self, ids, length=None, lengthmax=None, padtype='randshift', rand=None, rows=None, want_w=False):
+        """The batch load_inoutset(..., fid_lst=ids, length, lengthmax, maskpadtype=padtype, rand) gives, as device tensors
+        X [B,T,ctx], Y [B,T,out] (and W [B,T,1] with want_w): the plan, its three small tables uploaded asynchronously, one
+        gather launch on the current stream.  rows=(lo, hi): only these rows of the planned batch (a rank's shard; the plan, and
+        with it every random draw, is the whole batch's)."""
+        import torch
+        from . import ops
+        T, utt, shift, n = self.plan(ids, length, lengthmax, padtype, rand)
+        if rows is not None:
+            utt, shift, n = (a[rows[0]:rows[1]] for a in (utt, shift, n))
+        srcs = [self.X, self.Y] + ([self.W] if want_w else [])
+        return tuple(ops.batch_windows(srcs, self._row_off_host, torch.from_numpy(np.ascontiguousarray(utt)), torch.from_numpy(np.ascontiguousarray(shift)),
+                                       torch.from_numpy(np.ascontiguousarray(n)), T, row_off_dev=self._row_off_dev))
+
+
 # ---- evaluation helpers ----------------------------------------------------------------------------------
 def cost_0pred_rmse(Y_val):
     """RMSE of the all-zero prediction (the worst predictor)."""

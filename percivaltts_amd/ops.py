@@ -2282,6 +2282,70 @@ def rows_mean(v, lengths, sign=1.0):
     return out
 
 
+def _host_table(t, dtype, count, name):
+    if not (torch.is_tensor(t) and not t.is_cuda and t.dtype == dtype and t.dim() == 1 and t.is_contiguous()):
+        raise ValueError('batch_windows: {} has to be a contiguous {} host tensor [{}]'.format(name, str(dtype).split('.')[-1], count))
+    if t.numel() != count:
+        raise ValueError('batch_windows: {} has {} entries, not {}'.format(name, t.numel(), count))
+    return t
+
+
+def batch_windows(srcs, row_off, utt, shift, n, T, row_off_dev=None, out=None):
+    """One batch out of packed utterances in one launch (ptts_batch_windows).  srcs: one to three float32 device tensors
+    [N_total, D_k] that share row_off [U+1] (int64, host): utterance u is the rows row_off[u] .. row_off[u+1]-1 of each.  utt,
+    shift, n [B] (int32, host) describe the batch rows: row b is the n[b] frames of utterance utt[b] from frame shift[b] on, then
+    zeros up to T frames.  Returns [dst_k [B, T, D_k]], every element written by the kernel.  The tables are checked HERE, on the
+    host (the kernel trusts them): a bad table raises and nothing is launched.  They go up in one pinned, asynchronous copy on the
+    current stream; row_off_dev is row_off on the device (uploaded when None); out: the destinations to write instead of new ones."""
+    from .data import upload
+    srcs = list(srcs)
+    if not 1 <= len(srcs) <= 3:
+        raise ValueError('batch_windows: one to three streams, got {}'.format(len(srcs)))
+    row_off = _host_table(row_off, torch.int64, row_off.numel() if torch.is_tensor(row_off) else 0, 'row_off')
+    U, T = row_off.numel() - 1, int(T)
+    B = utt.numel() if torch.is_tensor(utt) else 0
+    utt, shift, n = (_host_table(t, torch.int32, B, k) for t, k in ((utt, 'utt'), (shift, 'shift'), (n, 'n')))
+    if U < 1 or B < 1 or T < 1:
+        raise ValueError('batch_windows: needs an utterance, a batch row and T >= 1 (U={}, B={}, T={})'.format(U, B, T))
+    lens = row_off[1:] - row_off[:-1]
+    if int(row_off[0]) != 0 or bool((lens < 0).any()):
+        raise ValueError('batch_windows: row_off has to start at 0 and never decrease')
+    for s in srcs:
+        if not (torch.is_tensor(s) and s.dtype == torch.float32 and s.dim() == 2 and s.is_contiguous()):
+            raise ValueError('batch_windows: every source has to be a contiguous float32 tensor [N_total, D]')
+        if s.shape[0] != int(row_off[-1]) or s.shape[1] < 1 or s.device != srcs[0].device:
+            raise ValueError('batch_windows: a source of shape {} on {} for {} packed rows on {}'.format(
+                tuple(s.shape), s.device, int(row_off[-1]), srcs[0].device))
+        if T * s.shape[1] >= 2 ** 31 - 8:
+            raise ValueError('batch_windows: a batch row of T*D = {} elements does not fit an int'.format(T * s.shape[1]))
+    if bool(((utt < 0) | (utt >= U)).any()):
+        raise ValueError('batch_windows: utt names an utterance outside 0..{}'.format(U - 1))
+    if bool((shift < 0).any()) or bool((n < 0).any()):
+        raise ValueError('batch_windows: negative shift or n')
+    if bool((n > T).any()):
+        raise ValueError('batch_windows: n > T = {}'.format(T))
+    if bool((shift.long() + n.long() > lens[utt.long()]).any()):
+        raise ValueError('batch_windows: a window (shift + n) ends behind its utterance')
+    dev = srcs[0].device
+    for s in srcs:
+        f32c(s, 'batch_windows.src')                      # (a host tensor: there is no CPU path)
+    if row_off_dev is None:
+        row_off_dev = upload(row_off, dev)
+    if not (row_off_dev.dtype == torch.int64 and row_off_dev.device == dev and row_off_dev.is_contiguous() and row_off_dev.numel() == U + 1):
+        raise ValueError('batch_windows: row_off_dev is not row_off on {}'.format(dev))
+    tables = upload(torch.stack((utt, shift, n)), dev)
+    if out is None:
+        dsts = [torch.empty((B, T, s.shape[1]), dtype=torch.float32, device=dev) for s in srcs]
+    else:
+        dsts = [f32c(d, 'batch_windows.out') for d in out]
+        if [(tuple(d.shape), d.device) for d in dsts] != [((B, T, s.shape[1]), dev) for s in srcs]:
+            raise ValueError('batch_windows: out has to be one [B, T, D] tensor per source, on {}'.format(dev))
+    pad = [None] * (3 - len(srcs))
+    call('ptts_batch_windows', *([ptr(s) for s in srcs] + pad + [ptr(d) for d in dsts] + pad + [s.shape[1] for s in srcs] + [0] * len(pad)
+                                 + [len(srcs), ptr(row_off_dev), U, ptr(tables[0]), ptr(tables[1]), ptr(tables[2]), B, T, stream()]))
+    return dsts
+
+
 def wlse_rows(y, yhat, w, lengths, want_ls=True, want_sq=True):
     """Per row of the ragged pair y, yhat [B,T,D]: (mean_{t<len,d} (y - yhat)^2 w[d] as float32 [B], sum_{t<len,d} (y - yhat)^2 as
     float64 [B]) in one pass (ptts_wlse_rows); an output not wanted is None.  w [D] or None."""

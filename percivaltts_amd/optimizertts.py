@@ -49,6 +49,25 @@ def _with_next(it):
     yield i, cur, None
 
 
+class _DeviceBatches(object):
+    """The batches of an epoch out of a data.DeviceCorpus, in batch order, with the face of data.BatchPrefetcher (iterator,
+    load_seconds, close).  A plain generator: `_with_next` asks for batch i+1 before it hands out batch i, so batch i+1 is gathered
+    (its shifts drawn) while batch i is still to be trained on, and the optimiser is told the very tensors it will get."""
+
+    def __init__(self, make_batch, n):
+        self._make, self._n, self.load_seconds = make_batch, int(n), 0.0
+
+    def __iter__(self):
+        for i in range(self._n):
+            t0 = time.time()
+            item = self._make(i)
+            self.load_seconds += time.time() - t0
+            yield item
+
+    def close(self):
+        pass
+
+
 class OptimizerTTS:
 
     _model = None    # the model whose parameters are optimised
@@ -70,6 +89,8 @@ class OptimizerTTS:
         cfg.train_batch_cropmode = 'begendbigger'
         cfg.train_batch_length = None
         cfg.train_batch_lengthmax = None
+        cfg.train_data_on_device = False               # build extension: True keeps the cropped training set on the device (data.DeviceCorpus) and cuts every batch out of it with one gather launch; False: load_inoutset reads the files of every batch, as the reference does
+        cfg.train_data_on_device_maxbytes = None       # ... the device memory that set may take (None: half of what is free); a larger set is trained from the host loader
         cfg.train_nbtrials = 1
         cfg.train_validation_batch_size = None         # build extension: n >= 1 computes the validation costs on ragged batches of up to n utterances of similar length (data.length_groups); None: one utterance at a time, as the reference does
         cfg.train_validation_sort_by_length = True     # ... grouped by length (False: consecutive groups in the order of the validation set)
@@ -146,7 +167,20 @@ class OptimizerTTS:
         print('    using {} batches of {} sentences each'.format(nbbatches, self.cfg.train_batch_size))
         print('    model #parameters={}'.format(self._model.count_params()))
 
-        nbtrainframes = sum(data.loadfile(outdir, fid).shape[0] for fid in fid_lst_tra)
+        # cfg.train_data_on_device: the training set is read, cropped and uploaded once (data.DeviceCorpus) and every batch is one
+        # gather launch; a set that does not fit the device memory allowed for it is trained from the host loader, as without the switch
+        corpus = None
+        if getattr(self.cfg, 'train_data_on_device', False):
+            try:
+                corpus = data.DeviceCorpus(indir, outdir, wdir, fid_lst_tra, cropmode=self.cfg.train_batch_cropmode, device=self._model.to_device(),
+                                           maxbytes=getattr(self.cfg, 'train_data_on_device_maxbytes', None))
+                print('    training set resident on the device: {} frames kept, {:.1f} MB'.format(int(corpus.row_off[-1]), corpus.nbytes / float(1024 ** 2)))
+            except data.DeviceCorpusTooLarge as e:
+                print_log('    WARNING: train_data_on_device: the packed training set needs {} bytes, {} bytes are allowed: batches come from the host loader'.format(e.needed, e.maxbytes))
+        if corpus is not None:
+            nbtrainframes = sum(corpus.raw_out_frames)      # (the output files as read, before any crop)
+        else:
+            nbtrainframes = sum(data.loadfile(outdir, fid).shape[0] for fid in fid_lst_tra)
         print('    Training set: {} sentences, #frames={} ({})'.format(
             len(fid_lst_tra), nbtrainframes, time.strftime('%H:%M:%S', time.gmtime(nbtrainframes * self._model.vocoder.shift))))
         print('    #parameters/#frames={:.2f}'.format(float(self._model.count_params()) / nbtrainframes))
@@ -220,8 +254,18 @@ class OptimizerTTS:
                     cropmode=self.cfg.train_batch_cropmode, rand=rnd)
                 return X_trab, Y_trab                        # already this rank's shard: only it was read and crosses PCIe
 
-            # batches are loaded, pinned and copied to the device two ahead of the step that consumes them
-            prefetch = data.BatchPrefetcher(make_batch, nbbatches, device=self.device, depth=2)
+            def gather_batch(batchid, rndidxb=rndidxb, shift_rand=shift_rand):
+                # the same windows out of the resident corpus: the plan of the GLOBAL batch (its T, its shifts -- drawn here, in batch
+                # order, or taken from shift_rand), this rank's rows of it
+                return corpus.batch(rndidxb[batchid], length=self.cfg.train_batch_length, lengthmax=self.cfg.train_batch_lengthmax,
+                                    padtype=self.cfg.train_batch_padtype, rand=shift_rand[batchid] if world > 1 else None,
+                                    rows=parallel.shard_batch(len(rndidxb[batchid]), world, rank) if world > 1 else None)
+
+            if corpus is not None:
+                prefetch = _DeviceBatches(gather_batch, nbbatches)
+            else:
+                # batches are loaded, pinned and copied to the device two ahead of the step that consumes them
+                prefetch = data.BatchPrefetcher(make_batch, nbbatches, device=self.device, depth=2)
             for batchid, (X_trab, Y_trab), nxt in _with_next(self._closing(prefetch)):
                 t0 = time.time()
                 self.hint_next_batch(*(nxt if nxt is not None else (None, None)))     # (the prefetcher has it on the device already)

@@ -225,6 +225,10 @@ def training(cont=False):
     # cfg.train_validation_batch_size = n (unset here: one utterance at a time, as the reference does): the validation costs of every
     # epoch on ragged batches of up to n utterances of similar length -- one generator forward per batch feeds the RMSE, the
     # generator's and the critic's cost (OptimizerTTSWGAN.validation_costs_batch); not with cfg.arch_critic_bf16
+    # cfg.train_data_on_device = True (unset here: load_inoutset reads the files of every batch, as the reference does): the training
+    # set is read, cropped and uploaded once (data.DeviceCorpus) and every batch is one gather launch at the windows the host loader
+    # would draw -- same numpy draws, same batches, same model; cfg.train_data_on_device_maxbytes bounds the device memory it may take
+    # (None: half of what is free), a larger set is trained from the host loader
     if errtype == 'LSE': opti = optimizertts.OptimizerTTS(cfg, mod)
     else:                opti = optimizertts_wgan.OptimizerTTSWGAN(cfg, mod, errtype=errtype, critic=networks_critic.Critic(vocoder, ctxsize, cfg))
     opti.train(cfg.inpath, cfg.outpath, cfg.wpath, fid_lst_tra, fid_lst_val, cfg.fparams_fullset, cont=cont)
