@@ -329,6 +329,81 @@ def _stream_counter(device):
     return c
 
 
+_caches = []        # of operands derived from a weight or a layer input: what clear_caches() calls, added by every _WeightCache and _Slot as created
+
+
+def _flat_epoch(w):
+    """(flat parameter buffer of a weight, its epoch); (None, None) for a tensor that is no parameter of an optimiser."""
+    flat = getattr(w, '_ptts_flat', None)
+    return flat, None if flat is None else flat.epoch
+
+
+class _Derived(object):
+    """An entry of a _WeightCache: `buf`, built from `owner` (a tensor, or a tuple of them) at its `_version` (their versions) and the `epoch` of its
+    flat buffer; out of date without a version.  One cache each: buf_t (_C2M: transposed table), Bm (_DenseSplit: the view split), sid (_C1Split), geo (_C1FFT)."""
+    __slots__ = ('owner', 'version', 'epoch', 'buf', 'buf_t', 'Bm', 'sid', 'geo')
+
+    def __init__(self, owner, buf, version=None, epoch=None, buf_t=None, sid=None, geo=None):
+        self.owner, self.buf, self.version, self.epoch, self.buf_t, self.Bm, self.sid, self.geo = owner, buf, version, epoch, buf_t, None, sid, geo
+
+    def current(self, owner, version, flat=None):
+        """The freshness rule: same object(s), same version(s), same epoch of the flat buffer (`flat`, if the caller has looked it up; of a
+        tuple of owners: the first one's) -- and never for a tensor without one."""
+        if flat is None:
+            flat = getattr(owner, '_ptts_flat', None)
+        return flat is not None and self.epoch == flat.epoch and self.version == version and \
+            (self.owner is owner or (type(self.owner) is tuple and all(a is b for a, b in zip(self.owner, owner))))
+
+    def stale_in(self, flat):
+        """Out of date, and its owner a weight of this flat buffer: to be rebuilt in the launch that rebuilds another entry of that buffer."""
+        return flat is not None and getattr(self.owner, '_ptts_flat', None) is flat and not self.current(self.owner, self.owner._version, flat)
+
+    def stale(self):
+        self.version = None         # out of date; the buffers stay, the next use rebuilds into them
+
+
+class _WeightCache(dict):
+    """key -> _Derived.  Its part of clear_caches(): every entry is dropped (`drop`), or every entry that `keep` does not accept is marked
+    out of date -- keys and buffers stay, the next use rebuilds them, grouped where the cache can."""
+    __slots__ = ('keep',)       # (no instance dictionary: a look-up is a hit path)
+    def __init__(self, drop=False, keep=None):
+        self.keep = keep
+        _caches.append(self.clear if drop else self.invalidate)
+
+    def invalidate(self):
+        for e in self.values():
+            if not (self.keep and self.keep(e)):
+                e.stale()
+
+
+class _Slot(object):
+    """One operand derived from a layer input, kept for the tensor it was made from (generator and critic read the same context input).  `src` is held: its
+    address cannot be reused while the entry lives.  Nothing is stored for src None: such a caller builds every time.  (_C1FFT.wgrad reads `key` and `value` directly.)"""
+    def __init__(self):
+        self.clear()
+        _caches.append(self.clear)
+
+    def get(self, src, key):
+        return self.value if self.src is src and self.key == key else None
+
+    def put(self, src, key, value):
+        if src is not None:
+            self.src, self.key, self.value = src, key, value
+        return value
+
+    def clear(self):
+        self.src = self.key = self.value = None
+
+
+def clear_caches():
+    """Forget every operand derived from a weight or an input (bf16 planes, transposed frames, Toeplitz tables, the reused
+    context-Conv1D product).  A hipGraph capture must start from empty caches: an entry made before the capture would be
+    taken instead of being recomputed INSIDE the graph, and every replay would then read the stale copy."""
+    for forget in _caches:
+        forget()
+    _C1Cache.key = _C1Cache.ap = _C1Cache.y = None
+
+
 # ----------------------------------------------------------------------------------------------
 # raw kernel wrappers (no autograd)
 # ----------------------------------------------------------------------------------------------
@@ -339,7 +414,7 @@ class _C2M(object):
     kernel (forward and transposed, 5.3 KB each) are rebuilt when the kernel changes (tensor version / flat-buffer epoch)."""
     default = os.environ.get('PTTS_CONV2D_MFMA', '1') == '1'
     enabled = default
-    tables = {}         # (id(w), stream) -> (w, version, epoch, fwd table, bwd table)
+    tables = _WeightCache()         # (id(w), stream, planes) -> _Derived(w, buf: forward table, buf_t: transposed table)
 
     @staticmethod
     def eligible(x, w, dil_t):
@@ -348,53 +423,42 @@ class _C2M(object):
 
     @classmethod
     def table(cls, w, transposed, planes=3):
-        flat = getattr(w, '_ptts_flat', None)
-        epoch = None if flat is None else flat.epoch
-        sid = _hip.stream_id()
+        flat, sid = getattr(w, '_ptts_flat', None), _hip.stream_id()
         key = (id(w), sid, planes)         # one copy per stream: the build is ordered with its consumers by the stream itself
         ent = cls.tables.get(key)
-        if ent is None or ent[0] is not w or ent[1] != w._version or ent[2] != epoch or flat is None:
+        # not ent.current(w, w._version, flat), written out (the owner is in the key): this test and _DenseSplit.get's run for every product of a step
+        if ent is None or flat is None or ent.version != w._version or ent.epoch != flat.epoch:
+            epoch = _flat_epoch(w)[1]
             nb = _hip.lib().ptts_conv2d_mfma_table_bytes(5)
-            reuse = ent is not None and ent[0] is w
-            tf = ent[3] if reuse else torch.empty(nb, dtype=torch.uint8, device=w.device)
-            tb = ent[4] if reuse else torch.empty(nb, dtype=torch.uint8, device=w.device)
+            ent = ent or _Derived(w, torch.empty(nb, dtype=torch.uint8, device=w.device), buf_t=torch.empty(nb, dtype=torch.uint8, device=w.device))
             if len(cls.tables) > 512:
-                cls.tables = {}
-            cls.tables[key] = ent = (w, w._version, epoch, tf, tb)
+                cls.tables.clear()
+            cls.tables[key] = ent
             # with it the other kernels of the same flat buffer whose tables on this stream are out of date (the 7 layers of a stack
             # after an update): one launch
-            todo = [ent]
-            if flat is not None:
-                for k2, e2 in cls.tables.items():
-                    if k2 is not key and k2[1] == sid and k2[2] == planes and getattr(e2[0], '_ptts_flat', None) is flat and \
-                            (e2[1] != e2[0]._version or e2[2] != epoch):
-                        cls.tables[k2] = e2 = (e2[0], e2[0]._version, epoch, e2[3], e2[4])
-                        todo.append(e2)
+            todo = [ent] + [e for k, e in cls.tables.items() if e is not ent and k[1] == sid and k[2] == planes and e.stale_in(flat)]
+            for e in todo:
+                e.version, e.epoch = e.owner._version, epoch
             if len(todo) == 1:
-                call('ptts_conv2d_mfma_tables', ptr(w), ptr(tf), ptr(tb), 5, 5, 4, 4, planes, stream(), tag=(5, 5, planes))
+                call('ptts_conv2d_mfma_tables', ptr(w), ptr(ent.buf), ptr(ent.buf_t), 5, 5, 4, 4, planes, stream(), tag=(5, 5, planes))
             else:
                 n = len(todo)
-                pw = (ctypes.c_void_p * n)(*[e[0].data_ptr() for e in todo])
-                pf = (ctypes.c_void_p * n)(*[e[3].data_ptr() for e in todo])
-                pb = (ctypes.c_void_p * n)(*[e[4].data_ptr() for e in todo])
+                pw = (ctypes.c_void_p * n)(*[e.owner.data_ptr() for e in todo])
+                pf = (ctypes.c_void_p * n)(*[e.buf.data_ptr() for e in todo])
+                pb = (ctypes.c_void_p * n)(*[e.buf_t.data_ptr() for e in todo])
                 call('ptts_conv2d_mfma_tables_grouped', ctypes.cast(pw, ctypes.c_void_p), ctypes.cast(pf, ctypes.c_void_p),
                      ctypes.cast(pb, ctypes.c_void_p), n, planes, stream(), tag=(n, planes))
-        return ent[4] if transposed else ent[3]
+        return ent.buf_t if transposed else ent.buf
 
     @staticmethod
     def pad_t(dil_t, pad_mode):
         return 4 * dil_t if pad_mode == PAD_CAUSAL else 2 * dil_t
 
-    @classmethod
-    def clear(cls):
-        """Mark every table out of date (keys and buffers stay: the next use rebuilds them, grouped)."""
-        cls.tables = {k: (e[0], None, -1, e[3], e[4]) for k, e in cls.tables.items()}
-
 
 def conv2d_mfma(on):
     """Switch the matrix-core Conv2D kernels on or off (None: the default)."""
     _C2M.enabled = _C2M.default if on is None else bool(on)
-    _C2M.clear()
+    _C2M.tables.invalidate()
 
 
 class _C2W(object):
@@ -726,46 +790,39 @@ class _DenseSplit(object):
     PTTS_DENSE_SPLIT=0 or dense_split(False) select the fp32-MFMA kernels of csrc/gemm.hip."""
     default = os.environ.get('PTTS_DENSE_SPLIT', '1') == '1'
     enabled = default
-    planes = {}      # (id(owner), data_ptr, K, N, ldb, transB, stream) -> (owner, version, epoch, planes)
+    planes = _WeightCache()      # (id(owner), data_ptr, K, N, ldb, transB, stream) -> _Derived(owner, planes, Bm); clear_caches() marks them out of date
     wgrad_min_n = int(os.environ.get('PTTS_DENSE_WGRAD_MIN_N', '16'))      # narrowest weight gradient the split kernel takes
 
     @classmethod
     def get(cls, Bm, K, N, ldb, transB):
         """Planes of B[K][N] (transB: stored [N][K]) if Bm is (a view of) a weight of a flat parameter buffer, else None."""
-        owner = Bm if hasattr(Bm, '_ptts_flat') else getattr(Bm, '_base', None)
-        flat = getattr(owner, '_ptts_flat', None)
+        owner, flat = Bm, getattr(Bm, '_ptts_flat', None)
+        if flat is None:        # (not a weight itself: a view of one?)
+            owner = getattr(Bm, '_base', None); flat = getattr(owner, '_ptts_flat', None)
         if flat is None:
             return None
         sid = _hip.stream_id()
         key = (id(owner), Bm.data_ptr(), K, N, ldb, transB, sid)
         ent = cls.planes.get(key)
-        if ent is None or ent[0] is not owner or ent[1] != owner._version or ent[2] != flat.epoch:
-            reuse = ent is not None and ent[0] is owner
-            buf = ent[3] if reuse else torch.empty(_hip.lib().ptts_dense_planes_bytes(N, K), dtype=torch.uint8, device=Bm.device)
+        if ent is None or ent.version != owner._version or ent.epoch != flat.epoch:       # (not ent.current(...), written out: see _C2M.table)
+            ent = ent or _Derived(owner, torch.empty(_hip.lib().ptts_dense_planes_bytes(N, K), dtype=torch.uint8, device=Bm.device))
+            ent.Bm = Bm
             if len(cls.planes) > 512:
-                cls.planes = {}
-            cls.planes[key] = ent = (owner, owner._version, flat.epoch, buf, Bm)
+                cls.planes.clear()
+            cls.planes[key] = ent
             # ... and with it every other weight of the same flat buffer whose planes on this stream are out of date: after an update
             # all of a network's Dense kernels need theirs again, one grouped launch instead of one launch per kernel and direction
-            todo = [(key, ent)]
-            for k2, e2 in cls.planes.items():
-                if k2 is not key and k2[6] == sid and len(e2) == 5 and getattr(e2[0], '_ptts_flat', None) is flat and \
-                        (e2[1] != e2[0]._version or e2[2] != flat.epoch) and e2[4].data_ptr() == k2[1]:
-                    todo.append((k2, e2))
+            todo = [(key, ent)] + [(k, e) for k, e in cls.planes.items() if e is not ent and k[6] == sid and e.stale_in(flat) and e.Bm.data_ptr() == k[1]]
+            for _, e2 in todo:
+                e2.version, e2.epoch = e2.owner._version, flat.epoch
             if len(todo) == 1:
-                call('ptts_split3_dense_weight', ptr(Bm), ldb, K, N, transB, ptr(buf), stream(), tag=(K, N, transB))
+                call('ptts_split3_dense_weight', ptr(Bm), ldb, K, N, transB, ptr(ent.buf), stream(), tag=(K, N, transB))
             else:
                 descs = (_hip.DenseSplitDesc * len(todo))()
                 for d, (k2, e2) in zip(descs, todo):
-                    d.w, d.planes, d.ldw, d.K, d.N, d.transposed = k2[1], e2[3].data_ptr(), k2[4], k2[2], k2[3], k2[5]
-                    cls.planes[k2] = (e2[0], e2[0]._version, flat.epoch, e2[3], e2[4])
+                    d.w, d.planes, d.ldw, d.K, d.N, d.transposed = k2[1], e2.buf.data_ptr(), k2[4], k2[2], k2[3], k2[5]
                 call('ptts_split3_dense_weight_grouped', ctypes.cast(descs, ctypes.c_void_p), len(todo), stream(), tag=(len(todo),))
-        return ent[3]
-
-    @classmethod
-    def clear(cls):
-        """Mark every plane set out of date (keys and buffers stay: the next use rebuilds them, grouped)."""
-        cls.planes = {k: (e[0], None, None, e[3], e[4]) for k, e in cls.planes.items() if len(e) == 5}
+        return ent.buf
 
     @classmethod
     def eligible(cls, A, C, M, N, K, lda, ldc, in_side):
@@ -1085,7 +1142,7 @@ def conv2d_pair(v0, v1, w, b=None, dil_t=1, pad_mode=PAD_SAME, bf16=None):
 # the stored maps are POST-activation (they serve as operands and as LeakyReLU masks: slope > 0 keeps the sign).
 # ----------------------------------------------------------------------------------------------
 class _C2C(object):
-    tables = {}         # (ids of the kernels, stream) -> (kernels, biases, versions, epoch, table buffer)
+    tables = _WeightCache(drop=True)         # (ids of the kernels, stream) -> _Derived(kernels, table buffer), version: those of kernels and biases
 
     @staticmethod
     def supported(F, ws):
@@ -1098,28 +1155,22 @@ class _C2C(object):
 
     @classmethod
     def table(cls, ws, bs):
-        flat = getattr(ws[0], '_ptts_flat', None)
-        epoch = None if flat is None else flat.epoch
-        sid = _hip.stream_id()
-        key = (tuple(id(w) for w in ws), sid)
+        flat, epoch = _flat_epoch(ws[0])
+        key = (tuple(id(w) for w in ws), _hip.stream_id())
         vers = tuple(w._version for w in ws) + tuple(-1 if b is None else b._version for b in bs)
         ent = cls.tables.get(key)
-        if ent is None or any(a is not b for a, b in zip(ent[0], ws)) or ent[2] != vers or ent[3] != epoch or flat is None:
-            tab = ent[4] if ent is not None else torch.empty(_hip.lib().ptts_conv2d_chain_tables_bytes(), dtype=torch.uint8, device=ws[0].device)
+        if ent is None or not ent.current(ws, vers, flat):
+            tab = ent.buf if ent is not None else torch.empty(_hip.lib().ptts_conv2d_chain_tables_bytes(), dtype=torch.uint8, device=ws[0].device)
             for w in ws:
                 f32c(w, 'conv2d_chain.w')
             wp = (ctypes.c_void_p * len(ws))(*[w.data_ptr() for w in ws])
             bp = (ctypes.c_void_p * len(ws))(*[None if b is None else f32c(b, 'conv2d_chain.b').data_ptr() for b in bs])
             call('ptts_conv2d_chain_tables', wp, bp, ptr(tab), len(ws), int(ws[0].shape[2]), stream(), tag=(len(ws),))
-            ent = (tuple(ws), tuple(bs), vers, epoch, tab)
+            ent = _Derived(tuple(ws), tab, version=vers, epoch=epoch)
             if len(cls.tables) > 64:
-                cls.tables = {}
+                cls.tables.clear()
             cls.tables[key] = ent
-        return ent[4]
-
-    @classmethod
-    def clear(cls):
-        cls.tables = {}
+        return ent.buf
 
 
 def _chain_x0(x0):
@@ -1487,10 +1538,9 @@ class _C1Split(object):
     context input, in the critic step and again in the generator step); the planes of a kernel until it is updated."""
     default = os.environ.get('PTTS_CONV1D_SPLIT', '1') == '1'
     enabled = default
-    x_src = None        # the tensor (kept alive: its address cannot be reused) ...
-    x_key = None        # ... its version / shape / padding
-    x_planes = None
-    w_planes = {}       # id(w) -> (w, version, flat epoch, planes)
+    x = _Slot()         # planes of the frames, by (version, shape, padding, stream)
+    xt = _Slot()        # their frame-major planes (the weight gradient), by (version, shape, KW, stream)
+    w_planes = _WeightCache(drop=True)       # id(w) -> _Derived(w, planes, sid)
 
     @staticmethod
     def eligible(a, w):
@@ -1503,34 +1553,28 @@ class _C1Split(object):
         B, T, Cin = a.shape
         Cp = (Cin + 31) // 32 * 32
         key = (a._version, tuple(a.shape), pl, pr, _hip.stream_id())
-        if cls.x_src is a and cls.x_key == key:
-            return cls.x_planes, Cp
-        planes = torch.empty((3, Cp // 32, B, T + pl + pr, 32), dtype=torch.bfloat16, device=a.device)
-        call('ptts_split3_frames', ptr(a), ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), B, T, Cin, pl, pr, Cp, stream(),
-             tag=(B, T, Cin))
-        cls.x_src, cls.x_key, cls.x_planes = a, key, planes
+        planes = cls.x.get(a, key)
+        if planes is None:
+            planes = cls.x.put(a, key, torch.empty((3, Cp // 32, B, T + pl + pr, 32), dtype=torch.bfloat16, device=a.device))
+            call('ptts_split3_frames', ptr(a), ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), B, T, Cin, pl, pr, Cp, stream(),
+                 tag=(B, T, Cin))
         return planes, Cp
 
     @classmethod
     def kernel(cls, w):
         KW, Cin, N = w.shape
         Cp = (Cin + 31) // 32 * 32
-        flat = getattr(w, '_ptts_flat', None)
-        epoch = None if flat is None else flat.epoch
         ent = cls.w_planes.get(id(w))
         sid = _hip.stream_id()
-        if ent is not None and ent[0] is w and ent[1] == w._version and ent[2] == epoch and ent[4] == sid and flat is not None:
-            return ent[3]
-        planes = ent[3] if ent is not None and ent[0] is w and ent[4] == sid else torch.empty((3, Cp // 32, N, KW, 32), dtype=torch.bfloat16, device=w.device)
+        if ent is not None and ent.sid == sid and ent.current(w, w._version):
+            return ent.buf
+        planes = ent.buf if ent is not None and ent.sid == sid else torch.empty((3, Cp // 32, N, KW, 32), dtype=torch.bfloat16, device=w.device)
         call('ptts_split3_weight_t', ptr(w), ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), KW, Cin, N, Cp, stream(),
              tag=(KW, Cin, N))
-        cls.w_planes[id(w)] = (w, w._version, epoch, planes, sid)
+        cls.w_planes[id(w)] = _Derived(w, planes, version=w._version, epoch=_flat_epoch(w)[1], sid=sid)
         return planes
 
     WGRAD_KW = (3, 5, 21)        # instantiations of wgrad_bf16x6_kernel<KW>
-    xt_src = None
-    xt_key = None
-    xt_planes = None
 
     @staticmethod
     def eligible_wgrad(KW, N):
@@ -1558,22 +1602,11 @@ class _C1Split(object):
         Tp = T + KW - 1
         Pp = cls.plane_len(B, T, KW)
         key = None if src is None else (src._version, tuple(src.shape), KW, _hip.stream_id())
-        if src is not None and cls.xt_src is src and cls.xt_key == key:
-            return cls.xt_planes
-        if padded:
-            planes, Crows = cls.transposed(saved, B, Tp, C, 0, Tp, Pp)
-        else:
-            planes, Crows = cls.transposed(saved, B, T, C, (KW - 1) // 2, Tp, Pp)
-        out = (planes, Crows, Pp)
-        if src is not None:
-            cls.xt_src, cls.xt_key, cls.xt_planes = src, key, out
+        out = cls.xt.get(src, key)
+        if out is None:
+            planes, Crows = cls.transposed(saved, B, Tp, C, 0, Tp, Pp) if padded else cls.transposed(saved, B, T, C, (KW - 1) // 2, Tp, Pp)
+            out = cls.xt.put(src, key, (planes, Crows, Pp))
         return out
-
-    @classmethod
-    def clear(cls):
-        cls.x_src = cls.x_key = cls.x_planes = None
-        cls.xt_src = cls.xt_key = cls.xt_planes = None
-        cls.w_planes = {}
 
 
 class _C1WgradT(object):
@@ -1582,9 +1615,8 @@ class _C1WgradT(object):
     PTTS_WGRAD_T=0 switches back to the stream-K product of gemm.hip.  The transposed frames are kept for the tensor the
     layer was called with (generator and critic convolve the same context input)."""
     enabled = os.environ.get('PTTS_WGRAD_T', '1') == '1'
-    src = None
-    key = None
-    planes = None
+    xt = _Slot()        # by (version, shape, KW, stream)
+    clear = xt.clear
 
     @classmethod
     def frames_t(cls, src, ap, KW):
@@ -1592,31 +1624,12 @@ class _C1WgradT(object):
         Pp = _C1Split.plane_len(B, Tp - (KW - 1), KW)
         Crows = (C + 63) // 64 * 64
         key = None if src is None else (src._version, tuple(src.shape), KW, _hip.stream_id())
-        if src is not None and cls.src is src and cls.key == key:
-            return cls.planes
-        xt = torch.empty((Crows, Pp), dtype=torch.float32, device=ap.device)
-        call('ptts_transpose_frames', ptr(ap), ptr(xt), B, Tp, C, 0, Tp, Crows, Pp, stream(), tag=(B, Tp, C))
-        out = (xt, Crows, Pp)
-        if src is not None:
-            cls.src, cls.key, cls.planes = src, key, out
+        out = cls.xt.get(src, key)
+        if out is None:
+            xt = torch.empty((Crows, Pp), dtype=torch.float32, device=ap.device)
+            call('ptts_transpose_frames', ptr(ap), ptr(xt), B, Tp, C, 0, Tp, Crows, Pp, stream(), tag=(B, Tp, C))
+            out = cls.xt.put(src, key, (xt, Crows, Pp))
         return out
-
-    @classmethod
-    def clear(cls):
-        cls.src = cls.key = cls.planes = None
-
-
-def clear_caches():
-    """Forget every operand derived from a weight or an input (bf16 planes, transposed frames, Toeplitz tables, the reused
-    context-Conv1D product).  A hipGraph capture must start from empty caches: an entry made before the capture would be
-    taken instead of being recomputed INSIDE the graph, and every replay would then read the stale copy."""
-    _C1Split.clear()
-    _C1FFT.clear()
-    _C1WgradT.clear()
-    _C2M.clear()
-    _C2C.clear()
-    _DenseSplit.clear()
-    _C1Cache.key = _C1Cache.ap = _C1Cache.y = None
 
 
 class _C1FFT(object):
@@ -1660,9 +1673,10 @@ class _C1FFT(object):
     bf16_one_product = os.environ.get('PTTS_CONV1D_FFT_BF16', '1') == '1'
     seg_target = int(os.environ.get('PTTS_CONV1D_FFT_SEG', '100'))      # preferred segment length (0: one segment per utterance)
     consts = {}         # (T, KW, device, stream) -> dict of the geometry and the twiddle operands
-    x_src = None; x_key = None; x_hat = None
-    xw_src = None; xw_key = None; xw_planes = None
-    w_hat = {}          # (id(w), stream) -> (w, version, epoch, None, planes, geometry)
+    x = _Slot()         # the input's transform, by (version, shape, KW, stream)
+    xw = _Slot()        # planes of that transform (the older weight-gradient stage list), by the key of x they were split from
+    # (id(w), stream) -> _Derived(w, planes, geo); `keep`: the kernels of frozen networks (see `frozen` below), spared by clear_caches() and eviction
+    w_hat = _WeightCache(keep=lambda e: id(getattr(e.owner, '_ptts_flat', None)) in _C1FFT.frozen)
     bufs = {}           # persistent buffers by (name, key, stream)
 
     @staticmethod
@@ -1760,8 +1774,9 @@ class _C1FFT(object):
         """[Xr | -Xi ; Xi | Xr] per frequency: Ap [NB][2][B NS][2 Kh] fp32, kept for the tensor it was made from."""
         B, T, Cin = a.shape
         key = (a._version, tuple(a.shape), KW, _hip.stream_id())
-        if cls.x_src is a and cls.x_key == key:
-            return cls.x_hat
+        Ap = cls.x.get(a, key)
+        if Ap is not None:
+            return Ap
         c = cls.const(T, KW, Cin, a.device)
         NB, Kh, NS, S, P = c['NB'], c['Kh'], c['NS'], c['S'], c['P']
         Z = B * NS
@@ -1771,42 +1786,34 @@ class _C1FFT(object):
             d = _hip.DenseRowsDesc(B=a.data_ptr(), strideB=0, ldb=Cin, windows=1, nB=B, T=T, NS=NS, S=S, row_off=-c['pl'], kvalid=P, mirror_cols=Kh)
             call('ptts_dense_bf16x6_batched', ptr(c['D']), 0, ctypes.byref(d), 0, None, ptr(Ap), 2 * Kh, Z, c['R'], Cin, P, P, Z * 2 * Kh,
                  3 | _hip.PLANES_ROWS, stream(), tag=('dft', Z, c['R'], Cin, P))
-            cls.x_src, cls.x_key, cls.x_hat = a, key, Ap
-            return Ap
+            return cls.x.put(a, key, Ap)
         npb = lib.ptts_dense_planes_bytes(Cin, P)
         xpl = cls._scratch('xpl', Z * npb, a.device)
         call('ptts_split3_frame_windows', ptr(a), B, T, Cin, NS, S, -c['pl'], P, P, ptr(xpl), npb, stream(), tag=('x', Z))
         call('ptts_dense_bf16x6_batched', ptr(c['D']), 0, ptr(xpl), npb, None, ptr(Ap), 2 * Kh, Z, c['R'], Cin, P, P, Z * 2 * Kh, 3, stream(),
              tag=('dft', Z, c['R'], Cin, P))
         call('ptts_dft_mirror', ptr(Ap), NB, Z, Cin, Kh, stream())
-        cls.x_src, cls.x_key, cls.x_hat = a, key, Ap
-        return Ap
+        return cls.x.put(a, key, Ap)
 
     @classmethod
     def kernel(cls, w, T):
         """Planes of [Hr ; Hi]_f [2 Kh x N] for all frequencies, rebuilt when the kernel changes."""
         KW, Cin, N = w.shape
-        flat = getattr(w, '_ptts_flat', None)
-        epoch = None if flat is None else flat.epoch
-        sid = _hip.stream_id()
+        key = (id(w), _hip.stream_id())
         c = cls.const(T, KW, Cin, w.device)
         NB, Kh = c['NB'], c['Kh']
         geo = (c['S'], NB, Kh)
-        ent = cls.w_hat.get((id(w), sid))
-        if ent is not None and ent[0] is w and ent[1] == w._version and ent[2] == epoch and flat is not None and ent[5] == geo:
-            if cls.frozen_log is not None and id(flat) in cls.frozen:
-                cls.frozen_log.append((w, ent[4], T))        # (a capture reads this buffer: its owner keeps it current, refresh_planes)
-            return ent[4]
-        lib = _hip.lib()
-        npb = lib.ptts_dense_planes_bytes(N, 2 * Kh)
-        if ent is not None and ent[0] is w and ent[5] == geo:
-            planes = ent[4]
-        else:
-            planes = torch.empty(NB * npb, dtype=torch.uint8, device=w.device)
+        ent = cls.w_hat.get(key)
+        if ent is not None and ent.geo == geo and ent.current(w, w._version):
+            if cls.frozen_log is not None and cls.w_hat.keep(ent):
+                cls.frozen_log.append((w, ent.buf, T))        # (a capture reads this buffer: its owner keeps it current, refresh_planes)
+            return ent.buf
+        planes = ent.buf if ent is not None and ent.geo == geo else torch.empty(NB * _hip.lib().ptts_dense_planes_bytes(N, 2 * Kh), dtype=torch.uint8, device=w.device)
         cls._build_kernel_planes(w, c, planes)
-        if len(cls.w_hat) >= 8 and (id(w), sid) not in cls.w_hat:
-            cls.w_hat = {k: e for k, e in cls.w_hat.items() if id(getattr(e[0], '_ptts_flat', None)) in cls.frozen}      # kernels of optimisers long gone would otherwise keep their plane sets alive
-        cls.w_hat[(id(w), sid)] = (w, w._version, epoch, None, planes, geo, T)
+        if len(cls.w_hat) >= 8 and key not in cls.w_hat:
+            for k in [k for k, e in cls.w_hat.items() if not cls.w_hat.keep(e)]:      # kernels of optimisers long gone would otherwise keep their plane sets alive
+                del cls.w_hat[k]
+        cls.w_hat[key] = _Derived(w, planes, version=w._version, epoch=_flat_epoch(w)[1], geo=geo)
         return planes
 
     @classmethod
@@ -1867,7 +1874,7 @@ class _C1FFT(object):
 
     @classmethod
     def has_x(cls, a, KW):
-        return a is not None and cls.x_src is a and cls.x_key == (a._version, tuple(a.shape), KW, _hip.stream_id())
+        return a is not None and cls.x.get(a, (a._version, tuple(a.shape), KW, _hip.stream_id())) is not None
 
     @classmethod
     def wgrad(cls, a, dy, KW):
@@ -1879,7 +1886,7 @@ class _C1FFT(object):
         Z = B * NS
         lib = _hip.lib()
         dev = a.device
-        Ap = cls.x_hat
+        Ap = cls.x.value
         # DY' = DFT of the segments' gradient frames (S frames, zero-padded to P): [NB][2][Z][N]
         npd = lib.ptts_dense_planes_bytes(N, P)
         dpl = cls._scratch('dpl', Z * npd, dev)
@@ -1896,13 +1903,13 @@ class _C1FFT(object):
         else:
             # planes of [Xr | -Xi ; Xi | Xr]_f as the right operand [K = 2Z][N' = 2 Kh]: once per input
             npx = lib.ptts_dense_planes_bytes(2 * Kh, 2 * Z)
-            if cls.xw_src is not a or cls.xw_key != cls.x_key or cls.xw_planes is None:
-                xw = cls._scratch('xw', NB * npx, dev)
+            xw = cls.xw.get(a, cls.x.key)
+            if xw is None:
+                xw = cls.xw.put(a, cls.x.key, cls._scratch('xw', NB * npx, dev))
                 call('ptts_split3_dense_weight_strided', ptr(Ap), 2 * Z * 2 * Kh, ptr(xw), npx, NB, 2 * Kh, 2 * Z, 2 * Kh, 0, stream(), tag=('xw', NB))
-                cls.xw_src, cls.xw_key, cls.xw_planes = a, cls.x_key, xw
             DYt = cls._scratch('DYt', NB * N * 2 * Z * 4, dev)                                         # [NB][N][2Z] fp32
             call('ptts_transpose_batched', ptr(DYh), ptr(DYt), NB, 2 * Z, N, stream())
-            call('ptts_dense_bf16x6_batched', ptr(DYt), N * 2 * Z, ptr(cls.xw_planes), npx, None, ptr(Gt), N * 2 * Kh, NB, N, 2 * Kh, 2 * Z,
+            call('ptts_dense_bf16x6_batched', ptr(DYt), N * 2 * Z, ptr(xw), npx, None, ptr(Gt), N * 2 * Kh, NB, N, 2 * Kh, 2 * Z,
                  2 * Z, 2 * Kh, 1 if _Flags.bf16_products else 3, stream(), tag=('corr', NB, N, 2 * Kh, 2 * Z))
         dw = torch.empty((KW, Cin, N), dtype=torch.float32, device=dev)
         if KW in cls.KWS:
@@ -1915,32 +1922,24 @@ class _C1FFT(object):
             call('ptts_conv1d_freq_wgrad_combine', ptr(out2), ptr(dw), KW, Cin, N, Kh, stream())
         return dw
 
-    @classmethod
-    def clear(cls):
-        cls.x_src = cls.x_key = cls.x_hat = None
-        cls.xw_src = cls.xw_key = cls.xw_planes = None
-        # (the planes of frozen networks' kernels stay valid: the owner of a graph that reads them keeps them current, refresh_planes)
-        cls.w_hat = {k: (e if id(getattr(e[0], '_ptts_flat', None)) in cls.frozen else (e[0], None, None, e[3], e[4], e[5]) + tuple(e[6:]))
-                     for k, e in cls.w_hat.items()}
-
 
 def conv1d_fft(on):
     """Context Conv1D forward in the frequency domain (see _C1FFT): True / False, None = the default (PTTS_CONV1D_FFT)."""
     _C1FFT.enabled = _C1FFT.default if on is None else bool(on)
-    _C1FFT.clear()
+    _C1FFT.x.clear(); _C1FFT.xw.clear(); _C1FFT.w_hat.invalidate()
 
 
 def conv1d_fft_rows(on):
     """The frequency-domain Conv1D's transforms on fp32 rows instead of pre-split planes (see _C1FFT.rows_sites): True / False, a mask of
     call sites (1: 'dft', 2: 'idft'), None = the default (PTTS_CONV1D_FFT_ROWS)."""
     _C1FFT.rows_sites = _C1FFT.rows_default if on is None else (3 if on is True else int(on))
-    _C1FFT.clear()
+    _C1FFT.x.clear(); _C1FFT.xw.clear(); _C1FFT.w_hat.invalidate()
 
 
 def conv1d_split(on):
     """Switch the bf16x6 split product of the context Conv1D forward on or off (see _C1Split); None: the default."""
     _C1Split.enabled = _C1Split.default if on is None else bool(on)
-    _C1Split.clear()
+    _C1Split.x.clear(); _C1Split.xt.clear(); _C1Split.w_planes.clear()
 
 
 class Conv1dFn(torch.autograd.Function):
