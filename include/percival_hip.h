@@ -546,6 +546,24 @@ int ptts_affine_act_rows(const float* x, const float* scale, const float* shift,
  * NULL for NONE).  The same indexing; a float4 path where C % 4 == 0 and the pointers are 16-byte aligned.  dx == dy is allowed. */
 int ptts_affine_act_rows_bwd(const float* dy, const float* x, const float* scale, const float* shift, float* dx,
                              const int* lens, int B, int T, int inner, int C, int act, float alpha, void* stream);
+/* Masked training: BatchNormalization over a zero-padded batch [B,T,inner] with a length per row (lens: device int [B],
+ * 1 <= lens[b] <= T; c = i % C, inner a multiple of C).  Pad frames are never read; all sums are fp64, two-stage, in a fixed
+ * order (bit-reproducible), with the float4 path of their dense siblings where C % 4 == 0 and the pointers are 16-byte aligned.
+ * workspace for the two reductions: ptts_colstats_rows_workspace_bytes (0 for dimensions the calls refuse).
+ *   ptts_colstats_rows: sums[0:C] = sum x, sums[C:2C] = sum x^2 over the real frames (ptts_colstats in identity input mode,
+ *     masked); finished by ptts_bn_finalize with count = N * inner / C, N = sum_b lens[b], which the host knows.
+ *   ptts_affine_act_rows_bwd_params: dx as ptts_affine_act_rows_bwd, and dsums [2C] = (dscale, dshift) over the real frames in
+ *     the same pass (ptts_affine_act_bwd, masked); act PTTS_ACT_NONE or PTTS_ACT_LRELU; dx == dy is allowed.
+ *   ptts_axpby_cols_rows: out[b,t,i] = t < lens[b] ? a + x*c2[c] + c0[c] : +0, the statistics' share of the BatchNorm
+ *     backward (c0, c2 of ptts_bn_bwd_coefs with the masked count); out == a is allowed. */
+size_t ptts_colstats_rows_workspace_bytes(int B, int T, int inner, int C);
+int ptts_colstats_rows(const float* x, const int* lens, int B, int T, int inner, int C, double* sums /*[2C]*/,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int ptts_affine_act_rows_bwd_params(const float* dy, const float* x, const float* scale, const float* shift, float* dx,
+                                    double* dsums /*[2C]: dscale, dshift*/, const int* lens, void* workspace,
+                                    size_t workspace_bytes, int B, int T, int inner, int C, int act, float alpha, void* stream);
+int ptts_axpby_cols_rows(const float* a, const float* x, const float* c2, const float* c0, float* out, const int* lens,
+                         int B, int T, int inner, int C, void* stream);
 /* dx = dy * act'(.) * scale ; dscale/dshift reductions (NULL to skip).  `y` is the forward output (sigmoid/tanh use it). */
 int ptts_affine_act_bwd(const float* dy, const float* x, const float* y, const float* scale, const float* shift,
                         float* dx, double* dsums /*[2C]: dscale, dshift; or NULL*/,
@@ -582,6 +600,18 @@ int ptts_rows_mean(const float* v, const int* lens, int B, int T, int inner, flo
  * out_sq[b] = sum_{t<lens[b],d} (y-yhat)^2 in one pass; either output may be NULL */
 int ptts_wlse_rows(const float* y, const float* yhat, const float* w /*[D] or NULL*/, const int* lens, int B, int T, int D,
                    float* out_ls /*[B] or NULL*/, double* out_sq /*[B] or NULL*/, void* stream);
+/* Masked training: the costs of the whole batch, means over its N = sum_b lens[b] real frames (N from the host, which made
+ * the lengths: 1 <= N <= B*T), and their backward.  Pad frames of the gradients are +0.
+ *   ptts_rows_combine:  out[0] = sum_b rows[b] * lens[b] / N in fp64, in index order: the batch mean out of the per-row means
+ *                       of ptts_rows_mean / ptts_wlse_rows (lengths read as those kernels read them, clamped to [0, T]).
+ *   ptts_rows_mean_bwd: dv[b,t,:] = t < lens[b] ? upstream * sign / (N * inner) : 0   (sign / N for a critic's [B,T,1])
+ *   ptts_wlse_rows_bwd: dyhat[b,t,d] = t < lens[b] ? upstream * 2 (yhat - y) w[d] / (N * D) : 0
+ * upstream: device float [1], or NULL for 1. */
+int ptts_rows_combine(const float* rows /*[B]*/, const int* lens, int B, int T, long long N, float* out /*[1]*/, void* stream);
+int ptts_rows_mean_bwd(const float* upstream, const int* lens, int B, int T, int inner, float sign, long long N,
+                       float* dv, void* stream);
+int ptts_wlse_rows_bwd(const float* y, const float* yhat, const float* w /*[D] or NULL*/, const float* upstream,
+                       const int* lens, int B, int T, int D, long long N, float* dyhat, void* stream);
 /* out[b] = (1 - sqrt(sq[b]))^2: the gradient penalty per sample, from ptts_gp_sqnorm's sq */
 int ptts_gp_penalty_rows(const float* sq /*[B]*/, float* out /*[B]*/, int B, void* stream);
 
@@ -645,6 +675,13 @@ size_t ptts_lstm_bwd_workspace_bytes(int B, int T, int H, int ndir);
 int ptts_lstm_bwd(const float* dh_out /*[B,T,ndir*H]*/, const float* U, const float* gates, const float* c_out,
                   float* dgates, void* workspace, size_t workspace_bytes,
                   int B, int T, int H, int ndir, int reverse, void* stream);
+/* ptts_lstm_bwd over a zero-padded batch with a length per row (masked training; lens as in ptts_lstm_fwd_ragged, gates and
+ * c_out as that call stored them): on t < lens[b] dgates holds what ptts_lstm_bwd gives for that row alone (B = 1,
+ * T = lens[b]), on t >= lens[b] +0.0f, whatever the pad frames of gates, c_out and dh_out hold -- they are not read.  The
+ * same step-kernel paths, chosen the same way; the same workspace. */
+int ptts_lstm_bwd_ragged(const float* dh_out, const float* U, const float* gates, const float* c_out, float* dgates,
+                         const int* lens, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, int reverse,
+                         void* stream);
 /* Kept for bench.py, which reports these counters.  The replay of a recurrence's step launches as one hipGraph was removed
  * (HISTORY.md), so it writes 0 to each non-null output and returns PTTS_OK. */
 int ptts_lstm_graph_stats(unsigned long long* hits, unsigned long long* captures, unsigned long long* direct);
@@ -676,6 +713,10 @@ int ptts_gru_fwd_ragged(const float* xproj, const float* U, float* h_out, float*
 size_t ptts_gru_bwd_workspace_bytes(int B, int T, int H, int ndir);
 int ptts_gru_bwd(const float* dh_out /*[B,T,ndir*H]*/, const float* U, const float* h_out, const float* gates,
                  float* dgates, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, void* stream);
+/* The same over a zero-padded batch with a length per row (masked training; h_out and gates as ptts_gru_fwd_ragged stored
+ * them): real frames as ptts_gru_bwd on the row alone, pad frames of dgates +0.0f; pad frames of the inputs are not read. */
+int ptts_gru_bwd_ragged(const float* dh_out, const float* U, const float* h_out, const float* gates, float* dgates,
+                        const int* lens, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Maximum-likelihood parameter generation (MLPG; external/merlin/mlpg_fast.py:95-135 as

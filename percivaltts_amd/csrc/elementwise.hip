@@ -335,6 +335,86 @@ struct ActBwdOp4 {
     }
 };
 
+// Masked training (a zero-padded batch [B][T][inner] with a length per row): the same two reductions over the real frames
+// only.  The reduction kernels walk [rows, C] with rows = B*T*inner/C; element i lies in frame i / inner = b*T + t, and a
+// pad frame (t >= lens[b]) is not read and contributes +0 to both sums, which leaves the fp64 sums of the real frames as
+// they are.  The gradient form also writes dx = +0 there.
+struct RowMask {
+    const int* lens; int T; int inner;
+    __device__ __forceinline__ bool real(long long i) const {
+        const long long frame = i / inner, b = frame / T;       // one division each; t is what is left
+        return (int)(frame - b * T) < lens[b];
+    }
+};
+
+struct StatsRowsOp {
+    static constexpr bool SQUARE = true;
+    const float* x; RowMask m;
+    __device__ __forceinline__ void operator()(long long i, int, float& a, float& b) const {
+        a = m.real(i) ? x[i] : 0.f;
+        b = a * a;
+    }
+};
+
+struct StatsRowsOp4 {
+    static constexpr bool SQUARE = true;
+    const float* x; RowMask m;
+    struct Regs { float4 v; };
+    __device__ __forceinline__ void load(long long off, Regs& r) const {
+        r.v = m.real(off) ? ld4(x + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __device__ __forceinline__ void apply(long long, int, const Regs& r, float* a, float* b) const {
+        a[0] = r.v.x; a[1] = r.v.y; a[2] = r.v.z; a[3] = r.v.w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) b[e] = a[e] * a[e];
+    }
+};
+
+// act: PTTS_ACT_NONE or PTTS_ACT_LRELU
+struct ActBwdRowsOp {
+    static constexpr bool SQUARE = false;
+    const float* dy; const float* x; const float* scale; const float* shift; float* dx; int act; float alpha; RowMask m;
+    __device__ __forceinline__ void operator()(long long i, int c, float& a, float& b) const {
+        if (!m.real(i)) { dx[i] = 0.f; a = 0.f; b = 0.f; return; }
+        const float xv = x[i];
+        const float sc = scale ? scale[c] : 1.f;
+        const float d = act == PTTS_ACT_LRELU ? lrelu_d(scale ? xv * sc + shift[c] : xv, alpha) : 1.f;
+        const float gd = dy[i] * d;
+        dx[i] = gd * sc;
+        a = gd * xv;   // dscale
+        b = gd;        // dshift
+    }
+};
+
+struct ActBwdRowsOp4 {
+    static constexpr bool SQUARE = false;
+    const float* dy; const float* x; const float* scale; const float* shift; float* dx; int act; float alpha; RowMask m;
+    struct Regs { float4 d, x; bool real; };      // (the mask is worked out once per group, with the loads)
+    __device__ __forceinline__ void load(long long off, Regs& r) const {
+        r.real = m.real(off);
+        if (r.real) { r.d = ld4(dy + off); r.x = ld4(x + off); }
+    }
+    __device__ __forceinline__ void apply(long long off, int c, const Regs& r, float* a, float* b) const {
+        float o[4];
+        if (r.real) {
+            const float dv[4] = {r.d.x, r.d.y, r.d.z, r.d.w}, xv[4] = {r.x.x, r.x.y, r.x.z, r.x.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float sc = scale ? scale[c + e] : 1.f;
+                const float d = act == PTTS_ACT_LRELU ? lrelu_d(scale ? xv[e] * sc + shift[c + e] : xv[e], alpha) : 1.f;
+                const float gd = dv[e] * d;
+                o[e] = gd * sc;
+                a[e] = gd * xv[e];   // dscale
+                b[e] = gd;           // dshift
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { o[e] = 0.f; a[e] = 0.f; b[e] = 0.f; }
+        }
+        *reinterpret_cast<float4*>(dx + off) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+};
+
 static inline bool al16(const void* p) { return p == nullptr || ((uintptr_t)p % 16) == 0; }
 
 // workgroups of the vectorised reduction: whole passes of R*VU rows each, at most 1024
@@ -699,6 +779,42 @@ __global__ void axpby_cols_kernel(const float* __restrict__ a, const float* __re
         if (a) v += a[i] * (c1 ? c1[c] : 1.f);
         if (x) v += x[i] * (c2 ? c2[c] : 1.f);
         out[i] = v;
+    }
+}
+
+// The BatchNorm backward fix-up of masked training: out = a + x*c2[c] + c0[c] on real frames, +0 on pad frames (so the
+// gradient that leaves the layer stays zero there).  The indexing of affine_act_rows_kernel.  Each lane reads its a before
+// it writes the same elements of out, so out == a is allowed.
+template <int VEC>
+__global__ void axpby_cols_rows_kernel(const float* a, const float* __restrict__ x, const float* __restrict__ c2,
+                                       const float* __restrict__ c0, float* out, const int* __restrict__ lens,
+                                       long long nv, int T, int inner, int C) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nv;
+         i += (long long)gridDim.x * blockDim.x) {
+        const long long e0 = i * VEC;
+        const long long frame = e0 / inner;
+        const int t = (int)(frame % T), b = (int)(frame / T);
+        float p[VEC];
+        if (t < lens[b]) {
+            float xv[VEC];
+            if (VEC == 4) {
+                const float4 v = *reinterpret_cast<const float4*>(a + e0);
+                const float4 w = *reinterpret_cast<const float4*>(x + e0);
+                p[0] = v.x; p[1 % VEC] = v.y; p[2 % VEC] = v.z; p[3 % VEC] = v.w;
+                xv[0] = w.x; xv[1 % VEC] = w.y; xv[2 % VEC] = w.z; xv[3 % VEC] = w.w;
+            } else {
+                p[0] = a[e0];
+                xv[0] = x[e0];
+            }
+            const int c = (int)(e0 % C);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) p[e] = c0[c + e] + p[e] + xv[e] * c2[c + e];   // axpby_cols_kernel's order of the sum
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) p[e] = 0.f;
+        }
+        if (VEC == 4) *reinterpret_cast<float4*>(out + e0) = make_float4(p[0], p[1 % VEC], p[2 % VEC], p[3 % VEC]);
+        else out[e0] = p[0];
     }
 }
 
@@ -1283,6 +1399,65 @@ extern "C" int ptts_axpby_cols(const float* a, const float* c1, const float* x, 
     hipLaunchKernelGGL(axpby_cols_kernel, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, (hipStream_t)stream, a, c1, x, c2,
                        c0, out, n, C);
     return check_launch("axpby_cols");
+}
+
+// ---- masked training: the three BatchNorm passes over a zero-padded batch with a length per row ----
+static int rows_args_ok(const char* what, int B, int T, int inner, int C) {
+    PTTS_REQUIRE(B > 0 && T > 0 && inner > 0 && C > 0, "%s: bad dims B=%d T=%d inner=%d C=%d", what, B, T, inner, C);
+    PTTS_REQUIRE(inner % C == 0, "%s: inner=%d is no multiple of C=%d", what, inner, C);
+    return PTTS_OK;
+}
+
+extern "C" size_t ptts_colstats_rows_workspace_bytes(int B, int T, int inner, int C) {
+    if (B <= 0 || T <= 0 || inner <= 0 || C <= 0 || inner % C != 0) return 0;
+    return ptts_colstats_workspace_bytes((long long)B * T * (inner / C), C);
+}
+
+extern "C" int ptts_colstats_rows(const float* x, const int* lens, int B, int T, int inner, int C, double* sums,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    PTTS_REQUIRE(x && lens && sums, "colstats_rows: null tensor");
+    if (int rc = rows_args_ok("colstats_rows", B, T, inner, C)) return rc;
+    const long long rows = (long long)B * T * (inner / C);
+    const RowMask m{lens, T, inner};
+    if (C % 4 == 0 && C <= 4 * EW_THREADS && al16(x)) {
+        StatsRowsOp4 op4{x, m};
+        return run_colreduce_vec4(op4, rows, C, sums, workspace, workspace_bytes, (hipStream_t)stream, "colstats_rows");
+    }
+    StatsRowsOp op{x, m};
+    return run_colreduce(op, rows, C, sums, workspace, workspace_bytes, (hipStream_t)stream, "colstats_rows");
+}
+
+extern "C" int ptts_affine_act_rows_bwd_params(const float* dy, const float* x, const float* scale, const float* shift,
+                                               float* dx, double* dsums, const int* lens, void* workspace,
+                                               size_t workspace_bytes, int B, int T, int inner, int C, int act,
+                                               float alpha, void* stream) {
+    PTTS_REQUIRE(dy && x && dx && dsums && lens, "affine_act_rows_bwd_params: null tensor");
+    if (int rc = rows_args_ok("affine_act_rows_bwd_params", B, T, inner, C)) return rc;
+    PTTS_REQUIRE((scale == nullptr) == (shift == nullptr), "affine_act_rows_bwd_params: scale/shift must come together");
+    PTTS_REQUIRE(act == PTTS_ACT_NONE || act == PTTS_ACT_LRELU, "affine_act_rows_bwd_params: act=%d (none and lrelu only)", act);
+    const long long rows = (long long)B * T * (inner / C);
+    const RowMask m{lens, T, inner};
+    if (C % 4 == 0 && C <= 4 * EW_THREADS && al16(dy) && al16(x) && al16(dx)) {
+        ActBwdRowsOp4 op4{dy, x, scale, shift, dx, act, alpha, m};
+        return run_colreduce_vec4(op4, rows, C, dsums, workspace, workspace_bytes, (hipStream_t)stream, "affine_act_rows_bwd_params");
+    }
+    ActBwdRowsOp op{dy, x, scale, shift, dx, act, alpha, m};
+    return run_colreduce(op, rows, C, dsums, workspace, workspace_bytes, (hipStream_t)stream, "affine_act_rows_bwd_params");
+}
+
+extern "C" int ptts_axpby_cols_rows(const float* a, const float* x, const float* c2, const float* c0, float* out,
+                                    const int* lens, int B, int T, int inner, int C, void* stream) {
+    PTTS_REQUIRE(a && x && c2 && c0 && out && lens, "axpby_cols_rows: null tensor");
+    if (int rc = rows_args_ok("axpby_cols_rows", B, T, inner, C)) return rc;
+    const long long n = (long long)B * T * inner;
+    hipStream_t st = (hipStream_t)stream;
+    if (C % 4 == 0 && al16(a) && al16(x) && al16(out))
+        hipLaunchKernelGGL(axpby_cols_rows_kernel<4>, dim3(ew_blocks(n / 4, 2)), dim3(EW_THREADS), 0, st, a, x, c2, c0, out,
+                           lens, n / 4, T, inner, C);
+    else
+        hipLaunchKernelGGL(axpby_cols_rows_kernel<1>, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, st, a, x, c2, c0, out, lens,
+                           n, T, inner, C);
+    return check_launch("axpby_cols_rows");
 }
 
 extern "C" int ptts_gp_interpolate(const float* real, const float* fake, const float* alpha_b, float* out, int B,

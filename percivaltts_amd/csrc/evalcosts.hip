@@ -2,6 +2,8 @@
 // per-row reductions behind OptimizerTTSWGAN.validation_costs_batch.  Every row's result depends on that row alone (one
 // workgroup per row, fixed-order fp64 sums, no atomics), so an utterance costs the same bytes in any batch; nothing here
 // goes to the host.  All of them are bandwidth-trivial single-pass kernels.
+// Masked training adds the costs of the whole batch, means over its N real frames: the per-row means combined on the device
+// (rows_combine_kernel) and the gradients of the two means, +0 on pad frames.
 #include "common.h"
 #include <cstdint>
 
@@ -127,6 +129,50 @@ __global__ void gp_penalty_rows_kernel(const float* __restrict__ sq, float* __re
     }
 }
 
+// ---- masked training: the batch costs out of the per-row ones, and their backward ----
+// out[0] = sum_b rows[b] * lens[b] / N in fp64, rows in index order: the mean over all N real frames of the batch from the
+// per-row means of rows_mean_kernel / wlse_rows_kernel.  One wave.
+__global__ __launch_bounds__(64) void rows_combine_kernel(const float* __restrict__ rows, const int* __restrict__ lens, int B,
+                                                          int T, double inv_n, float* __restrict__ out) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < B; b += 64) {
+        int len = lens[b];
+        len = len < 0 ? 0 : (len > T ? T : len);
+        s += (double)rows[b] * (double)len;
+    }
+    s = wave_sum(s);
+    if (threadIdx.x == 0) out[0] = (float)(s * inv_n);
+}
+
+// dv[b,t,:] = t < lens[b] ? upstream[0] * coef : +0  (coef = sign / (N * inner), formed in fp64 on the host)
+template <int VEC>
+__global__ void rows_mean_bwd_kernel(const float* __restrict__ upstream, const int* __restrict__ lens, float* __restrict__ dv,
+                                     long long nv, int T, int inner, float coef) {
+    const float g = upstream ? upstream[0] * coef : coef;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nv;
+         i += (long long)gridDim.x * blockDim.x) {
+        const long long e0 = i * VEC;
+        const long long frame = e0 / inner;
+        const float v = (int)(frame % T) < lens[frame / T] ? g : 0.f;
+        if (VEC == 4) *reinterpret_cast<float4*>(dv + e0) = make_float4(v, v, v, v);
+        else dv[e0] = v;
+    }
+}
+
+// dyhat[b,t,d] = t < lens[b] ? upstream[0] * 2 (yhat - y) w[d] * inv : +0  (inv = 1 / (N * D)); wlse_bwd_kernel's arithmetic
+__global__ void wlse_rows_bwd_kernel(const float* __restrict__ y, const float* __restrict__ yhat, const float* __restrict__ w,
+                                     const float* __restrict__ upstream, const int* __restrict__ lens,
+                                     float* __restrict__ dyhat, long long n, int T, int D, float inv) {
+    const float up = (upstream ? upstream[0] : 1.f) * inv;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
+         i += (long long)gridDim.x * blockDim.x) {
+        const long long frame = i / D;
+        float g = 0.f;
+        if ((int)(frame % T) < lens[frame / T]) g = up * 2.f * (yhat[i] - y[i]) * (w ? w[i % D] : 1.f);
+        dyhat[i] = g;
+    }
+}
+
 }  // namespace ptts
 
 using namespace ptts;
@@ -166,6 +212,39 @@ extern "C" int ptts_wlse_rows(const float* y, const float* yhat, const float* w,
     hipLaunchKernelGGL(wlse_rows_kernel, dim3(B), dim3(EC_ROW_THREADS), 0, (hipStream_t)stream, y, yhat, w, lens, T, D,
                        out_ls, out_sq);
     return check_launch("wlse_rows");
+}
+
+extern "C" int ptts_rows_combine(const float* rows, const int* lens, int B, int T, long long N, float* out, void* stream) {
+    PTTS_REQUIRE(rows && lens && out && B > 0 && T > 0, "rows_combine: bad args");
+    PTTS_REQUIRE(N > 0 && N <= (long long)B * T, "rows_combine: N=%lld real frames in a batch of %d x %d", N, B, T);
+    hipLaunchKernelGGL(rows_combine_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, rows, lens, B, T, 1.0 / (double)N, out);
+    return check_launch("rows_combine");
+}
+
+extern "C" int ptts_rows_mean_bwd(const float* upstream, const int* lens, int B, int T, int inner, float sign, long long N,
+                                  float* dv, void* stream) {
+    PTTS_REQUIRE(lens && dv && B > 0 && T > 0 && inner > 0, "rows_mean_bwd: bad args");
+    PTTS_REQUIRE(N > 0 && N <= (long long)B * T, "rows_mean_bwd: N=%lld real frames in a batch of %d x %d", N, B, T);
+    const long long n = (long long)B * T * inner;
+    const float coef = (float)((double)sign / ((double)N * (double)inner));
+    hipStream_t st = (hipStream_t)stream;
+    if (inner % 4 == 0 && (uintptr_t)dv % 16 == 0)
+        hipLaunchKernelGGL(rows_mean_bwd_kernel<4>, dim3(ec_blocks(n / 4, 2)), dim3(EC_THREADS), 0, st, upstream, lens, dv,
+                           n / 4, T, inner, coef);
+    else
+        hipLaunchKernelGGL(rows_mean_bwd_kernel<1>, dim3(ec_blocks(n, 4)), dim3(EC_THREADS), 0, st, upstream, lens, dv, n, T,
+                           inner, coef);
+    return check_launch("rows_mean_bwd");
+}
+
+extern "C" int ptts_wlse_rows_bwd(const float* y, const float* yhat, const float* w, const float* upstream, const int* lens,
+                                  int B, int T, int D, long long N, float* dyhat, void* stream) {
+    PTTS_REQUIRE(y && yhat && lens && dyhat && B > 0 && T > 0 && D > 0, "wlse_rows_bwd: bad args");
+    PTTS_REQUIRE(N > 0 && N <= (long long)B * T, "wlse_rows_bwd: N=%lld real frames in a batch of %d x %d", N, B, T);
+    const long long n = (long long)B * T * D;
+    hipLaunchKernelGGL(wlse_rows_bwd_kernel, dim3(ec_blocks(n, 4)), dim3(EC_THREADS), 0, (hipStream_t)stream, y, yhat, w,
+                       upstream, lens, dyhat, n, T, D, (float)(1.0 / ((double)N * (double)D)));
+    return check_launch("wlse_rows_bwd");
 }
 
 extern "C" int ptts_gp_penalty_rows(const float* sq, float* out, int B, void* stream) {

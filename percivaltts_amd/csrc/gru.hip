@@ -12,6 +12,8 @@
 // lstm_pack_u_fwd_kernel: each lane's B operands of all k-steps contiguous), K split over the 4 waves of a workgroup and the
 // partial tiles summed through LDS in a fixed order.  Any H: K is padded to a multiple of 16 with zero weights, and the A
 // operands, columns and samples beyond H / 2H / B are predicated off.
+// ptts_gru_fwd_ragged / ptts_gru_bwd_ragged: the same launches over a zero-padded batch with a length per row, every row walked
+// over its own length (inference, and masked training with gates and r*h stored).
 #include "common.h"
 
 namespace ptts {
@@ -205,21 +207,32 @@ __global__ __launch_bounds__(256) void gru_fwd_h_ragged_kernel(
 // Backward launch A' of forward step s (launched for s = T-1 .. 0): grid (tiles16(H), ceil(B/16), ndir), 256 threads.
 // dh = dh_out[t] + carry (dh_{t} through the recurrence, left by B' of step s+1).  Each workgroup recomputes da_h over its
 // K range as the MFMA's A operand; for its own 16 units it writes dgates (z, r, h) and carry2 = dh z + d(rh) r.
-__global__ __launch_bounds__(256) void gru_bwd_h_kernel(
+// Ragged backward (RAG, masked training): the backward of ptts_gru_fwd_ragged's walk.  Row b is active in forward step s while
+// s < len = lens[b] (a larger value is read as T), the backward direction at the row's own t = len - 1 - s, and the row has a
+// next step, whose carry it takes, while s < len - 1: its last step starts from the zero gradient the lone utterance ends
+// with.  An inactive row gives a zero operand, writes dgates = +0 at t = s (so every (b, t) is written exactly once) and
+// touches neither carry; nothing is read of dh_out, h_out or gates at t >= len.  Bodies templated on RAG behind two entries,
+// as in the forward.
+template <bool RAG>
+__device__ __forceinline__ void gru_bwd_h_body(
     const float* __restrict__ dh_out, const float* __restrict__ Upk, const float* __restrict__ h_out,
     const float* __restrict__ gates, float* __restrict__ dgates, const float* __restrict__ carry, float* __restrict__ carry2,
-    int B, int T, int H, int ndir, int s) {
+    int B, int T, int H, int ndir, int s, const int* __restrict__ lens) {
     __shared__ float red[4][256];
     __builtin_amdgcn_s_setprio(3);
     const int d = blockIdx.z;
-    const int t = d == 1 ? T - 1 - s : s, tp = d == 1 ? t + 1 : t - 1;
+    int t = d == 1 ? T - 1 - s : s, tp = d == 1 ? t + 1 : t - 1;
     const int jt = blockIdx.x, b0 = blockIdx.y * 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
     const int KS = round16(H) / 16, NT = tiles16(H);
     const long long G3 = 3LL * H, GG = ndir * G3, HH = (long long)ndir * H;
-    const bool has_next = s < T - 1;
     const int eb = b0 + (tid >> 4), j = jt * 16 + (tid & 15);
-    const bool epi = eb < B && j < H;
+    const int len_e = RAG ? (eb < B ? min(lens[eb], T) : 0) : T;
+    const int len_a = RAG ? (b0 + r16 < B ? min(lens[b0 + r16], T) : 0) : T;
+    const bool has_next = s < len_e - 1;          // of the epilogue's row (RAG = false: s < T - 1)
+    const bool own = eb < B && j < H;
+    const bool epi = own && (!RAG || s < len_e);
+    if (RAG && d == 1) { t = len_e - 1 - s; tp = t + 1; }
     const long long row = (long long)eb * T + t;
     float dh = 0.f, z = 0.f, r = 0.f, hh = 0.f, hp = 0.f;
     if (epi) {
@@ -231,20 +244,26 @@ __global__ __launch_bounds__(256) void gru_bwd_h_kernel(
     }
     if (s > 0) {      // at s = 0, d(rh) only meets h_{-1} = 0 and no earlier step takes carry2
         const int b = b0 + r16;
-        const bool bok = b < B;
+        const bool bok = RAG ? s < len_a : b < B;
+        const bool next_a = s < len_a - 1;
+        const int ta = RAG ? (bok ? (d == 1 ? len_a - 1 - s : s) : 0) : t;
         const long long bs = bok ? b : 0;
-        const float* dhrow = dh_out + (bs * T + t) * HH + (long long)d * H;
+        const float* dhrow = dh_out + (bs * T + ta) * HH + (long long)d * H;
         const float* crow = carry + ((long long)d * B + bs) * H;
-        const float* grow = gates + (bs * T + t) * GG + d * G3;
+        const float* grow = gates + (bs * T + ta) * GG + d * G3;
         const float* bp = Upk + ((((long long)d * NT + jt) * 4 + wave) * 64 + lane) * KS;
         gru_wave_tile(bp, KS, wave * 4 * KS + q * KS, [&](int n) {
             if (!(bok && n < H)) return 0.f;
             float g = dhrow[n];
-            if (has_next) g += crow[n];
+            if (next_a) g += crow[n];
             const float zn = grow[n], hn = grow[2 * H + n];
             return g * (1.f - zn) * (1.f - hn * hn);
         }, red[wave]);
         __syncthreads();
+    }
+    if (RAG && own && !epi) {
+        float* dg = dgates + ((long long)eb * T + s) * GG + d * G3;
+        dg[j] = 0.f; dg[H + j] = 0.f; dg[2 * H + j] = 0.f;
     }
     if (!epi) return;
     const float drh = s > 0 ? red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid] : 0.f;
@@ -256,30 +275,60 @@ __global__ __launch_bounds__(256) void gru_bwd_h_kernel(
     carry2[((long long)d * B + eb) * H + j] = dh * z + drh * r;
 }
 
-// Backward launch B' of forward step s (s >= 1): carry = carry2 + da_zr.U_zr^T; grid (tiles16(H), ceil(B/16), ndir).
-__global__ __launch_bounds__(256) void gru_bwd_zr_kernel(
-    const float* __restrict__ Upk, const float* __restrict__ dgates, const float* __restrict__ carry2, float* __restrict__ carry,
+__global__ __launch_bounds__(256) void gru_bwd_h_kernel(
+    const float* __restrict__ dh_out, const float* __restrict__ Upk, const float* __restrict__ h_out,
+    const float* __restrict__ gates, float* __restrict__ dgates, const float* __restrict__ carry, float* __restrict__ carry2,
     int B, int T, int H, int ndir, int s) {
+    gru_bwd_h_body<false>(dh_out, Upk, h_out, gates, dgates, carry, carry2, B, T, H, ndir, s, nullptr);
+}
+
+__global__ __launch_bounds__(256) void gru_bwd_h_ragged_kernel(
+    const float* __restrict__ dh_out, const float* __restrict__ Upk, const float* __restrict__ h_out,
+    const float* __restrict__ gates, float* __restrict__ dgates, const float* __restrict__ carry, float* __restrict__ carry2,
+    int B, int T, int H, int ndir, int s, const int* __restrict__ lens) {
+    gru_bwd_h_body<true>(dh_out, Upk, h_out, gates, dgates, carry, carry2, B, T, H, ndir, s, lens);
+}
+
+// Backward launch B' of forward step s (s >= 1): carry = carry2 + da_zr.U_zr^T; grid (tiles16(H), ceil(B/16), ndir).
+template <bool RAG>
+__device__ __forceinline__ void gru_bwd_zr_body(
+    const float* __restrict__ Upk, const float* __restrict__ dgates, const float* __restrict__ carry2, float* __restrict__ carry,
+    int B, int T, int H, int ndir, int s, const int* __restrict__ lens) {
     __shared__ float red[4][256];
     __builtin_amdgcn_s_setprio(3);
     const int d = blockIdx.z;
-    const int t = d == 1 ? T - 1 - s : s;
+    const int t0 = d == 1 ? T - 1 - s : s;
     const int jt = blockIdx.x, b0 = blockIdx.y * 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
     const int KS = round16(2 * H) / 16, NT = tiles16(H);
     const long long G3 = 3LL * H, GG = ndir * G3;
     const int eb = b0 + (tid >> 4), j = jt * 16 + (tid & 15);
-    const bool epi = eb < B && j < H;
+    const int len_e = RAG ? (eb < B ? min(lens[eb], T) : 0) : T;
+    const int len_a = RAG ? (b0 + r16 < B ? min(lens[b0 + r16], T) : 0) : T;
+    const bool epi = eb < B && j < H && (!RAG || s < len_e);
     const long long si = ((long long)d * B + eb) * H + j;
     const float base = epi ? carry2[si] : 0.f;
     const int b = b0 + r16;
-    const bool bok = b < B;
+    const bool bok = RAG ? s < len_a : b < B;
+    const int t = RAG ? (bok ? (d == 1 ? len_a - 1 - s : s) : 0) : t0;
     const float* grow = dgates + ((long long)(bok ? b : 0) * T + t) * GG + d * G3;
     const float* bp = Upk + ((((long long)d * NT + jt) * 4 + wave) * 64 + lane) * KS;
     gru_wave_tile(bp, KS, wave * 4 * KS + q * KS, [&](int n) { return bok && n < 2 * H ? grow[n] : 0.f; }, red[wave]);
     __syncthreads();
     if (!epi) return;
     carry[si] = base + (red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
+}
+
+__global__ __launch_bounds__(256) void gru_bwd_zr_kernel(
+    const float* __restrict__ Upk, const float* __restrict__ dgates, const float* __restrict__ carry2, float* __restrict__ carry,
+    int B, int T, int H, int ndir, int s) {
+    gru_bwd_zr_body<false>(Upk, dgates, carry2, carry, B, T, H, ndir, s, nullptr);
+}
+
+__global__ __launch_bounds__(256) void gru_bwd_zr_ragged_kernel(
+    const float* __restrict__ Upk, const float* __restrict__ dgates, const float* __restrict__ carry2, float* __restrict__ carry,
+    int B, int T, int H, int ndir, int s, const int* __restrict__ lens) {
+    gru_bwd_zr_body<true>(Upk, dgates, carry2, carry, B, T, H, ndir, s, lens);
 }
 
 // floats of one packed operand: ndir x tiles16(N) x 256 lanes x KS
@@ -361,13 +410,15 @@ extern "C" size_t ptts_gru_bwd_workspace_bytes(int B, int T, int H, int ndir) {
     return (packed_floats(ndir, H, H) + packed_floats(ndir, 2 * H, H) + (size_t)2 * ndir * B * H) * sizeof(float);
 }
 
-extern "C" int ptts_gru_bwd(const float* dh_out, const float* U, const float* h_out, const float* gates, float* dgates,
-                            void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, void* stream) {
-    PTTS_REQUIRE(dh_out && U && h_out && gates && dgates, "gru_bwd: null tensor");
-    PTTS_REQUIRE(B > 0 && T > 0 && H > 0 && (ndir == 1 || ndir == 2), "gru_bwd: bad dims B=%d T=%d H=%d ndir=%d", B, T, H, ndir);
+// The launches of ptts_gru_bwd (lens NULL) and of ptts_gru_bwd_ragged.
+static int gru_bwd_run(const char* what, const float* dh_out, const float* U, const float* h_out, const float* gates,
+                       float* dgates, const int* lens, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir,
+                       void* stream) {
+    PTTS_REQUIRE(dh_out && U && h_out && gates && dgates, "%s: null tensor", what);
+    PTTS_REQUIRE(B > 0 && T > 0 && H > 0 && (ndir == 1 || ndir == 2), "%s: bad dims B=%d T=%d H=%d ndir=%d", what, B, T, H, ndir);
     const size_t need = ptts_gru_bwd_workspace_bytes(B, T, H, ndir);
     if (!workspace || workspace_bytes < need) {
-        set_error("gru_bwd: workspace %zu < %zu", workspace_bytes, need);
+        set_error("%s: workspace %zu < %zu", what, workspace_bytes, need);
         return PTTS_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -379,11 +430,31 @@ extern "C" int ptts_gru_bwd(const float* dh_out, const float* U, const float* h_
     launch_pack(U, UzrT, H, ndir, 2 * H, H, 0, 1, st);
     const dim3 grid(tiles16(H), tiles16(B), ndir);
     for (int s = T - 1; s >= 0; --s) {
+        if (lens) {
+            hipLaunchKernelGGL(gru_bwd_h_ragged_kernel, grid, dim3(256), 0, st, dh_out, (const float*)UhT, h_out, gates, dgates,
+                               (const float*)carry, carry2, B, T, H, ndir, s, lens);
+            if (s > 0)
+                hipLaunchKernelGGL(gru_bwd_zr_ragged_kernel, grid, dim3(256), 0, st, (const float*)UzrT, (const float*)dgates,
+                                   (const float*)carry2, carry, B, T, H, ndir, s, lens);
+            continue;
+        }
         hipLaunchKernelGGL(gru_bwd_h_kernel, grid, dim3(256), 0, st, dh_out, (const float*)UhT, h_out, gates, dgates,
                            (const float*)carry, carry2, B, T, H, ndir, s);
         if (s > 0)
             hipLaunchKernelGGL(gru_bwd_zr_kernel, grid, dim3(256), 0, st, (const float*)UzrT, (const float*)dgates,
                                (const float*)carry2, carry, B, T, H, ndir, s);
     }
-    return check_launch("gru_bwd");
+    return check_launch(what);
+}
+
+extern "C" int ptts_gru_bwd(const float* dh_out, const float* U, const float* h_out, const float* gates, float* dgates,
+                            void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir, void* stream) {
+    return gru_bwd_run("gru_bwd", dh_out, U, h_out, gates, dgates, nullptr, workspace, workspace_bytes, B, T, H, ndir, stream);
+}
+
+extern "C" int ptts_gru_bwd_ragged(const float* dh_out, const float* U, const float* h_out, const float* gates, float* dgates,
+                                   const int* lens, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir,
+                                   void* stream) {
+    PTTS_REQUIRE(lens, "gru_bwd_ragged: null lens");
+    return gru_bwd_run("gru_bwd_ragged", dh_out, U, h_out, gates, dgates, lens, workspace, workspace_bytes, B, T, H, ndir, stream);
 }

@@ -11,7 +11,8 @@
 //   scalar      : any other H; one lane per (sample, unit), h_{t-1} staged in LDS
 // Limits: H <= 4096 forward, H <= 1024 backward (the scalar kernels' LDS rows bound every path).
 // ptts_lstm_fwd_ragged runs the same three forward paths, chosen the same way, for inference over a zero-padded batch with a
-// length per row (compile-time variants of the step kernels, see lstm_fwd_step_body).
+// length per row (compile-time variants of the step kernels, see lstm_fwd_step_body), and ptts_lstm_bwd_ragged the three backward
+// paths for masked training on such a batch (see lstm_bwd_step_body).
 #include "common.h"
 
 namespace ptts {
@@ -129,16 +130,28 @@ __global__ void lstm_transpose_kernel(const float* __restrict__ U, float* __rest
     }
 }
 
+// Ragged backward (masked training): the backward of ptts_lstm_fwd_ragged's walk.  Row b is active in forward step s while
+// s < len = lens[b]; a backward direction worked on t = len - 1 - s, so forward step s + 1 of that row lies at t - 1 of the ROW's
+// own t, and the row has a next step while s < len - 1: at its last step (s = len - 1, where the launches for larger s found it
+// inactive) neither the recurrent term nor the cell-state carry is read, which is the zero state the lone utterance ends with.
+// An inactive row gives a zero operand, writes dgates = +0 at t = s (so every (b, t) is written exactly once over the T steps)
+// and leaves the carry alone; nothing is read of gates, c_out or dh_out at t >= len.  A length above T is read as T, one
+// below 1 as an empty row.  As in the forward, the scalar kernel is a body templated on RAG behind two __global__ entries and
+// the MFMA kernels take `lens` as a trailing parameter pack, so the training instantiations keep their code.
+__device__ __forceinline__ void rag_lens(const int*& lens) { lens = nullptr; }
+__device__ __forceinline__ void rag_lens(const int*& lens, const int* l) { lens = l; }
+
 // backward of forward step s (launched for s = T-1 .. 0)
-__global__ __launch_bounds__(LX * LY) void lstm_bwd_step_kernel(
+template <bool RAG>
+__device__ __forceinline__ void lstm_bwd_step_body(
     const float* __restrict__ dh_out, const float* __restrict__ UT, const float* __restrict__ gates,
     const float* __restrict__ c_out, float* __restrict__ dgates, float* __restrict__ dc_state, int B, int T,
-    int H, int ndir, int reverse, int s) {
+    int H, int ndir, int reverse, int s, const int* __restrict__ lens) {
     extern __shared__ float das[];   // [LY][4H]: gate-preactivation grads of forward step s+1
     const int d = blockIdx.z;
     const bool rev = ndir == 2 ? d == 1 : reverse != 0;
-    const int t = rev ? T - 1 - s : s;
-    const int tp = rev ? t + 1 : t - 1;   // time of forward step s-1
+    int t = rev ? T - 1 - s : s;
+    int tp = rev ? t + 1 : t - 1;         // time of forward step s-1
     const int tn = rev ? t - 1 : t + 1;   // time of forward step s+1
     const int tid = threadIdx.y * LX + threadIdx.x;
     const long long G4 = 4LL * H;
@@ -148,15 +161,32 @@ __global__ __launch_bounds__(LX * LY) void lstm_bwd_step_kernel(
         for (int idx = tid; idx < LY * (int)G4; idx += LX * LY) {
             const int by = idx / (int)G4, n = idx - by * (int)G4;
             const int b = blockIdx.y * LY + by;
-            das[idx] = b < B ? dgates[(((long long)b * T + tn) * ndir + d) * G4 + n] : 0.f;
+            if (RAG) {
+                const int len = b < B ? min(lens[b], T) : 0;
+                const int tnb = rev ? len - 2 - s : s + 1;
+                das[idx] = s < len - 1 ? dgates[(((long long)b * T + tnb) * ndir + d) * G4 + n] : 0.f;
+            } else {
+                das[idx] = b < B ? dgates[(((long long)b * T + tn) * ndir + d) * G4 + n] : 0.f;
+            }
         }
         __syncthreads();
     }
     const int j = blockIdx.x * LX + threadIdx.x;
     const int b = blockIdx.y * LY + threadIdx.y;
     if (j >= H || b >= B) return;
+    bool nxt = has_next;                  // of this row
+    if (RAG) {
+        const int len = min(lens[b], T);
+        if (s >= len) {
+            float* dg = dgates + (((long long)b * T + s) * ndir + d) * G4;
+            dg[j] = 0.f; dg[H + j] = 0.f; dg[2 * H + j] = 0.f; dg[3 * H + j] = 0.f;
+            return;
+        }
+        if (rev) { t = len - 1 - s; tp = t + 1; }
+        nxt = s < len - 1;
+    }
     float dh = dh_out[((long long)b * T + t) * HH + (long long)d * H + j];
-    if (has_next) {
+    if (nxt) {
         const float* ut = UT + (long long)d * G4 * H + j;
         const float* drow = das + threadIdx.y * G4;
         float acc = 0.f;
@@ -172,13 +202,27 @@ __global__ __launch_bounds__(LX * LY) void lstm_bwd_step_kernel(
     const float tc = tanhf(c);
     const long long si = ((long long)d * B + b) * H + j;
     float dc = dh * go * (1.f - tc * tc);
-    if (has_next) dc += dc_state[si];
+    if (nxt) dc += dc_state[si];
     float* dg = dgates + (((long long)b * T + t) * ndir + d) * G4;
     dg[j] = dc * gc * gi * (1.f - gi);
     dg[H + j] = dc * cp * gf * (1.f - gf);
     dg[2 * H + j] = dc * gi * (1.f - gc * gc);
     dg[3 * H + j] = dh * tc * go * (1.f - go);
     dc_state[si] = dc * gf;
+}
+
+__global__ __launch_bounds__(LX * LY) void lstm_bwd_step_kernel(
+    const float* __restrict__ dh_out, const float* __restrict__ UT, const float* __restrict__ gates,
+    const float* __restrict__ c_out, float* __restrict__ dgates, float* __restrict__ dc_state, int B, int T,
+    int H, int ndir, int reverse, int s) {
+    lstm_bwd_step_body<false>(dh_out, UT, gates, c_out, dgates, dc_state, B, T, H, ndir, reverse, s, nullptr);
+}
+
+__global__ __launch_bounds__(LX * LY) void lstm_bwd_step_ragged_kernel(
+    const float* __restrict__ dh_out, const float* __restrict__ UT, const float* __restrict__ gates,
+    const float* __restrict__ c_out, float* __restrict__ dgates, float* __restrict__ dc_state, int B, int T,
+    int H, int ndir, int reverse, int s, const int* __restrict__ lens) {
+    lstm_bwd_step_body<true>(dh_out, UT, gates, c_out, dgates, dc_state, B, T, H, ndir, reverse, s, lens);
 }
 
 
@@ -282,15 +326,19 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_mfma_kernel(
     }
 }
 
+template <class... R>   // R: empty, or <const int* lens> for the ragged backward
 __global__ __launch_bounds__(256) void lstm_bwd_step_mfma_kernel(
     const float* __restrict__ dh_out, const float* __restrict__ UT, const float* __restrict__ gates,
     const float* __restrict__ c_out, float* __restrict__ dgates, float* __restrict__ dc_state, int B, int T,
-    int H, int ndir, int reverse, int s) {
+    int H, int ndir, int reverse, int s, R... rag) {
+    constexpr bool RAG = sizeof...(R) != 0;
+    const int* lens;
+    rag_lens(lens, rag...);
     __shared__ float red[4][256];
     const int d = blockIdx.z;
     const bool rev = ndir == 2 ? d == 1 : reverse != 0;
-    const int t = rev ? T - 1 - s : s;
-    const int tp = rev ? t + 1 : t - 1;
+    int t = rev ? T - 1 - s : s;
+    int tp = rev ? t + 1 : t - 1;
     const int tn = rev ? t - 1 : t + 1;
     const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -301,7 +349,14 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_mfma_kernel(
         const int nsteps = H / 4;                  // n-steps of 4 per wave (each wave owns H of the 4H gate columns)
         const int nbase = wave * H;
         const int b = b0 + r16;
-        const float* ap = dgates + (((long long)(b < B ? b : 0) * T + tn) * ndir + d) * G4 + nbase + q;
+        bool a_on = b < B;                          // the tile row has a next step
+        int tna = tn;
+        if constexpr (RAG) {
+            const int len = b < B ? min(lens[b], T) : 0;
+            a_on = s < len - 1;
+            tna = a_on ? (rev ? len - 2 - s : s + 1) : 0;
+        }
+        const float* ap = dgates + (((long long)(a_on ? b : 0) * T + tna) * ndir + d) * G4 + nbase + q;
         const float* bp = UT + (long long)d * G4 * H + (long long)(nbase + q) * H + j0 + r16;
         f32x4v acc = {0.f, 0.f, 0.f, 0.f};
         for (int s0 = 0; s0 < nsteps; s0 += 16) {
@@ -310,7 +365,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_mfma_kernel(
             for (int i = 0; i < 16; ++i) {
                 const int st = s0 + i;
                 if (st < nsteps) {
-                    a[i] = b < B ? ap[4 * st] : 0.f;
+                    a[i] = a_on ? ap[4 * st] : 0.f;
                     bv[i] = bp[(long long)(4 * st) * H];
                 } else { a[i] = 0.f; bv[i] = 0.f; }
             }
@@ -324,8 +379,19 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_mfma_kernel(
     const int bb = tid >> 4, jj = tid & 15;
     const int b = b0 + bb, j = j0 + jj;
     if (b >= B) return;
+    bool nxt = has_next;                            // of this row
+    if constexpr (RAG) {
+        const int len = min(lens[b], T);
+        if (s >= len) {
+            float* dg = dgates + (((long long)b * T + s) * ndir + d) * (4LL * H);
+            dg[j] = 0.f; dg[H + j] = 0.f; dg[2 * H + j] = 0.f; dg[3 * H + j] = 0.f;
+            return;
+        }
+        if (rev) { t = len - 1 - s; tp = t + 1; }
+        nxt = s < len - 1;
+    }
     float dh = dh_out[((long long)b * T + t) * HH + (long long)d * H + j];
-    if (has_next) dh += red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    if (nxt) dh += red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
     const float* gp = gates + (((long long)b * T + t) * ndir + d) * G4;
     const float gi = gp[j], gf = gp[H + j], gc = gp[2 * H + j], go = gp[3 * H + j];
     const long long so = ((long long)b * T + t) * HH + (long long)d * H + j;
@@ -334,7 +400,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_mfma_kernel(
     const float tc = tanhf(c);
     const long long si = ((long long)d * B + b) * H + j;
     float dc = dh * go * (1.f - tc * tc);
-    if (has_next) dc += dc_state[si];
+    if (nxt) dc += dc_state[si];
     float* dg = dgates + (((long long)b * T + t) * ndir + d) * G4;
     dg[j] = dc * gc * gi * (1.f - gi);
     dg[H + j] = dc * cp * gf * (1.f - gf);
@@ -491,18 +557,21 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_pk_kernel(
 }
 
 
-template <int NW>   // waves per workgroup: 4, or 8 (H = 256: the K = 4H reduction over eight waves -- half the dependent MFMA chain and
+template <int NW, class... R>   // R: empty, or <const int* lens> for the ragged backward.  NW: waves per workgroup: 4, or 8 (H = 256: the K = 4H reduction over eight waves -- half the dependent MFMA chain and
                     // half the load rounds per wave of this latency-bound step)
 __global__ __launch_bounds__(64 * NW) void lstm_bwd_step_pk_kernel(
     const float* __restrict__ dh_out, const float* __restrict__ UTpk, const float* __restrict__ gates,
     const float* __restrict__ c_out, float* __restrict__ dgates, float* __restrict__ dc_state, int B, int T,
-    int H, int ndir, int reverse, int s) {
+    int H, int ndir, int reverse, int s, R... rag) {
+    constexpr bool RAG = sizeof...(R) != 0;
+    const int* lens;
+    rag_lens(lens, rag...);
     __shared__ float red[NW][256];
     __builtin_amdgcn_s_setprio(3);         // as in the forward step: ahead of the co-resident wide kernels' waves
     const int d = blockIdx.z;
     const bool rev = ndir == 2 ? d == 1 : reverse != 0;
-    const int t = rev ? T - 1 - s : s;
-    const int tp = rev ? t + 1 : t - 1;
+    int t = rev ? T - 1 - s : s;
+    int tp = rev ? t + 1 : t - 1;
     const int tn = rev ? t - 1 : t + 1;
     const int jt = blockIdx.x, j0 = jt * 16, b0 = blockIdx.y * 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -515,44 +584,65 @@ __global__ __launch_bounds__(64 * NW) void lstm_bwd_step_pk_kernel(
     const int bb = tid >> 4, jj = tid & 15;
     const int eb = b0 + bb, ej = j0 + jj;
     const bool epi = tid < 256 && eb < B;
+    bool e_on = epi, nxt = has_next;                 // the epilogue's row is active in this step / has a next step
+    if constexpr (RAG) {
+        const int len = epi ? min(lens[eb], T) : 0;
+        e_on = s < len;
+        if (rev) { t = len - 1 - s; tp = t + 1; }
+        nxt = s < len - 1;
+    }
     float dh = 0.f, gi = 0.f, gf = 0.f, gc = 0.f, go = 0.f, c = 0.f, cp = 0.f, dcs = 0.f;
     const long long si = ((long long)d * B + eb) * H + ej;
-    if (epi) {
+    if (e_on) {
         dh = dh_out[((long long)eb * T + t) * HH + (long long)d * H + ej];
         const float* gp = gates + (((long long)eb * T + t) * ndir + d) * G4;
         gi = gp[ej]; gf = gp[H + ej]; gc = gp[2 * H + ej]; go = gp[3 * H + ej];
         c = c_out[((long long)eb * T + t) * HH + (long long)d * H + ej];
         if (s > 0) cp = c_out[((long long)eb * T + tp) * HH + (long long)d * H + ej];
-        if (has_next) dcs = dc_state[si];
+        if (nxt) dcs = dc_state[si];
     }
     if (has_next) {
         const int b = b0 + r16;
-        const float* ap = dgates + (((long long)(b < B ? b : 0) * T + tn) * ndir + d) * G4 + gate * H + q * NS + part * NSW;
+        bool a_on = b < B;                           // the tile row has a next step
+        int tna = tn;
+        if constexpr (RAG) {
+            const int len = b < B ? min(lens[b], T) : 0;
+            a_on = s < len - 1;
+            tna = a_on ? (rev ? len - 2 - s : s + 1) : 0;
+        }
+        const float* ap = dgates + (((long long)(a_on ? b : 0) * T + tna) * ndir + d) * G4 + gate * H + q * NS + part * NSW;
         const float* bp = UTpk + ((((long long)d * (H / 16) + jt) * 4 + gate) * 64 + lane) * NS + part * NSW;
         f32x4v acc = {0.f, 0.f, 0.f, 0.f};
         for (int s0 = 0; s0 < NSW; s0 += 16) {
             f32x4a av[4], bv[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                av[i] = *reinterpret_cast<const f32x4a*>(ap + s0 + 4 * i);
+                if (!RAG || a_on) av[i] = *reinterpret_cast<const f32x4a*>(ap + s0 + 4 * i);      // (RAG: dgates of an unfinished row is not read)
                 bv[i] = *reinterpret_cast<const f32x4a*>(bp + s0 + 4 * i);
             }
 #pragma unroll
             for (int i = 0; i < 16; ++i)
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(b < B ? av[i / 4][i % 4] : 0.f, bv[i / 4][i % 4], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a_on ? av[i / 4][i % 4] : 0.f, bv[i / 4][i % 4], acc, 0, 0, 0);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[wave][(q * 4 + r) * 16 + r16] = acc[r];
         __syncthreads();
     }
     if (!epi) return;
-    if (has_next) {
+    if constexpr (RAG) {
+        if (!e_on) {
+            float* dg = dgates + (((long long)eb * T + s) * ndir + d) * G4;
+            dg[ej] = 0.f; dg[H + ej] = 0.f; dg[2 * H + ej] = 0.f; dg[3 * H + ej] = 0.f;
+            return;
+        }
+    }
+    if (nxt) {
 #pragma unroll
         for (int w = 0; w < NW; ++w) dh += red[w][tid];
     }
     const float tc = tanhf(c);
     float dc = dh * go * (1.f - tc * tc);
-    if (has_next) dc += dcs;
+    if (nxt) dc += dcs;
     float* dg = dgates + (((long long)eb * T + t) * ndir + d) * G4;
     dg[ej] = dc * gc * gi * (1.f - gi);
     dg[H + ej] = dc * cp * gf * (1.f - gf);
@@ -670,15 +760,17 @@ extern "C" size_t ptts_lstm_bwd_workspace_bytes(int B, int T, int H, int ndir) {
     return ((size_t)2 * ndir * 4 * H * H + (size_t)ndir * B * H) * sizeof(float);
 }
 
-extern "C" int ptts_lstm_bwd(const float* dh_out, const float* U, const float* gates, const float* c_out,
-                             float* dgates, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir,
-                             int reverse, void* stream) {
-    PTTS_REQUIRE(dh_out && U && gates && c_out && dgates, "lstm_bwd: null tensor");
-    PTTS_REQUIRE(B > 0 && T > 0 && H > 0 && (ndir == 1 || ndir == 2), "lstm_bwd: bad dims");
-    PTTS_REQUIRE((size_t)LY * 4 * H * sizeof(float) <= 64 * 1024, "lstm_bwd: H=%d too large", H);
+// The launches of ptts_lstm_bwd; with rag = <const int* lens> those of ptts_lstm_bwd_ragged (the same paths, chosen the same way).
+template <class... R>
+static int lstm_bwd_run(const char* what, const float* dh_out, const float* U, const float* gates, const float* c_out,
+                        float* dgates, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir,
+                        int reverse, void* stream, R... rag) {
+    PTTS_REQUIRE(dh_out && U && gates && c_out && dgates, "%s: null tensor", what);
+    PTTS_REQUIRE(B > 0 && T > 0 && H > 0 && (ndir == 1 || ndir == 2), "%s: bad dims", what);
+    PTTS_REQUIRE((size_t)LY * 4 * H * sizeof(float) <= 64 * 1024, "%s: H=%d too large", what, H);
     const size_t need = ptts_lstm_bwd_workspace_bytes(B, T, H, ndir);
     if (!workspace || workspace_bytes < need) {
-        set_error("lstm_bwd: workspace %zu < %zu", workspace_bytes, need);
+        set_error("%s: workspace %zu < %zu", what, workspace_bytes, need);
         return PTTS_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -691,12 +783,12 @@ extern "C" int ptts_lstm_bwd(const float* dh_out, const float* U, const float* g
         hipLaunchKernelGGL(lstm_pack_u_bwd_kernel, dim3(1024), dim3(256), 0, st, U, UTpk, H, ndir);
         for (int s = T - 1; s >= 0; --s)
             if (w8)
-                hipLaunchKernelGGL(lstm_bwd_step_pk_kernel<8>, pgrid, dim3(512), 0, st, dh_out,
-                                   (const float*)UTpk, gates, c_out, dgates, dc_state, B, T, H, ndir, reverse, s);
+                hipLaunchKernelGGL((lstm_bwd_step_pk_kernel<8, R...>), pgrid, dim3(512), 0, st, dh_out,
+                                   (const float*)UTpk, gates, c_out, dgates, dc_state, B, T, H, ndir, reverse, s, rag...);
             else
-                hipLaunchKernelGGL(lstm_bwd_step_pk_kernel<4>, pgrid, dim3(256), 0, st, dh_out,
-                                   (const float*)UTpk, gates, c_out, dgates, dc_state, B, T, H, ndir, reverse, s);
-        return check_launch("lstm_bwd_pk");
+                hipLaunchKernelGGL((lstm_bwd_step_pk_kernel<4, R...>), pgrid, dim3(256), 0, st, dh_out,
+                                   (const float*)UTpk, gates, c_out, dgates, dc_state, B, T, H, ndir, reverse, s, rag...);
+        return check_launch(what);
     }
     const long long tot = (long long)ndir * 4 * H * H;
     int tb = (int)((tot + 255) / 256);
@@ -707,13 +799,31 @@ extern "C" int ptts_lstm_bwd(const float* dh_out, const float* U, const float* g
     if (H % 16 == 0) {
         dim3 mgrid(H / 16, (B + 15) / 16, ndir);
         for (int s = T - 1; s >= 0; --s)
-            hipLaunchKernelGGL(lstm_bwd_step_mfma_kernel, mgrid, dim3(256), 0, st, dh_out, (const float*)UT, gates,
-                               c_out, dgates, dc_state, B, T, H, ndir, reverse, s);
-        return check_launch("lstm_bwd_mfma");
+            hipLaunchKernelGGL(lstm_bwd_step_mfma_kernel<R...>, mgrid, dim3(256), 0, st, dh_out, (const float*)UT, gates,
+                               c_out, dgates, dc_state, B, T, H, ndir, reverse, s, rag...);
+        return check_launch(what);
     }
     for (int s = T - 1; s >= 0; --s) {
-        hipLaunchKernelGGL(lstm_bwd_step_kernel, grid, block, lds, st, dh_out, (const float*)UT, gates, c_out,
-                           dgates, dc_state, B, T, H, ndir, reverse, s);
+        if constexpr (sizeof...(R) != 0)
+            hipLaunchKernelGGL(lstm_bwd_step_ragged_kernel, grid, block, lds, st, dh_out, (const float*)UT, gates, c_out,
+                               dgates, dc_state, B, T, H, ndir, reverse, s, rag...);
+        else
+            hipLaunchKernelGGL(lstm_bwd_step_kernel, grid, block, lds, st, dh_out, (const float*)UT, gates, c_out,
+                               dgates, dc_state, B, T, H, ndir, reverse, s);
     }
-    return check_launch("lstm_bwd");
+    return check_launch(what);
+}
+
+extern "C" int ptts_lstm_bwd(const float* dh_out, const float* U, const float* gates, const float* c_out,
+                             float* dgates, void* workspace, size_t workspace_bytes, int B, int T, int H, int ndir,
+                             int reverse, void* stream) {
+    return lstm_bwd_run("lstm_bwd", dh_out, U, gates, c_out, dgates, workspace, workspace_bytes, B, T, H, ndir, reverse, stream);
+}
+
+extern "C" int ptts_lstm_bwd_ragged(const float* dh_out, const float* U, const float* gates, const float* c_out,
+                                    float* dgates, const int* lens, void* workspace, size_t workspace_bytes, int B, int T,
+                                    int H, int ndir, int reverse, void* stream) {
+    PTTS_REQUIRE(lens, "lstm_bwd_ragged: null lens");
+    return lstm_bwd_run("lstm_bwd_ragged", dh_out, U, gates, c_out, dgates, workspace, workspace_bytes, B, T, H, ndir, reverse,
+                        stream, lens);
 }

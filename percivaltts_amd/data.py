@@ -133,6 +133,10 @@ def croplen_weight(xs, w, thresh=0.5, cropmode='begend', cropsize=int(0.750 / 0.
 def batching(xs, length=None, lengthmax=None, padtype='randshift', outmask=False, rand=None):
     """Stack 2-D matrices into [B, length, feat] batches.  'randshift' takes a random window of `length` frames from
     every sample (np.random.randint, so the numpy seed makes it repeatable); 'padright' zero-pads on the right.
+    'randshiftpad' does both (masked training): `length` is the given one or the LONGEST sample's, capped by lengthmax; a
+    sample longer than that gives a random window, a shorter one all its frames, zero-padded on the right.  It takes one
+    np.random.randint(0, max(len - length, 0) + 1) draw per row, in row order, whatever the row's length, so the numbers a
+    batch consumes depend on its size alone.
     `rand` (optional, one uniform number in [0, 1) per sample): the shift of sample b is floor(rand[b] * (number of possible
     shifts)) instead of a fresh np.random.randint draw -- what data parallelism uses, so that a rank that loads only its
     shard of the files takes the same windows as the process that loads the whole batch (load_inoutset)."""
@@ -141,7 +145,7 @@ def batching(xs, length=None, lengthmax=None, padtype='randshift', outmask=False
     nb = len(xs[0])
     if length is None:
         lens = [xs[0][b].shape[0] for b in range(nb)]
-        length = max(lens) if padtype == 'padright' else min(lens)
+        length = max(lens) if padtype in ('padright', 'randshiftpad') else min(lens)
     if lengthmax is not None and length > lengthmax:
         length = lengthmax
     xbs = []
@@ -158,6 +162,9 @@ def batching(xs, length=None, lengthmax=None, padtype='randshift', outmask=False
                 shift = min(int(rand[b] * ((samplelen - length) + 1)), samplelen - length)
             else:
                 shift = np.random.randint(0, (samplelen - length) + 1)
+        elif padtype == 'randshiftpad':
+            nshift = max(samplelen - length, 0) + 1
+            shift = min(int(rand[b] * nshift), nshift - 1) if rand is not None else np.random.randint(0, nshift)
         for xi, x in enumerate(xs):
             seg = x[b][shift:shift + minlen]
             xbs[xi][b, :minlen, :] = seg.reshape(minlen, -1)
@@ -195,7 +202,7 @@ def _kept_len(wk, thresh, cropmode, cropsize):
 def batch_window_length(indir, outdir, outwdir, fid_lst, length=None, lengthmax=None, maskpadtype='padright', cropmode='begend',
                         thresh=0.5, cropsize=int(0.750 / 0.005)):
     """The window length T load_inoutset would choose for the batch `fid_lst` (reference data.py:297-322 -> croplen,
-    croplen_weight, batching: with length=None it is the min ('randshift') or max ('padright') of the cropped sample lengths,
+    croplen_weight, batching: with length=None it is the min ('randshift') or max ('padright', 'randshiftpad') of the cropped sample lengths,
     clipped by lengthmax), found WITHOUT reading the wide files: the frame counts of the inputs and outputs come from the file
     sizes, only the one-column time-weight files are read.  Data parallelism needs it before sharding: a rank that loads only its
     shard must window it to the GLOBAL batch's T -- the shard's own min / max can differ, and with it every random shift."""
@@ -218,24 +225,31 @@ def batch_window_length(indir, outdir, outwdir, fid_lst, length=None, lengthmax=
         n = min(frames(ipath, ishape, fid), frames(opath, oshape, fid), w.shape[0])
         wk = (w[:, 0] if w.ndim > 1 else w)[:n]
         lens.append(_kept_len(wk, thresh, cropmode, cropsize))
-    T = max(lens) if maskpadtype == 'padright' else min(lens)
+    T = max(lens) if maskpadtype in ('padright', 'randshiftpad') else min(lens)
     if lengthmax is not None and T > lengthmax:
         T = lengthmax
     return int(T)
 
 
 def load_inoutset(indir, outdir, outwdir, fid_lst, inouttimesync=True, length=None, lengthmax=None,
-                  maskpadtype='padright', cropmode='begend', verbose=0, rand=None):
+                  maskpadtype='padright', cropmode='begend', verbose=0, rand=None, outlengths=False):
     """Load one batch of inputs, outputs and time weights, cropped and windowed: X [B,T,ctx], Y [B,T,out], W [B,T,1]
     (reference data.py:297-322).  `rand`: see batching -- the per-sample uniforms of the random window shifts, drawn by the
-    caller for the WHOLE global batch so that every rank can load its shard of `fid_lst` alone."""
+    caller for the WHOLE global batch so that every rank can load its shard of `fid_lst` alone.  outlengths: also return
+    n [B] int32, the real frames of every row (min of the cropped length and T; the frames behind them are zero padding),
+    as a fourth value; time-synchronous sets only."""
+    if outlengths and not inouttimesync:
+        raise ValueError('outlengths needs inouttimesync=True')
     X = load(indir, fid_lst, verbose=verbose, label='Context labels: ')
     Y = load(outdir, fid_lst, verbose=verbose, label='Output features: ')
     W = load(outwdir, fid_lst, verbose=verbose, label='Time weights: ')
     if inouttimesync:
         X, Y, W = croplen([X, Y, W])
         [X, Y], W = croplen_weight([X, Y], W, cropmode=cropmode)
+        lens = [x.shape[0] for x in X]
         [X, Y, W], _ = batching([X, Y, W], length=length, lengthmax=lengthmax, padtype=maskpadtype, rand=rand)
+        if outlengths:
+            return X, Y, W, np.minimum(lens, X.shape[1]).astype(np.int32)
     else:
         X = addstop(X)
         Y, W = croplen([Y, W])
@@ -322,7 +336,7 @@ class DeviceCorpus(object):
         """The T of the batch `ids`: what batch_window_length finds for them, from the kept lengths (no file is touched)."""
         if length is None:
             lens = self.lens[self._utts(ids)]
-            length = lens.max() if padtype == 'padright' else lens.min()
+            length = lens.max() if padtype in ('padright', 'randshiftpad') else lens.min()
         if lengthmax is not None and length > lengthmax:
             length = lengthmax
         return int(length)
@@ -330,7 +344,8 @@ class DeviceCorpus(object):
     def plan(self, ids, length=None, lengthmax=None, padtype='randshift', rand=None):
         """(T, utt, shift, n) of the batch `ids` (int32 arrays [B]), exactly as batching chooses them: 'randshift' draws one
         np.random.randint(0, len - T + 1) per row, in row order -- the global numpy generator is left as load_inoutset leaves it
-        -- or takes floor(rand[b] * number of shifts); 'padright' draws nothing.  n[b] = min(len, T) real frames.  Host only."""
+        -- or takes floor(rand[b] * number of shifts); 'padright' draws nothing; 'randshiftpad' draws one
+        np.random.randint(0, max(len - T, 0) + 1) per row, a row shorter than T included.  n[b] = min(len, T) real frames.  Host only."""
         utt = self._utts(ids)
         T = self.window_length(utt, length, lengthmax, padtype)
         shift = np.zeros(len(utt), dtype=np.int32)
@@ -344,21 +359,27 @@ class DeviceCorpus(object):
                     raise ValueError('utterance {} has {} frames, fewer than the window of {}'.format(self.fid_lst[utt[b]], samplelen, T))
                 else:
                     shift[b] = min(int(rand[b] * ((samplelen - T) + 1)), samplelen - T)
+        elif padtype == 'randshiftpad':
+            for b, samplelen in enumerate(self.lens[utt]):
+                nshift = max(int(samplelen) - T, 0) + 1
+                shift[b] = min(int(rand[b] * nshift), nshift - 1) if rand is not None else np.random.randint(0, nshift)
         return T, utt.astype(np.int32), shift, n
 
-    def batch(self, ids, length=None, lengthmax=None, padtype='randshift', rand=None, rows=None, want_w=False):
+    def batch(self, ids, length=None, lengthmax=None, padtype='randshift', rand=None, rows=None, want_w=False, want_lengths=False):
         """The batch load_inoutset(..., fid_lst=ids, length, lengthmax, maskpadtype=padtype, rand) gives, as device tensors
         X [B,T,ctx], Y [B,T,out] (and W [B,T,1] with want_w): the plan, its three small tables uploaded asynchronously, one
         gather launch on the current stream.  rows=(lo, hi): only these rows of the planned batch (a rank's shard; the plan, and
-        with it every random draw, is the whole batch's)."""
+        with it every random draw, is the whole batch's).  want_lengths: n [B] (int32, on the host: the plan's real frames per
+        row) as the last value."""
         import torch
         from . import ops
         T, utt, shift, n = self.plan(ids, length, lengthmax, padtype, rand)
         if rows is not None:
             utt, shift, n = (a[rows[0]:rows[1]] for a in (utt, shift, n))
         srcs = [self.X, self.Y] + ([self.W] if want_w else [])
-        return tuple(ops.batch_windows(srcs, self._row_off_host, torch.from_numpy(np.ascontiguousarray(utt)), torch.from_numpy(np.ascontiguousarray(shift)),
-                                       torch.from_numpy(np.ascontiguousarray(n)), T, row_off_dev=self._row_off_dev))
+        out = tuple(ops.batch_windows(srcs, self._row_off_host, torch.from_numpy(np.ascontiguousarray(utt)), torch.from_numpy(np.ascontiguousarray(shift)),
+                                      torch.from_numpy(np.ascontiguousarray(n)), T, row_off_dev=self._row_off_dev))
+        return out + (np.ascontiguousarray(n),) if want_lengths else out
 
 
 # ---- evaluation helpers ----------------------------------------------------------------------------------
@@ -498,12 +519,14 @@ class BatchPrefetcher(object):
     reusable pinned buffer (a slot is rewritten only after its DMA completed) -- useful when the loader can fill such
     a buffer directly; for numpy arrays that already exist it measured slower than letting the runtime stage them.
 
+    host_items: positions of the batch tuple handed through unconverted, on the host (default: none).
+
     device=None (or a CPU device) gives the same iterator without pinning or streams (host tests).
     """
 
     _END = object()
 
-    def __init__(self, make_batch, n, device=None, depth=2, stage_pinned=False):
+    def __init__(self, make_batch, n, device=None, depth=2, stage_pinned=False, host_items=()):
         import threading
         try:
             import queue
@@ -517,6 +540,7 @@ class BatchPrefetcher(object):
         if self._cuda and self._device.index is None:
             self._device = torch.device('cuda', torch.cuda.current_device())
         self._stage = bool(stage_pinned)
+        self._host_items = frozenset(int(k) for k in host_items)
         self._q = queue.Queue(maxsize=self._depth)
         self._slots = [None] * (self._depth + 1)      # pinned buffers (+1: one is being filled while `depth` are queued)
         self._events = [None] * (self._depth + 1)
@@ -551,14 +575,20 @@ class BatchPrefetcher(object):
                 self.load_seconds += time.time() - t0
                 if not isinstance(arrays, (tuple, list)):
                     arrays = (arrays,)
+                # host_items: the positions of a batch that stay on the host as they are (the lengths of a 'randshiftpad' batch: the
+                # step uploads them and takes the number of real frames from them without asking the device)
+                ints = [k in self._host_items for k in range(len(arrays))]
                 if not self._cuda:
-                    item = tuple(torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)) for a in arrays)
+                    item = tuple(a if i else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)) for a, i in zip(arrays, ints))
                     self._q.put((item, None))
                     continue
                 slot = i % len(self._slots)
                 outs = []
                 with torch.cuda.stream(self._copy_stream):
                     for k, a in enumerate(arrays):
+                        if ints[k]:
+                            outs.append(a)
+                            continue
                         a = np.ascontiguousarray(a, dtype=np.float32)
                         d = torch.empty(a.shape, dtype=torch.float32, device=self._device)
                         if self._stage:
@@ -594,7 +624,8 @@ class BatchPrefetcher(object):
             cur = self._torch.cuda.current_stream(self._device)
             cur.wait_event(ev)
             for t in item:
-                t.record_stream(cur)       # allocated on the copy stream, consumed here
+                if self._torch.is_tensor(t):
+                    t.record_stream(cur)       # allocated on the copy stream, consumed here
         return item
 
     next = __next__

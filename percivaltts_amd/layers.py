@@ -57,20 +57,34 @@ def ragged_input_grad(memo):
     return memo is not None and bool(memo.get('lengths_input_grad', False))
 
 
+def ragged_train(memo):
+    """Masked training (memo['lengths_train'] = N beside memo['lengths']): N, the number of real frames of the batch (a host
+    int: sum of the lengths), or None.  In this mode gradients flow to the weights: the row masks, BatchNormalization and the
+    recurrences take their masked training forms (ops.affine_act_rows(train=True), ops.batchnorm_affine(lengths, count),
+    ops.lstm / ops.gru(lengths))."""
+    if memo is None or memo.get('lengths') is None or memo.get('lengths_train') is None:
+        return None
+    return int(memo['lengths_train'])
+
+
 def ragged_begin(memo, training, x):
     """The checks every ragged evaluation of a Model starts with; returns the lengths, or None for a dense pass."""
     lengths = ragged_lengths(memo)
     if lengths is not None:
         # a zero-padded batch with a length per row (see ops.affine_act_rows)
-        if training:
+        N = ragged_train(memo)
+        if training and N is None:
             raise ValueError('lengths are for inference: training=True is not supported')
-        ops.check_lengths(lengths, x.shape[0], x.shape[1], allow_grad=ragged_input_grad(memo))
+        if N is not None and not 1 <= N <= x.shape[0] * x.shape[1]:
+            raise ValueError('lengths_train={} real frames in a batch of {} x {}'.format(N, x.shape[0], x.shape[1]))
+        ops.check_lengths(lengths, x.shape[0], x.shape[1], allow_grad=ragged_input_grad(memo) or N is not None)
     return lengths
 
 
 def ragged_output(v, memo):
     """A result of a ragged evaluation as a tensor, its pad rows zero."""
-    return ops.affine_act_rows(v.tensor() if isinstance(v, LazyConcat) else v, ragged_lengths(memo), input_grad=ragged_input_grad(memo))
+    return ops.affine_act_rows(v.tensor() if isinstance(v, LazyConcat) else v, ragged_lengths(memo), input_grad=ragged_input_grad(memo),
+                               train=ragged_train(memo) is not None)
 
 
 def ragged_input(v, memo):
@@ -83,7 +97,7 @@ def ragged_input(v, memo):
     key = ('ragged_input', id(v))
     if key not in memo:
         memo[key] = (v, ops.affine_act_rows(v.tensor() if isinstance(v, LazyConcat) else v, lengths,
-                                            input_grad=ragged_input_grad(memo)))
+                                            input_grad=ragged_input_grad(memo), train=ragged_train(memo) is not None))
     return memo[key][1]
 
 
@@ -226,8 +240,9 @@ class Dense(Layer):
                     z = (z.view((k,) + tuple(y.shape)) + y).view(z.shape)
                 else:
                     z = y if z is None else z + y
-        elif getattr(self, 'bn_follows', False) and training and self.activation in (None, 'linear'):
-            # the BatchNormalization behind this layer takes its statistics from sums the product's launch leaves (ops._BNStats)
+        elif getattr(self, 'bn_follows', False) and training and self.activation in (None, 'linear') and ragged_lengths(memo) is None:
+            # the BatchNormalization behind this layer takes its statistics from sums the product's launch leaves (ops._BNStats);
+            # not under per-row lengths: those sums run over the pad frames too
             ops._BNStats.want, ops._BNStats.last = True, None
             try:
                 z = ops.dense(v, self.kernel, self.bias)
@@ -291,6 +306,14 @@ class BatchNormalization(Layer):
     def compute(self, vals, training, memo):
         z = to_tensor(vals[0])
         update = bool(training) and not (memo is not None and memo.get('freeze_bn_stats', False))
+        N = ragged_train(memo)
+        if training and N is not None:
+            # masked training: statistics over the real frames only, N for [B,T,C] and N*F for [B,T,F,C] values per channel
+            z = z.contiguous()
+            count = N * (z.numel() // (z.shape[0] * z.shape[1] * z.shape[-1]))
+            z, scale, shift = ops.batchnorm_affine(z, self.gamma, self.beta, self.moving_mean, self.moving_variance, True, update,
+                                                   self.fused4d, lengths=ragged_lengths(memo), count=count)
+            return Lazy(z, scale, shift, lrelu=False)
         z, scale, shift = ops.batchnorm_affine(z, self.gamma, self.beta, self.moving_mean, self.moving_variance,
                                                bool(training), update, self.fused4d)
         return Lazy(z, scale, shift, lrelu=False)
@@ -351,8 +374,10 @@ class Conv2D(Layer):
         v = ragged_input(vals[0], memo)
         if isinstance(v, LazyConcat):
             v = v.tensor()
-        if getattr(self, 'bn_follows', False) and training and self.activation in (None, 'linear') and self.bf16 is None:
-            # the BatchNormalization behind this layer takes its statistics from sums the convolution's launch leaves (ops._BNStats)
+        if getattr(self, 'bn_follows', False) and training and self.activation in (None, 'linear') and self.bf16 is None and \
+                ragged_lengths(memo) is None:
+            # the BatchNormalization behind this layer takes its statistics from sums the convolution's launch leaves (ops._BNStats);
+            # not under per-row lengths: those sums run over the pad frames too
             ops._BNStats.want, ops._BNStats.last = True, None
             try:
                 z = ops.conv2d(v, self.kernel, self.bias, self.dil_t, ops.PAD_CAUSAL if self.causal else ops.PAD_SAME, self.bf16)
@@ -438,6 +463,8 @@ class LSTM(Layer):
 
     def compute(self, vals, training, memo):
         x = to_tensor(vals[0] if not isinstance(vals[0], LazyConcat) else vals[0].tensor()).contiguous()
+        if ragged_train(memo) is not None and torch.is_grad_enabled():
+            return ops.lstm(x, self.kernel, self.recurrent_kernel, self.bias, lengths=ragged_lengths(memo))
         if ragged_lengths(memo) is not None:
             return ops.lstm_infer(x, self.kernel, self.recurrent_kernel, self.bias, ragged_lengths(memo))
         return ops.lstm(x, self.kernel, self.recurrent_kernel, self.bias)
@@ -464,6 +491,8 @@ class GRU(Layer):
 
     def compute(self, vals, training, memo):
         x = to_tensor(vals[0] if not isinstance(vals[0], LazyConcat) else vals[0].tensor()).contiguous()
+        if ragged_train(memo) is not None and torch.is_grad_enabled():
+            return ops.gru(x, self.kernel, self.recurrent_kernel, self.bias, lengths=ragged_lengths(memo))
         if ragged_lengths(memo) is not None:
             return ops.gru_infer(x, self.kernel, self.recurrent_kernel, self.bias, ragged_lengths(memo))
         return ops.gru(x, self.kernel, self.recurrent_kernel, self.bias)

@@ -2161,8 +2161,20 @@ class BatchNormTrainFn(torch.autograd.Function):
         return dz, dgamma, dbeta, None, None, None, None
 
 
-def batchnorm_affine(z, gamma, beta, moving_mean, moving_var, training, update_moving=True, unbiased_moving=False):
-    """Returns (z', scale, shift) such that BN(z) = scale*z' + shift; z' is z handed through the autograd node (training) or z itself."""
+def batchnorm_affine(z, gamma, beta, moving_mean, moving_var, training, update_moving=True, unbiased_moving=False,
+                     lengths=None, count=None):
+    """Returns (z', scale, shift) such that BN(z) = scale*z' + shift; z' is z handed through the autograd node (training) or z itself.
+    lengths, count (training only; masked training): z [B,T,..,C] is a zero-padded batch with lengths[b] real frames in row b, and
+    the statistics are taken over the `count` = N * (elements per frame) / C real values of every channel, N = sum_b lengths[b]."""
+    if training and lengths is not None:
+        if _SyncBN.world > 1:
+            raise ValueError('batchnorm_affine: per-row lengths and synchronised BatchNorm statistics do not go together')
+        B, T, C = z.shape[0], z.shape[1], z.shape[-1]
+        check_lengths(lengths, B, T, allow_grad=True)
+        if count is None or int(count) != count or not 2 <= count <= z.numel() // C:
+            raise ValueError('batchnorm_affine: count={!r} real values per channel (2 .. {} for this batch)'.format(count, z.numel() // C))
+        return BatchNormRowsTrainFn.apply(f32c(z.contiguous(), 'bn.z'), gamma, beta, moving_mean, moving_var, update_moving,
+                                          unbiased_moving, lengths, int(count))
     if training:
         return BatchNormTrainFn.apply(z, gamma, beta, moving_mean, moving_var, update_moving, unbiased_moving)
     C = z.shape[-1]
@@ -2211,6 +2223,11 @@ def affine_act(x, scale=None, shift=None, act=None, alpha=0.3):
 # (memo['lengths_input_grad'], evaluation of the critic's gradient penalty): there the mask is an autograd Function whose backward
 # is the masked gradient (ptts_affine_act_rows_bwd), so d sum_{t<len} D(x^)_b / d x^_b on the padded batch is the lone utterance's
 # gradient on its real frames and exactly zero behind them.  The recurrences refuse gradients in either mode.
+# Masked TRAINING is the third mode (memo['lengths_train'] = N, the number of real frames, beside memo['lengths']): gradients flow to the
+# weights.  The mask becomes AffineActRowsTrainFn (gradients for the input and the pending affine, differentiable once more with respect to
+# the incoming gradient), BatchNormalization takes its statistics over the real frames only (BatchNormRowsTrainFn), the recurrences walk
+# each row over its own length forward and backward (LSTMRowsFn, GRURowsFn), and the costs are means over the N real frames (masked_wlse,
+# masked_mean).  The gradient entering any layer is then exactly zero on pad frames, so every weight-gradient product runs unchanged.
 # ----------------------------------------------------------------------------------------------
 def check_lengths(lengths, B, T, allow_grad=False):
     """`lengths` must be an int32 device tensor [B]; the values (1 <= lengths[b] <= T) are the caller's to guarantee.
@@ -2255,20 +2272,213 @@ class AffineActRowsFn(torch.autograd.Function):
         return dx, None, None, None, None, None
 
 
-def affine_act_rows(v, lengths, act=None, alpha=0.3, input_grad=False):
+class AffineActRowsBwdFn(torch.autograd.Function):
+    """The backward of the masked affine + activation as a node of its own: (dx, dscale, dshift) from dy, the sums over the
+    real frames only (ptts_affine_act_rows_bwd_params; without a pending affine ptts_affine_act_rows_bwd and no sums).  dx is a
+    linear, diagonal map of dy, so its own backward with respect to dy is the same kernel applied to the incoming second-order
+    gradient: what the gradient penalty's sweep through the critic's masks needs.  x and shift are constants there (LeakyReLU
+    has no curvature) and the two sums carry no second-order gradient; a scale that wants its second-order share is refused
+    (NotImplementedError), not dropped."""
+    @staticmethod
+    def forward(ctx, dy, x, scale, shift, lengths, act, alpha):
+        dy = f32c(dy.contiguous(), 'affine_act_rows.dy')
+        B, T, C = x.shape[0], x.shape[1], x.shape[-1]
+        inner = x.numel() // (B * T)
+        dx = torch.empty_like(x)
+        ctx.save_for_backward(x, scale, shift, lengths)
+        ctx.cfg = (act, alpha)
+        if scale is None:
+            call('ptts_affine_act_rows_bwd', ptr(dy), ptr(x), None, None, ptr(dx), ptr(lengths), B, T, inner, C, act, alpha, stream())
+            return dx, None, None
+        dsums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
+        ws = _workspace(_hip.lib().ptts_colstats_rows_workspace_bytes(B, T, inner, C), x.device)
+        call('ptts_affine_act_rows_bwd_params', ptr(dy), ptr(x), ptr(scale), ptr(shift), ptr(dx), ptr(dsums), ptr(lengths),
+             ptr(ws), ws.numel(), B, T, inner, C, act, alpha, stream(), tag=(B, T, inner, C))
+        d32 = dsums.to(torch.float32)
+        dscale, dshift = d32[:C], d32[C:]
+        ctx.mark_non_differentiable(dscale, dshift)
+        return dx, dscale, dshift
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, u, _uscale, _ushift):
+        x, scale, shift, lengths = ctx.saved_tensors
+        act, alpha = ctx.cfg
+        if scale is not None and ctx.needs_input_grad[2]:
+            # dx = dy act' scale depends on the affine: a sweep that needs that share (a BatchNormalization under the gradient
+            # penalty) must not lose it silently
+            raise NotImplementedError('affine_act_rows: the second-order gradient with respect to a pending affine is not built; '
+                                      'the masked critic has to be free of BatchNormalization')
+        u = f32c(u.contiguous(), 'affine_act_rows.u')
+        B, T, C = x.shape[0], x.shape[1], x.shape[-1]
+        du = torch.empty_like(x)
+        call('ptts_affine_act_rows_bwd', ptr(u), ptr(x), ptr(scale), ptr(shift), ptr(du), ptr(lengths), B, T,
+             x.numel() // (B * T), C, act, alpha, stream())
+        return du, None, None, None, None, None, None
+
+
+class AffineActRowsTrainFn(torch.autograd.Function):
+    """affine_act_rows of masked training: gradients for x, scale and shift, through AffineActRowsBwdFn (so the gradient with
+    respect to x can be differentiated once more with respect to what came in from above)."""
+    @staticmethod
+    def forward(ctx, x, scale, shift, lengths, act, alpha):
+        ctx.save_for_backward(x, scale, shift, lengths)
+        ctx.cfg = (act, alpha)
+        return _affine_act_rows_raw(x, scale, shift, lengths, act, alpha)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, scale, shift, lengths = ctx.saved_tensors
+        act, alpha = ctx.cfg
+        dx, dscale, dshift = AffineActRowsBwdFn.apply(dy, x, scale, shift, lengths, act, alpha)
+        return dx, dscale, dshift, None, None, None
+
+
+def affine_act_rows(v, lengths, act=None, alpha=0.3, input_grad=False, train=False):
     """v [B,T,...,C], a tensor or a Lazy -> its pending affine and LeakyReLU (a plain tensor: `act`) applied and the frames
     t >= lengths[b] zeroed, in one pass (ptts_affine_act_rows).  Returns a new plain tensor.  `input_grad`: the input-gradient
-    mode -- gradients may be enabled and the result carries the masked gradient back to `v` (act none / lrelu)."""
+    mode -- gradients may be enabled and the result carries the masked gradient back to `v` (act none / lrelu).  `train`:
+    masked training -- gradients for `v` and for its pending affine, the sums taken over the real frames only."""
     lz = as_lazy(v)
     x = f32c(lz.z.contiguous(), 'affine_act_rows.x')
-    check_lengths(lengths, x.shape[0], x.shape[1], allow_grad=input_grad)
+    check_lengths(lengths, x.shape[0], x.shape[1], allow_grad=input_grad or train)
     if lz.lrelu:
         act, alpha = 'lrelu', lz.alpha
-    if input_grad and torch.is_grad_enabled():
+    if (input_grad or train) and torch.is_grad_enabled():
         if act not in (None, 'linear', 'lrelu'):
-            raise ValueError('affine_act_rows: the input-gradient mode knows no activation {!r}'.format(act))
-        return AffineActRowsFn.apply(x, lz.scale, lz.shift, lengths, ACT_CODES[act], alpha)
+            raise ValueError('affine_act_rows: no gradient through the activation {!r}'.format(act))
+        fn = AffineActRowsTrainFn if train else AffineActRowsFn
+        return fn.apply(x, lz.scale, lz.shift, lengths, ACT_CODES[act], alpha)
     return _affine_act_rows_raw(x, lz.scale, lz.shift, lengths, ACT_CODES[act], alpha)
+
+
+class BatchNormRowsTrainFn(torch.autograd.Function):
+    """BatchNormTrainFn over a zero-padded batch z [B,T,..,C] with a length per row (masked training): mean and biased variance
+    over the real frames only (ptts_colstats_rows; `count` values per channel, known on the host), the moving statistics updated
+    from them, and in the backward the statistics' share c0 + c2 z added on real frames only, +0 behind them
+    (ptts_axpby_cols_rows): the gradient that leaves the layer is zero on pad frames if the one that entered was.  Sums that the
+    producer of z left over all B*T rows (_BNStats) are never used here."""
+    @staticmethod
+    def forward(ctx, z, gamma, beta, moving_mean, moving_var, update_moving, unbiased_moving, lengths, count):
+        f32c(z, 'bn.z')
+        B, T, C = z.shape[0], z.shape[1], z.shape[-1]
+        inner = z.numel() // (B * T)
+        dev = z.device
+        scale, shift, mean, rstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(4))
+        ctx.gt = _Deferred.targets(gamma, beta)
+        ctx.count = count
+        sums = torch.empty(2 * C, dtype=torch.float64, device=dev)
+        ws = _workspace(_hip.lib().ptts_colstats_rows_workspace_bytes(B, T, inner, C), dev)
+        call('ptts_colstats_rows', ptr(z), ptr(lengths), B, T, inner, C, ptr(sums), ptr(ws), ws.numel(), stream(), tag=(B, T, inner, C))
+        call('ptts_bn_finalize', ptr(sums), count, ptr(gamma), ptr(beta), ptr(moving_mean), ptr(moving_var),
+             BN_EPS, BN_MOMENTUM, 1, 1 if update_moving else 0, 1 if unbiased_moving else 0, C,
+             ptr(scale), ptr(shift), ptr(mean), ptr(rstd), stream())
+        ctx.save_for_backward(z, gamma, mean, rstd, lengths)
+        return z.view_as(z), scale, shift
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dz_through, dscale, dshift):
+        z, gamma, mean, rstd, lengths = ctx.saved_tensors
+        B, T, C = z.shape[0], z.shape[1], z.shape[-1]
+        dev = z.device
+        dscale = dscale.contiguous() if dscale is not None else torch.zeros(C, dtype=torch.float32, device=dev)
+        dshift = dshift.contiguous() if dshift is not None else torch.zeros(C, dtype=torch.float32, device=dev)
+        c0 = torch.empty(C, dtype=torch.float32, device=dev)
+        c2 = torch.empty(C, dtype=torch.float32, device=dev)
+        gt = ctx.gt
+        if gt[0] is not None and gt[1] is not None and _Deferred.live() and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
+            call('ptts_bn_bwd_coefs_acc', ptr(dscale), ptr(dshift), ptr(mean), ptr(rstd), ptr(gamma), ctx.count, C,
+                 ptr(gt[0]), ptr(gt[1]), ptr(c0), ptr(c2), stream())
+            _Deferred.note_stream()
+            dgamma = dbeta = None
+        else:
+            dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+            dbeta = torch.empty(C, dtype=torch.float32, device=dev)
+            call('ptts_bn_bwd_coefs', ptr(dscale), ptr(dshift), ptr(mean), ptr(rstd), ptr(gamma), ctx.count, C,
+                 ptr(dgamma), ptr(dbeta), ptr(c0), ptr(c2), stream())
+        dz = None
+        if ctx.needs_input_grad[0]:
+            dz_through = f32c(dz_through.contiguous(), 'bn.dz') if dz_through is not None else torch.zeros_like(z)
+            dz = torch.empty_like(z)
+            call('ptts_axpby_cols_rows', ptr(dz_through), ptr(z), ptr(c2), ptr(c0), ptr(dz), ptr(lengths), B, T,
+                 z.numel() // (B * T), C, stream())
+        return dz, dgamma, dbeta, None, None, None, None, None, None
+
+
+class MaskedMeanFn(torch.autograd.Function):
+    """sign * the mean of v [B,T,...] over the N real frames of the batch: the per-row means (ptts_rows_mean) combined on the
+    device as sum_b out[b] n[b] / N (ptts_rows_combine); the gradient sign / (N * inner) on real frames, +0 behind them."""
+    @staticmethod
+    def forward(ctx, v, lengths, N, sign):
+        f32c(v, 'masked_mean.v')
+        B, T = v.shape[0], v.shape[1]
+        rows = torch.empty(B, dtype=torch.float32, device=v.device)
+        out = torch.empty(1, dtype=torch.float32, device=v.device)
+        call('ptts_rows_mean', ptr(v), ptr(lengths), B, T, v.numel() // (B * T), float(sign), ptr(rows), stream())
+        call('ptts_rows_combine', ptr(rows), ptr(lengths), B, T, N, ptr(out), stream())
+        ctx.save_for_backward(lengths)
+        ctx.cfg = (tuple(v.shape), N, float(sign))
+        return out.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, up):
+        lengths, = ctx.saved_tensors
+        shape, N, sign = ctx.cfg
+        B, T = shape[0], shape[1]
+        dv = torch.empty(shape, dtype=torch.float32, device=up.device)
+        call('ptts_rows_mean_bwd', ptr(f32c(up.contiguous().view(1), 'masked_mean.up')), ptr(lengths), B, T,
+             dv.numel() // (B * T), sign, N, ptr(dv), stream())
+        return dv, None, None, None
+
+
+class MaskedWLSEFn(torch.autograd.Function):
+    """sum_{b, t<n[b], d} (y - yhat)^2 w[d] / (N D): WLSEFn over the real frames of a zero-padded batch (ptts_wlse_rows,
+    ptts_rows_combine; backward ptts_wlse_rows_bwd)."""
+    @staticmethod
+    def forward(ctx, yhat, y, w, lengths, N):
+        f32c(yhat, 'masked_wlse.yhat'); f32c(y, 'masked_wlse.y'); f32c(w)
+        assert yhat.shape == y.shape and y.dim() == 3 and (w is None or w.numel() == y.shape[-1])
+        B, T, D = y.shape
+        rows = torch.empty(B, dtype=torch.float32, device=y.device)
+        out = torch.empty(1, dtype=torch.float32, device=y.device)
+        call('ptts_wlse_rows', ptr(y), ptr(yhat), ptr(w), ptr(lengths), B, T, D, ptr(rows), None, stream())
+        call('ptts_rows_combine', ptr(rows), ptr(lengths), B, T, N, ptr(out), stream())
+        ctx.save_for_backward(yhat, y, w, lengths)
+        ctx.N = N
+        return out.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, up):
+        yhat, y, w, lengths = ctx.saved_tensors
+        B, T, D = y.shape
+        d = torch.empty_like(yhat)
+        call('ptts_wlse_rows_bwd', ptr(y), ptr(yhat), ptr(w), ptr(f32c(up.contiguous().view(1), 'masked_wlse.up')), ptr(lengths),
+             B, T, D, ctx.N, ptr(d), stream())
+        return d, None, None, None, None
+
+
+def _real_frames(N, B, T):
+    N = int(N)
+    if not 1 <= N <= B * T:
+        raise ValueError('N={} real frames in a batch of {} x {}'.format(N, B, T))
+    return N
+
+
+def masked_mean(v, lengths, N, sign=1.0):
+    """sign * sum_{b, t<lengths[b]} v / (N * inner) of v [B,T,...], N = sum_b lengths[b] as a host int: the Wasserstein terms of
+    masked training.  With every length equal to T it is wasserstein(v, sign)."""
+    check_lengths(lengths, v.shape[0], v.shape[1], allow_grad=True)
+    return MaskedMeanFn.apply(v.contiguous(), lengths, _real_frames(N, v.shape[0], v.shape[1]), float(sign))
+
+
+def masked_wlse(y, yhat, w, lengths, N):
+    """sum_{b, t<lengths[b], d} (y - yhat)^2 w[d] / (N * D) of y, yhat [B,T,D] (w [D] or None), N = sum_b lengths[b] as a host
+    int: the least-squares cost of masked training, with a gradient for yhat.  With every length equal to T it is wlse(yhat, y, w)."""
+    check_lengths(lengths, y.shape[0], y.shape[1], allow_grad=True)
+    return MaskedWLSEFn.apply(yhat.contiguous(), y.contiguous(), w, lengths, _real_frames(N, y.shape[0], y.shape[1]))
 
 
 def rows_mean(v, lengths, sign=1.0):
@@ -2628,41 +2838,98 @@ class LSTMFn(torch.autograd.Function):
         call('ptts_lstm_bwd', ptr(dh), ptr(U), ptr(gates), ptr(c), ptr(dgates), ptr(ws), ws.numel(),
              B, T, H, ndir, ctx.reverse, stream())
         _lstm_mark('bwd1')
-        M = B * T
-        dx = dW = dU = db = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            gemm_raw(dgates, W, dx, M, In, ndir * G4, transB=1, ldb=ndir * G4)
-            # dx is what the rest of the backward pass waits for; the weight-gradient products below (0.5 ms at [64,400], H = 256) are
-            # not.  The point on this stream where dx is complete is published: a caller that runs this node on a side stream
-            # (optimizertts_wgan.generator_forward_early) lets the main stream wait for THIS event instead of for the whole node.
-            global lstm_dx_ready
-            lstm_dx_ready = (dx.data_ptr(), torch.cuda.current_stream().record_event())
-        if ctx.needs_input_grad[1]:
-            dW = torch.empty_like(W)
-            gemm_raw(x, dgates, dW, In, ndir * G4, M, transA=1, lda=In, rows_per_seg=M)
-        if ctx.needs_input_grad[3]:
-            db = _colsum_f32(dgates.view(M, ndir * G4))
-        if ctx.needs_input_grad[2]:
-            # dU[d] = sum_t h_prev[d]^T . dgates[d]; h_prev is h shifted by one step in the walking direction
-            hprev = _h_prev(h, ndir, H, ctx.reverse)
-            dU = torch.empty_like(U)
-            for d in range(ndir):
-                gemm_raw(hprev.view(M, ndir * H)[:, d * H:], dgates.view(M, ndir * G4)[:, d * G4:], dU[d],
-                         H, G4, M, transA=1, lda=ndir * H, rows_per_seg=M, ldb=ndir * G4)
-        gt = ctx.gt
-        if _Deferred.live() and \
-                all(t is not None or g is None for t, g in zip(gt, (dW, dU, db))):
-            for t, g in zip(gt, (dW, dU, db)):
-                if g is not None:
-                    t.add_(g.view(t.shape))
-            _Deferred.note_stream()             # flush_weight_grads() joins this stream before the optimiser reads the buffer
-            dW = dU = db = None
-        return dx, dW, dU, db, None
+        return _lstm_products(ctx, x, W, U, h, dgates) + (None,)
 
 
-def lstm(v, W, U, b, reverse=False):
-    return LSTMFn.apply(as_tensor(v).contiguous(), W, U, b, reverse)
+def _lstm_products(ctx, x, W, U, h, dgates):
+    """(dx, dW, dU, db) of an LSTM node out of the gate gradients: the products behind ptts_lstm_bwd / ptts_lstm_bwd_ragged."""
+    B, T, In = x.shape
+    ndir, H, G4 = U.shape
+    M = B * T
+    dx = dW = dU = db = None
+    if ctx.needs_input_grad[0]:
+        dx = torch.empty_like(x)
+        gemm_raw(dgates, W, dx, M, In, ndir * G4, transB=1, ldb=ndir * G4)
+        # dx is what the rest of the backward pass waits for; the weight-gradient products below (0.5 ms at [64,400], H = 256) are
+        # not.  The point on this stream where dx is complete is published: a caller that runs this node on a side stream
+        # (optimizertts_wgan.generator_forward_early) lets the main stream wait for THIS event instead of for the whole node.
+        global lstm_dx_ready
+        lstm_dx_ready = (dx.data_ptr(), torch.cuda.current_stream().record_event())
+    if ctx.needs_input_grad[1]:
+        dW = torch.empty_like(W)
+        gemm_raw(x, dgates, dW, In, ndir * G4, M, transA=1, lda=In, rows_per_seg=M)
+    if ctx.needs_input_grad[3]:
+        db = _colsum_f32(dgates.view(M, ndir * G4))
+    if ctx.needs_input_grad[2]:
+        # dU[d] = sum_t h_prev[d]^T . dgates[d]; h_prev is h shifted by one step in the walking direction
+        hprev = _h_prev(h, ndir, H, ctx.reverse)
+        dU = torch.empty_like(U)
+        for d in range(ndir):
+            gemm_raw(hprev.view(M, ndir * H)[:, d * H:], dgates.view(M, ndir * G4)[:, d * G4:], dU[d],
+                     H, G4, M, transA=1, lda=ndir * H, rows_per_seg=M, ldb=ndir * G4)
+    gt = ctx.gt
+    if _Deferred.live() and \
+            all(t is not None or g is None for t, g in zip(gt, (dW, dU, db))):
+        for t, g in zip(gt, (dW, dU, db)):
+            if g is not None:
+                t.add_(g.view(t.shape))
+        _Deferred.note_stream()             # flush_weight_grads() joins this stream before the optimiser reads the buffer
+        dW = dU = db = None
+    return dx, dW, dU, db
+
+
+def _lstm_rows_launch(x, W, U, b, lengths, reverse, store):
+    """The launches of the ragged LSTM forward: (h, c, gates); c and gates (None without `store`) hold real frames only."""
+    f32c(x, 'lstm.x'); f32c(W); f32c(U); f32c(b)
+    B, T, In = x.shape
+    ndir, H, G4 = U.shape
+    assert G4 == 4 * H and W.shape == (In, ndir * G4)
+    dev = x.device
+    xproj = torch.empty((B, T, ndir * G4), dtype=torch.float32, device=dev)
+    h = torch.empty((B, T, ndir * H), dtype=torch.float32, device=dev)
+    c = torch.empty((B, T, ndir * H), dtype=torch.float32, device=dev) if store else None
+    gates = torch.empty((B, T, ndir * G4), dtype=torch.float32, device=dev) if store else None
+    gemm_raw(x, W, xproj, B * T, ndir * G4, In, bias=b)
+    carry = (ndir * B * H * 4 + 255) // 256 * 256
+    ws = _workspace(carry + _hip.lib().ptts_lstm_fwd_workspace_bytes(B, T, H, ndir), dev)
+    call('ptts_lstm_fwd_ragged', ptr(xproj), ptr(U), ptr(h), ptr(gates), ptr(c), ptr(lengths), ptr(ws), ws.numel(), B, T, H, ndir,
+         int(reverse), stream())
+    return h, c, gates
+
+
+class LSTMRowsFn(torch.autograd.Function):
+    """LSTMFn over a zero-padded batch with a length per row (masked training): every row walks its own length, forward
+    (ptts_lstm_fwd_ragged with gates and cell states stored) and backward (ptts_lstm_bwd_ragged).  The gate gradients are +0 on
+    pad frames and h is 0 there, so the products of LSTMFn give the weight gradients unchanged."""
+    @staticmethod
+    def forward(ctx, x, W, U, b, reverse, lengths):
+        h, c, gates = _lstm_rows_launch(x, W, U, b, lengths, reverse, True)
+        ctx.save_for_backward(x, W, U, h, c, gates, lengths)
+        ctx.reverse = int(reverse)
+        ctx.gt = _Deferred.targets(W, U, b)
+        return h
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh):
+        x, W, U, h, c, gates, lengths = ctx.saved_tensors
+        B, T, In = x.shape
+        ndir, H, G4 = U.shape
+        dh = dh.contiguous()
+        dgates = torch.empty_like(gates)
+        ws = _workspace(_hip.lib().ptts_lstm_bwd_workspace_bytes(B, T, H, ndir), x.device)
+        call('ptts_lstm_bwd_ragged', ptr(dh), ptr(U), ptr(gates), ptr(c), ptr(dgates), ptr(lengths), ptr(ws), ws.numel(),
+             B, T, H, ndir, ctx.reverse, stream())
+        return _lstm_products(ctx, x, W, U, h, dgates) + (None, None)
+
+
+def lstm(v, W, U, b, reverse=False, lengths=None):
+    """lengths (int32 device [B]): masked training over a zero-padded batch, every row over its own length."""
+    x = as_tensor(v).contiguous()
+    if lengths is not None:
+        check_lengths(lengths, x.shape[0], x.shape[1], allow_grad=True)
+        return LSTMRowsFn.apply(x, W, U, b, reverse, lengths)
+    return LSTMFn.apply(x, W, U, b, reverse)
 
 
 def lstm_infer(x, W, U, b, lengths, reverse=False):
@@ -2670,20 +2937,8 @@ def lstm_infer(x, W, U, b, lengths, reverse=False):
     each row's real frames what lstm() gives for that row alone, zero behind them.  No autograd node; neither the gates nor the
     cell states are stored."""
     x = as_tensor(x).contiguous()
-    f32c(x, 'lstm.x'); f32c(W); f32c(U); f32c(b)
-    B, T, In = x.shape
-    ndir, H, G4 = U.shape
-    assert G4 == 4 * H and W.shape == (In, ndir * G4)
-    check_lengths(lengths, B, T)
-    dev = x.device
-    xproj = torch.empty((B, T, ndir * G4), dtype=torch.float32, device=dev)
-    h = torch.empty((B, T, ndir * H), dtype=torch.float32, device=dev)
-    gemm_raw(x, W, xproj, B * T, ndir * G4, In, bias=b)
-    carry = (ndir * B * H * 4 + 255) // 256 * 256
-    ws = _workspace(carry + _hip.lib().ptts_lstm_fwd_workspace_bytes(B, T, H, ndir), dev)
-    call('ptts_lstm_fwd_ragged', ptr(xproj), ptr(U), ptr(h), None, None, ptr(lengths), ptr(ws), ws.numel(), B, T, H, ndir,
-         int(reverse), stream())
-    return h
+    check_lengths(lengths, x.shape[0], x.shape[1])
+    return _lstm_rows_launch(x, W, U, b, lengths, reverse, False)[0]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -2724,54 +2979,98 @@ class GRUFn(torch.autograd.Function):
         ws = _workspace(_hip.lib().ptts_gru_bwd_workspace_bytes(B, T, H, ndir), dev)
         call('ptts_gru_bwd', ptr(dh), ptr(U), ptr(h), ptr(gates), ptr(dgates), ptr(ws), ws.numel(), B, T, H, ndir, stream(),
              tag=(B, T, H, ndir))
-        dg2 = dgates.view(M, ndir * G3)
-        dx = dW = dU = db = None
-        if ctx.needs_input_grad[0]:
-            # dx = sum_d dgates_d . W_d^T, the second direction added onto the first
-            dx = torch.empty_like(x)
-            for d in range(ndir):
-                gemm_raw(dg2[:, d * G3:], W[d], dx, M, In, G3, lda=ndir * G3, transB=1, ldb=G3, accumulate=int(d > 0))
-        if ctx.needs_input_grad[1]:
-            dW = torch.empty_like(W)
-            for d in range(ndir):
-                gemm_raw(x, dg2[:, d * G3:], dW[d], In, G3, M, transA=1, lda=In, rows_per_seg=M, ldb=ndir * G3)
-        if ctx.needs_input_grad[3]:
-            db = _colsum_f32(dg2).view(ndir, G3)
-        if ctx.needs_input_grad[2]:
-            # dU_zr[d] = sum_t h_{t-1}^T . da_zr,  dU_h[d] = sum_t (r * h_{t-1})^T . da_h
-            hprev = _h_prev(h, ndir, H).view(M, ndir * H)
-            rh2 = rh.view(M, ndir * H)
-            dU = torch.empty_like(U)
-            for d in range(ndir):
-                gemm_raw(hprev[:, d * H:], dg2[:, d * G3:], dU[d][:, :2 * H], H, 2 * H, M, transA=1, lda=ndir * H,
-                         rows_per_seg=M, ldb=ndir * G3, ldc=G3)
-                gemm_raw(rh2[:, d * H:], dg2[:, d * G3 + 2 * H:], dU[d][:, 2 * H:], H, H, M, transA=1, lda=ndir * H,
-                         rows_per_seg=M, ldb=ndir * G3, ldc=G3)
-        return dx, dW, dU, db
+        return _gru_products(ctx, x, W, U, h, rh, dgates)
 
 
-def gru(v, W, U, b):
-    return GRUFn.apply(as_tensor(v).contiguous(), W, U, b)
+def _gru_products(ctx, x, W, U, h, rh, dgates):
+    """(dx, dW, dU, db) of a GRU node out of the gate gradients: the products behind ptts_gru_bwd / ptts_gru_bwd_ragged."""
+    B, T, In = x.shape
+    ndir, H, G3 = U.shape
+    M = B * T
+    dg2 = dgates.view(M, ndir * G3)
+    dx = dW = dU = db = None
+    if ctx.needs_input_grad[0]:
+        # dx = sum_d dgates_d . W_d^T, the second direction added onto the first
+        dx = torch.empty_like(x)
+        for d in range(ndir):
+            gemm_raw(dg2[:, d * G3:], W[d], dx, M, In, G3, lda=ndir * G3, transB=1, ldb=G3, accumulate=int(d > 0))
+    if ctx.needs_input_grad[1]:
+        dW = torch.empty_like(W)
+        for d in range(ndir):
+            gemm_raw(x, dg2[:, d * G3:], dW[d], In, G3, M, transA=1, lda=In, rows_per_seg=M, ldb=ndir * G3)
+    if ctx.needs_input_grad[3]:
+        db = _colsum_f32(dg2).view(ndir, G3)
+    if ctx.needs_input_grad[2]:
+        # dU_zr[d] = sum_t h_{t-1}^T . da_zr,  dU_h[d] = sum_t (r * h_{t-1})^T . da_h
+        hprev = _h_prev(h, ndir, H).view(M, ndir * H)
+        rh2 = rh.view(M, ndir * H)
+        dU = torch.empty_like(U)
+        for d in range(ndir):
+            gemm_raw(hprev[:, d * H:], dg2[:, d * G3:], dU[d][:, :2 * H], H, 2 * H, M, transA=1, lda=ndir * H,
+                     rows_per_seg=M, ldb=ndir * G3, ldc=G3)
+            gemm_raw(rh2[:, d * H:], dg2[:, d * G3 + 2 * H:], dU[d][:, 2 * H:], H, H, M, transA=1, lda=ndir * H,
+                     rows_per_seg=M, ldb=ndir * G3, ldc=G3)
+    return dx, dW, dU, db
+
+
+def _gru_rows_launch(x, W, U, b, lengths, store):
+    """The launches of the ragged GRU forward: (h, gates, rh); gates and rh (None without `store`) hold real frames only, and
+    rh zeros behind them: it is an operand of the recurrent weight gradient's product."""
+    f32c(x, 'gru.x'); f32c(W); f32c(U); f32c(b)
+    B, T, In = x.shape
+    ndir, H, G3 = U.shape
+    assert G3 == 3 * H and W.shape == (ndir, In, G3) and b.shape == (ndir, G3)
+    dev, M = x.device, B * T
+    xproj = torch.empty((B, T, ndir * G3), dtype=torch.float32, device=dev)
+    h = torch.empty((B, T, ndir * H), dtype=torch.float32, device=dev)
+    gates = torch.empty((B, T, ndir * G3), dtype=torch.float32, device=dev) if store else None
+    rh = torch.zeros((B, T, ndir * H), dtype=torch.float32, device=dev) if store else None
+    xp2 = xproj.view(M, ndir * G3)
+    for d in range(ndir):
+        gemm_raw(x, W[d], xp2[:, d * G3:], M, G3, In, ldc=ndir * G3, bias=b[d])
+    ws = _workspace(_hip.lib().ptts_gru_fwd_workspace_bytes(B, T, H, ndir) + 2 * ndir * B * H * 4, dev)
+    call('ptts_gru_fwd_ragged', ptr(xproj), ptr(U), ptr(h), ptr(gates), ptr(rh), ptr(lengths), ptr(ws), ws.numel(), B, T, H, ndir,
+         stream(), tag=(B, T, H, ndir))
+    return h, gates, rh
+
+
+class GRURowsFn(torch.autograd.Function):
+    """GRUFn over a zero-padded batch with a length per row (masked training): ptts_gru_fwd_ragged with gates and r*h stored,
+    ptts_gru_bwd_ragged, and GRUFn's products (the gate gradients are +0 on pad frames, h and r*h are 0 there)."""
+    @staticmethod
+    def forward(ctx, x, W, U, b, lengths):
+        h, gates, rh = _gru_rows_launch(x, W, U, b, lengths, True)
+        ctx.save_for_backward(x, W, U, h, gates, rh, lengths)
+        return h
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh):
+        x, W, U, h, gates, rh, lengths = ctx.saved_tensors
+        B, T, In = x.shape
+        ndir, H, G3 = U.shape
+        dh = dh.contiguous()
+        dgates = torch.empty_like(gates)
+        ws = _workspace(_hip.lib().ptts_gru_bwd_workspace_bytes(B, T, H, ndir), x.device)
+        call('ptts_gru_bwd_ragged', ptr(dh), ptr(U), ptr(h), ptr(gates), ptr(dgates), ptr(lengths), ptr(ws), ws.numel(), B, T, H,
+             ndir, stream(), tag=(B, T, H, ndir))
+        return _gru_products(ctx, x, W, U, h, rh, dgates) + (None,)
+
+
+def gru(v, W, U, b, lengths=None):
+    """lengths (int32 device [B]): masked training over a zero-padded batch, every row over its own length."""
+    x = as_tensor(v).contiguous()
+    if lengths is not None:
+        check_lengths(lengths, x.shape[0], x.shape[1], allow_grad=True)
+        return GRURowsFn.apply(x, W, U, b, lengths)
+    return GRUFn.apply(x, W, U, b)
 
 
 def gru_infer(x, W, U, b, lengths):
     """GRU forward over a zero-padded batch with a length per row (ptts_gru_fwd_ragged); see lstm_infer."""
     x = as_tensor(x).contiguous()
-    f32c(x, 'gru.x'); f32c(W); f32c(U); f32c(b)
-    B, T, In = x.shape
-    ndir, H, G3 = U.shape
-    assert G3 == 3 * H and W.shape == (ndir, In, G3) and b.shape == (ndir, G3)
-    check_lengths(lengths, B, T)
-    dev, M = x.device, B * T
-    xproj = torch.empty((B, T, ndir * G3), dtype=torch.float32, device=dev)
-    h = torch.empty((B, T, ndir * H), dtype=torch.float32, device=dev)
-    xp2 = xproj.view(M, ndir * G3)
-    for d in range(ndir):
-        gemm_raw(x, W[d], xp2[:, d * G3:], M, G3, In, ldc=ndir * G3, bias=b[d])
-    ws = _workspace(_hip.lib().ptts_gru_fwd_workspace_bytes(B, T, H, ndir) + 2 * ndir * B * H * 4, dev)
-    call('ptts_gru_fwd_ragged', ptr(xproj), ptr(U), ptr(h), None, None, ptr(lengths), ptr(ws), ws.numel(), B, T, H, ndir,
-         stream(), tag=(B, T, H, ndir))
-    return h
+    check_lengths(lengths, x.shape[0], x.shape[1])
+    return _gru_rows_launch(x, W, U, b, lengths, False)[0]
 
 
 # ----------------------------------------------------------------------------------------------

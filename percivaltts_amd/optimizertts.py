@@ -230,6 +230,7 @@ class OptimizerTTS:
             rndidxb = np.split(rndidx, nbbatches)
             costs_tra_batches, load_times, train_times = [], [], []
             world, rank = getattr(self, 'world', 1), getattr(self, 'rank', 0)
+            masked = self.cfg.train_batch_padtype == 'randshiftpad'
             # data parallelism: a rank reads only the files of ITS shard of the global batch.  The random
             # window shifts are drawn for the whole batch, up front and in batch order (every rank holds the same numpy RNG
             # state), as uniforms that load_inoutset turns into shifts: W ranks take the windows one process would take.
@@ -248,33 +249,38 @@ class OptimizerTTS:
                     lo, hi = parallel.shard_batch(len(ids), world, rank)
                     ids, rnd = ids[lo:hi], shift_rand[batchid][lo:hi]
                 fid_lst_trab = [fid_lst_tra[bidx] for bidx in ids]
-                X_trab, Y_trab, W_trab = data.load_inoutset(
+                loaded = data.load_inoutset(
                     indir, outdir, wdir, fid_lst_trab, length=length,
                     lengthmax=self.cfg.train_batch_lengthmax, maskpadtype=self.cfg.train_batch_padtype,
-                    cropmode=self.cfg.train_batch_cropmode, rand=rnd)
-                return X_trab, Y_trab                        # already this rank's shard: only it was read and crosses PCIe
+                    cropmode=self.cfg.train_batch_cropmode, rand=rnd, outlengths=masked)
+                if masked:                                   # (X, Y, n): n [B] int32, the real frames of every row, stays on the host
+                    return loaded[0], loaded[1], loaded[3]
+                return loaded[0], loaded[1]                  # already this rank's shard: only it was read and crosses PCIe
 
             def gather_batch(batchid, rndidxb=rndidxb, shift_rand=shift_rand):
                 # the same windows out of the resident corpus: the plan of the GLOBAL batch (its T, its shifts -- drawn here, in batch
                 # order, or taken from shift_rand), this rank's rows of it
                 return corpus.batch(rndidxb[batchid], length=self.cfg.train_batch_length, lengthmax=self.cfg.train_batch_lengthmax,
                                     padtype=self.cfg.train_batch_padtype, rand=shift_rand[batchid] if world > 1 else None,
-                                    rows=parallel.shard_batch(len(rndidxb[batchid]), world, rank) if world > 1 else None)
+                                    rows=parallel.shard_batch(len(rndidxb[batchid]), world, rank) if world > 1 else None,
+                                    want_lengths=masked)
 
             if corpus is not None:
                 prefetch = _DeviceBatches(gather_batch, nbbatches)
             else:
                 # batches are loaded, pinned and copied to the device two ahead of the step that consumes them
-                prefetch = data.BatchPrefetcher(make_batch, nbbatches, device=self.device, depth=2)
-            for batchid, (X_trab, Y_trab), nxt in _with_next(self._closing(prefetch)):
+                prefetch = data.BatchPrefetcher(make_batch, nbbatches, device=self.device, depth=2, host_items=(2,) if masked else ())
+            for batchid, batch, nxt in _with_next(self._closing(prefetch)):
+                X_trab, Y_trab = batch[0], batch[1]
                 t0 = time.time()
-                self.hint_next_batch(*(nxt if nxt is not None else (None, None)))     # (the prefetcher has it on the device already)
+                self.hint_next_batch(*(nxt[:2] if nxt is not None else (None, None)))     # (the prefetcher has it on the device already)
                 print_tty('\r    Training batch {}/{}'.format(1 + batchid, nbbatches))
                 load_times.append(prefetch.load_seconds - sum(load_times))
                 print_tty(' (iter load: {:.6f}s); training '.format(load_times[-1]))
 
                 t1 = time.time()
-                cost_tra = self.train_on_batch(batchid, X_trab, Y_trab)
+                # masked training ('randshiftpad'): the batch carries the real frames of every row
+                cost_tra = self.train_on_batch(batchid, X_trab, Y_trab, lengths=batch[2]) if masked else self.train_on_batch(batchid, X_trab, Y_trab)
                 train_times.append(time.time() - t1)
 
                 if cost_tra is not None:
@@ -410,10 +416,22 @@ class OptimizerTTS:
         cfg.train_lse_adam_epsilon_log10 = -8
         return cfg
 
+    def _check_masked_training(self):
+        """cfg.train_batch_padtype == 'randshiftpad' (masked training on padded batches with a length per row) goes with one rank
+        and per-rank BatchNorm statistics only; called by prepare() once self.world is known."""
+        if self.cfg.train_batch_padtype != 'randshiftpad':
+            return
+        if getattr(self, 'world', 1) > 1:
+            raise ValueError("cfg.train_batch_padtype = 'randshiftpad' trains on one rank; {} ranks are running (data parallelism): "
+                             'use another train_batch_padtype or one rank'.format(self.world))
+        if bool(getattr(self.cfg, 'train_sync_batchnorm', False)):
+            raise ValueError("cfg.train_batch_padtype = 'randshiftpad' and cfg.train_sync_batchnorm = True do not go together: unset one of the two")
+
     def prepare(self):
         print('    Prepare LSE training')
         self.device = self._model.to_device()
         self.world, self.rank = parallel.init()
+        self._check_masked_training()
         self.opti = KerasAdam(self._model.kerasmodel, self.device, lr=10 ** self.cfg.train_lse_learningrate_log10,
                               beta_1=self.cfg.train_lse_adam_beta1, beta_2=self.cfg.train_lse_adam_beta2,
                               epsilon=10 ** self.cfg.train_lse_adam_epsilon_log10)
@@ -445,12 +463,26 @@ class OptimizerTTS:
             return a.to(device=self.device, dtype=torch.float32)
         return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32).to(self.device)
 
-    def train_on_batch(self, batchid, X_trab, Y_trab):
+    def _lengths_to_dev(self, lengths, B, T):
+        """(int32 device tensor [B], N) of the host array of real frames per row; N = their sum, a host int."""
+        n = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        if n.shape[0] != B or n.min() < 1 or n.max() > T:
+            raise ValueError('lengths {} do not fit a batch of {} rows of {} frames'.format(n.tolist(), B, T))
+        return torch.from_numpy(n).to(self.device, non_blocking=True), int(n.sum())
+
+    def train_on_batch(self, batchid, X_trab, Y_trab, lengths=None):
+        """lengths (host ints [B]; the driver passes them with cfg.train_batch_padtype = 'randshiftpad' only): masked training --
+        the frames t >= lengths[b] of X and Y are zero padding and take no part in statistics, cost or gradients."""
         X_trab, Y_trab = self._local_shard(X_trab, Y_trab)
         X, Y = self._to_dev(X_trab), self._to_dev(Y_trab)
         self.opti.zero_grad()
-        pred = self._model.kerasmodel(X, training=True)
-        loss = lse_loss(Y, pred)
+        if lengths is not None:
+            n, N = self._lengths_to_dev(lengths, X.shape[0], X.shape[1])
+            pred = self._model.kerasmodel(X, training=True, memo={'lengths': n, 'lengths_train': N})
+            loss = ops.masked_wlse(Y, pred, None, n, N)
+        else:
+            pred = self._model.kerasmodel(X, training=True)
+            loss = lse_loss(Y, pred)
         loss.backward()
         self.opti.step(parallel.allreduce_sum_(self.opti.flat.grad))
         return float(np.sqrt(float(loss.item())))   # a cost related to the generator's error, whatever the loss type

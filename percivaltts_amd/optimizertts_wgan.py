@@ -184,6 +184,11 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
             raise ValueError('cfg.train_validation_batch_size = {} needs a critic that takes per-row lengths, and the Conv2DStack of '
                              'cfg.arch_critic_bf16 = {!r} does not: unset one of the two'.format(
                                  cfg.train_validation_batch_size, getattr(self.critic.cfgarch, 'arch_critic_bf16', None)))
+        if cfg.train_batch_padtype == 'randshiftpad' and (self._critic_stack_layers() or getattr(self.critic.cfgarch, 'arch_critic_bf16', None)):
+            raise ValueError("cfg.train_batch_padtype = 'randshiftpad' (masked training) runs the critic in fp32 with per-row lengths, "
+                             'which the bf16 forms of cfg.arch_critic_bf16 = {!r} do not take: unset one of the two'.format(
+                                 getattr(self.critic.cfgarch, 'arch_critic_bf16', None)))
+        self._check_masked_training()        # ... nor with more than one rank or cfg.train_sync_batchnorm
         generator = self._model.kerasmodel
         critic = self.critic.model
         critic.to(dev)
@@ -270,9 +275,78 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
             return t.reshape(t.shape[0], t.shape[1], F)
         return t[:, :, 1:1 + F]
 
-    def critic_loss(self, X, Y, alpha=None, training=True, fake=None):
+    def _masked(self, lengths, B, T):
+        """(n, N) of `lengths`: host ints [B] (uploaded here), or the pair (int32 device tensor [B], N) itself."""
+        if isinstance(lengths, tuple):
+            return lengths
+        return self._lengths_to_dev(lengths, B, T)
+
+    def _critic_loss_masked(self, X, Y, alpha, training, lengths):
+        """critic_loss under the rule of masked training ("Ragged training"): the frozen generator's sample with
+        BatchNorm statistics over the real frames and no moving update; real, fake and x^ through the critic with the row masks in
+        front of every convolution and on the scores; the Wasserstein terms as means over the N real frames; the penalty from the
+        per-sample norm over [T, spec], whose pad frames hold exact zeros, as ever.  Plain order: three B-row evaluations over one
+        evaluation of the context branch, no stacked pair."""
+        n, N = self._masked(lengths, X.shape[0], X.shape[1])
+        self._wait_update('generator')
+        with torch.no_grad():
+            gen = self._gen_spec if self._gen_spec is not None else self._model.kerasmodel
+            fake = gen(X, training=training, memo={'freeze_bn_stats': True, 'lengths': n, 'lengths_train': N})
+        self._wait_update('critic')
+        B = Y.shape[0]
+        node = getattr(self.critic, 'node_spec_in', None)
+        at_slice = node is not None and getattr(self.cfg, 'train_wgan_feed_spectra', True)
+        if at_slice:
+            real, fake = self._spec_of(Y).contiguous(), self._spec_of(fake).contiguous()
+        else:
+            real = Y
+            if fake.shape[-1] != Y.shape[-1]:
+                full = torch.zeros_like(Y)
+                full[:, :, 1:1 + fake.shape[-1]] = fake
+                fake = full
+        if alpha is None:
+            alpha = torch.rand(B, device=Y.device, dtype=torch.float32)
+        x_hat = ops.gp_interpolate(real, fake, alpha.reshape(-1).contiguous()).detach().requires_grad_(True)     # zero on the pad frames, as both its sources
+        memo = {'lengths': n, 'lengths_train': N}
+        if at_slice:
+            valid, fake_v, v_hat = self.critic_net.forward_multi_at(node, [real, fake, x_hat], {self.critic.input_ctx: X},
+                                                                    training=training, memo=memo)
+        else:
+            valid, fake_v, v_hat = self.critic_net.forward_multi(0, [real, fake, x_hat], [X], training=training, memo=memo)
+        l_valid = ops.masked_mean(valid, n, N, -1.0)
+        l_fake = ops.masked_mean(fake_v, n, N, +1.0)
+        gp = gradient_penalty_loss(None, v_hat, x_hat)
+        if getattr(self, 'debug_keep_x_hat', False):      # (off: nothing of a step outlives it for inspection's sake)
+            self._x_hat = x_hat
+        total = l_valid + l_fake + float(self.cfg.train_wgan_pg_lambda) * gp
+        return total, (l_valid, l_fake, gp)
+
+    def _generator_loss_masked(self, X, Y, training, lengths):
+        """generator_loss under the rule of masked training: one masked forward, the critic on its spectral columns, the Wasserstein
+        and least-squares terms as means over the N real frames."""
+        n, N = self._masked(lengths, X.shape[0], X.shape[1])
+        memo = {'lengths': n, 'lengths_train': N}
+        self._wait_update('generator')
+        pred = self._model.kerasmodel(X, training=training, memo=memo)
+        self._wait_update('critic')
+        cnode = getattr(self.critic, 'node_spec_in', None)
+        if cnode is not None and getattr(self.cfg, 'train_wgan_feed_spectra', True):
+            valid = self.critic_net.forward_multi_at(cnode, [self._spec_of(pred).contiguous()], {self.critic.input_ctx: X},
+                                                     training=training, memo=dict(memo))[0]
+        else:
+            valid = self.critic_net(pred, X, training=training, memo=dict(memo))
+        l_w = ops.masked_mean(valid, n, N, -1.0)
+        if self._errtype == 'WGAN':
+            return l_w, (l_w, None)
+        l_ls = ops.masked_wlse(Y, pred, self._w_ls, n, N)
+        return self._wgan_weight * l_w + l_ls, (l_w, l_ls)
+
+    def critic_loss(self, X, Y, alpha=None, training=True, fake=None, lengths=None):
         """Total critic loss and its three parts on device tensors X [B,T,ctx], Y [B,T,out]; `fake`: G(x) as [B,T,out] or just its
-        spectral columns [B,T,spec]."""
+        spectral columns [B,T,spec].  lengths (host ints [B], or (int32 device tensor, their sum)): masked training on a zero-padded
+        batch, see _critic_loss_masked (`fake` is not taken then: the sample is drawn with the masked statistics)."""
+        if lengths is not None:
+            return self._critic_loss_masked(X, Y, alpha, training, lengths)
         if fake is None:
             fake = self._fake_sample(X, training)
         self._wait_update('critic')
@@ -399,7 +473,9 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         spec = kl.to_tensor(values[id(self._model.node_spec)]).detach()
         return spec.reshape(spec.shape[0], spec.shape[1], -1)
 
-    def generator_loss(self, X, Y, training=True, pre=None):
+    def generator_loss(self, X, Y, training=True, pre=None, lengths=None):
+        if lengths is not None:
+            return self._generator_loss_masked(X, Y, training, lengths)
         m = self._model.kerasmodel
         node_spec = getattr(self._model, 'node_spec', None)
         self._wait_update('generator')
@@ -492,7 +568,14 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
             run()
             self._pending[kind] = self._comm.record_event()
 
-    def _critic_grads(self, X, Y, alpha=None, fake=None):
+    def _critic_grads(self, X, Y, alpha=None, fake=None, lengths=None):
+        if lengths is not None:
+            self._wait_update('critic')
+            self.critic_opti.zero_grad()
+            with ops.deferred_weight_grads():
+                total, _ = self.critic_loss(X, Y, alpha, training=True, lengths=lengths)
+                total.backward()
+            return total.detach()
         if fake is None:
             fake = self._fake_sample(X, True)      # first: it does not need the critic's weights (a pending update may still run)
         self._wait_update('critic')
@@ -502,12 +585,12 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
             total.backward()
         return total.detach()
 
-    def critic_step(self, X, Y, alpha=None, fake=None):
-        total = self._critic_grads(X, Y, alpha, fake)
+    def critic_step(self, X, Y, alpha=None, fake=None, lengths=None):
+        total = self._critic_grads(X, Y, alpha, fake, lengths)
         self._update('critic')
         return total
 
-    def _generator_grads(self, X, Y, pre=None):
+    def _generator_grads(self, X, Y, pre=None, lengths=None):
         self._wait_update('generator')
         if pre is None:
             self.gen_opti.zero_grad()          # (a hoisted forward may already have run a side branch's backward: device_step zeroed before it)
@@ -518,7 +601,7 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
                 if pre is not None:
                     ops.deferred_attach(self._gen_deferred)
                     self._gen_deferred = None
-                total, _ = self.generator_loss(X, Y, training=True, pre=pre)
+                total, _ = self.generator_loss(X, Y, training=True, pre=pre, lengths=lengths)
                 ops._lstm_mark('loss')
                 cuts = self._gen_cuts if pre is not None else None
                 if cuts:
@@ -534,8 +617,8 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
             for p in cps: p.requires_grad_(True)
         return total.detach()
 
-    def generator_step(self, X, Y, pre=None):
-        total = self._generator_grads(X, Y, pre)
+    def generator_step(self, X, Y, pre=None, lengths=None):
+        total = self._generator_grads(X, Y, pre, lengths)
         self._update('generator')
         return total
 
@@ -691,12 +774,14 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
             self._update(kind)
         return out
 
-    def _use_graph(self, X, kind=None, Y=None):
+    def _use_graph(self, X, kind=None, Y=None, lengths=None):
         """cfg.train_wgan_hipgraph: True / False; 'auto' = replay the step as a hipGraph when it is launch-bound (few frames:
         about 1 000 launches of a few microseconds each against 8 ms of host enqueue time at the reference's B = 10); 'tune' = as
         'auto' below the frame threshold, above it measured per step kind on the first batch (`_tune_graph`): a step whose kernels
         are short against the host's enqueue time (the bf16 critic step) replays faster than it launches, one that lives on
         overlapping streams (the generator step's BLSTM branch) does not."""
+        if lengths is not None:         # masked training: eager steps only
+            return False
         pin = getattr(self.cfg, 'train_wgan_graph_' + kind, None) if kind in ('critic', 'generator') else None
         if pin is not None:             # 'on' / 'off' (bench.py --graph-critic / --graph-generator): the timed program is pinned,
             return pin in (True, 'on')  # not left to the wall-clock comparison of 'tune' (two runs of one tree time ONE program)
@@ -716,7 +801,7 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         generator step's forward is launched ONE BATCH AHEAD (cfg.train_wgan_generator_lookahead, see device_step)."""
         self._next_batch = None if X_next is None else (X_next, Y_next)
 
-    def device_step(self, batchid, X, Y, alpha=None, nxt=None):
+    def device_step(self, batchid, X, Y, alpha=None, nxt=None, lengths=None):
         """One `train_on_batch` worth of device work on resident tensors; returns (critic_loss, generator_loss|None)
         as device scalars.
 
@@ -741,6 +826,21 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
             if bool(split) != ops._C1Split.enabled:
                 ops.conv1d_split(split)
             ops.dense_split(split)
+        if lengths is not None:
+            # masked training (cfg.train_batch_padtype = 'randshiftpad'): the plain order, critic step and then the generator step
+            # when due -- no hipGraph, no hoisted or look-ahead forward, no stacked pair, no reuse of the context convolution
+            ahead, self._ahead, self._next_batch = self._ahead, None, None
+            if ahead is not None:
+                self._drop_ahead(ahead)
+            ops.conv1d_cache(False)
+            lengths = self._masked(lengths, X.shape[0], X.shape[1])
+            assert not self._use_graph(X, 'critic', Y, lengths)
+            lc = self.critic_step(X, Y, alpha, lengths=lengths)
+            lg = None
+            if gen_too:
+                lg = self.generator_step(X, Y, lengths=lengths)
+                self.generator_updates += 1
+            return lc, lg
         graph_c = self._use_graph(X, 'critic', Y)
         graph_g = gen_too and self._use_graph(X, 'generator', Y)
         use_graph = graph_c or graph_g
@@ -824,9 +924,13 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         self.gen_opti.zero_grad()
 
     # ---- the reference's hooks --------------------------------------------------------------------------------------
-    def train_on_batch(self, batchid, X_trab, Y_trab):
+    def train_on_batch(self, batchid, X_trab, Y_trab, lengths=None):
         X_trab, Y_trab = self._local_shard(X_trab, Y_trab)
         X, Y = self._to_dev(X_trab), self._to_dev(Y_trab)
+        if lengths is not None:
+            lc, lg = self.device_step(batchid, X, Y, lengths=lengths)
+            self.costs_tra_critic_batches.append_device(lc)
+            return None if lg is None else float(lg.item())
         nb = self._next_batch
         if nb is not None and torch.is_tensor(nb[0]) and nb[0].is_cuda:
             nb = (self._to_dev(nb[0]), self._to_dev(nb[1]))           # (identity for resident float32 tensors: the objects stay the same)
