@@ -230,8 +230,11 @@ int ptts_conv2d_mfma_debug(int flags, void* stamp_buf);
  * fp32 accumulation, fp32 master weights and weight gradients).  Replaces the L x (kl.Conv2D 5x5 + kl.LeakyReLU) of
  * networks_critic.py:64-70 -- forward, TF's Conv2DBackpropInput / Conv2DBackpropFilter chains behind it, and the
  * second-order sweep of K.gradients(K.gradients(...)) (optimizertts_wgan.py:53-68) -- with the maps between the layers
- * held in the LDS: a workgroup carries a tile of 32 time rows x all F <= 68 bins through all L <= 8 layers (two halo rows
- * per layer and side, recomputed).  Channels: cin0 (1) -> 4 -> ... -> 4.
+ * held in the LDS: a workgroup carries a tile of 32 time rows x up to 68 bins through all L <= 8 layers (two halo rows
+ * per layer and side, recomputed).  Spectra wider than 68 bins run in overlapping frequency blocks of one tile each: block
+ * origins and the cuts between the bins that blocks own are multiples of 8 bins, a block owns no bin within 2 L bins of a
+ * cut (recomputed by its neighbour), and only owned bins are stored or summed (ptts_conv2d_chain_blocks tells the plan).
+ * F <= 68 is one block: the kernels without any block state.  Channels: cin0 (1) -> 4 -> ... -> 4.
  *   maps     a_1 .. a_{L-1} = lrelu(z_l), POST-activation, [L-1][B][T][FP][4] bf16, FP = F rounded up to even, pad bin zero
  *            (ptts_conv2d_chain_map_elems(B, T, F) elements each);   a_last = a_L [B][T][F][4] bf16 (what the dense layers read)
  *   tables   ptts_conv2d_chain_tables_bytes() bytes: the banded operand tables of all layers, both directions (bf16 copies
@@ -245,7 +248,13 @@ int ptts_conv2d_mfma_debug(int flags, void* stamp_buf);
  *   _second    the backward of _bwd_data w.r.t. d_last and the kernels: u0 = d/d(g0) [B][T][F] fp32 -> out = d/d(d_last)
  *              [B][T][F][4] (fp32 / bf16) and the partial sums of dW_l (rows as _bwd, bias entries zero)
  * ------------------------------------------------------------------------------------- */
+/* 1 when the stack has a chain kernel: 2 <= F <= 1024 bins (run on the device up to 200), 1 <= L <= 8 layers, 1 <= Cin0 <= 4,
+ * C = 4 filters of 5 x 5 */
 int ptts_conv2d_chain_supported(int F, int L, int Cin0, int C, int KT, int KF);
+/* host only (tests, tools): the frequency blocks of a launch.  Block k computes bins [origin[k], origin[k] + min(68, F - origin[k]))
+ * and owns [own_lo[k], own_hi[k]).  Returns the block count (the arrays receive the first `cap` blocks and may be NULL), or 0
+ * when ptts_conv2d_chain_supported says no. */
+int ptts_conv2d_chain_blocks(int F, int L, int* origin, int* own_lo, int* own_hi, int cap);
 int ptts_conv2d_chain_debug(void* stamp_buf);   /* measurement hook of tools/chain_probe.py: 256 x 32 uint64 phase stamps, NULL = off */
 size_t ptts_conv2d_chain_tables_bytes(void);
 size_t ptts_conv2d_chain_partials_bytes(int L);

@@ -6,9 +6,11 @@
 // (optimizertts_wgan.py:53-68, K.gradients of a gradient) and that pass's own backward (the second-order sweep).  The layer-wise
 // kernels of conv2d_mfma.hip spend 71 launches per critic step on it and move every map between HBM and the LDS two to three
 // times; with bf16 maps the matrix-pipe work of a layer is 1.2 us, so the launches' prologues and the map traffic are all that is
-// left (0.106 of the HBM roofline).  Here a workgroup owns a tile of TR = 32 time rows of one utterance over the
-// whole frequency axis (F <= 68: one block of 17 bin groups), carries it through ALL layers with a halo of two rows per layer and
-// side (recomputed: the products are cheap, the bytes are not), and touches HBM only for what the algorithm must keep:
+// left (0.106 of the HBM roofline).  Here a workgroup owns a tile of TR = 32 time rows of one utterance over a
+// block of up to 68 bins (17 bin groups: F <= 68 is ONE block, the whole frequency axis; wider spectra run in overlapping frequency
+// blocks, see Blk and make_plan), carries it through ALL layers with a halo of two rows per layer and side -- and, at a cut between
+// two blocks, of two bins per layer -- (recomputed: the products are cheap, the bytes are not), and touches HBM only for what the
+// algorithm must keep:
 //     forward        reads the spectrum, writes the L activation maps a_l = lrelu(z_l) (the backward's masks and operands);
 //     backward       reads dL/da_L and the maps, keeps the gradient maps in the LDS, accumulates dW / db of all layers in
 //                    registers (a wave per kernel row, 8 accumulators per layer) -- writes per-workgroup partial sums only;
@@ -24,7 +26,7 @@
 // step (4 -> 1) run through the same instruction with the missing channels zero.  Weight gradients: K = 16 rows x 2 adjacent bin
 // groups, both operands read transposed out of the row-major LDS tiles by ds_read_b64_tr_b16.
 //
-// LDS tile: rows of 37 sixteen-byte units (bins -2 .. 71, four bf16 channels each), the unit order of conv2d_mfma.hip (two low
+// LDS tile: rows of 37 sixteen-byte units (bins -2 .. 71 of the block, four bf16 channels each), the unit order of conv2d_mfma.hip (two low
 // bits of the unit index swapped, lanes 4..11 of an MFMA column own the even rows): conflict-free ds_read_b128 fragments.
 // Internal maps lie in HBM as [B][T][FP][4] bf16 with FP = F rounded up to even and the pad bin zero, so that a row is a whole
 // number of 16-byte units; the last map a_L is written unpadded ([B][T][F][4]): the dense layers read it as [B*T, 4F].
@@ -129,6 +131,37 @@ struct Geo {
     float alpha;
     long long map_stride;              // elements between the internal maps of consecutive layers: B * T * FP * 4
 };
+// the frequency blocks of a launch (make_plan): blocks per time tile (1: the whole axis), bins between block origins, bins between
+// a cut and the nearest owned bin (both multiples of 8).  Kept out of Geo and at the END of the kernels' argument structures: the
+// one-block kernels, which never read it, keep the argument layout they had.
+struct FBlocks { int n, stride, halo; };
+
+// A tile's frequency block.  Inside a tile every bin index is LOCAL (bin 0 <-> global bin f_org) and the block is worked on as an
+// image of F bins: what lies outside is zero.  At an image edge that is the zero padding; at a CUT (f_org > 0, or f_org + F short
+// of the image) it is wrong, and the error advances two bins per layer, forward and backward alike -- the bins the block OWNS,
+// [own_lo, own_hi), lie at least 2 L bins inside every cut, and only owned bins are stored to HBM or enter a sum.  The owned ranges
+// of a time tile's blocks partition the frequency axis.  One block (BLK = false): f_org = 0, F and ng the image's, everything owned.
+struct Blk { int f_org, F, FP, ng, own_lo, own_hi; };
+
+// the block as the helpers of a tile see it: the image's geometry with the block's bins (T and the pitches stay the image's)
+__device__ __forceinline__ Geo block_geo(const Geo& g, const Blk& k) { Geo r = g; r.F = k.F; r.ng = k.ng; return r; }
+
+template <bool BLK>
+__device__ __forceinline__ Blk tile_of(const Geo& g, const FBlocks& p, int tile, int& b, int& t0) {
+    Blk k;
+    if (!BLK) {
+        b = tile / g.ntt; t0 = (tile - b * g.ntt) * TR;
+        k.f_org = 0; k.F = g.F; k.FP = g.FP; k.ng = g.ng; k.own_lo = 0; k.own_hi = g.F;
+    } else {
+        const int bt = tile / p.n, fb = tile - bt * p.n;
+        b = bt / g.ntt; t0 = (bt - b * g.ntt) * TR;
+        k.f_org = fb * p.stride;
+        k.F = min(4 * NGMAX, g.F - k.f_org); k.FP = (k.F + 1) & ~1; k.ng = (k.F + 3) >> 2;
+        k.own_lo = fb ? p.halo : 0;
+        k.own_hi = fb == p.n - 1 ? k.F : p.stride + p.halo;
+    }
+    return k;
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // tile loaders (global -> registers -> LDS; the loads of the next step's tile are in flight while this step multiplies)
@@ -149,24 +182,29 @@ __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" :
 template <int NS, int NT>
 struct MapDma {
     int pk[NS];        // tile-independent: row << 16 | element offset of the unit inside a map row, or -1 (no data)
-    __device__ __forceinline__ void init(const Geo& g) {
+    // fp: padded bins of a row that can hold data (one block: the image's FP; frequency blocks: those of a full block, a shorter
+    // last block is cut off in issue())
+    __device__ __forceinline__ void init(int fp) {
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             const int idx = threadIdx.x + k * NT;
             const int r = (int)__umulhi((unsigned)idx, 116080198u /* ceil(2^32 / 37) */), p = idx - r * RSU;
             const int u = unit_pos(p);
-            pk[k] = (r << 16) | ((u >= 1 && 2 * u <= g.FP) ? (2 * u - 2) * C : 0xffff);
+            pk[k] = (r << 16) | ((u >= 1 && 2 * u <= fp) ? (2 * u - 2) * C : 0xffff);
         }
     }
-    // rows [t_org, t_org + nrows) of utterance b -> tile (row 0 <-> t_org)
-    __device__ __forceinline__ void issue(const u16* __restrict__ map, const Geo& g, int b, int t_org, int nrows, const u16* tile, const u16* zeros) const {
+    // rows [t_org, t_org + nrows) of utterance b, bins of block kb -> tile (row 0 <-> t_org).  A block's origin is a multiple of
+    // 8 bins = 64 bytes: every source unit stays 16-byte aligned.
+    template <bool BLK>
+    __device__ __forceinline__ void issue(const u16* __restrict__ map, const Geo& g, const Blk& kb, int b, int t_org, int nrows, const u16* tile, const u16* zeros) const {
         const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        const u16* base = map + (long long)(b * g.T + t_org) * g.FP * C;
+        const u16* base = map + (long long)(b * g.T + t_org) * g.FP * C + kb.f_org * C;
+        const int ulim = kb.FP * C;                         // a shorter last block; (no data: 0xffff, beyond the limit)
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             if ((k * NT + wave * 64) >= nrows * RSU) break;                  // wave-uniform: nothing of this instruction is needed
             const int r = pk[k] >> 16, uo = pk[k] & 0xffff, t = t_org + r;
-            const u16* src = (uo != 0xffff && (unsigned)t < (unsigned)g.T) ? base + (long long)r * g.FP * C + uo : zeros;
+            const u16* src = ((BLK ? uo < ulim : uo != 0xffff) && (unsigned)t < (unsigned)g.T) ? base + (long long)r * g.FP * C + uo : zeros;
             if (r < nrows) dma16(src, tile + (size_t)(k * NT + wave * 64) * 8);
         }
     }
@@ -175,6 +213,7 @@ struct MapDma {
 template <int NS, int NT>
 struct X0Pref {
     float v[NS];
+    // (frequency blocks: x points at the block's bin 0 in the image's row 0, g is the block's geometry)
     __device__ __forceinline__ void load(const float* __restrict__ x, long long ld, const Geo& g, int b, int t_org, int nrows) {
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
@@ -196,7 +235,8 @@ struct X0Pref {
 };
 
 // own rows of an LDS tile -> a padded map in HBM: whole rows of FP / 2 units (the pad bin is zero in the tile).  The slots of a
-// thread (tile-independent) are worked out once per kernel; all reads are issued before the first store.
+// thread (tile-independent) are worked out once per kernel; all reads are issued before the first store.  Frequency blocks: the
+// owned units of a row only (cuts are multiples of 8 bins: whole units), slots worked out per tile by init_block().
 template <int NT>
 struct RowStore {
     static constexpr int NS = (TR * (4 * NGMAX / 2) + NT - 1) / NT;
@@ -214,6 +254,19 @@ struct RowStore {
             go_[k] = (r * g.FP + (2 * u - 2)) * C;
         }
     }
+    // the owned units of block kb; go_ is relative to the block's bin 0 in the own rows' first row
+    __device__ __forceinline__ void init_block(const Geo& g, const Blk& kb) {
+        const int u0 = kb.own_lo >> 1, upr = ((kb.own_hi + 1) >> 1) - u0, total = TR * upr;
+        const unsigned magic = 0xffffffffu / (unsigned)upr + 1u;            // ceil(2^32 / upr), upr >= 1
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int idx = threadIdx.x + k * NT;
+            const int r = upr > 1 ? (int)__umulhi((unsigned)idx, magic) : idx, u = idx - r * upr + 1 + u0;
+            r_[k] = idx < total ? r : (1 << 20);
+            lo_[k] = r * RS + unit_pos(u) * 8;
+            go_[k] = (r * g.FP + (2 * u - 2)) * C;
+        }
+    }
     __device__ __forceinline__ void run(const u16* tile_own, u16* __restrict__ map_own, int nrows) const {
         bf16x8 v[NS];
 #pragma unroll
@@ -223,14 +276,26 @@ struct RowStore {
     }
 };
 // ... -> the unpadded last map [B][T][F][4]: eight bytes per lane, consecutive lanes consecutive pixels
-template <int NT>
-__device__ __forceinline__ void store_rows_plain(const u16* tile, int tile_torg, u16* __restrict__ map, const Geo& g, int b, int t0) {
-    const int nrows = min(TR, g.T - t0), total = nrows * g.F;
-    const unsigned magic_f = (unsigned)(((1ULL << 32) + (unsigned)g.F - 1) / (unsigned)g.F);
-    u16* dst = map + (long long)(b * g.T + t0) * g.F * C;
-    for (int idx = threadIdx.x; idx < total; idx += NT) {
-        const int r = g.F > 1 ? (int)__umulhi((unsigned)idx, magic_f) : idx, f = idx - r * g.F;
-        *reinterpret_cast<bf16x4*>(dst + (size_t)idx * C) = *reinterpret_cast<const bf16x4*>(tile + (t0 + r - tile_torg) * RS + bin_off(f + 2));
+template <int NT, bool BLK>
+__device__ __forceinline__ void store_rows_plain(const u16* tile, int tile_torg, u16* __restrict__ map, const Geo& g, const Blk& kb, int b, int t0) {
+    if (!BLK) {
+        const int nrows = min(TR, g.T - t0), total = nrows * g.F;
+        const unsigned magic_f = (unsigned)(((1ULL << 32) + (unsigned)g.F - 1) / (unsigned)g.F);
+        u16* dst = map + (long long)(b * g.T + t0) * g.F * C;
+        for (int idx = threadIdx.x; idx < total; idx += NT) {
+            const int r = g.F > 1 ? (int)__umulhi((unsigned)idx, magic_f) : idx, f = idx - r * g.F;
+            *reinterpret_cast<bf16x4*>(dst + (size_t)idx * C) = *reinterpret_cast<const bf16x4*>(tile + (t0 + r - tile_torg) * RS + bin_off(f + 2));
+        }
+    } else {
+        // the owned bins of a row only
+        const int fo = kb.own_hi - kb.own_lo, nrows = min(TR, g.T - t0), total = nrows * fo;
+        const unsigned magic_f = 0xffffffffu / (unsigned)fo + 1u;           // ceil(2^32 / fo), fo >= 1
+        u16* dst = map + ((long long)(b * g.T + t0) * g.F + kb.f_org + kb.own_lo) * C;
+        for (int idx = threadIdx.x; idx < total; idx += NT) {
+            const int r = fo > 1 ? (int)__umulhi((unsigned)idx, magic_f) : idx, f = idx - r * fo;
+            *reinterpret_cast<bf16x4*>(dst + ((size_t)r * g.F + f) * C) =
+                *reinterpret_cast<const bf16x4*>(tile + (t0 + r - tile_torg) * RS + bin_off(kb.own_lo + f + 2));
+        }
     }
 }
 
@@ -392,11 +457,15 @@ __device__ __forceinline__ void conv_chunks(const u16* in, int in_torg, const bf
 //   C_hb[(fi, ci)][(fo, co)] += sum_{t, g} a[t + kt - 2][4 g + fi][ci] * d[t][4 (g + hb) + fo - 2][co],   kf = fi + 4 - 4 hb - fo
 // `at` / `dt` point at the tile rows of time t0 + kt - 2 / t0.  K step = 16 rows x 2 adjacent bin groups; with an odd number of
 // groups the last pair's second group does not exist: its fragments are read from the zero block.
-__device__ __forceinline__ void dw_step(f32x4& c0, f32x4& c1, const u16* at, const u16* dt, int ng, const u16* zero, int lane) {
+// Frequency blocks: the sum runs over the OWNED bin groups [glo, ng) of `a` only (glo = the first owned group, even; ng =
+// the groups up to the end of the owned range: a cut is a multiple of 8 bins, so a pair never straddles it, and the odd last
+// group can only be the image's); `d` is read two bins to either side of them.
+__device__ __forceinline__ void dw_step(f32x4& c0, f32x4& c1, const u16* at, const u16* dt, int glo, int ng, const u16* zero, int lane) {
     const int li = lane & 15, lg = lane >> 4;
     const int trow = 4 * lg + (li >> 2), fb = li & 3;
-    const int ng2 = (ng + 1) >> 1, nk = (TR / 16) * ng2;
+    const int ng2 = ((ng + 1) >> 1) - (glo >> 1), nk = (TR / 16) * ng2;
     const bool odd = (ng & 1) != 0;
+    at += 16 * glo; dt += 16 * glo;            // 32 elements per pair of groups
     const u16* ab = at + trow * RS;
     const u16* db = dt + trow * RS;
     const int oa0 = bin_off(2 + fb), oa1 = bin_off(6 + fb), od0 = bin_off(fb), od1 = bin_off(4 + fb), od2 = bin_off(8 + fb);
@@ -477,6 +546,23 @@ __device__ __forceinline__ void lds_init(u16* lds, size_t lds_bytes, const u16* 
     __syncthreads();
 }
 
+// Frequency blocks: a workgroup walks blocks of DIFFERENT widths through the same LDS tiles.  The loaders rewrite whole rows, but
+// the epilogues of conv_chunks (and stage_d_last) write the block's own bin groups only, and what lies to the right of them is read
+// as the zero padding (bins F, F + 1 by the layer; up to bin 4 ng + 1 by dw_step).  With one width per launch those bins stay zero
+// from lds_init; here a narrower block would find there what a wider block of an earlier tile left.  So a block of fewer than NGMAX
+// groups first clears bins 4 ng .. 67 (units 2 ng + 1 .. 34) of every row of a tile that epilogues write; the caller's barrier
+// behind the tile's loads publishes it.  (Bins 68 .. 71 are never written.)
+template <int NT>
+__device__ __forceinline__ void clear_right_of(u16* tile, int nrows, int ng) {
+    const int nu = 2 * (NGMAX - ng);
+    if (nu <= 0) return;
+    const int total = nrows * nu;
+    for (int idx = threadIdx.x; idx < total; idx += NT) {
+        const int r = idx / nu, u = 2 * ng + 1 + (idx - r * nu);
+        *reinterpret_cast<u32x4*>(tile + r * RS + unit_pos(u) * 8) = u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // forward: x0 [B][T][ldx] fp32 (one channel) -> a_1 .. a_{L-1} (padded maps), a_L (plain)
 // tiles P0, P1 of TR + 4 L rows, row i <-> t = t0 - 2 L + i; a_l is valid on [t0 - 2 (L - l), t0 + TR + 2 (L - l))
@@ -487,9 +573,10 @@ struct FwdArgs {
     u16* maps; u16* a_last;
     Geo g; size_t lds_bytes;
     unsigned long long* dbg;
+    FBlocks fb;
 };
 
-template <int NT>
+template <int NT, bool BLK>
 __global__ __launch_bounds__(NT) void chain_fwd_kernel(FwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) u16 lds[];
     constexpr int NW = NT / 64;
@@ -503,7 +590,7 @@ __global__ __launch_bounds__(NT) void chain_fwd_kernel(FwdArgs a) {
     LaneOff lo;
     lo.init(lane);
     RowStore<NT> rs;
-    rs.init(g);
+    if (!BLK) rs.init(g);
     const float* biasl = reinterpret_cast<const float*>(reinterpret_cast<const char*>(lds) + HDR_BIAS);
     const int RB = TR + 4 * L;
     u16* P0 = lds + HDR_BYTES / 2;
@@ -512,17 +599,31 @@ __global__ __launch_bounds__(NT) void chain_fwd_kernel(FwdArgs a) {
     X0Pref<NSX, NT> xp;
     int tile = blockIdx.x;
     if (tile < g.ntiles) {
-        const int b = tile / g.ntt, t0 = (tile - b * g.ntt) * TR;
-        xp.load(a.x0, a.ldx, g, b, t0 - 2 * L, RB);
+        int b, t0;
+        const Blk kb = tile_of<BLK>(g, a.fb, tile, b, t0);
+        Geo gblk;
+        if (BLK) gblk = block_geo(g, kb);
+        const Geo& gl = BLK ? gblk : g;          // what the tile's helpers work on: the block as an image
+        xp.load(a.x0 + kb.f_org, a.ldx, gl, b, t0 - 2 * L, RB);
     }
     for (; tile < g.ntiles; tile += gridDim.x) {
-        const int b = tile / g.ntt, t0 = (tile - b * g.ntt) * TR;
+        int b, t0;
+        const Blk kb = tile_of<BLK>(g, a.fb, tile, b, t0);
+        Geo gblk;
+        if (BLK) gblk = block_geo(g, kb);
+        const Geo& gl = BLK ? gblk : g;          // what the tile's helpers work on: the block as an image
         const int torg = t0 - 2 * L;
+        if (BLK) rs.init_block(g, kb);
         xp.commit(P0, RB);
+        if (BLK) clear_right_of<NT>(P1, RB, kb.ng);
         const int nxt = tile + gridDim.x;
         if (nxt < g.ntiles) {
-            const int nb = nxt / g.ntt, nt0 = (nxt - nb * g.ntt) * TR;
-            xp.load(a.x0, a.ldx, g, nb, nt0 - 2 * L, RB);
+            int nb, nt0;
+            const Blk nk = tile_of<BLK>(g, a.fb, nxt, nb, nt0);
+            Geo gnxt;
+            if (BLK) gnxt = block_geo(g, nk);
+            const Geo& gn = BLK ? gnxt : g;
+            xp.load(a.x0 + nk.f_org, a.ldx, gn, nb, nt0 - 2 * L, RB);
         }
         lds_barrier();
         stamp(a.dbg, 2);
@@ -532,10 +633,10 @@ __global__ __launch_bounds__(NT) void chain_fwd_kernel(FwdArgs a) {
             bf16x8 af[KT];
             load_afrag(lds + (l - 1) * TLAY, lane, af);
             const f32x4 bv = *reinterpret_cast<const f32x4*>(biasl + (l - 1) * C);
-            if (l >= 2) rs.run(in + (t0 - torg) * RS, a.maps + (long long)(l - 2) * g.map_stride + (long long)(b * g.T + t0) * g.FP * C, min(TR, g.T - t0));
+            if (l >= 2) rs.run(in + (t0 - torg) * RS, a.maps + (long long)(l - 2) * g.map_stride + (long long)(b * g.T + t0) * g.FP * C + kb.f_org * C, min(TR, g.T - t0));
             const int ext = 2 * (L - l);
             const int ta = t0 - ext, tb = t0 + TR + ext;
-            conv_chunks<NW, false, false>(in, torg, af, ta, tb, g, wave, l, lo, bv,
+            conv_chunks<NW, false, false>(in, torg, af, ta, tb, gl, wave, l, lo, bv,
                        [](int, int, int, int) { return 0; },
                        [&](int tc, int, int, int px, f32x4 v, int, bool ok, bool) {
 #pragma unroll
@@ -546,7 +647,7 @@ __global__ __launch_bounds__(NT) void chain_fwd_kernel(FwdArgs a) {
             stamp(a.dbg, 2 + l);
             lds_barrier();
         }
-        store_rows_plain<NT>((L & 1) ? P1 : P0, torg, a.a_last, g, b, t0);
+        store_rows_plain<NT, BLK>((L & 1) ? P1 : P0, torg, a.a_last, g, kb, b, t0);
         lds_barrier();
         stamp(a.dbg, 12);
         a.dbg = nullptr;           // stamps: the first tile of a workgroup only
@@ -569,14 +670,15 @@ struct BwdArgs {
     int cin0;                                  // input channels of the first layer (1)
     Geo g; size_t lds_bytes;
     unsigned long long* dbg;
+    FBlocks fb;
 };
 
 constexpr int MODE_BWD = 0, MODE_DATA = 1;
 
 // the first stage: d_L = lrelu'(a_L) . dL/da_L on rows [ta, tb) -> tile D (zero outside the image); db_L from the own rows
-template <int NT, bool WANT_B>
-__device__ __forceinline__ void stage_d_last(const BwdArgs& a, const Geo& g, u16* D, int d_torg, int b, int ta, int tb, int t0, f32x4& bsum) {
-    const int nb = 4 * g.ng, total = (tb - ta) * nb;
+template <int NT, bool WANT_B, bool BLK>
+__device__ __forceinline__ void stage_d_last(const BwdArgs& a, const Geo& g, const Blk& kb, u16* D, int d_torg, int b, int ta, int tb, int t0, f32x4& bsum) {
+    const int nb = 4 * (BLK ? kb.ng : g.ng), total = (tb - ta) * nb;
     const unsigned magic = (unsigned)(((1ULL << 32) + (unsigned)nb - 1) / (unsigned)nb);
 #pragma unroll 1
     for (int base = threadIdx.x; base < total; base += 4 * NT) {
@@ -587,8 +689,8 @@ __device__ __forceinline__ void stage_d_last(const BwdArgs& a, const Geo& g, u16
             const int r = (int)__umulhi((unsigned)idx, magic), f = idx - r * nb, t = ta + r;
             rr[k] = idx < total ? t : (1 << 30); ff[k] = f;
             dv[k] = zero4(); av[k] = to_bf16(zero4());
-            if (idx < total && (unsigned)t < (unsigned)g.T && f < g.F) {
-                const long long off = ((long long)(b * g.T + t) * g.F + f) * C;
+            if (idx < total && (unsigned)t < (unsigned)g.T && f < (BLK ? kb.F : g.F)) {
+                const long long off = ((long long)(b * g.T + t) * g.F + (BLK ? kb.f_org : 0) + f) * C;
                 if (a.d_bf16) dv[k] = to_f32(*reinterpret_cast<const bf16x4*>(reinterpret_cast<const u16*>(a.d_last) + off));
                 else dv[k] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(a.d_last) + off);
                 av[k] = *reinterpret_cast<const bf16x4*>(a.a_last + off);
@@ -601,13 +703,13 @@ __device__ __forceinline__ void stage_d_last(const BwdArgs& a, const Geo& g, u16
             f32x4 v = dv[k];
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = v[e] * (m[e] > 0.f ? 1.f : g.alpha);
-            if (WANT_B && rr[k] >= t0 && rr[k] < t0 + TR) bsum += v;          // (zero outside the image)
+            if (WANT_B && rr[k] >= t0 && rr[k] < t0 + TR && (!BLK || (ff[k] >= kb.own_lo && ff[k] < kb.own_hi))) bsum += v;          // (zero outside the image)
             *reinterpret_cast<bf16x4*>(D + (rr[k] - d_torg) * RS + bin_off(ff[k] + 2)) = to_bf16(v);
         }
     }
 }
 
-template <int NT, int MODE>
+template <int NT, int MODE, bool BLK>
 __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) u16 lds[];
     constexpr int NW = NT / 64;
@@ -622,7 +724,7 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
     LaneOff lo;
     lo.init(lane);
     RowStore<WG ? NT * 64 : NT> rs;         // (the weight-gradient kernel stores no rows: no slots)
-    if (!WG) rs.init(g);
+    if (!WG && !BLK) rs.init(g);
     const u16* zero = lds + HDR_ZERO / 2;
     float* bsl = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + HDR_BS);      // [LMAX][NW][4]
     // d_l valid on t0 -+ ext(l): MODE_BWD 2 (l - 1), MODE_DATA 2 l
@@ -636,7 +738,7 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
     constexpr int NSA = ((TR + 4 * (LMAX - 1)) * RSU + NT - 1) / NT;
     constexpr int NSX = ((TR + 4) * 72 + NT - 1) / NT;
     MapDma<NSA, NT> mp;
-    mp.init(g);
+    mp.init(BLK ? 4 * NGMAX : g.FP);
     const u16* zpage = reinterpret_cast<const u16*>(reinterpret_cast<const char*>(a.tab) + TAB_ZERO_OFF);
     X0Pref<NSX, NT> xp;
     f32x4 acc[LMAX][2];
@@ -644,19 +746,27 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
     for (int s = 0; s < LMAX; ++s) { acc[s][0] = zero4(); acc[s][1] = zero4(); }
 
     for (int tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
-        const int b = tile / g.ntt, t0 = (tile - b * g.ntt) * TR;
+        int b, t0;
+        const Blk kb = tile_of<BLK>(g, a.fb, tile, b, t0);
+        Geo gblk;
+        if (BLK) gblk = block_geo(g, kb);
+        const Geo& gl = BLK ? gblk : g;          // what the tile's helpers work on: the block as an image
         const int dorg = t0 - EXTD, aorg = t0 - EXTA;
+        // the weight gradient's bin groups: the owned ones
+        const int wg_lo = BLK ? kb.own_lo >> 2 : 0, wg_ng = BLK ? (kb.own_hi + 3) >> 2 : g.ng;
+        if (!WG && BLK && a.gmaps) rs.init_block(g, kb);
         // ---- stage 0: d_L -> D0, a_{L-1} -> A0
+        if (BLK) { clear_right_of<NT>(D0, RD, kb.ng); clear_right_of<NT>(D1, RD, kb.ng); }
         {
             f32x4 bs = zero4();
             const int e = WG ? 2 * (L - 1) : 2 * L;
-            if (L >= 2) mp.issue(a.maps + (long long)(L - 2) * g.map_stride, g, b, aorg, RA, A0, zpage);       // in flight under the first stage
-            stage_d_last<NT, WG>(a, g, D0, dorg, b, t0 - e, t0 + TR + e, t0, bs);
+            if (L >= 2) mp.template issue<BLK>(a.maps + (long long)(L - 2) * g.map_stride, g, kb, b, aorg, RA, A0, zpage);       // in flight under the first stage
+            stage_d_last<NT, WG, BLK>(a, g, kb, D0, dorg, b, t0 - e, t0 + TR + e, t0, bs);
             if (WG) wave_add4(bsl + ((L - 1) * NW + wave) * 4, bs, lane);
             if (L >= 2) {
                 dma_wait();
             } else if (WG) {
-                xp.load(a.x0, a.ldx, g, b, aorg, RA);
+                xp.load(a.x0 + kb.f_org, a.ldx, gl, b, aorg, RA);
                 xp.commit(A0, RA);
             }
         }
@@ -672,13 +782,13 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
                 u16* An = (s & 1) ? A0 : A1;
                 // the map of the next step: a_{l-2} (l - 2 >= 1: a padded map; l == 2: the stack's input, for the first layer's dW)
                 stamp_w(a.dbg, s, wave, lane, 0);
-                if (l >= 3) mp.issue(a.maps + (long long)(l - 3) * g.map_stride, g, b, aorg, RA, An, zpage);
-                else if (l == 2 && WG) xp.load(a.x0, a.ldx, g, b, t0 - 2, TR + 4);        // rows t0 - 2 .. t0 + TR + 2 of the input
+                if (l >= 3) mp.template issue<BLK>(a.maps + (long long)(l - 3) * g.map_stride, g, kb, b, aorg, RA, An, zpage);
+                else if (l == 2 && WG) xp.load(a.x0 + kb.f_org, a.ldx, gl, b, t0 - 2, TR + 4);        // rows t0 - 2 .. t0 + TR + 2 of the input
                 stamp_w(a.dbg, s, wave, lane, 1);
-                if (!WG && a.gmaps) rs.run(Dc + (t0 - dorg) * RS, a.gmaps + (long long)(l - 1) * g.map_stride + (long long)(b * g.T + t0) * g.FP * C, min(TR, g.T - t0));
+                if (!WG && a.gmaps) rs.run(Dc + (t0 - dorg) * RS, a.gmaps + (long long)(l - 1) * g.map_stride + (long long)(b * g.T + t0) * g.FP * C + kb.f_org * C, min(TR, g.T - t0));
                 if (WG && wave < KT) {
                     f32x4 c0 = zero4(), c1 = zero4();
-                    dw_step(c0, c1, Ac + (t0 + wave - 2 - aorg) * RS, Dc + (t0 - dorg) * RS, g.ng, zero, lane);
+                    dw_step(c0, c1, Ac + (t0 + wave - 2 - aorg) * RS, Dc + (t0 - dorg) * RS, wg_lo, wg_ng, zero, lane);
                     stamp_w(a.dbg, s, wave, lane, 2);
                     acc_add(acc, s, c0, c1);
                 }
@@ -690,14 +800,14 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
                     const int ta = t0 - ext, tb = t0 + TR + ext;
                     if (l >= 2) {
                         f32x4 bs = zero4();
-                        conv_chunks<NW, WG, false, false>(Dc, dorg, af, ta, tb, g, wave, s, lo, zero4(),      // (both pairs' reads in one burst measured 9 % slower here)
+                        conv_chunks<NW, WG, false, false>(Dc, dorg, af, ta, tb, gl, wave, s, lo, zero4(),      // (both pairs' reads in one burst measured 9 % slower here)
                                    [&](int tc, int, int, int px) { return *reinterpret_cast<const bf16x4*>(Ac + (tc - aorg) * RS + px); },
-                                   [&](int tc, int t, int, int px, f32x4 v, bf16x4 mk, bool ok, bool fresh) {
+                                   [&](int tc, int t, int f, int px, f32x4 v, bf16x4 mk, bool ok, bool fresh) {
                                        const f32x4 m = to_f32(mk);
 #pragma unroll
                                        for (int e = 0; e < 4; ++e) v[e] = v[e] * (m[e] > 0.f ? 1.f : g.alpha);
                                        if (!ok) v = zero4();
-                                       if (WG && fresh && t >= t0 && t < t0 + TR) bs += v;
+                                       if (WG && fresh && t >= t0 && t < t0 + TR && (!BLK || (f >= kb.own_lo && f < kb.own_hi))) bs += v;
                                        *reinterpret_cast<bf16x4*>(Dn + (tc - dorg) * RS + px) = to_bf16(v);
                                    });
                         stamp_w(a.dbg, s, wave, lane, 4);
@@ -705,10 +815,11 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
                         stamp_w(a.dbg, s, wave, lane, 5);
                     } else if (a.g0) {
                         // d/dx0: channel 0 of the transposed first layer, own rows, straight to HBM
-                        conv_chunks<NW, false, false>(Dc, dorg, af, t0, t0 + TR, g, wave, s, lo, zero4(),
+                        conv_chunks<NW, false, false>(Dc, dorg, af, t0, t0 + TR, gl, wave, s, lo, zero4(),
                                    [](int, int, int, int) { return 0; },
                                    [&](int, int t, int f, int, f32x4 v, int, bool ok, bool) {
-                                       if (ok) a.g0[(long long)(b * g.T + t) * g.F + f] = v[0];
+                                       if (BLK) ok = ok && f >= kb.own_lo && f < kb.own_hi;
+                                       if (ok) a.g0[(long long)(b * g.T + t) * g.F + kb.f_org + f] = v[0];
                                    });
                     }
                 }
@@ -775,9 +886,10 @@ struct SecArgs {
     int cin0;
     Geo g; size_t lds_bytes;
     unsigned long long* dbg;
+    FBlocks fb;
 };
 
-template <int NT>
+template <int NT, bool BLK>
 __global__ __launch_bounds__(NT) void chain_second_kernel(SecArgs a) {
     extern __shared__ __attribute__((aligned(16))) u16 lds[];
     constexpr int NW = NT / 64;
@@ -799,20 +911,26 @@ __global__ __launch_bounds__(NT) void chain_second_kernel(SecArgs a) {
     constexpr int NSG = (TR * RSU + NT - 1) / NT;
     constexpr int NSX = ((TR + 4 * LMAX) * 72 + NT - 1) / NT;
     MapDma<NSG, NT> mp;
-    mp.init(g);
+    mp.init(BLK ? 4 * NGMAX : g.FP);
     const u16* zpage = reinterpret_cast<const u16*>(reinterpret_cast<const char*>(a.tab) + TAB_ZERO_OFF);
     f32x4 acc[LMAX][2];
 #pragma unroll
     for (int s = 0; s < LMAX; ++s) { acc[s][0] = zero4(); acc[s][1] = zero4(); }
 
     for (int tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
-        const int b = tile / g.ntt, t0 = (tile - b * g.ntt) * TR;
+        int b, t0;
+        const Blk kb = tile_of<BLK>(g, a.fb, tile, b, t0);
+        Geo gblk;
+        if (BLK) gblk = block_geo(g, kb);
+        const Geo& gl = BLK ? gblk : g;          // what the tile's helpers work on: the block as an image
         const int uorg = t0 - 2 * L;
+        const int wg_lo = BLK ? kb.own_lo >> 2 : 0, wg_ng = BLK ? (kb.own_hi + 3) >> 2 : g.ng;
         {
             X0Pref<NSX, NT> xp;
-            xp.load(a.u0, g.F, g, b, uorg, RU);
-            mp.issue(a.gmaps, g, b, t0, TR, G0, zpage);
+            xp.load(a.u0 + kb.f_org, g.F, gl, b, uorg, RU);
+            mp.template issue<BLK>(a.gmaps, g, kb, b, t0, TR, G0, zpage);
             xp.commit(U0, RU);
+            if (BLK) clear_right_of<NT>(U1, RU, kb.ng);
             dma_wait();
         }
         lds_barrier();
@@ -825,10 +943,10 @@ __global__ __launch_bounds__(NT) void chain_second_kernel(SecArgs a) {
                 u16* Un = (s & 1) ? U0 : U1;
                 const u16* Gc = (s & 1) ? G1 : G0;
                 u16* Gn = (s & 1) ? G0 : G1;
-                if (l < L) mp.issue(a.gmaps + (long long)l * g.map_stride, g, b, t0, TR, Gn, zpage);
+                if (l < L) mp.template issue<BLK>(a.gmaps + (long long)l * g.map_stride, g, kb, b, t0, TR, Gn, zpage);
                 if (wave < KT) {
                     f32x4 c0 = zero4(), c1 = zero4();
-                    dw_step(c0, c1, Uc + (t0 + wave - 2 - uorg) * RS, Gc, g.ng, zero, lane);
+                    dw_step(c0, c1, Uc + (t0 + wave - 2 - uorg) * RS, Gc, wg_lo, wg_ng, zero, lane);
                     acc_add(acc, s, c0, c1);
                 }
                 bf16x8 af[KT];
@@ -836,12 +954,12 @@ __global__ __launch_bounds__(NT) void chain_second_kernel(SecArgs a) {
                 const int ext = 2 * (L - l);
                 const int ta = t0 - ext, tb = t0 + TR + ext;
                 const bool last = l == L;
-                const u16* am = last ? a.a_last : a.maps + (long long)(l - 1) * g.map_stride;
+                const u16* am = (last ? a.a_last : a.maps + (long long)(l - 1) * g.map_stride) + kb.f_org * C;
                 const int apitch = last ? g.F : g.FP;
-                conv_chunks<NW, true, false, true>(Uc, uorg, af, ta, tb, g, wave, s, lo, zero4(),
+                conv_chunks<NW, true, false, true>(Uc, uorg, af, ta, tb, gl, wave, s, lo, zero4(),
                            [&](int, int t, int f, int) {
                                bf16x4 m = to_bf16(zero4());
-                               if ((unsigned)t < (unsigned)g.T && f < g.F) m = *reinterpret_cast<const bf16x4*>(am + ((long long)(b * g.T + t) * apitch + f) * C);
+                               if ((unsigned)t < (unsigned)g.T && f < kb.F) m = *reinterpret_cast<const bf16x4*>(am + ((long long)(b * g.T + t) * apitch + f) * C);
                                return m;
                            },
                            [&](int tc, int t, int f, int px, f32x4 v, bf16x4 mk, bool ok, bool) {
@@ -850,8 +968,8 @@ __global__ __launch_bounds__(NT) void chain_second_kernel(SecArgs a) {
                                for (int e = 0; e < 4; ++e) v[e] = v[e] * (m[e] > 0.f ? 1.f : g.alpha);
                                if (!ok) v = zero4();
                                if (!last) *reinterpret_cast<bf16x4*>(Un + (tc - uorg) * RS + px) = to_bf16(v);
-                               else if (ok) {
-                                   const long long off = ((long long)(b * g.T + t) * g.F + f) * C;
+                               else if (ok && (!BLK || (f >= kb.own_lo && f < kb.own_hi))) {
+                                   const long long off = ((long long)(b * g.T + t) * g.F + kb.f_org + f) * C;
                                    if (a.out_bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<u16*>(a.out) + off) = to_bf16(v);
                                    else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + off) = v;
                                }
@@ -911,10 +1029,31 @@ int wide_nt() {
     return nt;
 }
 
-bool make_geo(Geo& g, int B, int T, int F, int L, float alpha) {
+// The frequency blocks of a stack of L layers over F bins -- the ONE plan behind every launch and ptts_conv2d_chain_blocks.
+// A block computes min(68, F - origin) bins from its origin; where it ends short of an image edge (a cut) nothing within 2 L bins
+// of the cut is owned.  Origins and cuts are multiples of 8 bins (whole, aligned 16-byte units in every map; a K step of the
+// weight gradient -- two adjacent bin groups -- never straddles a cut), hence
+//     halo   = 2 L rounded up to 8                 bins between a block's origin and its first owned bin
+//     stride = (68 - 2 L rounded down to 8) - halo bins between origins = bins owned by an inner block
+//     block k: origin k stride, owns [k stride + halo (0 for k = 0), (k + 1) stride + halo (F for the last block))
+// L = 8: halo 16, stride 32 -> F <= 68 one block, <= 100 two, <= 132 three, ... ; smaller L owns more per block.
+struct FPlan { int nfb, stride, halo; };
+constexpr int FMAX = 1024;         // bins (a block's work depends on its width and on being first or last, not on how many there are)
+bool make_plan(FPlan& p, int F, int L) {
+    if (F < 2 || F > FMAX || L < 1 || L > LMAX) return false;
+    p.halo = (2 * L + 7) & ~7;
+    p.stride = ((4 * NGMAX - 2 * L) & ~7) - p.halo;
+    p.nfb = F <= 4 * NGMAX ? 1 : 1 + (F - 4 * NGMAX + p.stride - 1) / p.stride;
+    return true;
+}
+
+bool make_geo(Geo& g, FBlocks& fb, int B, int T, int F, int L, float alpha) {
+    FPlan p;
+    if (!make_plan(p, F, L)) return false;
+    fb.n = p.nfb; fb.stride = p.stride; fb.halo = p.halo;
     g.B = B; g.T = T; g.F = F; g.FP = (F + 1) & ~1; g.L = L; g.ng = (F + 3) / 4;
     g.ntt = (T + TR - 1) / TR;
-    g.ntiles = B * g.ntt;
+    g.ntiles = B * g.ntt * p.nfb;
     const unsigned upr = (unsigned)(g.FP / 2);
     g.magic_fp2 = upr > 1 ? (unsigned)(((1ULL << 32) + upr - 1) / upr) : 0u;
     g.alpha = alpha;
@@ -924,11 +1063,11 @@ bool make_geo(Geo& g, int B, int T, int F, int L, float alpha) {
 
 int check_common(const char* what, int B, int T, int F, int L, float alpha) {
     PTTS_REQUIRE(B > 0 && T > 0, "%s: bad dims B=%d T=%d", what, B, T);
-    PTTS_REQUIRE(F >= 2 && F <= 4 * NGMAX, "%s: F = %d outside [2, %d] (one block of %d bin groups)", what, F, 4 * NGMAX, NGMAX);
+    PTTS_REQUIRE(F >= 2 && F <= FMAX, "%s: F = %d outside [2, %d]", what, F, FMAX);
     PTTS_REQUIRE(L >= 1 && L <= LMAX, "%s: %d layers (1 .. %d)", what, L, LMAX);
     PTTS_REQUIRE(alpha > 0.f && alpha <= 1.f, "%s: LeakyReLU slope %g outside (0, 1]: the stored activations must keep the sign", what, alpha);
     PTTS_REQUIRE((long long)B * T * ((F + 1) & ~1) * C < (1LL << 31), "%s: map too large for 32-bit frame offsets", what);
-    PTTS_REQUIRE((long long)B * ((T + TR - 1) / TR) < (1LL << 30), "%s: too many tiles", what);
+    PTTS_REQUIRE((long long)B * ((T + TR - 1) / TR) * (1 + F / 32) < (1LL << 30), "%s: too many tiles", what);
     return PTTS_OK;
 }
 
@@ -940,7 +1079,22 @@ void set_lds(K kernel) {
 
 // 1 when the stack (Cin0 -> C -> ... -> C, KT x KF kernels, F bins) has a chain kernel
 extern "C" int ptts_conv2d_chain_supported(int F, int L, int Cin0, int Cc, int KT_, int KF_) {
-    return (F >= 2 && F <= 4 * NGMAX && L >= 1 && L <= LMAX && Cin0 >= 1 && Cin0 <= 4 && Cc == 4 && KT_ == 5 && KF_ == 5) ? 1 : 0;
+    FPlan p;
+    return (make_plan(p, F, L) && Cin0 >= 1 && Cin0 <= 4 && Cc == 4 && KT_ == 5 && KF_ == 5) ? 1 : 0;
+}
+
+// host only: the frequency blocks a launch over F bins and L layers works in -- block k computes bins [origin[k], origin[k] +
+// min(68, F - origin[k])) and owns (stores, sums) [own_lo[k], own_hi[k]).  Returns the number of blocks (the arrays, which may
+// be NULL, receive the first `cap` of them), 0 when the geometry has no chain kernel.
+extern "C" int ptts_conv2d_chain_blocks(int F, int L, int* origin, int* own_lo, int* own_hi, int cap) {
+    FPlan p;
+    if (!make_plan(p, F, L)) return 0;
+    for (int k = 0; k < p.nfb && k < cap; ++k) {
+        if (origin) origin[k] = k * p.stride;
+        if (own_lo) own_lo[k] = k ? k * p.stride + p.halo : 0;
+        if (own_hi) own_hi[k] = k == p.nfb - 1 ? F : (k + 1) * p.stride + p.halo;
+    }
+    return p.nfb;
 }
 
 // measurement hook: a buffer of 256 x 32 uint64 that receives the phase stamps of the next launches (NULL: off)
@@ -973,16 +1127,21 @@ extern "C" int ptts_conv2d_chain_fwd(const float* x0, long long ldx, const void*
     if (rc) return rc;
     PTTS_REQUIRE(x0 && tables && a_last && (maps || L == 1) && ldx >= F, "conv2d_chain_fwd: null tensor or ldx < F");
     FwdArgs a;
-    make_geo(a.g, B, T, F, L, alpha);
+    make_geo(a.g, a.fb, B, T, F, L, alpha);
     a.x0 = x0; a.ldx = ldx; a.tab = (const u16*)tables; a.bias = reinterpret_cast<const float*>((const char*)tables + TAB_BIAS_OFF);
     a.maps = (u16*)maps; a.a_last = (u16*)a_last; a.dbg = g_dbg;
     a.lds_bytes = HDR_BYTES + (size_t)2 * (TR + 4 * L) * RS * sizeof(u16);
     PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "conv2d_chain_fwd: tiles do not fit the LDS");
     static bool attr = false;
-    if (!attr) { set_lds(&chain_fwd_kernel<512>); set_lds(&chain_fwd_kernel<1024>); attr = true; }
+    if (!attr) {
+        set_lds(&chain_fwd_kernel<512, false>); set_lds(&chain_fwd_kernel<1024, false>);
+        set_lds(&chain_fwd_kernel<512, true>); set_lds(&chain_fwd_kernel<1024, true>);
+        attr = true;
+    }
     const int grid = std::min(a.g.ntiles, NCU);
-    if (wide_nt() == 1024) hipLaunchKernelGGL(chain_fwd_kernel<1024>, dim3(grid), dim3(1024), a.lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(chain_fwd_kernel<512>, dim3(grid), dim3(512), a.lds_bytes, (hipStream_t)stream, a);
+    const bool blk = a.fb.n > 1;          // one block: the kernels without any block state
+    if (wide_nt() == 1024) hipLaunchKernelGGL((blk ? chain_fwd_kernel<1024, true> : chain_fwd_kernel<1024, false>), dim3(grid), dim3(1024), a.lds_bytes, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((blk ? chain_fwd_kernel<512, true> : chain_fwd_kernel<512, false>), dim3(grid), dim3(512), a.lds_bytes, (hipStream_t)stream, a);
     return check_launch("conv2d_chain_fwd");
 }
 
@@ -997,7 +1156,7 @@ extern "C" int ptts_conv2d_chain_bwd(const void* d_last, int d_bf16, const float
                  "conv2d_chain_bwd: null pointer or ldx < F");
     PTTS_REQUIRE(cin0 >= 1 && cin0 <= 4, "conv2d_chain_bwd: cin0 = %d", cin0);
     BwdArgs a;
-    make_geo(a.g, B, T, F, L, alpha);
+    make_geo(a.g, a.fb, B, T, F, L, alpha);
     const int grid = std::min(a.g.ntiles, NCU);
     if (partials_bytes < (size_t)L * grid * NPART * sizeof(float)) { set_error("conv2d_chain_bwd: partials buffer too small"); return PTTS_EWORKSPACE; }
     a.d_last = d_last; a.d_bf16 = d_bf16; a.x0 = x0; a.ldx = ldx; a.maps = (const u16*)maps; a.a_last = (const u16*)a_last;
@@ -1007,8 +1166,8 @@ extern "C" int ptts_conv2d_chain_bwd(const void* d_last, int d_bf16, const float
     a.lds_bytes = std::max(a.lds_bytes, (size_t)HDR_BYTES + (size_t)LMAX * KT * 2 * 4 * 64 * sizeof(float));
     PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "conv2d_chain_bwd: tiles do not fit the LDS");
     static bool attr = false;
-    if (!attr) { set_lds(&chain_bwd_kernel<NT, MODE_BWD>); attr = true; }
-    hipLaunchKernelGGL((chain_bwd_kernel<NT, MODE_BWD>), dim3(grid), dim3(NT), a.lds_bytes, (hipStream_t)stream, a);
+    if (!attr) { set_lds(&chain_bwd_kernel<NT, MODE_BWD, false>); set_lds(&chain_bwd_kernel<NT, MODE_BWD, true>); attr = true; }
+    hipLaunchKernelGGL((a.fb.n > 1 ? chain_bwd_kernel<NT, MODE_BWD, true> : chain_bwd_kernel<NT, MODE_BWD, false>), dim3(grid), dim3(NT), a.lds_bytes, (hipStream_t)stream, a);
     *nblocks_out = grid; *npart_out = NPART;
     return check_launch("conv2d_chain_bwd");
 }
@@ -1021,17 +1180,22 @@ extern "C" int ptts_conv2d_chain_bwd_data(const void* d_last, int d_bf16, const 
     if (rc) return rc;
     PTTS_REQUIRE(d_last && a_last && tables && (maps || L == 1) && (gmaps || g0), "conv2d_chain_bwd_data: null pointer");
     BwdArgs a;
-    make_geo(a.g, B, T, F, L, alpha);
+    make_geo(a.g, a.fb, B, T, F, L, alpha);
     a.d_last = d_last; a.d_bf16 = d_bf16; a.x0 = nullptr; a.ldx = 0; a.maps = (const u16*)maps; a.a_last = (const u16*)a_last;
     a.tab = (const u16*)tables; a.gmaps = (u16*)gmaps; a.g0 = g0; a.partials = nullptr; a.cin0 = 1; a.dbg = g_dbg;
     const int EXTD = 2 * L, EXTA = 2 * (L - 1);
     a.lds_bytes = HDR_BYTES + (size_t)(2 * (TR + 2 * EXTD) + 2 * (TR + 2 * EXTA)) * RS * sizeof(u16);
     PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "conv2d_chain_bwd_data: tiles do not fit the LDS");
     static bool attr = false;
-    if (!attr) { set_lds(&chain_bwd_kernel<512, MODE_DATA>); set_lds(&chain_bwd_kernel<1024, MODE_DATA>); attr = true; }
+    if (!attr) {
+        set_lds(&chain_bwd_kernel<512, MODE_DATA, false>); set_lds(&chain_bwd_kernel<1024, MODE_DATA, false>);
+        set_lds(&chain_bwd_kernel<512, MODE_DATA, true>); set_lds(&chain_bwd_kernel<1024, MODE_DATA, true>);
+        attr = true;
+    }
     const int grid = std::min(a.g.ntiles, NCU);
-    if (wide_nt() == 1024) hipLaunchKernelGGL((chain_bwd_kernel<1024, MODE_DATA>), dim3(grid), dim3(1024), a.lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((chain_bwd_kernel<512, MODE_DATA>), dim3(grid), dim3(512), a.lds_bytes, (hipStream_t)stream, a);
+    const bool blk = a.fb.n > 1;
+    if (wide_nt() == 1024) hipLaunchKernelGGL((blk ? chain_bwd_kernel<1024, MODE_DATA, true> : chain_bwd_kernel<1024, MODE_DATA, false>), dim3(grid), dim3(1024), a.lds_bytes, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((blk ? chain_bwd_kernel<512, MODE_DATA, true> : chain_bwd_kernel<512, MODE_DATA, false>), dim3(grid), dim3(512), a.lds_bytes, (hipStream_t)stream, a);
     return check_launch("conv2d_chain_bwd_data");
 }
 
@@ -1045,7 +1209,7 @@ extern "C" int ptts_conv2d_chain_second(const float* u0, const void* gmaps, cons
     PTTS_REQUIRE(u0 && gmaps && a_last && tables && out && partials && nblocks_out && npart_out && (maps || L == 1), "conv2d_chain_second: null pointer");
     PTTS_REQUIRE(cin0 >= 1 && cin0 <= 4, "conv2d_chain_second: cin0 = %d", cin0);
     SecArgs a;
-    make_geo(a.g, B, T, F, L, alpha);
+    make_geo(a.g, a.fb, B, T, F, L, alpha);
     const int grid = std::min(a.g.ntiles, NCU);
     if (partials_bytes < (size_t)L * grid * NPART * sizeof(float)) { set_error("conv2d_chain_second: partials buffer too small"); return PTTS_EWORKSPACE; }
     a.u0 = u0; a.gmaps = (const u16*)gmaps; a.maps = (const u16*)maps; a.a_last = (const u16*)a_last; a.tab = (const u16*)tables;
@@ -1054,8 +1218,8 @@ extern "C" int ptts_conv2d_chain_second(const float* u0, const void* gmaps, cons
     a.lds_bytes = std::max(a.lds_bytes, (size_t)HDR_BYTES + (size_t)LMAX * KT * 2 * 4 * 64 * sizeof(float));
     PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "conv2d_chain_second: tiles do not fit the LDS");
     static bool attr = false;
-    if (!attr) { set_lds(&chain_second_kernel<NT>); attr = true; }
-    hipLaunchKernelGGL(chain_second_kernel<NT>, dim3(grid), dim3(NT), a.lds_bytes, (hipStream_t)stream, a);
+    if (!attr) { set_lds(&chain_second_kernel<NT, false>); set_lds(&chain_second_kernel<NT, true>); attr = true; }
+    hipLaunchKernelGGL((a.fb.n > 1 ? chain_second_kernel<NT, true> : chain_second_kernel<NT, false>), dim3(grid), dim3(NT), a.lds_bytes, (hipStream_t)stream, a);
     *nblocks_out = grid; *npart_out = NPART;
     return check_launch("conv2d_chain_second");
 }

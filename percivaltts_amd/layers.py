@@ -432,7 +432,8 @@ class Conv2DStack(Layer):
         ws, bs = self.kernels()
         if x0.is_cuda and ops._C2C.supported(x0.shape[-1], ws):
             return ops.conv2d_chain(x0, ws, bs, self.alpha).float()
-        # shapes without a chain kernel (F > 68): layer by layer on the one-plane matrix-core / stencil kernels
+        # shapes without a chain kernel (other kernel sizes or filter counts, more than 8 layers, more bins than the chain's
+        # frequency blocks cover -- the library decides): layer by layer on the one-plane matrix-core / stencil kernels
         v = x0.reshape(x0.shape[0], x0.shape[1], x0.shape[2], 1)
         for li, (w, b) in enumerate(zip(ws, bs)):
             z = ops.conv2d(v, w, b)

@@ -12,6 +12,28 @@ from . import layers as kl
 from .networktts import pFC, pCNN1D
 
 
+CHAIN_MAX_LAYERS = 8
+# What arch_critic_bf16 = True sends to the chain kernels: spectra of one frequency block.  This is a rule of the DEFAULT, not a
+# limit of the kernels (that one is the library's, see chain_kernel_exists): wider spectra keep the layer-wise form under True,
+# whose numbers differ from the chain's (its first layer stays fp32), until the default is changed on purpose.
+CHAIN_DEFAULT_MAX_BINS = 68
+
+
+def chain_kernel_exists(spec, nlayers, filters, kt, kf):
+    """Whether csrc/conv2d_chain.hip runs the stack 1 -> filters -> ... -> filters over `spec` bins (the library's answer)."""
+    from . import _hip
+    return bool(_hip.lib().ptts_conv2d_chain_supported(int(spec), int(nlayers), 1, int(filters), int(kt), int(kf)))
+
+
+def chain_max_bins():
+    """The widest spectrum with a chain kernel (8 standard layers), asked of the library."""
+    lo, hi = 2, 1 << 20          # supported(lo), not supported(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if chain_kernel_exists(mid, CHAIN_MAX_LAYERS, 4, 5, 5) else (lo, mid)
+    return lo
+
+
 class Critic:
 
     input_features = None
@@ -37,14 +59,25 @@ class Critic:
             # build extension (BASELINE configs[2]; the reference is fp32): cfgarch.arch_critic_bf16
             #   True      the whole stack in bf16 storage / bf16 products / fp32 accumulation, ONE launch per pass with the maps
             #             between the layers in the LDS (kl.Conv2DStack -> csrc/conv2d_chain.hip); 4 filters of 5x5, <= 8 layers,
-            #             <= 68 bins -- other geometries take the layer-wise form below
+            #             <= CHAIN_DEFAULT_MAX_BINS bins (one frequency block) -- other geometries take the layer-wise form below
+            #   'chain'   the same stack wherever the library has a chain kernel (ptts_conv2d_chain_supported: wider spectra run
+            #             in overlapping frequency blocks); a geometry without one is a ValueError, never another form
             #   'layers'  the round-2 form: the maps between the 4 -> 4 channel layers (and their gradients) as bf16, one launch
             #             per layer and pass; the first layer (1 -> 4) and the map handed to the dense layers stay fp32
             # master weights and every weight gradient are fp32 either way
             bf16 = getattr(cfgarch, 'arch_critic_bf16', False)
             L = cfgarch.arch_gen_nbcnnlayers
             std = cfgarch.arch_gen_nbfilters == 4 and cfgarch.arch_gen_winlen == 5 and cfgarch.arch_spec_freqlen == 5
-            if bf16 and bf16 != 'layers' and std and L <= 8 and vocoder.specsize() <= 68:
+            if bf16 == 'chain':
+                chain = chain_kernel_exists(vocoder.specsize(), L, cfgarch.arch_gen_nbfilters, cfgarch.arch_gen_winlen, cfgarch.arch_spec_freqlen)
+                if not chain:
+                    raise ValueError("arch_critic_bf16='chain': no chain kernel for {} layers of {} filters {}x{} over {} bins (limits: "
+                                     "4 filters of 5x5, 1..{} layers, 2..{} bins); use True or 'layers'".format(
+                                         L, cfgarch.arch_gen_nbfilters, cfgarch.arch_gen_winlen, cfgarch.arch_spec_freqlen,
+                                         vocoder.specsize(), CHAIN_MAX_LAYERS, chain_max_bins()))
+            else:
+                chain = bool(bf16) and bf16 != 'layers' and std and L <= CHAIN_MAX_LAYERS and vocoder.specsize() <= CHAIN_DEFAULT_MAX_BINS
+            if chain:
                 l_spec = kl.Conv2DStack(L, cfgarch.arch_gen_nbfilters, [cfgarch.arch_gen_winlen, cfgarch.arch_spec_freqlen], alpha=0.3)(l_spec)
             else:
                 l_spec = kl.Reshape([vocoder.specsize(), 1])(l_spec)

@@ -1146,6 +1146,7 @@ class _C2C(object):
 
     @staticmethod
     def supported(F, ws):
+        """The library's answer (ptts_conv2d_chain_supported): spectra wider than one tile's 68 bins run in frequency blocks."""
         if not ws:
             return False
         KT, KF, cin0, Cc = ws[0].shape

@@ -1,5 +1,6 @@
-"""Times of the fused Conv2D-stack kernels (csrc/conv2d_chain.hip) at BASELINE size: per launch, HIP events, back to back."""
-import ctypes, sys, os, json
+"""Times of the fused Conv2D-stack kernels (csrc/conv2d_chain.hip) at BASELINE size: per launch, HIP events, back to back.
+--F BINS: another spectrum width (more than 68 bins run in frequency blocks); --B SIZE: that batch size alone (no phase stamps)."""
+import argparse, ctypes, sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from percivaltts_amd import ops, _hip
@@ -14,7 +15,11 @@ def timeit(fn, n=30, warm=5):
     return s.elapsed_time(e) / n * 1e3
 
 def main():
-    T, F, L = 400, 65, 8
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--F', type=int, default=65)
+    ap.add_argument('--B', type=int, default=None)
+    args = ap.parse_args()
+    T, F, L = 400, args.F, 8
     g = torch.Generator().manual_seed(1)
     ws = [(torch.rand(5, 5, 1 if l == 0 else 4, 4, generator=g) - 0.5).mul(0.3).cuda() for l in range(L)]
     bs = [torch.zeros(4).cuda() for _ in range(L)]
@@ -29,7 +34,7 @@ def main():
         print('fwdonly B=128 us:', round(timeit(fwd), 1))
         return
     short = os.environ.get('CHAIN_PROBE_SHORT') == '1'     # one batch size, few repetitions: the run under rocprofv3 --pmc
-    for B in ((128,) if short else (64, 128, 192)):
+    for B in ((args.B,) if args.B else (128,) if short else (64, 128, 192)):
         x0 = torch.randn(B, T, F, generator=g).cuda()
         maps = torch.empty((L - 1, B, T, FP, 4), dtype=torch.bfloat16, device='cuda')
         gmaps = torch.empty((L, B, T, FP, 4), dtype=torch.bfloat16, device='cuda')
@@ -53,7 +58,7 @@ def main():
         r = {'fwd': timeit(fwd, n, 1), 'bwd': timeit(bwd, n, 1), 'bwd_d16': timeit(bwd16, n, 1), 'bwd_data+gamma': timeit(dat, n, 1), 'bwd_data': timeit(dat0, n, 1), 'second': timeit(sec, n, 1)}
         out['B{}'.format(B)] = {k: round(v, 1) for k, v in r.items()}
         print('B =', B, out['B{}'.format(B)], flush=True)
-    if short:
+    if short or args.B:
         return
     # phase stamps of the first tile of every workgroup (100 MHz ticks -> us), B = 128
     B = 128
