@@ -16,6 +16,7 @@ optimizertts_wgan.py:53-68): LeakyReLU is piecewise linear, so the backward of a
 DenseBwdData are therefore Functions of their own whose backward is one masked forward sweep and
 one weight-gradient sweep.
 """
+import collections
 import contextlib
 import ctypes
 import os
@@ -135,10 +136,15 @@ def input_grad_only():
 # every noted stream, whether or not anything is queued, then launches what is queued: work that follows it on the current
 # stream (the optimiser) sees every gradient of the context.  Everything else keeps the immediate path.
 # ----------------------------------------------------------------------------------------------
+# One Conv2D backward pass: the per-workgroup partial sums its kernel left, [nblocks][npart] floats `off` bytes into `buf`, a row = nw
+# sums for the tensor dw, then cout for dbias (either may be None), then what else the kernel keeps.  dw / dbias: filled in by _conv2d_land.
+_Pass = collections.namedtuple('_Pass', 'buf off nblocks npart nw cout dw dbias')
+
+
 class _Deferred(object):
     active = False
     items = []          # (stream handle, x2, dy2, mask, scale, shift, gw, gb, K_in, N, M_rows, mode, alpha)
-    conv_items = []     # (partials buffer, byte offset of the rows, nblocks, npart, nw, cout, gw, gb): conv2d backward passes awaiting their reduction
+    conv_items = []     # _Pass records with dw = gw, dbias = gb: conv2d backward passes awaiting their reduction
     streams = []        # the streams the context's producers ran on
 
     @classmethod
@@ -164,7 +170,7 @@ class _Deferred(object):
 
     @classmethod
     def queue_conv(cls, *passes):
-        """Queue Conv2D passes (buffer, byte offset, nblocks, npart, nw, cout, gw, gb) launched on the current stream."""
+        """Queue Conv2D passes (_Pass records onto gradient buffers) launched on the current stream."""
         cls.note_stream()
         cls.conv_items.extend(passes)
 
@@ -303,9 +309,8 @@ def flush_weight_grads():
 
 
 def _conv2d_reduce(passes, record=None):
-    """ONE ptts_conv2d_reduce_grouped launch: the partial rows of every pass (buffer, byte offset, nblocks, npart, nw, cout, dw,
-    dbias) are added into its tensors dw [nw] / dbias [cout] (either may be None).  record: the stream that reads the buffers
-    when it is not the one that allocated them."""
+    """ONE ptts_conv2d_reduce_grouped launch: the partial rows of every pass (_Pass) are added into its tensors dw [nw] / dbias [cout]
+    (either may be None).  record: the stream that reads the buffers when it is not the one that allocated them."""
     descs = (_hip.Conv2dReduceDesc * len(passes))()
     for d, (buf, off, nblocks, npart, nw, cout, dw, db) in zip(descs, passes):
         if record is not None:
@@ -417,9 +422,13 @@ class _C2M(object):
     tables = _WeightCache()         # (id(w), stream, planes) -> _Derived(w, buf: forward table, buf_t: transposed table)
 
     @staticmethod
+    def shape_ok(Cin, Cout, KT, KF, dil_t):
+        return Cin == 4 and Cout == 4 and KT == 5 and KF == 5 and dil_t in (1, 2, 4, 8)
+
+    @staticmethod
     def eligible(x, w, dil_t):
         KT, KF, Cin, Cout = w.shape
-        return x.is_cuda and Cin == 4 and Cout == 4 and KT == 5 and KF == 5 and dil_t in (1, 2, 4, 8)
+        return x.is_cuda and _C2M.shape_ok(Cin, Cout, KT, KF, dil_t)
 
     @classmethod
     def table(cls, w, transposed, planes=3):
@@ -470,20 +479,14 @@ class _C2W(object):
     shapes = {}         # (F, Cin, Cout, KT, KF, dil_t) -> ptts_conv2d_wide_supported: the layers of the tuned corner ask at every call
 
     @staticmethod
-    def eligible(x, w, dil_t, *others):
-        """The wide kernels take this layer: the switch, the shape, and 16-byte aligned operands (their float4 loads)."""
-        if not (_C2W.enabled and x.is_cuda):
+    def shape_ok(F, Cin, Cout, KT, KF, dil_t):
+        if not _C2W.enabled:
             return False
-        KT, KF, Cin, Cout = w.shape
-        key = (x.shape[2], Cin, Cout, KT, KF, dil_t)
+        key = (F, Cin, Cout, KT, KF, dil_t)
         ok = _C2W.shapes.get(key)
         if ok is None:
             ok = _C2W.shapes[key] = bool(_hip.lib().ptts_conv2d_wide_supported(*key))
-        if not ok:
-            return False
-        if x.numel() // Cin * 16 >= 2 ** 31:
-            return False
-        return all(t is None or t.data_ptr() % 16 == 0 for t in (x,) + others)
+        return ok
 
 
 def conv2d_wide(on):
@@ -491,18 +494,54 @@ def conv2d_wide(on):
     _C2W.enabled = _C2W.default if on is None else bool(on)
 
 
+# Which tier takes a layer -- ONE rule, asked by the forward, both backward forms, the second-order sweep and conv2d_path_description
+# (a tier is its own description).  C2_MFMA_AFFINE: the backward of a matrix-core layer behind a BatchNormalization (_conv2d_bwd_tier).
+C2_MFMA, C2_MFMA_AFFINE = 'bf16x6 split on the bf16 matrix cores (csrc/conv2d_mfma.hip)', 'bf16x6 split, BatchNorm-fused input'
+C2_WIDE = 'fp32 matrix-core implicit GEMM (csrc/conv2d_wide.hip)'
+C2_STENCIL, C2_GENERIC = 'fp32 packed-FMA stencil (csrc/conv2d.hip)', 'generic fp32 kernels (csrc/conv2d.hip)'
+
+
+def _conv2d_shape_tier(F, Cin, Cout, KT, KF, dil_t, planes=3, mfma=True):
+    """The tier by shape, dilation and the switches alone.  planes = 1 (bf16 storage) has the matrix-core kernels only, whatever their
+    switch says; mfma = False: the caller has ruled them out.  C2_STENCIL / C2_GENERIC: the library chooses between the two inside the
+    entry points of csrc/conv2d.hip, the wrappers treat both as 'neither tier above'."""
+    if mfma and (planes == 1 or _C2M.enabled) and _C2M.shape_ok(Cin, Cout, KT, KF, dil_t):
+        return C2_MFMA
+    if planes == 3 and _C2W.shape_ok(F, Cin, Cout, KT, KF, dil_t):
+        return C2_WIDE
+    return C2_STENCIL if Cin in (1, 2, 4) and Cout in (1, 2, 4) and KT == KF and KT in (3, 5) else C2_GENERIC
+
+
+def _conv2d_tier(x, w, dil_t, alpha, planes, wide_reads, mfma=True):
+    """The tier of one launch: the shape's where the operands allow it -- a map on the device, a LeakyReLU slope in [0, 1] for the
+    matrix-core kernels, and for the wide kernels a small enough x, aligned like `wide_reads`, the other tensors they would read --
+    else the next one down.  The sites differ, kept as found: the bf16-storage forward also insists on dilation 1 (_conv2d_fwd_raw), its backward
+    takes every matrix-core dilation; the forward has the wide tier check (scale, shift, mask_src), the backward dy as well."""
+    KT, KF, Cin, Cout = w.shape
+    t = _conv2d_shape_tier(x.shape[2], Cin, Cout, KT, KF, dil_t, planes, mfma and 0.0 <= alpha <= 1.0) if x.is_cuda else C2_GENERIC
+    if t == C2_WIDE and not (x.numel() // Cin * 16 < 2 ** 31 and all(u is None or u.data_ptr() % 16 == 0 for u in (x,) + wide_reads)):
+        return C2_GENERIC        # the wide kernels: indices that fit 32 bits, 16-byte aligned operands (their float4 loads)
+    return t
+
+
+def _conv2d_bwd_tier(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_affine, planes):
+    """The backward's tier.  A BatchNorm-fused input (scale / shift, or their gradients wanted) keeps a matrix-core layer only as
+    C2_MFMA_AFFINE -- the fused launch with the affine in its staging: fp32 maps, LeakyReLU input, dx wanted, no mask source, the
+    forward's statistics switch on (_BNStats.enabled), a shape the fused kernels take (_C2MFused.ok), 16-byte aligned scale / shift."""
+    t = _conv2d_tier(x, w, dil_t, alpha, planes, (dy, scale, shift, mask_src))
+    if t != C2_MFMA or (scale is None and not want_affine):
+        return t
+    if planes == 3 and scale is not None and mode == IN_LRELU and want_dx and mask_src is None and _BNStats.enabled and \
+            _C2MFused.ok(x, dil_t, pad_mode, planes) and scale.data_ptr() % 16 == 0 and shift.data_ptr() % 16 == 0:
+        return C2_MFMA_AFFINE
+    return _conv2d_tier(x, w, dil_t, alpha, planes, (dy, scale, shift, mask_src), False)
+
+
 def conv2d_path_description(shape=None):
     """The kernels the Conv2D layers take.  shape = (F, Cin, Cout, KT, KF[, dil_t]): the tier of that one layer."""
     if shape is not None:
         F, Cin, Cout, KT, KF = shape[:5]
-        dil_t = shape[5] if len(shape) > 5 else 1
-        if _C2M.enabled and (Cin, Cout, KT, KF) == (4, 4, 5, 5) and dil_t in (1, 2, 4, 8):
-            return 'bf16x6 split on the bf16 matrix cores (csrc/conv2d_mfma.hip)'
-        if _C2W.enabled and _hip.lib().ptts_conv2d_wide_supported(F, Cin, Cout, KT, KF, dil_t):
-            return 'fp32 matrix-core implicit GEMM (csrc/conv2d_wide.hip)'
-        if Cin in (1, 2, 4) and Cout in (1, 2, 4) and KT == KF and KT in (3, 5):
-            return 'fp32 packed-FMA stencil (csrc/conv2d.hip)'
-        return 'generic fp32 kernels (csrc/conv2d.hip)'
+        return _conv2d_shape_tier(F, Cin, Cout, KT, KF, shape[5] if len(shape) > 5 else 1)
     base = ('4->4 5x5 layers: bf16x6 split on the bf16 matrix cores (fp32 accumulate); 1->4 / 4->1 layers: fp32 packed-FMA stencil'
             if _C2M.enabled else 'fp32 packed-FMA stencil')
     wide = ('; wide / non-square layers (1 or 4..16 channels, odd windows 3..7): fp32 matrix-core implicit GEMM' if _C2W.enabled
@@ -550,18 +589,26 @@ def _conv2d_mfma_fwd(x, w, table, b, scale, shift, mask_src, out_mask, mode, alp
     return y
 
 
-def _conv2d_mfma_wgrad(dy, x, mask_src, mode, alpha, dil_t, pad_t, planes=3):
-    """Partial sums of dW / dbias: (buffer, nblocks, npart); the rows start 4096 bytes into the buffer."""
-    B, T, F, _ = x.shape
-    assert planes == 1 or not (_is16(x) or _is16(dy))
-    assert mask_src is None or mask_src.dtype == x.dtype
-    nws = _hip.lib().ptts_conv2d_mfma_wgrad_workspace_bytes(B, T)
-    buf = torch.empty(int(nws), dtype=torch.uint8, device=x.device)
+_ROWS_HEAD = 4096      # bytes in front of the partial rows in the buffers of csrc/conv2d_mfma.hip and of ptts_conv2d_bwd_partials (none: wide, chain)
+
+
+def _rows_call(name, nbytes, dev, head, tail, tag):
+    """Launch a kernel that leaves partial rows: a buffer of nbytes of its own (None for 0), handed over as (pointer, bytes, &nblocks,
+    &npart) between the arguments `head` and `tail`.  Returns (buffer, nblocks, npart)."""
+    buf = torch.empty(int(nbytes), dtype=torch.uint8, device=dev) if nbytes else None
     nblocks, npart = ctypes.c_int(0), ctypes.c_int(0)
-    call('ptts_conv2d_mfma_wgrad_partials', ptr(dy), ptr(x), ptr(mask_src), ptr(buf), buf.numel(), ctypes.byref(nblocks),
-         ctypes.byref(npart), B, T, F, 5, dil_t, pad_t, mode, alpha, planes, int(_is16(x)), int(_is16(dy)), stream(),
-         tag=(B, T, F, 4, 4, mode, planes))
+    call(name, *head, ptr(buf), int(nbytes), ctypes.byref(nblocks), ctypes.byref(npart), *tail, stream(), tag=tag)
     return buf, nblocks.value, npart.value
+
+
+def _mfma_pass(buf, nblocks, npart, w):
+    """The dW | dbias pass of a matrix-core launch over kernel w: its rows lie behind the header."""
+    return _Pass(buf, _ROWS_HEAD, nblocks, npart, w.numel(), w.shape[3], None, None)
+
+
+def _affine_pass(p, Cin):
+    """The sums of a BatchNorm-fused input's scale | shift (Cin each) follow dW | dbias in every row of pass p (fused-affine, wide)."""
+    return _Pass(p.buf, p.off + 4 * (p.nw + p.cout), p.nblocks, p.npart, Cin, Cin, None, None)
 
 
 class _C2MFused(object):
@@ -582,31 +629,26 @@ def conv2d_fused(on):
 
 def _conv2d_mfma_bwd_fused(kind, p, q, mask_src, w, alpha):
     """kind 1: (dy, x) -> dx, partial rows of dW / dbias; kind 2: (u, dy, mask_src = x) -> cot_dy, partial rows of dW.
-    Returns (y, buffer, nblocks, npart); the rows start 4096 bytes into the buffer."""
+    Returns (y, buffer, nblocks, npart) -- the last three for _mfma_pass."""
     B, T, F, _ = p.shape
     f32c(p, 'conv2d_bwd_fused.p'); f32c(q, 'conv2d_bwd_fused.q'); f32c(mask_src)
     assert q.shape == p.shape and (mask_src is None or mask_src.shape == p.shape)
     y = torch.empty_like(p)
-    nws = _hip.lib().ptts_conv2d_mfma_bwd_fused_workspace_bytes(B, T)
-    buf = torch.empty(int(nws), dtype=torch.uint8, device=p.device)
-    nblocks, npart = ctypes.c_int(0), ctypes.c_int(0)
-    call('ptts_conv2d_mfma_bwd_fused', ptr(p), ptr(q), ptr(mask_src), ptr(_C2M.table(w, kind == 1)), ptr(y), ptr(buf), buf.numel(),
-         ctypes.byref(nblocks), ctypes.byref(npart), B, T, F, 5, 2, kind, alpha, stream(), tag=(B, T, F, kind))
-    return y, buf, nblocks.value, npart.value
+    return (y,) + _rows_call('ptts_conv2d_mfma_bwd_fused', _hip.lib().ptts_conv2d_mfma_bwd_fused_workspace_bytes(B, T), p.device,
+                             (ptr(p), ptr(q), ptr(mask_src), ptr(_C2M.table(w, kind == 1)), ptr(y)), (B, T, F, 5, 2, kind, alpha),
+                             (B, T, F, kind))
 
 
 def _conv2d_mfma_bwd_fused_affine(dy, x, w, alpha, scale, shift):
-    """Kind 1 for a layer input lrelu(scale x + shift): (dy, x) -> dx (w.r.t. the raw x), partial rows of dW / dbias / dscale / dshift."""
+    """Kind 1 for a layer input lrelu(scale x + shift): (dy, x) -> dx (w.r.t. the raw x), partial rows of dW / dbias / dscale / dshift
+    (_mfma_pass, _affine_pass).  Returns (dx, buffer, nblocks, npart)."""
     B, T, F, _ = dy.shape
     f32c(dy, 'conv2d_bwd_fused.dy'); f32c(x, 'conv2d_bwd_fused.x'); f32c(scale); f32c(shift)
     assert x.shape == dy.shape
     y = torch.empty_like(dy)
-    nws = _hip.lib().ptts_conv2d_mfma_bwd_fused_workspace_bytes(B, T)
-    buf = torch.empty(int(nws), dtype=torch.uint8, device=dy.device)
-    nblocks, npart = ctypes.c_int(0), ctypes.c_int(0)
-    call('ptts_conv2d_mfma_bwd_fused_affine', ptr(dy), ptr(x), ptr(_C2M.table(w, True)), ptr(y), ptr(buf), buf.numel(),
-         ctypes.byref(nblocks), ctypes.byref(npart), B, T, F, 5, 2, alpha, ptr(scale), ptr(shift), stream(), tag=(B, T, F, 'affine'))
-    return y, buf, nblocks.value, npart.value
+    return (y,) + _rows_call('ptts_conv2d_mfma_bwd_fused_affine', _hip.lib().ptts_conv2d_mfma_bwd_fused_workspace_bytes(B, T), dy.device,
+                             (ptr(dy), ptr(x), ptr(_C2M.table(w, True)), ptr(y)), (B, T, F, 5, 2, alpha, ptr(scale), ptr(shift)),
+                             (B, T, F, 'affine'))
 
 
 def _st(t, name='tensor'):
@@ -623,7 +665,7 @@ def _conv2d_fwd_raw(x, w, b, scale, shift, mask_src, mode, alpha, dil_t, pad_mod
     if planes == 1:
         # bf16 arithmetic / storage (BASELINE configs[2]): matrix-core kernels only
         _st(x, 'conv2d.x'); _st(mask_src, 'conv2d.mask_src'); f32c(w, 'conv2d.w'); f32c(b, 'conv2d.b'); f32c(scale); f32c(shift)
-        if not (_C2M.eligible(x, w, dil_t) and dil_t == 1 and 0.0 <= alpha <= 1.0):
+        if not (_conv2d_tier(x, w, dil_t, alpha, 1, ()) == C2_MFMA and dil_t == 1):
             raise _hip.HipLibraryError('conv2d: bf16 storage is built for the 4 -> 4 channel 5x5 layers at dilation 1')
         return _conv2d_mfma_fwd(x, w, _C2M.table(w, False, 1), b, scale, shift, mask_src, None, mode, alpha, dil_t,
                                 _C2M.pad_t(dil_t, pad_mode), 1, out_bf16)
@@ -634,153 +676,135 @@ def _conv2d_fwd_raw(x, w, b, scale, shift, mask_src, mode, alpha, dil_t, pad_mod
     assert b is None or b.numel() == Cout
     assert scale is None or (scale.numel() == Cin and shift.numel() == Cin)
     assert mask_src is None or mask_src.shape == x.shape
-    if _C2M.enabled and _C2M.eligible(x, w, dil_t) and 0.0 <= alpha <= 1.0:
+    tier = _conv2d_tier(x, w, dil_t, alpha, 3, (scale, shift, mask_src))
+    if tier == C2_MFMA:
         return _conv2d_mfma_fwd(x, w, _C2M.table(w, False), b, scale, shift, mask_src, None, mode, alpha, dil_t,
                                 _C2M.pad_t(dil_t, pad_mode))
     y = torch.empty((B, T, F, Cout), dtype=torch.float32, device=x.device)
-    if _C2W.eligible(x, w, dil_t, scale, shift, mask_src):
-        call('ptts_conv2d_wide_fwd', ptr(x), ptr(w), ptr(b), ptr(scale), ptr(shift), ptr(mask_src), ptr(y),
-             B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha, stream(), tag=(B, T, F, Cin, Cout, mode))
-        return y
-    call('ptts_conv2d_fwd', ptr(x), ptr(w), ptr(b), ptr(scale), ptr(shift), ptr(mask_src), ptr(y),
+    call('ptts_conv2d_wide_fwd' if tier == C2_WIDE else 'ptts_conv2d_fwd', ptr(x), ptr(w), ptr(b), ptr(scale), ptr(shift), ptr(mask_src), ptr(y),
          B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha, stream(), tag=(B, T, F, Cin, Cout, mode))
     return y
 
 
-def _conv2d_mfma_bwd(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_rows, planes):
-    """The matrix-core backward of a 4 -> 4 layer: backward data = forward through the transposed table with the layer input's
-    LeakyReLU mask in the store; weight gradient = per-workgroup partial sums -- ONE fused launch where both are wanted and the
-    shape allows.  Returns (dx, pass): the pass is (buffer, byte offset, nblocks, npart, nw, cout), its rows still to be
-    reduced (_conv2d_reduce) or queued (_Deferred.queue_conv); None where not wanted.  The gradient of a map is stored like the
-    map (bf16 storage: dx has x's type)."""
-    pad_t = _C2M.pad_t(dil_t, pad_mode)
-    dx = None
-    if want_dx and want_rows and mode == IN_LRELU and _C2MFused.ok(x, dil_t, pad_mode, planes):
-        dx, buf, nblocks, npart = _conv2d_mfma_bwd_fused(1, dy, x, None, w, alpha)      # dx + dW + dbias: one launch
-    else:
+def _conv2d_bwd_launch(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_dw, want_db, want_affine, planes, queue):
+    """A layer's backward on its tier (_conv2d_bwd_tier).  Returns (dx, weight pass, affine pass, direct): the passes are unreduced
+    (_conv2d_land), None where not wanted or where the tier leaves no partial rows; direct = (dw, db, dscale, dshift) where the launch
+    finished them itself, else None.  queue: the caller will queue the weight pass (no BatchNorm-fused input, dw or db wanted)."""
+    B, T, F, Cin = x.shape
+    KT, KF, _, Cout = w.shape
+    dev, want_rows = x.device, want_dw or want_db
+    tier = _conv2d_bwd_tier(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_affine, planes)
+    if tier == C2_MFMA:
+        # backward data = forward through the transposed table with the layer input's LeakyReLU mask in the store (bf16 storage: dx
+        # has x's type); weight gradient = partial sums -- ONE fused launch where both are wanted and the shape allows
+        pad_t = _C2M.pad_t(dil_t, pad_mode)
+        dx = wp = None
+        if want_dx and want_rows and mode == IN_LRELU and _C2MFused.ok(x, dil_t, pad_mode, planes):
+            dx, buf, nblocks, npart = _conv2d_mfma_bwd_fused(1, dy, x, None, w, alpha)      # dx + dW + dbias: one launch
+            return dx, _mfma_pass(buf, nblocks, npart, w), None, None
         if want_dx:
             assert mode != IN_MASKMUL, 'conv2d_bwd: dx is not defined for MASKMUL (weight-only sweep)'
             dx = _conv2d_mfma_fwd(dy, w, _C2M.table(w, True, planes), None, None, None, None, x if mode == IN_LRELU else None,
                                   IN_NONE, alpha, dil_t, 4 * dil_t - pad_t, planes, _is16(x))
         if want_rows:
-            buf, nblocks, npart = _conv2d_mfma_wgrad(dy, x, mask_src, mode, alpha, dil_t, pad_t, planes)
-    return dx, ((buf, 4096, nblocks, npart, w.numel(), w.shape[3]) if want_rows else None)
-
-
-def _conv2d_wide_bwd(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_rows, want_affine):
-    """The wide kernels' backward: dx (or None) and the partial rows dw | dbias | dscale | dshift of the pass as
-    (buffer, nblocks, npart); the rows start at the buffer's first byte.  (None, 0, npart) where no sums are wanted."""
-    B, T, F, Cin = x.shape
-    KT, KF, _, Cout = w.shape
-    dx = torch.empty_like(x) if want_dx else None
-    buf = None
-    if want_rows or want_affine:
-        nws = _hip.lib().ptts_conv2d_wide_bwd_workspace_bytes(B, T, F, Cin, Cout, KT, KF, dil_t)
-        buf = torch.empty(int(nws), dtype=torch.uint8, device=x.device)
-    nblocks, npart = ctypes.c_int(0), ctypes.c_int(0)
-    call('ptts_conv2d_wide_bwd_partials', ptr(dy), ptr(x), ptr(w), ptr(scale), ptr(shift), ptr(mask_src), ptr(dx), ptr(buf),
-         0 if buf is None else buf.numel(), ctypes.byref(nblocks), ctypes.byref(npart), int(want_rows), int(want_affine),
-         B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha, stream(),
-         tag=(B, T, F, Cin, Cout, mode, int(want_dx), int(want_rows), int(want_affine)))
-    return dx, buf, nblocks.value, npart.value
-
-
-def _conv2d_bwd_raw(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode,
-                    want_dx, want_dw, want_db, want_affine, planes=3):
-    if planes == 1:
-        _st(dy, 'conv2d_bwd.dy'); _st(x, 'conv2d_bwd.x'); _st(mask_src); f32c(w)
-        assert scale is None and not want_affine, 'conv2d: no BatchNorm-fused input on the bf16-storage path'
-    else:
-        f32c(dy, 'conv2d_bwd.dy'); f32c(x, 'conv2d_bwd.x'); f32c(w); f32c(scale); f32c(shift); f32c(mask_src)
-    B, T, F, Cin = x.shape
-    KT, KF, _, Cout = w.shape
-    assert dy.shape == (B, T, F, Cout), 'conv2d_bwd: dy shape {} vs {}'.format(tuple(dy.shape), (B, T, F, Cout))
-    assert mask_src is None or mask_src.shape == x.shape
-    dev = x.device
-    if (planes == 1 or _C2M.enabled) and _C2M.eligible(x, w, dil_t) and scale is None and not want_affine and 0.0 <= alpha <= 1.0:
-        # matrix-core kernels; the partial rows are reduced at once into fresh tensors
-        dw = db = None
-        dx, rows = _conv2d_mfma_bwd(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_dw or want_db, planes)
-        if rows is not None:
-            dw = torch.zeros_like(w) if want_dw else None
-            db = torch.zeros(Cout, dtype=torch.float32, device=dev) if want_db else None
-            _conv2d_reduce([rows + (dw, db)])
-        return dx, dw, db, None, None
-    if planes == 3 and scale is not None and mode == IN_LRELU and want_dx and mask_src is None and _C2M.enabled and _BNStats.enabled and \
-            _C2M.eligible(x, w, dil_t) and 0.0 <= alpha <= 1.0 and _C2MFused.ok(x, dil_t, pad_mode, planes) and \
-            scale.data_ptr() % 16 == 0 and shift.data_ptr() % 16 == 0:
+            assert (planes == 1 or not (_is16(x) or _is16(dy))) and (mask_src is None or mask_src.dtype == x.dtype)
+            wp = _mfma_pass(*_rows_call('ptts_conv2d_mfma_wgrad_partials', _hip.lib().ptts_conv2d_mfma_wgrad_workspace_bytes(B, T), x.device,
+                                        (ptr(dy), ptr(x), ptr(mask_src)), (B, T, F, 5, dil_t, pad_t, mode, alpha, planes, int(_is16(x)), int(_is16(dy))),
+                                        (B, T, F, 4, 4, mode, planes)), w)
+        return dx, wp, None, None
+    if tier == C2_MFMA_AFFINE:
         # a BatchNormalization in front of the layer (the generator's stack): the fused matrix-core launch with that input's affine in its
         # Q staging, its mask and scale in the store of dx, and the affine's two gradient sums behind dW / dbias in the partial rows
         dx, buf, nblocks, npart = _conv2d_mfma_bwd_fused_affine(dy, x, w, alpha, scale, shift)
-        nw = KT * KF * Cin * Cout
-        dw = torch.zeros_like(w) if want_dw else None
-        db = torch.zeros(Cout, dtype=torch.float32, device=dev) if want_db else None
-        daff = torch.zeros(2 * Cin, dtype=torch.float32, device=dev) if want_affine else None
-        passes = []
-        if want_dw or want_db:
-            passes.append((buf, 4096, nblocks, npart, nw, Cout, dw, db))
-        if want_affine:                 # (the eight sums behind dW and dbias in every row)
-            passes.append((buf, 4096 + 4 * (nw + Cout), nblocks, npart, Cin, Cin, daff[:Cin], daff[Cin:]))
-        if passes:
-            _conv2d_reduce(passes)
-        return dx, dw, db, (daff[:Cin] if want_affine else None), (daff[Cin:] if want_affine else None)
-    if planes == 3 and _C2W.eligible(x, w, dil_t, dy, scale, shift, mask_src):
-        # fp32 matrix-core kernels; the partial rows (dw | dbias | dscale | dshift) are reduced at once into fresh tensors
-        dx, buf, nblocks, npart = _conv2d_wide_bwd(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode,
-                                                   want_dx, want_dw or want_db, want_affine)
-        nw = KT * KF * Cin * Cout
-        dw = torch.zeros_like(w) if want_dw else None
-        db = torch.zeros(Cout, dtype=torch.float32, device=dev) if want_db else None
-        daff = torch.zeros(2 * Cin, dtype=torch.float32, device=dev) if want_affine else None
-        passes = []
-        if want_dw or want_db:
-            passes.append((buf, 0, nblocks, npart, nw, Cout, dw, db))
-        if want_affine:
-            passes.append((buf, 4 * (nw + Cout), nblocks, npart, Cin, Cin, daff[:Cin], daff[Cin:]))
-        if passes:
-            _conv2d_reduce(passes)
-        return dx, dw, db, (daff[:Cin] if want_affine else None), (daff[Cin:] if want_affine else None)
+        wp = _mfma_pass(buf, nblocks, npart, w)
+    elif tier == C2_WIDE:
+        # fp32 matrix-core kernels: rows dw | dbias | dscale | dshift from the buffer's first byte (no buffer where no sums are wanted)
+        dx = torch.empty_like(x) if want_dx else None
+        nws = _hip.lib().ptts_conv2d_wide_bwd_workspace_bytes(B, T, F, Cin, Cout, KT, KF, dil_t) if (want_rows or want_affine) else 0
+        buf, nblocks, npart = _rows_call('ptts_conv2d_wide_bwd_partials', nws, dev,
+                                         (ptr(dy), ptr(x), ptr(w), ptr(scale), ptr(shift), ptr(mask_src), ptr(dx)),
+                                         (int(want_rows), int(want_affine), B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha),
+                                         (B, T, F, Cin, Cout, mode, int(want_dx), int(want_rows), int(want_affine)))
+        wp = _Pass(buf, 0, nblocks, npart, KT * KF * Cin * Cout, Cout, None, None)
+    if tier == C2_MFMA_AFFINE or tier == C2_WIDE:        # the affine's sums ride in the same rows
+        return dx, (wp if want_rows else None), (_affine_pass(wp, Cin) if want_affine else None), None
+    nws = _hip.lib().ptts_conv2d_bwd_workspace_bytes(B, T, F, Cin, Cout, KT, KF, dil_t)
     dx = torch.empty_like(x) if want_dx else None
-    dw = torch.empty_like(w) if (want_dw or want_db) else None
+    if queue and nws > 16:
+        # the packed-FMA stencil has a tiled kernel: partial rows, a row = dW | dbias | the 2 Cin sums of a BatchNorm-fused input (unused)
+        nw = KT * KF * Cin * Cout
+        buf = torch.empty(int(nws), dtype=torch.uint8, device=dev)
+        nblocks = ctypes.c_int(0)
+        call('ptts_conv2d_bwd_partials', ptr(dy), ptr(x), ptr(w), ptr(mask_src), ptr(dx), ptr(buf), buf.numel(),
+             ctypes.byref(nblocks), B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha, stream(),
+             tag=(B, T, F, Cin, Cout, mode, int(want_dx), 1, 0))
+        return dx, _Pass(buf, _ROWS_HEAD, nblocks.value, nw + Cout + 2 * Cin, nw, Cout, None, None), None, None
+    # no partial rows (none asked, or no tiled kernel: the queue declines): the launch reduces through a workspace and finishes them
+    dw = torch.empty_like(w) if want_rows else None
     db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_db else None
     dscale = torch.empty(Cin, dtype=torch.float32, device=dev) if want_affine else None
     dshift = torch.empty(Cin, dtype=torch.float32, device=dev) if want_affine else None
-    nws = _hip.lib().ptts_conv2d_bwd_workspace_bytes(B, T, F, Cin, Cout, KT, KF, dil_t)
     ws = _workspace(nws, dev)
     call('ptts_conv2d_bwd', ptr(dy), ptr(x), ptr(w), ptr(scale), ptr(shift), ptr(mask_src),
          ptr(dx), ptr(dw), ptr(db), ptr(dscale), ptr(dshift), ptr(ws), ws.numel(),
          B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha, stream(),
-         tag=(B, T, F, Cin, Cout, mode, int(want_dx), int(want_dw or want_db), int(want_affine)))
-    return dx, (dw if want_dw else None), db, dscale, dshift
+         tag=(B, T, F, Cin, Cout, mode, int(want_dx), int(want_rows), int(want_affine)))
+    return dx, None, None, ((dw if want_dw else None), db, dscale, dshift)
 
 
-def _conv2d_bwd_deferred(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_dx, gw, gb, planes=3):
-    """conv2d backward whose dw / dbias stay as per-workgroup partial sums in a buffer of their own; the reduction into
-    the gradient buffers gw / gb is queued for the grouped launch at flush time.  Returns dx (or None), or False when
-    neither the stencil nor the wide tier has a tiled kernel for this shape."""
-    B, T, F, Cin = x.shape
-    KT, KF, _, Cout = w.shape
-    if (planes == 1 or _C2M.enabled) and _C2M.eligible(x, w, dil_t) and 0.0 <= alpha <= 1.0:
-        dx, rows = _conv2d_mfma_bwd(dy, x, w, mask_src, mode, alpha, dil_t, pad_mode, want_dx, True, planes)
-        _Deferred.queue_conv(rows + (gw, gb))
-        return dx
-    if planes == 3 and _C2W.eligible(x, w, dil_t, dy, mask_src):
-        dx, buf, nblocks, npart = _conv2d_wide_bwd(dy, x, w, None, None, mask_src, mode, alpha, dil_t, pad_mode, want_dx, True, False)
-        _Deferred.queue_conv((buf, 0, nblocks, npart, KT * KF * Cin * Cout, Cout, gw, gb))
-        return dx
-    nws = _hip.lib().ptts_conv2d_bwd_workspace_bytes(B, T, F, Cin, Cout, KT, KF, dil_t)
-    if nws <= 16:
-        return False
-    dev = x.device
-    buf = torch.empty(int(nws), dtype=torch.uint8, device=dev)
-    dx = torch.empty_like(x) if want_dx else None
-    nblocks = ctypes.c_int(0)
-    call('ptts_conv2d_bwd_partials', ptr(dy), ptr(x), ptr(w), ptr(mask_src), ptr(dx), ptr(buf), buf.numel(),
-         ctypes.byref(nblocks), B, T, F, Cin, Cout, KT, KF, dil_t, pad_mode, mode, alpha, stream(),
-         tag=(B, T, F, Cin, Cout, mode, int(want_dx), 1, 0))
-    nw = KT * KF * Cin * Cout
-    _Deferred.queue_conv((buf, 4096, nblocks.value, nw + Cout + 2 * Cin, nw, Cout, gw, gb))
-    return dx
+def _conv2d_target(want_w, gw, want_b, gb):
+    """Where a pass over a kernel and its bias lands, THE rule: queued onto (gw, gb), the gradient buffers noted at forward time (None for
+    one not wanted), while deferred_weight_grads() is live and every wanted buffer exists; else None -- reduced now, handed to autograd."""
+    if _Deferred.live() and (not want_w or gw is not None) and (not want_b or gb is not None):
+        return (gw if want_w else None, gb if want_b else None)
+    return None
+
+
+def _conv2d_land(passes, likes, targets=None):
+    """Land passes (an entry may be None: skipped).  targets, a (gw, gb) of _conv2d_target per pass: queued, returns None.  Else ONE
+    reduction now into fresh zeroed tensors, returned as a (dw, dbias) per entry.  likes, per pass: (w, want_dw, want_db), dw shaped
+    like w -- or None for a pass of plain sums: both, as the halves of one vector."""
+    if targets is not None:
+        _Deferred.queue_conv(*[_Pass(*p[:6], *t) for p, t in zip(passes, targets) if p is not None])
+        return None
+    out = []
+    for p, like in zip(passes, likes):
+        dw = db = None
+        if p is not None and like is None:
+            both = torch.zeros(p.nw + p.cout, dtype=torch.float32, device=p.buf.device)
+            dw, db = both[:p.nw], both[p.nw:]
+        elif p is not None:
+            dw = torch.zeros_like(like[0]) if like[1] else None
+            db = torch.zeros(p.cout, dtype=torch.float32, device=p.buf.device) if like[2] else None
+        out.append((dw, db))
+    todo = [_Pass(*p[:6], *o) for p, o in zip(passes, out) if p is not None]
+    if todo:
+        _conv2d_reduce(todo)
+    return out
+
+
+def _conv2d_bwd(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_dw, want_db, want_affine, planes, target):
+    """(dx, dw, db, dscale, dshift), None where not wanted.  target = (gw, gb) (_conv2d_target): dw / db are queued onto them and come
+    back None, unless the launch finished them itself.  (The queue's producers validated at forward time; the immediate form does here.)"""
+    if target is None:
+        if planes == 1:
+            _st(dy, 'conv2d_bwd.dy'); _st(x, 'conv2d_bwd.x'); _st(mask_src); f32c(w)
+            assert scale is None and not want_affine, 'conv2d: no BatchNorm-fused input on the bf16-storage path'
+        else:
+            f32c(dy, 'conv2d_bwd.dy'); f32c(x, 'conv2d_bwd.x'); f32c(w); f32c(scale); f32c(shift); f32c(mask_src)
+        assert dy.shape == x.shape[:3] + w.shape[3:], 'conv2d_bwd: dy shape {} vs {}'.format(tuple(dy.shape), tuple(x.shape[:3] + w.shape[3:]))
+        assert mask_src is None or mask_src.shape == x.shape
+    dx, wp, ap, direct = _conv2d_bwd_launch(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode,
+                                            want_dx, want_dw, want_db, want_affine, planes, target is not None)
+    if direct is not None:
+        return (dx,) + direct
+    got = _conv2d_land((wp, ap), ((w, want_dw, want_db), None), None if target is None else (target,))
+    return (dx, None, None, None, None) if got is None else (dx,) + got[0] + got[1]
+
+
+def _conv2d_bwd_raw(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode,
+                    want_dx, want_dw, want_db, want_affine, planes=3):
+    return _conv2d_bwd(dy, x, w, scale, shift, mask_src, mode, alpha, dil_t, pad_mode, want_dx, want_dw, want_db, want_affine, planes, None)
 
 
 class _DenseSplit(object):
@@ -982,6 +1006,8 @@ class Conv2dFn(torch.autograd.Function):
         dy = dy.contiguous()
         if _Flags.skip_param_grads:
             need_w = need_b = need_aff = False
+        # decided once: the parameter gradients are queued (a BatchNorm-fused input keeps the immediate path)
+        target = _conv2d_target(need_w, ctx.gw, need_b, ctx.gb) if (need_w or need_b) and scale is None and not need_aff else None
         if torch.is_grad_enabled() and need_x:
             # differentiable backward (gradient penalty): dx is itself a Function of (dy, w)
             if scale is not None:
@@ -990,25 +1016,12 @@ class Conv2dFn(torch.autograd.Function):
             dw = db = None
             if need_w or need_b:
                 with torch.no_grad():
-                    if _conv2d_can_defer(ctx, need_w, need_b) and \
-                            _conv2d_bwd_deferred(dy, x, w, None, mode, alpha, dil_t, pad_mode, False,
-                                                 ctx.gw if need_w else None, ctx.gb if need_b else None, planes) is not False:
-                        return dx, None, None, None, None, None, None, None, None, None
-                    _, dw, db, _, _ = _conv2d_bwd_raw(dy, x, w, None, None, None, mode, alpha, dil_t, pad_mode,
-                                                      False, need_w, need_b, False, planes)
+                    _, dw, db, _, _ = _conv2d_bwd(dy, x, w, None, None, None, mode, alpha, dil_t, pad_mode,
+                                                  False, need_w, need_b, False, planes, target)
             return dx, dw, db, None, None, None, None, None, None, None
-        if (need_w or need_b) and not need_aff and scale is None and _conv2d_can_defer(ctx, need_w, need_b):
-            dxd = _conv2d_bwd_deferred(dy, x, w, None, mode, alpha, dil_t, pad_mode, need_x,
-                                       ctx.gw if need_w else None, ctx.gb if need_b else None, planes)
-            if dxd is not False:
-                return dxd, None, None, None, None, None, None, None, None, None
-        dx, dw, db, dscale, dshift = _conv2d_bwd_raw(dy, x, w, scale, shift, None, mode, alpha, dil_t, pad_mode,
-                                                     need_x, need_w, need_b, need_aff, planes)
+        dx, dw, db, dscale, dshift = _conv2d_bwd(dy, x, w, scale, shift, None, mode, alpha, dil_t, pad_mode,
+                                                 need_x, need_w, need_b, need_aff, planes, target)
         return dx, dw, db, dscale, dshift, None, None, None, None, None
-
-
-def _conv2d_can_defer(ctx, need_w, need_b):
-    return _Deferred.live() and (not need_w or ctx.gw is not None) and (not need_b or ctx.gb is not None)
 
 
 class Conv2dBwdDataFn(torch.autograd.Function):
@@ -1035,25 +1048,17 @@ class Conv2dBwdDataFn(torch.autograd.Function):
         u = u.contiguous()
         m2, msk = (IN_MASKMUL, x) if mode == IN_LRELU else (IN_NONE, None)
         cot_dy = cot_w = None
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[2] and m2 == IN_MASKMUL and _C2M.enabled and _C2M.eligible(u, w, dil_t) and \
-                0.0 <= alpha <= 1.0 and _C2MFused.ok(u, dil_t, pad_mode, planes):
+        target = _conv2d_target(True, ctx.gw, False, None) if ctx.needs_input_grad[2] else None
+        if ctx.needs_input_grad[0] and ctx.needs_input_grad[2] and m2 == IN_MASKMUL and _C2MFused.ok(u, dil_t, pad_mode, planes) and \
+                _conv2d_tier(u, w, dil_t, alpha, planes, ()) == C2_MFMA:
             # the masked forward and the weight gradient of the sweep read the same staged tile u . lrelu'(x): one launch
             cot_dy, buf, nblocks, npart = _conv2d_mfma_bwd_fused(2, u, dy, msk, w, alpha)
-            rows = (buf, 4096, nblocks, npart, w.numel(), w.shape[3])
-            if _Deferred.live() and ctx.gw is not None:
-                _Deferred.queue_conv(rows + (ctx.gw, None))
-            else:
-                cot_w = torch.zeros_like(w)
-                _conv2d_reduce([rows + (cot_w, None)])
-            return cot_dy, None, cot_w, None, None, None, None, None, None
+            got = _conv2d_land((_mfma_pass(buf, nblocks, npart, w),), ((w, True, False),), None if target is None else (target,))
+            return cot_dy, None, (None if got is None else got[0][0]), None, None, None, None, None, None
         if ctx.needs_input_grad[0]:
             cot_dy = _conv2d_fwd_raw(u, w, None, None, None, msk, m2, alpha, dil_t, pad_mode, planes, _is16(dy))
         if ctx.needs_input_grad[2]:
-            if _Deferred.live() and ctx.gw is not None and \
-                    _conv2d_bwd_deferred(dy, u, w, msk, m2, alpha, dil_t, pad_mode, False, ctx.gw, None, planes) is not False:
-                return cot_dy, None, None, None, None, None, None, None, None
-            _, cot_w, _, _, _ = _conv2d_bwd_raw(dy, u, w, None, None, msk, m2, alpha, dil_t, pad_mode,
-                                                False, True, False, False, planes)
+            _, cot_w, _, _, _ = _conv2d_bwd(dy, u, w, None, None, msk, m2, alpha, dil_t, pad_mode, False, True, False, False, planes, target)
         return cot_dy, None, cot_w, None, None, None, None, None, None
 
 
@@ -1183,19 +1188,15 @@ def _chain_x0(x0):
     return x0
 
 
-def _chain_reduce(parts, nblocks, npart, ws, gws, gbs, want_b):
-    """Partial rows [L][nblocks][npart] -> the gradient buffers: queued for the grouped launch while deferred_weight_grads()
-    is live (gws / gbs: the parameters' .grad views, as noted at forward time), else reduced now into fresh tensors, which
-    are returned."""
-    L = len(ws)
-    rows = [(parts, l * nblocks * npart * 4, nblocks, npart, w.numel(), w.shape[3]) for l, w in enumerate(ws)]
-    if _Deferred.live() and all(g is not None for g in gws) and (not want_b or all(g is not None for g in gbs)):
-        _Deferred.queue_conv(*[r + (gw, gb if want_b else None) for r, gw, gb in zip(rows, gws, gbs)])
-        return None, None
-    dws = [torch.zeros_like(w) for w in ws]
-    dbs = [torch.zeros(w.shape[3], dtype=torch.float32, device=w.device) for w in ws] if want_b else [None] * L
-    _conv2d_reduce([r + (dw, db) for r, dw, db in zip(rows, dws, dbs)])
-    return dws, dbs
+def _chain_land(rows, ws, gws, gbs, want_b):
+    """The passes of a chain launch -- rows = (buffer, nblocks, npart), the buffer holds [L][nblocks][npart] floats, no header: layer
+    l's rows start l * nblocks * npart * 4 bytes in -- landed (_conv2d_land) onto gws / gbs, the parameters' .grad views as noted at
+    forward time.  Returns (dws, dbs): lists of fresh tensors, or (None, None) when queued."""
+    parts, nblocks, npart = rows
+    passes = [_Pass(parts, l * nblocks * npart * 4, nblocks, npart, w.numel(), w.shape[3], None, None) for l, w in enumerate(ws)]
+    targets = [_conv2d_target(True, gw, want_b, gb) for gw, gb in zip(gws, gbs)]
+    got = _conv2d_land(passes, [(w, True, want_b) for w in ws], None if None in targets else targets)
+    return (None, None) if got is None else ([g[0] for g in got], [g[1] for g in got])
 
 
 class Conv2dChainFn(torch.autograd.Function):
@@ -1243,13 +1244,10 @@ class Conv2dChainFn(torch.autograd.Function):
                      B, T, F, L, alpha, stream(), tag=(B, T, F, L, 0))
         if need_w:
             with torch.no_grad():
-                parts = torch.empty(_hip.lib().ptts_conv2d_chain_partials_bytes(L), dtype=torch.uint8, device=x0.device)
-                nblocks, npart = ctypes.c_int(0), ctypes.c_int(0)
-                call('ptts_conv2d_chain_bwd', ptr(d_last), int(_is16(d_last)), ptr(x0), x0.stride(1), ptr(maps), ptr(a_last), ptr(tab),
-                     ptr(parts), parts.numel(), ctypes.byref(nblocks), ctypes.byref(npart), B, T, F, L, int(ws[0].shape[2]), alpha, stream(),
-                     tag=(B, T, F, L))
-                want_b = any(ctx.has_b)
-                dws, dbs = _chain_reduce(parts, nblocks.value, npart.value, ws, ctx.gws, ctx.gbs, want_b)
+                rows = _rows_call('ptts_conv2d_chain_bwd', _hip.lib().ptts_conv2d_chain_partials_bytes(L), x0.device,
+                                  (ptr(d_last), int(_is16(d_last)), ptr(x0), x0.stride(1), ptr(maps), ptr(a_last), ptr(tab)),
+                                  (B, T, F, L, int(ws[0].shape[2]), alpha), (B, T, F, L))
+                dws, dbs = _chain_land(rows, ws, ctx.gws, ctx.gbs, any(ctx.has_b))
                 if dws is not None:
                     for l in range(L):
                         grads[2 * l] = dws[l]
@@ -1287,14 +1285,13 @@ class Conv2dChainBwdDataFn(torch.autograd.Function):
         B, T, F, _ = a_last.shape
         u0 = f32c(u0.contiguous(), 'conv2d_chain.u0')
         out = torch.empty((B, T, F, 4), dtype=d_dtype, device=u0.device)
-        parts = torch.empty(_hip.lib().ptts_conv2d_chain_partials_bytes(L), dtype=torch.uint8, device=u0.device)
-        nblocks, npart = ctypes.c_int(0), ctypes.c_int(0)
-        call('ptts_conv2d_chain_second', ptr(u0), ptr(gmaps), ptr(maps), ptr(a_last), ptr(tab), ptr(out), int(d_dtype == torch.bfloat16),
-             ptr(parts), parts.numel(), ctypes.byref(nblocks), ctypes.byref(npart), B, T, F, L, cin0, alpha, stream(), tag=(B, T, F, L))
+        rows = _rows_call('ptts_conv2d_chain_second', _hip.lib().ptts_conv2d_chain_partials_bytes(L), u0.device,
+                          (ptr(u0), ptr(gmaps), ptr(maps), ptr(a_last), ptr(tab), ptr(out), int(d_dtype == torch.bfloat16)),
+                          (B, T, F, L, cin0, alpha), (B, T, F, L))
         need_w = any(ctx.needs_input_grad[6 + l] for l in range(L))
         grads = [None] * L
         if need_w:
-            dws, _ = _chain_reduce(parts, nblocks.value, npart.value, ws, ctx.gws, [None] * L, False)
+            dws, _ = _chain_land(rows, ws, ctx.gws, [None] * L, False)
             if dws is not None:
                 grads = dws
         return (out if ctx.needs_input_grad[0] else None, None, None, None, None, None) + tuple(grads)

@@ -59,6 +59,34 @@ def test_switch_and_path_description():
         ops.conv2d_wide(None)
 
 
+# (Cin, Cout, KT, KF, dil_t) -> the word in its description with every switch on; a tier switched off hands its shapes down
+TIERS = dict([(s + (1,), 'conv2d_wide') for s in TAKEN] + [(s + (1,), 'generic') for s in DECLINED] +
+             [((4, 4, 5, 5, d), 'conv2d_mfma') for d in (1, 2, 8)] + [((4, 4, 5, 5, 3), 'stencil'), ((1, 4, 5, 5, 1), 'stencil'),
+                                                                      ((2, 2, 3, 3, 1), 'stencil')])
+DOWN = {'conv2d_mfma': 'stencil', 'conv2d_wide': 'generic'}
+
+
+@pytest.mark.parametrize('mfma', [True, False])
+@pytest.mark.parametrize('wide', [True, False])
+def test_path_description_names_the_tier_of_the_shape_rule(mfma, wide):
+    """One rule: what conv2d_path_description says of a shape is the tier _conv2d_shape_tier returns, for every switch setting;
+    (4, 4, 5, 5) at dilation 3 is no matrix-core shape."""
+    from percivaltts_amd import ops
+    off = [t for t, on in (('conv2d_mfma', mfma), ('conv2d_wide', wide)) if not on]
+    try:
+        ops.conv2d_mfma(mfma)
+        ops.conv2d_wide(wide)
+        for (Cin, Cout, KT, KF, dil), word in TIERS.items():
+            said = ops.conv2d_path_description((F_REF, Cin, Cout, KT, KF, dil))
+            assert (DOWN[word] if word in off else word) in said, (Cin, Cout, KT, KF, dil, said)
+            assert said == ops._conv2d_shape_tier(F_REF, Cin, Cout, KT, KF, dil), (Cin, Cout, KT, KF, dil)
+            if dil == 1:
+                assert said == ops.conv2d_path_description((F_REF, Cin, Cout, KT, KF))
+    finally:
+        ops.conv2d_mfma(None)
+        ops.conv2d_wide(None)
+
+
 @pytest.mark.parametrize('case', [(2, 12, 9, 8, 8, 5, 5, 1), (64, 400, 65, 16, 16, 5, 5, 1), (1, 37, 129, 8, 8, 5, 5, 1),
                                   (3, 100, 65, 1, 16, 3, 3, 1), (2, 50, 33, 12, 8, 7, 7, 2), (1, 1, 5, 8, 1, 5, 3, 1)])
 def test_workspace_covers_the_partial_rows(lib, case):

@@ -6,7 +6,8 @@ torch.cuda.current_stream and _hip.stream_id are patched to match.
 GPU: every producer of the queue, each case twice -- its backward inside deferred_weight_grads() and without it -- against the fp64
 torch result on the CPU, at the tolerances the op-level tests of these reductions use: rtol 2e-4 / atol 1e-4 for dW and db and RT / AT
 for dx (tests/test_ops_gpu.py), 2e-3 relative L2 against the same-roundings restatement for the chain (tests/test_chain_gpu.py),
-DSUM_TOL for the BatchNorm sums (tests/test_elementwise.py), G_TOL for the LSTM (tests/test_lstm.py).  Parameters are leaves whose
+DSUM_TOL for the BatchNorm sums (tests/test_elementwise.py), G_TOL for the LSTM (tests/test_lstm.py), the bf16 budget of
+test_conv2d_bf16_storage_layer (tests/test_ops_gpu.py) for the bf16-storage Conv2D layer.  Parameters are leaves whose
 .grad is preallocated to zeros, so that grad_target finds them."""
 import contextlib
 import functools
@@ -178,6 +179,13 @@ CONV = {
     'unfused': (2, 40, 7, 4, 4, 5, 2, True, True),        # matrix cores, dx through the transposed table + the partial rows
     'stencil': (2, 12, 9, 1, 4, 5, 1, False, False),      # packed-FMA stencil with partial rows
     'generic': (2, 10, 7, 3, 5, 3, 1, False, True),       # no tiled kernel: the queue declines
+    'wide': (2, 12, 9, 8, 8, 5, 1, False, True),          # fp32 matrix-core kernels, partial rows from the buffer's first byte
+    'bn-fused': (2, 16, 65, 4, 4, 5, 1, False, True),     # BatchNorm-fused input: the affine's sums behind dW | dbias, never queued
+    'bn-fused-no-stats': (2, 16, 65, 4, 4, 5, 1, False, True),       # conv_bn_stats(False): the generic kernel
+    'bn-wide': (2, 12, 9, 8, 8, 5, 1, False, True),       # BatchNorm-fused input of a wide layer: never queued
+    'fused-switched-off': (2, 16, 65, 4, 4, 5, 1, False, True),  # conv2d_fused(False): the pair of launches
+    'fused-no-mfma': (2, 16, 65, 4, 4, 5, 1, False, True),   # conv2d_mfma(False): the stencil's kernels
+    'bf16': (2, 16, 65, 4, 4, 5, 1, False, True),         # bf16 = 'out32': one-plane kernels, no fused launch
 }
 # the backward's launches: (deferred, immediate)
 CONV_BWD = {
@@ -185,23 +193,67 @@ CONV_BWD = {
     'unfused': (['ptts_conv2d_mfma_fwd', 'ptts_conv2d_mfma_wgrad_partials'],) * 2,
     'stencil': (['ptts_conv2d_bwd_partials'], ['ptts_conv2d_bwd']),
     'generic': (['ptts_conv2d_bwd'],) * 2,
+    'wide': (['ptts_conv2d_wide_bwd_partials'],) * 2,
+    'bn-fused': (['ptts_conv2d_mfma_bwd_fused_affine'],) * 2,
+    'bn-fused-no-stats': (['ptts_conv2d_bwd'],) * 2,
+    'bn-wide': (['ptts_conv2d_wide_bwd_partials'],) * 2,
+    'fused-switched-off': (['ptts_conv2d_mfma_fwd', 'ptts_conv2d_mfma_wgrad_partials'],) * 2,
+    'fused-no-mfma': (['ptts_conv2d_bwd_partials'], ['ptts_conv2d_bwd']),
+    'bf16': (['ptts_conv2d_mfma_fwd', 'ptts_conv2d_mfma_wgrad_partials'],) * 2,
 }
+CONV_QUEUED = {'fused', 'unfused', 'stencil', 'wide', 'fused-switched-off', 'fused-no-mfma', 'bf16'}   # inside the context
+CONV_REDUCED = {'fused', 'unfused', 'wide', 'bn-fused', 'bn-wide', 'fused-switched-off', 'bf16'}   # where not queued: ONE reduce at once
+CONV_AFFINE = {'bn-fused', 'bn-fused-no-stats', 'bn-wide'}                                             # input lrelu(scale x + shift)
+CONV_SWITCH = {'bn-fused-no-stats': 'conv_bn_stats', 'fused-switched-off': 'conv2d_fused', 'fused-no-mfma': 'conv2d_mfma'}
+CONV_BF16 = {'bf16': 'out32'}
+BF16_TOL = 2.0 ** -8       # relative L2 of dx and dW at the bf16 budget: tests/test_ops_gpu.py, test_conv2d_bf16_storage_layer
+BF16_DB = dict(rtol=2e-4, atol=1e-3)                    # db sums the raw dy values (the same test)
 
 
 @functools.lru_cache(maxsize=None)
-def conv_case(name):
-    """fp64: the inputs (x, w, b, dy) and the gradients (dx, dw, db)."""
+def conv_case_full(name):
+    """fp64: the inputs (x, w, b, dy, scale, shift) and the gradients (dx, dw, db, dscale, dshift); scale / shift are None
+    without a BatchNorm-fused input.  The bf16 case: the oracle with the kernels' roundings (the activation and the kernel to
+    bf16, exact products), as in tests/test_ops_gpu.py, test_conv2d_bf16_storage_layer."""
     B, T, F, Cin, Cout, K, dil, causal, act = CONV[name]
     g = gen(31)
     x, w, b, dy = randn(g, B, T, F, Cin), randn(g, K, K, Cin, Cout) * 0.3, randn(g, Cout), randn(g, B, T, F, Cout)
-    xr, wr, br = (t.clone().requires_grad_(True) for t in (x, w, b))
-    O.conv2d_nhwc(O.lrelu(xr) if act else xr, wr, br, dil_t=dil, causal=causal).backward(dy)
-    return (x, w, b, dy), (xr.grad, wr.grad, br.grad)
+    sc = sh = None
+    if name in CONV_AFFINE:
+        sc, sh = torch.rand(Cin, generator=g, dtype=torch.float64) + 0.5, randn(g, Cin)
+    leaves = [t.clone().requires_grad_(True) for t in (x, w, b, sc, sh) if t is not None]
+    xr, wr, br = leaves[:3]
+    a = xr if sc is None else xr * leaves[3] + leaves[4]
+    a = O.lrelu(a) if act else a
+    if name in CONV_BF16:
+        a, wr = O.bf16_st(a), O.bf16_st(wr)
+    O.conv2d_nhwc(a, wr, br, dil_t=dil, causal=causal).backward(dy)
+    return (x, w, b, dy, sc, sh), tuple(t.grad for t in leaves) + (None,) * (5 - len(leaves))
 
 
-def conv_layer(ops, name, x, w, b):
+def conv_case(name):
+    """fp64: the inputs (x, w, b, dy) and the gradients (dx, dw, db)."""
+    ins, grads = conv_case_full(name)
+    return ins[:4], grads[:3]
+
+
+@contextlib.contextmanager
+def conv_switches(ops, name):
+    """The case's tier switch off, and back at its default afterwards."""
+    sw = CONV_SWITCH.get(name)
+    if sw is not None:
+        getattr(ops, sw)(False)
+    try:
+        yield
+    finally:
+        if sw is not None:
+            getattr(ops, sw)(None)
+
+
+def conv_layer(ops, name, x, w, b, affine=()):
     dil, causal, act = CONV[name][6:]
-    return ops.conv2d(ops.Lazy(x, lrelu=True) if act else x, w, b, dil_t=dil, pad_mode=ops.PAD_CAUSAL if causal else ops.PAD_SAME)
+    return ops.conv2d(ops.Lazy(x, *affine, lrelu=True) if act else x, w, b, dil_t=dil, pad_mode=ops.PAD_CAUSAL if causal else ops.PAD_SAME,
+                      bf16=CONV_BF16.get(name))
 
 
 def conv_step(ops, name, leaves=None):
@@ -212,11 +264,23 @@ def conv_step(ops, name, leaves=None):
     return xd, wd, bd
 
 
-def conv_check(name, leaves, times=1):
-    _, (dx, dw, db) = conv_case(name)
+def l2(got, want):
+    return float((got.detach().double().cpu() - want).norm() / want.norm())
+
+
+def conv_check(name, leaves, times=1, affine=()):
+    _, (dx, dw, db, dsc, dsh) = conv_case_full(name)
+    if name in CONV_BF16:
+        errs = l2(leaves[0].grad, times * dx), l2(leaves[1].grad, times * dw)
+        print(name, 'relative L2 of dx, dw', errs)
+        assert max(errs) < BF16_TOL, errs
+        close(leaves[2].grad, times * db, what=name + ' db', **BF16_DB)
+        return
     close(leaves[0].grad, times * dx, RT, AT, what=name + ' dx')
     close(leaves[1].grad, times * dw, what=name + ' dw', **W_TOL)
     close(leaves[2].grad, times * db, what=name + ' db', **W_TOL)
+    for nm, p, want in zip(('dscale', 'dshift'), affine, (dsc, dsh)):
+        close(p.grad, times * want, what=name + ' ' + nm, **W_TOL)
 
 
 @pytest.mark.gpu
@@ -224,12 +288,14 @@ def conv_check(name, leaves, times=1):
 @pytest.mark.parametrize('name', list(CONV))
 def test_conv2d_every_backward_path(ops, name, deferred):
     """Queued passes leave the gradient buffer alone until the context exits, then ONE grouped reduction; a shape without a tiled
-    kernel is declined and its gradient arrives through autograd."""
-    (x, w, b, dy), _ = conv_case(name)
+    kernel is declined and its gradient arrives through autograd, and so does every gradient of a layer with a BatchNorm-fused
+    input (reduced at once, with the affine's sums, in ONE launch)."""
+    (x, w, b, dy, sc, sh), _ = conv_case_full(name)
     xd, wd, bd = dev(x, True), param(w), param(b)
-    with ops._hip.KernelTimer() as kt:
+    affine = (dev(sc, True), dev(sh, True)) if name in CONV_AFFINE else ()
+    with conv_switches(ops, name), ops._hip.KernelTimer() as kt:
         with scope(ops, deferred):
-            y = conv_layer(ops, name, xd, wd, bd)
+            y = conv_layer(ops, name, xd, wd, bd, affine)
             nfwd = len(kt.records)
             y.backward(dev(dy))
             inside, queued = names(kt, nfwd), len(ops._Deferred.conv_items)
@@ -237,13 +303,13 @@ def test_conv2d_every_backward_path(ops, name, deferred):
         total = names(kt, nfwd)
     for k in CONV_BWD[name][0 if deferred else 1]:
         assert inside.count(k) == 1, (k, inside)
-    if deferred and name != 'generic':
+    if deferred and name in CONV_QUEUED:
         assert queued == 1 and REDUCE not in inside and early == 0.0, (queued, inside, early)
         assert total.count(REDUCE) == 1, total
     else:
         assert queued == 0 and early > 0.0
-        assert total.count(REDUCE) == inside.count(REDUCE) == int(name in ('fused', 'unfused')), total
-    conv_check(name, (xd, wd, bd))
+        assert total.count(REDUCE) == inside.count(REDUCE) == int(name in CONV_REDUCED), total
+    conv_check(name, (xd, wd, bd), affine=affine)
 
 
 @pytest.mark.gpu
