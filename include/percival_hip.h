@@ -247,6 +247,19 @@ int ptts_conv2d_mfma_debug(int flags, void* stamp_buf);
  *              gradient maps gamma_l = lrelu'(a_l) . dL/da_l, l = 1 .. L, [L][B][T][FP][4] bf16 (operands of _second)
  *   _second    the backward of _bwd_data w.r.t. d_last and the kernels: u0 = d/d(g0) [B][T][F] fp32 -> out = d/d(d_last)
  *              [B][T][F][4] (fp32 / bf16) and the partial sums of dW_l (rows as _bwd, bias entries zero)
+ * The per-row form, ptts_conv2d_chain_{fwd,bwd,bwd_data,second}_rows: the same passes over a ZERO-PADDED batch.  The arguments
+ * of the plain entry point plus `lengths` (device int32 [B], in front of B; NULL is PTTS_EINVAL): utterance b holds
+ * n_b = min(max(lengths[b], 0), T) real rows.  n_b is the row limit of a tile of utterance b wherever the plain kernels test a
+ * row against T; T stays the pitch of every address.  The rule:
+ *   - every layer sees zeros at t >= n_b: the input, every map a_l, every gradient map d_l / gamma_l and every u_l are zero
+ *     there before the next layer reads them (a pad row whose convolution would give lrelu(bias) included);
+ *   - the pad rows of x0, d_last, u0, maps and gmaps are never looked at (a loader selects a zero in their place and never
+ *     multiplies): they may hold anything, NaN included;
+ *   - EVERY row 0 .. T-1 of every output is written -- maps, a_last, gmaps, g0, out: real rows as computed, pad rows as +0.0,
+ *     whatever the buffer held (consumers such as ptts_gp_sqnorm and the dense layers' weight gradients read them without lengths);
+ *   - the sums of dW_l / db_l run over real rows only.
+ * A real row equals, bit for bit, what the plain entry point gives for utterance b alone at T = n_b; with every n_b = T every
+ * output, partial rows included, equals the plain entry point's.
  * ------------------------------------------------------------------------------------- */
 /* 1 when the stack has a chain kernel: 2 <= F <= 1024 bins (run on the device up to 200), 1 <= L <= 8 layers, 1 <= Cin0 <= 4,
  * C = 4 filters of 5 x 5 */
@@ -270,6 +283,16 @@ int ptts_conv2d_chain_bwd_data(const void* d_last, int d_bf16, const void* maps,
 int ptts_conv2d_chain_second(const float* u0, const void* gmaps, const void* maps, const void* a_last, const void* tables,
                              void* out, int out_bf16, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out,
                              int B, int T, int F, int L, int cin0, float alpha, void* stream);
+int ptts_conv2d_chain_fwd_rows(const float* x0, long long ldx, const void* tables, void* maps, void* a_last,
+                               const int* lengths, int B, int T, int F, int L, float alpha, void* stream);
+int ptts_conv2d_chain_bwd_rows(const void* d_last, int d_bf16, const float* x0, long long ldx, const void* maps, const void* a_last,
+                               const void* tables, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out,
+                               const int* lengths, int B, int T, int F, int L, int cin0, float alpha, void* stream);
+int ptts_conv2d_chain_bwd_data_rows(const void* d_last, int d_bf16, const void* maps, const void* a_last, const void* tables,
+                                    void* gmaps, float* g0, const int* lengths, int B, int T, int F, int L, float alpha, void* stream);
+int ptts_conv2d_chain_second_rows(const float* u0, const void* gmaps, const void* maps, const void* a_last, const void* tables,
+                                  void* out, int out_bf16, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out,
+                                  const int* lengths, int B, int T, int F, int L, int cin0, float alpha, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * fp32 GEMM on the MFMA pipe (v_mfma_f32_32x32x2_f32), with implicit-convolution row

@@ -30,9 +30,19 @@
 // bits of the unit index swapped, lanes 4..11 of an MFMA column own the even rows): conflict-free ds_read_b128 fragments.
 // Internal maps lie in HBM as [B][T][FP][4] bf16 with FP = F rounded up to even and the pad bin zero, so that a row is a whole
 // number of 16-byte units; the last map a_L is written unpadded ([B][T][F][4]): the dense layers read it as [B*T, 4F].
+//
+// This file is compiled TWICE: as itself (the plain entry points and the kernels they have always launched), and through
+// conv2d_chain_rows.hip with PTTS_CHAIN_ROWS = 1 (the ..._rows entry points and the ROWS = true instantiations of the same
+// templates).  Two translation units, because the per-row instantiations in the plain kernels' module changed the register
+// allocation of one of THOSE (the blocked second-order kernel: 242 -> 234 VGPRs, every instruction the same, other registers) --
+// and these kernels' figures are measured ones.
+#ifndef PTTS_CHAIN_ROWS
+#define PTTS_CHAIN_ROWS 0
+#endif
 #include "common.h"
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace ptts {
 namespace c2c {
@@ -43,6 +53,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16;
 
+constexpr bool ROWS_TU = PTTS_CHAIN_ROWS != 0;
 constexpr int C = 4, KT = 5, KF = 5;
 constexpr int LMAX = 8;            // layers per chain
 constexpr int TR = 32;             // a tile's own time rows
@@ -90,7 +101,7 @@ __device__ __forceinline__ void stamp(unsigned long long* dbg, int slot) {
 __device__ __forceinline__ void stamp_w(unsigned long long* dbg, int s, int wave, int lane, int i) {
     if (dbg && s == 1 && lane == 0 && (wave == 0 || wave == 7)) dbg[(size_t)blockIdx.x * 32 + 16 + (wave == 7 ? 8 : 0) + i] = __builtin_amdgcn_s_memrealtime();
 }
-static unsigned long long* g_dbg = nullptr;
+static unsigned long long* g_dbg = nullptr;        // (set in the plain translation unit only: per-row launches carry no stamps)
 
 // ------------------------------------------------------------------------------------------------------------
 // operand tables of all layers, both directions (layout of conv2d_mfma.hip with one plane):
@@ -99,6 +110,7 @@ static unsigned long long* g_dbg = nullptr;
 // a layer with fewer than four input channels (the first one) has the missing channels zero.
 // ------------------------------------------------------------------------------------------------------------
 struct TabArgs { const float* w[LMAX]; const float* b[LMAX]; int cin[LMAX]; };
+#if !PTTS_CHAIN_ROWS
 __global__ void chain_tables_kernel(TabArgs a, u16* __restrict__ tab, float* __restrict__ bias) {
     const int l = blockIdx.x >> 1, transposed = blockIdx.x & 1;
     const float* __restrict__ w = a.w[l];
@@ -120,6 +132,7 @@ __global__ void chain_tables_kernel(TabArgs a, u16* __restrict__ tab, float* __r
     if (!transposed && idx < C) bias[l * C + idx] = a.b[l] ? a.b[l][idx] : 0.f;
     if (blockIdx.x == 0 && idx < 16) reinterpret_cast<unsigned*>(bias + LMAX * C)[idx] = 0u;       // the zero block
 }
+#endif
 
 // ------------------------------------------------------------------------------------------------------------
 // geometry of a launch
@@ -195,8 +208,8 @@ struct MapDma {
     }
     // rows [t_org, t_org + nrows) of utterance b, bins of block kb -> tile (row 0 <-> t_org).  A block's origin is a multiple of
     // 8 bins = 64 bytes: every source unit stays 16-byte aligned.
-    template <bool BLK>
-    __device__ __forceinline__ void issue(const u16* __restrict__ map, const Geo& g, const Blk& kb, int b, int t_org, int nrows, const u16* tile, const u16* zeros) const {
+    template <bool BLK, bool ROWS>
+    __device__ __forceinline__ void issue(const u16* __restrict__ map, const Geo& g, const Blk& kb, int b, int t_org, int nrows, const u16* tile, const u16* zeros, int tlim) const {
         const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         const u16* base = map + (long long)(b * g.T + t_org) * g.FP * C + kb.f_org * C;
         const int ulim = kb.FP * C;                         // a shorter last block; (no data: 0xffff, beyond the limit)
@@ -204,7 +217,7 @@ struct MapDma {
         for (int k = 0; k < NS; ++k) {
             if ((k * NT + wave * 64) >= nrows * RSU) break;                  // wave-uniform: nothing of this instruction is needed
             const int r = pk[k] >> 16, uo = pk[k] & 0xffff, t = t_org + r;
-            const u16* src = ((BLK ? uo < ulim : uo != 0xffff) && (unsigned)t < (unsigned)g.T) ? base + (long long)r * g.FP * C + uo : zeros;
+            const u16* src = ((BLK ? uo < ulim : uo != 0xffff) && (unsigned)t < (unsigned)(ROWS ? tlim : g.T)) ? base + (long long)r * g.FP * C + uo : zeros;
             if (r < nrows) dma16(src, tile + (size_t)(k * NT + wave * 64) * 8);
         }
     }
@@ -214,14 +227,15 @@ template <int NS, int NT>
 struct X0Pref {
     float v[NS];
     // (frequency blocks: x points at the block's bin 0 in the image's row 0, g is the block's geometry)
-    __device__ __forceinline__ void load(const float* __restrict__ x, long long ld, const Geo& g, int b, int t_org, int nrows) {
+    template <bool ROWS>
+    __device__ __forceinline__ void load(const float* __restrict__ x, long long ld, const Geo& g, int b, int t_org, int nrows, int tlim) {
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             const int idx = threadIdx.x + k * NT;
             const int r = (int)__umulhi((unsigned)idx, 59652324u /* ceil(2^32 / 72) */), c = idx - r * 72;
             const int t = t_org + r, f = c - 2;
             v[k] = 0.f;
-            if (r < nrows && (unsigned)t < (unsigned)g.T && (unsigned)f < (unsigned)g.F) v[k] = x[(long long)(b * g.T + t) * ld + f];
+            if (r < nrows && (unsigned)t < (unsigned)(ROWS ? tlim : g.T) && (unsigned)f < (unsigned)g.F) v[k] = x[(long long)(b * g.T + t) * ld + f];
         }
     }
     __device__ __forceinline__ void commit(u16* tile, int nrows) const {
@@ -358,8 +372,8 @@ __device__ __forceinline__ int pair_of(int j, int c, int wave, int ng2, int rot)
 // (A hand-pipelined stream of single units -- reads of unit i + 1 before the MFMAs of unit i -- was built and measured 1.7 x
 // SLOWER: a wave issues one instruction per four cycles, and the scalar bookkeeping of the stream cost more than the LDS latency
 // it hid.  What counts here is the number of instructions per wave and step.)
-template <int NW, bool WG, bool SEQ, bool DUAL = false, class Pre, class Epi>
-__device__ __forceinline__ void conv_chunks(const u16* in, int in_torg, const bf16x8 (&a)[KT], int ta, int tb, const Geo& g,
+template <bool ROWS, int NW, bool WG, bool SEQ, bool DUAL = false, class Pre, class Epi>
+__device__ __forceinline__ void conv_chunks(const u16* in, int in_torg, const bf16x8 (&a)[KT], int ta, int tb, const Geo& g, int tlim,
                                             int wave_, int rot, const LaneOff& lo, f32x4 acc0, Pre&& pre, Epi&& epi) {
     constexpr int NWP = NW > 8 ? 8 : NW, CST = NW / NWP;
     const int wave = wave_ & (NWP - 1), c0 = wave_ / NWP;
@@ -367,7 +381,7 @@ __device__ __forceinline__ void conv_chunks(const u16* in, int in_torg, const bf
     for (int c = c0; c < nch; c += CST) {
         const int tc = min(ta + 16 * c, tb - 16);
         const int t = tc + lo.rl;
-        const bool tin = (unsigned)t < (unsigned)g.T, fresh = t >= ta + 16 * c;
+        const bool tin = (unsigned)t < (unsigned)(ROWS ? tlim : g.T), fresh = t >= ta + 16 * c;
         if (DUAL) {
             // a wave that owns TWO full pairs at this chunk (the waves without weight-gradient work): all twenty fragment reads
             // and the four mask fetches first, then four interleaved MFMA chains -- one exposed LDS latency per chunk instead of
@@ -563,6 +577,25 @@ __device__ __forceinline__ void clear_right_of(u16* tile, int nrows, int ng) {
     }
 }
 
+// The per-row form (ROWS = true; the ..._rows entry points): utterance b holds lengths[b] real rows, the rest of its T rows is
+// padding whose content nobody has looked at.  A tile then works on the image [0, n) x F with n = clamp(lengths[b], 0, T) in
+// place of [0, T) x F: n is the row LIMIT of every loader and epilogue below (`tlim`), T stays the PITCH of every address.  A
+// loader selects between the datum and a zero (the zero page, a literal 0) and never multiplies, so a NaN in a pad row reaches
+// nothing; an epilogue zeroes what lies outside the image as it always did, so every layer reads zeros at t >= n, the sums of
+// dW / db run over real rows, and -- the stores still running to row T -- every pad row of every output is written as +0.0.
+// n is wave-uniform (a tile belongs to one utterance): one scalar load per tile.  ROWS = false: tlim IS g.T, and the code
+// is the one it was.
+// the arguments of a per-row launch: those of the plain one and the lengths (device int32 [B])
+template <class A> struct Rows : A { const int* lengths; };
+template <class A, bool ROWS> using ArgsOf = std::conditional_t<ROWS, Rows<A>, A>;
+template <class A> __device__ __forceinline__ const int* lengths_of(const A&) { return nullptr; }
+template <class A> __device__ __forceinline__ const int* lengths_of(const Rows<A>& a) { return a.lengths; }
+template <bool ROWS>
+__device__ __forceinline__ int row_limit(const int* __restrict__ lengths, int b, int T) {
+    if (!ROWS) return T;
+    return min(max(lengths[b], 0), T);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // forward: x0 [B][T][ldx] fp32 (one channel) -> a_1 .. a_{L-1} (padded maps), a_L (plain)
 // tiles P0, P1 of TR + 4 L rows, row i <-> t = t0 - 2 L + i; a_l is valid on [t0 - 2 (L - l), t0 + TR + 2 (L - l))
@@ -576,9 +609,10 @@ struct FwdArgs {
     FBlocks fb;
 };
 
-template <int NT, bool BLK>
-__global__ __launch_bounds__(NT) void chain_fwd_kernel(FwdArgs a) {
+template <int NT, bool BLK, bool ROWS = false>
+__global__ __launch_bounds__(NT) void chain_fwd_kernel(ArgsOf<FwdArgs, ROWS> a) {
     extern __shared__ __attribute__((aligned(16))) u16 lds[];
+    const int* __restrict__ lengths = lengths_of(a);
     constexpr int NW = NT / 64;
     const Geo g = a.g;
     const int L = g.L;
@@ -604,7 +638,7 @@ __global__ __launch_bounds__(NT) void chain_fwd_kernel(FwdArgs a) {
         Geo gblk;
         if (BLK) gblk = block_geo(g, kb);
         const Geo& gl = BLK ? gblk : g;          // what the tile's helpers work on: the block as an image
-        xp.load(a.x0 + kb.f_org, a.ldx, gl, b, t0 - 2 * L, RB);
+        xp.template load<ROWS>(a.x0 + kb.f_org, a.ldx, gl, b, t0 - 2 * L, RB, row_limit<ROWS>(lengths, b, g.T));
     }
     for (; tile < g.ntiles; tile += gridDim.x) {
         int b, t0;
@@ -612,6 +646,7 @@ __global__ __launch_bounds__(NT) void chain_fwd_kernel(FwdArgs a) {
         Geo gblk;
         if (BLK) gblk = block_geo(g, kb);
         const Geo& gl = BLK ? gblk : g;          // what the tile's helpers work on: the block as an image
+        const int tlim = row_limit<ROWS>(lengths, b, g.T);
         const int torg = t0 - 2 * L;
         if (BLK) rs.init_block(g, kb);
         xp.commit(P0, RB);
@@ -623,7 +658,7 @@ __global__ __launch_bounds__(NT) void chain_fwd_kernel(FwdArgs a) {
             Geo gnxt;
             if (BLK) gnxt = block_geo(g, nk);
             const Geo& gn = BLK ? gnxt : g;
-            xp.load(a.x0 + nk.f_org, a.ldx, gn, nb, nt0 - 2 * L, RB);
+            xp.template load<ROWS>(a.x0 + nk.f_org, a.ldx, gn, nb, nt0 - 2 * L, RB, row_limit<ROWS>(lengths, nb, g.T));
         }
         lds_barrier();
         stamp(a.dbg, 2);
@@ -636,7 +671,7 @@ __global__ __launch_bounds__(NT) void chain_fwd_kernel(FwdArgs a) {
             if (l >= 2) rs.run(in + (t0 - torg) * RS, a.maps + (long long)(l - 2) * g.map_stride + (long long)(b * g.T + t0) * g.FP * C + kb.f_org * C, min(TR, g.T - t0));
             const int ext = 2 * (L - l);
             const int ta = t0 - ext, tb = t0 + TR + ext;
-            conv_chunks<NW, false, false>(in, torg, af, ta, tb, gl, wave, l, lo, bv,
+            conv_chunks<ROWS, NW, false, false>(in, torg, af, ta, tb, gl, tlim, wave, l, lo, bv,
                        [](int, int, int, int) { return 0; },
                        [&](int tc, int, int, int px, f32x4 v, int, bool ok, bool) {
 #pragma unroll
@@ -676,8 +711,8 @@ struct BwdArgs {
 constexpr int MODE_BWD = 0, MODE_DATA = 1;
 
 // the first stage: d_L = lrelu'(a_L) . dL/da_L on rows [ta, tb) -> tile D (zero outside the image); db_L from the own rows
-template <int NT, bool WANT_B, bool BLK>
-__device__ __forceinline__ void stage_d_last(const BwdArgs& a, const Geo& g, const Blk& kb, u16* D, int d_torg, int b, int ta, int tb, int t0, f32x4& bsum) {
+template <int NT, bool WANT_B, bool BLK, bool ROWS>
+__device__ __forceinline__ void stage_d_last(const BwdArgs& a, const Geo& g, const Blk& kb, u16* D, int d_torg, int b, int ta, int tb, int t0, int tlim, f32x4& bsum) {
     const int nb = 4 * (BLK ? kb.ng : g.ng), total = (tb - ta) * nb;
     const unsigned magic = (unsigned)(((1ULL << 32) + (unsigned)nb - 1) / (unsigned)nb);
 #pragma unroll 1
@@ -689,7 +724,7 @@ __device__ __forceinline__ void stage_d_last(const BwdArgs& a, const Geo& g, con
             const int r = (int)__umulhi((unsigned)idx, magic), f = idx - r * nb, t = ta + r;
             rr[k] = idx < total ? t : (1 << 30); ff[k] = f;
             dv[k] = zero4(); av[k] = to_bf16(zero4());
-            if (idx < total && (unsigned)t < (unsigned)g.T && f < (BLK ? kb.F : g.F)) {
+            if (idx < total && (unsigned)t < (unsigned)(ROWS ? tlim : g.T) && f < (BLK ? kb.F : g.F)) {
                 const long long off = ((long long)(b * g.T + t) * g.F + (BLK ? kb.f_org : 0) + f) * C;
                 if (a.d_bf16) dv[k] = to_f32(*reinterpret_cast<const bf16x4*>(reinterpret_cast<const u16*>(a.d_last) + off));
                 else dv[k] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(a.d_last) + off);
@@ -709,9 +744,10 @@ __device__ __forceinline__ void stage_d_last(const BwdArgs& a, const Geo& g, con
     }
 }
 
-template <int NT, int MODE, bool BLK>
-__global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
+template <int NT, int MODE, bool BLK, bool ROWS = false>
+__global__ __launch_bounds__(NT) void chain_bwd_kernel(ArgsOf<BwdArgs, ROWS> a) {
     extern __shared__ __attribute__((aligned(16))) u16 lds[];
+    const int* __restrict__ lengths = lengths_of(a);
     constexpr int NW = NT / 64;
     constexpr bool WG = MODE == MODE_BWD;
     const Geo g = a.g;
@@ -751,6 +787,7 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
         Geo gblk;
         if (BLK) gblk = block_geo(g, kb);
         const Geo& gl = BLK ? gblk : g;          // what the tile's helpers work on: the block as an image
+        const int tlim = row_limit<ROWS>(lengths, b, g.T);
         const int dorg = t0 - EXTD, aorg = t0 - EXTA;
         // the weight gradient's bin groups: the owned ones
         const int wg_lo = BLK ? kb.own_lo >> 2 : 0, wg_ng = BLK ? (kb.own_hi + 3) >> 2 : g.ng;
@@ -760,13 +797,13 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
         {
             f32x4 bs = zero4();
             const int e = WG ? 2 * (L - 1) : 2 * L;
-            if (L >= 2) mp.template issue<BLK>(a.maps + (long long)(L - 2) * g.map_stride, g, kb, b, aorg, RA, A0, zpage);       // in flight under the first stage
-            stage_d_last<NT, WG, BLK>(a, g, kb, D0, dorg, b, t0 - e, t0 + TR + e, t0, bs);
+            if (L >= 2) mp.template issue<BLK, ROWS>(a.maps + (long long)(L - 2) * g.map_stride, g, kb, b, aorg, RA, A0, zpage, tlim);       // in flight under the first stage
+            stage_d_last<NT, WG, BLK, ROWS>(a, g, kb, D0, dorg, b, t0 - e, t0 + TR + e, t0, tlim, bs);
             if (WG) wave_add4(bsl + ((L - 1) * NW + wave) * 4, bs, lane);
             if (L >= 2) {
                 dma_wait();
             } else if (WG) {
-                xp.load(a.x0 + kb.f_org, a.ldx, gl, b, aorg, RA);
+                xp.template load<ROWS>(a.x0 + kb.f_org, a.ldx, gl, b, aorg, RA, tlim);
                 xp.commit(A0, RA);
             }
         }
@@ -782,8 +819,8 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
                 u16* An = (s & 1) ? A0 : A1;
                 // the map of the next step: a_{l-2} (l - 2 >= 1: a padded map; l == 2: the stack's input, for the first layer's dW)
                 stamp_w(a.dbg, s, wave, lane, 0);
-                if (l >= 3) mp.template issue<BLK>(a.maps + (long long)(l - 3) * g.map_stride, g, kb, b, aorg, RA, An, zpage);
-                else if (l == 2 && WG) xp.load(a.x0 + kb.f_org, a.ldx, gl, b, t0 - 2, TR + 4);        // rows t0 - 2 .. t0 + TR + 2 of the input
+                if (l >= 3) mp.template issue<BLK, ROWS>(a.maps + (long long)(l - 3) * g.map_stride, g, kb, b, aorg, RA, An, zpage, tlim);
+                else if (l == 2 && WG) xp.template load<ROWS>(a.x0 + kb.f_org, a.ldx, gl, b, t0 - 2, TR + 4, tlim);        // rows t0 - 2 .. t0 + TR + 2 of the input
                 stamp_w(a.dbg, s, wave, lane, 1);
                 if (!WG && a.gmaps) rs.run(Dc + (t0 - dorg) * RS, a.gmaps + (long long)(l - 1) * g.map_stride + (long long)(b * g.T + t0) * g.FP * C + kb.f_org * C, min(TR, g.T - t0));
                 if (WG && wave < KT) {
@@ -800,7 +837,7 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
                     const int ta = t0 - ext, tb = t0 + TR + ext;
                     if (l >= 2) {
                         f32x4 bs = zero4();
-                        conv_chunks<NW, WG, false, false>(Dc, dorg, af, ta, tb, gl, wave, s, lo, zero4(),      // (both pairs' reads in one burst measured 9 % slower here)
+                        conv_chunks<ROWS, NW, WG, false, false>(Dc, dorg, af, ta, tb, gl, tlim, wave, s, lo, zero4(),      // (both pairs' reads in one burst measured 9 % slower here)
                                    [&](int tc, int, int, int px) { return *reinterpret_cast<const bf16x4*>(Ac + (tc - aorg) * RS + px); },
                                    [&](int tc, int t, int f, int px, f32x4 v, bf16x4 mk, bool ok, bool fresh) {
                                        const f32x4 m = to_f32(mk);
@@ -815,9 +852,15 @@ __global__ __launch_bounds__(NT) void chain_bwd_kernel(BwdArgs a) {
                         stamp_w(a.dbg, s, wave, lane, 5);
                     } else if (a.g0) {
                         // d/dx0: channel 0 of the transposed first layer, own rows, straight to HBM
-                        conv_chunks<NW, false, false>(Dc, dorg, af, t0, t0 + TR, gl, wave, s, lo, zero4(),
+                        conv_chunks<ROWS, NW, false, false>(Dc, dorg, af, t0, t0 + TR, gl, tlim, wave, s, lo, zero4(),
                                    [](int, int, int, int) { return 0; },
                                    [&](int, int t, int f, int, f32x4 v, int, bool ok, bool) {
+                                       if constexpr (ROWS) {
+                                           // every row of the buffer is written: a pad row (inside the pitch, outside the image) as +0.0
+                                           const bool in = (unsigned)t < (unsigned)g.T && f < gl.F && (!BLK || (f >= kb.own_lo && f < kb.own_hi));
+                                           if (in) a.g0[(long long)(b * g.T + t) * g.F + kb.f_org + f] = ok ? v[0] : 0.f;
+                                           return;
+                                       }
                                        if (BLK) ok = ok && f >= kb.own_lo && f < kb.own_hi;
                                        if (ok) a.g0[(long long)(b * g.T + t) * g.F + kb.f_org + f] = v[0];
                                    });
@@ -889,9 +932,10 @@ struct SecArgs {
     FBlocks fb;
 };
 
-template <int NT, bool BLK>
-__global__ __launch_bounds__(NT) void chain_second_kernel(SecArgs a) {
+template <int NT, bool BLK, bool ROWS = false>
+__global__ __launch_bounds__(NT) void chain_second_kernel(ArgsOf<SecArgs, ROWS> a) {
     extern __shared__ __attribute__((aligned(16))) u16 lds[];
+    const int* __restrict__ lengths = lengths_of(a);
     constexpr int NW = NT / 64;
     const Geo g = a.g;
     const int L = g.L;
@@ -923,12 +967,13 @@ __global__ __launch_bounds__(NT) void chain_second_kernel(SecArgs a) {
         Geo gblk;
         if (BLK) gblk = block_geo(g, kb);
         const Geo& gl = BLK ? gblk : g;          // what the tile's helpers work on: the block as an image
+        const int tlim = row_limit<ROWS>(lengths, b, g.T);
         const int uorg = t0 - 2 * L;
         const int wg_lo = BLK ? kb.own_lo >> 2 : 0, wg_ng = BLK ? (kb.own_hi + 3) >> 2 : g.ng;
         {
             X0Pref<NSX, NT> xp;
-            xp.load(a.u0 + kb.f_org, g.F, gl, b, uorg, RU);
-            mp.template issue<BLK>(a.gmaps, g, kb, b, t0, TR, G0, zpage);
+            xp.template load<ROWS>(a.u0 + kb.f_org, g.F, gl, b, uorg, RU, tlim);
+            mp.template issue<BLK, ROWS>(a.gmaps, g, kb, b, t0, TR, G0, zpage, tlim);
             xp.commit(U0, RU);
             if (BLK) clear_right_of<NT>(U1, RU, kb.ng);
             dma_wait();
@@ -943,7 +988,7 @@ __global__ __launch_bounds__(NT) void chain_second_kernel(SecArgs a) {
                 u16* Un = (s & 1) ? U0 : U1;
                 const u16* Gc = (s & 1) ? G1 : G0;
                 u16* Gn = (s & 1) ? G0 : G1;
-                if (l < L) mp.template issue<BLK>(a.gmaps + (long long)l * g.map_stride, g, kb, b, t0, TR, Gn, zpage);
+                if (l < L) mp.template issue<BLK, ROWS>(a.gmaps + (long long)l * g.map_stride, g, kb, b, t0, TR, Gn, zpage, tlim);
                 if (wave < KT) {
                     f32x4 c0 = zero4(), c1 = zero4();
                     dw_step(c0, c1, Uc + (t0 + wave - 2 - uorg) * RS, Gc, wg_lo, wg_ng, zero, lane);
@@ -956,10 +1001,15 @@ __global__ __launch_bounds__(NT) void chain_second_kernel(SecArgs a) {
                 const bool last = l == L;
                 const u16* am = (last ? a.a_last : a.maps + (long long)(l - 1) * g.map_stride) + kb.f_org * C;
                 const int apitch = last ? g.F : g.FP;
-                conv_chunks<NW, true, false, true>(Uc, uorg, af, ta, tb, gl, wave, s, lo, zero4(),
+                conv_chunks<ROWS, NW, true, false, true>(Uc, uorg, af, ta, tb, gl, tlim, wave, s, lo, zero4(),
                            [&](int, int t, int f, int) {
                                bf16x4 m = to_bf16(zero4());
-                               if ((unsigned)t < (unsigned)g.T && f < kb.F) m = *reinterpret_cast<const bf16x4*>(am + ((long long)(b * g.T + t) * apitch + f) * C);
+                               // (if constexpr: the plain form's closure must not capture tlim -- its code is to stay what it was)
+                               if constexpr (ROWS) {
+                                   if ((unsigned)t < (unsigned)tlim && f < kb.F) m = *reinterpret_cast<const bf16x4*>(am + ((long long)(b * g.T + t) * apitch + f) * C);
+                               } else {
+                                   if ((unsigned)t < (unsigned)g.T && f < kb.F) m = *reinterpret_cast<const bf16x4*>(am + ((long long)(b * g.T + t) * apitch + f) * C);
+                               }
                                return m;
                            },
                            [&](int tc, int t, int f, int px, f32x4 v, bf16x4 mk, bool ok, bool) {
@@ -968,7 +1018,14 @@ __global__ __launch_bounds__(NT) void chain_second_kernel(SecArgs a) {
                                for (int e = 0; e < 4; ++e) v[e] = v[e] * (m[e] > 0.f ? 1.f : g.alpha);
                                if (!ok) v = zero4();
                                if (!last) *reinterpret_cast<bf16x4*>(Un + (tc - uorg) * RS + px) = to_bf16(v);
-                               else if (ok && (!BLK || (f >= kb.own_lo && f < kb.own_hi))) {
+                               else if constexpr (ROWS) {
+                                   // every row of the buffer is written: v is +0.0 on a pad row (!ok above)
+                                   if ((unsigned)t < (unsigned)g.T && f < kb.F && (!BLK || (f >= kb.own_lo && f < kb.own_hi))) {
+                                       const long long off = ((long long)(b * g.T + t) * g.F + kb.f_org + f) * C;
+                                       if (a.out_bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<u16*>(a.out) + off) = to_bf16(v);
+                                       else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + off) = v;
+                                   }
+                               } else if (ok && (!BLK || (f >= kb.own_lo && f < kb.own_hi))) {
                                    const long long off = ((long long)(b * g.T + t) * g.F + kb.f_org + f) * C;
                                    if (a.out_bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<u16*>(a.out) + off) = to_bf16(v);
                                    else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + off) = v;
@@ -1077,6 +1134,7 @@ void set_lds(K kernel) {
 }
 }  // namespace
 
+#if !PTTS_CHAIN_ROWS
 // 1 when the stack (Cin0 -> C -> ... -> C, KT x KF kernels, F bins) has a chain kernel
 extern "C" int ptts_conv2d_chain_supported(int F, int L, int Cin0, int Cc, int KT_, int KF_) {
     FPlan p;
@@ -1118,108 +1176,180 @@ extern "C" int ptts_conv2d_chain_tables(const float* const* w, const float* cons
                        reinterpret_cast<float*>((char*)tables + TAB_BIAS_OFF));
     return check_launch("conv2d_chain_tables");
 }
+#endif
+
+// ------------------------------------------------------------------------------------------------------------
+// launches.  ROWS_TU: this translation unit's form (see the top of the file) -- the plain entry points, or the ..._rows ones,
+// which take `lengths` (device int32 [B]) in front of B and launch the ROWS = true instantiations.
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+template <class A>
+ArgsOf<A, ROWS_TU> launch_args(const A& a, const int* lengths) {
+    ArgsOf<A, ROWS_TU> r;
+    static_cast<A&>(r) = a;
+    if constexpr (ROWS_TU) r.lengths = lengths;
+    return r;
+}
 
 // forward of the stack: x0 [B][T][ldx] fp32 (the first F columns of a row are the spectrum) -> maps a_1 .. a_{L-1}
 // ([L-1][B][T][FP][4] bf16, FP = F rounded up to even) and a_last = a_L [B][T][F][4] bf16
-extern "C" int ptts_conv2d_chain_fwd(const float* x0, long long ldx, const void* tables, void* maps, void* a_last,
-                                     int B, int T, int F, int L, float alpha, void* stream) {
-    int rc = check_common("conv2d_chain_fwd", B, T, F, L, alpha);
+int chain_fwd(const char* what, const float* x0, long long ldx, const void* tables, void* maps, void* a_last, const int* lengths,
+              int B, int T, int F, int L, float alpha, void* stream) {
+    int rc = check_common(what, B, T, F, L, alpha);
     if (rc) return rc;
-    PTTS_REQUIRE(x0 && tables && a_last && (maps || L == 1) && ldx >= F, "conv2d_chain_fwd: null tensor or ldx < F");
+    PTTS_REQUIRE(x0 && tables && a_last && (maps || L == 1) && ldx >= F, "%s: null tensor or ldx < F", what);
+    PTTS_REQUIRE(!ROWS_TU || lengths, "%s: lengths is null", what);
     FwdArgs a;
     make_geo(a.g, a.fb, B, T, F, L, alpha);
     a.x0 = x0; a.ldx = ldx; a.tab = (const u16*)tables; a.bias = reinterpret_cast<const float*>((const char*)tables + TAB_BIAS_OFF);
     a.maps = (u16*)maps; a.a_last = (u16*)a_last; a.dbg = g_dbg;
     a.lds_bytes = HDR_BYTES + (size_t)2 * (TR + 4 * L) * RS * sizeof(u16);
-    PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "conv2d_chain_fwd: tiles do not fit the LDS");
+    PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "%s: tiles do not fit the LDS", what);
+    constexpr bool R = ROWS_TU;
     static bool attr = false;
     if (!attr) {
-        set_lds(&chain_fwd_kernel<512, false>); set_lds(&chain_fwd_kernel<1024, false>);
-        set_lds(&chain_fwd_kernel<512, true>); set_lds(&chain_fwd_kernel<1024, true>);
+        set_lds(&chain_fwd_kernel<512, false, R>); set_lds(&chain_fwd_kernel<1024, false, R>);
+        set_lds(&chain_fwd_kernel<512, true, R>); set_lds(&chain_fwd_kernel<1024, true, R>);
         attr = true;
     }
     const int grid = std::min(a.g.ntiles, NCU);
     const bool blk = a.fb.n > 1;          // one block: the kernels without any block state
-    if (wide_nt() == 1024) hipLaunchKernelGGL((blk ? chain_fwd_kernel<1024, true> : chain_fwd_kernel<1024, false>), dim3(grid), dim3(1024), a.lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((blk ? chain_fwd_kernel<512, true> : chain_fwd_kernel<512, false>), dim3(grid), dim3(512), a.lds_bytes, (hipStream_t)stream, a);
-    return check_launch("conv2d_chain_fwd");
+    const auto ar = launch_args(a, lengths);
+    if (wide_nt() == 1024) hipLaunchKernelGGL((blk ? chain_fwd_kernel<1024, true, R> : chain_fwd_kernel<1024, false, R>), dim3(grid), dim3(1024), a.lds_bytes, (hipStream_t)stream, ar);
+    else hipLaunchKernelGGL((blk ? chain_fwd_kernel<512, true, R> : chain_fwd_kernel<512, false, R>), dim3(grid), dim3(512), a.lds_bytes, (hipStream_t)stream, ar);
+    return check_launch(what);
 }
 
 // first-order backward: per-workgroup partial sums of dW_l / db_l, rows [l][nblocks][npart] (layer l's row: KT*KF*Cin_l*4 kernel
 // entries, then 4 bias entries) for ptts_conv2d_reduce_grouped.  d_last = dL/da_L [B][T][F][4], fp32 or bf16.
-extern "C" int ptts_conv2d_chain_bwd(const void* d_last, int d_bf16, const float* x0, long long ldx, const void* maps, const void* a_last,
-                                     const void* tables, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out,
-                                     int B, int T, int F, int L, int cin0, float alpha, void* stream) {
-    int rc = check_common("conv2d_chain_bwd", B, T, F, L, alpha);
+int chain_bwd(const char* what, const void* d_last, int d_bf16, const float* x0, long long ldx, const void* maps, const void* a_last,
+              const void* tables, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out, const int* lengths,
+              int B, int T, int F, int L, int cin0, float alpha, void* stream) {
+    int rc = check_common(what, B, T, F, L, alpha);
     if (rc) return rc;
     PTTS_REQUIRE(d_last && x0 && a_last && tables && partials && nblocks_out && npart_out && (maps || L == 1) && ldx >= F,
-                 "conv2d_chain_bwd: null pointer or ldx < F");
-    PTTS_REQUIRE(cin0 >= 1 && cin0 <= 4, "conv2d_chain_bwd: cin0 = %d", cin0);
+                 "%s: null pointer or ldx < F", what);
+    PTTS_REQUIRE(!ROWS_TU || lengths, "%s: lengths is null", what);
+    PTTS_REQUIRE(cin0 >= 1 && cin0 <= 4, "%s: cin0 = %d", what, cin0);
     BwdArgs a;
     make_geo(a.g, a.fb, B, T, F, L, alpha);
     const int grid = std::min(a.g.ntiles, NCU);
-    if (partials_bytes < (size_t)L * grid * NPART * sizeof(float)) { set_error("conv2d_chain_bwd: partials buffer too small"); return PTTS_EWORKSPACE; }
+    if (partials_bytes < (size_t)L * grid * NPART * sizeof(float)) { set_error("%s: partials buffer too small", what); return PTTS_EWORKSPACE; }
     a.d_last = d_last; a.d_bf16 = d_bf16; a.x0 = x0; a.ldx = ldx; a.maps = (const u16*)maps; a.a_last = (const u16*)a_last;
     a.tab = (const u16*)tables; a.gmaps = nullptr; a.g0 = nullptr; a.partials = partials; a.cin0 = cin0; a.dbg = g_dbg;
     const int EXTD = 2 * (L - 1), EXTA = std::max(2 * (L - 2), 2);
     a.lds_bytes = HDR_BYTES + (size_t)(2 * (TR + 2 * EXTD) + 2 * (TR + 2 * EXTA)) * RS * sizeof(u16);
     a.lds_bytes = std::max(a.lds_bytes, (size_t)HDR_BYTES + (size_t)LMAX * KT * 2 * 4 * 64 * sizeof(float));
-    PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "conv2d_chain_bwd: tiles do not fit the LDS");
+    PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "%s: tiles do not fit the LDS", what);
+    constexpr bool R = ROWS_TU;
     static bool attr = false;
-    if (!attr) { set_lds(&chain_bwd_kernel<NT, MODE_BWD, false>); set_lds(&chain_bwd_kernel<NT, MODE_BWD, true>); attr = true; }
-    hipLaunchKernelGGL((a.fb.n > 1 ? chain_bwd_kernel<NT, MODE_BWD, true> : chain_bwd_kernel<NT, MODE_BWD, false>), dim3(grid), dim3(NT), a.lds_bytes, (hipStream_t)stream, a);
+    if (!attr) { set_lds(&chain_bwd_kernel<NT, MODE_BWD, false, R>); set_lds(&chain_bwd_kernel<NT, MODE_BWD, true, R>); attr = true; }
+    hipLaunchKernelGGL((a.fb.n > 1 ? chain_bwd_kernel<NT, MODE_BWD, true, R> : chain_bwd_kernel<NT, MODE_BWD, false, R>), dim3(grid), dim3(NT), a.lds_bytes, (hipStream_t)stream,
+                       launch_args(a, lengths));
     *nblocks_out = grid; *npart_out = NPART;
-    return check_launch("conv2d_chain_bwd");
+    return check_launch(what);
 }
 
 // backward-data chain: g0 = d(.)/dx0 [B][T][F] fp32 (or NULL) and, when gmaps is given, gamma_l = lrelu'(a_l) . dL/da_l for
 // l = 1 .. L as padded maps [L][B][T][FP][4] bf16 (the operands of the second-order sweep)
-extern "C" int ptts_conv2d_chain_bwd_data(const void* d_last, int d_bf16, const void* maps, const void* a_last, const void* tables,
-                                          void* gmaps, float* g0, int B, int T, int F, int L, float alpha, void* stream) {
-    int rc = check_common("conv2d_chain_bwd_data", B, T, F, L, alpha);
+int chain_bwd_data(const char* what, const void* d_last, int d_bf16, const void* maps, const void* a_last, const void* tables,
+                   void* gmaps, float* g0, const int* lengths, int B, int T, int F, int L, float alpha, void* stream) {
+    int rc = check_common(what, B, T, F, L, alpha);
     if (rc) return rc;
-    PTTS_REQUIRE(d_last && a_last && tables && (maps || L == 1) && (gmaps || g0), "conv2d_chain_bwd_data: null pointer");
+    PTTS_REQUIRE(d_last && a_last && tables && (maps || L == 1) && (gmaps || g0), "%s: null pointer", what);
+    PTTS_REQUIRE(!ROWS_TU || lengths, "%s: lengths is null", what);
     BwdArgs a;
     make_geo(a.g, a.fb, B, T, F, L, alpha);
     a.d_last = d_last; a.d_bf16 = d_bf16; a.x0 = nullptr; a.ldx = 0; a.maps = (const u16*)maps; a.a_last = (const u16*)a_last;
     a.tab = (const u16*)tables; a.gmaps = (u16*)gmaps; a.g0 = g0; a.partials = nullptr; a.cin0 = 1; a.dbg = g_dbg;
     const int EXTD = 2 * L, EXTA = 2 * (L - 1);
     a.lds_bytes = HDR_BYTES + (size_t)(2 * (TR + 2 * EXTD) + 2 * (TR + 2 * EXTA)) * RS * sizeof(u16);
-    PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "conv2d_chain_bwd_data: tiles do not fit the LDS");
+    PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "%s: tiles do not fit the LDS", what);
+    constexpr bool R = ROWS_TU;
     static bool attr = false;
     if (!attr) {
-        set_lds(&chain_bwd_kernel<512, MODE_DATA, false>); set_lds(&chain_bwd_kernel<1024, MODE_DATA, false>);
-        set_lds(&chain_bwd_kernel<512, MODE_DATA, true>); set_lds(&chain_bwd_kernel<1024, MODE_DATA, true>);
+        set_lds(&chain_bwd_kernel<512, MODE_DATA, false, R>); set_lds(&chain_bwd_kernel<1024, MODE_DATA, false, R>);
+        set_lds(&chain_bwd_kernel<512, MODE_DATA, true, R>); set_lds(&chain_bwd_kernel<1024, MODE_DATA, true, R>);
         attr = true;
     }
     const int grid = std::min(a.g.ntiles, NCU);
     const bool blk = a.fb.n > 1;
-    if (wide_nt() == 1024) hipLaunchKernelGGL((blk ? chain_bwd_kernel<1024, MODE_DATA, true> : chain_bwd_kernel<1024, MODE_DATA, false>), dim3(grid), dim3(1024), a.lds_bytes, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((blk ? chain_bwd_kernel<512, MODE_DATA, true> : chain_bwd_kernel<512, MODE_DATA, false>), dim3(grid), dim3(512), a.lds_bytes, (hipStream_t)stream, a);
-    return check_launch("conv2d_chain_bwd_data");
+    const auto ar = launch_args(a, lengths);
+    if (wide_nt() == 1024) hipLaunchKernelGGL((blk ? chain_bwd_kernel<1024, MODE_DATA, true, R> : chain_bwd_kernel<1024, MODE_DATA, false, R>), dim3(grid), dim3(1024), a.lds_bytes, (hipStream_t)stream, ar);
+    else hipLaunchKernelGGL((blk ? chain_bwd_kernel<512, MODE_DATA, true, R> : chain_bwd_kernel<512, MODE_DATA, false, R>), dim3(grid), dim3(512), a.lds_bytes, (hipStream_t)stream, ar);
+    return check_launch(what);
 }
 
 // second-order sweep: u0 = d/d(g0) [B][T][F] fp32 -> out = d/d(d_last) [B][T][F][4] (fp32 or bf16) and the partial sums of dW_l
 // (rows as ptts_conv2d_chain_bwd; the bias slots are zero)
-extern "C" int ptts_conv2d_chain_second(const float* u0, const void* gmaps, const void* maps, const void* a_last, const void* tables,
-                                        void* out, int out_bf16, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out,
-                                        int B, int T, int F, int L, int cin0, float alpha, void* stream) {
-    int rc = check_common("conv2d_chain_second", B, T, F, L, alpha);
+int chain_second(const char* what, const float* u0, const void* gmaps, const void* maps, const void* a_last, const void* tables,
+                 void* out, int out_bf16, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out, const int* lengths,
+                 int B, int T, int F, int L, int cin0, float alpha, void* stream) {
+    int rc = check_common(what, B, T, F, L, alpha);
     if (rc) return rc;
-    PTTS_REQUIRE(u0 && gmaps && a_last && tables && out && partials && nblocks_out && npart_out && (maps || L == 1), "conv2d_chain_second: null pointer");
-    PTTS_REQUIRE(cin0 >= 1 && cin0 <= 4, "conv2d_chain_second: cin0 = %d", cin0);
+    PTTS_REQUIRE(u0 && gmaps && a_last && tables && out && partials && nblocks_out && npart_out && (maps || L == 1), "%s: null pointer", what);
+    PTTS_REQUIRE(!ROWS_TU || lengths, "%s: lengths is null", what);
+    PTTS_REQUIRE(cin0 >= 1 && cin0 <= 4, "%s: cin0 = %d", what, cin0);
     SecArgs a;
     make_geo(a.g, a.fb, B, T, F, L, alpha);
     const int grid = std::min(a.g.ntiles, NCU);
-    if (partials_bytes < (size_t)L * grid * NPART * sizeof(float)) { set_error("conv2d_chain_second: partials buffer too small"); return PTTS_EWORKSPACE; }
+    if (partials_bytes < (size_t)L * grid * NPART * sizeof(float)) { set_error("%s: partials buffer too small", what); return PTTS_EWORKSPACE; }
     a.u0 = u0; a.gmaps = (const u16*)gmaps; a.maps = (const u16*)maps; a.a_last = (const u16*)a_last; a.tab = (const u16*)tables;
     a.out = out; a.out_bf16 = out_bf16; a.partials = partials; a.cin0 = cin0; a.dbg = g_dbg;
     a.lds_bytes = HDR_BYTES + (size_t)(2 * (TR + 4 * L) + 2 * TR) * RS * sizeof(u16);
     a.lds_bytes = std::max(a.lds_bytes, (size_t)HDR_BYTES + (size_t)LMAX * KT * 2 * 4 * 64 * sizeof(float));
-    PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "conv2d_chain_second: tiles do not fit the LDS");
+    PTTS_REQUIRE(a.lds_bytes <= LDS_MAX, "%s: tiles do not fit the LDS", what);
+    constexpr bool R = ROWS_TU;
     static bool attr = false;
-    if (!attr) { set_lds(&chain_second_kernel<NT, false>); set_lds(&chain_second_kernel<NT, true>); attr = true; }
-    hipLaunchKernelGGL((a.fb.n > 1 ? chain_second_kernel<NT, true> : chain_second_kernel<NT, false>), dim3(grid), dim3(NT), a.lds_bytes, (hipStream_t)stream, a);
+    if (!attr) { set_lds(&chain_second_kernel<NT, false, R>); set_lds(&chain_second_kernel<NT, true, R>); attr = true; }
+    hipLaunchKernelGGL((a.fb.n > 1 ? chain_second_kernel<NT, true, R> : chain_second_kernel<NT, false, R>), dim3(grid), dim3(NT), a.lds_bytes, (hipStream_t)stream,
+                       launch_args(a, lengths));
     *nblocks_out = grid; *npart_out = NPART;
-    return check_launch("conv2d_chain_second");
+    return check_launch(what);
 }
+}  // namespace
+
+#if !PTTS_CHAIN_ROWS
+extern "C" int ptts_conv2d_chain_fwd(const float* x0, long long ldx, const void* tables, void* maps, void* a_last,
+                                     int B, int T, int F, int L, float alpha, void* stream) {
+    return chain_fwd("conv2d_chain_fwd", x0, ldx, tables, maps, a_last, nullptr, B, T, F, L, alpha, stream);
+}
+extern "C" int ptts_conv2d_chain_bwd(const void* d_last, int d_bf16, const float* x0, long long ldx, const void* maps, const void* a_last,
+                                     const void* tables, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out,
+                                     int B, int T, int F, int L, int cin0, float alpha, void* stream) {
+    return chain_bwd("conv2d_chain_bwd", d_last, d_bf16, x0, ldx, maps, a_last, tables, partials, partials_bytes, nblocks_out, npart_out,
+                     nullptr, B, T, F, L, cin0, alpha, stream);
+}
+extern "C" int ptts_conv2d_chain_bwd_data(const void* d_last, int d_bf16, const void* maps, const void* a_last, const void* tables,
+                                          void* gmaps, float* g0, int B, int T, int F, int L, float alpha, void* stream) {
+    return chain_bwd_data("conv2d_chain_bwd_data", d_last, d_bf16, maps, a_last, tables, gmaps, g0, nullptr, B, T, F, L, alpha, stream);
+}
+extern "C" int ptts_conv2d_chain_second(const float* u0, const void* gmaps, const void* maps, const void* a_last, const void* tables,
+                                        void* out, int out_bf16, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out,
+                                        int B, int T, int F, int L, int cin0, float alpha, void* stream) {
+    return chain_second("conv2d_chain_second", u0, gmaps, maps, a_last, tables, out, out_bf16, partials, partials_bytes, nblocks_out, npart_out,
+                        nullptr, B, T, F, L, cin0, alpha, stream);
+}
+#else
+// the same passes over zero-padded rows: utterance b holds clamp(lengths[b], 0, T) real rows (the rule: percival_hip.h)
+extern "C" int ptts_conv2d_chain_fwd_rows(const float* x0, long long ldx, const void* tables, void* maps, void* a_last,
+                                          const int* lengths, int B, int T, int F, int L, float alpha, void* stream) {
+    return chain_fwd("conv2d_chain_fwd_rows", x0, ldx, tables, maps, a_last, lengths, B, T, F, L, alpha, stream);
+}
+extern "C" int ptts_conv2d_chain_bwd_rows(const void* d_last, int d_bf16, const float* x0, long long ldx, const void* maps, const void* a_last,
+                                          const void* tables, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out,
+                                          const int* lengths, int B, int T, int F, int L, int cin0, float alpha, void* stream) {
+    return chain_bwd("conv2d_chain_bwd_rows", d_last, d_bf16, x0, ldx, maps, a_last, tables, partials, partials_bytes, nblocks_out, npart_out,
+                     lengths, B, T, F, L, cin0, alpha, stream);
+}
+extern "C" int ptts_conv2d_chain_bwd_data_rows(const void* d_last, int d_bf16, const void* maps, const void* a_last, const void* tables,
+                                               void* gmaps, float* g0, const int* lengths, int B, int T, int F, int L, float alpha, void* stream) {
+    return chain_bwd_data("conv2d_chain_bwd_data_rows", d_last, d_bf16, maps, a_last, tables, gmaps, g0, lengths, B, T, F, L, alpha, stream);
+}
+extern "C" int ptts_conv2d_chain_second_rows(const float* u0, const void* gmaps, const void* maps, const void* a_last, const void* tables,
+                                             void* out, int out_bf16, float* partials, size_t partials_bytes, int* nblocks_out, int* npart_out,
+                                             const int* lengths, int B, int T, int F, int L, int cin0, float alpha, void* stream) {
+    return chain_second("conv2d_chain_second_rows", u0, gmaps, maps, a_last, tables, out, out_bf16, partials, partials_bytes, nblocks_out, npart_out,
+                        lengths, B, T, F, L, cin0, alpha, stream);
+}
+#endif

@@ -405,10 +405,17 @@ class Conv2DStack(Layer):
     layer: the bf16-storage path of BASELINE configs[2] runs the whole stack per launch with the maps between the layers in
     the LDS (ops.conv2d_chain, csrc/conv2d_chain.hip).  Input [B,T,F] (the Reshape to one channel is implied), output
     [B,T,F,filters] with the last LeakyReLU applied.  The parameters are the L kernels and biases in Keras order
-    (kernel_0, bias_0, kernel_1, ...), so weight lists, counts and checkpoints match the layer-by-layer graph."""
-    def __init__(self, nlayers, filters, kernel_size, alpha=0.3, name=None):
+    (kernel_0, bias_0, kernel_1, ...), so weight lists, counts and checkpoints match the layer-by-layer graph.
+
+    take_lengths=True: under memo['lengths'] (a zero-padded batch with a length per row: ragged inference, its input-gradient
+    mode and masked training alike) the chain kernels run their per-row form (ops.conv2d_chain(lengths=)): every layer of the
+    stack reads zeros at t >= length, the output and the input gradient are +0.0 there, the weight gradients sum over real
+    frames -- no masking pass in front of the stack or between its layers.  Only the chain kernels have that form: off, or on
+    the layer-wise fallback, lengths are refused."""
+    def __init__(self, nlayers, filters, kernel_size, alpha=0.3, take_lengths=False, name=None):
         super(Conv2DStack, self).__init__(name)
         self.nlayers, self.filters, self.alpha = int(nlayers), int(filters), float(alpha)
+        self.take_lengths = bool(take_lengths)
         self.kt, self.kf = int(kernel_size[0]), int(kernel_size[1])
 
     def build(self, in_shapes):
@@ -425,13 +432,17 @@ class Conv2DStack(Layer):
         return [getattr(self, 'kernel_{}'.format(li)) for li in range(self.nlayers)], [getattr(self, 'bias_{}'.format(li)) for li in range(self.nlayers)]
 
     def compute(self, vals, training, memo):
-        if ragged_lengths(memo) is not None:
+        lengths = ragged_lengths(memo)
+        if lengths is not None and not self.take_lengths:
             raise ValueError('Conv2DStack {!r} does not take per-row lengths: ragged inference covers the generator\'s layers only'
                              .format(self.lname))
         x0 = to_tensor(vals[0])
         ws, bs = self.kernels()
         if x0.is_cuda and ops._C2C.supported(x0.shape[-1], ws):
-            return ops.conv2d_chain(x0, ws, bs, self.alpha).float()
+            return ops.conv2d_chain(x0, ws, bs, self.alpha, lengths=lengths).float()
+        if lengths is not None:
+            raise ValueError('Conv2DStack {!r} does not take per-row lengths on its layer-wise form: only the chain kernels have a '
+                             'per-row form, and this stack ({} bins on {}) has no chain kernel'.format(self.lname, x0.shape[-1], x0.device))
         # shapes without a chain kernel (other kernel sizes or filter counts, more than 8 layers, more bins than the chain's
         # frequency blocks cover -- the library decides): layer by layer on the one-plane matrix-core / stencil kernels
         v = x0.reshape(x0.shape[0], x0.shape[1], x0.shape[2], 1)
@@ -441,7 +452,8 @@ class Conv2DStack(Layer):
         return v
 
     def config(self):
-        return {'nlayers': self.nlayers, 'filters': self.filters, 'kernel_size': [self.kt, self.kf], 'alpha': self.alpha}
+        return {'nlayers': self.nlayers, 'filters': self.filters, 'kernel_size': [self.kt, self.kf], 'alpha': self.alpha,
+                'take_lengths': self.take_lengths}
 
 
 class LSTM(Layer):

@@ -61,7 +61,9 @@ class Critic:
             #             between the layers in the LDS (kl.Conv2DStack -> csrc/conv2d_chain.hip); 4 filters of 5x5, <= 8 layers,
             #             <= CHAIN_DEFAULT_MAX_BINS bins (one frequency block) -- other geometries take the layer-wise form below
             #   'chain'   the same stack wherever the library has a chain kernel (ptts_conv2d_chain_supported: wider spectra run
-            #             in overlapping frequency blocks); a geometry without one is a ValueError, never another form
+            #             in overlapping frequency blocks); a geometry without one is a ValueError, never another form.  Being
+            #             sure of the kernel, this is also the bf16 form that takes zero-padded batches with a length per row
+            #             (Conv2DStack(take_lengths=True): validation on ragged batches, masked training)
             #   'layers'  the round-2 form: the maps between the 4 -> 4 channel layers (and their gradients) as bf16, one launch
             #             per layer and pass; the first layer (1 -> 4) and the map handed to the dense layers stay fp32
             # master weights and every weight gradient are fp32 either way
@@ -78,7 +80,8 @@ class Critic:
             else:
                 chain = bool(bf16) and bf16 != 'layers' and std and L <= CHAIN_MAX_LAYERS and vocoder.specsize() <= CHAIN_DEFAULT_MAX_BINS
             if chain:
-                l_spec = kl.Conv2DStack(L, cfgarch.arch_gen_nbfilters, [cfgarch.arch_gen_winlen, cfgarch.arch_spec_freqlen], alpha=0.3)(l_spec)
+                l_spec = kl.Conv2DStack(L, cfgarch.arch_gen_nbfilters, [cfgarch.arch_gen_winlen, cfgarch.arch_spec_freqlen], alpha=0.3,
+                                        take_lengths=(bf16 == 'chain'))(l_spec)
             else:
                 l_spec = kl.Reshape([vocoder.specsize(), 1])(l_spec)
                 for li in range(L):

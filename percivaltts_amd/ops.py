@@ -1199,10 +1199,18 @@ def _chain_land(rows, ws, gws, gbs, want_b):
     return (None, None) if got is None else ([g[0] for g in got], [g[1] for g in got])
 
 
+def _chain_rows(name, lengths):
+    """(entry point, arguments in front of B) of a chain launch: the plain one, or under `lengths` (int32 device [B]) its per-row
+    form ptts_..._rows, which takes the lengths there -- every row of every output is written either way (pad rows +0.0)."""
+    return (name, ()) if lengths is None else (name + '_rows', (ptr(lengths),))
+
+
 class Conv2dChainFn(torch.autograd.Function):
-    """a_L = stack(x0): x0 [B,T,F] fp32 -> [B,T,F,4] bf16 (post-activation).  Arguments after alpha: w_1, b_1, ..., w_L, b_L."""
+    """a_L = stack(x0): x0 [B,T,F] fp32 -> [B,T,F,4] bf16 (post-activation).  cfg = (alpha, lengths): lengths None, or int32 device
+    [B] -- the per-row form of every pass.  Arguments after cfg: w_1, b_1, ..., w_L, b_L."""
     @staticmethod
-    def forward(ctx, x0, alpha, *wb):
+    def forward(ctx, x0, cfg, *wb):
+        alpha, lengths = cfg
         ws, bs = list(wb[0::2]), list(wb[1::2])
         x0 = _chain_x0(x0)
         B, T, F = x0.shape
@@ -1211,8 +1219,10 @@ class Conv2dChainFn(torch.autograd.Function):
         FP = (F + 1) & ~1
         maps = torch.empty((max(L - 1, 1), B, T, FP, 4), dtype=torch.bfloat16, device=x0.device)
         a_last = torch.empty((B, T, F, 4), dtype=torch.bfloat16, device=x0.device)
-        call('ptts_conv2d_chain_fwd', ptr(x0), x0.stride(1), ptr(tab), ptr(maps), ptr(a_last), B, T, F, L, alpha, stream(), tag=(B, T, F, L))
+        name, rows_arg = _chain_rows('ptts_conv2d_chain_fwd', lengths)
+        call(name, ptr(x0), x0.stride(1), ptr(tab), ptr(maps), ptr(a_last), *rows_arg, B, T, F, L, alpha, stream(), tag=(B, T, F, L))
         ctx.save_for_backward(x0, maps, a_last, tab, *ws)
+        ctx.lengths = lengths
         ctx.alpha, ctx.L, ctx.has_b = alpha, L, [b is not None for b in bs]
         ctx.gws, ctx.gbs = _Deferred.targets(*ws), _Deferred.targets(*bs)
         ctx.set_materialize_grads(False)
@@ -1237,16 +1247,18 @@ class Conv2dChainFn(torch.autograd.Function):
         if need_x:
             if torch.is_grad_enabled():
                 # differentiable backward (gradient penalty): its own backward is the second-order sweep
-                g0 = Conv2dChainBwdDataFn.apply(d_last, maps, a_last, tab, alpha, (ctx.gws, int(ws[0].shape[2])), *ws)
+                g0 = Conv2dChainBwdDataFn.apply(d_last, maps, a_last, tab, alpha, (ctx.gws, int(ws[0].shape[2]), ctx.lengths), *ws)
             else:
                 g0 = torch.empty((B, T, F), dtype=torch.float32, device=x0.device)
-                call('ptts_conv2d_chain_bwd_data', ptr(d_last), int(_is16(d_last)), ptr(maps), ptr(a_last), ptr(tab), None, ptr(g0),
-                     B, T, F, L, alpha, stream(), tag=(B, T, F, L, 0))
+                name, rows_arg = _chain_rows('ptts_conv2d_chain_bwd_data', ctx.lengths)
+                call(name, ptr(d_last), int(_is16(d_last)), ptr(maps), ptr(a_last), ptr(tab), None, ptr(g0),
+                     *rows_arg, B, T, F, L, alpha, stream(), tag=(B, T, F, L, 0))
         if need_w:
             with torch.no_grad():
-                rows = _rows_call('ptts_conv2d_chain_bwd', _hip.lib().ptts_conv2d_chain_partials_bytes(L), x0.device,
+                name, rows_arg = _chain_rows('ptts_conv2d_chain_bwd', ctx.lengths)
+                rows = _rows_call(name, _hip.lib().ptts_conv2d_chain_partials_bytes(L), x0.device,
                                   (ptr(d_last), int(_is16(d_last)), ptr(x0), x0.stride(1), ptr(maps), ptr(a_last), ptr(tab)),
-                                  (B, T, F, L, int(ws[0].shape[2]), alpha), (B, T, F, L))
+                                  rows_arg + (B, T, F, L, int(ws[0].shape[2]), alpha), (B, T, F, L))
                 dws, dbs = _chain_land(rows, ws, ctx.gws, ctx.gbs, any(ctx.has_b))
                 if dws is not None:
                     for l in range(L):
@@ -1260,15 +1272,17 @@ class Conv2dChainBwdDataFn(torch.autograd.Function):
     sweep of the gradient penalty (optimizertts_wgan.py:53-68)."""
     @staticmethod
     def forward(ctx, d_last, maps, a_last, tab, alpha, extra, *ws):
-        gws, cin0 = extra
+        gws, cin0, lengths = extra
         B, T, F, _ = a_last.shape
         L = len(ws)
         FP = (F + 1) & ~1
         gmaps = torch.empty((L, B, T, FP, 4), dtype=torch.bfloat16, device=a_last.device)
         g0 = torch.empty((B, T, F), dtype=torch.float32, device=a_last.device)
-        call('ptts_conv2d_chain_bwd_data', ptr(d_last), int(_is16(d_last)), ptr(maps), ptr(a_last), ptr(tab), ptr(gmaps), ptr(g0),
-             B, T, F, L, alpha, stream(), tag=(B, T, F, L, 1))
+        name, rows_arg = _chain_rows('ptts_conv2d_chain_bwd_data', lengths)
+        call(name, ptr(d_last), int(_is16(d_last)), ptr(maps), ptr(a_last), ptr(tab), ptr(gmaps), ptr(g0),
+             *rows_arg, B, T, F, L, alpha, stream(), tag=(B, T, F, L, 1))
         ctx.save_for_backward(gmaps, maps, a_last, tab, *ws)
+        ctx.lengths = lengths
         ctx.cfg = (alpha, L, cin0, d_last.dtype)
         ctx.gws = gws
         ctx.set_materialize_grads(False)
@@ -1285,9 +1299,10 @@ class Conv2dChainBwdDataFn(torch.autograd.Function):
         B, T, F, _ = a_last.shape
         u0 = f32c(u0.contiguous(), 'conv2d_chain.u0')
         out = torch.empty((B, T, F, 4), dtype=d_dtype, device=u0.device)
-        rows = _rows_call('ptts_conv2d_chain_second', _hip.lib().ptts_conv2d_chain_partials_bytes(L), u0.device,
+        name, rows_arg = _chain_rows('ptts_conv2d_chain_second', ctx.lengths)
+        rows = _rows_call(name, _hip.lib().ptts_conv2d_chain_partials_bytes(L), u0.device,
                           (ptr(u0), ptr(gmaps), ptr(maps), ptr(a_last), ptr(tab), ptr(out), int(d_dtype == torch.bfloat16)),
-                          (B, T, F, L, cin0, alpha), (B, T, F, L))
+                          rows_arg + (B, T, F, L, cin0, alpha), (B, T, F, L))
         need_w = any(ctx.needs_input_grad[6 + l] for l in range(L))
         grads = [None] * L
         if need_w:
@@ -1297,12 +1312,22 @@ class Conv2dChainBwdDataFn(torch.autograd.Function):
         return (out if ctx.needs_input_grad[0] else None, None, None, None, None, None) + tuple(grads)
 
 
-def conv2d_chain(x0, ws, bs, alpha=0.3):
-    """The whole stack: x0 [B,T,F] fp32 -> a_L [B,T,F,4] bf16 (LeakyReLU applied)."""
+def conv2d_chain(x0, ws, bs, alpha=0.3, lengths=None):
+    """The whole stack: x0 [B,T,F] fp32 -> a_L [B,T,F,4] bf16 (LeakyReLU applied).
+
+    lengths (int32 device tensor [B], or None): x0 is a zero-padded batch, row b holds min(max(lengths[b], 0), T) real frames.
+    Every pass then runs its per-row form (ptts_conv2d_chain_*_rows): every layer reads zeros at t >= length whatever the pad
+    rows of x0 or of an incoming gradient hold (NaN included), the result, the input gradient and the gradient the second-order
+    sweep returns are +0.0 there, and the weight / bias gradients sum over real frames only.  No pass over any map is added and
+    nothing here depends on the ragged mode: which passes run is decided as without lengths."""
+    if lengths is not None:
+        if not (torch.is_tensor(lengths) and lengths.is_cuda and lengths.dtype == torch.int32 and lengths.dim() == 1
+                and lengths.shape[0] == x0.shape[0] and lengths.is_contiguous()):
+            raise _hip.HipLibraryError('conv2d_chain: lengths must be a contiguous int32 device tensor [B = {}]'.format(x0.shape[0]))
     wb = []
     for w, b in zip(ws, bs):
         wb += [w, b]
-    return Conv2dChainFn.apply(x0, float(alpha), *wb)
+    return Conv2dChainFn.apply(x0, (float(alpha), lengths), *wb)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -180,13 +180,16 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         self.device = dev = self._model.to_device()
         self.world, self.rank = parallel.init()
 
-        if self._validation_batch_size() is not None and self._critic_stack_layers():
+        # per-row lengths and the bf16 critic: 'chain' takes them (its Conv2DStack is sure of the chain kernels, which have a
+        # per-row form); True and 'layers' do not
+        if self._validation_batch_size() is not None and self._critic_stack_refuses_lengths():
             raise ValueError('cfg.train_validation_batch_size = {} needs a critic that takes per-row lengths, and the Conv2DStack of '
-                             'cfg.arch_critic_bf16 = {!r} does not: unset one of the two'.format(
-                                 cfg.train_validation_batch_size, getattr(self.critic.cfgarch, 'arch_critic_bf16', None)))
-        if cfg.train_batch_padtype == 'randshiftpad' and (self._critic_stack_layers() or getattr(self.critic.cfgarch, 'arch_critic_bf16', None)):
-            raise ValueError("cfg.train_batch_padtype = 'randshiftpad' (masked training) runs the critic in fp32 with per-row lengths, "
-                             'which the bf16 forms of cfg.arch_critic_bf16 = {!r} do not take: unset one of the two'.format(
+                             "cfg.arch_critic_bf16 = {!r} does not: unset one of the two, or use arch_critic_bf16 = 'chain', the bf16 form "
+                             'that takes lengths'.format(cfg.train_validation_batch_size, getattr(self.critic.cfgarch, 'arch_critic_bf16', None)))
+        if cfg.train_batch_padtype == 'randshiftpad' and self._critic_refuses_lengths():
+            raise ValueError("cfg.train_batch_padtype = 'randshiftpad' (masked training) runs the critic with per-row lengths, "
+                             "which the bf16 forms of cfg.arch_critic_bf16 = {!r} do not take: unset one of the two, or use "
+                             "arch_critic_bf16 = 'chain', the bf16 form that takes lengths".format(
                                  getattr(self.critic.cfgarch, 'arch_critic_bf16', None)))
         self._check_masked_training()        # ... nor with more than one rank or cfg.train_sync_batchnorm
         generator = self._model.kerasmodel
@@ -946,6 +949,17 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
     def _critic_stack_layers(self):
         return [l for l in self.critic.model.layers_list if isinstance(l, kl.Conv2DStack)]
 
+    def _critic_stack_refuses_lengths(self):
+        """Whether the critic holds a Conv2DStack that takes no per-row lengths (arch_critic_bf16 = True; 'chain' builds the one
+        that takes them)."""
+        return any(not l.take_lengths for l in self._critic_stack_layers())
+
+    def _critic_refuses_lengths(self):
+        """... or is any other bf16 form but 'chain' (the layer-wise bf16 maps: 'layers', or True on a geometry outside its default)."""
+        if self._critic_stack_layers():
+            return self._critic_stack_refuses_lengths()
+        return bool(getattr(self.critic.cfgarch, 'arch_critic_bf16', None))
+
     def _validation_costs_group(self, Xs, Ys, alpha):
         """validation_costs_batch for ONE group: the utterances zero-padded to the longest, one ragged generator forward, the critic
         on real / fake / x^ of the same padded group under the input-gradient rule (layers.ragged_input_grad)."""
@@ -999,9 +1013,10 @@ class OptimizerTTSWGAN(optimizertts.OptimizerTTS):
         cfg.train_validation_batch_size, or all in one group).  Per group ONE ragged generator forward feeds all three costs, the
         critic and its gradient penalty run on the same padded group, and nothing goes to the host.  `alphas`: the interpolation
         weight of each utterance's penalty, [N] in the order of the lists (None: torch.rand per group).  WGAN: gen_ls is zero."""
-        if self._critic_stack_layers():
-            raise ValueError('validation_costs_batch: a critic built with arch_critic_bf16 (Conv2DStack) takes no per-row lengths; '
-                             'unset cfg.train_validation_batch_size or cfg.arch_critic_bf16')
+        if self._critic_stack_refuses_lengths():
+            raise ValueError('validation_costs_batch: a critic built with arch_critic_bf16 = True (Conv2DStack) takes no per-row lengths; '
+                             "unset cfg.train_validation_batch_size or cfg.arch_critic_bf16, or use arch_critic_bf16 = 'chain', the bf16 "
+                             'form that takes lengths')
         if len(Xs) != len(Ys) or len(Xs) == 0:
             raise ValueError('validation_costs_batch: {} inputs for {} targets'.format(len(Xs), len(Ys)))
         if batch_size is None:

@@ -224,7 +224,8 @@ def training(cont=False):
     mod = build_model()
     # cfg.train_validation_batch_size = n (unset here: one utterance at a time, as the reference does): the validation costs of every
     # epoch on ragged batches of up to n utterances of similar length -- one generator forward per batch feeds the RMSE, the
-    # generator's and the critic's cost (OptimizerTTSWGAN.validation_costs_batch); not with cfg.arch_critic_bf16
+    # generator's and the critic's cost (OptimizerTTSWGAN.validation_costs_batch); with the bf16 critic only as
+    # cfg.arch_critic_bf16 = 'chain' (its Conv2D stack takes a length per row; True is refused at prepare())
     # cfg.train_data_on_device = True (unset here: load_inoutset reads the files of every batch, as the reference does): the training
     # set is read, cropped and uploaded once (data.DeviceCorpus) and every batch is one gather launch at the windows the host loader
     # would draw -- same numpy draws, same batches, same model; cfg.train_data_on_device_maxbytes bounds the device memory it may take

@@ -20,7 +20,11 @@ on the host, the ptts_batch_windows gather and the step; under 'randshift' it al
 come before (T changes with the batch's shortest row, so no warm-up covers them: that is the case being measured).
 frames/s = real frames of the round / its time; median, p10 and p90 over --rounds rounds.
 
-    python tools/ragged_train_probe.py [--utts 256] [--batch 64] [--steps 200] [--rounds 5] [--warmup 20]
+--critic chain: the critic form instead -- two cases on the spread corpus, the same batches and lengths (same seed), alternating
+as above: 'randshiftpad' (the masked step, fp32 layer-wise critic) and 'randshiftpad_chain' (the masked step with
+cfg.arch_critic_bf16 = 'chain': the Conv2D stack on the per-row chain kernels).
+
+    python tools/ragged_train_probe.py [--utts 256] [--batch 64] [--steps 200] [--rounds 5] [--warmup 20] [--critic fp32|chain]
 """
 from __future__ import print_function
 
@@ -55,7 +59,7 @@ def make_corpus(nutts, lo, hi, seed):
     return data.DeviceCorpus.from_utterances(Xs, Ys, Ws), lens
 
 
-def make_optimiser(batch, padtype):
+def make_optimiser(batch, padtype, critic=None):
     import torch
     import percivaltts_amd
     from percivaltts_amd import modeltts_common, networks_critic, optimizertts_wgan, vocoders
@@ -64,6 +68,8 @@ def make_optimiser(batch, padtype):
     cfg.arch_hiddenwidth = 256; cfg.arch_ctx_nbcnnlayers = 1; cfg.arch_ctx_winlen = 21
     cfg.arch_gen_nbcnnlayers = 8; cfg.arch_gen_nbfilters = 4; cfg.arch_gen_winlen = 5; cfg.arch_spec_freqlen = 5
     cfg.train_batch_size = batch; cfg.train_batch_lengthmax = LENGTHMAX; cfg.train_batch_padtype = padtype
+    if critic == 'chain':
+        cfg.arch_critic_bf16 = 'chain'
     voc = vocoders.VocoderPML(16000, 0.005, SPEC, NM)
     mod = modeltts_common.DCNNF0SpecNoiseFeatures(CTX, voc, cfg)
     crit = networks_critic.Critic(voc, CTX, cfg)
@@ -74,10 +80,10 @@ def make_optimiser(batch, padtype):
 
 
 class Case(object):
-    def __init__(self, name, corpus, batch, padtype, seed):
+    def __init__(self, name, corpus, batch, padtype, seed, critic=None):
         self.name, self.corpus, self.batch, self.padtype = name, corpus, batch, padtype
         self.masked = padtype == 'randshiftpad'
-        self.opt = make_optimiser(batch, padtype)
+        self.opt = make_optimiser(batch, padtype, critic)
         self.rng = np.random.RandomState(seed)
         self.batchid = 0
         self.rates, self.frames, self.ms = [], [], []
@@ -119,6 +125,7 @@ def main():
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--critic', choices=['fp32', 'chain'], default='fp32', help="'chain': the masked step with the bf16 chain critic against the masked fp32 one")
     args = ap.parse_args()
 
     import torch
@@ -128,10 +135,14 @@ def main():
         with contextlib.redirect_stdout(quiet):
             spread_corpus, lens = make_corpus(args.utts, 150, 900, seed=0)
             full_corpus, _ = make_corpus(args.utts, LENGTHMAX, 900, seed=1)
-            cases = [Case('randshift', spread_corpus, args.batch, 'randshift', 10),
-                     Case('randshiftpad', spread_corpus, args.batch, 'randshiftpad', 10),
-                     Case('randshift_full', full_corpus, args.batch, 'randshift', 11),
-                     Case('randshiftpad_full', full_corpus, args.batch, 'randshiftpad', 11)]
+            if args.critic == 'chain':
+                cases = [Case('randshiftpad', spread_corpus, args.batch, 'randshiftpad', 10),
+                         Case('randshiftpad_chain', spread_corpus, args.batch, 'randshiftpad', 10, critic='chain')]
+            else:
+                cases = [Case('randshift', spread_corpus, args.batch, 'randshift', 10),
+                         Case('randshiftpad', spread_corpus, args.batch, 'randshiftpad', 10),
+                         Case('randshift_full', full_corpus, args.batch, 'randshift', 11),
+                         Case('randshiftpad_full', full_corpus, args.batch, 'randshiftpad', 11)]
             for c in cases:
                 c.steps(args.warmup)
             for _ in range(args.rounds):
@@ -141,11 +152,11 @@ def main():
         sys.stderr.write(quiet.getvalue()[-4000:])
         raise
     res = {'device': torch.cuda.get_device_name(0), 'utterances': args.utts, 'cropped_lengths': [int(lens.min()), int(lens.max())],
-           'batch': args.batch, 'lengthmax': LENGTHMAX, 'steps_per_round': args.steps, 'rounds': args.rounds,
+           'batch': args.batch, 'lengthmax': LENGTHMAX, 'steps_per_round': args.steps, 'rounds': args.rounds, 'critic': args.critic,
            'cases': dict((c.name, c.result()) for c in cases)}
-    base = res['cases']['randshift']['real_frames_per_s']['median']
+    base = res['cases'][cases[0].name]['real_frames_per_s']['median']
     for c in cases:
-        res['cases'][c.name]['over_randshift'] = res['cases'][c.name]['real_frames_per_s']['median'] / base
+        res['cases'][c.name]['over_' + cases[0].name] = res['cases'][c.name]['real_frames_per_s']['median'] / base
     print(json.dumps(res, indent=1, sort_keys=True))
 
 
