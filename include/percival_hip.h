@@ -1236,6 +1236,20 @@ int ptts_highpass_zerophase(const float* x, float* y, const long long* off, long
  *   _MINIMAL_PHONEME (3)       (i+1)/fn, (fn-i)/fn, fn      _NONE (0)
  *   _COARSE_CODING (4)         cc[0][300+k], cc[1][200+k], cc[2][100+k], pd with
  *                              k = int((200/pd)*(base+i)); cc_table [3][PTTS_LABELS_CC_POINTS] fp32
+ *
+ * ptts_labels_segments: the segment table of ptts_labels_expand from durations instead of a label
+ * file's times.  dur [P][D] device fp32, D = PTTS_LABELS_SEG_STATES (state durations) or 1 (phone
+ * durations), in frames; unit_off [U+1] device int32: utterance u owns phones unit_off[u] ..
+ * unit_off[u+1]-1 (ascending from 0 to P; clamped into that range).  Per duration n = rint(d), ties
+ * to even; NaN and n < min_frames become min_frames; n > max_frames becomes max_frames and sets
+ * PTTS_LABELS_SEG_CLAMPED in status[u] (status [U] device int32, 0 otherwise).  seg [P*D][8]
+ * (16-byte aligned) row p*D+k = {p, first output row, n, k+1, D-k, sum_k n, sum_{j<k} n, 0}, for
+ * D = 1 {p, first output row, n, 0, 0, n, 0, 0}; first rows run on across the utterances of the call.
+ * rows [U+1] device int32: the first row of every utterance, rows[U] = T, the rows ptts_labels_expand
+ * will write.  0 <= min_frames <= max_frames <= PTTS_LABELS_SEG_MAX_FRAMES, and P*D*max_frames has
+ * to stay below 2^31 (PTTS_EINVAL otherwise: no total can then reach 2^31 rows).  P = 0 is allowed
+ * (dur and seg may be null): rows and status come back as zeros.  No atomics, no workspace; the
+ * output does not depend on the launch geometry.
  * ------------------------------------------------------------------------------------- */
 #define PTTS_LABELS_MAX_LABEL       1024
 #define PTTS_LABELS_CC_POINTS       600
@@ -1252,12 +1266,17 @@ int ptts_highpass_zerophase(const float* x, float* y, const long long* off, long
 #define PTTS_LABELS_NONE            3
 #define PTTS_LABELS_MINIMAL_PHONEME 4
 #define PTTS_LABELS_COARSE_CODING   5
+#define PTTS_LABELS_SEG_STATES      5
+#define PTTS_LABELS_SEG_CLAMPED     1
+#define PTTS_LABELS_SEG_MAX_FRAMES  16777216
 int ptts_labels_feature_count(int mode);
 int ptts_labels_match(const unsigned char* labels, const int* label_off, int P, int label_bytes, int max_label_len,
                       const unsigned char* pat_bytes, int n_pat_bytes, const int* pat_off, const int* pat_meta, int NP,
                       const int* qs_first, int nQS, const int* cqs, int nCQS, float* V, int* status, void* stream);
 int ptts_labels_expand(const float* V, const int* seg, const float* cc_table, float* X, int P, int Q, int S, int T,
                        int mode, void* stream);
+int ptts_labels_segments(const float* dur, const int* unit_off, int P, int D, int U, int min_frames, int max_frames, int* seg,
+                         int* rows, int* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Random numbers: Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), counter-based.

@@ -240,6 +240,26 @@ def normalise_meanstd_nmnoscale(filepath, fids, outfilepath=None, featurepaths=N
     _normalise_files(plan, filepath, fids, outfilepath)
 
 
+def normalise_minmax_stored(rows, statsdir, nrange=None, zerovarstozeros=True):
+    """Device rows [T, W] through the min-max normalisation whose statistics normalise_minmax stored in `statsdir` (min4norm.dat,
+    max4norm.dat): what that call wrote for its own files, for rows that were not among them -- context rows built at generation
+    time.  The statistics are read, never recomputed or rewritten.  Returns a new device tensor."""
+    from . import ops_offline as ops
+    import torch
+    mins, maxs = _stat(os.path.join(statsdir, 'x'), 'min4norm.dat'), _stat(os.path.join(statsdir, 'x'), 'max4norm.dat')
+    if rows.dim() != 2 or mins.shape != (rows.shape[1],) or maxs.shape != mins.shape:
+        raise ValueError('min4norm.dat / max4norm.dat of {} hold {} / {} values, the rows are {}'.format(statsdir, mins.size, maxs.size, tuple(rows.shape)))
+    if nrange is None: nrange = [-1, 1]
+    diff = maxs - mins
+    if zerovarstozeros:
+        mins[diff == 0.0] = 0.0
+    diff[diff == 0.0] = 1.0
+    if rows.shape[0] == 0:
+        return rows.clone()
+    return ops.compose_normalise(rows, torch.from_numpy(mins).to(rows.device), torch.from_numpy(diff).to(rows.device), mode=ops.NORM_MINMAX,
+                                 scale=(nrange[1] - nrange[0]) / 2.0, offset=0.5 * (nrange[0] + nrange[1]))
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # compose (compose.py:186-362)
 # ---------------------------------------------------------------------------------------------------------------------------

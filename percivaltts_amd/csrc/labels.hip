@@ -29,6 +29,18 @@
 //   once to fp32, which is the reference's "fp64 matrix, then numpy.array(data, 'float32')" bit for bit -- into the LDS; then
 //   all threads write the block as one flat, 16-byte aligned span of float4 stores (LAB_ROWS rows of any width are a whole number
 //   of float4), reading the phone rows of V with coalesced loads (a phone row is re-read for each of its frames: L2 hits).
+//
+// labels_segments: durations dur [P, D] fp32 (D = 5 states or 1 phone, in frames) of U utterances (unit_off [U+1] over the phones)
+//   -> the segment table labels_expand reads, what parse_label_file builds on the host from a label file's times.  Three small
+//   launches, no atomics, every word with one writer and no dependence on the launch geometry:
+//   * totals: one workgroup per utterance rounds its durations (seg_frames: rint, ties to even; NaN and anything below min_frames
+//     become min_frames, anything above max_frames becomes max_frames and sets PTTS_LABELS_SEG_CLAMPED in status[u]) and sums them
+//     into rows[u];
+//   * offsets: one workgroup scans rows [U] in place in tiles of SEG_TILE -> each utterance's first row, rows[U] = T;
+//   * table: one workgroup per utterance scans its P_u * D frame counts in tiles of SEG_TILE (SEG_ITEMS consecutive elements a
+//     thread, the wave's inclusive scan by wave shuffles, the four wave totals through the LDS, a carry from tile to tile) and writes
+//     the eight words of every segment; a phone's duration and a state's base are re-summed from the phone's own D values.
+//   The host bounds P * D * max_frames below 2^31, so no sum can leave int.
 #include "common.h"
 
 namespace ptts {
@@ -40,6 +52,9 @@ constexpr int LAB_META_LEN = 0xffff;            // pat_meta: length | flags
 constexpr int LAB_ROWS = 16;                    // output rows per workgroup of labels_expand
 constexpr int LAB_MAX_F = 9;
 constexpr int LAB_CC_POINTS = PTTS_LABELS_CC_POINTS;
+constexpr int SEG_ITEMS = 4;                    // consecutive elements per thread of a scan tile
+constexpr int SEG_TILE = LAB_THREADS * SEG_ITEMS;
+constexpr int SEG_MAX_D = PTTS_LABELS_SEG_STATES;
 
 __host__ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -290,6 +305,123 @@ __global__ __launch_bounds__(LAB_THREADS) void labels_expand_kernel(const float*
     }
 }
 
+// frames of one duration: rint (ties to even), NaN and n < lo -> lo, n > hi -> hi with `clamped` set.  lo <= hi <= 2^24 are exact
+// in fp32, so the comparisons decide before the conversion to int and no value outside int is ever converted.
+__host__ __device__ __forceinline__ int seg_frames(float d, int lo, int hi, int& clamped) {
+    const float r = rintf(d);
+    if (!(r >= (float)lo)) return lo;
+    if (r > (float)hi) { clamped = 1; return hi; }
+    return (int)r;
+}
+
+// exclusive scan of one value per thread over the workgroup: returns the sum of the threads before this one, `total` the sum of
+// all.  s_w [LAB_THREADS / 64]; two barriers, so s_w is free again on return.
+__device__ __forceinline__ int block_exclusive_scan(int v, int* s_w, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    __syncthreads();
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < LAB_THREADS / 64; ++w) {
+        before += w < wave ? s_w[w] : 0;
+        all += s_w[w];
+    }
+    total = all;
+    return before + incl - v;
+}
+
+// the phones [p0, p1) of utterance u, clamped into [0, P] and made monotone
+__device__ __forceinline__ void seg_unit(const int* __restrict__ unit_off, int u, int P, int& p0, int& p1) {
+    p0 = clampi(unit_off[u], 0, P);
+    p1 = clampi(unit_off[u + 1], p0, P);
+}
+
+// grid U: rows[u] = frames of utterance u, status[u] = PTTS_LABELS_SEG_CLAMPED when a duration was above max_frames
+__global__ __launch_bounds__(LAB_THREADS) void labels_segments_totals_kernel(const float* __restrict__ dur, const int* __restrict__ unit_off,
+                                                                             int* __restrict__ rows, int* __restrict__ status, const int P,
+                                                                             const int D, const int lo, const int hi) {
+    __shared__ int s_w[LAB_THREADS / 64];
+    const int u = blockIdx.x;
+    int p0, p1;
+    seg_unit(unit_off, u, P, p0, p1);
+    const int e0 = p0 * D, n = (p1 - p0) * D;
+    int sum = 0, clamped = 0;
+    for (int e = threadIdx.x; e < n; e += LAB_THREADS) sum += seg_frames(dur[e0 + e], lo, hi, clamped);
+    int total, any;
+    block_exclusive_scan(sum, s_w, total);
+    block_exclusive_scan(clamped, s_w, any);
+    if (threadIdx.x == 0) {
+        rows[u] = total;
+        status[u] = any ? PTTS_LABELS_SEG_CLAMPED : 0;
+    }
+}
+
+// grid 1: rows [U] totals -> rows [U+1] first rows, in place
+__global__ __launch_bounds__(LAB_THREADS) void labels_segments_offsets_kernel(int* __restrict__ rows, const int U) {
+    __shared__ int s_w[LAB_THREADS / 64];
+    int carry = 0;
+    for (int t0 = 0; t0 < U; t0 += SEG_TILE) {
+        const int i0 = t0 + threadIdx.x * SEG_ITEMS;
+        int v[SEG_ITEMS], sum = 0;
+#pragma unroll
+        for (int k = 0; k < SEG_ITEMS; ++k) { v[k] = i0 + k < U ? rows[i0 + k] : 0; sum += v[k]; }
+        int total;
+        int at = carry + block_exclusive_scan(sum, s_w, total);
+#pragma unroll
+        for (int k = 0; k < SEG_ITEMS; ++k) {
+            if (i0 + k < U) rows[i0 + k] = at;
+            at += v[k];
+        }
+        carry += total;
+    }
+    if (threadIdx.x == 0) rows[U] = carry;
+}
+
+// grid U: seg [P*D][8] of utterance u's phones; rows[u] is its first output row
+__global__ __launch_bounds__(LAB_THREADS) void labels_segments_table_kernel(const float* __restrict__ dur, const int* __restrict__ unit_off,
+                                                                            const int* __restrict__ rows, int* __restrict__ seg, const int P,
+                                                                            const int D, const int lo, const int hi) {
+    __shared__ int s_w[LAB_THREADS / 64];
+    const int u = blockIdx.x;
+    int p0, p1;
+    seg_unit(unit_off, u, P, p0, p1);
+    const int e0 = p0 * D, n = (p1 - p0) * D;
+    int carry = rows[u], unused = 0;
+    for (int t0 = 0; t0 < n; t0 += SEG_TILE) {
+        const int i0 = t0 + threadIdx.x * SEG_ITEMS;
+        int v[SEG_ITEMS], sum = 0;
+#pragma unroll
+        for (int k = 0; k < SEG_ITEMS; ++k) { v[k] = i0 + k < n ? seg_frames(dur[e0 + i0 + k], lo, hi, unused) : 0; sum += v[k]; }
+        int total;
+        int at = carry + block_exclusive_scan(sum, s_w, total);
+#pragma unroll
+        for (int k = 0; k < SEG_ITEMS; ++k) {
+            const int e = e0 + i0 + k;                          // < P * D inside the bound below
+            if (i0 + k < n) {
+                const int p = e / D, st = e - p * D;
+                int pd = 0, base = 0;
+                for (int j = 0; j < D; ++j) {
+                    const int f = seg_frames(dur[p * D + j], lo, hi, unused);
+                    pd += f;
+                    base += j < st ? f : 0;
+                }
+                int4* sp = (int4*)(seg + (size_t)e * 8);
+                sp[0] = make_int4(p, at, v[k], D > 1 ? st + 1 : 0);
+                sp[1] = make_int4(D > 1 ? D - st : 0, pd, base, 0);
+            }
+            at += v[k];
+        }
+        carry += total;
+    }
+}
+
 static int labels_cus() {
     static int cus = 0;
     if (cus == 0) {
@@ -353,4 +485,24 @@ extern "C" int ptts_labels_expand(const float* V, const int* seg, const float* c
     hipLaunchKernelGGL(labels_expand_kernel, dim3((T + LAB_ROWS - 1) / LAB_ROWS), dim3(LAB_THREADS), 0, (hipStream_t)stream, V, seg,
                        cc_table, X, P, Q, S, T, mode);
     return check_launch("labels_expand");
+}
+
+extern "C" int ptts_labels_segments(const float* dur, const int* unit_off, int P, int D, int U, int min_frames, int max_frames, int* seg,
+                                    int* rows, int* status, void* stream) {
+    PTTS_REQUIRE(unit_off && rows && status, "labels_segments: null tensor");
+    PTTS_REQUIRE(P >= 0 && U > 0 && (D == SEG_MAX_D || D == 1), "labels_segments: bad dims P=%d D=%d U=%d (D is %d or 1)", P, D, U, SEG_MAX_D);
+    PTTS_REQUIRE(P == 0 || (dur && seg), "labels_segments: null tensor");
+    PTTS_REQUIRE(((size_t)seg & 15) == 0, "labels_segments: seg has to be 16-byte aligned");
+    PTTS_REQUIRE(min_frames >= 0 && min_frames <= max_frames && max_frames <= PTTS_LABELS_SEG_MAX_FRAMES,
+                 "labels_segments: bad bounds min_frames=%d max_frames=%d (0 <= min <= max <= %d)", min_frames, max_frames,
+                 PTTS_LABELS_SEG_MAX_FRAMES);
+    PTTS_REQUIRE((long long)P * D * max_frames < (1ll << 31), "labels_segments: P=%d D=%d max_frames=%d allow 2^31 rows or more", P, D,
+                 max_frames);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(labels_segments_totals_kernel, dim3(U), dim3(LAB_THREADS), 0, st, dur, unit_off, rows, status, P, D, min_frames,
+                       max_frames);
+    hipLaunchKernelGGL(labels_segments_offsets_kernel, dim3(1), dim3(LAB_THREADS), 0, st, rows, U);
+    hipLaunchKernelGGL(labels_segments_table_kernel, dim3(U), dim3(LAB_THREADS), 0, st, dur, unit_off, rows, seg, P, D, min_frames,
+                       max_frames);
+    return check_launch("labels_segments");
 }

@@ -1,7 +1,8 @@
 """Wrappers of the offline pipeline over the HIP kernels of libpercival_hip.so: parameter generation (MLPG), feature
 composition, spectral envelope decompression, pulse-and-noise synthesis (PML) and periodic-plus-aperiodic synthesis (WORLD), each per
 utterance with a host pulse table or over a batch with the table built on the device, waveform analysis (PML and WORLD), F0 estimation,
-both per utterance or over a packed batch in one launch per kernel, waveform pre-processing and the label front end.
+both per utterance or over a packed batch in one launch per kernel, waveform pre-processing and the label front end (questions,
+frame expansion, and the segment table from durations).
 
 Argument checks, scratch memory and one C-ABI call (include/percival_hip.h) each; no autograd nodes, no switches, nothing
 of the training path (ops.py, which re-exports the names of __all__).  There is no CPU path.
@@ -38,7 +39,7 @@ __all__ = [
     'resample_length', 'resample_table', 'resample', 'highpass_tile', 'highpass_zerophase',
     'LABELS_MAX_LABEL', 'LABELS_CC_POINTS', 'LABELS_ANCHOR_START', 'LABELS_ANCHOR_END', 'LABELS_WILD', 'LABELS_CAPTURE_DIGITS',
     'LABELS_CAPTURE_DECIMAL', 'LABELS_ERR_DIGITS', 'LABELS_ERR_FORMAT', 'LABELS_MODES', 'LABELS_FEATURES', 'labels_match',
-    'labels_expand',
+    'labels_expand', 'LABELS_SEG_STATES', 'LABELS_SEG_CLAMPED', 'LABELS_SEG_MAX_FRAMES', 'labels_segments',
 ]
 
 
@@ -1823,3 +1824,33 @@ def labels_expand(V, seg, T, subphone_feats, cc_table=None):
     call('ptts_labels_expand', ptr(V), ptr(seg), ptr(cc_table), ptr(X), P, Q, seg.shape[0], T, LABELS_MODES[subphone_feats], stream(),
          tag=(P, Q, seg.shape[0], T))
     return X
+
+
+LABELS_SEG_STATES = 5                       # PTTS_LABELS_SEG_STATES
+LABELS_SEG_CLAMPED = 1
+LABELS_SEG_MAX_FRAMES = 1 << 24
+
+
+def labels_segments(dur, unit_off, min_frames, max_frames):
+    """dur [P,D] fp32 durations in frames (D = 5 states or 1 phone), unit_off [U+1] int32 utterance offsets over the P phones (both
+    device) -> (seg [P*D,8] int32 as labels_expand reads it, rows [U+1] int32: every utterance's first output row and, last, the
+    total T, status [U] int32: LABELS_SEG_CLAMPED where a duration was above max_frames), all on the device.  A duration is
+    rounded to the nearest integer, ties to even; NaN and anything below min_frames count min_frames.  P = 0 is allowed."""
+    f32c(dur, 'labels_segments.dur')
+    if dur.dim() != 2 or dur.shape[1] not in (LABELS_SEG_STATES, 1):
+        raise ValueError('ops.labels_segments: dur {} is not [P,{}] or [P,1]'.format(tuple(dur.shape), LABELS_SEG_STATES))
+    _no_backward('labels_segments', dur)
+    P, D = dur.shape
+    U = _offsets(unit_off, 'labels_segments', 'unit_off', 'U')
+    min_frames, max_frames = int(min_frames), int(max_frames)
+    if not 0 <= min_frames <= max_frames <= LABELS_SEG_MAX_FRAMES:
+        raise ValueError('ops.labels_segments: min_frames={} max_frames={} are not 0 <= min <= max <= {}'.format(
+            min_frames, max_frames, LABELS_SEG_MAX_FRAMES))
+    if P * D * max_frames >= 1 << 31:
+        raise ValueError('ops.labels_segments: P={} D={} max_frames={} allow 2^31 rows or more'.format(P, D, max_frames))
+    seg = torch.zeros((P * D, 8), dtype=torch.int32, device=dur.device)      # zeros: phones outside every utterance own no row
+    rows = torch.empty(U + 1, dtype=torch.int32, device=dur.device)
+    status = torch.empty(U, dtype=torch.int32, device=dur.device)
+    call('ptts_labels_segments', ptr(dur), ptr(unit_off), P, D, U, min_frames, max_frames, ptr(seg), ptr(rows), ptr(status), stream(),
+         tag=(P, D, U))
+    return seg, rows, status

@@ -10,7 +10,11 @@ files + file_id_list.scp) so that the training stages run without recordings.  `
 that name (run.py:168-180): HTS labels through the label normaliser (percivaltts_amd.external.merlin, on the device), the
 time weights from the labels, and the min-max normalised inputs `cfg.inpath` points at.  `features_compose()` is the
 composition half of the reference's features_extraction (run.py:155-165): from raw per-stream feature files it writes the time weights and the composed, normalised outputs `cfg.outpath` points at
-(percivaltts_amd.compose, on the device).
+(percivaltts_amd.compose, on the device).  The duration side is the build's own addition in the same shape: `durations_extraction()`
+writes a duration model's corpus from state-aligned labels (phone-level inputs, the five state durations per phone as targets),
+`build_duration_model()` / `training_durations()` train it with the least-squares optimiser over the phone index, and
+`generate(dur_fparams=..., lab_path=..., lab_questions=...)` takes its context rows from predicted durations
+(`contexts_from_durations()`), so that labels without times go through to a waveform.
 """
 from __future__ import print_function
 
@@ -45,6 +49,15 @@ errtype = 'WLSWGAN'   # 'LSE', 'WGAN', 'WLSWGAN'
 out_size = vocoder.featuressize()
 cfg.outpath = cp + 'wav_PML_cmp_lf0_fwlspec' + str(vocoder.specsize()) + '_fwnm' + str(vocoder.noisesize()) + '_nmnoscale/*.cmp:(-1,' + str(out_size) + ')'
 cfg.wpath = cp + 'label_state_align_weights/*.w:(-1,1)'
+
+# Duration model (a build extension: durations_extraction, build_duration_model, training_durations, generate(dur_fparams=...))
+dur_ctxsize = 416
+dur_nstates = 5
+cfg.dur_inpath = cp + 'label_phone_bin' + str(dur_ctxsize) + '_norm_minmaxm11/*.lab:(-1,' + str(dur_ctxsize) + ')'
+cfg.dur_outpath = cp + 'label_state_align_dur' + str(dur_nstates) + '_norm_meanstd/*.dur:(-1,' + str(dur_nstates) + ')'
+cfg.dur_wpath = cp + 'label_phone_weights/*.w:(-1,1)'
+cfg.dur_fparams_fullset = 'model-dur.h5'
+dur_layertypes = ['FC', 'BLSTM']
 
 # Model architecture (run.py:114-120)
 cfg.arch_hiddenwidth = 256
@@ -213,6 +226,77 @@ def contexts_extraction(lab_path, fids, lab_questions, labbin_path, labs_wpath, 
                            normfn=compose.normalise_minmax, wins=[], do_finalcheck=False)
 
 
+def phone_labels_from_state_labels(lab_path, fids, phonelab_path):
+    """State-aligned HTS labels (five lines "start end label[k]", k = 2 .. 6, per phone) -> phone-aligned ones: one line
+    "start end label" per phone, from the start of its first state to the end of its last, the state suffix dropped.  What a
+    duration model reads, one row per line (HTSDurationLabelNormalisation)."""
+    fids = readids(fids) if isinstance(fids, str) else list(fids)
+    makedirs(os.path.dirname(phonelab_path))
+    for fid in fids:
+        with open(lab_path.replace('*', fid)) as f:
+            rows = [line.split() for line in f if line.strip()]
+        if len(rows) % 5 or any(len(r) != 3 for r in rows) or any([r[2][-3:] for r in rows[i:i + 5]] != ['[2]', '[3]', '[4]', '[5]', '[6]']
+                                                                for i in range(0, len(rows), 5)):
+            raise ValueError('{}: a state-aligned label file holds five lines "start end label[k]", k = 2 .. 6, per phone'.format(lab_path.replace('*', fid)))
+        with open(phonelab_path.replace('*', fid), 'w') as f:
+            f.writelines('{} {} {}\n'.format(rows[i][0], rows[i + 4][1], rows[i][2][:-3]) for i in range(0, len(rows), 5))
+
+
+def durations_extraction(lab_path, fids, lab_questions, phonelab_path, labbin_path, dur_path, durs_wpath, inpath, outpath, id_valid_start=-1):
+    """The corpus of a duration model from state-aligned HTS labels `lab_path` ('dir/*.lab'): phone-aligned labels to
+    phonelab_path (phone_labels_from_state_labels); the phone-level inputs -- one row of question columns per phone,
+    HTSDurationLabelNormalisation -- un-normalised to labbin_path and min-max normalised to [-1, 1] to inpath; the targets -- the
+    five state durations of every phone in frames, HTSLabelNormalisation.prepare_dur_data -- un-normalised to dur_path and
+    mean/std normalised to outpath; one weight per phone, all ones, to durs_wpath.  The statistics are those of the first
+    `id_valid_start` files, written beside inpath (min4norm.dat, max4norm.dat) and outpath (mean4norm.dat, std4norm.dat) by
+    compose.compose.  A ':(-1,D)' suffix on a path is ignored.  Returns the two compose results as {'in': ..., 'out': ...}."""
+    from percivaltts_amd.external.merlin.label_normalisation import HTSDurationLabelNormalisation, HTSLabelNormalisation
+    fids = readids(fids) if isinstance(fids, str) else list(fids)
+    phonelab_path, labbin_path, dur_path, durs_wpath = (p.split(':')[0] for p in (phonelab_path, labbin_path, dur_path, durs_wpath))
+    phone_labels_from_state_labels(lab_path, fids, phonelab_path)
+    for p in (labbin_path, dur_path, durs_wpath):
+        makedirs(os.path.dirname(p))
+    each = lambda path: [path.replace('*', fid) for fid in fids]
+    inputs = HTSDurationLabelNormalisation(question_file_name=lab_questions)
+    inputs.perform_normalisation(each(phonelab_path), each(labbin_path))
+    HTSLabelNormalisation(question_file_name=lab_questions).prepare_dur_data(each(lab_path), each(dur_path), label_type='state_align')
+    for d, w in zip(each(dur_path), each(durs_wpath)):
+        np.ones((os.path.getsize(d) // (4 * dur_nstates), 1), dtype=np.float32).tofile(w)
+    res_in = compose.compose([labbin_path + ':(-1,' + str(inputs.dimension) + ')'], fids, inpath, id_valid_start=id_valid_start,
+                             normfn=compose.normalise_minmax, wins=[], do_finalcheck=False)
+    res_out = compose.compose([dur_path + ':(-1,' + str(dur_nstates) + ')'], fids, outpath, id_valid_start=id_valid_start,
+                              normfn=compose.normalise_meanstd, wins=[], do_finalcheck=False)
+    return {'in': res_in, 'out': res_out}
+
+
+def contexts_from_durations(lab_path, fids, lab_questions, dur_path, inpath, outpath, lab_type='state', min_frames=1, batch_size=64):
+    """The inputs of the acoustic model from durations instead of a forced alignment: the labels of `lab_path` (their times, if
+    any, are ignored) and the duration files `dur_path` ('dir/*.dur': float32 [P,5] frames per state for lab_type 'state', [P,1]
+    frames per phone for 'phone') go through HTSLabelNormalisation.normalise_with_durations, `batch_size` utterances a call, and
+    the rows, still on the device, through the min-max normalisation whose statistics contexts_extraction stored beside `inpath`
+    (min4norm.dat / max4norm.dat; compose.normalise_minmax_stored -- they are read, not recomputed).  Writes `outpath` ('dir/*.lab')
+    and returns the number of rows of every file."""
+    import torch
+    from percivaltts_amd.external.merlin.label_normalisation import HTSLabelNormalisation
+    fids = readids(fids) if isinstance(fids, str) else list(fids)
+    state = bool(lab_type) and lab_type != 'phone'
+    normaliser = HTSLabelNormalisation(question_file_name=lab_questions, add_frame_features=True,
+                                       subphone_feats='full' if state else 'coarse_coding')
+    dur_path, outpath, statsdir = dur_path.split(':')[0], outpath.split(':')[0], os.path.dirname(inpath.split(':')[0])
+    makedirs(os.path.dirname(outpath))
+    dev = compose._device()
+    nbrows = []
+    for first in range(0, len(fids), int(batch_size)):
+        chunk = fids[first:first + int(batch_size)]
+        durs = [torch.from_numpy(np.fromfile(dur_path.replace('*', fid), dtype=np.float32).reshape(-1, dur_nstates if state else 1)).to(dev)
+                for fid in chunk]
+        X, offs = normaliser.normalise_with_durations([lab_path.replace('*', fid) for fid in chunk], durs,
+                                                      label_type='state_align' if state else 'phone_align', min_frames=min_frames)
+        compose._write_rows(compose.normalise_minmax_stored(X, statsdir).cpu().numpy(), offs, outpath, chunk)
+        nbrows.extend(int(n) for n in np.diff(offs))
+    return nbrows
+
+
 def build_model():
     return modeltts_common.DCNNF0SpecNoiseFeatures(ctxsize, vocoder, cfg)    # DCNN in the paper
 
@@ -236,13 +320,46 @@ def training(cont=False):
     del mod
 
 
-def generate(fparams=None):
+def build_duration_model():
+    return modeltts_common.DurationModel(dur_ctxsize, cfg, layertypes=dur_layertypes, nstates=dur_nstates)
+
+
+def training_durations(cont=False):
+    """training() for the duration model: the LSE optimiser on cfg.dur_inpath / cfg.dur_outpath / cfg.dur_wpath, whose time axis
+    is the phone index (cfg.train_batch_lengthmax then counts phones); the model goes to cfg.dur_fparams_fullset."""
+    fids = readids(cfg.fileids)
+    fid_lst_tra = fids[:cfg.id_train_nb()]
+    fid_lst_val = fids[cfg.id_valid_start:cfg.id_valid_start + cfg.id_valid_nb]
+    mod = build_duration_model()
+    opti = optimizertts.OptimizerTTS(cfg, mod)
+    opti.train(cfg.dur_inpath, cfg.dur_outpath, cfg.dur_wpath, fid_lst_tra, fid_lst_val, cfg.dur_fparams_fullset, cont=cont)
+    del mod
+
+
+def generate(fparams=None, dur_fparams=None, lab_path=None, lab_questions=None):
+    """`dur_fparams` (with `lab_path`, the test utterances' labels -- times are not needed -- and `lab_questions`): the context
+    rows come from predicted durations instead of cfg.inpath's aligned ones.  The duration model of that file predicts from
+    cfg.dur_inpath (DurationModel.generate_durations, <model>-gen-dur/*.dur), contexts_from_durations expands them and normalises
+    the rows with the statistics stored beside cfg.inpath, and generation goes on from <model>-gen-lab/*.lab; the objective
+    measures are left out, since the generated utterances no longer have the targets' lengths."""
+    if dur_fparams is not None and (lab_path is None or lab_questions is None):
+        raise ValueError('generate: dur_fparams goes with lab_path and lab_questions')
     fparams = cfg.fparams_fullset if fparams is None else fparams
     fids = readids(cfg.fileids)
+    fid_lst_test = fids[cfg.id_valid_start + cfg.id_valid_nb:cfg.id_valid_start + cfg.id_valid_nb + cfg.id_test_nb]
+    inpath, do_objmeas = cfg.inpath, True
+    if dur_fparams is not None:
+        durmod = build_duration_model()
+        durmod.load(dur_fparams)
+        durdir = os.path.splitext(fparams)[0] + '-gen-dur'
+        durmod.generate_durations(cfg.dur_inpath, cfg.dur_outpath, fid_lst_test, durdir, do_objmeas=False)
+        del durmod
+        inpath = os.path.splitext(fparams)[0] + '-gen-lab/*.lab:(-1,' + str(ctxsize) + ')'
+        contexts_from_durations(lab_path, fid_lst_test, lab_questions, durdir + '/*.dur', cfg.inpath, inpath)
+        do_objmeas = False
     mod = build_model()
     mod.load(fparams)
-    fid_lst_test = fids[cfg.id_valid_start + cfg.id_valid_nb:cfg.id_valid_start + cfg.id_valid_nb + cfg.id_test_nb]
-    mod.generate_cmp(cfg.inpath, os.path.splitext(fparams)[0] + '-gen/*.cmp', fid_lst_test)
+    mod.generate_cmp(inpath, os.path.splitext(fparams)[0] + '-gen/*.cmp', fid_lst_test)
     # where the reference calls generate_wav (run.py:218): everything of it up to the vocoder's synthesis, and, for a vocoder
     # with synthesis_device (VocoderPML, VocoderWORLDDevice), the waveforms of the build's own synthesiser in <model>-demo-snd
     # (cfg.wavdir overrides the place)
@@ -251,8 +368,8 @@ def generate(fparams=None):
     # cfg.predict_batched, if present and true: the network runs on each group of utterances at once (ragged inference)
     # (cfg.group_by_length beside it: the groups hold utterances of similar length); the counterpart for the validation sweep of
     # training() is cfg.train_validation_batch_size -- all three unset here
-    mod.generate_params(cfg.inpath, cfg.outpath, fid_lst_test[demostart:demostart + 10], os.path.splitext(fparams)[0] + '-demo-params',
-                        do_objmeas=True, pp_mcep=getattr(cfg, 'pp_mcep', False), specdir=getattr(cfg, 'specdir', None),
+    mod.generate_params(inpath, cfg.outpath, fid_lst_test[demostart:demostart + 10], os.path.splitext(fparams)[0] + '-demo-params',
+                        do_objmeas=do_objmeas, pp_mcep=getattr(cfg, 'pp_mcep', False), specdir=getattr(cfg, 'specdir', None),
                         wavdir=(getattr(cfg, 'wavdir', os.path.splitext(fparams)[0] + '-demo-snd')
                                 if hasattr(mod.vocoder, 'synthesis_device') else None),
                         predict_batched=bool(getattr(cfg, 'predict_batched', False)),

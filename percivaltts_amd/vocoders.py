@@ -718,3 +718,33 @@ class VocoderWORLDAnalysisDevice(VocoderWORLDDevice):
         (vocoders.py:297-298); outputpathdicts: {'f0': .., 'spec': .., 'noise': .., 'vuv': ..}; f0in_path None: the build's own F0
         estimate."""
         return self._analysisfid_device(fid, wav_path, f0in_path, f0_min, f0_max, outputpathdicts, ('f0', 'spec', 'noise', 'vuv'), kwargs)
+
+
+class DurationFeatures(Vocoder):
+    """The output features of a duration model (modeltts_common.DurationModel): `nstates` durations per phone, in frames of `shift`
+    seconds.  A Vocoder only as far as the model and the optimiser ask one: sizes, the shift, objective measures.  There is no
+    f0, spectrum or noise stream, no delta window and no waveform."""
+
+    def __init__(self, shift, nstates=5):
+        if int(nstates) != nstates or nstates < 1:
+            raise ValueError('DurationFeatures: nstates={!r} is not a positive integer'.format(nstates))
+        Vocoder.__init__(self, 'durations', None, shift, mlpg_wins=None)
+        self.nstates = int(nstates)
+
+    def featuressizeraw(self): return self.nstates
+    def f0size(self): return 0
+    def specsize(self): return 0
+    def noisesize(self): return 0
+    def vuvsize(self): return 0
+
+    def objmeasures_add(self, DUR, REF):
+        """DUR, REF [P, nstates] in frames: the RMSE per state in frames, and per phone (the states summed) the RMSE in ms and the
+        correlation (left out for an utterance whose generated or reference phone durations are all equal)."""
+        DUR, REF = np.asarray(DUR, dtype=np.float64), np.asarray(REF, dtype=np.float64)
+        if DUR.ndim != 2 or DUR.shape[1] != self.nstates or DUR.shape != REF.shape or DUR.shape[0] < 1:
+            raise ValueError('objmeasures_add: durations {} and reference {} are not [P,{}]'.format(DUR.shape, REF.shape, self.nstates))
+        self.features_err.setdefault('DUR_STATE[frames]', []).append(np.sqrt(np.mean((DUR - REF) ** 2)))
+        dms, rms = DUR.sum(axis=1) * self.shift * 1e3, REF.sum(axis=1) * self.shift * 1e3
+        self.features_err.setdefault('DUR_PHONE[ms]', []).append(np.sqrt(np.mean((dms - rms) ** 2)))
+        if dms.std() > 0 and rms.std() > 0:
+            self.features_err.setdefault('DUR_PHONE[corr]', []).append(np.corrcoef(dms, rms)[0, 1])
