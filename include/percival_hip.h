@@ -320,6 +320,34 @@ int ptts_gemm(const float* A, const float* Bm, const float* bias, float* C,
               int in_mode, const float* in_scale, const float* in_shift, const float* mask_src,
               float alpha, int accumulate, const float* out_mask, float* colsum_b, void* stream);
 
+/* Which kernel family a ptts_gemm call with these arguments launches: the choice ptts_gemm itself makes, as a pure host
+ * function (no device, no launch; it reads the deterministic setting and the PTTS_GEMM_* / PTTS_TALL_* switches, as ptts_gemm
+ * does).  The scalar arguments are ptts_gemm's; has_bias / has_out_mask / has_colsum_b tell whether that pointer is given;
+ * aligned16 is non-zero when A, C, mask_src and out_mask (those that are given) all lie at 16-byte boundaries -- it selects
+ * only between the vector and the element-wise form of a thin kernel.  Returns a PTTS_GEMM_PATH_* value, or PTTS_EINVAL for
+ * arguments ptts_gemm refuses.  The tests assert the path of every case, so a moved threshold shows as a failure there. */
+#define PTTS_GEMM_PATH_GEMV          1   /* thin.hip gemv_rows_kernel<NT, false>: N <= 4, K >= 16, M >= 256, transA = 0   */
+#define PTTS_GEMM_PATH_GEMV_VEC      2   /* gemv_rows_kernel<NT, true>: also K % 4 == 0, K <= 256, lda % 4 == 0, aligned  */
+#define PTTS_GEMM_PATH_THIN_K        3   /* thin_k_kernel<KT, false>: K <= 4, M N >= 65536, transA = 0                    */
+#define PTTS_GEMM_PATH_THIN_K_VEC    4   /* thin_k_kernel<KT, true>: also N % 4 == 0, ldc % 4 == 0, aligned               */
+#define PTTS_GEMM_PATH_WCOL_PART     5   /* wcol_part_kernel + wcol_reduce_kernel: transA = 1, N <= 2, K >= 1024          */
+#define PTTS_GEMM_PATH_WCOL_PART4    6   /* wcol_part4_kernel + wcol_reduce_kernel: also M % 4 == 0, lda % 4 == 0, aligned */
+#define PTTS_GEMM_PATH_WCOL_ATOMIC   7   /* wcol_kernel: the partial rows exceed the stream's buffer (or, not told here: the
+                                            buffer cannot be allocated because the stream is being captured)             */
+#define PTTS_GEMM_PATH_NSPLIT        8   /* 256 < N <= 512, M >= 2048, K <= 2048, transA = 0: two calls, N = 256 and the rest */
+#define PTTS_GEMM_PATH_TALL_MT4      12  /* gemm_tall_kc_kernel<.., MT, 16>, 16 MT rows per workgroup: PTTS_GEMM_PATH_TALL_MT4 + MT - 4 */
+#define PTTS_GEMM_PATH_TALL_MT5      13
+#define PTTS_GEMM_PATH_TALL_MT6      14
+#define PTTS_GEMM_PATH_TALL_MT7      15
+#define PTTS_GEMM_PATH_TALL_MT8      16
+#define PTTS_GEMM_PATH_DMA           20  /* gemm_dma_kernel, one workgroup per 128 x 128 tile (edge tiles: the register-staged body) */
+#define PTTS_GEMM_PATH_DMA_STREAMK   21  /* gemm_dma_kernel, stream-K: equal (tile, k-step) ranges, fp32 atomics           */
+#define PTTS_GEMM_PATH_TILE          22  /* gemm_f32_mfma_kernel (register-staged), one workgroup per tile                 */
+#define PTTS_GEMM_PATH_TILE_STREAMK  23  /* gemm_f32_mfma_kernel, stream-K                                                 */
+int ptts_gemm_path(int M, int N, int K, int transA, long long lda, long long rows_per_seg, long long seg_stride,
+                   int transB, long long ldb, long long ldc, int in_mode, int accumulate,
+                   int has_bias, int has_out_mask, int has_colsum_b, int aligned16);
+
 /* Weight gradients of several layers in ONE launch: for every product  C[M,N] += T(A)[K,M]^T . B[K,N]  and, when
  * colsum_b is given,  colsum_b[N] += sum_k B[k,:]  (the bias gradient).  A is the layer input as stored ([K rows][lda]),
  * B the incoming gradient; T is the same fused transform as in ptts_gemm (in_mode on the stored A element, channel =

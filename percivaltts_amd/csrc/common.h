@@ -58,6 +58,10 @@ int thin_gemm_dispatch(const float* A, const float* Bm, const float* bias, float
                        long long ldc, int in_mode, const float* in_scale, const float* in_shift,
                        const float* mask_src, float alpha, int accumulate, const float* out_mask, hipStream_t st);
 
+// thin.hip: the kernel thin_gemm_dispatch picks for this product (PTTS_GEMM_PATH_*), 0 for none; host arithmetic only
+int thin_gemm_path(int M, int N, int K, int transA, long long lda, long long rows_per_seg, long long seg_stride, int transB,
+                   long long ldc, bool has_bias, bool has_out_mask, bool in_al16, bool out_al16);
+
 __device__ __forceinline__ float lrelu(float p, float alpha) { return p > 0.f ? p : alpha * p; }
 __device__ __forceinline__ float lrelu_d(float p, float alpha) { return p > 0.f ? 1.f : alpha; }
 

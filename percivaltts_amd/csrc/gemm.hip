@@ -899,6 +899,88 @@ extern "C" int ptts_gemm_wgrad_grouped(const ptts_wgrad_desc* descs, int n, void
     return PTTS_OK;
 }
 
+static int tall_kmax() {
+    static int v = -1;
+    if (v < 0) { const char* e = getenv("PTTS_TALL_KMAX"); v = e ? atoi(e) : 2048; }
+    return v;
+}
+
+static bool dma_enabled() {
+    static int v = -1;
+    if (v < 0) { const char* e = getenv("PTTS_GEMM_DMA"); v = e ? atoi(e) : 1; }
+    return v != 0;
+}
+
+// The whole choice ptts_gemm makes, on the host: which kernel family (a PTTS_GEMM_PATH_* value) and, for the 128x128 tile
+// kernels, the decomposition of the (tile, k-step) space.  allow_thin = false leaves the thin kernels out (thin_gemm_dispatch
+// declined: no partial-row buffer while the stream is captured, in deterministic mode).
+struct GemmPlan {
+    int path;
+    int tiles_n, ksteps;
+    long long tiles, iters_total, workers;
+};
+
+static GemmPlan gemm_plan(int M, int N, int K, int transA, long long lda, long long rows_per_seg, long long seg_stride,
+                          int transB, long long ldc, int in_mode, bool has_bias, bool has_out_mask, bool has_colsum_b,
+                          bool in_al16, bool out_al16, bool allow_thin) {
+    GemmPlan p;
+    p.path = 0; p.tiles_n = 0; p.ksteps = 0; p.tiles = 0; p.iters_total = 0; p.workers = 0;
+    // thin products (N <= 4 heads, K <= 4 outer products, 1-2 weighted column sums) never reach the MFMA tiles
+    if (allow_thin && thin_enabled() && !has_colsum_b) {
+        p.path = thin_gemm_path(M, N, K, transA, lda, rows_per_seg, seg_stride, transB, ldc, has_bias, has_out_mask, in_al16, out_al16);
+        if (p.path) return p;
+    }
+    // N slightly above one full-width tile (the critic's 260-wide spectral part): full-width tile + remainder
+    if (transA == 0 && N > TBN && N <= 2 * TBN && M >= 2048 && K <= 2048) { p.path = PTTS_GEMM_PATH_NSPLIT; return p; }
+    // tall products (M >> N, N in (128, 256]) take the full-width tile kernel: A read once, one round, no atomics
+    // (for deep K the stream-K 128x128 kernel below is faster: its two co-resident workgroups per CU overlap better)
+    if (transA == 0 && N > 128 && N <= TBN && M >= 2048 && K <= tall_kmax()) {
+        p.path = PTTS_GEMM_PATH_TALL_MT4 + pick_tall_mt(M) - 4;
+        return p;
+    }
+    const int tm = (M + BM - 1) / BM;
+    p.tiles_n = (N + BN - 1) / BN;
+    p.tiles = (long long)tm * p.tiles_n;
+    p.ksteps = (K + BK - 1) / BK;
+    p.iters_total = p.tiles * p.ksteps;
+    // persistent workgroups: two per CU (the second hides the first one's barriers), never less than
+    // 8 k-steps of work each
+    // stream-K pays when the tile count loads the 512 workgroup slots unevenly AND K is deep enough to amortise
+    // the atomic epilogue; otherwise one workgroup per tile (plain stores).
+    const long long slots = gemm_slots();
+    const double eff_dp = (double)p.tiles / (double)(((p.tiles + slots - 1) / slots) * slots);
+    // (atomic combination makes the last bits order-dependent: it is kept for the deep products only, K >= 2048 -- the
+    // reference's own batch, 10 x 400 frames, is a reduction over K = 4000 and ran at 3.5 TF on 14 tiles without it)
+    const bool streamk = p.ksteps >= 128 && eff_dp < 0.9 && !deterministic();
+    if (streamk) {
+        p.workers = slots;
+        if (p.workers > p.iters_total / 8) p.workers = p.iters_total / 8;
+        if (p.workers < 1) p.workers = 1;
+    } else {
+        p.workers = p.tiles;
+    }
+    // A rows are fetched as 16-byte pieces by the LDS-DMA path: the product must not need masking inside a row
+    const bool dma_ok = dma_enabled() && in_mode == PTTS_IN_NONE && transB == 0 && !has_out_mask && K >= 4 * BK;
+    p.path = dma_ok ? (streamk ? PTTS_GEMM_PATH_DMA_STREAMK : PTTS_GEMM_PATH_DMA)
+                    : (streamk ? PTTS_GEMM_PATH_TILE_STREAMK : PTTS_GEMM_PATH_TILE);
+    return p;
+}
+
+static bool gemm_al16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+extern "C" int ptts_gemm_path(int M, int N, int K, int transA, long long lda, long long rows_per_seg, long long seg_stride,
+                              int transB, long long ldb, long long ldc, int in_mode, int accumulate,
+                              int has_bias, int has_out_mask, int has_colsum_b, int aligned16) {
+    (void)accumulate;       // (part of the call, not of the choice)
+    PTTS_REQUIRE(!has_colsum_b || (transA == 1 && transB == 0), "gemm: colsum_b needs transA=1, transB=0 (a weight-gradient product)");
+    PTTS_REQUIRE(M > 0 && N > 0 && K > 0, "gemm: bad dims M=%d N=%d K=%d", M, N, K);
+    PTTS_REQUIRE(rows_per_seg > 0 && rows_per_seg < (1LL << 31) && lda > 0 && ldb > 0 && ldc >= N, "gemm: bad leading dims");
+    PTTS_REQUIRE(in_mode >= 0 && in_mode <= 2, "gemm: bad in_mode %d", in_mode);
+    PTTS_REQUIRE(!(has_out_mask && has_bias), "gemm: out_mask with bias is not defined");
+    return gemm_plan(M, N, K, transA, lda, rows_per_seg, seg_stride, transB, ldc, in_mode, has_bias != 0, has_out_mask != 0,
+                     has_colsum_b != 0, aligned16 != 0, aligned16 != 0, true).path;
+}
+
 extern "C" int ptts_gemm(const float* A, const float* Bm, const float* bias, float* C, int M, int N, int K,
                          int transA, long long lda, long long rows_per_seg, long long seg_stride, int transB,
                          long long ldb, long long ldc, int in_mode, const float* in_scale,
@@ -925,15 +1007,19 @@ extern "C" int ptts_gemm(const float* A, const float* Bm, const float* bias, flo
     if (prio < 0) { const char* e = getenv("PTTS_GEMM_PRIO"); prio = e ? atoi(e) : 1; }
     g.prio = prio;
 
-    // thin products (N <= 4 heads, K <= 4 outer products, 1-2 weighted column sums) never reach the MFMA tiles
-    if (thin_enabled() && !colsum_b) {
+    const bool in_al = gemm_al16(A) && gemm_al16(mask_src), out_al = gemm_al16(C) && gemm_al16(out_mask);
+    GemmPlan plan = gemm_plan(M, N, K, transA, lda, rows_per_seg, seg_stride, transB, ldc, in_mode, bias != nullptr, out_mask != nullptr,
+                              colsum_b != nullptr, in_al, out_al, true);
+    if (plan.path >= PTTS_GEMM_PATH_GEMV && plan.path <= PTTS_GEMM_PATH_WCOL_ATOMIC) {
         const int thin = thin_gemm_dispatch(A, Bm, bias, C, M, N, K, transA, lda, rows_per_seg, seg_stride, transB, ldb, ldc,
                                             in_mode, in_scale, in_shift, mask_src, alpha, accumulate, out_mask, st);
         if (thin < 0) return thin;
         if (thin == 1) return PTTS_OK;
+        plan = gemm_plan(M, N, K, transA, lda, rows_per_seg, seg_stride, transB, ldc, in_mode, bias != nullptr, out_mask != nullptr,
+                         colsum_b != nullptr, in_al, out_al, false);
     }
     // N slightly above one full-width tile (the critic's 260-wide spectral part): full-width tile + remainder
-    if (transA == 0 && N > TBN && N <= 2 * TBN && M >= 2048 && K <= 2048) {
+    if (plan.path == PTTS_GEMM_PATH_NSPLIT) {
         const int n1 = TBN, n2 = N - TBN;
         const float* B2 = transB == 0 ? Bm + n1 : Bm + (long long)n1 * ldb;
         int rc = ptts_gemm(A, Bm, bias, C, M, n1, K, transA, lda, rows_per_seg, seg_stride, transB, ldb, ldc, in_mode,
@@ -943,12 +1029,8 @@ extern "C" int ptts_gemm(const float* A, const float* Bm, const float* bias, flo
                          transB, ldb, ldc, in_mode, in_scale, in_shift, mask_src, alpha, accumulate,
                          out_mask ? out_mask + n1 : nullptr, nullptr, stream);
     }
-    // tall products (M >> N, N in (128, 256]) take the full-width tile kernel: A read once, one round, no atomics
-    // (for deep K the stream-K 128x128 kernel below is faster: its two co-resident workgroups per CU overlap better)
-    static int tall_kmax = -1;
-    if (tall_kmax < 0) { const char* e = getenv("PTTS_TALL_KMAX"); tall_kmax = e ? atoi(e) : 2048; }
-    if (transA == 0 && N > 128 && N <= TBN && M >= 2048 && K <= tall_kmax) {
-        const int mt = pick_tall_mt(M);
+    if (plan.path >= PTTS_GEMM_PATH_TALL_MT4 && plan.path <= PTTS_GEMM_PATH_TALL_MT8) {
+        const int mt = plan.path - PTTS_GEMM_PATH_TALL_MT4 + 4;
         dim3 tgrid((M + 16 * mt - 1) / (16 * mt)), tblock(TALL_THREADS);
 #define PTTS_TALL(TB, MD, MTT) hipLaunchKernelGGL((gemm_tall_kc_kernel<TB, MD, MTT, 16>), tgrid, tblock, 0, st, g)
 #define PTTS_TALL_MT(TB, MD)                                          \
@@ -972,27 +1054,10 @@ extern "C" int ptts_gemm(const float* A, const float* Bm, const float* bias, flo
 #undef PTTS_TALL
         return check_launch("gemm_tall");
     }
-    const int tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN;
-    const long long tiles = (long long)tm * tn;
-    g.tiles_n = tn;
-    g.ksteps = (K + BK - 1) / BK;
-    g.iters_total = tiles * g.ksteps;
-    // persistent workgroups: two per CU (the second hides the first one's barriers), never less than
-    // 8 k-steps of work each
-    // stream-K pays when the tile count loads the 512 workgroup slots unevenly AND K is deep enough to amortise
-    // the atomic epilogue; otherwise one workgroup per tile (plain stores).
-    const long long slots = gemm_slots();
-    const double eff_dp = (double)tiles / (double)(((tiles + slots - 1) / slots) * slots);
-    long long workers;
-    // (atomic combination makes the last bits order-dependent: it is kept for the deep products only, K >= 2048 -- the
-    // reference's own batch, 10 x 400 frames, is a reduction over K = 4000 and ran at 3.5 TF on 14 tiles without it)
-    if (g.ksteps >= 128 && eff_dp < 0.9 && !deterministic()) {
-        workers = slots;
-        if (workers > g.iters_total / 8) workers = g.iters_total / 8;
-        if (workers < 1) workers = 1;
-    } else {
-        workers = tiles;
-    }
+    g.tiles_n = plan.tiles_n;
+    g.ksteps = plan.ksteps;
+    g.iters_total = plan.iters_total;
+    const long long workers = plan.workers;
     g.workers = (int)workers;
     const bool split = (g.iters_total % workers != 0) || ((g.iters_total / workers) % g.ksteps != 0);
     if (split && !accumulate) {
@@ -1008,10 +1073,7 @@ extern "C" int ptts_gemm(const float* A, const float* Bm, const float* bias, flo
         case PTTS_IN_MASKMUL: PTTS_GEMM_LAUNCH(TA, TB, 0, PTTS_IN_MASKMUL); break; \
         default: PTTS_GEMM_LAUNCH(TA, TB, 0, PTTS_IN_NONE); break;               \
     }
-    static int use_dma = -1;
-    if (use_dma < 0) { const char* e = getenv("PTTS_GEMM_DMA"); use_dma = e ? atoi(e) : 1; }
-    // A rows are fetched as 16-byte pieces by the LDS-DMA path: the product must not need masking inside a row
-    const bool dma_ok = use_dma && in_mode == PTTS_IN_NONE && transB == 0 && !out_mask && K >= 4 * BK;
+    const bool dma_ok = plan.path == PTTS_GEMM_PATH_DMA || plan.path == PTTS_GEMM_PATH_DMA_STREAMK;
     if (dma_ok && transA == 0 && conv) hipLaunchKernelGGL((gemm_dma_kernel<0, 1>), grid, block, 0, st, g);
     else if (dma_ok && transA == 1 && conv) hipLaunchKernelGGL((gemm_dma_kernel<1, 1>), grid, block, 0, st, g);
     else if (dma_ok && transA == 0) hipLaunchKernelGGL((gemm_dma_kernel<0, 0>), grid, block, 0, st, g);

@@ -350,17 +350,48 @@ static float* wcol_workspace(hipStream_t st) {
 
 static inline bool thin_al16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// row blocks of the two-stage wcol form: enough to hide the loads, at least four rows per lane
+static int wcol_row_blocks(int M, int K, bool vec4) {
+    const int cbp = vec4 ? (M + 255) / 256 : (M + 63) / 64;
+    int rbp = (vec4 ? 512 : 2048) / cbp;
+    if (rbp > 512) rbp = 512;
+    if (rbp > (K + 15) / 16) rbp = (K + 15) / 16;
+    if (rbp < 1) rbp = 1;
+    return rbp;
+}
+
+// The thin kernel that takes this product (a PTTS_GEMM_PATH_* value), or 0 for the MFMA kernels: thin_gemm_dispatch's whole choice
+// but for the stream's partial-row buffer.  in_al16: A and mask_src at 16-byte boundaries; out_al16: C and out_mask.
+int thin_gemm_path(int M, int N, int K, int transA, long long lda, long long rows_per_seg, long long seg_stride, int transB,
+                   long long ldc, bool has_bias, bool has_out_mask, bool in_al16, bool out_al16) {
+    if (seg_stride != 0) return 0;
+    if (transA == 0 && N <= 4 && K >= 16 && M >= 256)
+        return (K % 4 == 0 && K <= 256 && lda % 4 == 0 && in_al16) ? PTTS_GEMM_PATH_GEMV_VEC : PTTS_GEMM_PATH_GEMV;
+    if (transA == 0 && K <= 4 && (long long)M * N >= 65536)
+        return (N % 4 == 0 && ldc % 4 == 0 && out_al16) ? PTTS_GEMM_PATH_THIN_K_VEC : PTTS_GEMM_PATH_THIN_K;
+    if (transA == 1 && transB == 0 && N <= 2 && K >= 1024 && !has_bias && !has_out_mask && rows_per_seg >= K) {
+        // two stages, no atomics, as long as the partial rows fit the stream's buffer
+        const bool vec4 = M % 4 == 0 && lda % 4 == 0 && in_al16;
+        if ((size_t)wcol_row_blocks(M, K, vec4) * M * N * sizeof(float) <= WCOL_WS_BYTES)
+            return vec4 ? PTTS_GEMM_PATH_WCOL_PART4 : PTTS_GEMM_PATH_WCOL_PART;
+        return deterministic() ? 0 : PTTS_GEMM_PATH_WCOL_ATOMIC;
+    }
+    return 0;
+}
+
 // returns 1 if the product was handled here, 0 if the caller should use the MFMA kernels, <0 on error
 int thin_gemm_dispatch(const float* A, const float* Bm, const float* bias, float* C, int M, int N, int K, int transA,
                        long long lda, long long rows_per_seg, long long seg_stride, int transB, long long ldb,
                        long long ldc, int in_mode, const float* in_scale, const float* in_shift,
                        const float* mask_src, float alpha, int accumulate, const float* out_mask, hipStream_t st) {
-    if (seg_stride != 0) return 0;
+    const int path = thin_gemm_path(M, N, K, transA, lda, rows_per_seg, seg_stride, transB, ldc, bias != nullptr, out_mask != nullptr,
+                                    thin_al16(A) && thin_al16(mask_src), thin_al16(C) && thin_al16(out_mask));
+    if (path == 0) return 0;
     ThinArgs g{A, Bm, bias, C, M, N, K, lda, ldb, ldc, transB, in_mode, in_scale, in_shift, mask_src, alpha, accumulate, out_mask};
-    if (transA == 0 && N <= 4 && K >= 16 && M >= 256) {
+    if (path == PTTS_GEMM_PATH_GEMV || path == PTTS_GEMM_PATH_GEMV_VEC) {
         int blocks = (M + 3) / 4;
         if (blocks > 2048) blocks = 2048;
-        const bool vec = K % 4 == 0 && K <= 256 && lda % 4 == 0 && thin_al16(A) && thin_al16(mask_src);
+        const bool vec = path == PTTS_GEMM_PATH_GEMV_VEC;
 #define PTTS_GEMV(NTT) do { if (vec) hipLaunchKernelGGL((gemv_rows_kernel<NTT, true>), dim3(blocks), dim3(256), 0, st, g); \
                             else hipLaunchKernelGGL((gemv_rows_kernel<NTT, false>), dim3(blocks), dim3(256), 0, st, g); } while (0)
         if (N == 1) PTTS_GEMV(1);
@@ -370,10 +401,10 @@ int thin_gemm_dispatch(const float* A, const float* Bm, const float* bias, float
         int rc = check_launch("gemv_rows");
         return rc ? rc : 1;
     }
-    if (transA == 0 && K <= 4 && (long long)M * N >= 65536) {
+    if (path == PTTS_GEMM_PATH_THIN_K || path == PTTS_GEMM_PATH_THIN_K_VEC) {
         long long b = ((long long)M * N + 1023) / 1024;
         if (b > 2048) b = 2048;
-        const bool vec = N % 4 == 0 && ldc % 4 == 0 && thin_al16(C) && thin_al16(out_mask);
+        const bool vec = path == PTTS_GEMM_PATH_THIN_K_VEC;
 #define PTTS_THINK(KTT) do { if (vec) hipLaunchKernelGGL((thin_k_kernel<KTT, true>), dim3((int)b), dim3(256), 0, st, g); \
                              else hipLaunchKernelGGL((thin_k_kernel<KTT, false>), dim3((int)b), dim3(256), 0, st, g); } while (0)
         if (K == 1) PTTS_THINK(1);
@@ -383,46 +414,40 @@ int thin_gemm_dispatch(const float* A, const float* Bm, const float* bias, float
         int rc = check_launch("thin_k");
         return rc ? rc : 1;
     }
-    if (transA == 1 && transB == 0 && N <= 2 && K >= 1024 && !bias && !out_mask && rows_per_seg >= K) {
-        // two stages, no atomics: enough row blocks to hide the loads, as long as the partial rows fit the stream's buffer
-        const bool vec4 = M % 4 == 0 && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (!mask_src || (reinterpret_cast<uintptr_t>(mask_src) & 15) == 0);
-        const int cbp = vec4 ? (M + 255) / 256 : (M + 63) / 64;
-        int rbp = (vec4 ? 512 : 2048) / cbp;
-        if (rbp > 512) rbp = 512;
-        if (rbp > (K + 15) / 16) rbp = (K + 15) / 16;              // (at least four rows per lane)
-        if (rbp < 1) rbp = 1;
-        float* part = ((size_t)rbp * M * N * sizeof(float) <= WCOL_WS_BYTES) ? wcol_workspace(st) : nullptr;
-        if (part) {
-            if (vec4 && N == 1) {
-                hipLaunchKernelGGL(wcol_part4_kernel<1>, dim3(cbp, rbp), dim3(256), 0, st, g, K, part);
-                hipLaunchKernelGGL(wcol_reduce_kernel<1>, dim3((M + 15) / 16), dim3(256), 0, st, part, rbp, M, N, C, ldc, accumulate);
-            } else if (vec4) {
-                hipLaunchKernelGGL(wcol_part4_kernel<2>, dim3(cbp, rbp), dim3(256), 0, st, g, K, part);
-                hipLaunchKernelGGL(wcol_reduce_kernel<2>, dim3((2 * M + 15) / 16), dim3(256), 0, st, part, rbp, M, N, C, ldc, accumulate);
-            } else if (N == 1) {
-                hipLaunchKernelGGL(wcol_part_kernel<1>, dim3(cbp, rbp), dim3(256), 0, st, g, K, part);
-                hipLaunchKernelGGL(wcol_reduce_kernel<1>, dim3((M + 15) / 16), dim3(256), 0, st, part, rbp, M, N, C, ldc, accumulate);
-            } else {
-                hipLaunchKernelGGL(wcol_part_kernel<2>, dim3(cbp, rbp), dim3(256), 0, st, g, K, part);
-                hipLaunchKernelGGL(wcol_reduce_kernel<2>, dim3((2 * M + 15) / 16), dim3(256), 0, st, part, rbp, M, N, C, ldc, accumulate);
-            }
-            int rcp = check_launch("wcol (two stages)");
-            return rcp ? rcp : 1;
+    const bool vec4 = path == PTTS_GEMM_PATH_WCOL_PART4;
+    const int cbp = vec4 ? (M + 255) / 256 : (M + 63) / 64;
+    const int rbp = wcol_row_blocks(M, K, vec4);
+    // (the buffer is refused while the stream is captured: then the atomics kernel below, like partial rows that do not fit)
+    float* part = path != PTTS_GEMM_PATH_WCOL_ATOMIC ? wcol_workspace(st) : nullptr;
+    if (part) {
+        if (vec4 && N == 1) {
+            hipLaunchKernelGGL(wcol_part4_kernel<1>, dim3(cbp, rbp), dim3(256), 0, st, g, K, part);
+            hipLaunchKernelGGL(wcol_reduce_kernel<1>, dim3((M + 15) / 16), dim3(256), 0, st, part, rbp, M, N, C, ldc, accumulate);
+        } else if (vec4) {
+            hipLaunchKernelGGL(wcol_part4_kernel<2>, dim3(cbp, rbp), dim3(256), 0, st, g, K, part);
+            hipLaunchKernelGGL(wcol_reduce_kernel<2>, dim3((2 * M + 15) / 16), dim3(256), 0, st, part, rbp, M, N, C, ldc, accumulate);
+        } else if (N == 1) {
+            hipLaunchKernelGGL(wcol_part_kernel<1>, dim3(cbp, rbp), dim3(256), 0, st, g, K, part);
+            hipLaunchKernelGGL(wcol_reduce_kernel<1>, dim3((M + 15) / 16), dim3(256), 0, st, part, rbp, M, N, C, ldc, accumulate);
+        } else {
+            hipLaunchKernelGGL(wcol_part_kernel<2>, dim3(cbp, rbp), dim3(256), 0, st, g, K, part);
+            hipLaunchKernelGGL(wcol_reduce_kernel<2>, dim3((2 * M + 15) / 16), dim3(256), 0, st, part, rbp, M, N, C, ldc, accumulate);
         }
-        if (deterministic()) return 0;
-        if (!accumulate) {
-            if (zero_f32_2d(C, (size_t)ldc, (size_t)N, (size_t)M, st) != PTTS_OK) return PTTS_ELAUNCH;
-        }
-        const int cb = (M + 63) / 64;
-        int rb = 1024 / cb;
-        if (rb < 1) rb = 1;
-        if (rb > 256) rb = 256;
-        if (N == 1) hipLaunchKernelGGL(wcol_kernel<1>, dim3(cb, rb), dim3(256), 0, st, g, K);
-        else hipLaunchKernelGGL(wcol_kernel<2>, dim3(cb, rb), dim3(256), 0, st, g, K);
-        int rc = check_launch("wcol");
-        return rc ? rc : 1;
+        int rcp = check_launch("wcol (two stages)");
+        return rcp ? rcp : 1;
     }
-    return 0;
+    if (deterministic()) return 0;
+    if (!accumulate) {
+        if (zero_f32_2d(C, (size_t)ldc, (size_t)N, (size_t)M, st) != PTTS_OK) return PTTS_ELAUNCH;
+    }
+    const int cb = (M + 63) / 64;
+    int rb = 1024 / cb;
+    if (rb < 1) rb = 1;
+    if (rb > 256) rb = 256;
+    if (N == 1) hipLaunchKernelGGL(wcol_kernel<1>, dim3(cb, rb), dim3(256), 0, st, g, K);
+    else hipLaunchKernelGGL(wcol_kernel<2>, dim3(cb, rb), dim3(256), 0, st, g, K);
+    int rc = check_launch("wcol");
+    return rc ? rc : 1;
 }
 
 }  // namespace ptts
