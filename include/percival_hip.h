@@ -1192,6 +1192,54 @@ int ptts_world_aperiodicity_batch(const float* wav, const long long* wav_off, lo
                                   const double* fwtable, size_t fwtable_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * DTW alignment of utterance pairs of unequal length (csrc/dtw.hip; the build's own definition,
+ * DESIGN.md section 3; the reference has no counterpart).  G [g_total, D] generated and
+ * R [r_total, D] reference rows, fp32, B <= 65535 pairs packed one after the other by g_off and
+ * r_off [B+1] (int64, DEVICE memory, as for the analysis batch); pair b has Tg = g_off[b+1] -
+ * g_off[b] and Tr = r_off[b+1] - r_off[b] frames.
+ *   local cost   c(i,j) = sqrt( sum_{d=c0}^{c1-1} (scale (G[i,d] - R[j,d]))^2 ) in fp64, the
+ *                columns added in index order, one IEEE square root, no contraction
+ *   accumulated  A(0,0) = c(0,0); A(i,j) = c(i,j) + min(A(i-1,j-1), A(i-1,j), A(i,j-1)), fp64; a
+ *                predecessor outside the matrix does not take part.  TIE RULE: the diagonal
+ *                predecessor wins a tie, then (i-1,j), then (i,j-1) -- a candidate replaces the
+ *                best so far only if it is strictly smaller, tried in that order
+ *   path         the back-pointers from (Tg-1, Tr-1) to (0,0), reported FORWARDS as gi[k], ri[k],
+ *                k = 0 .. L-1, max(Tg,Tr) <= L <= Tg+Tr-1, in the pair's slots path_off[b] ..
+ *                path_off[b] + Tg + Tr - 2 of gi, ri [path_total] int32 (path_off [B+1] int64
+ *                DEVICE memory; only the first L slots are written); L [B] int32; cost [B] fp64 =
+ *                A(Tg-1,Tr-1)
+ * info [B] int32 is WRITTEN (not OR-ed into): 0, or the PTTS_DTW_* bits of a pair that is not
+ * aligned -- it gets L = 0 and cost NaN, nothing of it is read or written out of bounds, and its
+ * neighbours are not affected.  PTTS_DTW_NOT_FINITE is set by the cost pass (a vector atomic OR).
+ * max_gen, max_ref: the longest Tg and Tr as the host measured them (the grid of the cost pass),
+ * each at most ptts_dtw_max_frames() = 2048 (three diagonals of A in LDS); a longer pair is
+ * PTTS_DTW_TOO_LONG.  cells: sum Tg Tr over the batch as the host measured it (the workspace).
+ * Workspace: ptts_dtw_workspace_bytes(cells, B, path_total) bytes (0 for arguments out of range),
+ * 256-byte aligned: the cell offsets, the fp64 local costs and the back-pointer bytes, both
+ * skewed (diagonal-major), and the backward paths; a shorter one is PTTS_EWORKSPACE.
+ * phases: PTTS_DTW_PHASE_ALL; a subset runs only those launches on what an earlier call left in
+ * the same workspace (tools/dtw_probe.py times them one by one).
+ * No atomics on results, nothing between workgroups: the same input gives the same bytes and a
+ * pair's result depends on nothing but that pair.  B = 0 succeeds without a launch; D < 1, a
+ * column range that is not 0 <= c0 < c1 <= D, a scale that is not finite or a null pointer is
+ * PTTS_EINVAL without a launch.
+ * ------------------------------------------------------------------------------------- */
+#define PTTS_DTW_EMPTY 1            /* Tg = 0 or Tr = 0 */
+#define PTTS_DTW_TOO_LONG 2         /* Tg > max_gen or Tr > max_ref */
+#define PTTS_DTW_NOT_FINITE 4       /* a local cost is not finite */
+#define PTTS_DTW_BAD_OFFSETS 8      /* the offsets do not lie inside the totals, or the cells exceed `cells` */
+#define PTTS_DTW_PHASE_COSTS 1      /* the layout and the local costs */
+#define PTTS_DTW_PHASE_WAVEFRONT 2  /* the accumulated costs and the back-pointers */
+#define PTTS_DTW_PHASE_BACKTRACK 4  /* the path, backwards, and its reversal */
+#define PTTS_DTW_PHASE_ALL 7
+int ptts_dtw_max_frames(void);
+size_t ptts_dtw_workspace_bytes(long long cells, int B, long long path_total);
+int ptts_dtw_align_batch(const float* G, const long long* g_off, long long g_total, const float* R, const long long* r_off,
+                         long long r_total, int B, int D, int c0, int c1, double scale, int max_gen, int max_ref, long long cells,
+                         const long long* path_off, long long path_total, int* gi, int* ri, int* L, double* cost, int* info,
+                         int phases, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Waveform pre-processing (csrc/preproc.hip; the reference's Vocoder.preprocwav,
  * vocoders.py:45-63; both definitions are this build's own).  fp32 in
  * memory, fp64 arithmetic, one rounding per sample.  Both entry points take a packed batch:

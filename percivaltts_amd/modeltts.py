@@ -152,7 +152,7 @@ class ModelTTS:
         return [self.vocoder.synthesis_device(c, pp_mcep=pp_mcep) for c in CMPs]
 
     def generate_params(self, inpath, outpath, fid_lst, gendir, do_objmeas=True, batch_size=8, pp_mcep=False, specdir=None,
-                        *, predict_batched=False, group_by_length=False, wavdir=None):
+                        *, predict_batched=False, group_by_length=False, objmeas_align=None, wavdir=None):
         """The reference's generate_wav (modeltts.py:144-205) up to the vocoder call: read mean4norm.dat / std4norm.dat beside
         `outpath`, predict each file of `fid_lst`, de-normalise (with MLPG when the vocoder has `mlpg_wins`), write
         `gendir/<fid>.cmp` as headerless float32 [T, featuressizeraw()], and, with `do_objmeas`, feed the vocoder's objective
@@ -184,7 +184,20 @@ class ModelTTS:
         utterance by utterance through its synthesis_device where it has no batched form (the files are the same either way), while
         they are on the device (csrc/pulsesynth.hip for VocoderPML, csrc/worldsynth.hip for VocoderWORLDDevice) and `wavdir/<fid>.wav` is written as 16-bit PCM at the vocoder's fs; the noise
         comes from the library's generator (ops.rng_seed).  The .cmp and .spec files are what they are without it.  A vocoder
-        without synthesis_device (VocoderWORLD itself among them) is a ValueError."""
+        without synthesis_device (VocoderWORLD itself among them) is a ValueError.
+
+        With `objmeas_align='dtw'` (and `do_objmeas`) the inputs and the targets keep their own lengths -- no data.croplen, so the
+        generated files are bit for bit those of do_objmeas=False -- and each utterance is measured along its DTW path to its target:
+        the generated parameters of a batch group (still on the device where MLPG leaves them there) and the de-normalised targets
+        go through ONE ops.dtw_align per group, over the vocoder's alignment_columns() (csrc/dtw.hip), and the
+        measures are fed through objmeasures_add_aligned(..., path=...): the keys of objmeasures_add, now along the path, plus
+        'DTW[cost/step]' and 'DTW[len ratio]'.  This is what measures inputs whose lengths are not the targets', e.g. those
+        expanded from predicted durations.  None: as ever, croplen included.  Any other value is a ValueError."""
+        if objmeas_align not in (None, 'dtw'):
+            raise ValueError('objmeas_align={!r} is not None or \'dtw\''.format(objmeas_align))
+        align = objmeas_align == 'dtw' and do_objmeas
+        if align:
+            a0, a1, ascale = self.vocoder.alignment_columns()      # ValueError for features without an alignment
         Ymean = np.fromfile(os.path.join(os.path.dirname(outpath), 'mean4norm.dat'), dtype='float32')
         Ystd = np.fromfile(os.path.join(os.path.dirname(outpath), 'std4norm.dat'), dtype='float32')
         nout, nraw = self.vocoder.featuressize(), self.vocoder.featuressizeraw()
@@ -198,7 +211,8 @@ class ModelTTS:
         X_test = data.load(inpath, fid_lst, verbose=1, label='Context labels: ')
         if do_objmeas:
             y_test = data.load(outpath, fid_lst, verbose=1, label='Output features: ')
-            X_test, y_test = data.croplen((X_test, y_test))
+            if not align:
+                X_test, y_test = data.croplen((X_test, y_test))
             self.vocoder.objmeasures_clear()
         if not os.path.isdir(gendir): os.makedirs(gendir)
         if specdir is not None:
@@ -243,6 +257,8 @@ class ModelTTS:
                     specs = [self.vocoder.decompress_spectrum(gen[i, :lens[i], s0:s1], pp_mcep=pp_mcep) for i in range(len(ys))]
                 if wavdir is not None:
                     wavs = self._synthesise([gen[i, :lens[i]] for i in range(len(ys))], pp_mcep)
+                if align:
+                    gen_rows = torch.cat([gen[i, :lens[i]] for i in range(len(ys))])
                 gen = gen.cpu().numpy()
                 CMPs = [gen[i, :lens[i]] for i in range(len(ys))]
             else:
@@ -253,17 +269,27 @@ class ModelTTS:
                 if wavdir is not None:
                     wavs = self._synthesise([torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)).to(self.to_device()) for c in CMPs],
                                             pp_mcep)
+                if align:
+                    gen_rows = torch.from_numpy(np.ascontiguousarray(np.concatenate(CMPs), dtype=np.float32)).to(self.to_device())
+            if align:                       # one alignment for the group; the paths and costs come back with two downloads
+                REFs = [self.denormalise(y_test[vi], Ymean, Ystd, mlpg_ignore=True) for vi in vis]
+                ref_rows = torch.from_numpy(np.ascontiguousarray(np.concatenate(REFs), dtype=np.float32)).to(gen_rows.device)
+                ali = ops.dtw_align(gen_rows.contiguous(), ref_rows, [c.shape[0] for c in CMPs], [r.shape[0] for r in REFs],
+                                    cols=(a0, a1), scale=ascale)
+                paths, costs = ali.host(), ali.cost.cpu().numpy()
             if specdir is not None:
                 for vi, spec in zip(vis, specs):
                     spec.cpu().numpy().tofile(os.path.join(specdir, fid_lst[vi] + '.spec'))
             if wavdir is not None:
                 for vi, wav in zip(vis, wavs):
                     vocoders.wavwrite(os.path.join(wavdir, fid_lst[vi] + '.wav'), wav, self.vocoder.fs)
-            for vi, CMP in zip(vis, CMPs):
+            for gi, (vi, CMP) in enumerate(zip(vis, CMPs)):
                 CMP = np.ascontiguousarray(CMP, dtype=np.float32)
                 assert CMP.shape[1] == nraw
                 CMP.tofile(os.path.join(gendir, fid_lst[vi] + '.cmp'))
-                if do_objmeas:
+                if align:
+                    self.vocoder.objmeasures_add_aligned(CMP, REFs[gi], path=paths[gi] + (costs[gi],))
+                elif do_objmeas:
                     self.vocoder.objmeasures_add(CMP, self.denormalise(y_test[vi], Ymean, Ystd, mlpg_ignore=True))
         stats = self.vocoder.objmeasures_stats() if do_objmeas else None
         print('Generation finished')

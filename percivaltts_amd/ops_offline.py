@@ -35,6 +35,7 @@ __all__ = [
     'ANALYSIS_MAX_UTTS', 'PackedOffsets', 'packed_offsets', 'analysis_status', 'wave_peak', 'f0_track_lengths', 'f0_track_device',
     'f0_candidates_batch', 'f0_viterbi_batch', 'f0_estimate_batch', 'f0_refine_batch', 'frame_harmonics_batch',
     'phase_coherence_batch', 'world_envelope_batch', 'world_aperiodicity_batch',
+    'DTW_WORKSPACE_CAP', 'dtw_max_frames', 'dtw_status', 'dtw_check', 'DtwAlignment', 'dtw_align',
     'RESAMPLE_MAX_UP', 'RESAMPLE_MAX_TABLE_BYTES', 'HIGHPASS_PADLEN', 'HIGHPASS_MAX_PADLEN', 'PREPROC_MAX_UTTS', 'preproc_check',
     'resample_length', 'resample_table', 'resample', 'highpass_tile', 'highpass_zerophase',
     'LABELS_MAX_LABEL', 'LABELS_CC_POINTS', 'LABELS_ANCHOR_START', 'LABELS_ANCHOR_END', 'LABELS_WILD', 'LABELS_CAPTURE_DIGITS',
@@ -1620,6 +1621,122 @@ def world_aperiodicity_batch(wav, wav_lengths, f0, voiced, frame_lengths, shift,
         call('ptts_world_aperiodicity_batch', *_wav_args(wav, wo), ptr(fo.dev), len(fo), T, ptr(f0), ptr(voiced), ptr(aper), int(nb),
              float(shift), float(fs), int(dftlen), ptr(fw), fwbytes, stream(), tag=(len(fo), T, dftlen, int(nb)))
     return aper
+
+
+# ----------------------------------------------------------------------------------------------
+# DTW alignment of utterance pairs of unequal length (the build's own): csrc/dtw.hip
+# ----------------------------------------------------------------------------------------------
+DTW_WORKSPACE_CAP = 1 << 30         # bytes of workspace one ptts_dtw_align_batch call may use; a larger batch is split along B
+_DTW_STATUS = tuple((_hip._define('PTTS_DTW_' + name), text) for name, text in (
+    ('EMPTY', 'a side has no frames'),
+    ('TOO_LONG', 'a side is longer than ptts_dtw_max_frames()'),
+    ('NOT_FINITE', 'a local cost is not finite (a NaN or Inf in the alignment columns)'),
+    ('BAD_OFFSETS', 'the offsets do not lie inside the tensors')))
+_DTW_PHASE_ALL = _hip._define('PTTS_DTW_PHASE_ALL')
+
+
+def dtw_max_frames():
+    """The longest side of one pair (ptts_dtw_max_frames; a host call, no device)."""
+    return int(_hip.lib().ptts_dtw_max_frames())
+
+
+def dtw_status(fn, info):
+    """The one read-back of a DTW alignment: info [B] int32 device, the PTTS_DTW_* bits of every pair -> ValueError naming the first
+    pair that has one set (ops.analysis_status for this family)."""
+    info = info.cpu().numpy()
+    for b in range(info.size):
+        for bit, text in _DTW_STATUS:
+            if info[b] & bit:
+                raise ValueError('{}: utterance {}: {}'.format(fn, b, text))
+
+
+def dtw_check(D, gen_lengths, ref_lengths, cols=None, scale=1.0):
+    """The argument rules of ops.dtw_align, raisable without a device: D columns per row, the pairs' lengths (lists of ints),
+    cols = (c0, c1) with 0 <= c0 < c1 <= D (None: all columns), a finite scale, no side longer than ptts_dtw_max_frames()
+    -> (c0, c1, scale, the pairs' cell counts Tg Tr, the pairs' path slots max(Tg + Tr - 1, 0))."""
+    if int(D) != D or D < 1:
+        raise ValueError('ops.dtw_align: D={!r} columns'.format(D))
+    c0, c1 = (0, D) if cols is None else cols
+    if int(c0) != c0 or int(c1) != c1 or not 0 <= c0 < c1 <= D:
+        raise ValueError('ops.dtw_align: cols={!r} is not a range 0 <= c0 < c1 <= D={}'.format(cols, D))
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError('ops.dtw_align: scale={!r} is not finite'.format(scale))
+    try:
+        gl, rl = [int(n) for n in gen_lengths], [int(n) for n in ref_lengths]
+    except (TypeError, ValueError):
+        raise ValueError('ops.dtw_align: gen_lengths and ref_lengths have to be the utterances\' lengths')
+    if len(gl) != len(rl) or not 1 <= len(gl) <= ANALYSIS_MAX_UTTS:
+        raise ValueError('ops.dtw_align: {} generated and {} reference lengths (1 to {} pairs)'.format(len(gl), len(rl), ANALYSIS_MAX_UTTS))
+    if min(gl + rl) < 0:
+        raise ValueError('ops.dtw_align: a negative length')
+    cap = dtw_max_frames()
+    if max(gl + rl) > cap:
+        raise ValueError('ops.dtw_align: a side of {} frames; at most {} (ptts_dtw_max_frames)'.format(max(gl + rl), cap))
+    return int(c0), int(c1), scale, [g * r for g, r in zip(gl, rl)], [max(g + r - 1, 0) for g, r in zip(gl, rl)]
+
+
+class DtwAlignment(object):
+    """What ops.dtw_align returns.  gi, ri: device int32 [path_offsets.total], pair b's path in its first lengths[b] slots from
+    path_offsets.off[b] (the slots behind them hold -1); path_offsets: the PackedOffsets of the slots, Tg + Tr - 1 per pair;
+    lengths: device int32 [B], the path lengths L; cost: device fp64 [B], A(Tg-1, Tr-1); info: device int32 [B], the PTTS_DTW_*
+    bits (0 for an aligned pair; a flagged one has L = 0).  host(): the paths as a list of (gi, ri) numpy arrays."""
+
+    def __init__(self, gi, ri, path_offsets, lengths, cost, info):
+        self.gi, self.ri, self.path_offsets, self.lengths, self.cost, self.info = gi, ri, path_offsets, lengths, cost, info
+
+    def host(self):
+        """[(gi_b, ri_b) numpy int32] for every pair, with one download."""
+        n, B = self.path_offsets.total, len(self.path_offsets)
+        flat = torch.cat([self.gi, self.ri, self.lengths]).cpu().numpy()
+        gi, ri, L, off = flat[:n], flat[n:2 * n], flat[2 * n:2 * n + B], self.path_offsets.off
+        return [(gi[off[b]:off[b] + L[b]].copy(), ri[off[b]:off[b] + L[b]].copy()) for b in range(B)]
+
+
+def dtw_align(gen, ref, gen_lengths, ref_lengths, cols=None, scale=1.0, info=None, phases=None):
+    """Dynamic time warping of B utterance pairs on the device (ptts_dtw_align_batch, csrc/dtw.hip; the definition with its tie
+    rule: DESIGN.md section 3): gen [sum Tg, D] and ref [sum Tr, D] fp32 device, the utterances one after the other, gen_lengths
+    and ref_lengths their frame counts (lists, or PackedOffsets), the local cost scale * ||gen[i, c0:c1] - ref[j, c0:c1]|| in fp64
+    -> a DtwAlignment.  A pair's result depends on nothing but that pair, and the same input gives the same bytes.  What cannot be
+    aligned (an empty side, a local cost that is not finite) is a PTTS_DTW_* bit in `info` [B] int32, which the op writes; without
+    `info` the op reads the status back itself and raises the ValueError.  phases (tools/dtw_probe.py): a subset of the launches,
+    on what the last call with the same arguments left in the workspace."""
+    fn = 'dtw_align'
+    if not (torch.is_tensor(gen) and torch.is_tensor(ref)) or gen.dim() != 2 or ref.dim() != 2 or gen.shape[1] != ref.shape[1]:
+        raise ValueError('ops.{}: gen and ref have to be packed [rows, D] device tensors of one width'.format(fn))
+    D = gen.shape[1]
+    go = packed_offsets(gen_lengths, gen.device, fn, 'gen_lengths')
+    ro = packed_offsets(ref_lengths, gen.device, fn, 'ref_lengths')
+    c0, c1, scale, cells, slots = dtw_check(D, go.lengths, ro.lengths, cols, scale)
+    if gen.shape[0] != go.total or ref.shape[0] != ro.total:
+        raise ValueError('ops.{}: gen {} and ref {} are not [sum(lengths)={} and {}, D]'.format(fn, tuple(gen.shape), tuple(ref.shape),
+                                                                                               go.total, ro.total))
+    _no_backward(fn, gen, ref)
+    f32c(gen, fn + '.gen'); f32c(ref, fn + '.ref')
+    B, dev = len(go), gen.device
+    po = packed_offsets(slots, dev, fn, 'path slots')
+    info, own = _info(info, B, dev, fn)
+    gi = torch.full((po.total,), -1, dtype=torch.int32, device=dev)
+    ri = torch.full((po.total,), -1, dtype=torch.int32, device=dev)
+    L = torch.empty(B, dtype=torch.int32, device=dev)
+    cost = torch.empty(B, dtype=torch.float64, device=dev)
+    l = _hip.lib()
+    b0 = 0
+    while b0 < B:                                           # as many pairs per call as DTW_WORKSPACE_CAP holds, at least one
+        n, ncells, nslots = 0, 0, 0
+        while b0 + n < B and (n == 0 or l.ptts_dtw_workspace_bytes(ncells + cells[b0 + n], n + 1, po.total) <= DTW_WORKSPACE_CAP):
+            ncells += cells[b0 + n]
+            n += 1
+        nws = l.ptts_dtw_workspace_bytes(ncells, n, po.total)
+        ws = _workspace(nws, dev)
+        call('ptts_dtw_align_batch', ptr(gen) if go.total else None, ptr(go.dev[b0:]), go.total, ptr(ref) if ro.total else None,
+             ptr(ro.dev[b0:]), ro.total, n, D, c0, c1, scale, max(go.lengths[b0:b0 + n]), max(ro.lengths[b0:b0 + n]), ncells,
+             ptr(po.dev[b0:]), po.total, ptr(gi) if po.total else None, ptr(ri) if po.total else None, ptr(L[b0:]), ptr(cost[b0:]),
+             ptr(info[b0:]), _DTW_PHASE_ALL if phases is None else int(phases), ptr(ws), nws, stream(), tag=(n, ncells, D))
+        b0 += n
+    if own:
+        dtw_status('ops.' + fn, info)
+    return DtwAlignment(gi, ri, po, L, cost, info)
 
 
 # ----------------------------------------------------------------------------------------------

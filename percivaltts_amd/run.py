@@ -340,14 +340,16 @@ def generate(fparams=None, dur_fparams=None, lab_path=None, lab_questions=None):
     """`dur_fparams` (with `lab_path`, the test utterances' labels -- times are not needed -- and `lab_questions`): the context
     rows come from predicted durations instead of cfg.inpath's aligned ones.  The duration model of that file predicts from
     cfg.dur_inpath (DurationModel.generate_durations, <model>-gen-dur/*.dur), contexts_from_durations expands them and normalises
-    the rows with the statistics stored beside cfg.inpath, and generation goes on from <model>-gen-lab/*.lab; the objective
-    measures are left out, since the generated utterances no longer have the targets' lengths."""
+    the rows with the statistics stored beside cfg.inpath, and generation goes on from <model>-gen-lab/*.lab.  The generated
+    utterances then no longer have the targets' lengths: without cfg.objmeas_align the objective measures are left out; with
+    cfg.objmeas_align = 'dtw' they are taken along each utterance's DTW path to its target of cfg.outpath
+    (generate_params(objmeas_align='dtw'), csrc/dtw.hip).  cfg.objmeas_align is passed on without dur_fparams as well."""
     if dur_fparams is not None and (lab_path is None or lab_questions is None):
         raise ValueError('generate: dur_fparams goes with lab_path and lab_questions')
     fparams = cfg.fparams_fullset if fparams is None else fparams
     fids = readids(cfg.fileids)
     fid_lst_test = fids[cfg.id_valid_start + cfg.id_valid_nb:cfg.id_valid_start + cfg.id_valid_nb + cfg.id_test_nb]
-    inpath, do_objmeas = cfg.inpath, True
+    inpath, do_objmeas, objmeas_align = cfg.inpath, True, getattr(cfg, 'objmeas_align', None)
     if dur_fparams is not None:
         durmod = build_duration_model()
         durmod.load(dur_fparams)
@@ -356,7 +358,7 @@ def generate(fparams=None, dur_fparams=None, lab_path=None, lab_questions=None):
         del durmod
         inpath = os.path.splitext(fparams)[0] + '-gen-lab/*.lab:(-1,' + str(ctxsize) + ')'
         contexts_from_durations(lab_path, fid_lst_test, lab_questions, durdir + '/*.dur', cfg.inpath, inpath)
-        do_objmeas = False
+        do_objmeas = objmeas_align is not None
     mod = build_model()
     mod.load(fparams)
     mod.generate_cmp(inpath, os.path.splitext(fparams)[0] + '-gen/*.cmp', fid_lst_test)
@@ -373,7 +375,7 @@ def generate(fparams=None, dur_fparams=None, lab_path=None, lab_questions=None):
                         wavdir=(getattr(cfg, 'wavdir', os.path.splitext(fparams)[0] + '-demo-snd')
                                 if hasattr(mod.vocoder, 'synthesis_device') else None),
                         predict_batched=bool(getattr(cfg, 'predict_batched', False)),
-                        group_by_length=bool(getattr(cfg, 'group_by_length', False)))
+                        group_by_length=bool(getattr(cfg, 'group_by_length', False)), objmeas_align=objmeas_align)
 
 
 if __name__ == "__main__":

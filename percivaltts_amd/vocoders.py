@@ -175,6 +175,63 @@ class Vocoder(object):
             print('{}: {}'.format(key, stats[key]))
         return stats
 
+    # Objective measures of a pair of unequal length, along its DTW path (the build's own; DESIGN.md section 3, "DTW alignment")
+    def alignment_columns(self):
+        """(c0, c1, scale): the columns [c0, c1) of the raw features whose distance, times `scale`, is the local cost of the DTW
+        alignment.  Overridden by the vocoders that have an alignment."""
+        raise ValueError('{} has no alignment columns: its features are not frame-level'.format(self.name()))
+
+    @staticmethod
+    def check_path(gi, ri, Tg, Tr):
+        """A DTW path over a Tg x Tr matrix: (0,0) to (Tg-1,Tr-1) in steps (1,1), (1,0), (0,1) -> (gi, ri) as int64 arrays."""
+        gi, ri = np.asarray(gi), np.asarray(ri)
+        if gi.ndim != 1 or gi.shape != ri.shape or gi.size < 1 or gi.dtype.kind not in 'iu' or ri.dtype.kind not in 'iu':
+            raise ValueError('objmeasures_add_aligned: the path is not two integer index lists of one length')
+        gi, ri = gi.astype(np.int64), ri.astype(np.int64)
+        if gi.min() < 0 or ri.min() < 0 or gi.max() >= Tg or ri.max() >= Tr:
+            raise ValueError('objmeasures_add_aligned: the path leaves the {} x {} frames'.format(Tg, Tr))
+        if (gi[0], ri[0]) != (0, 0) or (gi[-1], ri[-1]) != (Tg - 1, Tr - 1):
+            raise ValueError('objmeasures_add_aligned: the path does not run from (0,0) to ({},{})'.format(Tg - 1, Tr - 1))
+        dg, dr = np.diff(gi), np.diff(ri)
+        if not (((dg == 0) | (dg == 1)) & ((dr == 0) | (dr == 1)) & (dg + dr >= 1)).all():
+            raise ValueError('objmeasures_add_aligned: a step of the path is not one of (1,1), (1,0), (0,1)')
+        return gi, ri
+
+    def objmeasures_add_aligned(self, CMP, REF, path=None):
+        """objmeasures_add for a generated CMP [Tg, >=raw] and a reference REF [Tr, >=raw] of unequal length: the class's own
+        objmeasures_add(CMP[gi], REF[ri]) along the DTW path (gi, ri), so that every key keeps its meaning, plus
+        'DTW[cost/step]' = cost / L and 'DTW[len ratio]' = Tg / Tr.  path: None -- the pair is aligned on the device over
+        alignment_columns() (ops.dtw_align); or (gi, ri) or (gi, ri, cost), e.g. of one ops.dtw_align over a batch -- then
+        nothing here touches the device, and a cost that is not given is the path's own, summed in fp64 in path order."""
+        CMP, REF = np.asarray(CMP), np.asarray(REF)
+        raw = self.featuressizeraw()
+        if CMP.ndim != 2 or REF.ndim != 2 or min(CMP.shape[0], REF.shape[0]) < 1 or min(CMP.shape[1], REF.shape[1]) < raw:
+            raise ValueError('objmeasures_add_aligned: CMP {} and REF {} are not [T>=1, >={}]'.format(CMP.shape, REF.shape, raw))
+        c0, c1, scale = self.alignment_columns()
+        Tg, Tr = CMP.shape[0], REF.shape[0]
+        cost = None
+        if path is None:
+            import torch
+            from . import backend_hip, ops_offline as ops
+            dev = backend_hip.device()
+            g = torch.from_numpy(np.ascontiguousarray(CMP[:, :raw], dtype=np.float32)).to(dev)
+            r = torch.from_numpy(np.ascontiguousarray(REF[:, :raw], dtype=np.float32)).to(dev)
+            res = ops.dtw_align(g, r, [Tg], [Tr], cols=(c0, c1), scale=scale)
+            gi, ri = res.host()[0]
+            cost = float(res.cost.cpu()[0])
+        elif len(path) == 3:
+            gi, ri, cost = path
+            cost = float(cost)
+        else:
+            gi, ri = path
+        gi, ri = self.check_path(gi, ri, Tg, Tr)
+        if cost is None:
+            d = scale * (CMP[gi, c0:c1].astype(np.float64) - REF[ri, c0:c1].astype(np.float64))
+            cost = float(np.sum(np.sqrt(np.sum(d * d, axis=1))))
+        self.objmeasures_add(CMP[gi], REF[ri])
+        self.features_err.setdefault('DTW[cost/step]', []).append(cost / gi.size)
+        self.features_err.setdefault('DTW[len ratio]', []).append(Tg / float(Tr))
+
     def _out_of_scope(self, *a, **k):
         """analysisf / analysisfid / synthesis promise pulsemodel's or pyworld's signal processing, which this build does not have.
         The build's own synthesisers are VocoderPML.synthesis_device and VocoderWORLDDevice.synthesis_device."""
@@ -298,6 +355,15 @@ class VocoderF0Spec(Vocoder):
         spectrg = log2db(REF[:, 1:1 + self.spec_size])
         specgen = log2db(CMP[:, 1:1 + self.spec_size])
         self.features_err.setdefault('SPEC[dB]', []).append(np.sqrt(np.mean((spectrg - specgen)**2, 0)))
+
+    def alignment_columns(self):
+        """The spectral columns, times the log2db factor: the local cost is a distance in dB over the bands.  For 'mcep' c_0 is
+        left out (the mel-cepstral-distortion convention), so a spec_size of 1 has nothing to align on."""
+        c0 = 2 if self.spec_type == 'mcep' else 1
+        if c0 >= 1 + self.spec_size:
+            raise ValueError('{}: no alignment columns for spec_type={!r} with spec_size={}'.format(self.name(), self.spec_type,
+                                                                                                    self.spec_size))
+        return c0, 1 + self.spec_size, log2db(1.0)
 
     def _objmeasures_add_band(self, key, CMP, REF, size):
         lo = 1 + self.spec_size
@@ -736,6 +802,9 @@ class DurationFeatures(Vocoder):
     def specsize(self): return 0
     def noisesize(self): return 0
     def vuvsize(self): return 0
+
+    def alignment_columns(self):
+        raise ValueError('DurationFeatures has no alignment: durations are per phone, and both sides have the same phones')
 
     def objmeasures_add(self, DUR, REF):
         """DUR, REF [P, nstates] in frames: the RMSE per state in frames, and per phone (the states summed) the RMSE in ms and the
