@@ -1240,6 +1240,80 @@ int ptts_dtw_align_batch(const float* G, const long long* g_off, long long g_tot
                          int phases, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Forced alignment by flat-start Viterbi training (segmental k-means; csrc/align.hip; the build's
+ * own definition; the reference has no counterpart and nothing is claimed
+ * about HTK's numbers).  Monophone, left-to-right, no skips, one diagonal Gaussian per state, no
+ * transition probabilities.  All arithmetic fp64; the features fp32 in memory.
+ *   chain       utterance b is a chain of N = state_off[b+1] - state_off[b] states in a fixed order
+ *               over T = frame_off[b+1] - frame_off[b] rows of X [t_total, Dx] (offsets [B+1] int64
+ *               in DEVICE memory, B <= 65535).  Chain state n uses the Gaussian gauss[state_off[b]
+ *               + n] in [0, Q) (gauss [n_total] int32); the kernels know nothing else about phones
+ *   emission    e(t,n) = -0.5 (sum_d ((x_d - mu[q,d]) (x_d - mu[q,d])) w[q,d] + g[q]), x = X[t, c0:c1],
+ *               D = c1 - c0, q = gauss[n]; the columns added in index order, no contraction.
+ *               mu, w [Q,D] and g [Q] fp64: w = 1 / var, g = sum_d log var[q,d]; the constant
+ *               D log 2 pi is dropped
+ *   alignment   V(0,0) = e(0,0), V(0,n>0) unreachable; V(t,n) = e(t,n) + max(V(t-1,n), V(t-1,n-1)),
+ *               an unreachable predecessor does not take part.  TIE RULE: staying wins -- the
+ *               advance from n-1 replaces it only if it is strictly greater.  The path is followed
+ *               back from (T-1, N-1).  dur [n_total] int32: frames in chain state n, every dur >= 1
+ *               and sum dur = T; state [t_total] int32 (or NULL): the chain state of frame t;
+ *               score [B] fp64 = V(T-1,N-1)
+ * info [B] int32 is WRITTEN (not OR-ed into): 0, or the PTTS_ALIGN_* bits of an utterance that is
+ * not aligned -- it gets dur = zeros, state = -1 and score = NaN (with PTTS_ALIGN_BAD_OFFSETS the
+ * score alone: its slots are not known); nothing else of it is read or written, and every other
+ * utterance of the batch comes out exactly as it does alone.  NOT_FINITE and BAD_GAUSS are set by
+ * the emission pass (a vector atomic OR on the flag word).
+ * cells: sum T N over the utterances that can be aligned, as the host measured it (the workspace);
+ * an utterance that does not fit into what is left of it is PTTS_ALIGN_BAD_OFFSETS.
+ * Workspace: ptts_align_workspace_bytes(cells, B, t_total) bytes (0 for arguments out of range),
+ * 256-byte aligned: two offset arrays, the time loop's scores, the fp64 emissions row-major
+ * (a row of N rounded up to the states of a lane, at most 31 more) and 64 back-pointer words per
+ * frame; a shorter one is PTTS_EWORKSPACE.
+ * phases: PTTS_ALIGN_PHASE_ALL; a subset runs only those launches on what an earlier call left in
+ * the same workspace (tools/align_probe.py times them one by one).  The outputs are written by
+ * the backtrack phase.
+ * ptts_align_accumulate: count[q] += frames, s1[q,d] += sum x_d, s2[q,d] += sum x_d x_d (count
+ * [Q] int64, s1 and s2 [Q,D] fp64) over the frames whose chain state uses q, ADDED to what the
+ * arrays hold, so that a corpus goes through in several calls; a Gaussian without frames in the
+ * call is left untouched.  occ [n_total] int32: the indices into gauss / dur of the chain states,
+ * sorted by Gaussian (the host built gauss); occ_off [Q+1] int64: Gaussian q's run of occ (both
+ * DEVICE memory).  An entry whose state does not use q, and an utterance whose dur are negative
+ * or sum to more than its frames (a flagged one has zeros), add nothing.  The frames of a
+ * Gaussian are added in a fixed order, four partial sums in the table's order, then those four.
+ * Workspace: ptts_align_accumulate_workspace_bytes(n_total) (the first row of every state).
+ * ptts_align_update: for count[q] >= min_count (>= 1): mu = s1 / count, var = max(s2 / count -
+ * mu mu, floor[d]), w = 1 / var, g = sum_d log var in index order; kept[q] = 0 and floored[q] =
+ * the variances that took the floor.  Below min_count mu, w, g stay and kept[q] = 1.
+ * No floating-point atomics, nothing between workgroups, no device allocation: the same call on
+ * the same inputs writes the same bytes.  B = 0 succeeds without a launch; invalid scalar
+ * arguments (Dx < 1, not 0 <= c0 < c1 <= Dx, Q < 1, B > 65535, phases) or a null pointer are
+ * PTTS_EINVAL without a launch.
+ * ------------------------------------------------------------------------------------- */
+#define PTTS_ALIGN_EMPTY 1          /* T = 0 or N = 0 */
+#define PTTS_ALIGN_TOO_LONG 2       /* N > ptts_align_max_states() */
+#define PTTS_ALIGN_TOO_SHORT 4      /* T < N */
+#define PTTS_ALIGN_NOT_FINITE 8     /* an emission or the score is not finite */
+#define PTTS_ALIGN_BAD_OFFSETS 16   /* the offsets do not lie inside the totals, or the cells exceed `cells` */
+#define PTTS_ALIGN_BAD_GAUSS 32     /* an index of gauss lies outside [0, Q) */
+#define PTTS_ALIGN_PHASE_EMISSIONS 1  /* the layout and the emissions */
+#define PTTS_ALIGN_PHASE_TIME_LOOP 2  /* the recurrence and the back-pointer bits */
+#define PTTS_ALIGN_PHASE_BACKTRACK 4  /* the path: dur, state; the outputs of flagged utterances */
+#define PTTS_ALIGN_PHASE_ALL 7
+int ptts_align_max_states(void);
+size_t ptts_align_workspace_bytes(long long cells, int B, long long t_total);
+int ptts_align_viterbi_batch(const float* X, const long long* frame_off, long long t_total, int Dx, int c0, int c1,
+                             const int* gauss, const long long* state_off, long long n_total, const double* mu, const double* w,
+                             const double* g, int Q, int B, long long cells, int* dur, int* state /* or NULL */, double* score,
+                             int* info, int phases, void* workspace, size_t workspace_bytes, void* stream);
+size_t ptts_align_accumulate_workspace_bytes(long long n_total);
+int ptts_align_accumulate(const float* X, const long long* frame_off, long long t_total, int Dx, int c0, int c1,
+                          const int* gauss, const long long* state_off, long long n_total, const int* dur, const int* occ,
+                          const long long* occ_off, int Q, int B, long long* count, double* s1, double* s2, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int ptts_align_update(const long long* count, const double* s1, const double* s2, const double* floor, int Q, int D,
+                      long long min_count, double* mu, double* w, double* g, int* kept, int* floored, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Waveform pre-processing (csrc/preproc.hip; the reference's Vocoder.preprocwav,
  * vocoders.py:45-63; both definitions are this build's own).  fp32 in
  * memory, fp64 arithmetic, one rounding per sample.  Both entry points take a packed batch:

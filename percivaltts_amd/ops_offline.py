@@ -36,6 +36,8 @@ __all__ = [
     'f0_candidates_batch', 'f0_viterbi_batch', 'f0_estimate_batch', 'f0_refine_batch', 'frame_harmonics_batch',
     'phase_coherence_batch', 'world_envelope_batch', 'world_aperiodicity_batch',
     'DTW_WORKSPACE_CAP', 'dtw_max_frames', 'dtw_status', 'dtw_check', 'DtwAlignment', 'dtw_align',
+    'ALIGN_WORKSPACE_CAP', 'ALIGN_FLAGS', 'align_max_states', 'align_status', 'align_check', 'AlignResult', 'align_viterbi',
+    'align_occurrences', 'align_accumulate', 'align_update', 'align_uniform', 'AlignModel', 'forced_align_train',
     'RESAMPLE_MAX_UP', 'RESAMPLE_MAX_TABLE_BYTES', 'HIGHPASS_PADLEN', 'HIGHPASS_MAX_PADLEN', 'PREPROC_MAX_UTTS', 'preproc_check',
     'resample_length', 'resample_table', 'resample', 'highpass_tile', 'highpass_zerophase',
     'LABELS_MAX_LABEL', 'LABELS_CC_POINTS', 'LABELS_ANCHOR_START', 'LABELS_ANCHOR_END', 'LABELS_WILD', 'LABELS_CAPTURE_DIGITS',
@@ -1737,6 +1739,341 @@ def dtw_align(gen, ref, gen_lengths, ref_lengths, cols=None, scale=1.0, info=Non
     if own:
         dtw_status('ops.' + fn, info)
     return DtwAlignment(gi, ri, po, L, cost, info)
+
+
+# ----------------------------------------------------------------------------------------------
+# forced alignment by flat-start Viterbi training (the build's own): csrc/align.hip
+# ----------------------------------------------------------------------------------------------
+ALIGN_WORKSPACE_CAP = 1 << 30       # bytes of workspace one ptts_align_viterbi_batch call may use; a larger batch is split along B
+ALIGN_FLAGS = tuple((name, _hip._define('PTTS_ALIGN_' + name), text) for name, text in (
+    ('EMPTY', 'no frames or no states'),
+    ('TOO_LONG', 'more states than ptts_align_max_states()'),
+    ('TOO_SHORT', 'fewer frames than states'),
+    ('NOT_FINITE', 'an emission or the score is not finite (a NaN or Inf in the alignment columns or the model)'),
+    ('BAD_OFFSETS', 'the offsets do not lie inside the tensors'),
+    ('BAD_GAUSS', 'a Gaussian index outside [0, Q)')))
+_ALIGN_PHASE_ALL = _hip._define('PTTS_ALIGN_PHASE_ALL')
+
+
+def align_max_states():
+    """The longest chain of one utterance (ptts_align_max_states; a host call, no device)."""
+    return int(_hip.lib().ptts_align_max_states())
+
+
+def align_status(fn, info, names=None):
+    """The one read-back of an alignment: info [B] int32 (device or numpy), the PTTS_ALIGN_* bits of every utterance -> ValueError
+    naming the first utterance that has one set (names[b] if given, else its index) and the flag."""
+    info = info.cpu().numpy() if torch.is_tensor(info) else np.asarray(info)
+    for b in range(info.size):
+        for flag, bit, text in ALIGN_FLAGS:
+            if info[b] & bit:
+                raise ValueError('{}: utterance {}: PTTS_ALIGN_{}: {}'.format(fn, b if names is None else names[b], flag, text))
+
+
+def align_check(Dx, frame_lengths, state_lengths, Q, cols=None):
+    """The argument rules of ops.align_viterbi, raisable without a device: Dx columns per row, the utterances' frame and state
+    counts (lists of ints), Q Gaussians, cols = (c0, c1) with 0 <= c0 < c1 <= Dx (None: all columns)
+    -> (c0, c1, the utterances' cell counts T N; 0 for one the kernels will flag)."""
+    if int(Dx) != Dx or Dx < 1:
+        raise ValueError('ops.align_viterbi: Dx={!r} columns'.format(Dx))
+    c0, c1 = (0, Dx) if cols is None else cols
+    if int(c0) != c0 or int(c1) != c1 or not 0 <= c0 < c1 <= Dx:
+        raise ValueError('ops.align_viterbi: cols={!r} is not a range 0 <= c0 < c1 <= Dx={}'.format(cols, Dx))
+    if int(Q) != Q or Q < 1:
+        raise ValueError('ops.align_viterbi: Q={!r} Gaussians'.format(Q))
+    try:
+        fl, sl = [int(n) for n in frame_lengths], [int(n) for n in state_lengths]
+    except (TypeError, ValueError):
+        raise ValueError('ops.align_viterbi: frame_lengths and state_lengths have to be the utterances\' lengths')
+    if len(fl) != len(sl) or not 1 <= len(fl) <= ANALYSIS_MAX_UTTS:
+        raise ValueError('ops.align_viterbi: {} frame and {} state counts (1 to {} utterances)'.format(len(fl), len(sl), ANALYSIS_MAX_UTTS))
+    if min(fl + sl) < 0:
+        raise ValueError('ops.align_viterbi: a negative length')
+    if sum(fl) >= 1 << 31 or sum(sl) >= 1 << 31:
+        raise ValueError('ops.align_viterbi: {} frames and {} states; fewer than 2^31 each'.format(sum(fl), sum(sl)))
+    cap = align_max_states()
+    return int(c0), int(c1), [t * n if 1 <= n <= min(t, cap) else 0 for t, n in zip(fl, sl)]
+
+
+class AlignResult(object):
+    """What ops.align_viterbi returns, all on the device.  dur: int32 [sum N], the frames in every chain state; state: int32 [sum T],
+    the chain state of every frame (None unless asked for); score: fp64 [B], V(T-1, N-1); info: int32 [B], the PTTS_ALIGN_* bits
+    (0 for an aligned utterance; a flagged one has dur 0, state -1 and score NaN); frame_offsets, state_offsets: the PackedOffsets."""
+
+    def __init__(self, dur, state, score, info, frame_offsets, state_offsets):
+        self.dur, self.state, self.score, self.info = dur, state, score, info
+        self.frame_offsets, self.state_offsets = frame_offsets, state_offsets
+
+
+def _align_model_check(fn, mu, w, g):
+    for name, t in (('mu', mu), ('w', w), ('g', g)):
+        _dev_tensor(t, torch.float64, '{}.{}'.format(fn, name))
+    if mu.dim() != 2 or min(mu.shape) < 1 or tuple(w.shape) != tuple(mu.shape) or tuple(g.shape) != (mu.shape[0],):
+        raise ValueError('ops.{}: mu {}, w {} and g {} are not [Q,D], [Q,D] and [Q]'.format(fn, tuple(mu.shape), tuple(w.shape), tuple(g.shape)))
+    return mu.shape
+
+
+def _align_inputs(fn, X, frame_lengths, gauss, state_lengths):
+    if not torch.is_tensor(X) or X.dim() != 2 or X.shape[1] < 1:
+        raise ValueError('ops.{}: X has to be a packed [rows, Dx] device tensor'.format(fn))
+    fo = packed_offsets(frame_lengths, X.device, fn, 'frame_lengths')
+    so = packed_offsets(state_lengths, X.device, fn, 'state_lengths')
+    if X.shape[0] != fo.total:
+        raise ValueError('ops.{}: X {} is not [sum(frame_lengths)={}, Dx]'.format(fn, tuple(X.shape), fo.total))
+    _no_backward(fn, X)
+    f32c(X, fn + '.X')
+    _dev_tensor(gauss, torch.int32, fn + '.gauss', (so.total,))
+    return fo, so
+
+
+def _align_chunks(cells, fo, so, cap):
+    """[(first utterance, count, cells)]: as many utterances per call as `cap` bytes of workspace hold, at least one."""
+    l, B, b0, out = _hip.lib(), len(fo), 0, []
+    while b0 < B:
+        n, ncells = 0, 0
+        while b0 + n < B and (n == 0 or l.ptts_align_workspace_bytes(ncells + cells[b0 + n], n + 1, int(fo.off[b0 + n + 1] - fo.off[b0])) <= cap):
+            ncells += cells[b0 + n]
+            n += 1
+        out.append((b0, n, ncells))
+        b0 += n
+    return out
+
+
+def align_viterbi(X, frame_lengths, gauss, state_lengths, mu, w, g, cols=None, want_state=True, info=None, phases=None,
+                  workspace_bytes=None):
+    """Viterbi alignment of B utterances to their chains on the device (ptts_align_viterbi_batch, csrc/align.hip; the definition
+    with its tie rule -- staying wins -- is in DESIGN.md section 3): X [sum T, Dx] fp32 device, the utterances one after the other,
+    frame_lengths their frame counts; gauss [sum N] int32 device, the Gaussian of every chain state, state_lengths the chains'
+    lengths (lists, or PackedOffsets); mu, w [Q, D] and g [Q] fp64 device with D = c1 - c0 the width of cols (None: all columns of
+    X) -> an AlignResult.  An utterance's result depends on nothing but that utterance, and the same input gives the same bytes.
+    What cannot be aligned is a PTTS_ALIGN_* bit in `info` [B] int32, which the op writes; without `info` the op reads the status
+    back itself and raises the ValueError.  workspace_bytes (default ALIGN_WORKSPACE_CAP): the batch goes through in chunks of
+    utterances whose workspace stays below it.  phases (tools/align_probe.py): a subset of the launches, on what the last call with
+    the same arguments left in the workspace."""
+    fn = 'align_viterbi'
+    fo, so = _align_inputs(fn, X, frame_lengths, gauss, state_lengths)
+    Q, D = _align_model_check(fn, mu, w, g)
+    c0, c1, cells = align_check(X.shape[1], fo.lengths, so.lengths, Q, cols)
+    if c1 - c0 != D:
+        raise ValueError('ops.{}: the model has {} columns, cols={} selects {}'.format(fn, D, (c0, c1), c1 - c0))
+    B, dev = len(fo), X.device
+    info, own = _info(info, B, dev, fn)
+    dur = torch.zeros(so.total, dtype=torch.int32, device=dev)
+    state = torch.full((fo.total,), -1, dtype=torch.int32, device=dev) if want_state else None
+    score = torch.full((B,), float('nan'), dtype=torch.float64, device=dev)
+    l = _hip.lib()
+    for b0, n, ncells in _align_chunks(cells, fo, so, ALIGN_WORKSPACE_CAP if workspace_bytes is None else int(workspace_bytes)):
+        f0, f1, s0, s1 = (int(v) for v in (fo.off[b0], fo.off[b0 + n], so.off[b0], so.off[b0 + n]))
+        whole = n == B
+        foff = fo.dev if whole else fo.dev[b0:b0 + n + 1] - f0
+        soff = so.dev if whole else so.dev[b0:b0 + n + 1] - s0
+        nws = l.ptts_align_workspace_bytes(ncells, n, f1 - f0)
+        ws = _workspace(nws, dev)
+        call('ptts_align_viterbi_batch', ptr(X[f0:]) if f1 > f0 else None, ptr(foff), f1 - f0, X.shape[1], c0, c1,
+             ptr(gauss[s0:]) if s1 > s0 else None, ptr(soff), s1 - s0, ptr(mu), ptr(w), ptr(g), Q, n, ncells,
+             ptr(dur[s0:]) if s1 > s0 else None, ptr(state[f0:]) if want_state and f1 > f0 else None, ptr(score[b0:]), ptr(info[b0:]),
+             _ALIGN_PHASE_ALL if phases is None else int(phases), ptr(ws), nws, stream(), tag=(n, ncells, D))
+    if own:
+        align_status('ops.' + fn, info)
+    return AlignResult(dur, state, score, info, fo, so)
+
+
+def align_occurrences(gauss, Q):
+    """The occurrence table of ptts_align_accumulate from the host's copy of gauss [sum N]: (occ int32 [sum N], the indices of the
+    chain states sorted by Gaussian, equal ones in index order; occ_off int64 [Q+1], Gaussian q's run of occ), numpy arrays.  An
+    index outside [0, Q) is a ValueError."""
+    gauss = np.asarray(gauss)
+    if gauss.ndim != 1 or gauss.dtype.kind not in 'iu' or (gauss.size and (gauss.min() < 0 or gauss.max() >= Q)):
+        raise ValueError('ops.align_occurrences: gauss has to be a vector of integers in [0, {})'.format(Q))
+    occ = np.argsort(gauss, kind='stable').astype(np.int32)
+    occ_off = np.concatenate([[0], np.cumsum(np.bincount(gauss, minlength=Q))]).astype(np.int64)
+    return occ, occ_off
+
+
+def align_accumulate(X, frame_lengths, gauss, state_lengths, dur, occ, occ_off, Q, cols=None, sums=None):
+    """The sufficient statistics of the Gaussians under a segmentation (ptts_align_accumulate): dur [sum N] int32 device, the
+    frames of every chain state (ops.align_viterbi's, or ops.align_uniform's); occ, occ_off: the table of ops.align_occurrences on
+    the device -> (count [Q] int64, s1 [Q,D], s2 [Q,D] fp64).  With sums = (count, s1, s2) the call ADDS to them (a corpus in
+    several calls); a Gaussian without frames is left untouched.  No floating-point atomics: the same call writes the same bytes."""
+    fn = 'align_accumulate'
+    fo, so = _align_inputs(fn, X, frame_lengths, gauss, state_lengths)
+    if len(fo) != len(so):
+        raise ValueError('ops.{}: {} frame and {} state counts'.format(fn, len(fo), len(so)))
+    if int(Q) != Q or Q < 1:
+        raise ValueError('ops.{}: Q={!r} Gaussians'.format(fn, Q))
+    Dx = X.shape[1]
+    c0, c1 = (0, Dx) if cols is None else cols
+    if int(c0) != c0 or int(c1) != c1 or not 0 <= c0 < c1 <= Dx:
+        raise ValueError('ops.{}: cols={!r} is not a range 0 <= c0 < c1 <= Dx={}'.format(fn, cols, Dx))
+    if fo.total >= 1 << 31 or so.total >= 1 << 31:
+        raise ValueError('ops.{}: {} frames and {} states; fewer than 2^31 each'.format(fn, fo.total, so.total))
+    D, dev = int(c1) - int(c0), X.device
+    _dev_tensor(dur, torch.int32, fn + '.dur', (so.total,))
+    _dev_tensor(occ, torch.int32, fn + '.occ', (so.total,))
+    _dev_tensor(occ_off, torch.int64, fn + '.occ_off', (Q + 1,))
+    if sums is None:
+        sums = (torch.zeros(Q, dtype=torch.int64, device=dev), torch.zeros((Q, D), dtype=torch.float64, device=dev),
+                torch.zeros((Q, D), dtype=torch.float64, device=dev))
+    count, s1, s2 = sums
+    _dev_tensor(count, torch.int64, fn + '.count', (Q,))
+    _dev_tensor(s1, torch.float64, fn + '.s1', (Q, D))
+    _dev_tensor(s2, torch.float64, fn + '.s2', (Q, D))
+    nws = _hip.lib().ptts_align_accumulate_workspace_bytes(so.total)
+    ws = _workspace(nws, dev)
+    call('ptts_align_accumulate', ptr(X) if fo.total else None, ptr(fo.dev), fo.total, Dx, int(c0), int(c1), ptr(gauss) if so.total else None,
+         ptr(so.dev), so.total, ptr(dur) if so.total else None, ptr(occ) if so.total else None, ptr(occ_off), int(Q), len(fo), ptr(count),
+         ptr(s1), ptr(s2), ptr(ws), nws, stream(), tag=(len(fo), fo.total, int(Q), D))
+    return count, s1, s2
+
+
+def align_update(count, s1, s2, floor, mu, w, g, min_count=2):
+    """The Gaussians from their statistics, in place (ptts_align_update): for count[q] >= min_count mu = s1 / count,
+    var = max(s2 / count - mu mu, floor[d]), w = 1 / var, g = sum_d log var; a Gaussian below min_count keeps its mu, w, g.
+    floor [D] fp64 device.  Returns (kept [Q] int32: 1 for a Gaussian that was kept, floored [Q] int32: its variances that took
+    the floor), on the device."""
+    fn = 'align_update'
+    Q, D = _align_model_check(fn, mu, w, g)
+    if isinstance(min_count, bool) or int(min_count) != min_count or min_count < 1:
+        raise ValueError('ops.{}: min_count={!r} is not an integer >= 1'.format(fn, min_count))
+    _dev_tensor(count, torch.int64, fn + '.count', (Q,))
+    _dev_tensor(s1, torch.float64, fn + '.s1', (Q, D))
+    _dev_tensor(s2, torch.float64, fn + '.s2', (Q, D))
+    _dev_tensor(floor, torch.float64, fn + '.floor', (D,))
+    kept = torch.empty(Q, dtype=torch.int32, device=mu.device)
+    floored = torch.empty(Q, dtype=torch.int32, device=mu.device)
+    call('ptts_align_update', ptr(count), ptr(s1), ptr(s2), ptr(floor), Q, D, int(min_count), ptr(mu), ptr(w), ptr(g), ptr(kept),
+         ptr(floored), stream(), tag=(Q, D))
+    return kept, floored
+
+
+def align_uniform(fo, so):
+    """The flat start: dur[n] = floor((n+1) T / N) - floor(n T / N) for every chain state, and the chain state of every frame, in
+    integer arithmetic on the device -> (dur int32 [sum N], state int32 [sum T]).  Every utterance needs T >= N >= 1."""
+    dev = fo.dev.device
+    N = torch.from_numpy(np.asarray(so.lengths, dtype=np.int64)).to(dev)
+    T = torch.from_numpy(np.asarray(fo.lengths, dtype=np.int64)).to(dev)
+    n = torch.arange(so.total, dtype=torch.int64, device=dev) - torch.repeat_interleave(so.dev[:-1], N, output_size=so.total)
+    Ts, Ns = (torch.repeat_interleave(v, N, output_size=so.total) for v in (T, N))
+    dur = torch.div((n + 1) * Ts, Ns, rounding_mode='floor') - torch.div(n * Ts, Ns, rounding_mode='floor')
+    state = torch.repeat_interleave(n, dur, output_size=fo.total)
+    return dur.to(torch.int32), state.to(torch.int32)
+
+
+class AlignModel(object):
+    """Q diagonal Gaussians on the device as the kernels read them: mu [Q,D], w = 1 / var [Q,D], g = sum_d log var [Q], fp64."""
+
+    def __init__(self, mu, w, g):
+        self.mu, self.w, self.g = mu, w, g
+
+    @classmethod
+    def from_host(cls, mu, var, device):
+        """mu, var [Q,D] numpy -> the model on `device` (w and g in fp64 on the host: 1 / var, the logs added in index order)."""
+        mu, var = np.ascontiguousarray(mu, dtype=np.float64), np.ascontiguousarray(var, dtype=np.float64)
+        if mu.ndim != 2 or mu.shape != var.shape or min(mu.shape) < 1 or not (var > 0).all() or not np.isfinite(mu).all():
+            raise ValueError('AlignModel.from_host: mu and var have to be [Q,D], var positive')
+        g = np.zeros(mu.shape[0])
+        for d in range(mu.shape[1]):
+            g = g + np.log(var[:, d])
+        return cls(*(torch.from_numpy(a).to(device) for a in (mu, 1.0 / var, g)))
+
+    def host(self):
+        """(mu, var) [Q,D] numpy fp64."""
+        return self.mu.cpu().numpy(), 1.0 / self.w.cpu().numpy()
+
+
+def forced_align_train(X, frame_lengths, chains, Q, c0=0, c1=None, n_iter=20, var_floor=0.01, min_count=2, model=None,
+                       workspace_bytes=ALIGN_WORKSPACE_CAP, names=None, trace=None):
+    """Flat-start Viterbi training (segmental k-means) of Q diagonal Gaussians on a corpus, and its alignment.
+    X [sum T, Dx] fp32 device: the corpus packed row-wise once; frame_lengths: the utterances' frame counts; chains: per utterance
+    the Gaussian index of every chain state (a list of integer vectors); the alignment columns are X[:, c0:c1].
+    Iteration 0 is the uniform segmentation (ops.align_uniform), accumulate, update; every later one aligns every utterance
+    (in chunks of utterances whose workspace stays below workspace_bytes), accumulates from zeroed sums and updates.  It stops when
+    no frame of the corpus changed its chain state, or after n_iter alignments.  floor[d] = var_floor x the variance of column d over
+    all frames (two passes in fp64, torch on the device); a Gaussian with fewer than min_count frames keeps its values (mean 0,
+    variance 1 from the flat start).  With `model` (an AlignModel) the flat start is skipped, and with n_iter = 0 besides the call
+    only aligns: how new utterances are aligned with stored models.
+    -> (AlignModel, dur int32 [sum N] device: the last alignment, history): history holds per iteration
+    (total score: the utterances' scores added in index order, NaN for the flat start; frames that changed their chain state;
+    Gaussians kept; variances floored).  Everything but the history stays on the device.  An utterance that cannot be aligned is a
+    ValueError naming it (names[b], else its index) and its PTTS_ALIGN_* flag.  trace: a list that receives, per iteration, numpy
+    copies of (dur, the utterances' scores, and mu, w, g as the alignment of that iteration read them; None for the flat start)."""
+    fn = 'forced_align_train'
+    if not torch.is_tensor(X) or X.dim() != 2:
+        raise ValueError('ops.{}: X has to be a packed [rows, Dx] device tensor'.format(fn))
+    Dx = X.shape[1]
+    c1 = Dx if c1 is None else c1
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or n_iter < 0:
+        raise ValueError('ops.{}: n_iter={!r} is not an integer >= 0'.format(fn, n_iter))
+    if not (math.isfinite(float(var_floor)) and var_floor > 0):
+        raise ValueError('ops.{}: var_floor={!r} is not positive'.format(fn, var_floor))
+    try:
+        chains = [np.asarray(c).astype(np.int64).reshape(-1) for c in chains]
+    except (TypeError, ValueError):
+        raise ValueError('ops.{}: chains has to hold one vector of Gaussian indices per utterance'.format(fn))
+    fl = list(frame_lengths.lengths) if isinstance(frame_lengths, PackedOffsets) else [int(n) for n in frame_lengths]
+    if len(chains) != len(fl):
+        raise ValueError('ops.{}: {} chains for {} utterances'.format(fn, len(chains), len(fl)))
+    sl = [c.size for c in chains]
+    c0, c1, cells = align_check(Dx, fl, sl, Q, (c0, c1))
+    D, dev = c1 - c0, X.device
+    gauss_host = np.concatenate(chains) if chains else np.zeros(0, np.int64)
+    occ, occ_off = align_occurrences(gauss_host, Q)
+    cap = align_max_states()
+    for b, (t, n) in enumerate(zip(fl, sl)):                # what the kernels would flag, before the device is touched
+        if not 1 <= n <= min(t, cap):
+            flag = 'EMPTY' if n == 0 or t == 0 else 'TOO_LONG' if n > cap else 'TOO_SHORT'
+            raise ValueError('ops.{}: utterance {}: PTTS_ALIGN_{}: {} frames for {} states (1 <= states <= frames, at most {} states)'.format(
+                fn, b if names is None else names[b], flag, t, n, cap))
+    fo, so = packed_offsets(fl, dev, fn, 'frame_lengths'), packed_offsets(sl, dev, fn, 'chains')
+    gauss = torch.from_numpy(gauss_host.astype(np.int32)).to(dev)
+    _align_inputs(fn, X, fo, gauss, so)
+    occ, occ_off = torch.from_numpy(occ).to(dev), torch.from_numpy(occ_off).to(dev)
+    history, prev, dur = [], None, None
+    kept = floored = 0
+
+    def reestimate(dur):
+        sums = align_accumulate(X, fo, gauss, so, dur, occ, occ_off, Q, (c0, c1))
+        k, f = align_update(*sums, floor, model.mu, model.w, model.g, min_count)
+        return int(k.sum().item()), int(f.sum().item())
+
+    if model is None:
+        Xc = X[:, c0:c1].to(torch.float64)
+        floor = (float(var_floor) * ((Xc - Xc.mean(dim=0)) ** 2).mean(dim=0)).contiguous()
+        del Xc
+        model = AlignModel(torch.zeros((Q, D), dtype=torch.float64, device=dev), torch.ones((Q, D), dtype=torch.float64, device=dev),
+                           torch.zeros(Q, dtype=torch.float64, device=dev))
+        dur, prev = align_uniform(fo, so)
+        kept, floored = reestimate(dur)
+        history.append((float('nan'), fo.total, kept, floored))
+        if trace is not None:
+            trace.append((dur.cpu().numpy(), None, None, None, None))
+    else:
+        if tuple(_align_model_check(fn, model.mu, model.w, model.g)) != (Q, D):
+            raise ValueError('ops.{}: the model is not {} Gaussians of {} columns'.format(fn, Q, D))
+        if n_iter > 0:
+            Xc = X[:, c0:c1].to(torch.float64)
+            floor = (float(var_floor) * ((Xc - Xc.mean(dim=0)) ** 2).mean(dim=0)).contiguous()
+            del Xc
+    done = 0
+    while done < n_iter or (n_iter == 0 and done == 0 and dur is None):
+        used = None if trace is None else tuple(t.cpu().numpy() for t in (model.mu, model.w, model.g))
+        res = align_viterbi(X, fo, gauss, so, model.mu, model.w, model.g, (c0, c1), want_state=True,
+                            info=torch.zeros(len(fo), dtype=torch.int32, device=dev), workspace_bytes=workspace_bytes)
+        done += 1
+        align_status('ops.' + fn, res.info, names)
+        total = 0.0
+        for v in res.score.cpu().numpy().tolist():
+            total = total + v
+        changed = fo.total if prev is None else int((res.state != prev).sum().item())
+        dur, prev = res.dur, res.state
+        if changed and n_iter > 0:
+            kept, floored = reestimate(dur)
+        history.append((total, changed, kept, floored))
+        if trace is not None:
+            trace.append((dur.cpu().numpy(), res.score.cpu().numpy()) + used)
+        if changed == 0:
+            break
+    return model, dur, history
 
 
 # ----------------------------------------------------------------------------------------------
